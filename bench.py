@@ -171,6 +171,9 @@ def parse():
                    "--same-device lets several ranks share ONE GPU to exercise the N>1 code path on a 1-GPU box")
     p.add_argument("--same-device", action="store_true", help="debug: every rank uses cuda:0")
     p.add_argument("--dump-preds", default=None, help="debug: rank 0 writes the last step's predictions to this .npy")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR", help="rank 0 writes what the last timed step returned to its caller "
+                   "(predictions, matches, sims) as DIR/<name>.npy in float32 / float64, at most 64 MB in all: two builds run with "
+                   "the same arguments see the same inputs and can be compared output for output")
     p.add_argument("--pmc-calibrate", action="store_true", help="map a 1 GiB tensor through torch.sign (a known 1 GiB read + 1 GiB write) "
                    "right before and right after the timed steps: tools/pmc_summary.py calibrates FETCH_SIZE / WRITE_SIZE on them and "
                    "takes the dispatches BETWEEN them as the timed path's (rocprofv3 --pmc passes over this very process)")
@@ -253,6 +256,33 @@ class ImageFactory:
         a = self.query_own
         own = a * self.own_noise(tau) + (1.0 - a * a) ** 0.5 * torch.randn(self.N, self.D, device=self.dev, generator=self._gen(30_000_001 + qid))
         return self.tokens(z, base, own), m
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir: str, out) -> None:
+    """--dump-outputs: what index.retrieve handed back in the last timed step -- the top-5 image ids per query image, the kept
+    segment matches (k_vote reference-segment ids per query segment) and their similarities -- as float64 (ids, exact) and
+    float32 .npy files.  Over DUMP_LIMIT_BYTES the two per-segment arrays keep the same seeded sample of rows, whose row numbers
+    are written beside them (sample_rows.npy)."""
+    pred, _scores, matches, sims = out
+    host = lambda x: x.cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)   # noqa: E731
+    arrays = {"predictions": host(pred).astype(np.float64), "matches": host(matches).astype(np.float64),
+              "sims": host(sims).astype(np.float32)}
+    n_rows = arrays["matches"].shape[0]
+    if sum(v.nbytes for v in arrays.values()) > DUMP_LIMIT_BYTES - 4096:      # (4 KB: the .npy headers)
+        row_bytes = arrays["matches"][0].nbytes + arrays["sims"][0].nbytes + 8
+        keep = (DUMP_LIMIT_BYTES - 4096 - arrays["predictions"].nbytes) // row_bytes
+        rows = np.sort(np.random.Generator(np.random.PCG64(0)).choice(n_rows, size=keep, replace=False))
+        arrays["matches"], arrays["sims"] = arrays["matches"][rows], arrays["sims"][rows]
+        arrays["sample_rows"] = rows.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    stale = os.path.join(out_dir, "sample_rows.npy")
+    if "sample_rows" not in arrays and os.path.exists(stale):
+        os.remove(stale)
+    for name, v in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(v))
 
 
 def run(a, top=True):
@@ -541,6 +571,8 @@ def run(a, top=True):
     pred = out[0].cpu().numpy()
     if a.dump_preds and rank == 0:
         np.save(a.dump_preds, pred)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, out)
     recalls = recall_at(pred, gt, 5)
     recalls_group = recall_at(pred, gt_group, 5)
 
@@ -841,7 +873,7 @@ def sub_record(a, **over):
     import copy
     b = copy.copy(a)
     b.no_cpu_baseline, b.no_sub_records, b.no_ubench, b.pipeline = True, True, True, False
-    b.dump_preds = b.sweep_own = None
+    b.dump_preds = b.dump_outputs = b.sweep_own = None
     b.debug_timing = b.pmc_calibrate = False
     b.steps, b.warmup = 3, 1
     for k, v in over.items():

@@ -63,14 +63,21 @@ def test_bench_two_ranks_one_gpu_equal_single_rank(tmp_path):
     (d2, id) all-gather, merge, vote) must reproduce the single-rank predictions exactly."""
     p1, p2 = str(tmp_path / "p1.npy"), str(tmp_path / "p2.npy")
     common = ["--steps", "1", "--warmup", "1", "--db-images", "4000", "--query-images", "40", "--no-cpu-baseline"]
-    j1 = _run([sys.executable, "bench.py", *common, "--dump-preds", p1], 900)
+    o1, o2 = tmp_path / "o1", tmp_path / "o2"
+    j1 = _run([sys.executable, "bench.py", *common, "--dump-preds", p1, "--dump-outputs", str(o1)], 900)
     port = 29500 + (os.getpid() % 2000)
     j2 = _run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                "--master-port", str(port), "bench.py", "--gpus", "2", "--same-device", "--dist-backend", "gloo", *common,
-               "--dump-preds", p2], 900)
+               "--dump-preds", p2, "--dump-outputs", str(o2)], 900)
     assert j2["n_gpus"] == 2 and j1["n_gpus"] == 1
     assert np.array_equal(np.load(p1), np.load(p2))
     assert j1["recall_at_1"] == j2["recall_at_1"]
+    # --dump-outputs: the same last-step arrays as float32 / float64 files (40 query images x 50 segments, k_vote 50)
+    for o, p in ((o1, p1), (o2, p2)):
+        pred, m, s = (np.load(o / f"{n}.npy") for n in ("predictions", "matches", "sims"))
+        assert pred.dtype == np.float64 and np.array_equal(pred, np.load(p))
+        assert m.dtype == np.float64 and s.dtype == np.float32 and m.shape == s.shape == (40 * 50, 50)
+        assert not os.path.exists(o / "sample_rows.npy")
 
 
 def test_bench_four_ranks_one_gpu_ragged_slices_equal_single_rank(tmp_path):

@@ -102,3 +102,43 @@ def test_pmc_summary_window_cuts_the_timed_steps_out_between_the_markers(tmp_pat
     _write(tmp_path / "t.csv", trace)
     r = subprocess.run(cmd, capture_output=True, text=True)
     assert r.returncode == 3 and json.loads(r.stdout)["launch_multiset_equals_timeline"] is False
+
+
+def test_bench_dump_outputs_writes_the_callers_arrays_within_the_size_limit(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: predictions, matches and sims of the last timed step as float64 / float32 .npy files; ids stay
+    exact; over the limit both per-segment arrays keep the same seeded rows, and a later unsampled dump drops the row list."""
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import torch
+
+    import bench
+
+    rng = np.random.Generator(np.random.PCG64(7))
+    pred = torch.from_numpy(rng.integers(0, 20000, (40, 5)).astype(np.int32))
+    matches = torch.from_numpy(rng.integers(0, 1 << 20, (2000, 50)))
+    sims = torch.from_numpy(rng.random((2000, 50), dtype=np.float32))
+    out = (pred, None, matches, sims)
+
+    bench.dump_outputs(str(tmp_path / "a"), out)
+    got = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in ("predictions", "matches", "sims")}
+    assert sorted(os.listdir(tmp_path / "a")) == ["matches.npy", "predictions.npy", "sims.npy"]
+    assert got["predictions"].dtype == np.float64 and np.array_equal(got["predictions"], pred.numpy())
+    assert got["matches"].dtype == np.float64 and np.array_equal(got["matches"], matches.numpy())
+    assert got["sims"].dtype == np.float32 and np.array_equal(got["sims"], sims.numpy())
+
+    limit = 300_000
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", limit)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), out)
+    assert sum(os.path.getsize(tmp_path / "b" / f) for f in os.listdir(tmp_path / "b")) <= limit
+    rows = np.load(tmp_path / "b" / "sample_rows.npy")
+    assert 0 < len(rows) < 2000 and np.array_equal(rows, np.unique(rows))
+    m, s = np.load(tmp_path / "b" / "matches.npy"), np.load(tmp_path / "b" / "sims.npy")
+    assert np.array_equal(m, matches.numpy()[rows.astype(np.int64)]) and np.array_equal(s, sims.numpy()[rows.astype(np.int64)])
+    assert np.array_equal(np.load(tmp_path / "b" / "predictions.npy"), pred.numpy())
+    for f in os.listdir(tmp_path / "b"):                                                   # the sample is fixed
+        assert np.array_equal(np.load(tmp_path / "b" / f), np.load(tmp_path / "c" / f))
+
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 64 << 20)
+    bench.dump_outputs(str(tmp_path / "b"), out)
+    assert not os.path.exists(tmp_path / "b" / "sample_rows.npy")

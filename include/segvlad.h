@@ -332,6 +332,33 @@ int segvlad_comm_info(segvlad_ctx* ctx, int* rank_out, int* world_out, char* ori
 int segvlad_allgather_rows(segvlad_ctx* ctx, const float* local_rows, int n_local, int d, float* all_rows);
 int segvlad_search_sharded(segvlad_ctx* ctx, const float* Q, int nq, int k, int64_t id_base, float* d2_out, int64_t* idx_out);
 
+/* ---- query-sharded retrieval over a REPLICATED index: every rank adds the whole reference matrix to its context and
+ *      searches and votes only ITS OWN query images (contiguous blocks: an image's segments never straddle ranks).
+ *      The only step that crosses ranks before the predictions is the vote's normalisation: func_vpr.py:211-214 divides by
+ *      the GLOBAL max - min over all kept similarities of the whole query set, and since a reference image's score is
+ *      (sum s - n min) / (max - min) with n differing between images, per-rank extrema would change the ORDER of the
+ *      predictions, not only their scale.
+ *
+ *      segvlad_vote_global      segvlad_vote's contract over this rank's query images, with the extrema taken over
+ *                               the similarities of ALL ranks (no smin / smax arguments).  Collective: each rank
+ *                               reduces its own min / max on the device (a rank without query segments contributes
+ *                               (+inf, -inf)), ONE ncclAllGather exchanges a 16-byte record per rank {min bits, max bits,
+ *                               local status, query segments}, and a one-wave kernel reduces the records in place on
+ *                               the context stream; the vote reads the result from device memory.  min / max are exact,
+ *                               so the extrema -- and the votes -- are bit for bit what one process computes over all
+ *                               similarities, whatever the rank order.  Failure semantics of segvlad_search_sharded: a
+ *                               rank whose local step fails (arguments included) still joins with its status in its
+ *                               record, then every rank returns an error (the failing rank its own, the others
+ *                               SEGVLAD_ERR_COMM naming it) and the communicator stays usable; a rank that cannot join
+ *                               aborts the communicator.  Mode COUNT needs no extrema but stays collective.  No
+ *                               communicator bound: exactly segvlad_vote with NaN extrema.  Synchronises the stream.
+ *      Gathering the predictions in image order: segvlad_allgather_rows, a byte-exact copy.  Each rank packs its images
+ *      as rows of 3 * n_top 32-bit words {pred int32 [n_top], score fp64 bits [n_top]} viewed as fp32, padded to the
+ *      largest rank's image count (n_local must be equal on every rank); fp64 scores arrive bit for bit.           */
+int segvlad_vote_global(segvlad_ctx* ctx, const int64_t* idx, const float* sims, const int32_t* img_of_seg,
+                        int64_t n_ref_seg, const int32_t* qseg_offsets, int n_img, int k, int n_top, int mode,
+                        int32_t* pred_out, double* score_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -69,6 +69,8 @@ SIGNATURES = {
     "segvlad_comm_info": (C.c_int, [c_ctx_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_char_p, C.c_int]),
     "segvlad_allgather_rows": (C.c_int, [c_ctx_p, _f32p, C.c_int, C.c_int, _f32p]),
     "segvlad_search_sharded": (C.c_int, [c_ctx_p, _f32p, C.c_int, C.c_int, C.c_int64, _f32p, C.c_void_p]),
+    "segvlad_vote_global": (C.c_int, [c_ctx_p, C.c_void_p, _f32p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                       C.c_int, C.c_void_p, C.c_void_p]),
 }
 
 _lib = None

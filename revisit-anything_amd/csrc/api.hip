@@ -2082,10 +2082,15 @@ int segvlad_minmax(segvlad_ctx* ctx, const float* sims, int64_t count, float* mi
   return sv_finish(ctx);
 }
 
-int segvlad_vote(segvlad_ctx* ctx, const int64_t* idx, const float* sims, const int32_t* img_of_seg,
-                 int64_t n_ref_seg, const int32_t* qseg_offsets, int n_img, int k, float smin, float smax, int n_top, int mode,
-                 int32_t* pred_out, double* score_out) {
-  CHECK_CTX();
+}  // extern "C"
+
+// The argument checks and the staging of segvlad_vote, shared with segvlad_vote_global (comm.hip): on return the operands
+// are on the device and the query-image offsets are on their way to ctx->s_voteoff; v->mm is the two-float extrema slot
+// behind them.  n_img == 0 returns SEGVLAD_OK with nothing staged.
+int sv_vote_prepare(segvlad_ctx* ctx, const int64_t* idx, const float* sims, const int32_t* img_of_seg, int64_t n_ref_seg,
+                    const int32_t* qseg_offsets, int n_img, int k, int n_top, int mode, int32_t* pred_out, double* score_out,
+                    SvVote* v) {
+  *v = SvVote{};
   if (n_img < 0 || k < 1 || n_top < 1) return ctx->fail(SEGVLAD_ERR_ARG, "vote: bad shape");
   if (mode != SEGVLAD_VOTE_WT_BORDA_IM && mode != SEGVLAD_VOTE_COUNT) return ctx->fail(SEGVLAD_ERR_ARG, "vote: unknown mode %d", mode);
   if (n_img == 0) return SEGVLAD_OK;
@@ -2111,20 +2116,39 @@ int segvlad_vote(segvlad_ctx* ctx, const int64_t* idx, const float* sims, const 
   if (score_out) SV_TRY(sv_out(ctx, score_out, (size_t)n_img * n_top * 8, &os));
   SV_HIP(ctx->s_voteoff.reserve((size_t)(n_img + 1) * 4 + 32));
   SV_HIP(hipMemcpyAsync(ctx->s_voteoff.p, qseg_offsets, (size_t)(n_img + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
-  float* mm = reinterpret_cast<float*>(ctx->s_voteoff.as<char>() + (((size_t)(n_img + 1) * 4 + 7) & ~7ull));
+  v->di = di;
+  v->ds = ds;
+  v->dimg = dimg;
+  v->n_ref = n_ref;
+  v->op = op;
+  v->os = os;
+  v->mm = reinterpret_cast<float*>(ctx->s_voteoff.as<char>() + (((size_t)(n_img + 1) * 4 + 7) & ~7ull));
+  v->nq = nq;
+  return SEGVLAD_OK;
+}
+
+extern "C" {
+
+int segvlad_vote(segvlad_ctx* ctx, const int64_t* idx, const float* sims, const int32_t* img_of_seg,
+                 int64_t n_ref_seg, const int32_t* qseg_offsets, int n_img, int k, float smin, float smax, int n_top, int mode,
+                 int32_t* pred_out, double* score_out) {
+  CHECK_CTX();
+  SvVote v;
+  SV_TRY(sv_vote_prepare(ctx, idx, sims, img_of_seg, n_ref_seg, qseg_offsets, n_img, k, n_top, mode, pred_out, score_out, &v));
+  if (n_img == 0) return SEGVLAD_OK;
   StageScope sc(ctx, "vote");
   if (mode == SEGVLAD_VOTE_WT_BORDA_IM) {
     if (std::isnan(smin) || std::isnan(smax)) {
-      SV_TRY(sv_launch_minmax(ctx, (const float*)ds, (int64_t)nq * k, mm));
+      SV_TRY(sv_launch_minmax(ctx, (const float*)v.ds, (int64_t)v.nq * k, v.mm));
       sc.count(3);
     } else {
       const float h[2] = {smin, smax};
-      SV_HIP(hipMemcpyAsync(mm, h, sizeof(h), hipMemcpyHostToDevice, ctx->stream));
+      SV_HIP(hipMemcpyAsync(v.mm, h, sizeof(h), hipMemcpyHostToDevice, ctx->stream));
       SV_HIP(hipStreamSynchronize(ctx->stream));
     }
   }
-  SV_TRY(sv_launch_vote(ctx, (const int64_t*)di, (const float*)ds, (const int32_t*)dimg, n_ref, ctx->s_voteoff.as<int32_t>(),
-                        qseg_offsets, n_img, k, mm, n_top, mode, (int32_t*)op, (double*)os));
+  SV_TRY(sv_launch_vote(ctx, (const int64_t*)v.di, (const float*)v.ds, (const int32_t*)v.dimg, v.n_ref, ctx->s_voteoff.as<int32_t>(),
+                        qseg_offsets, n_img, k, v.mm, n_top, mode, (int32_t*)v.op, (double*)v.os));
   sc.count();
   return sv_finish(ctx);
 }

@@ -29,6 +29,7 @@ const char* ncclGetErrorString(ncclResult_t result);
 }
 #endif
 
+#include <cmath>
 #include <mutex>
 
 #include "ctx.h"
@@ -138,6 +139,47 @@ __global__ __launch_bounds__(256) void unpack_topk_kernel(const uint32_t* __rest
   const int64_t src = 3 * (j + r);   // r trailers lie in front of rank r's records
   d2c[o] = __uint_as_float(rec[src]);
   idc[o] = (int64_t)((uint64_t)rec[src + 1] | ((uint64_t)rec[src + 2] << 32));
+}
+
+// ---- the vote's exchange (segvlad_vote_global): one 16-byte record per rank {min bits, max bits, status, query segments} ----
+// min / max on the order-preserving key of select_kernels.hip's reduction: exact and order-independent, so the reduction of
+// the ranks' records gives the bits one process gets from all the similarities
+__device__ __forceinline__ uint32_t vote_f2key(float f) {
+  const uint32_t u = __float_as_uint(f);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float vote_key2f(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
+
+// this rank's record: the local extrema from the vote's extrema slot, or (+inf, -inf) when it has none to contribute
+__global__ void vote_record_kernel(const float* __restrict__ mm, int have_mm, uint32_t status, uint32_t nseg, uint32_t* __restrict__ rec) {
+  rec[0] = have_mm ? __float_as_uint(mm[0]) : 0x7f800000u;
+  rec[1] = have_mm ? __float_as_uint(mm[1]) : 0xff800000u;
+  rec[2] = status;
+  rec[3] = have_mm ? nseg : 0u;
+}
+
+// the gathered records [world][4] -> the global extrema (gmm[0] = min, gmm[1] = max) and the ranks' status words.  A record
+// without query segments is skipped rather than folded in as (+inf, -inf): with no segments anywhere the result is the
+// identity of the single-process reduction (NaN, NaN), as segvlad_minmax returns for an empty list.  One wave.
+__global__ __launch_bounds__(64) void vote_extrema_reduce_kernel(const uint32_t* __restrict__ rec, int world, float* __restrict__ gmm,
+                                                                 uint32_t* __restrict__ flags) {
+  uint32_t lo = ~0u, hi = 0u;
+  for (int r = threadIdx.x; r < world; r += 64) {
+    const uint32_t* x = rec + 4 * (int64_t)r;
+    flags[r] = x[2];
+    if (x[3] != 0u) {
+      lo = min(lo, vote_f2key(__uint_as_float(x[0])));
+      hi = max(hi, vote_f2key(__uint_as_float(x[1])));
+    }
+  }
+  for (int o = 32; o > 0; o >>= 1) {
+    lo = min(lo, (uint32_t)__shfl_xor((int)lo, o));
+    hi = max(hi, (uint32_t)__shfl_xor((int)hi, o));
+  }
+  if (threadIdx.x == 0) {
+    gmm[0] = vote_key2f(lo);
+    gmm[1] = vote_key2f(hi);
+  }
 }
 
 }  // namespace
@@ -332,6 +374,88 @@ int segvlad_search_sharded(segvlad_ctx* ctx, const float* Q, int nq, int k, int6
     if (ctx->sh_flags_host[(size_t)r])
       return ctx->fail(SEGVLAD_ERR_COMM, "search_sharded: rank %d failed its local search (every rank returns an error)", r);
   return rc_fin;
+}
+
+int segvlad_vote_global(segvlad_ctx* ctx, const int64_t* idx, const float* sims, const int32_t* img_of_seg, int64_t n_ref_seg,
+                        const int32_t* qseg_offsets, int n_img, int k, int n_top, int mode, int32_t* pred_out, double* score_out) {
+  if (!ctx) return SEGVLAD_ERR_ARG;
+  if (!ctx->comm)   // no communicator: the single-process vote, extrema from this call's own similarities
+    return segvlad_vote(ctx, idx, sims, img_of_seg, n_ref_seg, qseg_offsets, n_img, k, NAN, NAN, n_top, mode, pred_out, score_out);
+  sv_begin(ctx);
+  const int world = ctx->comm_world;
+  // this rank's record, the gathered records, the status words and the global extrema
+  hipError_t he = ctx->s_sh_rec.reserve(16);
+  if (he == hipSuccess) he = ctx->s_sh_all.reserve((size_t)world * 20 + 8);
+  if (he != hipSuccess) {
+    (void)ctx->fail(SEGVLAD_ERR_NOMEM, "vote exchange buffers: %s", hipGetErrorString(he));
+    return comm_abort_local(ctx, "vote_global", SEGVLAD_ERR_NOMEM);
+  }
+  uint32_t* rec_all = ctx->s_sh_all.as<uint32_t>();
+  uint32_t* flags = rec_all + 4 * (size_t)world;
+  float* gmm = reinterpret_cast<float*>(flags + world);
+  // The local step -- checks, staging, the local min / max into the vote's extrema slot -- may fail on THIS rank only (its
+  // arguments, its memory).  The rank then still enters the all-gather, with its status in its record, and every rank
+  // returns an error (as segvlad_search_sharded does).
+  SvVote v;
+  int local_rc = sv_vote_prepare(ctx, idx, sims, img_of_seg, n_ref_seg, qseg_offsets, n_img, k, n_top, mode, pred_out, score_out, &v);
+  int have_mm = 0;
+  if (local_rc == SEGVLAD_OK && n_img > 0 && mode == SEGVLAD_VOTE_WT_BORDA_IM && v.nq > 0) {
+    StageScope sc(ctx, "vote");
+    local_rc = sv_launch_minmax(ctx, (const float*)v.ds, (int64_t)v.nq * k, v.mm);
+    have_mm = local_rc == SEGVLAD_OK;
+    sc.count(3);
+  }
+  char local_err[sizeof(ctx->err)] = {0};
+  if (local_rc != SEGVLAD_OK) snprintf(local_err, sizeof(local_err), "%s", ctx->err);
+  // From here to the all-gather the peers may already be inside it: a failure aborts the communicator (segvlad_search_sharded)
+#define SV_PRE(expr)                                                                                        \
+  do {                                                                                                      \
+    hipError_t _e = (expr);                                                                                 \
+    if (_e != hipSuccess) {                                                                                 \
+      (void)ctx->fail(SEGVLAD_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
+      return comm_abort_local(ctx, "vote_global", SEGVLAD_ERR_HIP);                                         \
+    }                                                                                                       \
+  } while (0)
+  ctx->sh_flags_host.assign((size_t)world, 0u);
+  int post_rc = SEGVLAD_OK;   // failures behind the collective: remembered, the stream is synchronised either way
+  {
+    StageScope sc(ctx, "vote_exchange");
+    hipLaunchKernelGGL(vote_record_kernel, dim3(1), dim3(1), 0, ctx->stream, (const float*)v.mm, have_mm,
+                       local_rc != SEGVLAD_OK ? 1u : 0u, (uint32_t)v.nq, ctx->s_sh_rec.as<uint32_t>());
+    SV_PRE(hipGetLastError());
+    {
+      const ncclResult_t r = g_rccl.AllGather(ctx->s_sh_rec.p, rec_all, 16, ncclUint8, reinterpret_cast<ncclComm_t>(ctx->comm), ctx->stream);
+      if (r != ncclSuccess) {
+        (void)ctx->fail(SEGVLAD_ERR_COMM, "ncclAllGather failed: %s", g_rccl.GetErrorString(r));
+        return comm_abort_local(ctx, "vote_global", SEGVLAD_ERR_COMM);
+      }
+    }
+#undef SV_PRE
+    // the global extrema stay on the device: the vote below reads them there, no host round trip in between
+    hipLaunchKernelGGL(vote_extrema_reduce_kernel, dim3(1), dim3(64), 0, ctx->stream, (const uint32_t*)rec_all, world, gmm, flags);
+    hipError_t he2 = hipGetLastError();
+    if (he2 == hipSuccess)
+      he2 = hipMemcpyAsync(ctx->sh_flags_host.data(), flags, (size_t)world * 4, hipMemcpyDeviceToHost, ctx->stream);
+    if (he2 != hipSuccess) post_rc = ctx->fail(SEGVLAD_ERR_HIP, "vote_global: behind the collective: %s", hipGetErrorString(he2));
+    sc.count(2);
+  }
+  if (post_rc == SEGVLAD_OK && local_rc == SEGVLAD_OK && n_img > 0) {
+    StageScope sc(ctx, "vote");
+    post_rc = sv_launch_vote(ctx, (const int64_t*)v.di, (const float*)v.ds, (const int32_t*)v.dimg, v.n_ref, ctx->s_voteoff.as<int32_t>(),
+                             qseg_offsets, n_img, k, gmm, n_top, mode, (int32_t*)v.op, (double*)v.os);
+    sc.count();
+  }
+  {
+    const hipError_t hs = hipStreamSynchronize(ctx->stream);   // the status words of all ranks (4 bytes each)
+    if (hs != hipSuccess && post_rc == SEGVLAD_OK)
+      post_rc = ctx->fail(SEGVLAD_ERR_HIP, "vote_global: hipStreamSynchronize: %s", hipGetErrorString(hs));
+  }
+  if (post_rc != SEGVLAD_OK) return post_rc;
+  if (local_rc != SEGVLAD_OK) return ctx->fail(local_rc, "vote_global: this rank's local step failed: %s", local_err);
+  for (int r = 0; r < world; ++r)
+    if (ctx->sh_flags_host[(size_t)r])
+      return ctx->fail(SEGVLAD_ERR_COMM, "vote_global: rank %d failed its local step (every rank returns an error)", r);
+  return sv_finish(ctx);
 }
 
 }  // extern "C"

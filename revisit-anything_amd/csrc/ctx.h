@@ -539,3 +539,18 @@ int sv_launch_minmax(segvlad_ctx* ctx, const float* sims, int64_t count, float* 
 int sv_launch_vote(segvlad_ctx* ctx, const int64_t* idx, const float* sims, const int32_t* img_of_seg,
                    int64_t n_ref_seg, const int32_t* qoff_dev, const int32_t* qoff_host, int n_img, int k,
                    const float* minmax_dev, int n_top, int mode, int32_t* pred, double* score);
+
+// api.hip: the checks and staging of segvlad_vote, shared with segvlad_vote_global (comm.hip)
+struct SvVote {
+  const void* di = nullptr;    // idx on the device
+  const void* ds = nullptr;    // sims on the device (null in COUNT mode without sims)
+  const void* dimg = nullptr;  // segment -> image map on the device
+  int64_t n_ref = 0;
+  void* op = nullptr;          // pred / score outputs (device, or staging flushed by sv_finish)
+  void* os = nullptr;
+  float* mm = nullptr;         // the two-float extrema slot the vote kernel reads
+  int nq = 0;                  // query segments (qseg_offsets[n_img])
+};
+int sv_vote_prepare(segvlad_ctx* ctx, const int64_t* idx, const float* sims, const int32_t* img_of_seg, int64_t n_ref_seg,
+                    const int32_t* qseg_offsets, int n_img, int k, int n_top, int mode, int32_t* pred_out, double* score_out,
+                    SvVote* v);

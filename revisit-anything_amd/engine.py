@@ -170,6 +170,25 @@ class SegVLADEngine:
         self._keep = [q]
         return d2, idx
 
+    def vote_global(self, idx, sims, qseg_offsets, n_top=5, mode=_lib.VOTE_WT_BORDA_IM, img_of_seg=None, want_scores=True):
+        """Collective (query-sharded retrieval): vote() over this rank's query images with the min / max of the similarities of
+        ALL ranks of the context's communicator (func_vpr.py:211-214).  Every rank calls it, a rank without images included
+        (idx / sims [0, k])."""
+        i = _as(idx, np.int64, torch.int64)
+        s = None if sims is None else _as(sims, np.float32, torch.float32)
+        qo = np.ascontiguousarray(qseg_offsets, dtype=np.int32)
+        n_img = len(qo) - 1
+        k = int(i.shape[1])
+        im = None if img_of_seg is None else _as(img_of_seg, np.int32, torch.int32)
+        n_ref = 0 if im is None else int(im.shape[0])
+        pred = self._empty((n_img, n_top), torch.int32)
+        sc = self._empty((n_img, n_top), torch.float64) if want_scores else None
+        self._stream()
+        self._check(self.lib.segvlad_vote_global(self._h, _ptr(i), _ptr(s), _ptr(im), n_ref, _ptr(qo), n_img, k, int(n_top), int(mode),
+                                                 _ptr(pred), _ptr(sc)), "vote_global")
+        self._keep = [i, s, im]
+        return pred, sc
+
     # ---- vocabulary -------------------------------------------------------------------------------
     def set_vocab(self, c_centers):
         c = _as(c_centers, np.float32, torch.float32)

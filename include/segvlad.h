@@ -198,6 +198,21 @@ int segvlad_db_size(segvlad_ctx* ctx, int64_t* n_rows, int* d);
  *      beyond the database size hold (+inf, -1) like faiss).  1 <= k <= 1024.                      */
 int segvlad_search(segvlad_ctx* ctx, const float* Q, int nq, int k, float* d2_out, int64_t* idx_out);
 
+/* ---- shortlist-restricted exact search (no reference counterpart: the reference searches the whole index,
+ *      place_rec_main.py:53-60; this is the re-ranking of a global shortlist / a location prior of deployed place recognition).
+ *      Q [nq][d] query segment rows (device or host), qseg_offsets [n_img+1] int32 HOST as in segvlad_vote: query image b owns
+ *      the rows qseg_offsets[b] .. qseg_offsets[b+1]-1 (0 rows allowed).  shortlist [n_img][M] int32: the reference image ids
+ *      (the img_of_seg values given to segvlad_db_add) that image b's segments may match; -1 is padding, a duplicate counts
+ *      once, an id no row carries contributes no rows.  1 <= M <= 4096, 1 <= k <= 1024.
+ *      d2_out [nq][k] / idx_out [nq][k]: per query row the top-k rows of the index whose image is in its image's shortlist,
+ *      ordered by (squared L2, lower id) as segvlad_search; (+inf, -1) beyond the number of allowed rows.  Every distance is
+ *      the exact fp32 chain of segvlad_search (sequential fma dot product in k order, the stored row norms, negatives set to
+ *      0): a pair's value is bit for bit segvlad_search's, and a shortlist of every image returns segvlad_search(Q, k).
+ *      SEGVLAD_ERR_STATE without an img_of_seg map; SEGVLAD_ERR_LIMIT when d % 32 != 0.  The image -> row map is built on
+ *      the device by the first call after segvlad_db_add / segvlad_db_reset.                                          */
+int segvlad_search_shortlist(segvlad_ctx* ctx, const float* Q, int nq, const int32_t* qseg_offsets, int n_img,
+                             const int32_t* shortlist, int M, int k, float* d2_out, int64_t* idx_out);
+
 /* ---- merge of per-shard top-k lists (no reference counterpart: the reference is single-process).
  *      d2_parts/idx_parts [nq][parts*k] (shard-major within a row, global ids); output top-k by
  *      (distance, lower id).                                                                       */
@@ -225,7 +240,7 @@ int segvlad_vote(segvlad_ctx* ctx, const int64_t* idx, const float* sims, const 
                  int32_t* pred_out, double* score_out);
 
 /* ---- instrumentation: with profiling on, every kernel group of a stage ("incidence", "adjacency",
- *      "assign", "prep", "aggregate", "pca", "describe" (segvlad_describe as a whole: its parts overlap), "knn_level0", "knn_gemm", "knn_select", "knn_fallback", "vote") is bracketed by a HIP event pair
+ *      "assign", "prep", "aggregate", "pca", "describe" (segvlad_describe as a whole: its parts overlap), "knn_level0", "knn_gemm", "knn_select", "knn_fallback", "knn_shortlist" (segvlad_search_shortlist), "vote") is bracketed by a HIP event pair
  *      on the context stream.  segvlad_stage_ms returns the SUM of the elapsed times (ms) and the number
  *      of kernel launches recorded for the stage since the last segvlad_profile_reset; it returns
  *      SEGVLAD_ERR_STATE if the stage has not run.  Replaces the (discarded) time.time() pair of

@@ -53,6 +53,8 @@ SIGNATURES = {
     "segvlad_db_add": (C.c_int, [c_ctx_p, _f32p, C.c_int, C.c_int, C.c_void_p]),
     "segvlad_db_size": (C.c_int, [c_ctx_p, C.POINTER(C.c_int64), C.POINTER(C.c_int)]),
     "segvlad_search": (C.c_int, [c_ctx_p, _f32p, C.c_int, C.c_int, _f32p, C.c_void_p]),
+    "segvlad_search_shortlist": (C.c_int, [c_ctx_p, _f32p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, _f32p,
+                                            C.c_void_p]),
     "segvlad_merge_topk": (C.c_int, [c_ctx_p, _f32p, C.c_void_p, C.c_int, C.c_int, C.c_int, _f32p, C.c_void_p]),
     "segvlad_sims_from_d2": (C.c_int, [c_ctx_p, _f32p, C.c_void_p, C.c_int, C.c_int, C.c_int, _f32p, C.c_void_p]),
     "segvlad_minmax": (C.c_int, [c_ctx_p, _f32p, C.c_int64, _f32p]),

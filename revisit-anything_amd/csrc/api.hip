@@ -1170,6 +1170,8 @@ int segvlad_db_reset(segvlad_ctx* ctx) {
   ctx->db_n = 0;
   ctx->db_d = 0;
   ctx->db_has_img = false;
+  ctx->db_img_max = -1;
+  ctx->sl_map_valid = false;
   ctx->db_split_rows = 0;
   ctx->db_f16_rows = 0;
   ctx->db_f16_scale = 0.f;
@@ -1219,7 +1221,12 @@ int segvlad_db_add(segvlad_ctx* ctx, const float* R, int n, int d, const int32_t
     SV_HIP(grow(ctx->db_img, (size_t)ctx->db_n * 4, (size_t)n_new * 4));
     SV_HIP(hipMemcpyAsync(ctx->db_img.as<int32_t>() + ctx->db_n, img_of_seg, (size_t)n * 4, hipMemcpyDefault, ctx->stream));
     ctx->db_has_img = true;
+    // the largest image id sizes the image -> row map of segvlad_search_shortlist (rebuilt by its next call)
+    int mx = -1;
+    SV_TRY(sv_img_max(ctx, ctx->db_img.as<int32_t>() + ctx->db_n, n, &mx));
+    ctx->db_img_max = std::max(ctx->db_img_max, mx);
   }
+  ctx->sl_map_valid = false;
   SV_TRY(sv_launch_row_sumsq(ctx, dst, n, d, ctx->db_norms.as<float>() + ctx->db_n));
   ctx->db_n = n_new;
   ctx->db_d = d;
@@ -2032,6 +2039,42 @@ int segvlad_search(segvlad_ctx* ctx, const float* Q, int nq, int k, float* d2_ou
                        ctx->s_rd_rows.as<int32_t>(), k, (float*)dd2, (int64_t*)didx);
     SV_HIP(hipGetLastError());
   }
+  return sv_finish(ctx);
+}
+
+int segvlad_search_shortlist(segvlad_ctx* ctx, const float* Q, int nq, const int32_t* qseg_offsets, int n_img,
+                             const int32_t* shortlist, int M, int k, float* d2_out, int64_t* idx_out) {
+  CHECK_CTX();
+  if (nq < 0 || n_img < 0 || k < 1 || k > 1024 || M < 1 || M > 4096)
+    return ctx->fail(SEGVLAD_ERR_ARG, "search_shortlist: need nq, n_img >= 0, 1<=k<=1024, 1<=M<=4096 (k=%d, M=%d)", k, M);
+  if (!qseg_offsets) return ctx->fail(SEGVLAD_ERR_ARG, "search_shortlist: null qseg_offsets");
+  if (sv_is_device_ptr(qseg_offsets)) return ctx->fail(SEGVLAD_ERR_ARG, "search_shortlist: qseg_offsets must be host memory");
+  if (qseg_offsets[0] != 0 || qseg_offsets[n_img] != nq)
+    return ctx->fail(SEGVLAD_ERR_ARG, "search_shortlist: qseg_offsets must run from 0 to nq=%d", nq);
+  for (int b = 0; b < n_img; ++b)
+    if (qseg_offsets[b + 1] < qseg_offsets[b]) return ctx->fail(SEGVLAD_ERR_ARG, "search_shortlist: qseg_offsets decrease at %d", b);
+  if (ctx->db_d == 0) return ctx->fail(SEGVLAD_ERR_STATE, "search_shortlist: the index is empty and has no dimension yet");
+  if (!ctx->db_has_img) return ctx->fail(SEGVLAD_ERR_STATE, "search_shortlist: no img_of_seg map: give it to segvlad_db_add");
+  if (nq == 0) return SEGVLAD_OK;
+  if (!Q || !shortlist || !d2_out || !idx_out) return ctx->fail(SEGVLAD_ERR_ARG, "search_shortlist: null pointer");
+  const int d = ctx->db_d;
+  if (d % 32 != 0) return ctx->fail(SEGVLAD_ERR_LIMIT, "search_shortlist: d=%d (the exact GEMM takes d %% 32 == 0)", d);
+  if (ctx->db_n > 0x7fffffffll) return ctx->fail(SEGVLAD_ERR_LIMIT, "search_shortlist: more than 2^31 - 1 rows");
+  const void *dq, *dsl;
+  void *dd2, *didx;
+  SV_TRY(sv_in(ctx, Q, (size_t)nq * d * 4, &dq));
+  if ((reinterpret_cast<uintptr_t>(dq) & 15) != 0) {   // (a row-offset view of a device tensor: the GEMM loads 16-byte pieces)
+    SV_HIP(ctx->s_sl_q.reserve((size_t)nq * d * 4));
+    SV_HIP(hipMemcpyAsync(ctx->s_sl_q.p, dq, (size_t)nq * d * 4, hipMemcpyDeviceToDevice, ctx->stream));
+    dq = ctx->s_sl_q.p;
+  }
+  SV_TRY(sv_in(ctx, shortlist, (size_t)n_img * M * 4, &dsl));
+  SV_TRY(sv_out(ctx, d2_out, (size_t)nq * k * 4, &dd2));
+  SV_TRY(sv_out(ctx, idx_out, (size_t)nq * k * 8, &didx));
+  SV_HIP(ctx->s_qnorm.reserve((size_t)nq * 4));
+  SV_TRY(sv_launch_row_sumsq(ctx, (const float*)dq, nq, d, ctx->s_qnorm.as<float>()));
+  SV_TRY(sv_search_shortlist(ctx, (const float*)dq, nq, ctx->s_qnorm.as<float>(), qseg_offsets, n_img, (const int32_t*)dsl, M, k,
+                             (float*)dd2, (int64_t*)didx));
   return sv_finish(ctx);
 }
 

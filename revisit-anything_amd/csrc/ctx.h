@@ -282,6 +282,10 @@ struct segvlad_ctx {
   const float* f16_scale_dev = nullptr;   // set by segvlad_search for the duration of a single-image search (see above)
   bool small_head_ran = false;   // this search's pass started with small_head_kernel (which also repairs a poisoned hand-over buffer)
   bool db_heur_off = false;   // set when > 25 % of a search's queries needed the rigorous redo (until the index changes)
+  // shortlist search (shortlist_kernels.hip): largest image id of db_img (-1: none), and whether sl_img_off / sl_img_rows -- the
+  // image -> row map -- describe the current index (cleared by segvlad_db_add / segvlad_db_reset, rebuilt by the next shortlist search)
+  int db_img_max = -1;
+  bool sl_map_valid = false;
   // device-driven single-image passes (small_pass_kernels.hip): the tail kernel's counters of the LAST such search live in device
   // memory and are fetched by segvlad_search_stats (the search itself never reads them back); its running totals reach the host
   // through two pinned words that segvlad_search looks at WITHOUT synchronising -- a database on which the low-rank thresholds
@@ -298,7 +302,7 @@ struct segvlad_ctx {
   //  s_tail_tick: tickets (all zero between launches) + running totals of small_tail_kernel
 #define SV_PERSISTENT_BUFS(X)                                                                                                    \
   X(vocab) X(vocab_bt) X(pca_mean) X(pca_comps) X(pca_scale) X(pca_w1) X(pca_w2) X(pca_cproj) X(db_rows) X(db_norms) X(db_img)    \
-  X(db_hi) X(db_lo) X(db_f16) X(s_ref_keys) X(s_ref_tick) X(s_tail_tick)
+  X(db_hi) X(db_lo) X(db_f16) X(s_ref_keys) X(s_ref_tick) X(s_tail_tick) X(sl_img_off) X(sl_img_rows)
   //  scratch: grow-only, reused across calls, nothing in them is read after the call that wrote it; s_sh_*: exchange buffers of
   //  the row-sharded index (comm.hip)
 #define SV_SCRATCH_BUFS(X)                                                                                                       \
@@ -307,7 +311,8 @@ struct segvlad_ctx {
   X(s_ref_cnt) X(s_ref_id) X(s_qscale) X(s_qf16) X(s_xh1) X(s_xh2) X(s_desc) X(s_tokorder) X(s_laboff) X(s_rnsorted) X(s_ovf)     \
   X(s_fb_q) X(s_fb_d2) X(s_fb_idx) X(s_fb_rows) X(s_rd_rows) X(s_rd_q) X(s_rd_d2) X(s_rd_idx) X(s_rd_flags) X(s_rd_p1) X(s_rd_p2)  \
   X(s_sel_todo) X(s_vote_keys) X(s_pz) X(s_rowbase) X(s_tilegrp) X(s_bn) X(s_l0part) X(s_ref_lim) X(s_sh_d2) X(s_sh_idx)          \
-  X(s_sh_rec) X(s_sh_all) X(s_sh_d2c) X(s_sh_idc) X(s_grp_cnt) X(s_grp_ids) X(s_grp_rows) X(s_grp_keys) X(s_grp_work) X(s_grp_pos) X(s_tnk_redo) X(s_tail_part) X(s_km_part) X(s_km_cnt) X(s_kflush)
+  X(s_sh_rec) X(s_sh_all) X(s_sh_d2c) X(s_sh_idc) X(s_grp_cnt) X(s_grp_ids) X(s_grp_rows) X(s_grp_keys) X(s_grp_work) X(s_grp_pos) X(s_tnk_redo) X(s_tail_part) X(s_km_part) X(s_km_cnt) X(s_kflush) \
+  X(s_sl_misc) X(s_sl_q) X(s_sl_cur) X(s_sl_uids) X(s_sl_uoff) X(s_sl_unum) X(s_sl_cand) X(s_sl_lens)
 #define SV_DECL_BUF(n) DevBuf n;
   SV_PERSISTENT_BUFS(SV_DECL_BUF)
   SV_SCRATCH_BUFS(SV_DECL_BUF)
@@ -534,6 +539,12 @@ int sv_launch_merge_topk(segvlad_ctx* ctx, const float* d2_parts, const int64_t*
 int sv_launch_sims(segvlad_ctx* ctx, const float* d2, const int64_t* idx, int nq, int k_in, int k_keep, float* sims,
                    int64_t* idx_out);
 int sv_launch_minmax(segvlad_ctx* ctx, const float* sims, int64_t count, float* minmax_dev);
+
+// shortlist_kernels.hip: the largest id of img_dev[0, n) (synchronises), and segvlad_search_shortlist after its checks (Q on the
+// device and 16-byte aligned, qn its squared norms, qoff host, shortlist / outputs on the device)
+int sv_img_max(segvlad_ctx* ctx, const int32_t* img_dev, int64_t n, int* out);
+int sv_search_shortlist(segvlad_ctx* ctx, const float* Q, int nq, const float* qn, const int32_t* qoff, int n_img,
+                        const int32_t* shortlist, int M, int k, float* d2_out, int64_t* idx_out);
 
 // vote_kernels.hip
 int sv_launch_vote(segvlad_ctx* ctx, const int64_t* idx, const float* sims, const int32_t* img_of_seg,

@@ -77,8 +77,27 @@ def describe_split(dino_in, masks_in, image_keys: Sequence[str], describe: Calla
     return desc, im, seg_range
 
 
+def shortlist_from_global(db_global, q_global, m: int) -> np.ndarray:
+    """First stage of a two-stage re-rank: per query image the exact top-``m`` reference images by the AnyLoc global VLAD
+    (``func_vpr.aggFt(..., 'vlad')`` descriptors, one row per image, in the reference's image order), as the padded
+    ``int32 [n_q, m]`` shortlist ``run_segloc(..., shortlist=...)`` / ``SegVLADPipeline.retrieve`` take (``-1`` where fewer
+    than ``m`` reference images exist).  The search is ``place_rec.IndexFlatL2`` -- exact, ties to the lower image id."""
+    from .place_rec import IndexFlatL2
+
+    db = np.ascontiguousarray(np.stack([np.asarray(v, np.float32) for v in db_global]) if isinstance(db_global, (list, tuple))
+                              else np.asarray(db_global, np.float32))
+    q = np.ascontiguousarray(np.stack([np.asarray(v, np.float32) for v in q_global]) if isinstance(q_global, (list, tuple))
+                             else np.asarray(q_global, np.float32))
+    if int(m) < 1:
+        raise ValueError(f"m={m}: a shortlist holds at least one image")
+    index = IndexFlatL2(db.shape[1])
+    index.add(db)
+    _, ids = index.search(q, int(m))
+    return np.ascontiguousarray(ids, dtype=np.int32)
+
+
 def run_segloc(dino_r, masks_r, keys_r, dino_q, masks_q, keys_q, gt, pipeline, batch_size: int = 100, n_top: int = 5,
-               k_search: int = 200, k_vote: int = 50, save_results: Optional[dict] = None):
+               k_search: int = 200, k_vote: int = 50, save_results: Optional[dict] = None, shortlist=None):
     """Reference split -> index, query split -> ranked reference images -> recall@1..n_top, on the device pipeline
     (``pipeline``: a ``SegVLADPipeline`` whose engine has the vocabulary and, if used, the PCA model set).
     The chain is ``recall_segloc``'s (place_rec_main.py:44-96): normalised descriptors, exact search ``k_search``,
@@ -88,7 +107,10 @@ def run_segloc(dino_r, masks_r, keys_r, dino_q, masks_q, keys_q, gt, pipeline, b
     reference pickles under its ``--save_results`` switch, under the reference's file names: the reference descriptors
     ``segFtVLAD1`` (place_rec_main.py:292-305), the query descriptors ``segFtVLAD2`` (``:357-370``) -- torch CPU tensors, the
     rows as they are handed to ``recall_segloc`` -- and ``{'sims', 'matches'}``, the ``k_search``-deep search output
-    (``:61-75``)."""
+    (``:61-75``).
+
+    ``shortlist`` (optional, ``int32 [len(keys_q), M]``, -1 padded -- e.g. ``shortlist_from_global``): query image i is
+    searched against the segments of its listed reference images only (``SegVLADPipeline.retrieve(shortlist=...)``)."""
     from .pipeline import recall_at
     from . import store
 
@@ -105,7 +127,8 @@ def run_segloc(dino_r, masks_r, keys_r, dino_q, masks_q, keys_q, gt, pipeline, b
     pipeline.index_reset()
     pipeline.index_add(d1, im1.astype(np.int32))
     q_off = np.concatenate([[0], np.cumsum([len(r) for r in seg_range2])]).astype(np.int32)
-    pred, _, matches, sims = pipeline.retrieve(d2, q_off, k_search=k_search, k_vote=k_vote, n_top=n_top)
+    extra = {} if shortlist is None else {"shortlist": shortlist}
+    pred, _, matches, sims = pipeline.retrieve(d2, q_off, k_search=k_search, k_vote=k_vote, n_top=n_top, **extra)
     pred = pred.cpu().numpy() if hasattr(pred, "cpu") else np.asarray(pred)
     if save_results is not None:
         full_d2, full_idx = pipeline.last_search

@@ -37,6 +37,37 @@ def _as(x, dtype_np, dtype_t):
     return np.ascontiguousarray(x, dtype=dtype_np)
 
 
+def pad_shortlists(lists, M: Optional[int] = None) -> np.ndarray:
+    """Ragged per-image shortlists (a sequence of sequences of reference image ids) -> the padded ``int32 [n_img][M]`` array
+    of segvlad_search_shortlist: each row's ids in their given order, then -1.  M defaults to the longest list (at least 1)."""
+    rows = [np.asarray(x, dtype=np.int64).reshape(-1) for x in lists]
+    longest = max((len(r) for r in rows), default=0)
+    M = max(1, longest) if M is None else int(M)
+    if longest > M:
+        raise ValueError(f"a shortlist holds {longest} ids, more than M={M}")
+    out = np.full((len(rows), M), -1, dtype=np.int32)
+    for b, r in enumerate(rows):
+        if r.size and (r.min() < np.iinfo(np.int32).min or r.max() > np.iinfo(np.int32).max):
+            raise ValueError(f"shortlist {b}: id out of the int32 range")
+        out[b, :len(r)] = r
+    return out
+
+
+def check_shortlist(shortlist: np.ndarray, n_img: int, n_img_ref: int) -> None:
+    """Host-side validation of a padded shortlist: shape [n_img][M] with 1 <= M <= 4096, ids in -1 .. n_img_ref - 1
+    (-1 is padding); raises ValueError otherwise."""
+    if shortlist.ndim != 2 or shortlist.shape[0] != n_img:
+        raise ValueError(f"shortlist must be [n_img={n_img}][M], got shape {tuple(shortlist.shape)}")
+    if not 1 <= shortlist.shape[1] <= 4096:
+        raise ValueError(f"shortlist width M={shortlist.shape[1]} outside 1 .. 4096")
+    if shortlist.size:
+        lo, hi = int(shortlist.min()), int(shortlist.max())
+        if lo < -1:
+            raise ValueError(f"shortlist id {lo} < -1 (-1 is the only padding value)")
+        if hi >= n_img_ref:
+            raise ValueError(f"shortlist id {hi} >= the number of reference images {n_img_ref}")
+
+
 class SegVLADEngine:
     """One context per (device, stream user).  Not thread-safe (the C context is not re-entrant)."""
 
@@ -56,6 +87,7 @@ class SegVLADEngine:
         self.vocab_generation = 0   # bumped by every set_vocab / pca_set: lets callers cache "my model is resident"
         self.pca_generation = 0
         self._keep = []  # tensors that must outlive async kernels of the last call
+        self.n_img_ref = 0   # 1 + the largest img_of_seg id given to db_add since the last db_reset
 
     # ---- plumbing ---------------------------------------------------------------------------------
     def close(self):
@@ -524,6 +556,7 @@ class SegVLADEngine:
     # ---- exact kNN --------------------------------------------------------------------------------
     def db_reset(self):
         self._check(self.lib.segvlad_db_reset(self._h), "db_reset")
+        self.n_img_ref = 0
 
     def db_add(self, R, img_of_seg=None):
         r = _as(R, np.float32, torch.float32)
@@ -531,6 +564,8 @@ class SegVLADEngine:
         im = None if img_of_seg is None else _as(img_of_seg, np.int32, torch.int32)
         self._stream()
         self._check(self.lib.segvlad_db_add(self._h, _ptr(r), n, d, _ptr(im)), "db_add")
+        if im is not None and n > 0:
+            self.n_img_ref = max(self.n_img_ref, int(im.max()) + 1)
         if isinstance(r, torch.Tensor) and r.is_cuda:
             torch.cuda.current_stream(self.device).synchronize()  # the index copied the rows: r may now be freed
 
@@ -547,6 +582,37 @@ class SegVLADEngine:
         self._stream()
         self._check(self.lib.segvlad_search(self._h, _ptr(q), nq, k, _ptr(d2), _ptr(idx)), "search")
         self._keep = [q]
+        return d2, idx
+
+    def search_shortlist(self, Q, qseg_offsets, shortlist, k: int):
+        """segvlad_search_shortlist: per query row the exact top-k rows of the index whose image is in its query image's
+        shortlist.  ``qseg_offsets`` [n_img + 1] (host); ``shortlist``: ``int32 [n_img][M]`` (-1 padded; a host array is
+        validated here, ids < -1 or >= n_img_ref raise ValueError) or a ragged list of lists (padded by pad_shortlists).
+        Returns device tensors (d2 [nq][k] fp32, idx [nq][k] int64) like search(); (+inf, -1) beyond the allowed rows."""
+        q = _as(Q, np.float32, torch.float32)
+        nq = q.shape[0]
+        qo = np.ascontiguousarray(qseg_offsets, dtype=np.int32)
+        n_img = len(qo) - 1
+        if isinstance(shortlist, torch.Tensor) and shortlist.is_cuda:
+            sl = shortlist.to(torch.int32).contiguous()
+            if sl.dim() != 2 or sl.shape[0] != n_img:
+                raise ValueError(f"shortlist must be [n_img={n_img}][M], got shape {tuple(sl.shape)}")
+        else:
+            if isinstance(shortlist, torch.Tensor):
+                shortlist = shortlist.numpy()
+            if isinstance(shortlist, np.ndarray) and shortlist.ndim == 2:
+                sl = np.ascontiguousarray(shortlist, dtype=np.int64)
+            else:
+                sl = pad_shortlists(shortlist).astype(np.int64)
+            check_shortlist(sl, n_img, self.n_img_ref)
+            sl = np.ascontiguousarray(sl, dtype=np.int32)
+        M = int(sl.shape[1])
+        d2 = self._empty((nq, k), torch.float32)
+        idx = self._empty((nq, k), torch.int64)
+        self._stream()
+        self._check(self.lib.segvlad_search_shortlist(self._h, _ptr(q), nq, _ptr(qo), n_img, _ptr(sl), M, k, _ptr(d2), _ptr(idx)),
+                    "search_shortlist")
+        self._keep = [q, sl]
         return d2, idx
 
     def merge_topk(self, d2_parts, idx_parts, parts: int, k: int):

@@ -49,7 +49,8 @@ int segvlad_version(void);
 int segvlad_create(segvlad_ctx** out, int device_id);
 int segvlad_destroy(segvlad_ctx* ctx);
 const char* segvlad_last_error(const segvlad_ctx* ctx);
-/* hip_stream: a hipStream_t (e.g. torch.cuda.current_stream().cuda_stream); NULL = default stream */
+/* hip_stream: a hipStream_t (e.g. torch.cuda.current_stream().cuda_stream); NULL = default stream.  The context's scratch and
+ * barrier words assume its work is stream-ordered: synchronise the old stream before switching to another one. */
 int segvlad_set_stream(segvlad_ctx* ctx, void* hip_stream);
 int segvlad_synchronize(segvlad_ctx* ctx);
 

@@ -280,6 +280,9 @@ struct segvlad_ctx {
   int64_t db_rn_max_rows = 0;
   bool f16_bias_ok = false;   // this search's batch filter launches may use the biased-accumulator kernel (segvlad_search)
   const float* f16_scale_dev = nullptr;   // set by segvlad_search for the duration of a single-image search (see above)
+  // small_head_kernel's grid barrier: arrivals on the device counter (s_tail_tick words 132-133) of every head launched on this
+  // context -- the next launch's target is this + its grid size (stream order: see segvlad_set_stream)
+  uint64_t small_head_arrivals = 0;
   bool small_head_ran = false;   // this search's pass started with small_head_kernel (which also repairs a poisoned hand-over buffer)
   bool db_heur_off = false;   // set when > 25 % of a search's queries needed the rigorous redo (until the index changes)
   // shortlist search (shortlist_kernels.hip): largest image id of db_img (-1: none), and whether sl_img_off / sl_img_rows -- the

@@ -237,7 +237,7 @@ __global__ __launch_bounds__(SH_T) void small_head_kernel(const float* __restric
                                                           _Float16* __restrict__ qplane, float* __restrict__ scales,
                                                           float* __restrict__ qn_out, uint32_t* __restrict__ zero, int zero_words,
                                                           float* __restrict__ cand, unsigned long long* __restrict__ ticket,
-                                                          float* __restrict__ thr_out, uint32_t* __restrict__ cnt, int dbg,
+                                                          unsigned long long target, float* __restrict__ thr_out, uint32_t* __restrict__ cnt, int dbg,
                                                           uint32_t* __restrict__ rtick, int rtick_poison, uint64_t* __restrict__ gkeys,
                                                           int64_t gkeys_words) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -502,16 +502,18 @@ __global__ __launch_bounds__(SH_T) void small_head_kernel(const float* __restric
   TICK();
   // (7) grid barrier, then every workgroup ranks the minima of ITS queries (q = w, w + NW, ...: at most one or two, one wave each).
   //     A single last workgroup ranking all m queries -- seven per wave, each a dependent chain of ~3000 cycles -- took 10-16 us;
-  //     spread over the grid it is one chain.  The barrier is a 64-bit arrival counter that only ever grows (no reset, no ABA):
-  //     this workgroup's target is the end of its own generation.  All workgroups of the launch are resident together (<= 128
+  //     spread over the grid it is one chain.  The barrier is a 64-bit arrival counter of the context: every workgroup of every
+  //     launch adds one, and the HOST passes the count this launch completes (target = the count before it + NW; sv_small_words
+  //     zeroes both together).  The generation cannot be derived from the ticket: NW follows the index size, so a ticket count
+  //     left by a launch of another grid is not a multiple of this one's NW.  The context's launches are stream-ordered, so no
+  //     workgroup of a later launch draws a ticket before this launch's NW have.  All workgroups of the launch are resident together (<= 128
   //     workgroups, one per CU); should they ever not be -- or should anything else go wrong -- the spin is BOUNDED and the rows get
   //     a threshold of -inf instead: their candidate lists stay empty, the pass flags them and small_tail_kernel finishes them
   //     exactly.  Nothing can hang, nothing can come out wrong.
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
   if (tid == 0) {
-    const unsigned long long mine = __hip_atomic_fetch_add(ticket, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const unsigned long long target = (mine / (unsigned long long)NW + 1ull) * (unsigned long long)NW;
+    __hip_atomic_fetch_add(ticket, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     int ok = 0;
     for (int spin = 0; spin < (1 << 20); ++spin) {
       if (__hip_atomic_load(ticket, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= target) {
@@ -576,7 +578,10 @@ bool sv_small_head_ok(int m, int d, int n0, int rank) {
 int sv_small_words(segvlad_ctx* ctx) {   // [129] tail tickets, [2] tail totals, 1 pad, [2] the head's 64-bit arrival counter
   const size_t tcap = ctx->s_tail_tick.cap;
   SV_HIP(ctx->s_tail_tick.reserve((size_t)(129 + 2 + 1 + 2) * 4));
-  if (ctx->s_tail_tick.cap != tcap) SV_HIP(hipMemsetAsync(ctx->s_tail_tick.p, 0, ctx->s_tail_tick.cap, ctx->stream));
+  if (ctx->s_tail_tick.cap != tcap) {
+    SV_HIP(hipMemsetAsync(ctx->s_tail_tick.p, 0, ctx->s_tail_tick.cap, ctx->stream));
+    ctx->small_head_arrivals = 0;   // (the head's barrier: the host's count of the device counter, zeroed with it)
+  }
   return SEGVLAD_OK;
 }
 
@@ -597,11 +602,13 @@ int sv_launch_small_head(segvlad_ctx* ctx, const float* X, int m, int d, const u
   const bool frag = fr * steps <= 16 && ctx->opt.small_head == 3;
   const size_t lds = frag ? lds_r : (lds_a > lds_r ? lds_a : lds_r);
   if (lds > 160 * 1024) return ctx->fail(SEGVLAD_ERR_LIMIT, "small head: %zu bytes of LDS", lds);
+  // the barrier's generation: this launch's nw arrivals on top of every earlier launch's (the kernel adds them, the host counts them)
+  const unsigned long long target = ctx->small_head_arrivals + (unsigned long long)nw;
   auto kern = !frag ? small_head_kernel<0> : fr == 1 ? small_head_kernel<1> : fr == 2 ? small_head_kernel<2> : fr == 4 ? small_head_kernel<4> : small_head_kernel<8>;
   SV_HIP(sv_max_dyn_lds(reinterpret_cast<const void*>(kern), lds));
   hipLaunchKernelGGL(kern, dim3(nw), dim3(SH_T), lds, ctx->stream, X, m, d, reinterpret_cast<const _Float16*>(Rh), rn, stride, n0,
                      db_scale, rank, reinterpret_cast<_Float16*>(qplane), scales_dev, qn_out, zero, zero_words, cand_scratch,
-                     reinterpret_cast<unsigned long long*>(ctx->s_tail_tick.as<uint32_t>() + 132), thr_out, cand_cnt,
+                     reinterpret_cast<unsigned long long*>(ctx->s_tail_tick.as<uint32_t>() + 132), target, thr_out, cand_cnt,
 #ifdef SV_HEAD_TIMING
                      1,
 #else
@@ -610,6 +617,7 @@ int sv_launch_small_head(segvlad_ctx* ctx, const float* X, int m, int d, const u
                      ctx->s_ref_tick.as<uint32_t>(), 128, ctx->s_ref_keys.as<uint64_t>(), (int64_t)(ctx->s_ref_keys.cap / 8));
   ctx->small_head_ran = true;
   SV_HIP(hipGetLastError());
+  ctx->small_head_arrivals = target;
   return SEGVLAD_OK;
 }
 

@@ -73,3 +73,51 @@ def d2(q2, r2, dot):
     """sv_d2: fmaf(-2, dot, q2 + r2) with negative results set to zero (faiss's clamp)."""
     v = fma32(np.float32(-2.0), dot, (np.asarray(q2, np.float32) + np.asarray(r2, np.float32)).astype(np.float32))
     return np.where(v < 0, np.float32(0), v).astype(np.float32)
+
+
+def check_contested(Q, R, d2_dev, idx_dev, k, queries=None, margin=1e-3, tol64=4e-6):
+    """The device's top-k lists of query rows `queries` (default: all) against the emulated fp32 reference, bit for bit and ties
+    included, and the fp64 oracle beside it.  Q [nq, d], R [n, d]: fp32 torch tensors on the device; d2_dev [nq, k], idx_dev [nq, k]:
+    the device's result.  The emulation runs on the CONTESTED rows only: per query every row whose distance by a plain fp32 GEMM
+    (a tool of the test, not the product) lies within `margin` x max(1, k-th smallest) of the k-th smallest -- 100 x the worst fp32
+    deviation at that magnitude, so no row outside the set can be in anybody's top k.  Every emulated distance of the result lies
+    within tol64 x max(1, (||q||^2 + max ||r||^2) / 2) of the fp64 distance (tol64 itself for unit rows).
+    Returns (contested pairs, exact-tie neighbours among the results, worst |fp32 - fp64| relative to that scale)."""
+    import torch
+
+    nq = Q.shape[0]
+    queries = range(nq) if queries is None else [int(q) for q in queries]
+    qsel = torch.as_tensor(list(queries), dtype=torch.int64, device=Q.device)
+    Qs = Q[qsel]
+    approx = (Qs * Qs).sum(1, keepdim=True) + (R * R).sum(1)[None, :] - 2.0 * (Qs @ R.T)
+    kth = torch.kthvalue(approx, k, dim=1).values
+    lim = kth + margin * torch.clamp(kth, min=1.0)
+    Qn = Q.cpu().numpy()
+    q2 = row_sumsq(Qn)
+    dd, ii = d2_dev.cpu().numpy(), idx_dev.cpu().numpy()
+    # every query's contested rows in ONE emulated chain (row-wise query operand)
+    sel = [torch.nonzero(approx[j] <= lim[j]).flatten() for j in range(len(qsel))]
+    for j, q in enumerate(queries):
+        assert sel[j].numel() >= k, (q, sel[j].numel())
+    ids_all = torch.cat(sel)
+    rr_all = R[ids_all].cpu().numpy()
+    owner = np.repeat(np.arange(len(sel)), [s.numel() for s in sel])
+    qq_all = Qn[np.asarray(list(queries), np.int64)[owner]]
+    dist_all = d2(q2[np.asarray(list(queries), np.int64)[owner]], row_sumsq(rr_all), dot_chain(qq_all, rr_all))
+    ids_all = ids_all.cpu().numpy()
+    n_contested, n_tie_pairs, worst64 = 0, 0, 0.0
+    off = 0
+    for j, q in enumerate(queries):
+        cnt = sel[j].numel()
+        ids, dist, rr = ids_all[off:off + cnt], dist_all[off:off + cnt], rr_all[off:off + cnt]
+        off += cnt
+        order = np.lexsort((ids, dist))[:k]                         # (distance, id): IndexFlatL2's order, ties to the lower id
+        assert np.array_equal(ids[order], ii[q]), (q, np.nonzero(ids[order] != ii[q])[0][:5])
+        assert np.array_equal(dist[order].view(np.uint32), dd[q].view(np.uint32)), q
+        n_contested += cnt
+        n_tie_pairs += int((np.diff(dist[order]) == 0).sum())
+        d64 = ((Qn[q].astype(np.float64)[None, :] - rr[order].astype(np.float64)) ** 2).sum(1)
+        scale = max(1.0, (float(q2[q]) + float(row_sumsq(rr).max())) / 2.0)
+        worst64 = max(worst64, float(np.abs(d64 - dist[order]).max()) / scale)
+    assert worst64 < tol64, worst64
+    return n_contested, n_tie_pairs, worst64

@@ -3,10 +3,8 @@ and ties included, the lists a host emulation of the device's documented fp32 ar
 sequential fma chain, the row_sumsq lane order, sv_d2 with faiss's clamp) -- on 64 queries of the three kinds (planted, random,
 near-copies), for the batch search, the single-image pass and the fp32 filter.
 
-The emulation runs on the CONTESTED rows only: per query every row whose distance (a plain fp32 GEMM on the device: a tool of the
-test, not the product) lies within 1e-3 of the k-th smallest -- 100 x the worst fp32 deviation, so no row outside the set can be in
-anybody's top k -- typically 200-400 rows.  The fp64 oracle stays beside it: every emulated distance within 2e-6 of it."""
-import numpy as np
+The emulation runs on the CONTESTED rows only (tests/fp32_emu.py: check_contested): per query every row whose distance by a
+plain fp32 GEMM lies near the k-th smallest, typically 200-400 rows; the fp64 oracle stays beside it."""
 import pytest
 import torch
 
@@ -52,28 +50,8 @@ def test_device_ids_equal_the_emulated_fp32_arithmetic_bit_for_bit():
     d2_f, id_f = eng.search(Q, k)
     eng.set_option("knn_filter", "auto")
     assert torch.equal(id_big[:nq], id_b) and torch.equal(d2_big[:nq], d2_b) and torch.equal(id_f, id_b) and torch.equal(d2_f, d2_b)
-    # contested rows (test tool: plain torch GEMM, fp32)
-    approx = (Q * Q).sum(1, keepdim=True) + (R * R).sum(1)[None, :] - 2.0 * (Q @ R.T)
-    kth = torch.kthvalue(approx, k, dim=1).values
-    Rn, Qn = None, Q.cpu().numpy()
-    q2 = E.row_sumsq(Qn)
+    n_contested, n_tie_pairs, worst64 = E.check_contested(Q, R, d2_b, id_b, k)   # (contested rows, emulated fp32, fp64 within 4e-6)
     dd, ii = d2_b.cpu().numpy(), id_b.cpu().numpy()
-    n_contested, n_tie_pairs, worst64 = 0, 0, 0.0
-    for q in range(nq):
-        rows = torch.nonzero(approx[q] <= kth[q] + 1e-3).flatten()
-        assert rows.numel() >= k
-        rr = R[rows].cpu().numpy()
-        ids = rows.cpu().numpy()
-        r2 = E.row_sumsq(rr)
-        dist = E.d2(q2[q], r2, E.dot_chain(Qn[q], rr))
-        order = np.lexsort((ids, dist))[:k]                         # (distance, id): IndexFlatL2's order, ties to the lower id
-        assert np.array_equal(ids[order], ii[q]), (q, np.nonzero(ids[order] != ii[q])[0][:5])
-        assert np.array_equal(dist[order].view(np.uint32), dd[q].view(np.uint32)), q
-        n_contested += len(ids)
-        n_tie_pairs += int((np.diff(dist[order]) == 0).sum())
-        d64 = ((Qn[q].astype(np.float64)[None, :] - rr[order].astype(np.float64)) ** 2).sum(1)
-        worst64 = max(worst64, float(np.abs(d64 - dist[order]).max()))
-    assert worst64 < 4e-6
     assert ii[0, 0] == 123_456 and ii[0, 1] == 777_777 and dd[0, 0] == dd[0, 1]      # the planted exact tie: lower id first
     print(f"[exact ids] {nq} queries x {k}: {n_contested} contested pairs emulated, {n_tie_pairs} exact-tie neighbours among the results, "
           f"max |fp32 - fp64| {worst64:.2e}")

@@ -4,13 +4,14 @@
 parity test turned the builder's own full-suite run red and, under `-x`, hid every parity test behind it).  What a box's
 clocks can move lives here: `pytest -m gpu_perf` on a GPU box.  The test re-uses the line the parity test
 `test_gpu_bench_step.py::test_bench_step_predictions_equal_oracle_on_20_images` left behind when it ran in the same
-checkout, and runs bench.py itself otherwise."""
+checkout, and runs bench.py itself otherwise.  The single-image head's stage time after a grow of the index is timed here too."""
 import json
 import os
 import subprocess
 import sys
 
 import pytest
+import torch
 
 pytestmark = pytest.mark.gpu_perf
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -53,3 +54,39 @@ def test_streaming_pass_reaches_the_north_star_fraction_by_the_wall_clock(line):
     # north_star: >= 60 % of the HBM roofline for the kNN stage, by the call's wall clock
     st = line["roofline_knn_stream"]
     assert st["frac_by_call_wall"] >= 0.55, st
+
+
+def test_first_single_image_pass_after_a_grow_is_not_slower():
+    """The single-image head's stage time (knn_level0) on the first pass after a db_add that changes its grid (80 000 -> 100 000
+    rows of d = 1024: NW 79 -> 98), against a fresh context's.  A loose bound only: a misaligned grid barrier waits out its bounded
+    spin (2^20 polls), orders of magnitude above it (tests/test_gpu_index_lifecycle.py holds the results)."""
+    from revisit_anything_amd.engine import SegVLADEngine
+
+    dev = torch.device("cuda:0")
+    n, d, k = 100_000, 1024, 50
+    g = torch.Generator(device=dev)
+    g.manual_seed(95)
+    R = torch.nn.functional.normalize(torch.randn(n, d, device=dev, generator=g), dim=1)
+    src = torch.randint(0, n, (50,), device=dev, generator=g)
+    Q = torch.nn.functional.normalize(R[src] + 0.05 * torch.randn(50, d, device=dev, generator=g), dim=1)
+
+    def level0(eng):
+        eng.set_profiling(True)
+        eng.profile_reset()
+        eng.search(Q, k)
+        eng.synchronize()
+        return eng.stage_ms("knn_level0")[0]
+
+    live = SegVLADEngine(0)
+    live.db_add(R[:80_000])
+    live.search(Q, k)
+    live.db_add(R[80_000:])
+    grown = level0(live)
+    live.close()
+    fresh = SegVLADEngine(0)
+    fresh.db_add(R)
+    fresh.search(Q, k)
+    ref = level0(fresh)
+    fresh.close()
+    print(f"[lifecycle] knn_level0 after a grow {grown:.3f} ms, fresh context {ref:.3f} ms")
+    assert grown < 5 * ref + 0.05, (grown, ref)

@@ -11,7 +11,6 @@
 #include <initializer_list>
 
 #include "ctx.h"
-#include "small_pass_dev.h"
 
 int segvlad_ctx::fail(int code, const char* fmt, ...) {
   va_list ap;
@@ -180,10 +179,6 @@ StageScope::~StageScope() {
   if (t) (void)hipEventRecord(t->ev[2 * slot + 1], ctx->stream);
 }
 
-#define CHECK_CTX()                 \
-  if (!ctx) return SEGVLAD_ERR_ARG; \
-  sv_begin(ctx)
-
 // Between segvlad_describe_begin and segvlad_describe_end the context's per-batch scratch (segment / adjacency offsets, the
 // token-major copy, the labels) belongs to THAT batch, and the mask branch is in flight on the side stream: every other entry
 // point that would write them refuses instead of describing a different batch with the open one's offsets.
@@ -345,25 +340,6 @@ int segvlad_set_option(segvlad_ctx* ctx, const char* key, const char* value) {
     return SEGVLAD_OK;
   }
   return ctx->fail(SEGVLAD_ERR_ARG, "set_option: unknown key '%s'", key);
-}
-
-int segvlad_search_stats(segvlad_ctx* ctx, int64_t* stats_out, int n) {
-  if (!ctx) return SEGVLAD_ERR_ARG;
-  if (!stats_out || n < 0) return ctx->fail(SEGVLAD_ERR_ARG, "search_stats: bad arguments");
-  if (ctx->tail_stats_dev) {   // the last search was a device-driven pass: its tail's counters are still on the device
-    uint32_t h[4] = {0, 0, 0, 0};
-    (void)hipSetDevice(ctx->device);
-    SV_HIP(hipStreamSynchronize(ctx->stream));
-    SV_HIP(hipMemcpy(h, ctx->tail_stats_dev, sizeof(h), hipMemcpyDeviceToHost));
-    ctx->sstats.n_redo = h[0];      // rows redone exactly (brute force on the device)
-    ctx->sstats.n_refine2 = h[1];   // rows refined from their candidate lists (second tier)
-    ctx->tail_stats_dev = nullptr;
-  }
-  const SvSearchStats& t = ctx->sstats;
-  const int64_t v[13] = {t.levels, t.filter, t.n_fallback, t.cand_max, t.cand_sum, t.refine_max, t.refine_sum, t.n_queries, t.n_redo, t.n_refine2,
-                         t.grp_groups, t.grp_union_sum, t.carry_rows};
-  for (int j = 0; j < n && j < 13; ++j) stats_out[j] = v[j];
-  return SEGVLAD_OK;
 }
 
 int segvlad_destroy(segvlad_ctx* ctx) {
@@ -1161,884 +1137,6 @@ int segvlad_normalize_rows(segvlad_ctx* ctx, const float* X, int n, int d, float
   SV_TRY(sv_in(ctx, X, (size_t)n * d * sizeof(float), &dx));
   SV_TRY(sv_out(ctx, Y, (size_t)n * d * sizeof(float), &dy));
   SV_TRY(sv_launch_normalize_rows(ctx, (const float*)dx, n, d, (float*)dy));
-  return sv_finish(ctx);
-}
-
-// ---- database / search ---------------------------------------------------------------------------------------
-int segvlad_db_reset(segvlad_ctx* ctx) {
-  CHECK_CTX();
-  ctx->db_n = 0;
-  ctx->db_d = 0;
-  ctx->db_has_img = false;
-  ctx->db_img_max = -1;
-  ctx->sl_map_valid = false;
-  ctx->db_split_rows = 0;
-  ctx->db_f16_rows = 0;
-  ctx->db_f16_scale = 0.f;
-  ctx->db_maxabs = 0.f;
-  ctx->db_rn_max = 0.f;
-  ctx->db_rn_max_rows = 0;
-  ctx->db_heur_off = false;
-  if (ctx->tail_rows_since > 0) (void)hipStreamSynchronize(ctx->stream);   // (the tail's pinned totals have landed)
-  ctx->tail_fail_base = ctx->h_pin ? reinterpret_cast<volatile uint32_t*>(ctx->h_pin)[8] : 0u;
-  ctx->tail_rows_since = 0;
-  return SEGVLAD_OK;
-}
-
-int segvlad_db_add(segvlad_ctx* ctx, const float* R, int n, int d, const int32_t* img_of_seg) {
-  CHECK_CTX();
-  if (n < 0 || d <= 0) return ctx->fail(SEGVLAD_ERR_ARG, "db_add: bad shape");
-  if (ctx->db_n > 0 && d != ctx->db_d) return ctx->fail(SEGVLAD_ERR_ARG, "db_add: d=%d but the index holds d=%d", d, ctx->db_d);
-  if (ctx->db_n > 0 && ctx->db_has_img != (img_of_seg != nullptr))
-    return ctx->fail(SEGVLAD_ERR_ARG, "db_add: img_of_seg must be given for all rows or none");
-  if (n == 0) return SEGVLAD_OK;
-  if (!R) return ctx->fail(SEGVLAD_ERR_ARG, "db_add: null rows");
-  const int64_t n_new = ctx->db_n + n;
-  // grow (keeping old contents)
-  auto grow = [&](DevBuf& b, size_t old_bytes, size_t new_bytes) -> hipError_t {
-    if (new_bytes <= b.cap) return hipSuccess;
-    DevBuf nb;
-    nb.tag = b.tag;
-    nb.guard = b.guard;
-    nb.fixed = b.fixed;
-    hipError_t e = nb.reserve(new_bytes + new_bytes / 2);
-    if (e != hipSuccess) return e;
-    if (old_bytes) {
-      e = hipMemcpyAsync(nb.p, b.p, old_bytes, hipMemcpyDeviceToDevice, ctx->stream);
-      if (e != hipSuccess) return e;
-      e = hipStreamSynchronize(ctx->stream);
-      if (e != hipSuccess) return e;
-    }
-    b.release();
-    b = nb;
-    return hipSuccess;
-  };
-  SV_HIP(grow(ctx->db_rows, (size_t)ctx->db_n * d * 4, (size_t)n_new * d * 4));
-  SV_HIP(grow(ctx->db_norms, (size_t)ctx->db_n * 4, (size_t)n_new * 4));
-  float* dst = ctx->db_rows.as<float>() + (size_t)ctx->db_n * d;
-  SV_HIP(hipMemcpyAsync(dst, R, (size_t)n * d * 4, hipMemcpyDefault, ctx->stream));
-  if (img_of_seg) {
-    SV_HIP(grow(ctx->db_img, (size_t)ctx->db_n * 4, (size_t)n_new * 4));
-    SV_HIP(hipMemcpyAsync(ctx->db_img.as<int32_t>() + ctx->db_n, img_of_seg, (size_t)n * 4, hipMemcpyDefault, ctx->stream));
-    ctx->db_has_img = true;
-    // the largest image id sizes the image -> row map of segvlad_search_shortlist (rebuilt by its next call)
-    int mx = -1;
-    SV_TRY(sv_img_max(ctx, ctx->db_img.as<int32_t>() + ctx->db_n, n, &mx));
-    ctx->db_img_max = std::max(ctx->db_img_max, mx);
-  }
-  ctx->sl_map_valid = false;
-  SV_TRY(sv_launch_row_sumsq(ctx, dst, n, d, ctx->db_norms.as<float>() + ctx->db_n));
-  ctx->db_n = n_new;
-  ctx->db_d = d;
-  ctx->db_heur_off = false;
-  if (ctx->tail_rows_since > 0) (void)hipStreamSynchronize(ctx->stream);   // (the tail's pinned totals have landed)
-  ctx->tail_fail_base = ctx->h_pin ? reinterpret_cast<volatile uint32_t*>(ctx->h_pin)[8] : 0u;
-  ctx->tail_rows_since = 0;
-  return sv_finish(ctx);
-}
-
-int segvlad_db_size(segvlad_ctx* ctx, int64_t* n_rows, int* d) {
-  if (!ctx) return SEGVLAD_ERR_ARG;
-  if (n_rows) *n_rows = ctx->db_n;
-  if (d) *d = ctx->db_d;
-  return SEGVLAD_OK;
-}
-
-// Exact search.  Small databases: distance matrix + radix select.  Large ones: a strided 1/16^L sample gives an
-// exact UPPER bound T0[q] of the k-th smallest distance; each finer level re-runs the distance GEMM with the
-// epilogue keeping only entries <= T[q] (about 16 k per query), whose exact top-k tightens T for the next level;
-// the last level covers every row, so the final top-k is exact (ties included: all entries <= T are candidates
-// and the final order is (distance, id)).  A query whose candidate or refine list overflows (adversarial data) is
-// redone -- alone -- on the matrix path; the other queries keep their filtered result.
-static int search_matrix(segvlad_ctx* ctx, const float* dq, int m, int64_t n, int d, int k, const float* qn, float* dd2,
-                         int64_t* didx) {
-  const int64_t ld = (n + 3) & ~3ll;
-  int64_t rows = ld > 0 ? (int64_t)(2ll << 30) / (ld * 4) : m;
-  if (rows < 128) rows = 128;
-  if (rows > m) rows = m;
-  SV_HIP(ctx->s_dist.reserve((size_t)rows * (ld > 0 ? ld : 1) * 4));
-  for (int64_t q0 = 0; q0 < m; q0 += rows) {
-    const int mm = (int)((m - q0 < rows) ? (m - q0) : rows);
-    {
-      StageScope sc(ctx, "knn_gemm");
-      SV_TRY(sv_launch_gemm_nt(ctx, 1, dq + (size_t)q0 * d, ctx->db_rows.as<float>(), ctx->s_dist.as<float>(), mm, (int)n, d,
-                               ld, nullptr, nullptr, qn + q0, ctx->db_norms.as<float>()));
-      sc.count();
-    }
-    {
-      StageScope sc(ctx, "knn_select");
-      SV_TRY(sv_launch_select_topk(ctx, ctx->s_dist.as<float>(), ld, mm, n, k, dd2 + (size_t)q0 * k, didx + (size_t)q0 * k, k, 0));
-      sc.count();
-    }
-  }
-  return SEGVLAD_OK;
-}
-
-// rows of the redo / overflow passes: gather flagged query rows into a dense block, scatter their results back
-__global__ __launch_bounds__(256) void gather_rows_kernel(const float* __restrict__ X, const float* __restrict__ xn,
-                                                          const int32_t* __restrict__ rows, int d, float* __restrict__ Y,
-                                                          float* __restrict__ yn) {
-  const int r = blockIdx.x;
-  const int64_t src = rows[r];
-  for (int j = threadIdx.x; j < d; j += 256) Y[(int64_t)r * d + j] = X[src * d + j];
-  if (threadIdx.x == 0) yn[r] = xn[src];
-}
-__global__ __launch_bounds__(256) void scatter_topk_kernel(const float* __restrict__ d2, const int64_t* __restrict__ idx,
-                                                           const int32_t* __restrict__ rows, int k, float* __restrict__ d2_out,
-                                                           int64_t* __restrict__ idx_out) {
-  const int r = blockIdx.x;
-  const int64_t dst = rows[r];
-  for (int j = threadIdx.x; j < k; j += 256) {
-    d2_out[dst * k + j] = d2[(int64_t)r * k + j];
-    idx_out[dst * k + j] = idx[(int64_t)r * k + j];
-  }
-}
-
-// ---- the level scheme ---------------------------------------------------------------------------------------------
-struct SearchPlan {
-  int levels = 0;          // filter levels after the sampled exact level
-  int64_t stride0 = 1;     // stride of the sampled exact level (16^levels)
-  int kind = 3;            // filter arithmetic: 1 f16, 2 bf16x3, 3 fp32
-  int d = 0, k = 0;
-  int64_t n = 0;
-  float c_eps = 0.f, inv_scale = 1.f, rn_max = 0.f;
-  int ratio_last = 16;     // sample growth into the LAST (full) level; the levels before it grow by SV_RATIO = 16
-  double pfail = 2e-5;     // heur_rank_small's tolerance when ratio_last != 16 (one redone query in ~1000 passes of 50)
-};
-constexpr int SV_RATIO = 16, SV_CAP = 8192, SV_RCAP = 512, SV_CHUNK = 16384;
-
-// Smallest rank r such that a threshold at the r-th smallest value of a 1/16 sample admits, 4 sigma below its
-// expectation 16 r, still `target` values of the full set (relative spread of the r-th order statistic ~ 1/sqrt(r)).
-static int heur_rank(int target) {
-  int r = 16;
-  while (16.0 * r - 64.0 * std::sqrt((double)r) < (double)target) ++r;
-  return r;
-}
-
-// The same question for a sample `ratio` times smaller and SMALL ranks, where the normal approximation is off: the
-// number of full-set values below the r-th smallest sample value is ~ ratio * Gamma(r, 1), so take the smallest r with
-// P[Gamma(r, 1) < target / ratio] < pfail (2e-5: one redo in ~1000 passes of 50 queries).
-static int heur_rank_small(int target, int ratio, double pfail) {
-  const double x = (double)target / ratio, ex = std::exp(-x);
-  double term = 1.0, sum = 0.0;   // sum_{i < r} x^i / i!
-  for (int r = 1; r < target; ++r) {
-    sum += term;
-    term *= x / r;
-    if (r >= 2 && 1.0 - ex * sum < pfail) return r;
-  }
-  return target;
-}
-
-// One pass of the level scheme over m <= SV_CHUNK query rows: exact distances to the coarsest sample, then `levels`
-// filter GEMMs over samples 16x larger each, the last one covering every row, then the exact refinement.
-//   rigorous : every threshold is the k-th smallest distance of the previous (coarser) sample -- an UPPER bound of
-//              the k-th smallest of the finer one, so no true neighbour is ever dropped; ~16 k candidates per level.
-//   heuristic: thresholds at much lower ranks r_j (heur_rank) that admit ~16 r_j candidates -- 5-10x fewer -- and are
-//              verified afterwards: a level whose list holds fewer than r_{j+1} entries, or a final list whose k-th
-//              smallest approximate distance A_k exceeds the threshold T it was collected under (then {d2~ <= A_k + 2 eps}
-//              might not be contained in the collected {d2~ <= T + 2 eps}), flags the query; flagged queries are redone
-//              with the rigorous thresholds.  Exactness never depends on the ranks; they only decide how often the redo runs.
-// q16a / q16b: this chunk's 16-bit query planes (f16: plane, unused; bf16x3: hi, lo).  fail_rows [m]: flags;
-// fail_count[0] / fail_count[1]: running counts of the flagged rows and of the second-tier rows (adjacent: ONE read-back per
-// chunk); rovf_rows_in [m]: second-tier flags, zero on entry; n_rovf_seen: the caller's copy of fail_count[1] so far.
-static int levels_chunk(segvlad_ctx* ctx, const SearchPlan& pl, bool heuristic, const float* qp, const uint16_t* q16a,
-                        const uint16_t* q16b, const float* qn, int m, float* out_d2, int64_t* out_idx, uint32_t* fail_rows,
-                        uint32_t* fail_count, uint32_t* rovf_rows_in, uint32_t* n_fail_host, uint32_t* n_rovf_seen, int phase = 0,
-                        uint32_t* tail_stats = nullptr) {
-  // tail_stats != null (one query image per pass, round 6): NO read-back -- small_tail_kernel is launched behind the refinement,
-  // reads the two counters on the device and finishes flagged rows there (small_pass_kernels.hip); the host learns nothing
-  // about them in this call (*n_fail_host = 0), segvlad_search_stats fetches the kernel's counters on demand
-  // phase 0: the whole pass.  1: the exact sample level only; 2: everything behind it -- a batch search enqueues phase 1 (which
-  // needs neither the query plane nor the filter's margin) BEFORE it waits for the two scalars that fix them, so that the device
-  // has that level to run while the host waits (m > 128 only: the single-image plan's fused level 0 is one chain with its pass)
-  const int d = pl.d, k = pl.k, levels = pl.levels;
-  const int64_t n = pl.n;
-  const float* R = ctx->db_rows.as<float>();
-  const float* rn = ctx->db_norms.as<float>();
-  // rank of the threshold handed to level j+1 (rank[levels] = k: the final top-k)
-  int rank[8];
-  rank[levels] = k;
-  for (int j = levels - 1; j >= 0; --j)
-  {
-    const int ratio_j = (j + 1 == levels) ? pl.ratio_last : SV_RATIO;   // growth from level j's sample to level j + 1's
-    rank[j] = !heuristic ? k
-                         : std::min(rank[j + 1], ratio_j == SV_RATIO ? heur_rank(rank[j + 1]) : heur_rank_small(rank[j + 1], ratio_j, pl.pfail));
-  }
-  const int64_t n0 = (n + pl.stride0 - 1) / pl.stride0;
-  const int64_t ld0 = (n0 + 3) & ~3ll;
-  float* thr = ctx->s_thr_d2.as<float>();
-  // second refinement tier (filters with an approximate domain only): [m] row flags + 1 count, [m] band limits
-  uint32_t* rovf_rows = nullptr;
-  uint32_t* rovf_count = fail_count + 1;
-  float* ref_lim = nullptr;
-  if (pl.kind != 3) {
-    SV_HIP(ctx->s_ref_lim.reserve((size_t)m * 4));
-    rovf_rows = rovf_rows_in;
-    ref_lim = ctx->s_ref_lim.as<float>();
-  }
-  const uint32_t* poison_dev = nullptr;   // see sv_launch_refine_exact
-  bool tail_fused = false;                // the refinement kernel finished the flagged rows itself (no small_tail_kernel)
-  const int r0 = rank[0];
-  bool l0_fused = false, l0_lists = false;
-  if (phase != 2) {  // level 0: exact (fp32) top-r0 of the coarsest sample -> thr[q][r0-1]
-    {
-      StageScope sc(ctx, "knn_level0");   // its own stage: "knn_gemm" then times the filter kernel's launches only
-      if (m <= 128 && n0 <= 4096 && pl.kind != 3) {
-        // one query image per pass: the K split's reduction and the rank select in ONE launch (l0_reduce_rank_kernel)
-        const float* parts = nullptr;
-        int splits = 1;
-        SV_TRY(sv_launch_l2_strided_parts(ctx, qp, R, ctx->s_dist.as<float>(), m, (int)n0, d, ld0, qn, rn, (int)pl.stride0, &parts, &splits));
-        sc.count();
-        if (splits > 1) {
-          SV_TRY(sv_launch_l0_reduce_rank(ctx, parts, splits, m, (int)n0, ld0, qn, rn, (int)pl.stride0, r0, thr,
-                                          ctx->s_cand_cnt.as<uint32_t>(), fail_rows));
-          sc.count();
-          l0_fused = true;
-        }
-      } else if (heuristic && pl.kind == 1 && m > 128 && n0 <= 4096 && q16a && ctx->opt.batch_l0_f16 && !ctx->f16_scale_dev &&
-                 sv_f16_kblock(ctx->opt, d) && ctx->opt.batch_l0_f16 != 2) {
-        // deep rows (raw K*D descriptors): the sample through the FILTER KERNEL under thresholds of +inf -- every sampled row lands in
-        // the candidate lists (n0 <= 4096 entries per query), the mode-0 select below ranks them like any level's.  The no-LDS sample
-        // kernel re-reads the query plane (2 GB at 10 000 x 98 304: not L2 resident) once per 32 sample rows: 8.5 ms for 196 rows,
-        // against ~0.6 ms at the filter's rate.
-        SV_HIP(hipMemsetD32Async((hipDeviceptr_t)thr, 0x7f800000, (size_t)m, ctx->stream));
-        SV_HIP(hipMemsetAsync(ctx->s_cand_cnt.p, 0, (size_t)m * 4, ctx->stream));
-        SV_TRY(sv_launch_f16_filter(ctx, q16a, ctx->db_f16.as<uint16_t>(), m, (int)n0, d, (int)pl.stride0, pl.inv_scale, qn, rn, thr, 1, 2.f,
-                                    pl.c_eps, pl.rn_max, ctx->s_cand_cnt.as<uint32_t>(), ctx->s_cand_d2.as<float>(),
-                                    ctx->s_cand_id.as<uint32_t>(), SV_CAP));
-        sc.count();
-        l0_lists = true;
-      } else if (heuristic && pl.kind == 1 && m > 128 && n0 <= 4096 && q16a && ctx->opt.batch_l0_f16 && !ctx->f16_scale_dev) {
-        // round 6: a guessed threshold needs no exact distances -- the sample through the filter's own fp16 product (~15 us instead
-        // of 115-160 us of poorly filled fp32 MFMA tiles); the thresholds are then approximate-domain values like every later level's
-        SV_TRY(sv_launch_sample_f16_batch(ctx, q16a, ctx->db_f16.as<uint16_t>(), m, (int)n0, d, pl.stride0, pl.inv_scale, qn, rn,
-                                          ctx->s_dist.as<float>(), ld0));
-        sc.count();
-      } else {
-        SV_TRY(sv_launch_l2_strided(ctx, qp, R, ctx->s_dist.as<float>(), m, (int)n0, d, ld0, qn, rn, (int)pl.stride0, true));
-        sc.count();
-      }
-    }
-    StageScope sc(ctx, "knn_select");
-    if (l0_fused) {
-      // (thr[q] is in place)
-    } else if (l0_lists) {
-      SV_TRY(sv_launch_select_approx(ctx, ctx->s_cand_cnt.as<uint32_t>(), ctx->s_cand_d2.as<float>(), ctx->s_cand_id.as<uint32_t>(), m,
-                                     SV_CAP, r0, 0, 1, nullptr, 0, qn, pl.c_eps, pl.rn_max, thr, ctx->s_ref_cnt.as<uint32_t>(),
-                                     ctx->s_ref_id.as<uint32_t>(), SV_RCAP, fail_rows, fail_count));
-    } else if (n0 <= 4096 && pl.kind != 3) {
-      // a short sample row: only its r0-th smallest distance is needed -- the wave-per-query register select of the
-      // candidate lists (mode 0: thr[q] = rank-th smallest), the distance block standing in for a list of n0 entries
-      SV_TRY(sv_launch_select_approx(ctx, ctx->s_cand_cnt.as<uint32_t>(), ctx->s_dist.as<float>(), ctx->s_cand_id.as<uint32_t>(), m,
-                                     (int)ld0, r0, 0, 0, nullptr, 0, qn, pl.c_eps, pl.rn_max, thr, ctx->s_ref_cnt.as<uint32_t>(),
-                                     ctx->s_ref_id.as<uint32_t>(), SV_RCAP, fail_rows, fail_count, nullptr, nullptr, nullptr, (int)n0));
-    } else {
-      SV_TRY(sv_launch_select_topk(ctx, ctx->s_dist.as<float>(), ld0, m, n0, r0, thr, ctx->s_thr_idx.as<int64_t>(), r0, 0));
-    }
-    if (!l0_fused) sc.count();
-  }
-  if (phase == 1) return SEGVLAD_OK;
-  const bool l0_small = n0 <= 4096 && pl.kind != 3;
-  const float* thr_ptr = l0_small ? thr : thr + (r0 - 1);
-  int64_t thr_ld = l0_small ? 1 : r0;
-  // rigorous: level-0 thresholds are exact distances, one margin covers the filter's error.  heuristic: the final
-  // check needs the collected set to reach 2 eps beyond the threshold at every level.
-  float eps_mult = heuristic ? 2.f : 1.f;
-  int64_t stride = pl.stride0;
-  std::vector<uint32_t> hcnt;
-  // carry (round 6b): the stride-16 level's filter has already evaluated 1/16 of the rows with the arithmetic of the last level; its
-  // survivors under the NEXT threshold stay in the lists (select mode 2) and the last level runs over the other 15/16 only.  Guessed
-  // thresholds only (every level collects under thr + 2 eps there, so the kept set is exactly what the last level would append).
-  const int64_t n_comp = n - (n + SV_RATIO - 1) / SV_RATIO;   // rows that are not multiples of 16
-  const bool carry = heuristic && pl.kind == 1 && levels >= 2 && pl.ratio_last == SV_RATIO && m > 128 && n_comp < 0x7fffffffLL &&
-                     sv_f16_filter_skip_ok(ctx, m, n_comp, d);
-  if (carry) ctx->sstats.carry_rows = n - n_comp;
-  for (int lv = 1; lv <= levels; ++lv) {
-    stride /= (lv == levels) ? pl.ratio_last : SV_RATIO;
-    const bool last = (lv == levels);
-    const int64_t ns = (last && carry) ? n_comp : (n + stride - 1) / stride;
-    // the candidate counters start every level at zero: the mode-0 selects of the approximate-domain filters leave them so;
-    // only the first filter level behind a select_topk level 0, and the fp32 filter's select, need the memset
-    if (pl.kind == 3 || (lv == 1 && !l0_small)) SV_HIP(hipMemsetAsync(ctx->s_cand_cnt.p, 0, (size_t)m * 4, ctx->stream));
-    if (pl.kind != 3) {
-      {
-        StageScope sc(ctx, "knn_gemm");
-        if (pl.kind == 1)
-          SV_TRY(sv_launch_f16_filter(ctx, q16a, ctx->db_f16.as<uint16_t>(), m, (int)ns, d, (int)stride, pl.inv_scale, qn, rn, thr_ptr,
-                                      thr_ld, eps_mult, pl.c_eps, pl.rn_max, ctx->s_cand_cnt.as<uint32_t>(), ctx->s_cand_d2.as<float>(),
-                                      ctx->s_cand_id.as<uint32_t>(), SV_CAP, (last && carry) ? SV_RATIO : 0));
-        else
-          SV_TRY(sv_launch_bf16_filter(ctx, q16a, q16b, ctx->db_hi.as<uint16_t>(), ctx->db_lo.as<uint16_t>(), m, (int)ns, d, (int)stride,
-                                       qn, rn, thr_ptr, thr_ld, eps_mult, pl.c_eps, pl.rn_max, ctx->s_cand_cnt.as<uint32_t>(),
-                                       ctx->s_cand_d2.as<float>(), ctx->s_cand_id.as<uint32_t>(), SV_CAP));
-        sc.count();
-      }
-      if (ctx->opt.debug_search || (ctx->opt.search_stats && last)) {  // candidate-list statistics (synchronises)
-        hcnt.resize(m);
-        SV_HIP(hipStreamSynchronize(ctx->stream));
-        SV_HIP(hipMemcpy(hcnt.data(), ctx->s_cand_cnt.p, (size_t)m * 4, hipMemcpyDeviceToHost));
-        uint64_t tot = 0;
-        uint32_t mx = 0, over = 0;
-        for (uint32_t c : hcnt) {
-          tot += c;
-          if (c > mx) mx = c;
-          if (c > (uint32_t)SV_CAP) ++over;
-        }
-        if (last) {
-          ctx->sstats.cand_sum += (int64_t)tot;
-          if ((int64_t)mx > ctx->sstats.cand_max) ctx->sstats.cand_max = mx;
-        }
-        if (ctx->opt.debug_search)
-          fprintf(stderr, "[search] %s m=%d level %d/%d ns=%lld rank %d: candidates mean %.1f max %u, %u lists over cap %d\n",
-                  heuristic ? "heuristic" : "rigorous", m, lv, levels, (long long)ns, rank[lv], (double)tot / m, mx, over, SV_CAP);
-      }
-      {
-        StageScope sc(ctx, "knn_select");
-        SV_TRY(sv_launch_select_approx(ctx, ctx->s_cand_cnt.as<uint32_t>(), ctx->s_cand_d2.as<float>(), ctx->s_cand_id.as<uint32_t>(), m,
-                                       SV_CAP, rank[lv], last ? 1 : ((carry && lv + 1 == levels) ? 2 : 0), heuristic ? 1 : 0, thr_ptr, thr_ld, qn,
-                                       pl.c_eps, pl.rn_max, thr,
-                                       ctx->s_ref_cnt.as<uint32_t>(), ctx->s_ref_id.as<uint32_t>(), SV_RCAP, fail_rows, fail_count,
-                                       rovf_rows, rovf_count, ref_lim));
-        sc.count();
-        if (last && m > 128) {
-          // batches: bands of 32 consecutive query rows (the segments of an image) over the union of their rows where they
-          // overlap, the rest row by row (refine_group_kernels.hip); same bits either way
-          int nl = 0;
-          SV_TRY(sv_launch_refine_grouped(ctx, qp, R, m, d, qn, rn, ctx->s_ref_cnt.as<uint32_t>(), ctx->s_ref_id.as<uint32_t>(), SV_RCAP,
-                                          k, out_d2, out_idx, &nl));
-          sc.count(nl);
-          if (ctx->opt.search_stats && nl > 1) {
-            int64_t ng = 0, gg = 0, us = 0;
-            SV_TRY(sv_refine_group_stats(ctx, m, &ng, &gg, &us));
-            ctx->sstats.grp_groups += gg;
-            ctx->sstats.grp_union_sum += us;
-          }
-        } else if (last) {
-          // a device-driven pass whose head was small_head_kernel (it repairs a poisoned hand-over buffer): the refinement finishes the
-          // flagged rows itself -- no small_tail_kernel behind it (a kernel boundary of 4-5 us, whatever the kernel does)
-          SvSmallFinish fz;
-          if (tail_stats && ctx->small_head_ran && ctx->opt.small_tail != 2) {
-            fz.on = 1;
-            fz.rovf_rows = rovf_rows;
-            fz.ref_lim = ref_lim;
-            fz.cand_cnt = ctx->s_cand_cnt.as<uint32_t>();
-            fz.cand_d2 = ctx->s_cand_d2.as<float>();
-            fz.cand_id = ctx->s_cand_id.as<uint32_t>();
-            fz.cap = SV_CAP;
-            fz.n_db = n;
-            fz.stats = tail_stats;
-            SV_TRY(sv_launch_small_tail_debug(ctx, m, fail_rows, fail_count, rovf_rows, ref_lim));
-          }
-          SV_TRY(sv_launch_refine_exact(ctx, qp, R, m, d, qn, rn, ctx->s_ref_cnt.as<uint32_t>(), ctx->s_ref_id.as<uint32_t>(), SV_RCAP,
-                                        k, out_d2, out_idx, nullptr, fail_rows, fail_count, &poison_dev, &fz, &tail_fused));
-          sc.count();
-        }
-      }   // (the stage's stop event is recorded before the host waits below)
-      if (last && tail_stats && tail_fused) {
-        if (n_fail_host) *n_fail_host = 0;   // (the refinement kernel has finished its flagged rows itself)
-      } else if (last && tail_stats) {
-        StageScope sc(ctx, "knn_select");
-        SV_TRY(sv_launch_small_tail(ctx, qp, R, qn, rn, n, d, m, k, fail_rows, fail_count, rovf_rows, ref_lim, ctx->s_cand_cnt.as<uint32_t>(),
-                                    ctx->s_cand_d2.as<float>(), ctx->s_cand_id.as<uint32_t>(), SV_CAP, out_d2, out_idx, tail_stats));
-        sc.count();
-        if (n_fail_host) *n_fail_host = 0;
-      } else if (last) {
-        // one read-back per chunk: rows flagged for the redo / matrix-path fallback (handled by the caller) and rows whose
-        // refine band outgrew the first-tier list.  The latter are refined here, straight from their candidate lists,
-        // which the next chunk would overwrite.
-        uint32_t h_cnt[2] = {0, 0}, h_poison = 0;
-        SV_HIP(hipMemcpyAsync(&h_cnt[0], fail_count, 8, hipMemcpyDeviceToHost, ctx->stream));
-        if (poison_dev) SV_HIP(hipMemcpyAsync(&h_poison, poison_dev, 4, hipMemcpyDeviceToHost, ctx->stream));
-        SV_HIP(hipStreamSynchronize(ctx->stream));
-        if (h_poison) SV_TRY(sv_refine_small_repair(ctx));   // a checked hand-over failed (its rows are flagged): fresh buffers
-        if (n_fail_host) *n_fail_host = h_cnt[0];
-        const uint32_t seen = n_rovf_seen ? *n_rovf_seen : 0u;
-        if (n_rovf_seen) *n_rovf_seen = h_cnt[1];
-        h_cnt[1] -= seen;   // the second-tier rows of THIS chunk
-        if (h_cnt[1]) {
-          StageScope sc(ctx, "knn_select");
-          SV_TRY(sv_launch_refine2_compact(ctx, rovf_rows, ref_lim, ctx->s_cand_cnt.as<uint32_t>(), ctx->s_cand_d2.as<float>(),
-                                           ctx->s_cand_id.as<uint32_t>(), m, SV_CAP));
-          if (m > 128 && d > 4096) {   // deep rows: a second-tier list as its own union GEMM (parallel over its 128-row tiles)
-            // In blocks of <= 1024 + 128 query rows: the grouped path's scratch is per ROW of the block it is handed (positions
-            // [rows][8192] u16, keys [rows][2048] u64, ids [rows][2048] u32: 40 KiB per row -- 670 MB for a whole 16 384-row chunk, kept
-            // for the context's life, where a handful of rows are flagged).  Blocks without a flagged row cost four
-            // early-exit launches in a path that is taken once in a blue moon.
-            int nl_sum = 0;
-            for (int r0 = 0; r0 < m;) {
-              int mb = std::min(1024, m - r0);
-              if (m - (r0 + mb) < 129) mb = m - r0;   // (the grouped path wants > 128 rows: the tail joins the last block)
-              int nl = 0;
-              SV_TRY(sv_launch_refine_grouped(ctx, qp + (size_t)r0 * d, R, mb, d, qn + r0, rn, ctx->s_cand_cnt.as<uint32_t>() + r0,
-                                              ctx->s_cand_id.as<uint32_t>() + (size_t)r0 * SV_CAP, SV_CAP, k, out_d2 + (size_t)r0 * k,
-                                              out_idx + (size_t)r0 * k, &nl, rovf_rows + r0, std::min<int>((int)h_cnt[1], mb)));
-              nl_sum += nl;
-              r0 += mb;
-            }
-            sc.count(1 + nl_sum);
-          } else {
-            SV_TRY(sv_launch_refine_exact(ctx, qp, R, m, d, qn, rn, ctx->s_cand_cnt.as<uint32_t>(), ctx->s_cand_id.as<uint32_t>(), SV_CAP,
-                                          k, out_d2, out_idx, rovf_rows));
-            sc.count(2);
-          }
-          ctx->sstats.n_refine2 += h_cnt[1];
-        }
-      }
-      if (last && ctx->opt.search_stats) {
-        hcnt.resize(m);
-        SV_HIP(hipStreamSynchronize(ctx->stream));
-        SV_HIP(hipMemcpy(hcnt.data(), ctx->s_ref_cnt.p, (size_t)m * 4, hipMemcpyDeviceToHost));
-        for (uint32_t c : hcnt) {
-          ctx->sstats.refine_sum += c;
-          if ((int64_t)c > ctx->sstats.refine_max) ctx->sstats.refine_max = c;
-        }
-      }
-      // thresholds now hold approximate rank-th distances A_r: the exact one is <= A_r + eps, and any row at least that
-      // close has d2~ <= A_r + 2 eps
-      thr_ptr = thr;
-      thr_ld = 1;
-      eps_mult = 2.f;
-    } else {
-      {
-        StageScope sc(ctx, "knn_gemm");
-        SV_TRY(sv_launch_l2_filter(ctx, qp, R, m, (int)ns, d, qn, rn, (int)stride, thr_ptr, thr_ld, ctx->s_cand_cnt.as<uint32_t>(),
-                                   ctx->s_cand_d2.as<float>(), ctx->s_cand_id.as<uint32_t>(), SV_CAP));
-        sc.count();
-      }
-      StageScope sc(ctx, "knn_select");
-      // the filter pass has consumed thr; the select may overwrite it with the tighter thresholds
-      SV_TRY(sv_launch_select_cand(ctx, ctx->s_cand_cnt.as<uint32_t>(), ctx->s_cand_d2.as<float>(), ctx->s_cand_id.as<uint32_t>(), m,
-                                   SV_CAP, k, last ? out_d2 : thr, last ? out_idx : nullptr, fail_rows, fail_count));
-      sc.count();
-      thr_ptr = thr + (k - 1);
-      thr_ld = k;
-      if (last && n_fail_host) {
-        SV_HIP(hipMemcpyAsync(n_fail_host, fail_count, 4, hipMemcpyDeviceToHost, ctx->stream));
-        SV_HIP(hipStreamSynchronize(ctx->stream));
-      }
-    }
-  }
-  return SEGVLAD_OK;
-}
-
-// rows flagged in flags[0..nrows) are redone on the exact distance-matrix path; their results replace rows of (d2, idx)
-static int fallback_rows(segvlad_ctx* ctx, const SearchPlan& pl, const float* q, const float* qn, const uint32_t* flags, int nrows,
-                         float* d2, int64_t* idx, int* n_done) {
-  std::vector<uint32_t> hf(nrows);
-  SV_HIP(hipMemcpyAsync(hf.data(), flags, (size_t)nrows * 4, hipMemcpyDeviceToHost, ctx->stream));
-  SV_HIP(hipStreamSynchronize(ctx->stream));
-  std::vector<int32_t> rows;
-  for (int r = 0; r < nrows; ++r)
-    if (hf[r]) rows.push_back(r);
-  const int nf = (int)rows.size();
-  *n_done = nf;
-  if (nf == 0) return SEGVLAD_OK;
-  const int d = pl.d, k = pl.k;
-  SV_HIP(ctx->s_fb_rows.reserve((size_t)nf * 4));
-  SV_HIP(ctx->s_fb_q.reserve((size_t)nf * ((size_t)d + 1) * 4));
-  SV_HIP(ctx->s_fb_d2.reserve((size_t)nf * k * 4));
-  SV_HIP(ctx->s_fb_idx.reserve((size_t)nf * k * 8));
-  SV_HIP(hipMemcpyAsync(ctx->s_fb_rows.p, rows.data(), (size_t)nf * 4, hipMemcpyHostToDevice, ctx->stream));
-  float* fq = ctx->s_fb_q.as<float>();
-  float* fqn = fq + (size_t)nf * d;
-  hipLaunchKernelGGL(gather_rows_kernel, dim3(nf), dim3(256), 0, ctx->stream, q, qn, ctx->s_fb_rows.as<int32_t>(), d, fq, fqn);
-  SV_HIP(hipGetLastError());
-  {
-    StageScope sc(ctx, "knn_fallback");   // one stage (the matrix path's own scopes are muted: no double counting)
-    const bool was_muted = ctx->scope_mute;
-    ctx->scope_mute = true;
-    const int rc = search_matrix(ctx, fq, nf, pl.n, d, k, fqn, ctx->s_fb_d2.as<float>(), ctx->s_fb_idx.as<int64_t>());
-    ctx->scope_mute = was_muted;
-    SV_TRY(rc);
-    sc.count(nf);
-  }
-  hipLaunchKernelGGL(scatter_topk_kernel, dim3(nf), dim3(256), 0, ctx->stream, ctx->s_fb_d2.as<float>(), ctx->s_fb_idx.as<int64_t>(),
-                     ctx->s_fb_rows.as<int32_t>(), k, d2, idx);
-  SV_HIP(hipGetLastError());
-  SV_HIP(hipStreamSynchronize(ctx->stream));  // rows[] lives on this frame
-  return SEGVLAD_OK;
-}
-
-int segvlad_search(segvlad_ctx* ctx, const float* Q, int nq, int k, float* d2_out, int64_t* idx_out) {
-  CHECK_CTX();
-  if (nq < 0 || k < 1 || k > 1024) return ctx->fail(SEGVLAD_ERR_ARG, "search: need nq>=0 and 1<=k<=1024 (k=%d)", k);
-  if (nq == 0) return SEGVLAD_OK;
-  if (!Q || !d2_out || !idx_out) return ctx->fail(SEGVLAD_ERR_ARG, "search: null pointer");
-  if (ctx->db_d == 0) return ctx->fail(SEGVLAD_ERR_STATE, "search: the index is empty and has no dimension yet");
-  if (ctx->opt.debug_fail_search == 1) return ctx->fail(SEGVLAD_ERR_STATE, "search: failing on request (option debug_fail_search)");
-  const int d = ctx->db_d;
-  const int64_t n = ctx->db_n;
-  ctx->f16_scale_dev = nullptr;
-  const void* dq;
-  void *dd2, *didx;
-  SV_TRY(sv_in(ctx, Q, (size_t)nq * d * 4, &dq));
-  SV_TRY(sv_out(ctx, d2_out, (size_t)nq * k * 4, &dd2));
-  SV_TRY(sv_out(ctx, idx_out, (size_t)nq * k * 8, &didx));
-  SV_HIP(ctx->s_qnorm.reserve((size_t)nq * 4));
-  const float* qn = ctx->s_qnorm.as<float>();
-  // the queries' squared norms: a launch of their own -- except on the single-image fp16 path, whose query-preparation kernel
-  // computes them too (one dependent launch less in a pass that is a chain of them)
-  bool qn_done = false;
-  auto ensure_qn = [&]() -> int {
-    if (!qn_done) SV_TRY(sv_launch_row_sumsq(ctx, (const float*)dq, nq, d, ctx->s_qnorm.as<float>()));
-    qn_done = true;
-    return SEGVLAD_OK;
-  };
-  ctx->sstats = SvSearchStats();
-  ctx->sstats.n_queries = nq;
-  ctx->tail_stats_dev = nullptr;
-  ctx->small_head_ran = false;
-  // device-driven single-image passes never tell the host how many rows they had to redo -- but their running total lands in a
-  // pinned word (small_tail_kernel): looked at here WITHOUT synchronising (it may be a pass or two behind).  More than a quarter
-  // of >= 64 rows redone since the index last changed: the sample misleads on this database, stop guessing (as the read-back path
-  // decides below for its own redos).
-  if (ctx->h_pin && ctx->tail_rows_since >= 64) {
-    const uint32_t redone = reinterpret_cast<volatile uint32_t*>(ctx->h_pin)[8] - ctx->tail_fail_base;
-    if ((int64_t)redone * 4 > ctx->tail_rows_since) ctx->db_heur_off = true;
-  }
-
-  // level plan: strides 16^L, ..., 16, 1.  The coarsest sample goes through the exact fp32 matrix path (an order of
-  // magnitude dearer per row than the fp16 filter), so take as many levels as keep it selective: a sample of s rows
-  // admits a fraction k/s of the next level, which must stay below the filter's per-wave list capacity (25 % of a
-  // block) -> s >= 4.8 k.  Databases of <= 32768 rows keep the plain matrix path; the sample never exceeds 32768 rows.
-  // (Row shards of 250 k - 500 k rows -- the 1 M-row database on 2 or 4 GPUs -- get two levels instead of a 15 k - 31 k
-  // row exact level.)
-  SearchPlan pl;
-  pl.d = d;
-  pl.k = k;
-  pl.n = n;
-  if (n > 32768) {
-    const int64_t want = std::max<int64_t>((24 * (int64_t)k + 4) / 5, 512);
-    while (n / (pl.stride0 * SV_RATIO) >= want) {
-      pl.stride0 *= SV_RATIO;
-      ++pl.levels;
-    }
-    while (n / pl.stride0 > 32768) {
-      pl.stride0 *= SV_RATIO;
-      ++pl.levels;
-    }
-  }
-  if (pl.levels == 0 || n / pl.stride0 < 4 * (int64_t)k) {
-    SV_TRY(ensure_qn());
-    SV_TRY(search_matrix(ctx, (const float*)dq, nq, n, d, k, qn, (float*)dd2, (int64_t*)didx));
-    return sv_finish(ctx);
-  }
-  const float* R = ctx->db_rows.as<float>();
-  const float* rn = ctx->db_norms.as<float>();
-  // filter arithmetic (ctx->opt.knn_filter, see SvOptions): "f16" = one fp16 product (d % 64 == 0), "bf16x3" = three
-  // bf16 products (d % 32 == 0), else plain fp32
-  const int want_f = ctx->opt.knn_filter;
-  const bool f16_path = (want_f == 0 || want_f == 1) && (d % 64 == 0);
-  const bool bf16_path = !f16_path && want_f != 3 && (d % 32 == 0);
-  pl.kind = f16_path ? 1 : bf16_path ? 2 : 3;
-  ctx->sstats.filter = pl.kind;
-  // The low-rank ("heuristic") thresholds need only a few dozen sample rows per rank, so their plan goes deeper: the
-  // exact fp32 level (an order of magnitude dearer per row than a filter level) shrinks to >= 192 rows -- 1 M rows:
-  // strides 4096, 256, 16, 1 instead of 256, 16, 1 (0.9 ms of exact GEMM per 10 000 queries -> 0.06 ms); a 125 k-row
-  // shard: 256, 16, 1 instead of 16, 1 (1.35 -> 0.1 ms).  The rigorous redo keeps the plan above.
-  const bool heuristic = pl.kind != 3 && ctx->opt.knn_heuristic && !ctx->db_heur_off && heur_rank(k) < k;
-  SearchPlan plh = pl;
-  // One query image per pass (<= 128 rows) is bound by its chain of dependent launches, not by the exact level's flops
-  // (option small_plan): ONE filter level behind an exact sample of 2048..4096 rows (stride = the power of two that gives
-  // it: 256 for 1 M rows, 64 for a 250 k-row shard).  The threshold is a low rank of that sample (heur_rank_small: ~7 at
-  // stride 256), the full level collects stride x rank candidates per query (~1800 + the margin's ~900 at 1 M rows: a
-  // workgroup select's worth, SV_CAP bounds it -- hence stride <= 512), and the deeper plan's two sampled filter launches
-  // with their selects (~90 us of a ~500 us pass) are gone.  (The same last step for batches -- strides 4096, 256, 1 instead
-  // of 4096, 256, 16, 1 -- was measured and dropped: the stride-16 level's 1.3 ms come back as epilogue time of the full
-  // level, which then collects 2900 candidates per query instead of 780, and as 0.2 ms of longer selects.)
-  int small_stride = 16;
-  while ((n + small_stride - 1) / small_stride > 4096 && small_stride <= 512) small_stride *= 2;
-  bool small_taken = false;
-  if (heuristic && nq <= 128 && ctx->opt.small_plan && small_stride <= 512) {
-    small_taken = true;
-    plh.levels = 1;
-    plh.stride0 = small_stride;
-    plh.ratio_last = small_stride;
-  } else if (heuristic) {
-    while (plh.levels < 6 && n / (plh.stride0 * SV_RATIO) >= 192) {
-      plh.stride0 *= SV_RATIO;
-      ++plh.levels;
-    }
-  }
-  ctx->sstats.levels = plh.levels;
-  auto grow = [&](DevBuf& b, size_t old_bytes, size_t new_bytes) -> hipError_t {
-    if (new_bytes <= b.cap) return hipSuccess;
-    DevBuf nb;
-    nb.tag = b.tag;
-    nb.guard = b.guard;
-    nb.fixed = b.fixed;
-    hipError_t e = nb.reserve(new_bytes + new_bytes / 4);
-    if (e != hipSuccess) return e;
-    if (old_bytes) {
-      e = hipMemcpyAsync(nb.p, b.p, old_bytes, hipMemcpyDeviceToDevice, ctx->stream);
-      if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-      if (e != hipSuccess) return e;
-    }
-    b.release();
-    b = nb;
-    return hipSuccess;
-  };
-  // power-of-two scales that put the largest magnitude in [8192, 16384): no overflow, negligible underflow
-  auto pow2_scale = [](float maxabs) -> float {
-    if (!(maxabs > 0.f) || !std::isfinite(maxabs)) return 1.f;
-    int e;
-    frexpf(maxabs, &e);  // maxabs = m * 2^e, m in [0.5, 1)
-    return ldexpf(1.f, 14 - e);
-  };
-  float qscale = 1.f;
-  // per-query scratch is sized for the rows of one chunk -- min(nq, SV_CHUNK), not SV_CHUNK: a one-image search on a large
-  // index used to allocate > 1 GiB of candidate lists (the buffers only ever grow, so a later large batch re-allocates once)
-  const size_t mrows = (size_t)std::min(nq, SV_CHUNK);
-  // flag block: [nq] row flags, 2 counts (flagged, second-tier), [mrows] second-tier flags of the current chunk -- one fill
-  // (+ 4 words behind them: the device-driven tail's counters of this search)
-  const size_t ovf_bytes = (((size_t)nq + 2 + mrows + 4) * 4 + 255) & ~(size_t)255;   // (a whole number of 256-byte blocks: one fill kernel)
-  bool ovf_zeroed = false;
-  // the per-chunk scratch and the flag block, reserved (and the flags zeroed) once -- by the early exact level of a batch
-  // search (below) or in front of the chunk loop
-  bool scratch_ready = false, level0_done = false;
-  const bool heuristic_pre = heuristic;
-  SearchPlan plh_pre = plh;
-  auto reserve_scratch = [&]() -> int {
-    if (scratch_ready) return SEGVLAD_OK;
-    SV_HIP(ctx->s_cand_cnt.reserve(mrows * 4));
-    SV_HIP(ctx->s_cand_d2.reserve(mrows * SV_CAP * 4));
-    SV_HIP(ctx->s_cand_id.reserve(mrows * SV_CAP * 4));
-    SV_HIP(ctx->s_thr_d2.reserve(mrows * k * 4));
-    SV_HIP(ctx->s_thr_idx.reserve(mrows * k * 8));
-    // the exact level's distance block: the larger of the two plans' samples (the single-image plan's stride can be SMALLER than
-    // the rigorous plan's: 64 against 256 for a 250 k-row shard)
-    const int64_t stride_min = heuristic ? std::min(pl.stride0, plh.stride0) : pl.stride0;
-    const int64_t n0 = (n + stride_min - 1) / stride_min;
-    SV_HIP(ctx->s_dist.reserve(mrows * ((n0 + 3) & ~3ll) * 4));
-    // layout: [nq] row flags, 2 counts (flagged, second-tier), [mrows] second-tier flags of the current chunk -- one memset
-    SV_HIP(ctx->s_ovf.reserve(ovf_bytes));
-    if (!ovf_zeroed) SV_HIP(hipMemsetAsync(ctx->s_ovf.p, 0, ovf_bytes, ctx->stream));
-    ovf_zeroed = true;
-    scratch_ready = true;
-    return SEGVLAD_OK;
-  };
-  if (f16_path || bf16_path) {
-    if (ctx->db_rn_max_rows < n) {
-      float m = 0.f;
-      SV_TRY(sv_row_norm_max(ctx, rn + ctx->db_rn_max_rows, n - ctx->db_rn_max_rows, &m));
-      if (m > ctx->db_rn_max) ctx->db_rn_max = m;
-      ctx->db_rn_max_rows = n;
-    }
-    pl.rn_max = ctx->db_rn_max;
-    SV_HIP(ctx->s_ref_cnt.reserve((size_t)mrows * 4));
-    SV_HIP(ctx->s_ref_id.reserve((size_t)mrows * SV_RCAP * 4));
-  }
-  if (f16_path) {
-    if (ctx->db_f16_rows < n) {
-      float m_new = 0.f;
-      SV_TRY(sv_maxabs(ctx, R + (size_t)ctx->db_f16_rows * d, (n - ctx->db_f16_rows) * d, &m_new));
-      const bool rescale = ctx->db_f16_rows == 0 || m_new * ctx->db_f16_scale >= 32768.f;
-      if (m_new > ctx->db_maxabs) ctx->db_maxabs = m_new;
-      int64_t r0 = ctx->db_f16_rows;
-      if (rescale) {
-        ctx->db_f16_scale = pow2_scale(ctx->db_maxabs);
-        r0 = 0;
-      }
-      SV_HIP(grow(ctx->db_f16, (size_t)r0 * d * 2, (size_t)n * d * 2));
-      SV_TRY(sv_launch_to_f16(ctx, R + (size_t)r0 * d, (n - r0) * d, ctx->db_f16_scale, ctx->db_f16.as<uint16_t>() + (size_t)r0 * d));
-      ctx->db_f16_rows = n;
-    }
-    SV_HIP(ctx->s_qf16.reserve((size_t)nq * d * 2));
-    // batches on the default configuration take the biased-accumulator kernel when the norms allow it (below): min ||q||^2
-    const bool want_q2min = nq > 128 && (ctx->opt.f16_cfg < 0 || ctx->opt.f16_cfg == 250 || ctx->opt.f16_cfg == 300);
-    float q2min_pre = 0.f;
-    bool have_q2min = false;
-    if (nq <= 128 && (((int64_t)nq * d) & 3) == 0 && (int64_t)nq * d <= (1 << 18)) {
-      // one query image per pass: the scale is computed AND consumed on the device (a host round trip in front of every pass
-      // was ~45 us of a ~600 us call).  One workgroup reads the block twice: up to 1 MiB of queries (128 x 2048 floats);
-      // deeper rows (raw K*D descriptors) keep the many-workgroup kernels and their read-back.
-      SV_HIP(ctx->s_qscale.reserve(16));
-      const bool fuse_qn = !qn_done && (reinterpret_cast<uintptr_t>(dq) & 15) == 0;   // (d % 64 == 0 on this path)
-      SV_HIP(ctx->s_ovf.reserve(ovf_bytes));
-      // round 6: the whole head of a single-image pass in ONE launch (small_pass_kernels.hip) -- plane, scale, norms, flags AND the
-      // sample thresholds (from the filter's own fp16 product on the strided sample: the thresholds are guesses the pass verifies,
-      // they need no exact distances) -- instead of query preparation -> exact sample GEMM -> reduce + rank (three dependent launches)
-      const int64_t n0_small = (n + small_stride - 1) / small_stride;
-      const int r0_small = std::min(k, small_stride == SV_RATIO ? heur_rank(k) : heur_rank_small(k, small_stride, plh.pfail));   // (levels_chunk's rank[0])
-      if (small_taken && fuse_qn && ctx->opt.small_head && ctx->opt.debug_search == 0 && n0_small <= 4096 &&
-          sv_small_head_ok(nq, d, (int)n0_small, r0_small)) {
-        ovf_zeroed = true;
-        SV_TRY(reserve_scratch());
-        StageScope sc(ctx, "knn_level0");
-        SV_TRY(sv_launch_small_head(ctx, (const float*)dq, nq, d, ctx->db_f16.as<uint16_t>(), rn, small_stride, (int)n0_small,
-                                    ctx->db_f16_scale, r0_small, ctx->s_qf16.as<uint16_t>(), ctx->s_qscale.as<float>(),
-                                    ctx->s_qnorm.as<float>(), ctx->s_ovf.as<uint32_t>(), (int)(ovf_bytes / 4), ctx->s_dist.as<float>(),
-                                    ctx->s_thr_d2.as<float>(), ctx->s_cand_cnt.as<uint32_t>()));
-        sc.count();
-        level0_done = true;
-      } else {
-      SV_TRY(sv_launch_query_f16_small(ctx, (const float*)dq, (int64_t)nq * d, ctx->db_f16_scale, ctx->s_qf16.as<uint16_t>(),
-                                       ctx->s_qscale.as<float>(), fuse_qn ? ctx->s_qnorm.as<float>() : nullptr, nq, d,
-                                       ctx->s_ovf.as<uint32_t>(), (int)(ovf_bytes / 4)));
-      }
-      ovf_zeroed = true;   // (the flag block of this search: no fill launch of its own in front of the pass)
-      if (fuse_qn) qn_done = true;
-      ctx->f16_scale_dev = ctx->s_qscale.as<float>();
-      pl.inv_scale = 0.f;   // (unused: the kernels read s_qscale[1])
-    } else {
-      SV_TRY(ensure_qn());
-      float qmax = 0.f;
-      if (want_q2min) {   // both scalars behind one read-back
-        SV_TRY(sv_maxabs_and_norm_min_begin(ctx, (const float*)dq, (int64_t)nq * d, qn, nq));
-        // the exact sample level of the first chunk goes out BEFORE the host waits for the two scalars: it needs neither the
-        // query plane nor the margin they fix, and the device runs it while the host round trip is under way (round 5; the
-        // wait used to leave the device idle in front of every batch search)
-        // (not when the sampled level runs on the fp16 product -- batch_l0_f16: that needs the query plane the scalars fix; it is
-        //  ten times cheaper than the exact GEMM it replaces, which is worth more than hiding that GEMM under the host's wait)
-        const int64_t n0_pre = (n + plh_pre.stride0 - 1) / plh_pre.stride0;
-        const bool l0_f16 = ctx->opt.batch_l0_f16 && n0_pre <= 4096;
-        if (heuristic_pre && nq > 128 && ctx->opt.debug_search == 0 && !l0_f16) {
-          SV_TRY(reserve_scratch());
-          SV_TRY(levels_chunk(ctx, plh_pre, true, (const float*)dq, nullptr, nullptr, qn, std::min(nq, SV_CHUNK), nullptr, nullptr,
-                              ctx->s_ovf.as<uint32_t>(), ctx->s_ovf.as<uint32_t>() + nq, nullptr, nullptr, nullptr, 1));
-          level0_done = true;
-        }
-        SV_TRY(sv_maxabs_and_norm_min_end(ctx, (int64_t)nq * d, nq, &qmax, &q2min_pre));
-        have_q2min = true;
-      } else {
-        SV_TRY(sv_maxabs(ctx, (const float*)dq, (int64_t)nq * d, &qmax));
-      }
-      qscale = pow2_scale(qmax);
-      SV_TRY(sv_launch_to_f16(ctx, (const float*)dq, (int64_t)nq * d, qscale, ctx->s_qf16.as<uint16_t>()));
-      pl.inv_scale = 1.f / (qscale * ctx->db_f16_scale);
-    }
-    // |d2~ - d2| <= c_eps ||q|| ||r||: ctx.h, sv_f16_c_eps (the constant of the kernel variant that will run).  Batches
-    // (> 128 queries, default configuration) take the biased-accumulator kernel when the norms are balanced enough for
-    // its margin: bias_mult = 1 + max||r|| / (2 min||q||), 1.5 for unit vectors
-    float bias_mult = 1.f;
-    ctx->f16_bias_ok = false;
-    if (want_q2min) {   // (deep rows too: round 4)
-      float q2min = q2min_pre;
-      if (!have_q2min) SV_TRY(sv_row_norm_min(ctx, qn, nq, &q2min));
-      if (q2min > 0.f && pl.rn_max > 0.f) {
-        const float bm = 1.f + std::sqrt(pl.rn_max) / (2.f * std::sqrt(q2min));
-        if (std::isfinite(bm) && bm <= 5.f) {
-          bias_mult = bm;
-          ctx->f16_bias_ok = true;
-        }
-      }
-    }
-    pl.c_eps = sv_f16_c_eps(d, sv_f16_eps_kblock(ctx->opt, d), bias_mult);
-  } else if (bf16_path) {
-    // lazily extend the bf16 planes to the rows added since the last search
-    if (ctx->db_split_rows < n) {
-      SV_HIP(grow(ctx->db_hi, (size_t)ctx->db_split_rows * d * 2, (size_t)n * d * 2));
-      SV_HIP(grow(ctx->db_lo, (size_t)ctx->db_split_rows * d * 2, (size_t)n * d * 2));
-      const int64_t r0 = ctx->db_split_rows;
-      SV_TRY(sv_launch_split_bf16(ctx, R + (size_t)r0 * d, (n - r0) * d, ctx->db_hi.as<uint16_t>() + (size_t)r0 * d,
-                                  ctx->db_lo.as<uint16_t>() + (size_t)r0 * d));
-      ctx->db_split_rows = n;
-    }
-    // |d2~ - d2| <= 2 * (3*2^-16 + 4*d*2^-24) * ||q|| * ||r||   (+25 % slack)
-    pl.c_eps = 2.5f * (3.f / 65536.f + 4.f * (float)d / 16777216.f);
-    SV_HIP(ctx->s_qh.reserve((size_t)nq * d * 2));
-    SV_HIP(ctx->s_ql.reserve((size_t)nq * d * 2));
-    SV_TRY(sv_launch_split_bf16(ctx, (const float*)dq, (int64_t)nq * d, ctx->s_qh.as<uint16_t>(), ctx->s_ql.as<uint16_t>()));
-  }
-  SV_TRY(ensure_qn());   // (every path that has not produced the norms on its way)
-  if (ovf_zeroed && !scratch_ready) {   // (the single-image query preparation zeroed the flag block in its own launch)
-    SV_HIP(ctx->s_ovf.reserve(ovf_bytes));
-  }
-  SV_TRY(reserve_scratch());
-  // Flags: [nq] rows + 1 count.  A heuristic pass flags the queries whose low-rank thresholds did not verify (-> redo
-  // with the rigorous thresholds, below); a rigorous pass flags list overflows (-> exact distance-matrix path, alone).
-  plh.c_eps = pl.c_eps;
-  plh.inv_scale = pl.inv_scale;
-  plh.rn_max = pl.rn_max;
-  uint32_t* flag_rows = ctx->s_ovf.as<uint32_t>();
-  uint32_t* flag_count = flag_rows + nq;
-  uint32_t* rovf_flags = flag_count + 2;
-  uint32_t n_rovf_seen = 0;
-  auto plane_a = [&](const DevBuf& f16, const DevBuf& hi, int64_t q0) -> const uint16_t* {
-    return (pl.kind == 1 ? reinterpret_cast<const uint16_t*>(f16.p) : reinterpret_cast<const uint16_t*>(hi.p)) + (size_t)q0 * d;
-  };
-  uint32_t n_flag = 0;   // running count of the flagged rows, read back by every chunk (levels_chunk synchronises once)
-  // one query image per pass on the single-image plan with the scale on the device: the pass ends in small_tail_kernel instead of
-  // a read-back (option small_tail = 0: the round-5 path, for A/B and for the tests that compare the two)
-  uint32_t* tail_stats = nullptr;
-  if (small_taken && pl.kind == 1 && ctx->f16_scale_dev && ctx->opt.small_tail &&
-      ctx->opt.debug_search == 0 && n <= 0xffffffffLL)
-    tail_stats = rovf_flags + mrows;
-  for (int q0 = 0; q0 < nq; q0 += SV_CHUNK) {
-    const int m = (nq - q0 < SV_CHUNK) ? (nq - q0) : SV_CHUNK;
-    if (q0) SV_HIP(hipMemsetAsync(rovf_flags, 0, (size_t)m * 4, ctx->stream));
-    SV_TRY(levels_chunk(ctx, heuristic ? plh : pl, heuristic, (const float*)dq + (size_t)q0 * d,
-                        pl.kind == 3 ? nullptr : plane_a(ctx->s_qf16, ctx->s_qh, q0),
-                        pl.kind == 2 ? ctx->s_ql.as<uint16_t>() + (size_t)q0 * d : nullptr, qn + q0, m, (float*)dd2 + (size_t)q0 * k,
-                        (int64_t*)didx + (size_t)q0 * k, flag_rows + q0, flag_count, rovf_flags, &n_flag, &n_rovf_seen,
-                        (q0 == 0 && level0_done) ? 2 : 0, tail_stats));
-  }
-  if (tail_stats) {
-    ctx->tail_stats_dev = tail_stats;
-    ctx->tail_rows_since += nq;
-  }
-  if (n_flag && !heuristic) {
-    int nf = 0;
-    SV_TRY(fallback_rows(ctx, pl, (const float*)dq, qn, flag_rows, nq, (float*)dd2, (int64_t*)didx, &nf));
-    ctx->sstats.n_fallback = nf;
-  } else if (n_flag) {
-    // ---- redo of the flagged queries with the rigorous thresholds, as one dense batch ---------------------------------
-    std::vector<uint32_t> hf(nq);
-    SV_HIP(hipMemcpy(hf.data(), flag_rows, (size_t)nq * 4, hipMemcpyDeviceToHost));
-    std::vector<int32_t> rows;
-    for (int q = 0; q < nq; ++q)
-      if (hf[q]) rows.push_back(q);
-    const int nr = (int)rows.size();
-    ctx->sstats.n_redo = nr;
-    if ((int64_t)nr * 4 > nq && nq >= 64) ctx->db_heur_off = true;   // the sample misleads on this database: stop guessing
-    SV_HIP(ctx->s_rd_rows.reserve((size_t)nr * 4));
-    SV_HIP(ctx->s_rd_q.reserve((size_t)nr * ((size_t)d + 1) * 4));
-    SV_HIP(ctx->s_rd_d2.reserve((size_t)nr * k * 4));
-    SV_HIP(ctx->s_rd_idx.reserve((size_t)nr * k * 8));
-    const size_t rd_m = (size_t)std::min(nr, SV_CHUNK);
-    SV_HIP(ctx->s_rd_flags.reserve(((size_t)nr + 2 + rd_m) * 4));   // (same layout as s_ovf, without the tail's counters)
-    SV_HIP(hipMemsetAsync(ctx->s_rd_flags.p, 0, ((size_t)nr + 2 + rd_m) * 4, ctx->stream));
-    SV_HIP(hipMemcpyAsync(ctx->s_rd_rows.p, rows.data(), (size_t)nr * 4, hipMemcpyHostToDevice, ctx->stream));
-    float* rq = ctx->s_rd_q.as<float>();
-    float* rqn = rq + (size_t)nr * d;
-    hipLaunchKernelGGL(gather_rows_kernel, dim3(nr), dim3(256), 0, ctx->stream, (const float*)dq, qn, ctx->s_rd_rows.as<int32_t>(), d, rq,
-                       rqn);
-    SV_HIP(hipGetLastError());
-    SV_HIP(ctx->s_rd_p1.reserve((size_t)nr * d * 2));
-    if (pl.kind == 1) {
-      if (ctx->f16_scale_dev)   // same scale as the main pass
-        SV_TRY(sv_launch_to_f16_devscale(ctx, rq, (int64_t)nr * d, ctx->f16_scale_dev, ctx->s_rd_p1.as<uint16_t>()));
-      else
-        SV_TRY(sv_launch_to_f16(ctx, rq, (int64_t)nr * d, qscale, ctx->s_rd_p1.as<uint16_t>()));
-    } else {
-      SV_HIP(ctx->s_rd_p2.reserve((size_t)nr * d * 2));
-      SV_TRY(sv_launch_split_bf16(ctx, rq, (int64_t)nr * d, ctx->s_rd_p1.as<uint16_t>(), ctx->s_rd_p2.as<uint16_t>()));
-    }
-    uint32_t* rflags = ctx->s_rd_flags.as<uint32_t>();
-    uint32_t n_ovf = 0, rd_rovf_seen = 0;
-    for (int q0 = 0; q0 < nr; q0 += SV_CHUNK) {
-      const int m = (nr - q0 < SV_CHUNK) ? (nr - q0) : SV_CHUNK;
-      if (q0) SV_HIP(hipMemsetAsync(rflags + nr + 2, 0, (size_t)m * 4, ctx->stream));
-      StageScope sc(ctx, "knn_redo");   // the whole redo is ONE stage: its inner level / filter / select scopes are muted,
-      ctx->scope_mute = true;           // so "knn_gemm" etc. keep describing the main pass only (no double counting)
-      const int rc = levels_chunk(ctx, pl, false, rq + (size_t)q0 * d, ctx->s_rd_p1.as<uint16_t>() + (size_t)q0 * d,
-                                  pl.kind == 2 ? ctx->s_rd_p2.as<uint16_t>() + (size_t)q0 * d : nullptr, rqn + q0, m,
-                                  ctx->s_rd_d2.as<float>() + (size_t)q0 * k, ctx->s_rd_idx.as<int64_t>() + (size_t)q0 * k, rflags + q0,
-                                  rflags + nr, rflags + nr + 2, &n_ovf, &rd_rovf_seen);
-      ctx->scope_mute = false;
-      SV_TRY(rc);
-      sc.count(m);
-    }
-    SV_HIP(hipStreamSynchronize(ctx->stream));   // rows[] lives on this frame
-    if (n_ovf) {
-      int nf = 0;
-      SV_TRY(fallback_rows(ctx, pl, rq, rqn, rflags, nr, ctx->s_rd_d2.as<float>(), ctx->s_rd_idx.as<int64_t>(), &nf));
-      ctx->sstats.n_fallback = nf;
-    }
-    hipLaunchKernelGGL(scatter_topk_kernel, dim3(nr), dim3(256), 0, ctx->stream, ctx->s_rd_d2.as<float>(), ctx->s_rd_idx.as<int64_t>(),
-                       ctx->s_rd_rows.as<int32_t>(), k, (float*)dd2, (int64_t*)didx);
-    SV_HIP(hipGetLastError());
-  }
   return sv_finish(ctx);
 }
 

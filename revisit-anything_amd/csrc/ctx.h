@@ -176,7 +176,7 @@ struct SvOptions {
                           // launch); 0 = query preparation -> exact sample level -> reduce + rank (rounds 3-5)
   int small_tail = 1;     // single-image passes end in small_tail_kernel (no read-back); 0 = the read-back of rounds 3-5
   int small_plan = 1;     // <= 128 queries (one query image per pass): one filter level behind an exact sample of 2048..4096
-                          // rows (see segvlad_search); 0 = the deep plan of the batches
+                          // rows (see plan_search, search.hip); 0 = the deep plan of the batches
   int pj_f16 = 1;         // P-space aggregation: the tile sums on the 16-bit matrix pipe (0: fp32 MFMA, as before round 4)
   int pj_nw = 8;          // waves (32-column slices) per workgroup of the P-space aggregation: 8, or 4 (three workgroups per
                           // CU instead of one: measured SLOWER, 3.72 vs 3.40 ms for the PCA stage of 200 images)
@@ -214,7 +214,7 @@ inline int sv_f16_eps_kblock(const SvOptions& o, int d) {
 //                relative to the largest running magnitude: sum_i |q_i r_i| <= ||q|| ||r||.  The batch kernels' BIAS starts
 //                the accumulators at -||r||^2 / 2, so the running magnitude is <= ||q|| ||r|| + ||r||^2 / 2
 //                <= bias_mult ||q|| max||r|| with bias_mult = 1 + max||r|| / (2 min||q||) over the query batch (1.5 for unit
-//                vectors; segvlad_search measures it and keeps the unbiased kernel when it exceeds 5); bias_mult = 1 without;
+//                vectors; prepare_queries (search.hip) measures it and keeps the unbiased kernel when it exceeds 5); bias_mult = 1 without;
 // the factor 2 turns the error of the dot product into that of d2.
 inline float sv_f16_c_eps(int d, int kb, float bias_mult) {
   const float acc = kb > 0 ? (2.f * (float)kb + (float)((d + kb - 1) / kb) + 1.f) / 16777216.f : 2.f * (float)d / 16777216.f;
@@ -365,6 +365,10 @@ int sv_guard_check(segvlad_ctx* ctx);
 int sv_fork_side(segvlad_ctx* ctx);   // side stream waits for everything enqueued on `stream` so far
 int sv_join_side(segvlad_ctx* ctx);   // `stream` waits for everything enqueued on the side stream so far
 void sv_begin(segvlad_ctx* ctx);
+// first line of every entry point that takes a context
+#define CHECK_CTX()                 \
+  if (!ctx) return SEGVLAD_ERR_ARG; \
+  sv_begin(ctx)
 
 struct StageScope {
   segvlad_ctx* ctx;

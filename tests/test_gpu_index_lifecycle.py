@@ -88,7 +88,7 @@ def _check_against_fresh(R, Qs, got, k=K, opts=None, emulate=True, single_levels
 
 
 # Growth across the single-image plan's stride and grid changes.  small_stride = the smallest power of two >= 16 that leaves
-# n0 = ceil(n / stride) <= 4096 sample rows, and small_head_kernel's grid NW = ceil(n0 / 32) (csrc/api.hip, small_pass_kernels.hip):
+# n0 = ceil(n / stride) <= 4096 sample rows, and small_head_kernel's grid NW = ceil(n0 / 32) (csrc/search.hip, small_pass_kernels.hip):
 #        80 000 rows: stride  32, n0 2500, NW  79
 #       100 000 rows: stride  32, n0 3125, NW  98
 #       140 000 rows: stride  64, n0 2188, NW  69

@@ -1,5 +1,5 @@
 """NumPy model of the mixed-precision leveled search: real fp16 operand rounding, fp32 accumulation,
-the margins and threshold rules of csrc/api.hip -- and the claim that the refined result equals the exact fp32 top-k.
+the margins and threshold rules of csrc/search.hip -- and the claim that the refined result equals the exact fp32 top-k.
 This checks the MATH on the CPU (the kernels themselves are checked bit for bit in tests/test_gpu_parity.py)."""
 import numpy as np
 import pytest
@@ -130,7 +130,7 @@ def test_two_term_fp16_split_projection_is_fp32_class():
 
 
 def heur_rank_small(target, ratio):
-    """csrc/api.hip: heur_rank_small -- the smallest r >= 2 with P[Gamma(r, 1) < target / ratio] < 2e-5."""
+    """csrc/search.hip: heur_rank_small -- the smallest r >= 2 with P[Gamma(r, 1) < target / ratio] < 2e-5."""
     import math
 
     x = target / ratio

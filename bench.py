@@ -14,6 +14,12 @@ x 50 = 1 M segments.  The DB is built (untimed) by the same VLAD+PCA kernels fro
 images; queries are perturbed copies of reference images so Recall@1 is meaningful.
 
   python bench.py --gpus N --steps K --warmup W          (N>1: launched by torch.distributed.run)
+  python bench.py --full ...                               (the same line with everything else it can carry)
+
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the line: the headline, the stage timers of
+the timed steps and the rooflines priced on them.  --full adds what takes runs of its own: the CPU baseline and the fp64
+oracle check, the sub-records (other filters, workloads and timing modes), the single-image searches, the micro-benchmark
+and the GEMM yardstick.
 
 Prints ONE JSON line on rank 0.  Strong scaling: the 1 M-segment DB and the 200-image query batch
 are fixed; rank r holds DB rows of reference images [r*n/N, (r+1)*n/N) and describes query images
@@ -165,6 +171,11 @@ def parse():
     p.add_argument("--pca-dim", type=int, default=1024)
     p.add_argument("--order", type=int, default=3)
     p.add_argument("--no-pca", action="store_true", help="raw K*D descriptors (only with a small --db-images)")
+    p.add_argument("--full", action="store_true", help="besides the headline, everything else the line can carry: the CPU baseline "
+                   "and its oracle check, the sub-records (pipelined, fp32_filter, config2, redundant_db, vote_depth, "
+                   "config2_vote_depth, shard_sim), the back-to-back and single-image searches, the MFMA micro-benchmark and the "
+                   "GEMM yardstick; the --no-* switches below and --shard-sim then pick among them.  Without it a run sets up, "
+                   "warms up, times the steps, writes --dump-outputs and prints the line")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--build-batch", type=int, default=100)
     p.add_argument("--dist-backend", default="nccl", help="torch.distributed backend (nccl = RCCL over xGMI); 'gloo' + "
@@ -182,7 +193,7 @@ def parse():
     p.add_argument("--sweep-own", default=None, help="debug: comma-separated --query-own values; after the DB build print the device "
                    "Recall@1 for each (stderr) and exit")
     p.add_argument("--verify-images", type=int, default=20, help="query images re-computed by the CPU oracle (fp64) and compared "
-                   "with the device's predictions (N=1 only; part of the cpu_baseline leg)")
+                   "with the device's predictions (--full, N=1 only; part of the cpu_baseline leg)")
     p.add_argument("--debug-timing", action="store_true", help="after the timed region, print a synchronised per-phase wall-clock breakdown of one step to stderr")
     p.add_argument("--group", type=int, default=4, help="reference images per 'same place' sibling group (4 = the headline workload; 31 = a "
                    "17places-like video sequence, gt.py:60-64: every frame has its +-15 neighbours as near-duplicates)")
@@ -203,10 +214,16 @@ def parse():
                    "(sharded.dry_run_collectives: operand shapes / dtypes / contiguity of both collectives and the unpack + merge for world "
                    "sizes 2..8 against a single index, the real collectives + the C-ABI communicator at world size 1 on the nccl backend); "
                    "prints a JSON report and exits non-zero on a violation")
-    p.add_argument("--shard-sim", type=int, default=8, help="N=1 line: emulate ONE rank of a row-sharded run over this many GPUs on the one "
+    p.add_argument("--shard-sim", type=int, default=8, help="--full N=1 line: emulate ONE rank of a row-sharded run over this many GPUs on the one "
                    "GPU (a 1/W shard of the database, ALL query segments searched k_vote deep, 1/W of the query images described, the "
                    "W-way merge and the vote; no collective) -> the 'shard_sim' sub-record; 0 = skip")
-    return p.parse_args()
+    a = p.parse_args()
+    if a.shard_sim_only and not a.full:
+        p.error("--shard-sim-only picks among the --full measurements: add --full")
+    if not a.full:   # a plain run: only what the headline needs
+        a.no_cpu_baseline = a.no_sub_records = a.no_ubench = True
+        a.shard_sim = 0
+    return a
 
 
 # ------------------------------------------------------------------------------------------------
@@ -589,7 +606,7 @@ def run(a, top=True):
             except Exception:
                 pass
     b2b = None
-    if top and world == 1 and not a.sweep_own:
+    if a.full and top and world == 1 and not a.sweep_own:
         # the same searches back to back, without a describe stage in between (a diagnostic: the filter kernel is power
         # limited, and what runs before it -- and what its operands look like -- moves its clock)
         qd_b = pipe.describe(q_tok, q_msk, q_off_local)
@@ -756,7 +773,7 @@ def run(a, top=True):
 
     # secondary: the kNN stage in its HBM-bound regime (B_q <= 50, i.e. ONE query image per pass)
     stream_roof = None
-    if use_pca and world == 1 and n_local_rows > 0:
+    if a.full and use_pca and world == 1 and n_local_rows > 0:
         qd1 = pipe.describe(q_tok[:1], q_msk[:S], np.array([0, S], dtype=np.int32))
         for _ in range(3):
             eng.search(qd1, 200)
@@ -820,7 +837,7 @@ def run(a, top=True):
         "ms_per_step_hip_event_median": float(np.median(step_ms_events)), "ms_per_step_hip_event_min": float(np.min(step_ms_events)),
         "timing_note": "value / ms_per_step: wall clock over the K steps between two barrier + synchronize fences (the contract); "
                        "the hip_event figures are per-step HIP events on the issuing stream (SURVEY 8d)",
-        "mode": "pipelined (describe i+1 on its own context/stream under search i)" if a.pipeline else "serial",
+        "mode": "pipelined (describe i+1 on its own context/stream under search i)" if a.pipeline else "serial", "full": a.full,
         "options": a.set or None,
         "pipelined": pipelined, "fp32_filter": fp32_rec, "search_back_to_back": b2b,
         "higher_is_better": True, "scaling": "strong",

@@ -24,7 +24,7 @@ def _run(cmd, timeout):
 
 
 def test_bench_step_predictions_equal_oracle_on_20_images():
-    j = _run([sys.executable, "bench.py", "--steps", "1", "--warmup", "1", "--verify-images", "20"], 1500)
+    j = _run([sys.executable, "bench.py", "--full", "--steps", "1", "--warmup", "1", "--verify-images", "20"], 1500)
     oc = j["oracle_check"]
     assert oc["images"] == 20
     assert oc["top1_identical"] == 20, oc                     # north_star: identical top-1 image ids
@@ -105,7 +105,7 @@ def test_bench_config2_raw_descriptors_end_to_end_equals_oracle():
     """BASELINE configs[1] literally (place_rec_main.py:49-60 with pca off): 1000 reference images x 50 segments of raw
     K*D = 98 304-d descriptors, 200 query images, search 200 / vote 50 -- one image's 50 query segments re-computed by the
     fp64 oracle against all 50 000 rows: identical top-1 image, sims within 1e-4, every id mismatch a near-tie."""
-    j = _run([sys.executable, "bench.py", "--no-pca", "--db-images", "1000", "--steps", "1", "--warmup", "1", "--verify-images", "1",
+    j = _run([sys.executable, "bench.py", "--full", "--no-pca", "--db-images", "1000", "--steps", "1", "--warmup", "1", "--verify-images", "1",
               "--no-sub-records", "--no-ubench", "--search-stats"], 1500)
     oc = j["oracle_check"]
     assert oc["images"] == 1 and oc["top1_identical"] == 1 and oc["ok"], oc

@@ -23,7 +23,7 @@ def _line():
             with open(p) as f:
                 return json.load(f)
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", SEGVLAD_GUARD="0")
-    r = subprocess.run([sys.executable, "bench.py", "--steps", "3", "--warmup", "1", "--verify-images", "2"], cwd=ROOT,
+    r = subprocess.run([sys.executable, "bench.py", "--full", "--steps", "3", "--warmup", "1", "--verify-images", "2"], cwd=ROOT,
                        capture_output=True, text=True, timeout=1500, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     return json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])

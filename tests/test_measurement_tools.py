@@ -142,3 +142,28 @@ def test_bench_dump_outputs_writes_the_callers_arrays_within_the_size_limit(tmp_
     monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 64 << 20)
     bench.dump_outputs(str(tmp_path / "b"), out)
     assert not os.path.exists(tmp_path / "b" / "sample_rows.npy")
+
+
+def test_bench_plain_run_leaves_everything_but_the_headline_to_full(monkeypatch, capsys):
+    """bench.py without --full switches off every measurement beyond the timed steps; --full keeps today's defaults and the
+    --no-* switches; --shard-sim-only only picks among the --full measurements."""
+    import pytest
+
+    sys.path.insert(0, ROOT)
+    import bench
+
+    def parse(*argv):
+        monkeypatch.setattr(sys, "argv", ["bench.py", *argv])
+        return bench.parse()
+
+    a = parse("--steps", "3")
+    assert not a.full and a.no_cpu_baseline and a.no_sub_records and a.no_ubench and a.shard_sim == 0
+    assert a.steps == 3 and a.verify_images == 20
+    a = parse("--full")
+    assert a.full and not (a.no_cpu_baseline or a.no_sub_records or a.no_ubench) and a.shard_sim == 8
+    a = parse("--full", "--no-ubench", "--shard-sim", "4")
+    assert a.no_ubench and not a.no_cpu_baseline and a.shard_sim == 4
+    assert parse("--full", "--shard-sim-only").shard_sim_only
+    with pytest.raises(SystemExit):
+        parse("--shard-sim-only")
+    assert "--full" in capsys.readouterr().err

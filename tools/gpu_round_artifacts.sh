@@ -87,13 +87,13 @@ PY
   [ -s $OUT/${TAG}_step_timeline.txt ] && cp $OUT/${TAG}_step_timeline.txt $REPO/profiles/${TAG}_step_timeline.txt
 fi
 if [ "$WHAT" = all ] || [ "$WHAT" = bench ]; then
-  timeout 420 python bench.py > $OUT/${TAG}_bench_n1.json 2> $OUT/${TAG}_bench_n1.err
+  timeout 420 python bench.py --full > $OUT/${TAG}_bench_n1.json 2> $OUT/${TAG}_bench_n1.err
   tail -c 600 $OUT/${TAG}_bench_n1.json
   cd /tmp && export TMPDIR=/tmp
   # same command under the kernel trace (the CPU-baseline leg launches no kernels)
   # (--no-ubench: the micro-benchmark is a child process, rocprofv3 would trace it into a second set of files)
   rm -rf /tmp/prof_kt
-  timeout 420 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_kt -- python $REPO/bench.py --no-cpu-baseline --no-ubench --shard-sim 0 \
+  timeout 420 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_kt -- python $REPO/bench.py --full --no-cpu-baseline --no-ubench --shard-sim 0 \
      > $OUT/${TAG}_bench_n1_under_rocprof.json 2> /tmp/prof_kt.err
   f=$(ls -S $(find /tmp/prof_kt -name '*kernel_stats.csv') 2>/dev/null | head -1); [ -n "$f" ] && cp $f $OUT/${TAG}_bench_n1_kernel_stats.csv
   # the single-image streaming pass (roofline_knn_stream): per-kernel durations of 50 passes

@@ -195,6 +195,22 @@ int segvlad_normalize_rows(segvlad_ctx* ctx, const float* X, int n, int d, float
 int segvlad_db_reset(segvlad_ctx* ctx);
 int segvlad_db_add(segvlad_ctx* ctx, const float* R, int n, int d, const int32_t* img_of_seg);
 int segvlad_db_size(segvlad_ctx* ctx, int64_t* n_rows, int* d);
+
+/* ---- removal from the index: faiss IndexFlat::remove_ids (no reference counterpart: the reference builds its index once,
+ *      place_rec_main.py:53-60; this is the upkeep of a deployed map).
+ *      A row is removed when its id is listed in row_ids [n_row_ids] int64, or when its image id (img_of_seg of
+ *      segvlad_db_add) is listed in img_ids [n_img_ids] int32.  Either list may be NULL / empty.  Ids outside 0 .. n-1,
+ *      negative image ids, image ids no row carries and duplicates are ignored.  img_ids on an index without an img_of_seg
+ *      map: SEGVLAD_ERR_STATE.
+ *      The surviving rows keep their order and are renumbered 0 .. n'-1 (faiss's semantics: every id above a removed one
+ *      moves down).  new_id_out [n] int64 or NULL: the new id of every OLD row, -1 if it was removed.  n_removed_out: HOST,
+ *      may be NULL.
+ *      Afterwards every segvlad_search / _search_shortlist / _vote (img_of_seg NULL) / _search_sharded returns, bit for
+ *      bit, what a fresh context returns that holds the surviving rows (and their image ids) from one segvlad_db_add.
+ *      Removing every row leaves an empty index that keeps its dimension and its img_of_seg rule: a search then returns
+ *      (+inf, -1) in every slot.  Synchronises.  Peak device memory during the call: the old AND the new buffers.   */
+int segvlad_db_remove(segvlad_ctx* ctx, const int64_t* row_ids, int64_t n_row_ids, const int32_t* img_ids, int n_img_ids,
+                      int64_t* new_id_out, int64_t* n_removed_out);
 /*      d2_out [nq][k] fp32 ascending squared L2; idx_out [nq][k] int64 (ties -> lower id; slots
  *      beyond the database size hold (+inf, -1) like faiss).  1 <= k <= 1024.                      */
 int segvlad_search(segvlad_ctx* ctx, const float* Q, int nq, int k, float* d2_out, int64_t* idx_out);
@@ -241,7 +257,7 @@ int segvlad_vote(segvlad_ctx* ctx, const int64_t* idx, const float* sims, const 
                  int32_t* pred_out, double* score_out);
 
 /* ---- instrumentation: with profiling on, every kernel group of a stage ("incidence", "adjacency",
- *      "assign", "prep", "aggregate", "pca", "describe" (segvlad_describe as a whole: its parts overlap), "knn_level0", "knn_gemm", "knn_select", "knn_fallback", "knn_shortlist" (segvlad_search_shortlist), "vote") is bracketed by a HIP event pair
+ *      "assign", "prep", "aggregate", "pca", "describe" (segvlad_describe as a whole: its parts overlap), "knn_level0", "knn_gemm", "knn_select", "knn_fallback", "knn_shortlist" (segvlad_search_shortlist), "db_remove" (segvlad_db_remove), "vote") is bracketed by a HIP event pair
  *      on the context stream.  segvlad_stage_ms returns the SUM of the elapsed times (ms) and the number
  *      of kernel launches recorded for the stage since the last segvlad_profile_reset; it returns
  *      SEGVLAD_ERR_STATE if the stage has not run.  Replaces the (discarded) time.time() pair of

@@ -52,6 +52,7 @@ SIGNATURES = {
     "segvlad_db_reset": (C.c_int, [c_ctx_p]),
     "segvlad_db_add": (C.c_int, [c_ctx_p, _f32p, C.c_int, C.c_int, C.c_void_p]),
     "segvlad_db_size": (C.c_int, [c_ctx_p, C.POINTER(C.c_int64), C.POINTER(C.c_int)]),
+    "segvlad_db_remove": (C.c_int, [c_ctx_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_int64)]),
     "segvlad_search": (C.c_int, [c_ctx_p, _f32p, C.c_int, C.c_int, _f32p, C.c_void_p]),
     "segvlad_search_shortlist": (C.c_int, [c_ctx_p, _f32p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, _f32p,
                                             C.c_void_p]),

@@ -1169,6 +1169,11 @@ int segvlad_search_shortlist(segvlad_ctx* ctx, const float* Q, int nq, const int
   SV_TRY(sv_in(ctx, shortlist, (size_t)n_img * M * 4, &dsl));
   SV_TRY(sv_out(ctx, d2_out, (size_t)nq * k * 4, &dd2));
   SV_TRY(sv_out(ctx, idx_out, (size_t)nq * k * 8, &didx));
+  if (ctx->db_n == 0) {   // emptied by segvlad_db_remove: no row is allowed anywhere
+    SV_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(dd2), 0x7f800000, (size_t)nq * k, ctx->stream));
+    SV_HIP(hipMemsetAsync(didx, 0xff, (size_t)nq * k * 8, ctx->stream));
+    return sv_finish(ctx);
+  }
   SV_HIP(ctx->s_qnorm.reserve((size_t)nq * 4));
   SV_TRY(sv_launch_row_sumsq(ctx, (const float*)dq, nq, d, ctx->s_qnorm.as<float>()));
   SV_TRY(sv_search_shortlist(ctx, (const float*)dq, nq, ctx->s_qnorm.as<float>(), qseg_offsets, n_img, (const int32_t*)dsl, M, k,

@@ -273,6 +273,7 @@ struct segvlad_ctx {
   int db_d = 0;
   int64_t db_n = 0;
   bool db_has_img = false;
+  bool db_added = false;                  // rows were added since the last reset: db_d and db_has_img are fixed (even once removal empties it)
   int64_t db_split_rows = 0;              // rows covered by the bf16 hi/lo planes (built lazily for the large-database search path)
   int64_t db_f16_rows = 0;                // rows covered by the fp16 image of the rows, scaled by a power of two (single-product filter)
   float db_f16_scale = 0.f, db_maxabs = 0.f;
@@ -307,7 +308,8 @@ struct segvlad_ctx {
   X(vocab) X(vocab_bt) X(pca_mean) X(pca_comps) X(pca_scale) X(pca_w1) X(pca_w2) X(pca_cproj) X(db_rows) X(db_norms) X(db_img)    \
   X(db_hi) X(db_lo) X(db_f16) X(s_ref_keys) X(s_ref_tick) X(s_tail_tick) X(sl_img_off) X(sl_img_rows)
   //  scratch: grow-only, reused across calls, nothing in them is read after the call that wrote it; s_sh_*: exchange buffers of
-  //  the row-sharded index (comm.hip)
+  //  the row-sharded index (comm.hip); s_rm_*: removal flags, block counts / offsets and the source of every surviving row
+  //  (remove_kernels.hip)
 #define SV_SCRATCH_BUFS(X)                                                                                                       \
   X(s_xt) X(s_labels) X(s_rnorm) X(s_gap) X(s_colmask) X(s_gscale) X(s_segimg) X(s_segoff) X(s_adjoff) X(s_dist) X(s_qnorm)      \
   X(s_misc) X(s_minmax) X(s_voteoff) X(s_cand_cnt) X(s_cand_d2) X(s_cand_id) X(s_thr_d2) X(s_thr_idx) X(s_flag) X(s_qh) X(s_ql)  \
@@ -315,7 +317,8 @@ struct segvlad_ctx {
   X(s_fb_q) X(s_fb_d2) X(s_fb_idx) X(s_fb_rows) X(s_rd_rows) X(s_rd_q) X(s_rd_d2) X(s_rd_idx) X(s_rd_flags) X(s_rd_p1) X(s_rd_p2)  \
   X(s_sel_todo) X(s_vote_keys) X(s_pz) X(s_rowbase) X(s_tilegrp) X(s_bn) X(s_l0part) X(s_ref_lim) X(s_sh_d2) X(s_sh_idx)          \
   X(s_sh_rec) X(s_sh_all) X(s_sh_d2c) X(s_sh_idc) X(s_grp_cnt) X(s_grp_ids) X(s_grp_rows) X(s_grp_keys) X(s_grp_work) X(s_grp_pos) X(s_tnk_redo) X(s_tail_part) X(s_km_part) X(s_km_cnt) X(s_kflush) \
-  X(s_sl_misc) X(s_sl_q) X(s_sl_cur) X(s_sl_uids) X(s_sl_uoff) X(s_sl_unum) X(s_sl_cand) X(s_sl_lens)
+  X(s_sl_misc) X(s_sl_q) X(s_sl_cur) X(s_sl_uids) X(s_sl_uoff) X(s_sl_unum) X(s_sl_cand) X(s_sl_lens)                            \
+  X(s_rm_row) X(s_rm_img) X(s_rm_blk) X(s_rm_src) X(s_rm_misc)
 #define SV_DECL_BUF(n) DevBuf n;
   SV_PERSISTENT_BUFS(SV_DECL_BUF)
   SV_SCRATCH_BUFS(SV_DECL_BUF)
@@ -552,6 +555,14 @@ int sv_launch_minmax(segvlad_ctx* ctx, const float* sims, int64_t count, float* 
 int sv_img_max(segvlad_ctx* ctx, const int32_t* img_dev, int64_t n, int* out);
 int sv_search_shortlist(segvlad_ctx* ctx, const float* Q, int nq, const float* qn, const int32_t* qoff, int n_img,
                         const int32_t* shortlist, int M, int k, float* d2_out, int64_t* idx_out);
+
+// remove_kernels.hip (segvlad_db_remove): the keep flags of the listed rows / images, every surviving row's new position
+// (src_of_dst in ctx->s_rm_src, new_id [db_n] or null), then counts_host [3] = {n', survivors below plane_rows_a, below plane_rows_b}
+// (synchronises; *launches = kernels launched); and the gather of one plane's first n_dst surviving rows (row pitch in bytes, a
+// multiple of 4) into dst -- one launch
+int sv_remove_positions(segvlad_ctx* ctx, const int64_t* row_ids, int64_t n_row_ids, const int32_t* img_ids, int64_t n_img_ids,
+                        int64_t* new_id, int64_t plane_rows_a, int64_t plane_rows_b, int64_t* counts_host, int* launches);
+int sv_launch_remove_gather(segvlad_ctx* ctx, const void* src, void* dst, size_t pitch, int64_t n_dst);
 
 // vote_kernels.hip
 int sv_launch_vote(segvlad_ctx* ctx, const int64_t* idx, const float* sims, const int32_t* img_of_seg,

@@ -42,6 +42,7 @@ int segvlad_db_reset(segvlad_ctx* ctx) {
   ctx->db_n = 0;
   ctx->db_d = 0;
   ctx->db_has_img = false;
+  ctx->db_added = false;
   ctx->db_img_max = -1;
   ctx->db_split_rows = 0;
   ctx->db_f16_rows = 0;
@@ -56,8 +57,9 @@ int segvlad_db_reset(segvlad_ctx* ctx) {
 int segvlad_db_add(segvlad_ctx* ctx, const float* R, int n, int d, const int32_t* img_of_seg) {
   CHECK_CTX();
   if (n < 0 || d <= 0) return ctx->fail(SEGVLAD_ERR_ARG, "db_add: bad shape");
-  if (ctx->db_n > 0 && d != ctx->db_d) return ctx->fail(SEGVLAD_ERR_ARG, "db_add: d=%d but the index holds d=%d", d, ctx->db_d);
-  if (ctx->db_n > 0 && ctx->db_has_img != (img_of_seg != nullptr))
+  // (an index that removal has emptied keeps its dimension and its img_of_seg rule until db_reset)
+  if (ctx->db_added && d != ctx->db_d) return ctx->fail(SEGVLAD_ERR_ARG, "db_add: d=%d but the index holds d=%d", d, ctx->db_d);
+  if (ctx->db_added && ctx->db_has_img != (img_of_seg != nullptr))
     return ctx->fail(SEGVLAD_ERR_ARG, "db_add: img_of_seg must be given for all rows or none");
   if (n == 0) return SEGVLAD_OK;
   if (!R) return ctx->fail(SEGVLAD_ERR_ARG, "db_add: null rows");
@@ -78,6 +80,114 @@ int segvlad_db_add(segvlad_ctx* ctx, const float* R, int n, int d, const int32_t
   SV_TRY(sv_launch_row_sumsq(ctx, dst, n, d, ctx->db_norms.as<float>() + ctx->db_n));
   ctx->db_n = n_new;
   ctx->db_d = d;
+  ctx->db_added = true;
+  index_changed(ctx);
+  return sv_finish(ctx);
+}
+
+// One plane of the index to be compacted: the old buffer, its row pitch in bytes, the surviving rows it takes, and the fresh
+// buffer (same tag, guard and persistence) that receives them.
+struct PlaneMove {
+  DevBuf* old;
+  size_t pitch;
+  int64_t rows;
+  DevBuf fresh;
+};
+
+static void release_fresh(std::vector<PlaneMove>& mv) {
+  for (auto& m : mv) m.fresh.release();
+}
+
+int segvlad_db_remove(segvlad_ctx* ctx, const int64_t* row_ids, int64_t n_row_ids, const int32_t* img_ids, int n_img_ids,
+                      int64_t* new_id_out, int64_t* n_removed_out) {
+  CHECK_CTX();
+  if (n_row_ids < 0 || n_img_ids < 0) return ctx->fail(SEGVLAD_ERR_ARG, "db_remove: negative list length");
+  if ((n_row_ids > 0 && !row_ids) || (n_img_ids > 0 && !img_ids)) return ctx->fail(SEGVLAD_ERR_ARG, "db_remove: null id list");
+  if (n_img_ids > 0 && !ctx->db_has_img)
+    return ctx->fail(SEGVLAD_ERR_STATE, "db_remove: image ids given, but the index holds no img_of_seg map");
+  if (n_removed_out) *n_removed_out = 0;
+  const int64_t n = ctx->db_n;
+  const int d = ctx->db_d;
+  if (n == 0 || (n_row_ids == 0 && n_img_ids == 0)) {
+    if (n > 0 && new_id_out) {   // nothing listed: every row keeps its id
+      void* dn;
+      SV_TRY(sv_out(ctx, new_id_out, (size_t)n * 8, &dn));
+      std::vector<int64_t> ident(n);
+      for (int64_t r = 0; r < n; ++r) ident[r] = r;
+      SV_HIP(hipMemcpyAsync(dn, ident.data(), (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
+      SV_HIP(hipStreamSynchronize(ctx->stream));
+    }
+    return sv_finish(ctx);
+  }
+  const void *drow = nullptr, *dimg = nullptr;
+  void* dnew = nullptr;
+  SV_TRY(sv_in(ctx, row_ids, (size_t)n_row_ids * 8, &drow));
+  SV_TRY(sv_in(ctx, img_ids, (size_t)n_img_ids * 4, &dimg));
+  if (new_id_out) SV_TRY(sv_out(ctx, new_id_out, (size_t)n * 8, &dnew));
+  int64_t cnt[3] = {n, 0, 0};   // n', survivors below db_f16_rows, below db_split_rows
+  StageScope sc(ctx, "db_remove");
+  int launches = 0;
+  SV_TRY(sv_remove_positions(ctx, (const int64_t*)drow, n_row_ids, (const int32_t*)dimg, n_img_ids, (int64_t*)dnew, ctx->db_f16_rows,
+                             ctx->db_split_rows, cnt, &launches));
+  sc.count(launches);
+  const int64_t n_new = cnt[0];
+  if (n_removed_out) *n_removed_out = n - n_new;
+  if (n_new == n) return sv_finish(ctx);   // (a removal that removes nothing moves nothing)
+  // Every destination is reserved before anything is moved: a failed allocation releases the fresh buffers and leaves the index as
+  // it was.  The gathers only READ the old planes, so until the swap below the index still describes its old buffers whatever
+  // happens; after it nothing can fail.  Peak memory: the old and the new planes together.
+  std::vector<PlaneMove> mv;
+  mv.push_back({&ctx->db_rows, (size_t)d * 4, n_new, {}});
+  mv.push_back({&ctx->db_norms, 4, n_new, {}});
+  if (ctx->db_has_img) mv.push_back({&ctx->db_img, 4, n_new, {}});
+  if (ctx->db_f16_rows > 0) mv.push_back({&ctx->db_f16, (size_t)d * 2, cnt[1], {}});
+  if (ctx->db_split_rows > 0) {
+    mv.push_back({&ctx->db_hi, (size_t)d * 2, cnt[2], {}});
+    mv.push_back({&ctx->db_lo, (size_t)d * 2, cnt[2], {}});
+  }
+  for (auto& m : mv) {
+    m.fresh.tag = m.old->tag;
+    m.fresh.guard = m.old->guard;
+    m.fresh.fixed = m.old->fixed;
+    if (m.rows <= 0) continue;
+    const hipError_t e = m.fresh.reserve((size_t)m.rows * m.pitch);
+    if (e != hipSuccess) {
+      release_fresh(mv);
+      return ctx->fail(e == hipErrorOutOfMemory ? SEGVLAD_ERR_NOMEM : SEGVLAD_ERR_HIP,
+                       "db_remove: reserving %zu bytes for %s: %s (the index is unchanged)", (size_t)m.rows * m.pitch, m.old->tag,
+                       hipGetErrorString(e));
+    }
+  }
+  for (auto& m : mv) {
+    if (m.rows <= 0) continue;
+    const int rc = sv_launch_remove_gather(ctx, m.old->p, m.fresh.p, m.pitch, m.rows);
+    if (rc != SEGVLAD_OK) {
+      (void)hipStreamSynchronize(ctx->stream);
+      release_fresh(mv);
+      return rc;
+    }
+    sc.count();
+  }
+  const hipError_t e = hipStreamSynchronize(ctx->stream);   // (the gathers have read the old planes)
+  if (e != hipSuccess) {
+    release_fresh(mv);
+    return ctx->fail(SEGVLAD_ERR_HIP, "db_remove: the gathers failed: %s (the index is unchanged)", hipGetErrorString(e));
+  }
+  for (auto& m : mv) {
+    m.old->release();
+    *m.old = m.fresh;
+  }
+  // the surviving rows keep their order, so the planes' prefixes stay valid; the fp16 scale still bounds every surviving row.  The max
+  // row norm is recomputed from the compacted norms by the next search that needs it (prepare_index_planes: exact, as a fresh index's)
+  ctx->db_n = n_new;
+  ctx->db_f16_rows = cnt[1];
+  ctx->db_split_rows = cnt[2];
+  ctx->db_rn_max = 0.f;
+  ctx->db_rn_max_rows = 0;
+  if (n_new == 0) {
+    ctx->db_f16_scale = 0.f;
+    ctx->db_maxabs = 0.f;
+  }
   index_changed(ctx);
   return sv_finish(ctx);
 }
@@ -977,6 +1087,11 @@ extern "C" int segvlad_search(segvlad_ctx* ctx, const float* Q, int nq, int k, f
     if ((int64_t)redone * 4 > ctx->tail_rows_since) ctx->db_heur_off = true;
   }
 
+  if (ctx->db_n == 0) {   // emptied by segvlad_db_remove: every slot beyond the (zero) rows is (+inf, -1)
+    SV_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d2), 0x7f800000, (size_t)nq * k, ctx->stream));
+    SV_HIP(hipMemsetAsync(idx, 0xff, (size_t)nq * k * 8, ctx->stream));
+    return sv_finish(ctx);
+  }
   const SearchPlan p = plan_search(ctx, nq, k, dq);
   if (p.matrix) {
     SV_TRY(sv_launch_row_sumsq(ctx, q, nq, p.d, qn));

@@ -569,6 +569,24 @@ class SegVLADEngine:
         if isinstance(r, torch.Tensor) and r.is_cuda:
             torch.cuda.current_stream(self.device).synchronize()  # the index copied the rows: r may now be freed
 
+    def db_remove(self, row_ids=None, img_ids=None, want_new_ids: bool = False):
+        """segvlad_db_remove (faiss IndexFlat::remove_ids): drops the rows whose id is in ``row_ids`` or whose image id (the
+        img_of_seg of db_add) is in ``img_ids``; the survivors keep their order and are renumbered 0 .. n' - 1.  Out-of-range
+        and duplicate ids are ignored.  Returns the number removed, and with ``want_new_ids`` also the int64 device tensor [n]
+        of every old row's new id (-1: removed).  n_img_ref keeps its meaning (1 + the largest id given to db_add since
+        db_reset): a shortlist may still name a removed image, which then contributes no rows."""
+        ri = None if row_ids is None else _as(row_ids, np.int64, torch.int64).reshape(-1)
+        ii = None if img_ids is None else _as(img_ids, np.int32, torch.int32).reshape(-1)
+        n_r = 0 if ri is None else int(ri.shape[0])
+        n_i = 0 if ii is None else int(ii.shape[0])
+        n, _ = self.db_size()
+        new_ids = self._empty((n,), torch.int64) if want_new_ids else None
+        removed = C.c_int64(0)
+        self._stream()
+        self._check(self.lib.segvlad_db_remove(self._h, _ptr(ri) if n_r else None, n_r, _ptr(ii) if n_i else None, n_i,
+                                               _ptr(new_ids) if n else None, C.byref(removed)), "db_remove")
+        return (int(removed.value), new_ids) if want_new_ids else int(removed.value)
+
     def db_size(self):
         n, d = C.c_int64(), C.c_int()
         self.lib.segvlad_db_size(self._h, C.byref(n), C.byref(d))

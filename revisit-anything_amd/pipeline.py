@@ -180,6 +180,11 @@ class SegVLADPipeline:
     def index_add(self, desc: torch.Tensor, img_of_seg):
         self.eng.db_add(desc, img_of_seg)
 
+    def index_remove_images(self, img_ids) -> int:
+        """Drops every segment row of the listed reference images (stale, mis-registered or withdrawn) from the index on the
+        device; later rows move down (engine.db_remove).  Returns the number of rows removed."""
+        return self.eng.db_remove(img_ids=img_ids)
+
     # ---- a10..a12: descriptors -> ranked reference images ----------------------------------------------
     def retrieve(self, qdesc: torch.Tensor, qseg_offsets: np.ndarray, k_search: int = 200, k_vote: int = 50, n_top: int = 5,
                  mode: int = _lib.VOTE_WT_BORDA_IM, want_scores: bool = False, vote_depth_only: bool = False, shortlist=None):

@@ -15,7 +15,7 @@ from . import func_vpr
 
 class IndexFlatL2:
     """faiss.IndexFlatL2 surface used by the reference (place_rec_main.py:53-60): ``add(x)``,
-    ``search(x, k) -> (D2 float32 [n,k] ascending, I int64 [n,k])``, ``ntotal``, ``d``.  Exact,
+    ``search(x, k) -> (D2 float32 [n,k] ascending, I int64 [n,k])``, ``ntotal``, ``d`` -- and faiss's ``remove_ids(ids)``.  Exact,
     brute force, on the MI355X (16-bit MFMA candidate filter + exact fp32 refinement, or the fp32 distance-matrix
     path for small indices).  Every index owns its own engine context (its own rows, planes and scratch), so several
     indices can be alive at once -- as with faiss -- and none of them disturbs the vocabulary / PCA state of the
@@ -38,6 +38,18 @@ class IndexFlatL2:
             raise ValueError(f"IndexFlatL2(d={self.d}).add got vectors of dimension {x.shape[1]}")
         self._eng.db_add(x)
         self.ntotal += int(x.shape[0])
+
+    def remove_ids(self, ids) -> int:
+        """faiss.IndexFlat.remove_ids for an integer array of ids: the listed rows go, every later id moves down (the
+        survivors keep their order).  Ids outside 0 .. ntotal - 1 and duplicates are ignored.  Returns the number removed."""
+        ids = ids if isinstance(ids, torch.Tensor) else np.asarray(ids)
+        integer = (not ids.is_floating_point() and not ids.is_complex() and ids.dtype != torch.bool) if isinstance(ids, torch.Tensor) \
+            else np.issubdtype(ids.dtype, np.integer)
+        if not integer:
+            raise TypeError(f"IndexFlatL2.remove_ids takes an integer array, got {ids.dtype}")
+        n = self._eng.db_remove(row_ids=ids.reshape(-1))
+        self.ntotal -= n
+        return n
 
     def search(self, x, k: int):
         x = np.ascontiguousarray(x, dtype=np.float32) if not isinstance(x, torch.Tensor) else x

@@ -11,7 +11,7 @@ The reference is single-process; sharding is the build's 
   ties by lower global id, i.e. exactly what a single index over all rows returns -- and votes.
 
 The compute is delegated to a backend object with the SegVLADEngine interface (db_reset, db_add,
-search, merge_topk, sims_from_d2, vote); the distributed plumbing below is backend-agnostic so
+db_remove, search, merge_topk, sims_from_d2, vote); the distributed plumbing below is backend-agnostic so
 that it can be exercised with gloo on CPU (tests/test_sharded_gloo.py) with a checker backend.
 """
 from __future__ import annotations
@@ -31,6 +31,28 @@ def shard_bounds(n_rows: int, world: int) -> np.ndarray:
 def shard_images(n_images: int, world: int) -> np.ndarray:
     """Contiguous image blocks (a reference image's segments never straddle two ranks)."""
     return np.array([(r * n_images) // world for r in range(world + 1)], dtype=np.int64)
+
+
+def removal_keep_mask(img_of_seg: torch.Tensor, row_ids=None, img_ids=None) -> torch.Tensor:
+    """The keep flag [n] of every row of an index whose segment -> image map is ``img_of_seg`` [n] after removing the rows listed
+    in ``row_ids`` and the rows of the images listed in ``img_ids`` (segvlad_db_remove's rule: out-of-range ids, negative image ids
+    and duplicates are ignored).  On img_of_seg's device."""
+    n = int(img_of_seg.shape[0])
+    dev = img_of_seg.device
+    keep = torch.ones(n, dtype=torch.bool, device=dev)
+    if row_ids is not None:
+        r = torch.as_tensor(np.asarray(row_ids) if not isinstance(row_ids, torch.Tensor) else row_ids).reshape(-1).to(dev, torch.int64)
+        keep[r[(r >= 0) & (r < n)]] = False
+    if img_ids is not None and n:
+        g = torch.as_tensor(np.asarray(img_ids) if not isinstance(img_ids, torch.Tensor) else img_ids).reshape(-1).to(dev, torch.int64)
+        top = int(img_of_seg.max()) if n else -1
+        g = g[(g >= 0) & (g <= top)]
+        if g.numel():
+            gone = torch.zeros(top + 1, dtype=torch.bool, device=dev)
+            gone[g] = True
+            im = img_of_seg.to(torch.int64)
+            keep &= ~torch.where(im >= 0, gone[im.clamp(min=0)], torch.zeros_like(keep))
+    return keep
 
 
 class ShardedSegmentIndex:
@@ -121,6 +143,35 @@ class ShardedSegmentIndex:
     @property
     def n_total(self) -> int:
         return int(self.row_start[-1])
+
+    # ---- removal ------------------------------------------------------------------------------------
+    def remove(self, row_ids=None, img_ids=None) -> int:
+        """Removes rows by GLOBAL row id and / or by reference image id; the survivors keep their order and their global ids
+        move down, exactly as one index over all rows (segvlad_db_remove).  Collective: every rank passes the same lists.  Each
+        rank derives the global keep mask from img_of_seg_global (the rank engines hold no image map: image removal becomes row
+        removal), removes its own rows, and takes the new row_start and the compacted map.  One all-gather of every rank's view
+        -- the kept rows per shard and a checksum of the removed ids -- comes first: if any rank was given other lists, every
+        rank raises before any shard changes.  Shards may become uneven (no rebalancing).  Returns the number of rows removed."""
+        keep = removal_keep_mask(self.img_of_seg_global, row_ids, img_ids)
+        bounds = [int(b) for b in self.row_start]
+        kept = [int(keep[bounds[r]:bounds[r + 1]].sum()) for r in range(self.world)]
+        gone = torch.nonzero(~keep).reshape(-1).to(torch.int64)
+        view = torch.tensor(kept + [int(gone.sum()), int((gone * gone % 1000000007).sum())], dtype=torch.int64, device=self.device)
+        if self.world > 1:
+            views = [torch.zeros_like(view) for _ in range(self.world)]
+            dist.all_gather(views, view, group=self.group)
+            if any(not torch.equal(v, views[0]) for v in views):
+                from ._lib import SegVLADError
+
+                raise SegVLADError("ShardedSegmentIndex.remove: the ranks were given different removal lists (no shard changed)")
+        lo, hi = bounds[self.rank], bounds[self.rank + 1]
+        local = gone[(gone >= lo) & (gone < hi)] - lo
+        if local.numel():
+            self.be.db_remove(row_ids=local)
+        self.row_start = np.concatenate([[0], np.cumsum(kept)]).astype(np.int64)
+        self.n_local = kept[self.rank]
+        self.img_of_seg_global = self.img_of_seg_global[keep].contiguous()
+        return int(gone.numel())
 
     # ---- query descriptors: every rank describes a slice of the query images, all ranks need all rows -----------
     def gather_rows(self, local_rows: torch.Tensor, rows_per_rank: Sequence[int]) -> torch.Tensor:
@@ -296,6 +347,17 @@ class QueryShardedRetrieval:
             if self.world > 1:
                 dist.broadcast_object_list(uid, src=0, group=self.group)
             self.be.comm_init(uid[0], self.rank, self.world)
+
+    def remove(self, row_ids=None, img_ids=None) -> int:
+        """Removes rows by row id and / or by reference image id from the replicated index (segvlad_db_remove: survivors keep
+        their order, ids move down).  Every rank removes the same rows -- the engine holds no image map, so image ids become row
+        ids through the Python-side map, which is compacted with them.  Returns the number of rows removed."""
+        keep = removal_keep_mask(self.img_of_seg, row_ids, img_ids)
+        gone = torch.nonzero(~keep).reshape(-1).to(torch.int64)
+        if gone.numel():
+            self.be.db_remove(row_ids=gone)
+        self.img_of_seg = self.img_of_seg[keep].contiguous()
+        return int(gone.numel())
 
     def split(self, n_query_images: int) -> np.ndarray:
         """The query split (contiguous image blocks): rank r describes and retrieves images [b[r], b[r + 1])."""

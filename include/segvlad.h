@@ -230,6 +230,29 @@ int segvlad_search(segvlad_ctx* ctx, const float* Q, int nq, int k, float* d2_ou
 int segvlad_search_shortlist(segvlad_ctx* ctx, const float* Q, int nq, const int32_t* qseg_offsets, int n_img,
                              const int32_t* shortlist, int M, int k, float* d2_out, int64_t* idx_out);
 
+/* ---- search excluding image-id windows per query image (no reference counterpart: the reference searches the whole index,
+ *      place_rec_main.py:53-60; this is the self-query of a live map -- loop closure, the leave-one-out check of a map -- where
+ *      the query image's own rows and its neighbours in time are in the index).
+ *      Q [nq][d] device or host; qseg_offsets [n_img+1] int32 HOST as in segvlad_search_shortlist (0 rows allowed).
+ *      excl [n_img][E][2] int32 HOST: per query image E inclusive intervals [lo, hi] of reference image ids (the img_of_seg
+ *      values of segvlad_db_add) its rows must not match.  lo > hi is an empty interval (padding); intervals may overlap, reach
+ *      below 0 or above the largest id, cover ids no row carries.  1 <= E <= 8, 1 <= k <= 1024.  A row whose image id is
+ *      negative is never excluded.
+ *      d2_out / idx_out [nq][k]: per query row the top-k rows of the index whose image id lies in none of its image's intervals,
+ *      ordered by (squared L2, lower id); (+inf, -1) beyond the number of allowed rows -- bit for bit what segvlad_search
+ *      returns on an index without those images (ids aside).  All intervals empty: exactly segvlad_search(Q, k).
+ *      The search runs once at depth k_fetch = min(1024, k + the largest number of rows any query image excludes) and keeps
+ *      each row's first k allowed entries; rows of an image whose window holds more than 1024 - k rows AND fills the row's
+ *      nearest 1024 are finished by an exact fp32 pass over the allowed rows (needs every row's image id >= 0: a call whose
+ *      largest window holds more than 1024 - k rows on an index with a negative image id returns SEGVLAD_ERR_LIMIT).  SEGVLAD_ERR_STATE without an img_of_seg map; SEGVLAD_ERR_LIMIT when d % 32 != 0; SEGVLAD_ERR_ARG
+ *      on bad shapes, offsets or E.  Stage timer "knn_exclude": the kernels this call adds to the inner search's own stages.
+ *      segvlad_exclude_stats: HOST array, up to 4 values, of the last segvlad_search_excluding -- [0] the depth the inner
+ *      search ran at (k_fetch), [1] the largest number of excluded index rows of any query image that owns rows, [2] query
+ *      rows finished by the exact pass, [3] query images (that own rows) with at least one excluded row.  Synchronises. */
+int segvlad_search_excluding(segvlad_ctx* ctx, const float* Q, int nq, const int32_t* qseg_offsets, int n_img,
+                             const int32_t* excl, int E, int k, float* d2_out, int64_t* idx_out);
+int segvlad_exclude_stats(segvlad_ctx* ctx, int64_t* stats_out, int n);
+
 /* ---- merge of per-shard top-k lists (no reference counterpart: the reference is single-process).
  *      d2_parts/idx_parts [nq][parts*k] (shard-major within a row, global ids); output top-k by
  *      (distance, lower id).                                                                       */
@@ -257,7 +280,7 @@ int segvlad_vote(segvlad_ctx* ctx, const int64_t* idx, const float* sims, const 
                  int32_t* pred_out, double* score_out);
 
 /* ---- instrumentation: with profiling on, every kernel group of a stage ("incidence", "adjacency",
- *      "assign", "prep", "aggregate", "pca", "describe" (segvlad_describe as a whole: its parts overlap), "knn_level0", "knn_gemm", "knn_select", "knn_fallback", "knn_shortlist" (segvlad_search_shortlist), "db_remove" (segvlad_db_remove), "vote") is bracketed by a HIP event pair
+ *      "assign", "prep", "aggregate", "pca", "describe" (segvlad_describe as a whole: its parts overlap), "knn_level0", "knn_gemm", "knn_select", "knn_fallback", "knn_shortlist" (segvlad_search_shortlist), "knn_exclude" (the kernels segvlad_search_excluding adds to its inner search), "db_remove" (segvlad_db_remove), "vote") is bracketed by a HIP event pair
  *      on the context stream.  segvlad_stage_ms returns the SUM of the elapsed times (ms) and the number
  *      of kernel launches recorded for the stage since the last segvlad_profile_reset; it returns
  *      SEGVLAD_ERR_STATE if the stage has not run.  Replaces the (discarded) time.time() pair of

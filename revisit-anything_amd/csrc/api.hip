@@ -1181,6 +1181,60 @@ int segvlad_search_shortlist(segvlad_ctx* ctx, const float* Q, int nq, const int
   return sv_finish(ctx);
 }
 
+int segvlad_search_excluding(segvlad_ctx* ctx, const float* Q, int nq, const int32_t* qseg_offsets, int n_img,
+                             const int32_t* excl, int E, int k, float* d2_out, int64_t* idx_out) {
+  CHECK_CTX();
+  if (nq < 0 || n_img < 0 || k < 1 || k > 1024 || E < 1 || E > SV_EX_MAX_E)
+    return ctx->fail(SEGVLAD_ERR_ARG, "search_excluding: need nq, n_img >= 0, 1<=k<=1024, 1<=E<=%d (k=%d, E=%d)", SV_EX_MAX_E, k, E);
+  if (!qseg_offsets) return ctx->fail(SEGVLAD_ERR_ARG, "search_excluding: null qseg_offsets");
+  if (sv_is_device_ptr(qseg_offsets)) return ctx->fail(SEGVLAD_ERR_ARG, "search_excluding: qseg_offsets must be host memory");
+  if (qseg_offsets[0] != 0 || qseg_offsets[n_img] != nq)
+    return ctx->fail(SEGVLAD_ERR_ARG, "search_excluding: qseg_offsets must run from 0 to nq=%d", nq);
+  for (int b = 0; b < n_img; ++b)
+    if (qseg_offsets[b + 1] < qseg_offsets[b]) return ctx->fail(SEGVLAD_ERR_ARG, "search_excluding: qseg_offsets decrease at %d", b);
+  if (n_img > 0 && !excl) return ctx->fail(SEGVLAD_ERR_ARG, "search_excluding: null excl");
+  if (excl && sv_is_device_ptr(excl)) return ctx->fail(SEGVLAD_ERR_ARG, "search_excluding: excl must be host memory");
+  if (ctx->db_d == 0) return ctx->fail(SEGVLAD_ERR_STATE, "search_excluding: the index is empty and has no dimension yet");
+  if (!ctx->db_has_img) return ctx->fail(SEGVLAD_ERR_STATE, "search_excluding: no img_of_seg map: give it to segvlad_db_add");
+  const int d = ctx->db_d;
+  if (d % 32 != 0) return ctx->fail(SEGVLAD_ERR_LIMIT, "search_excluding: d=%d (the exact GEMM of the tail takes d %% 32 == 0)", d);
+  if (ctx->db_n > 0x7fffffffll) return ctx->fail(SEGVLAD_ERR_LIMIT, "search_excluding: more than 2^31 - 1 rows");
+  if (ctx->opt.debug_fail_search == 1) return ctx->fail(SEGVLAD_ERR_STATE, "search_excluding: failing on request (option debug_fail_search)");
+  ctx->ex_stats[0] = ctx->ex_stats[1] = ctx->ex_stats[2] = ctx->ex_stats[3] = 0;
+  ctx->ex_short_dev = nullptr;
+  if (nq == 0) return SEGVLAD_OK;
+  if (!Q || !d2_out || !idx_out) return ctx->fail(SEGVLAD_ERR_ARG, "search_excluding: null pointer");
+  const void* dq;
+  void *dd2, *didx;
+  SV_TRY(sv_in(ctx, Q, (size_t)nq * d * 4, &dq));
+  SV_TRY(sv_out(ctx, d2_out, (size_t)nq * k * 4, &dd2));
+  SV_TRY(sv_out(ctx, idx_out, (size_t)nq * k * 8, &didx));
+  if (ctx->db_n == 0) {   // emptied by segvlad_db_remove: no row is allowed anywhere
+    ctx->ex_stats[0] = k;
+    SV_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(dd2), 0x7f800000, (size_t)nq * k, ctx->stream));
+    SV_HIP(hipMemsetAsync(didx, 0xff, (size_t)nq * k * 8, ctx->stream));
+    return sv_finish(ctx);
+  }
+  SV_TRY(sv_search_excluding(ctx, (const float*)dq, nq, qseg_offsets, n_img, excl, E, k, (float*)dd2, (int64_t*)didx));
+  return sv_finish(ctx);
+}
+
+int segvlad_exclude_stats(segvlad_ctx* ctx, int64_t* stats_out, int n) {
+  CHECK_CTX();
+  if (!stats_out || n < 0) return ctx->fail(SEGVLAD_ERR_ARG, "exclude_stats: bad arguments");
+  if (ctx->ex_short_dev) {   // the rows the last call's tail finished: fetched once
+    uint32_t w = 0;
+    SV_HIP(hipMemcpyAsync(&w, ctx->ex_short_dev, 4, hipMemcpyDeviceToHost, ctx->stream));
+    SV_HIP(hipStreamSynchronize(ctx->stream));
+    ctx->ex_stats[2] = w;
+    ctx->ex_short_dev = nullptr;
+  } else {
+    SV_HIP(hipStreamSynchronize(ctx->stream));
+  }
+  for (int i = 0; i < n && i < 4; ++i) stats_out[i] = ctx->ex_stats[i];
+  return SEGVLAD_OK;
+}
+
 int segvlad_merge_topk(segvlad_ctx* ctx, const float* d2_parts, const int64_t* idx_parts, int nq, int parts, int k,
                        float* d2_out, int64_t* idx_out) {
   CHECK_CTX();

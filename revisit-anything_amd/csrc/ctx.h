@@ -290,6 +290,13 @@ struct segvlad_ctx {
   // image -> row map -- describe the current index (cleared by segvlad_db_add / segvlad_db_reset, rebuilt by the next shortlist search)
   int db_img_max = -1;
   bool sl_map_valid = false;
+  // segvlad_search_excluding (exclude_kernels.hip): the host copy of sl_img_off (valid while the map it was copied from is), and the
+  // statistics of the last call -- [0] k_fetch, [1] max X_b, [3] images with excluded rows are the host's; [2], the rows the
+  // exact tail finished, is a device word fetched by segvlad_exclude_stats (null: no call yet, or the call flagged nothing by construction)
+  std::vector<uint32_t> sl_off_host;
+  bool sl_off_host_valid = false;
+  int64_t ex_stats[4] = {0, 0, 0, 0};
+  const uint32_t* ex_short_dev = nullptr;
   // device-driven single-image passes (small_pass_kernels.hip): the tail kernel's counters of the LAST such search live in device
   // memory and are fetched by segvlad_search_stats (the search itself never reads them back); its running totals reach the host
   // through two pinned words that segvlad_search looks at WITHOUT synchronising -- a database on which the low-rank thresholds
@@ -309,7 +316,8 @@ struct segvlad_ctx {
   X(db_hi) X(db_lo) X(db_f16) X(s_ref_keys) X(s_ref_tick) X(s_tail_tick) X(sl_img_off) X(sl_img_rows)
   //  scratch: grow-only, reused across calls, nothing in them is read after the call that wrote it; s_sh_*: exchange buffers of
   //  the row-sharded index (comm.hip); s_rm_*: removal flags, block counts / offsets and the source of every surviving row
-  //  (remove_kernels.hip)
+  //  (remove_kernels.hip); s_ex_*: the deep lists, row flags (+ the short-row counter), query norms and the tail's slot results of
+  //  segvlad_search_excluding (exclude_kernels.hip)
 #define SV_SCRATCH_BUFS(X)                                                                                                       \
   X(s_xt) X(s_labels) X(s_rnorm) X(s_gap) X(s_colmask) X(s_gscale) X(s_segimg) X(s_segoff) X(s_adjoff) X(s_dist) X(s_qnorm)      \
   X(s_misc) X(s_minmax) X(s_voteoff) X(s_cand_cnt) X(s_cand_d2) X(s_cand_id) X(s_thr_d2) X(s_thr_idx) X(s_flag) X(s_qh) X(s_ql)  \
@@ -318,6 +326,7 @@ struct segvlad_ctx {
   X(s_sel_todo) X(s_vote_keys) X(s_pz) X(s_rowbase) X(s_tilegrp) X(s_bn) X(s_l0part) X(s_ref_lim) X(s_sh_d2) X(s_sh_idx)          \
   X(s_sh_rec) X(s_sh_all) X(s_sh_d2c) X(s_sh_idc) X(s_grp_cnt) X(s_grp_ids) X(s_grp_rows) X(s_grp_keys) X(s_grp_work) X(s_grp_pos) X(s_tnk_redo) X(s_tail_part) X(s_km_part) X(s_km_cnt) X(s_kflush) \
   X(s_sl_misc) X(s_sl_q) X(s_sl_cur) X(s_sl_uids) X(s_sl_uoff) X(s_sl_unum) X(s_sl_cand) X(s_sl_lens)                            \
+  X(s_ex_d2) X(s_ex_idx) X(s_ex_flag) X(s_ex_qn) X(s_ex_td2) X(s_ex_tidx)                                                          \
   X(s_rm_row) X(s_rm_img) X(s_rm_blk) X(s_rm_src) X(s_rm_misc)
 #define SV_DECL_BUF(n) DevBuf n;
   SV_PERSISTENT_BUFS(SV_DECL_BUF)
@@ -555,6 +564,20 @@ int sv_launch_minmax(segvlad_ctx* ctx, const float* sims, int64_t count, float* 
 int sv_img_max(segvlad_ctx* ctx, const int32_t* img_dev, int64_t n, int* out);
 int sv_search_shortlist(segvlad_ctx* ctx, const float* Q, int nq, const float* qn, const int32_t* qoff, int n_img,
                         const int32_t* shortlist, int M, int k, float* d2_out, int64_t* idx_out);
+
+// search.hip: segvlad_search behind its checks and staging (q / d2 / idx on the device, nq >= 1, the index has a dimension)
+int sv_search_dev(segvlad_ctx* ctx, const float* q, int nq, int k, float* d2, int64_t* idx);
+// shortlist_kernels.hip, for segvlad_search_excluding: the image -> row map with its offsets mirrored in ctx->sl_off_host; and the
+// exact tail (see there)
+constexpr int SV_EX_MAX_E = 8;                  // exclusion intervals per query image
+constexpr int SV_EX_RANGES = SV_EX_MAX_E + 1;   // ... whose complement is at most this many ranges of image ids
+int sv_sl_map_host(segvlad_ctx* ctx);
+int sv_launch_exclude_tail(segvlad_ctx* ctx, const float* Q, const float* qn, const int32_t* groups, int ng, int gmax, int n_slots,
+                           const uint32_t* unum, const uint32_t* uoff, const uint32_t* ustart, int n_tab, const uint32_t* flags,
+                           int k, float* d2_tmp, int64_t* idx_tmp);
+// exclude_kernels.hip: segvlad_search_excluding after the argument checks (Q on the device, qoff / excl host, outputs on the device)
+int sv_search_excluding(segvlad_ctx* ctx, const float* Q, int nq, const int32_t* qoff, int n_img, const int32_t* excl, int E, int k,
+                        float* d2_out, int64_t* idx_out);
 
 // remove_kernels.hip (segvlad_db_remove): the keep flags of the listed rows / images, every surviving row's new position
 // (src_of_dst in ctx->s_rm_src, new_id [db_n] or null), then counts_host [3] = {n', survivors below plane_rows_a, below plane_rows_b}

@@ -1063,17 +1063,22 @@ extern "C" int segvlad_search(segvlad_ctx* ctx, const float* Q, int nq, int k, f
   if (!Q || !d2_out || !idx_out) return ctx->fail(SEGVLAD_ERR_ARG, "search: null pointer");
   if (ctx->db_d == 0) return ctx->fail(SEGVLAD_ERR_STATE, "search: the index is empty and has no dimension yet");
   if (ctx->opt.debug_fail_search == 1) return ctx->fail(SEGVLAD_ERR_STATE, "search: failing on request (option debug_fail_search)");
-  ctx->f16_scale_dev = nullptr;
   const void* dq;
   void *dd2, *didx;
   SV_TRY(sv_in(ctx, Q, (size_t)nq * ctx->db_d * 4, &dq));
   SV_TRY(sv_out(ctx, d2_out, (size_t)nq * k * 4, &dd2));
   SV_TRY(sv_out(ctx, idx_out, (size_t)nq * k * 8, &didx));
+  SV_TRY(sv_search_dev(ctx, (const float*)dq, nq, k, (float*)dd2, (int64_t*)didx));
+  return sv_finish(ctx);
+}
+
+// segvlad_search behind its argument checks and staging: q / d2 / idx on the device, nq >= 1, the index has a dimension.  Also the
+// inner search of segvlad_search_excluding (exclude_kernels.hip), which runs it at a larger depth into scratch of its own.
+int sv_search_dev(segvlad_ctx* ctx, const float* q, int nq, int k, float* d2, int64_t* idx) {
+  const void* dq = q;
+  ctx->f16_scale_dev = nullptr;
   SV_HIP(ctx->s_qnorm.reserve((size_t)nq * 4));
-  const float* q = (const float*)dq;
   float* qn = ctx->s_qnorm.as<float>();
-  float* d2 = (float*)dd2;
-  int64_t* idx = (int64_t*)didx;
   ctx->sstats = SvSearchStats();
   ctx->sstats.n_queries = nq;
   ctx->tail_stats_dev = nullptr;
@@ -1090,13 +1095,13 @@ extern "C" int segvlad_search(segvlad_ctx* ctx, const float* Q, int nq, int k, f
   if (ctx->db_n == 0) {   // emptied by segvlad_db_remove: every slot beyond the (zero) rows is (+inf, -1)
     SV_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d2), 0x7f800000, (size_t)nq * k, ctx->stream));
     SV_HIP(hipMemsetAsync(idx, 0xff, (size_t)nq * k * 8, ctx->stream));
-    return sv_finish(ctx);
+    return SEGVLAD_OK;
   }
   const SearchPlan p = plan_search(ctx, nq, k, dq);
   if (p.matrix) {
     SV_TRY(sv_launch_row_sumsq(ctx, q, nq, p.d, qn));
     SV_TRY(search_matrix(ctx, q, nq, p.n, p.d, k, qn, d2, idx));
-    return sv_finish(ctx);
+    return SEGVLAD_OK;
   }
   ctx->sstats.filter = (int)p.filter;
   ctx->sstats.levels = p.pass.levels;
@@ -1116,5 +1121,5 @@ extern "C" int segvlad_search(segvlad_ctx* ctx, const float* Q, int nq, int k, f
   // flags list overflows (-> exact distance-matrix path, alone)
   if (fb.flagged && !p.pass.guessed) SV_TRY(fallback_rows(ctx, p, q, qn, fb.rows(), nq, d2, idx));
   else if (fb.flagged) SV_TRY(redo_rows(ctx, p, v, q, qn, fb, d2, idx));
-  return sv_finish(ctx);
+  return SEGVLAD_OK;
 }

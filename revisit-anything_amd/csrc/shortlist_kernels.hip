@@ -23,6 +23,8 @@
 //                         (the k-th key); at the end every buffer is cut to <= k
 //     sl_final_kernel     per query row: its S slices' lists, (distance, id) sort, top k; (+inf, -1) beyond the allowed rows
 // Nothing is read back during a call: the grid sizes come from qseg_offsets, n_img, M and k (host), the union sizes stay on the device.
+// sl_gemm_kernel and sl_final_kernel also are the exact tail of segvlad_search_excluding (exclude_kernels.hip), whose "union" is the
+// complement of a few intervals of image ids: sv_launch_exclude_tail, at the end of this file.
 #include <algorithm>
 
 #include "ctx.h"
@@ -223,17 +225,23 @@ __global__ __launch_bounds__(256) void sl_union_kernel(const int32_t* __restrict
 #endif
 
 struct SlGroup {
-  int q0, nrows, img, pad;
+  int q0, nrows, img, pad;   // (pad: the group's first list slot in the exclusion's tail, unused by the shortlist search)
 };
 
-template <int MT>
+// EX (the exact tail of segvlad_search_excluding, exclude_kernels.hip): the "union" of group image b is the complement of its merged
+// exclusion intervals -- nu <= 9 contiguous ranges of sl_img_rows POSITIONS, uids[j] the first position of range j (not an image id)
+// and uoff the prefix sums of the ranges' lengths; a group none of whose rows is marked in ex_flags writes empty lists and leaves;
+// a group's lists go to cand / lens at its slot base (SlGroup::pad) instead of its query rows.  Everything else -- the operand
+// staging, the chain, sv_d2, the candidate buffers -- is the one code for both.
+template <int MT, bool EX>
 __global__ __launch_bounds__(256) void sl_gemm_kernel(const float* __restrict__ Q, const float* __restrict__ R, int d,
                                                       const float* __restrict__ qn, const float* __restrict__ rn,
                                                       const SlGroup* __restrict__ groups, int S, int M,
                                                       const uint32_t* __restrict__ off, const uint32_t* __restrict__ rows,
                                                       const uint32_t* __restrict__ uids, const uint32_t* __restrict__ uoff,
                                                       const uint32_t* __restrict__ unum, int k, int cap,
-                                                      uint64_t* __restrict__ cand, uint32_t* __restrict__ lens) {
+                                                      uint64_t* __restrict__ cand, uint32_t* __restrict__ lens,
+                                                      const uint32_t* __restrict__ ex_flags) {
   constexpr int KS = SL_KS;
   constexpr int LDR = KS + 4;
   constexpr int LPR = KS / 4;
@@ -254,6 +262,13 @@ __global__ __launch_bounds__(256) void sl_gemm_kernel(const float* __restrict__ 
   const SlGroup gr = groups[g];
   const int q0 = gr.q0, nrows = gr.nrows, b = gr.img;
   const int q_end = q0 + nrows;
+  const int o0 = EX ? gr.pad : q0;   // first list of the group in cand / lens
+  if constexpr (EX) {
+    if (!__syncthreads_or(threadIdx.x < nrows && ex_flags[q0 + threadIdx.x] != 0u)) {
+      if ((int)threadIdx.x < nrows) lens[(size_t)(o0 + threadIdx.x) * S + s] = 0u;
+      return;
+    }
+  }
   const int nu = (int)unum[b];
   const uint32_t* uo = uoff + (size_t)b * (M + 1);
   const uint32_t* ui = uids + (size_t)b * M;
@@ -267,7 +282,7 @@ __global__ __launch_bounds__(256) void sl_gemm_kernel(const float* __restrict__ 
   __syncthreads();
   // the k best keys of row r's buffer stay, the threshold becomes the k-th (a sort of the whole buffer by the workgroup)
   auto compact = [&](int r, int keep) {
-    uint64_t* buf = cand + ((size_t)(q0 + r) * S + s) * cap;
+    uint64_t* buf = cand + ((size_t)(o0 + r) * S + s) * cap;
     const int n = (int)s_cnt[r];
     int np2 = 2;
     while (np2 < n) np2 <<= 1;
@@ -294,7 +309,7 @@ __global__ __launch_bounds__(256) void sl_gemm_kernel(const float* __restrict__ 
           if ((int)uo[mid] <= p) lo = mid;
           else hi = mid - 1;
         }
-        id = rows[off[ui[lo]] + (uint32_t)(p - (int)uo[lo])];
+        id = rows[(EX ? ui[lo] : off[ui[lo]]) + (uint32_t)(p - (int)uo[lo])];
       }
       ids[tid] = id;   // (columns beyond U: row 0, computed and never used)
     }
@@ -377,7 +392,7 @@ __global__ __launch_bounds__(256) void sl_gemm_kernel(const float* __restrict__ 
     __syncthreads();
     // candidates: a wave per row, two columns per lane, appended in ballot order
     for (int r = w; r < nrows; r += 4) {
-      uint64_t* buf = cand + ((size_t)(q0 + r) * S + s) * cap;
+      uint64_t* buf = cand + ((size_t)(o0 + r) * S + s) * cap;
       const uint64_t thr = s_thr[r];
       uint32_t cnt = s_cnt[r];
 #pragma unroll
@@ -398,7 +413,7 @@ __global__ __launch_bounds__(256) void sl_gemm_kernel(const float* __restrict__ 
   }
   for (int r = 0; r < nrows; ++r)
     if ((int)s_cnt[r] > k) compact(r, k);
-  if (tid < nrows) lens[(size_t)(q0 + tid) * S + s] = s_cnt[tid];
+  if (tid < nrows) lens[(size_t)(o0 + tid) * S + s] = s_cnt[tid];
 }
 
 // ---- per query row: the slices' lists, (distance, id) order, top k -------------------------------------------------------
@@ -473,6 +488,19 @@ static int sl_build_map(segvlad_ctx* ctx) {
     SV_HIP(hipGetLastError());
   }
   ctx->sl_map_valid = true;
+  ctx->sl_off_host_valid = false;
+  return SEGVLAD_OK;
+}
+
+// the map, and ctx->sl_off_host = the host copy of sl_img_off [n_img_ref + 1] (segvlad_search_excluding counts an interval's rows
+// with it): copied when the map was rebuilt -- one synchronisation per index change, none per call
+int sv_sl_map_host(segvlad_ctx* ctx) {
+  SV_TRY(sl_build_map(ctx));
+  if (ctx->sl_off_host_valid) return SEGVLAD_OK;
+  ctx->sl_off_host.resize((size_t)ctx->db_img_max + 2);
+  SV_HIP(hipMemcpyAsync(ctx->sl_off_host.data(), ctx->sl_img_off.p, ctx->sl_off_host.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
+  SV_HIP(hipStreamSynchronize(ctx->stream));
+  ctx->sl_off_host_valid = true;
   return SEGVLAD_OK;
 }
 
@@ -521,12 +549,13 @@ int sv_search_shortlist(segvlad_ctx* ctx, const float* Q, int nq, const float* q
     const int mt = gmax > 32 ? 2 : 1;
     const size_t stage_bytes = std::max((size_t)(32 * mt + 128) * (SL_KS + 4) * 4, (size_t)cap * 8);
     const size_t glds = stage_bytes + (size_t)32 * mt * 128 * 4;
-    auto gk = mt == 2 ? sl_gemm_kernel<2> : sl_gemm_kernel<1>;
+    auto gk = mt == 2 ? sl_gemm_kernel<2, false> : sl_gemm_kernel<1, false>;
     SV_HIP(sv_max_dyn_lds(reinterpret_cast<const void*>(gk), glds));
     hipLaunchKernelGGL(gk, dim3((unsigned)(ng * S)), dim3(256), glds, ctx->stream, Q, ctx->db_rows.as<float>(), d, qn,
                        ctx->db_norms.as<float>(), (const SlGroup*)dgrp, S, M, ctx->sl_img_off.as<uint32_t>(),
                        ctx->sl_img_rows.as<uint32_t>(), ctx->s_sl_uids.as<uint32_t>(), ctx->s_sl_uoff.as<uint32_t>(),
-                       ctx->s_sl_unum.as<uint32_t>(), k, cap, ctx->s_sl_cand.as<uint64_t>(), ctx->s_sl_lens.as<uint32_t>());
+                       ctx->s_sl_unum.as<uint32_t>(), k, cap, ctx->s_sl_cand.as<uint64_t>(), ctx->s_sl_lens.as<uint32_t>(),
+                       (const uint32_t*)nullptr);
     SV_HIP(hipGetLastError());
     int np2 = 2;
     while (np2 < S * k) np2 <<= 1;
@@ -537,5 +566,45 @@ int sv_search_shortlist(segvlad_ctx* ctx, const float* Q, int nq, const float* q
     SV_HIP(hipGetLastError());
     sc.count(rebuilt ? 8 : 3);
   }
+  return SEGVLAD_OK;
+}
+
+// The exact tail of segvlad_search_excluding: sl_gemm_kernel<., true> over the allowed rows of every group that holds a flagged
+// query row, sl_final_kernel over the groups' n_slots list slots.  groups [ng] = {q0, nrows, table index, slot base} (HOST);
+// unum [n_tab], uoff [n_tab][10], ustart [n_tab][9] (HOST): the allowed position ranges of sl_img_rows per table entry;
+// flags [nq] device words; d2_tmp / idx_tmp [n_slots][k] device.  Two launches, nothing read back.
+int sv_launch_exclude_tail(segvlad_ctx* ctx, const float* Q, const float* qn, const int32_t* groups, int ng, int gmax, int n_slots,
+                           const uint32_t* unum, const uint32_t* uoff, const uint32_t* ustart, int n_tab, const uint32_t* flags,
+                           int k, float* d2_tmp, int64_t* idx_tmp) {
+  static_assert(sizeof(SlGroup) == 16, "groups are handed over as int32 quadruples");
+  constexpr int M = SV_EX_RANGES;
+  const int d = ctx->db_d;
+  const void *dgrp, *dnum, *doff, *dst;
+  SV_TRY(sv_in(ctx, groups, (size_t)ng * sizeof(SlGroup), &dgrp));
+  SV_TRY(sv_in(ctx, unum, (size_t)n_tab * 4, &dnum));
+  SV_TRY(sv_in(ctx, uoff, (size_t)n_tab * (M + 1) * 4, &doff));
+  SV_TRY(sv_in(ctx, ustart, (size_t)n_tab * M * 4, &dst));
+  const int cap = k <= 256 ? 1024 : 2048;
+  int S = std::max(1, std::min(SL_SLICES_MAX, (1536 + ng - 1) / std::max(ng, 1)));
+  while (S > 1 && (S * k > 8192 || (size_t)n_slots * S * cap * 8 > ((size_t)512 << 20))) --S;
+  SV_HIP(ctx->s_sl_cand.reserve((size_t)n_slots * S * cap * 8));
+  SV_HIP(ctx->s_sl_lens.reserve((size_t)n_slots * S * 4));
+  const int mt = gmax > 32 ? 2 : 1;
+  const size_t stage_bytes = std::max((size_t)(32 * mt + 128) * (SL_KS + 4) * 4, (size_t)cap * 8);
+  const size_t glds = stage_bytes + (size_t)32 * mt * 128 * 4;
+  auto gk = mt == 2 ? sl_gemm_kernel<2, true> : sl_gemm_kernel<1, true>;
+  SV_HIP(sv_max_dyn_lds(reinterpret_cast<const void*>(gk), glds));
+  hipLaunchKernelGGL(gk, dim3((unsigned)(ng * S)), dim3(256), glds, ctx->stream, Q, ctx->db_rows.as<float>(), d, qn,
+                     ctx->db_norms.as<float>(), (const SlGroup*)dgrp, S, M, ctx->sl_img_off.as<uint32_t>(),
+                     ctx->sl_img_rows.as<uint32_t>(), (const uint32_t*)dst, (const uint32_t*)doff, (const uint32_t*)dnum, k, cap,
+                     ctx->s_sl_cand.as<uint64_t>(), ctx->s_sl_lens.as<uint32_t>(), flags);
+  SV_HIP(hipGetLastError());
+  int np2 = 2;
+  while (np2 < S * k) np2 <<= 1;
+  const size_t flds = (size_t)np2 * 8;
+  if (flds > 48 * 1024) SV_HIP(sv_max_dyn_lds(reinterpret_cast<const void*>(sl_final_kernel), flds));
+  hipLaunchKernelGGL(sl_final_kernel, dim3((unsigned)n_slots), dim3(256), flds, ctx->stream, ctx->s_sl_cand.as<uint64_t>(),
+                     ctx->s_sl_lens.as<uint32_t>(), S, cap, k, np2, d2_tmp, idx_tmp);
+  SV_HIP(hipGetLastError());
   return SEGVLAD_OK;
 }

@@ -68,6 +68,93 @@ def check_shortlist(shortlist: np.ndarray, n_img: int, n_img_ref: int) -> None:
             raise ValueError(f"shortlist id {hi} >= the number of reference images {n_img_ref}")
 
 
+MAX_EXCLUDE_INTERVALS = 8   # E of segvlad_search_excluding
+
+
+def pad_intervals(lists, E: Optional[int] = None) -> np.ndarray:
+    """Ragged per-image exclusion intervals (a sequence, per query image, of ``(lo, hi)`` pairs of reference image ids, both
+    ends inclusive) -> the padded ``int32 [n_img][E][2]`` array of segvlad_search_excluding: each image's intervals in their
+    given order, then empty ones ``(0, -1)``.  E defaults to the longest list (at least 1); more than 8 raise ValueError."""
+    rows = []
+    for b, x in enumerate(lists):
+        r = np.asarray(x, dtype=np.int64)
+        if r.size == 0:
+            r = r.reshape(0, 2)
+        if r.ndim != 2 or r.shape[1] != 2:
+            raise ValueError(f"image {b}: intervals must be (lo, hi) pairs, got shape {tuple(r.shape)}")
+        rows.append(r)
+    longest = max((len(r) for r in rows), default=0)
+    E = max(1, longest) if E is None else int(E)
+    if not 1 <= E <= MAX_EXCLUDE_INTERVALS:
+        raise ValueError(f"E={E} intervals per image outside 1 .. {MAX_EXCLUDE_INTERVALS}")
+    if longest > E:
+        raise ValueError(f"an image holds {longest} intervals, more than E={E}")
+    out = np.empty((len(rows), E, 2), dtype=np.int32)
+    out[:, :, 0] = 0
+    out[:, :, 1] = -1
+    info = np.iinfo(np.int32)
+    for b, r in enumerate(rows):
+        if r.size and (r.min() < info.min or r.max() > info.max):
+            raise ValueError(f"image {b}: id out of the int32 range")
+        out[b, :len(r)] = r
+    return out
+
+
+def window_intervals(frame_ids, radius: int) -> np.ndarray:
+    """The exclusion array of a self-query: query image i is frame ``frame_ids[i]`` of the map, and must not match the frames
+    ``frame_ids[i] - radius .. frame_ids[i] + radius`` (radius 0: itself only).  ``int32 [n_img][1][2]``."""
+    f = np.asarray(frame_ids, dtype=np.int64).reshape(-1)
+    radius = int(radius)
+    if radius < 0:
+        raise ValueError(f"radius={radius} < 0")
+    info = np.iinfo(np.int32)
+    lo, hi = f - radius, f + radius
+    if f.size and (lo.min() < info.min or hi.max() > info.max):
+        raise ValueError("frame id +- radius out of the int32 range")
+    return np.stack([lo, hi], axis=1).astype(np.int32).reshape(-1, 1, 2)
+
+
+def merge_intervals(intervals) -> list:
+    """One image's ``(lo, hi)`` intervals with the empty ones (lo > hi) dropped, sorted, and overlapping or adjacent ones joined
+    -- what segvlad_search_excluding makes of them (there after clamping to the ids the index holds)."""
+    iv = sorted((int(lo), int(hi)) for lo, hi in np.asarray(intervals, dtype=np.int64).reshape(-1, 2) if lo <= hi)
+    out = []
+    for lo, hi in iv:
+        if out and lo <= out[-1][1] + 1:
+            out[-1][1] = max(out[-1][1], hi)
+        else:
+            out.append([lo, hi])
+    return [(lo, hi) for lo, hi in out]
+
+
+def excluded_rows(exclude, rows_per_image) -> np.ndarray:
+    """X_b of segvlad_search_excluding on the host: per query image the number of index rows its intervals cover, from
+    ``rows_per_image`` (rows of reference image 0, 1, ...).  ``exclude``: ``[n_img][E][2]``.  The inner search runs at depth
+    ``min(1024, k + max X_b)``; an image with ``k + X_b <= 1024`` never needs the exact tail."""
+    cum = np.concatenate([[0], np.cumsum(np.asarray(rows_per_image, dtype=np.int64))])
+    n = len(cum) - 1
+    ex = np.asarray(exclude, dtype=np.int64)
+    out = np.zeros(len(ex), dtype=np.int64)
+    for b in range(len(ex)):
+        for lo, hi in merge_intervals(ex[b]):
+            lo, hi = max(lo, 0), min(hi, n - 1)
+            if lo <= hi:
+                out[b] += cum[hi + 1] - cum[lo]
+    return out
+
+
+def check_intervals(exclude: np.ndarray, n_img: int) -> None:
+    """Host-side validation of an exclusion array: shape [n_img][E][2] with 1 <= E <= 8; raises ValueError otherwise."""
+    if exclude.ndim != 3 or exclude.shape[0] != n_img or exclude.shape[2] != 2:
+        raise ValueError(f"exclude must be [n_img={n_img}][E][2], got shape {tuple(exclude.shape)}")
+    if not 1 <= exclude.shape[1] <= MAX_EXCLUDE_INTERVALS:
+        raise ValueError(f"exclude holds E={exclude.shape[1]} intervals per image, outside 1 .. {MAX_EXCLUDE_INTERVALS}")
+    if exclude.size:
+        info = np.iinfo(np.int32)
+        if int(exclude.min()) < info.min or int(exclude.max()) > info.max:
+            raise ValueError("exclude: id out of the int32 range")
+
+
 class SegVLADEngine:
     """One context per (device, stream user).  Not thread-safe (the C context is not re-entrant)."""
 
@@ -632,6 +719,45 @@ class SegVLADEngine:
                     "search_shortlist")
         self._keep = [q, sl]
         return d2, idx
+
+    def search_excluding(self, Q, qseg_offsets, exclude, k: int):
+        """segvlad_search_excluding: per query row the exact top-k rows of the index whose image id lies in none of its query
+        image's intervals -- what a fresh index without those images returns.  ``qseg_offsets`` [n_img + 1] (host);
+        ``exclude``: host ``int32 [n_img][E][2]`` of inclusive ``[lo, hi]`` reference image ids (lo > hi: empty; E <= 8), or a
+        ragged list of ``(lo, hi)`` lists per image (padded by pad_intervals); window_intervals builds the self-query form.
+        Malformed input raises ValueError.  Returns device tensors (d2 [nq][k] fp32, idx [nq][k] int64) like search();
+        (+inf, -1) beyond the allowed rows.
+        Cost: the search runs once at depth ``k_fetch = min(1024, k + rows of the largest window)``, and that depth is what a
+        caller pays: a few per cent for a window of a few images, 1.4 - 1.8 x the plain search at depths 600 - 900
+        -- and 27 - 37 x once k_fetch reaches the depth at which the search plan leaves its filter levels for the
+        distance-matrix path (977 on a 1 M-row index: 19 images of 50 rows at k = 50).  Keep ``k + rows of the window`` below
+        that; for a larger window of ONE image, db_remove + search + db_add is cheaper today."""
+        q = _as(Q, np.float32, torch.float32)
+        nq = q.shape[0]
+        qo = np.ascontiguousarray(qseg_offsets, dtype=np.int32)
+        n_img = len(qo) - 1
+        if isinstance(exclude, torch.Tensor):
+            exclude = exclude.cpu().numpy()
+        if isinstance(exclude, np.ndarray) and exclude.ndim == 3:
+            ex = np.ascontiguousarray(exclude, dtype=np.int64)
+        else:
+            ex = pad_intervals(exclude).astype(np.int64)
+        check_intervals(ex, n_img)
+        ex = np.ascontiguousarray(ex, dtype=np.int32)
+        d2 = self._empty((nq, k), torch.float32)
+        idx = self._empty((nq, k), torch.int64)
+        self._stream()
+        self._check(self.lib.segvlad_search_excluding(self._h, _ptr(q), nq, _ptr(qo), n_img, _ptr(ex), int(ex.shape[1]), k,
+                                                      _ptr(d2), _ptr(idx)), "search_excluding")
+        self._keep = [q]
+        return d2, idx
+
+    def exclude_stats(self) -> dict:
+        """Statistics of the last search_excluding(): the depth of the inner search, the largest number of index rows a query
+        image excluded, the query rows the exact tail finished, the query images that excluded any row.  Synchronises."""
+        v = (C.c_int64 * 4)()
+        self._check(self.lib.segvlad_exclude_stats(self._h, v, 4), "exclude_stats")
+        return dict(zip(("k_fetch", "x_max", "tail_rows", "n_img_excluding"), [int(x) for x in v]))
 
     def merge_topk(self, d2_parts, idx_parts, parts: int, k: int):
         d = _as(d2_parts, np.float32, torch.float32)

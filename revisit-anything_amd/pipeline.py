@@ -187,16 +187,25 @@ class SegVLADPipeline:
 
     # ---- a10..a12: descriptors -> ranked reference images ----------------------------------------------
     def retrieve(self, qdesc: torch.Tensor, qseg_offsets: np.ndarray, k_search: int = 200, k_vote: int = 50, n_top: int = 5,
-                 mode: int = _lib.VOTE_WT_BORDA_IM, want_scores: bool = False, vote_depth_only: bool = False, shortlist=None):
+                 mode: int = _lib.VOTE_WT_BORDA_IM, want_scores: bool = False, vote_depth_only: bool = False, shortlist=None,
+                 exclude=None):
         """search k_search (place_rec_main.py:56) -> keep k_vote and 2-d^2 (:78-81) -> vote (:84).  vote_depth_only: search
         only as deep as the vote reads (the 200-wide lists are only pickled under save_results, :61-75): the same k_vote columns
         -- an exact search's first columns do not depend on its depth -- for a quarter of the refinement.
         shortlist: per query image the reference image ids its segments may match (engine.search_shortlist: an
         ``int32 [n_img][M]`` array, -1 padded, or a ragged list of lists): the search runs over those images' rows only, and
         the vote's global extrema (func_vpr.py:212-213) are taken over the filled slots -- a (+inf, -1) pad is a -inf
-        similarity, which the vote skips and which must not become the minimum."""
+        similarity, which the vote skips and which must not become the minimum.
+        exclude: per query image the intervals of reference image ids its segments must NOT match (engine.search_excluding:
+        ``int32 [n_img][E][2]`` or a ragged list; engine.window_intervals for a map queried with its own frames); the extrema
+        as for a shortlist.  Not together with ``shortlist`` (ValueError)."""
+        if shortlist is not None and exclude is not None:
+            raise ValueError("retrieve: give shortlist or exclude, not both")
         depth = k_vote if vote_depth_only else k_search
-        if shortlist is None:
+        if exclude is not None:
+            self.eng.hint_query_groups(qseg_offsets)
+            d2, idx = self.eng.search_excluding(qdesc, qseg_offsets, exclude, depth)
+        elif shortlist is None:
             self.eng.hint_query_groups(qseg_offsets)
             d2, idx = self.eng.search(qdesc, depth)
         else:
@@ -204,7 +213,7 @@ class SegVLADPipeline:
         self.last_search = (d2, idx)   # the full-depth lists: what `save_results` pickles (place_rec_main.py:61-75)
         sims, m = self.eng.sims_from_d2(d2, idx, k_vote)
         smin = smax = float("nan")
-        if shortlist is not None and mode == _lib.VOTE_WT_BORDA_IM:
+        if (shortlist is not None or exclude is not None) and mode == _lib.VOTE_WT_BORDA_IM:
             kept = sims[m >= 0]
             if kept.numel():
                 smin, smax = float(kept.min()), float(kept.max())

@@ -56,6 +56,9 @@ def removal_keep_mask(img_of_seg: torch.Tensor, row_ids=None, img_ids=None) -> t
 
 
 class ShardedSegmentIndex:
+    """A reference index split by rows over the ranks.  Excluding image-id windows per query image (engine.search_excluding)
+    is a single-index feature for now: the row-sharded search has no such form."""
+
     def __init__(self, backend, rank: Optional[int] = None, world: Optional[int] = None, group=None,
                  device: Optional[torch.device] = None, native_comm: bool = False):
         """native_comm: exchange through the C-ABI's own RCCL communicator (segvlad_comm_init / segvlad_search_sharded /
@@ -309,7 +312,8 @@ class QueryShardedRetrieval:
     Two transports, as ShardedSegmentIndex: a torch.distributed group (gloo / nccl), or ``native_comm=True`` -- the context's
     own RCCL communicator (segvlad_vote_global + segvlad_allgather_rows), the id travelling over torch.distributed's host
     channel.  The compute is delegated to a backend with the SegVLADEngine interface (db_reset, db_add, search, sims_from_d2,
-    minmax, vote; vote_global / allgather_rows / comm_* for native_comm)."""
+    minmax, vote; vote_global / allgather_rows / comm_* for native_comm).  Excluding image-id windows per query image
+    (engine.search_excluding) is a single-index feature for now: this class has no ``exclude`` option."""
 
     def __init__(self, backend, rank: Optional[int] = None, world: Optional[int] = None, group=None,
                  device: Optional[torch.device] = None, native_comm: bool = False):

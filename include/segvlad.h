@@ -253,6 +253,36 @@ int segvlad_search_excluding(segvlad_ctx* ctx, const float* Q, int nq, const int
                              const int32_t* excl, int E, int k, float* d2_out, int64_t* idx_out);
 int segvlad_exclude_stats(segvlad_ctx* ctx, int64_t* stats_out, int n);
 
+/* ---- exact range search: faiss IndexFlat::range_search (no reference counterpart: the reference only searches top-k,
+ *      place_rec_main.py:53-60, and turns distances into similarities with 2 - d^2, place_rec_main.py:78-81 -- a similarity
+ *      floor s on unit rows is the squared radius 2 - s).  Loop closure and map upkeep ask "which rows are closer than this?".
+ *      Q [nq][d] device or host.  radius2 [nq] fp32, device or host: one SQUARED radius per query row.
+ *      A pair (q, r) is a hit when d2(q, r) < radius2[q], strictly, as faiss.  d2 is exactly the value segvlad_search reports
+ *      for that pair (sequential fma dot product in k order, the stored row norms, fmaf(-2, dot, |q|^2 + |r|^2), negatives
+ *      set to 0): a hit list is, bit for bit, the entries of an unbounded segvlad_search list that lie below the radius.
+ *      A radius that is NaN, zero or negative yields no hit; +inf yields every row whose distance is neither NaN nor +inf; a
+ *      query row holding NaN yields no hit.
+ *      lims_out [nq + 1] int64, device or host: lims[0] = 0, row q's hits occupy slots lims[q] .. lims[q+1]-1.  Always
+ *      written, always the true counts.  n_total_out (HOST, may be NULL) = lims[nq].
+ *      d2_out / idx_out hold `capacity` slots each (device or host; both may be NULL when capacity == 0: a count-only call).
+ *      When lims[nq] <= capacity they receive the hits, each row's in ascending (d2, lower id) order, the order of
+ *      segvlad_search.  When lims[nq] > capacity they are NOT WRITTEN AT ALL, the call still returns SEGVLAD_OK, and the
+ *      caller allocates lims[nq] slots and calls again.  Slots beyond lims[nq] are never written.
+ *      An index that removal has emptied: all-zero lims.  No dimension yet: SEGVLAD_ERR_STATE.  nq == 0: OK.  Bad pointers /
+ *      negative sizes: SEGVLAD_ERR_ARG.  More than 2^32 - 1 index rows: SEGVLAD_ERR_LIMIT (candidate ids are 32-bit, as in
+ *      the search).  Works after any sequence of segvlad_db_add / segvlad_db_remove, like segvlad_search.  Deterministic: two
+ *      calls return the same bits.  Synchronises (the total has to reach the host).
+ *      How: d % 64 == 0 (d <= 8192) on more than 32 768 rows -- ONE pass of the search's fp16 filter over every row under
+ *      thr = radius2 with its rigorous margin, then the exact chain on every candidate; a row with more than 8192 candidates
+ *      (or a +inf radius), and every row of the other shapes or under option knn_filter = fp32, goes through exact fp32
+ *      distance blocks against slabs of the index, counted in one sweep and emitted in a second.  Stage timer "knn_range".
+ *      segvlad_range_stats: HOST array, up to 5 values, of the last segvlad_range_search -- [0] total hits, [1] query rows
+ *      finished by the long-row path, [2] max and [3] sum of the candidate-list lengths the filter produced, [4] the path
+ *      taken (0 exact blocks, 1 fp16 filter).                                                                            */
+int segvlad_range_search(segvlad_ctx* ctx, const float* Q, int nq, const float* radius2, int64_t* lims_out, float* d2_out,
+                         int64_t* idx_out, int64_t capacity, int64_t* n_total_out);
+int segvlad_range_stats(segvlad_ctx* ctx, int64_t* stats_out, int n);
+
 /* ---- merge of per-shard top-k lists (no reference counterpart: the reference is single-process).
  *      d2_parts/idx_parts [nq][parts*k] (shard-major within a row, global ids); output top-k by
  *      (distance, lower id).                                                                       */
@@ -280,7 +310,7 @@ int segvlad_vote(segvlad_ctx* ctx, const int64_t* idx, const float* sims, const 
                  int32_t* pred_out, double* score_out);
 
 /* ---- instrumentation: with profiling on, every kernel group of a stage ("incidence", "adjacency",
- *      "assign", "prep", "aggregate", "pca", "describe" (segvlad_describe as a whole: its parts overlap), "knn_level0", "knn_gemm", "knn_select", "knn_fallback", "knn_shortlist" (segvlad_search_shortlist), "knn_exclude" (the kernels segvlad_search_excluding adds to its inner search), "db_remove" (segvlad_db_remove), "vote") is bracketed by a HIP event pair
+ *      "assign", "prep", "aggregate", "pca", "describe" (segvlad_describe as a whole: its parts overlap), "knn_level0", "knn_gemm", "knn_select", "knn_fallback", "knn_shortlist" (segvlad_search_shortlist), "knn_exclude" (the kernels segvlad_search_excluding adds to its inner search), "knn_range" (the kernels of segvlad_range_search), "db_remove" (segvlad_db_remove), "vote") is bracketed by a HIP event pair
  *      on the context stream.  segvlad_stage_ms returns the SUM of the elapsed times (ms) and the number
  *      of kernel launches recorded for the stage since the last segvlad_profile_reset; it returns
  *      SEGVLAD_ERR_STATE if the stage has not run.  Replaces the (discarded) time.time() pair of

@@ -59,6 +59,9 @@ SIGNATURES = {
     "segvlad_search_excluding": (C.c_int, [c_ctx_p, _f32p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, _f32p,
                                             C.c_void_p]),
     "segvlad_exclude_stats": (C.c_int, [c_ctx_p, C.POINTER(C.c_int64), C.c_int]),
+    "segvlad_range_search": (C.c_int, [c_ctx_p, _f32p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                        C.POINTER(C.c_int64)]),
+    "segvlad_range_stats": (C.c_int, [c_ctx_p, C.POINTER(C.c_int64), C.c_int]),
     "segvlad_merge_topk": (C.c_int, [c_ctx_p, _f32p, C.c_void_p, C.c_int, C.c_int, C.c_int, _f32p, C.c_void_p]),
     "segvlad_sims_from_d2": (C.c_int, [c_ctx_p, _f32p, C.c_void_p, C.c_int, C.c_int, C.c_int, _f32p, C.c_void_p]),
     "segvlad_minmax": (C.c_int, [c_ctx_p, _f32p, C.c_int64, _f32p]),

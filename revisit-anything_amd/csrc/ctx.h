@@ -296,6 +296,7 @@ struct segvlad_ctx {
   std::vector<uint32_t> sl_off_host;
   bool sl_off_host_valid = false;
   int64_t ex_stats[4] = {0, 0, 0, 0};
+  int64_t rs_stats[5] = {0, 0, 0, 0, 0};   // segvlad_range_stats: total hits, long rows, max / sum of the candidate lists, path
   const uint32_t* ex_short_dev = nullptr;
   // device-driven single-image passes (small_pass_kernels.hip): the tail kernel's counters of the LAST such search live in device
   // memory and are fetched by segvlad_search_stats (the search itself never reads them back); its running totals reach the host
@@ -317,7 +318,10 @@ struct segvlad_ctx {
   //  scratch: grow-only, reused across calls, nothing in them is read after the call that wrote it; s_sh_*: exchange buffers of
   //  the row-sharded index (comm.hip); s_rm_*: removal flags, block counts / offsets and the source of every surviving row
   //  (remove_kernels.hip); s_ex_*: the deep lists, row flags (+ the short-row counter), query norms and the tail's slot results of
-  //  segvlad_search_excluding (exclude_kernels.hip)
+  //  segvlad_search_excluding (exclude_kernels.hip); s_rs_*: segvlad_range_search (range_kernels.hip) -- the effective radii and
+  //  filter thresholds, the long-row flags (+ the query preparation's flag block), per-row hit counts, where a short row's ordered
+  //  words sit in s_rs_stage, the long rows' offsets / cursors / words before and after their ordering, the dense query block of
+  //  the exact sweeps, the device lims of a host caller and a few counters
 #define SV_SCRATCH_BUFS(X)                                                                                                       \
   X(s_xt) X(s_labels) X(s_rnorm) X(s_gap) X(s_colmask) X(s_gscale) X(s_segimg) X(s_segoff) X(s_adjoff) X(s_dist) X(s_qnorm)      \
   X(s_misc) X(s_minmax) X(s_voteoff) X(s_cand_cnt) X(s_cand_d2) X(s_cand_id) X(s_thr_d2) X(s_thr_idx) X(s_flag) X(s_qh) X(s_ql)  \
@@ -327,7 +331,9 @@ struct segvlad_ctx {
   X(s_sh_rec) X(s_sh_all) X(s_sh_d2c) X(s_sh_idc) X(s_grp_cnt) X(s_grp_ids) X(s_grp_rows) X(s_grp_keys) X(s_grp_work) X(s_grp_pos) X(s_tnk_redo) X(s_tail_part) X(s_km_part) X(s_km_cnt) X(s_kflush) \
   X(s_sl_misc) X(s_sl_q) X(s_sl_cur) X(s_sl_uids) X(s_sl_uoff) X(s_sl_unum) X(s_sl_cand) X(s_sl_lens)                            \
   X(s_ex_d2) X(s_ex_idx) X(s_ex_flag) X(s_ex_qn) X(s_ex_td2) X(s_ex_tidx)                                                          \
-  X(s_rm_row) X(s_rm_img) X(s_rm_blk) X(s_rm_src) X(s_rm_misc)
+  X(s_rm_row) X(s_rm_img) X(s_rm_blk) X(s_rm_src) X(s_rm_misc)                                                                    \
+  X(s_rs_thr) X(s_rs_flag) X(s_rs_fb) X(s_rs_cnt) X(s_rs_soff) X(s_rs_stage) X(s_rs_loff) X(s_rs_cur) X(s_rs_words) X(s_rs_sorted)  \
+  X(s_rs_tmp) X(s_rs_rows) X(s_rs_q) X(s_rs_misc)
 #define SV_DECL_BUF(n) DevBuf n;
   SV_PERSISTENT_BUFS(SV_DECL_BUF)
   SV_SCRATCH_BUFS(SV_DECL_BUF)
@@ -578,6 +584,24 @@ int sv_launch_exclude_tail(segvlad_ctx* ctx, const float* Q, const float* qn, co
 // exclude_kernels.hip: segvlad_search_excluding after the argument checks (Q on the device, qoff / excl host, outputs on the device)
 int sv_search_excluding(segvlad_ctx* ctx, const float* Q, int nq, const int32_t* qoff, int n_img, const int32_t* excl, int E, int k,
                         float* d2_out, int64_t* idx_out);
+
+// range_kernels.hip (segvlad_range_search; see the kernels): thresholds and long-row flags from the radii; one chunk's list
+// statistics out_dev = {stage words needed, sum, max, long rows}; the exact evaluation + ordering of the short rows' lists into
+// `stage`; the counts -> offsets scan (flags != null: flagged rows only); the dense block of the listed query rows; one exact
+// distance block counted (words == null) or emitted; the ordering of the emitted segments; the unpacking of ordered words
+int sv_launch_range_thr(segvlad_ctx* ctx, const float* radius2, int nq, float* eff, float* thr, uint32_t* flags, bool all_long);
+int sv_launch_range_cand_stats(segvlad_ctx* ctx, const uint32_t* cand_cnt, int m, int cap, uint32_t* flags, uint64_t* out_dev);
+int sv_launch_range_refine(segvlad_ctx* ctx, const float* Q, const float* R, int m, int d, const float* qn, const float* rn,
+                           const float* eff, const uint32_t* cand_cnt, const uint32_t* cand_id, int cap, uint32_t list_max,
+                           const uint32_t* flags, uint32_t* cnt, int64_t* soff, uint64_t* stage, uint64_t* cursor);
+int sv_launch_range_scan(segvlad_ctx* ctx, const uint32_t* cnt, const uint32_t* flags, int nq, int64_t* lims);
+int sv_launch_range_gather(segvlad_ctx* ctx, const float* Q, const float* qn, const float* eff, const int32_t* rows, int nr, int d,
+                           float* Y, float* yn, float* yeff);
+int sv_launch_range_block(segvlad_ctx* ctx, const float* dist, int64_t ld, int mq, int ns, int64_t col0, const float* eff,
+                          const int32_t* rows, uint32_t* cnt, const int64_t* woff, uint32_t* cur, uint64_t* words);
+int sv_range_sort_segments(segvlad_ctx* ctx, const uint64_t* words, uint64_t* sorted, int64_t n_words, int nq, const int64_t* off);
+int sv_launch_range_unpack(segvlad_ctx* ctx, const uint64_t* src, const int64_t* srcoff, const uint32_t* flags, uint32_t want, int nq,
+                           const int64_t* lims, float* d2_out, int64_t* idx_out);
 
 // remove_kernels.hip (segvlad_db_remove): the keep flags of the listed rows / images, every surviving row's new position
 // (src_of_dst in ctx->s_rm_src, new_id [db_n] or null), then counts_host [3] = {n', survivors below plane_rows_a, below plane_rows_b}

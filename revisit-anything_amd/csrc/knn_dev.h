@@ -35,6 +35,29 @@ __device__ __forceinline__ void bitonic64(uint64_t* a, int n, int tid) {
   __syncthreads();
 }
 
+// The exact chain of every distance the search reports: the sequential fp32 fma dot product over k = 0 .. 4 n4 - 1 (what
+// refine_exact_kernel evaluates, bit for bit the fp32 distance GEMM's chain), with U 16-byte loads of the index row in flight
+// per lane (n4 % U == 0); the query row sits in LDS.
+template <int U>
+__device__ __forceinline__ float sv_dot_seq_(const float4* qp, const float4* __restrict__ rp, int n4) {
+  float acc = 0.f;
+  for (int t = 0; t < n4; t += U) {
+    float4 buf[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) buf[u] = rp[t + u];
+    __builtin_amdgcn_sched_barrier(0);   // every load is issued before the first fma (see refine_exact_kernel)
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const float4 qv = qp[t + u];
+      acc = fmaf(qv.x, buf[u].x, acc);
+      acc = fmaf(qv.y, buf[u].y, acc);
+      acc = fmaf(qv.z, buf[u].z, acc);
+      acc = fmaf(qv.w, buf[u].w, acc);
+    }
+  }
+  return acc;
+}
+
 // sum over the 64 lanes, returned wave-uniform: quad swaps, half-row and row mirrors (DPP: no LDS crossbar), then the four
 // row sums through readlane
 __device__ __forceinline__ uint32_t wave_sum_u32_(uint32_t v) {

@@ -450,6 +450,7 @@ static SearchPlan plan_search(const segvlad_ctx* ctx, int nq, int k, const void*
 // with the defaults.
 struct PassScalars {
   float c_eps = 0.f, inv_scale = 1.f, rn_max = 0.f, qscale = 1.f;
+  float qmax = 0.f;   // batch preparations: max |q| as read back (NaN / inf when a query holds one: segvlad_range_search looks at it)
 };
 
 // Flag block of one pass: [nrows] row flags, 2 counts (flagged rows, second-tier rows: ONE read-back per chunk), [mrows]
@@ -1023,6 +1024,7 @@ static int prepare_queries(segvlad_ctx* ctx, const SearchPlan& p, const float* q
       } else {
         SV_TRY(sv_maxabs(ctx, q, ne, &qmax));
       }
+      v.qmax = qmax;
       v.qscale = pow2_scale(qmax);
       SV_TRY(sv_launch_to_f16(ctx, q, ne, v.qscale, ctx->s_qf16.as<uint16_t>()));
       v.inv_scale = 1.f / (v.qscale * ctx->db_f16_scale);
@@ -1121,5 +1123,246 @@ int sv_search_dev(segvlad_ctx* ctx, const float* q, int nq, int k, float* d2, in
   // flags list overflows (-> exact distance-matrix path, alone)
   if (fb.flagged && !p.pass.guessed) SV_TRY(fallback_rows(ctx, p, q, qn, fb.rows(), nq, d2, idx));
   else if (fb.flagged) SV_TRY(redo_rows(ctx, p, v, q, qn, fb, d2, idx));
+  return SEGVLAD_OK;
+}
+
+// ---- segvlad_range_search ------------------------------------------------------------------------------------------
+// Every index row within a squared radius of each query row (faiss IndexFlat::range_search), in the search's own bits.
+//   filter path : ONE full-level fp16 filter launch per chunk under thr = radius2 with one margin (an exact d2 < r2 has
+//                 d2~ <= r2 + eps: the argument of the rigorous level 0), then range_refine_kernel evaluates every candidate with
+//                 the exact chain, keeps the hits and orders them.  A row whose list outgrew SV_CAP (the filter keeps counting),
+//                 or whose radius is +inf, is a LONG row.
+//   exact path  : small index, d % 64 != 0, option knn_filter = fp32, a NaN / inf among the queries: every row is a long row.
+//   long rows   : exact distance blocks (the fp32 distance GEMM: same chain, same bits) of those rows against slabs of the index,
+//                 counted in one sweep and -- once the offsets are known and the result fits -- emitted in a second one, each
+//                 row's segment then ordered by its 64-bit words.
+// The counts of all rows are scanned into lims on the device; the total reaches the host, and only a result that fits is unpacked.
+constexpr int64_t SV_RS_SLAB = 65536;   // index rows of one exact distance block
+constexpr int SV_RS_QBLOCK = 512;       // ... and its query rows (128 MiB of distances)
+
+// Grows a scratch buffer whose first `keep` bytes are still needed (the staged words of the chunks so far).
+static hipError_t regrow_keep(segvlad_ctx* ctx, DevBuf& b, size_t keep, size_t bytes) {
+  if (b.p && (b.guard ? bytes <= b.req : bytes <= b.cap)) return hipSuccess;
+  if (!keep || !b.p) return b.reserve(bytes);
+  DevBuf nb;
+  nb.tag = b.tag;
+  nb.guard = b.guard;
+  nb.fixed = b.fixed;
+  hipError_t e = nb.reserve(bytes + bytes / 2);
+  if (e != hipSuccess) return e;
+  e = hipMemcpyAsync(nb.p, b.p, keep, hipMemcpyDeviceToDevice, ctx->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+  if (e != hipSuccess) {
+    nb.release();
+    return e;
+  }
+  b.release();
+  b = nb;
+  return hipSuccess;
+}
+
+// One sweep of the exact distance blocks of the nl dense query rows (qx, their norms qnx, their radii effx; rows_dev: the row of
+// the call each one is) over the whole index: counted into cnt (words == null) or emitted.
+static int range_exact_sweep(segvlad_ctx* ctx, const float* qx, const float* qnx, const float* effx, const int32_t* rows_dev, int nl,
+                             uint32_t* cnt, const int64_t* woff, uint32_t* cur, uint64_t* words, int* launches) {
+  const int d = ctx->db_d;
+  const int64_t n = ctx->db_n;
+  const int64_t ld = (std::min(n, SV_RS_SLAB) + 3) & ~3ll;
+  SV_HIP(ctx->s_dist.reserve((size_t)std::min(nl, SV_RS_QBLOCK) * ld * 4));
+  for (int qb = 0; qb < nl; qb += SV_RS_QBLOCK) {
+    const int mq = std::min(nl - qb, SV_RS_QBLOCK);
+    for (int64_t c0 = 0; c0 < n; c0 += SV_RS_SLAB) {
+      const int ns = (int)std::min(n - c0, SV_RS_SLAB);
+      SV_TRY(sv_launch_gemm_nt(ctx, 1, qx + (size_t)qb * d, ctx->db_rows.as<float>() + (size_t)c0 * d, ctx->s_dist.as<float>(), mq, ns, d,
+                               ld, nullptr, nullptr, qnx + qb, ctx->db_norms.as<float>() + c0));
+      SV_TRY(sv_launch_range_block(ctx, ctx->s_dist.as<float>(), ld, mq, ns, c0, effx + qb, rows_dev + qb, cnt, woff, cur, words));
+      *launches += 2;
+    }
+  }
+  return SEGVLAD_OK;
+}
+
+// segvlad_range_search behind its checks: q / radius2 / lims on the device, nq >= 1, the index holds rows.
+static int range_search_dev(segvlad_ctx* ctx, const float* q, int nq, const float* radius2, int64_t* lims, float* d2_out, int64_t* idx_out,
+                            int64_t capacity, int64_t* total_out) {
+  const SvOptions& o = ctx->opt;
+  const int d = ctx->db_d;
+  const int64_t n = ctx->db_n;
+  const float* R = ctx->db_rows.as<float>();
+  const float* rn = ctx->db_norms.as<float>();
+  ctx->f16_scale_dev = nullptr;
+  StageScope sc(ctx, "knn_range");
+  SV_HIP(ctx->s_qnorm.reserve((size_t)nq * 4));
+  SV_HIP(ctx->s_rs_thr.reserve((size_t)nq * 8));
+  SV_HIP(ctx->s_rs_flag.reserve((size_t)nq * 4));
+  SV_HIP(ctx->s_rs_cnt.reserve((size_t)nq * 4));
+  SV_HIP(ctx->s_rs_soff.reserve((size_t)nq * 8));
+  SV_HIP(ctx->s_rs_misc.reserve(64));
+  float* qn = ctx->s_qnorm.as<float>();
+  float* eff = ctx->s_rs_thr.as<float>();
+  float* thr = eff + nq;
+  uint32_t* flags = ctx->s_rs_flag.as<uint32_t>();
+  uint32_t* cnt = ctx->s_rs_cnt.as<uint32_t>();
+  int64_t* soff = ctx->s_rs_soff.as<int64_t>();
+  uint64_t* misc = ctx->s_rs_misc.as<uint64_t>();   // [0] the stage cursor, [2..5] one chunk's list statistics
+  SV_HIP(hipMemsetAsync(cnt, 0, (size_t)nq * 4, ctx->stream));
+  SV_HIP(hipMemsetAsync(misc, 0, 64, ctx->stream));
+
+  // the filter path: where plan_search starts filtering, on the fp16 product; the refinement keeps a query row and up to SV_CAP
+  // words in LDS (d <= 8192) and reads rows in 16-byte pieces
+  bool filt = (o.knn_filter == 0 || o.knn_filter == 1) && d % 64 == 0 && d <= 8192 && n > 32768 && n <= 0x7fffffffLL &&
+              (reinterpret_cast<uintptr_t>(q) & 15) == 0;
+  SearchPlan p{nq, d, 1, n};
+  PassScalars v;
+  if (filt) {
+    // query preparation as the search's batches: norms, scale (read back), plane, the margin constant of the filter variant
+    // that runs -- the forms that only prepare, whatever the number of rows
+    p.filter = Filter::F16;
+    p.prep = Prep::BatchF16;
+    p.q2min = nq > 128 && (o.f16_cfg < 0 || o.f16_cfg == 250 || o.f16_cfg == 300);
+    p.mrows = std::min(nq, SV_CHUNK);
+    FlagBlock fb{&ctx->s_rs_fb, nq, p.mrows, false};
+    SV_TRY(prepare_index_planes(ctx, Filter::F16));
+    SV_HIP(ctx->s_qf16.reserve((size_t)nq * d * 2));
+    SV_HIP(ctx->s_cand_cnt.reserve((size_t)p.mrows * 4));
+    SV_HIP(ctx->s_cand_d2.reserve((size_t)p.mrows * SV_CAP * 4));
+    SV_HIP(ctx->s_cand_id.reserve((size_t)p.mrows * SV_CAP * 4));
+    SV_HIP(fb.buf->reserve(fb.bytes()));
+    SV_TRY(prepare_queries(ctx, p, q, fb, v));
+    sc.count(4);
+    // a NaN or inf among the queries: no scale serves the other rows' plane -- the exact path takes the call
+    if (!std::isfinite(v.qmax)) filt = false;
+  } else {
+    SV_TRY(sv_launch_row_sumsq(ctx, q, nq, d, qn));
+    sc.count();
+  }
+  SV_TRY(sv_launch_range_thr(ctx, radius2, nq, eff, thr, flags, !filt));
+  sc.count();
+  ctx->rs_stats[4] = filt ? 1 : 0;
+
+  int64_t n_long = filt ? 0 : nq;
+  if (filt) {
+    uint64_t used = 0;   // words of s_rs_stage the chunks so far may have filled
+    for (int q0 = 0; q0 < nq; q0 += SV_CHUNK) {
+      const int m = std::min(nq - q0, SV_CHUNK);
+      uint32_t* cand_cnt = ctx->s_cand_cnt.as<uint32_t>();
+      SV_HIP(hipMemsetAsync(cand_cnt, 0, (size_t)m * 4, ctx->stream));
+      SV_TRY(sv_launch_f16_filter(ctx, ctx->s_qf16.as<uint16_t>() + (size_t)q0 * d, ctx->db_f16.as<uint16_t>(), m, (int)n, d, 1, v.inv_scale,
+                                  qn + q0, rn, thr + q0, 1, 1.f, v.c_eps, v.rn_max, cand_cnt, ctx->s_cand_d2.as<float>(),
+                                  ctx->s_cand_id.as<uint32_t>(), SV_CAP));
+      SV_TRY(sv_launch_range_cand_stats(ctx, cand_cnt, m, SV_CAP, flags + q0, misc + 2));
+      uint64_t h[4] = {0, 0, 0, 0};   // words the short rows may stage, sum and max of the list lengths, long rows
+      SV_HIP(hipMemcpyAsync(h, misc + 2, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
+      SV_HIP(hipStreamSynchronize(ctx->stream));
+      ctx->rs_stats[3] += (int64_t)h[1];
+      ctx->rs_stats[2] = std::max<int64_t>(ctx->rs_stats[2], (int64_t)h[2]);
+      n_long += (int64_t)h[3];
+      const hipError_t e = regrow_keep(ctx, ctx->s_rs_stage, (size_t)used * 8, (size_t)std::max<uint64_t>(used + h[0], 1) * 8);
+      if (e != hipSuccess)
+        return ctx->fail(e == hipErrorOutOfMemory ? SEGVLAD_ERR_NOMEM : SEGVLAD_ERR_HIP, "range search: staging %llu candidate words: %s",
+                         (unsigned long long)(used + h[0]), hipGetErrorString(e));
+      SV_TRY(sv_launch_range_refine(ctx, q + (size_t)q0 * d, R, m, d, qn + q0, rn, eff + q0, cand_cnt, ctx->s_cand_id.as<uint32_t>(), SV_CAP,
+                                    (uint32_t)std::min<uint64_t>(h[2], SV_CAP), flags + q0, cnt + q0, soff + q0,
+                                    ctx->s_rs_stage.as<uint64_t>(), misc));
+      used += h[0];
+      sc.count(3);
+    }
+  }
+  ctx->rs_stats[1] = n_long;
+
+  // long rows: the dense block of their query rows, and the counting sweep
+  std::vector<int32_t> rows;
+  const float *qx = nullptr, *qnx = nullptr, *effx = nullptr;
+  if (n_long > 0) {
+    if (filt) {
+      SV_TRY(read_flagged(ctx, flags, nq, rows));
+    } else {
+      rows.resize(nq);
+      for (int r = 0; r < nq; ++r) rows[r] = r;
+    }
+    const size_t nl = rows.size();
+    SV_HIP(ctx->s_rs_rows.reserve(nl * 4));
+    SV_HIP(ctx->s_rs_q.reserve(nl * ((size_t)d + 2) * 4));
+    SV_HIP(hipMemcpyAsync(ctx->s_rs_rows.p, rows.data(), nl * 4, hipMemcpyHostToDevice, ctx->stream));
+    float* qxw = ctx->s_rs_q.as<float>();
+    qx = qxw;
+    qnx = qxw + nl * d;
+    effx = qxw + nl * d + nl;
+    SV_TRY(sv_launch_range_gather(ctx, q, qn, eff, ctx->s_rs_rows.as<int32_t>(), (int)nl, d, qxw, qxw + nl * d, qxw + nl * d + nl));
+    int launches = 1;
+    SV_TRY(range_exact_sweep(ctx, qx, qnx, effx, ctx->s_rs_rows.as<int32_t>(), (int)nl, cnt, nullptr, nullptr, nullptr, &launches));
+    sc.count(launches);
+  }
+
+  // counts -> lims; the long rows' own offsets; the totals to the host
+  int64_t total = 0, total_long = 0;
+  int64_t* loff = nullptr;
+  SV_TRY(sv_launch_range_scan(ctx, cnt, nullptr, nq, lims));
+  sc.count();
+  SV_HIP(hipMemcpyAsync(&total, lims + nq, 8, hipMemcpyDeviceToHost, ctx->stream));
+  if (n_long > 0) {
+    SV_HIP(ctx->s_rs_loff.reserve(((size_t)nq + 1) * 8));
+    loff = ctx->s_rs_loff.as<int64_t>();
+    SV_TRY(sv_launch_range_scan(ctx, cnt, flags, nq, loff));
+    sc.count();
+    SV_HIP(hipMemcpyAsync(&total_long, loff + nq, 8, hipMemcpyDeviceToHost, ctx->stream));
+  }
+  SV_HIP(hipStreamSynchronize(ctx->stream));   // (rows[] has been copied, too)
+  ctx->rs_stats[0] = total;
+  *total_out = total;
+  if (total == 0 || total > capacity) return SEGVLAD_OK;   // nothing to write, or the caller's buffers stay untouched
+
+  void *dd2 = nullptr, *didx = nullptr;
+  SV_TRY(sv_out(ctx, d2_out, (size_t)total * 4, &dd2));
+  SV_TRY(sv_out(ctx, idx_out, (size_t)total * 8, &didx));
+  if (filt) {
+    SV_TRY(sv_launch_range_unpack(ctx, ctx->s_rs_stage.as<uint64_t>(), soff, flags, 0u, nq, lims, (float*)dd2, (int64_t*)didx));
+    sc.count();
+  }
+  if (total_long > 0) {
+    SV_HIP(ctx->s_rs_cur.reserve((size_t)nq * 4));
+    SV_HIP(ctx->s_rs_words.reserve((size_t)total_long * 8));
+    SV_HIP(ctx->s_rs_sorted.reserve((size_t)total_long * 8));
+    SV_HIP(hipMemsetAsync(ctx->s_rs_cur.p, 0, (size_t)nq * 4, ctx->stream));
+    int launches = 0;
+    SV_TRY(range_exact_sweep(ctx, qx, qnx, effx, ctx->s_rs_rows.as<int32_t>(), (int)rows.size(), cnt, loff, ctx->s_rs_cur.as<uint32_t>(),
+                             ctx->s_rs_words.as<uint64_t>(), &launches));
+    SV_TRY(sv_range_sort_segments(ctx, ctx->s_rs_words.as<uint64_t>(), ctx->s_rs_sorted.as<uint64_t>(), total_long, nq, loff));
+    SV_TRY(sv_launch_range_unpack(ctx, ctx->s_rs_sorted.as<uint64_t>(), loff, flags, 1u, nq, lims, (float*)dd2, (int64_t*)didx));
+    sc.count(launches + 2);
+  }
+  return SEGVLAD_OK;
+}
+
+extern "C" int segvlad_range_search(segvlad_ctx* ctx, const float* Q, int nq, const float* radius2, int64_t* lims_out, float* d2_out,
+                                    int64_t* idx_out, int64_t capacity, int64_t* n_total_out) {
+  CHECK_CTX();
+  if (nq < 0 || capacity < 0) return ctx->fail(SEGVLAD_ERR_ARG, "range_search: need nq>=0 and capacity>=0");
+  if (!lims_out || (nq > 0 && (!Q || !radius2)) || (capacity > 0 && (!d2_out || !idx_out)))
+    return ctx->fail(SEGVLAD_ERR_ARG, "range_search: null pointer");
+  if (nq > 0 && ctx->db_d == 0) return ctx->fail(SEGVLAD_ERR_STATE, "range_search: the index is empty and has no dimension yet");
+  if (ctx->db_n > 0xffffffffLL) return ctx->fail(SEGVLAD_ERR_LIMIT, "range_search: %lld index rows (candidate ids are 32-bit)", (long long)ctx->db_n);
+  for (int64_t& s : ctx->rs_stats) s = 0;
+  if (n_total_out) *n_total_out = 0;
+  void* dlims;
+  SV_TRY(sv_out(ctx, lims_out, ((size_t)nq + 1) * 8, &dlims));
+  if (nq == 0 || ctx->db_n == 0) {   // no query rows, or an index that removal has emptied: all-zero lims
+    SV_HIP(hipMemsetAsync(dlims, 0, ((size_t)nq + 1) * 8, ctx->stream));
+    SV_HIP(hipStreamSynchronize(ctx->stream));
+    return sv_finish(ctx);
+  }
+  const void *dq, *drad;
+  SV_TRY(sv_in(ctx, Q, (size_t)nq * ctx->db_d * 4, &dq));
+  SV_TRY(sv_in(ctx, radius2, (size_t)nq * 4, &drad));
+  int64_t total = 0;
+  SV_TRY(range_search_dev(ctx, (const float*)dq, nq, (const float*)drad, (int64_t*)dlims, d2_out, idx_out, capacity, &total));
+  if (n_total_out) *n_total_out = total;
+  return sv_finish(ctx);
+}
+
+extern "C" int segvlad_range_stats(segvlad_ctx* ctx, int64_t* stats_out, int n) {
+  if (!ctx) return SEGVLAD_ERR_ARG;
+  if (!stats_out || n < 0) return ctx->fail(SEGVLAD_ERR_ARG, "range_stats: bad arguments");
+  for (int j = 0; j < n && j < 5; ++j) stats_out[j] = ctx->rs_stats[j];
   return SEGVLAD_OK;
 }

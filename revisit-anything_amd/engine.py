@@ -155,6 +155,76 @@ def check_intervals(exclude: np.ndarray, n_img: int) -> None:
             raise ValueError("exclude: id out of the int32 range")
 
 
+def radius2_from_sim(sim):
+    """Squared radius of a similarity floor: the reference turns distances into similarities with ``2 - d^2`` (unit rows), so
+    ``sim > s`` is ``d^2 < 2 - s``.  Scalar or array; fp32."""
+    out = np.float32(2.0) - np.asarray(sim, dtype=np.float32)
+    return np.float32(out) if out.ndim == 0 else out.astype(np.float32)
+
+
+def range_from_topk(d2, idx, radius2):
+    """Cut top-k lists at a radius: ``(lims, d2, idx)`` of the entries with ``d2 < radius2[q]`` (strictly), each row's in
+    list order -- what segvlad_range_search returns when the lists are deep enough.  ``d2`` / ``idx``: ``[nq][k]`` ascending
+    lists as search() returns them ((+inf, -1) beyond the index); ``radius2``: scalar or ``[nq]``.  A NaN, zero or negative
+    radius yields no hit.  Raises ValueError when a row's list is full (its last slot holds a row) and its last entry is still
+    below the radius: the list was too shallow to decide."""
+    d2 = np.asarray(d2, dtype=np.float32)
+    idx = np.asarray(idx, dtype=np.int64)
+    if d2.ndim != 2 or idx.shape != d2.shape:
+        raise ValueError(f"d2 / idx must be [nq][k] of one shape, got {d2.shape} and {idx.shape}")
+    nq, k = d2.shape
+    r = np.broadcast_to(np.asarray(radius2, dtype=np.float32), (nq,)) if np.ndim(radius2) == 0 else np.asarray(radius2, dtype=np.float32)
+    if r.shape != (nq,):
+        raise ValueError(f"radius2 must be a scalar or [nq={nq}], got shape {r.shape}")
+    with np.errstate(invalid="ignore"):
+        hit = (d2 < r[:, None]) & (idx >= 0) & (r[:, None] > 0)
+    if k > 0:
+        shallow = np.nonzero(hit[:, k - 1])[0]
+        if shallow.size:
+            raise ValueError(f"range_from_topk: the lists of {shallow.size} rows (first: {int(shallow[0])}) are full and still below "
+                             f"the radius at depth {k}: too shallow to decide")
+    lims = np.zeros(nq + 1, dtype=np.int64)
+    np.cumsum(hit.sum(1), out=lims[1:])
+    return lims, d2[hit].astype(np.float32), idx[hit].astype(np.int64)
+
+
+def range_image_counts(lims, idx, img_of_seg, qseg_offsets) -> list:
+    """The count vote over a radius: per query image the reference images its rows hit and how many hits each --
+    ``(image ids ascending int64, counts int64)``.  ``lims`` / ``idx``: a range result; ``img_of_seg [n_ref_seg]``: the image of
+    every index row; ``qseg_offsets [n_img + 1]``: the query images' rows."""
+    lims = np.asarray(lims, dtype=np.int64)
+    idx = np.asarray(idx, dtype=np.int64)
+    img = np.asarray(img_of_seg, dtype=np.int64)
+    qo = np.asarray(qseg_offsets, dtype=np.int64)
+    if qo.ndim != 1 or qo.size < 1 or qo[-1] + 1 != lims.size:
+        raise ValueError("qseg_offsets must end at the number of query rows of lims")
+    out = []
+    for b in range(qo.size - 1):
+        ids, cnt = np.unique(img[idx[lims[qo[b]]:lims[qo[b + 1]]]], return_counts=True)
+        out.append((ids.astype(np.int64), cnt.astype(np.int64)))
+    return out
+
+
+def expand_radius2(radius2, nq: int, qseg_offsets=None) -> np.ndarray:
+    """``radius2`` of range_search as one fp32 value per query row: a scalar, ``[nq]``, or -- with ``qseg_offsets`` --
+    ``[n_img]`` (repeated over each image's rows).  Raises ValueError on any other shape."""
+    r = np.asarray(radius2.detach().cpu().numpy() if isinstance(radius2, torch.Tensor) else radius2, dtype=np.float32)
+    if r.ndim == 0:
+        return np.full(nq, r, dtype=np.float32)
+    if qseg_offsets is not None:
+        qo = np.asarray(qseg_offsets, dtype=np.int64)
+        if qo.ndim != 1 or qo.size < 1 or qo[0] != 0 or qo[-1] != nq or np.any(np.diff(qo) < 0):
+            raise ValueError(f"qseg_offsets must rise from 0 to nq={nq}")
+        if r.shape == (qo.size - 1,) and r.shape != (nq,):
+            return np.repeat(r, np.diff(qo)).astype(np.float32)
+        if r.shape != (nq,):
+            raise ValueError(f"radius2 must be a scalar, [nq={nq}] or [n_img={qo.size - 1}], got shape {r.shape}")
+        return np.ascontiguousarray(r)
+    if r.shape != (nq,):
+        raise ValueError(f"radius2 must be a scalar or [nq={nq}], got shape {r.shape}")
+    return np.ascontiguousarray(r)
+
+
 class SegVLADEngine:
     """One context per (device, stream user).  Not thread-safe (the C context is not re-entrant)."""
 
@@ -758,6 +828,52 @@ class SegVLADEngine:
         v = (C.c_int64 * 4)()
         self._check(self.lib.segvlad_exclude_stats(self._h, v, 4), "exclude_stats")
         return dict(zip(("k_fetch", "x_max", "tail_rows", "n_img_excluding"), [int(x) for x in v]))
+
+    def range_search(self, Q, radius2, qseg_offsets=None, capacity: Optional[int] = None):
+        """segvlad_range_search: every index row with ``d2 < radius2`` of each query row (strictly; faiss range_search), the
+        distances bit for bit search()'s.  ``radius2``: SQUARED radii -- a scalar, ``[nq]`` (host, or a device tensor used
+        as it is), or with ``qseg_offsets`` one per query image (radius2_from_sim gives the radius of a similarity floor).
+        Returns device tensors ``(lims [nq + 1] int64, d2 [total] fp32, idx [total] int64)``: row q's hits, ascending
+        (d2, lower id), are ``lims[q] .. lims[q + 1] - 1``.  The first call offers ``capacity`` slots (default: the previous
+        call's total, else 4 nq); when the hits do not fit it is repeated once with the total it reported."""
+        q = _as(Q, np.float32, torch.float32)
+        nq = int(q.shape[0])
+        if isinstance(radius2, torch.Tensor) and radius2.is_cuda and radius2.dim() == 1 and qseg_offsets is None:
+            if tuple(radius2.shape) != (nq,):
+                raise ValueError(f"radius2 must be a scalar or [nq={nq}], got shape {tuple(radius2.shape)}")
+            r = radius2.to(torch.float32).contiguous()
+        else:
+            r = expand_radius2(radius2, nq, qseg_offsets)
+        if capacity is None:
+            capacity = getattr(self, "_range_total", 0) or 4 * nq
+        capacity = int(capacity)
+        if capacity < 0:
+            raise ValueError("capacity must be >= 0")
+        lims = self._empty((nq + 1,), torch.int64)
+        total = C.c_int64()
+        self._stream()
+        self.range_retried = False
+        while True:
+            d2 = self._empty((capacity,), torch.float32)
+            idx = self._empty((capacity,), torch.int64)
+            self._check(self.lib.segvlad_range_search(self._h, _ptr(q), nq, _ptr(r), _ptr(lims), _ptr(d2) if capacity else None,
+                                                      _ptr(idx) if capacity else None, capacity, C.byref(total)), "range_search")
+            if total.value <= capacity:
+                break
+            capacity = int(total.value)
+            self.range_retried = True
+        self._range_total = int(total.value)
+        self._keep = [q, r]
+        return lims, d2[:total.value], idx[:total.value]
+
+    def range_stats(self) -> dict:
+        """Statistics of the last range_search(): total hits, query rows finished by the long-row path, the longest and the
+        sum of the candidate lists the filter produced, the path taken ("exact" distance blocks or the "f16" filter)."""
+        v = (C.c_int64 * 5)()
+        self._check(self.lib.segvlad_range_stats(self._h, v, 5), "range_stats")
+        d = dict(zip(("total", "long_rows", "cand_max", "cand_sum", "path"), [int(x) for x in v]))
+        d["path"] = {0: "exact", 1: "f16"}[d["path"]]
+        return d
 
     def merge_topk(self, d2_parts, idx_parts, parts: int, k: int):
         d = _as(d2_parts, np.float32, torch.float32)

@@ -283,6 +283,42 @@ int segvlad_range_search(segvlad_ctx* ctx, const float* Q, int nq, const float* 
                          int64_t* idx_out, int64_t capacity, int64_t* n_total_out);
 int segvlad_range_stats(segvlad_ctx* ctx, int64_t* stats_out, int n);
 
+/* ---- mutual nearest segments between query images and candidate reference images (no reference counterpart as a batched
+ *      call: get_matches_for_single_image_pair, func_vpr.py:247-270, studies ONE query / reference pair on the host; this is
+ *      the verification step behind the vote -- does query image b really show candidate image c? -- whose counts and summed
+ *      similarities re-rank the vote's top-n).
+ *      Q [nq][d] device or host; qseg_offsets [n_img+1] int32 HOST as in segvlad_search_shortlist (0 rows allowed).
+ *      cand [n_img][C] int32 HOST: reference image ids (the img_of_seg values of segvlad_db_add), 1 <= C <= 64.  -1 is
+ *      padding -- segvlad_vote's pred_out can be passed as it is --, an id no row carries behaves like -1, and every slot is
+ *      evaluated on its own: a duplicate id gets the same answer twice.
+ *      For slot (b, j): A = the query rows of image b, B = the index rows whose image id is cand[b][j].  d2(q, r) is exactly
+ *      the value segvlad_search reports for the pair (sequential fma dot product in k order, the stored row norms,
+ *      fmaf(-2, dot, |q|^2 + |r|^2), negatives set to 0).  fwd(q) = the row of B with the smallest (d2, row id) -- what
+ *      segvlad_search_shortlist returns for the shortlist {cand[b][j]} at k = 1 --, bwd(r) = the row of A with the smallest
+ *      (d2, query row index); a NaN distance is never anyone's nearest.  The pair (q, fwd(q)) is MUTUAL when
+ *      bwd(fwd(q)) == q and d2 < max_d2, strictly: max_d2 = +inf admits every finite distance; NaN, zero or a negative value
+ *      admit none (the rule of segvlad_range_search's radii).
+ *      Outputs, device or host; all but n_mutual_out and score_out may be NULL:
+ *        n_mutual_out [n_img][C] int32   the number of mutual pairs (0 when A or B is empty)
+ *        score_out    [n_img][C] fp64    the sum over the mutual pairs, in ascending query-row order, of (double)(2.0f - d2):
+ *                                        the subtraction in fp32 as in segvlad_sims_from_d2, the additions in fp64 in that
+ *                                        fixed order -- a host loop reproduces it bit for bit
+ *        order_out    [n_img][C] int32   image b's slots sorted by (n_mutual desc, score desc, slot asc); slots that are -1
+ *                                        or carry no rows come last, in slot order: cand[b][order[b][j]] is the re-ranked list
+ *        fwd_idx_out  [nq][C] int64, fwd_d2_out [nq][C] fp32   fwd(q) and its distance; (-1, +inf) where B is empty
+ *        mutual_out   [nq][C] uint8      1 where (q, fwd(q)) is mutual, else 0
+ *      SEGVLAD_ERR_STATE without an img_of_seg map or with no dimension yet; SEGVLAD_ERR_LIMIT when d % 32 != 0 (the shortlist
+ *      search's limit); SEGVLAD_ERR_ARG on bad pointers, offsets, C, or nq != qseg_offsets[n_img].  nq == 0: OK; with n_img > 0 the per-image outputs are
+ *      still written (zero counts and scores, the slots that carry rows first).  Deterministic: two calls return the same bits.  Works after any sequence of segvlad_db_add /
+ *      segvlad_db_remove: it uses the image -> row map of segvlad_search_shortlist, whose offsets are mirrored on the host --
+ *      the FIRST call after the index changed synchronises once for that copy; otherwise the call does not synchronise when
+ *      every output is device memory (the grid and the scratch are sized on the host from cand; host outputs are copied back
+ *      behind one synchronisation).  Stage timer "match_pairs".  One index, one context: the row-sharded and query-sharded
+ *      classes have no counterpart yet.                                                                                  */
+int segvlad_match_pairs(segvlad_ctx* ctx, const float* Q, int nq, const int32_t* qseg_offsets, int n_img, const int32_t* cand, int C,
+                        float max_d2, int32_t* n_mutual_out, double* score_out, int32_t* order_out, int64_t* fwd_idx_out,
+                        float* fwd_d2_out, uint8_t* mutual_out);
+
 /* ---- merge of per-shard top-k lists (no reference counterpart: the reference is single-process).
  *      d2_parts/idx_parts [nq][parts*k] (shard-major within a row, global ids); output top-k by
  *      (distance, lower id).                                                                       */
@@ -310,7 +346,7 @@ int segvlad_vote(segvlad_ctx* ctx, const int64_t* idx, const float* sims, const 
                  int32_t* pred_out, double* score_out);
 
 /* ---- instrumentation: with profiling on, every kernel group of a stage ("incidence", "adjacency",
- *      "assign", "prep", "aggregate", "pca", "describe" (segvlad_describe as a whole: its parts overlap), "knn_level0", "knn_gemm", "knn_select", "knn_fallback", "knn_shortlist" (segvlad_search_shortlist), "knn_exclude" (the kernels segvlad_search_excluding adds to its inner search), "knn_range" (the kernels of segvlad_range_search), "db_remove" (segvlad_db_remove), "vote") is bracketed by a HIP event pair
+ *      "assign", "prep", "aggregate", "pca", "describe" (segvlad_describe as a whole: its parts overlap), "knn_level0", "knn_gemm", "knn_select", "knn_fallback", "knn_shortlist" (segvlad_search_shortlist), "knn_exclude" (the kernels segvlad_search_excluding adds to its inner search), "knn_range" (the kernels of segvlad_range_search), "match_pairs" (segvlad_match_pairs), "db_remove" (segvlad_db_remove), "vote") is bracketed by a HIP event pair
  *      on the context stream.  segvlad_stage_ms returns the SUM of the elapsed times (ms) and the number
  *      of kernel launches recorded for the stage since the last segvlad_profile_reset; it returns
  *      SEGVLAD_ERR_STATE if the stage has not run.  Replaces the (discarded) time.time() pair of

@@ -58,6 +58,8 @@ SIGNATURES = {
                                             C.c_void_p]),
     "segvlad_search_excluding": (C.c_int, [c_ctx_p, _f32p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, _f32p,
                                             C.c_void_p]),
+    "segvlad_match_pairs": (C.c_int, [c_ctx_p, _f32p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_float, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_void_p, _f32p, C.c_void_p]),
     "segvlad_exclude_stats": (C.c_int, [c_ctx_p, C.POINTER(C.c_int64), C.c_int]),
     "segvlad_range_search": (C.c_int, [c_ctx_p, _f32p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
                                         C.POINTER(C.c_int64)]),

@@ -1181,6 +1181,50 @@ int segvlad_search_shortlist(segvlad_ctx* ctx, const float* Q, int nq, const int
   return sv_finish(ctx);
 }
 
+int segvlad_match_pairs(segvlad_ctx* ctx, const float* Q, int nq, const int32_t* qseg_offsets, int n_img, const int32_t* cand, int C,
+                        float max_d2, int32_t* n_mutual_out, double* score_out, int32_t* order_out, int64_t* fwd_idx_out,
+                        float* fwd_d2_out, uint8_t* mutual_out) {
+  CHECK_CTX();
+  if (nq < 0 || n_img < 0 || C < 1 || C > 64)
+    return ctx->fail(SEGVLAD_ERR_ARG, "match_pairs: need nq, n_img >= 0, 1<=C<=64 (C=%d)", C);
+  if (!qseg_offsets) return ctx->fail(SEGVLAD_ERR_ARG, "match_pairs: null qseg_offsets");
+  if (sv_is_device_ptr(qseg_offsets)) return ctx->fail(SEGVLAD_ERR_ARG, "match_pairs: qseg_offsets must be host memory");
+  if (qseg_offsets[0] != 0 || qseg_offsets[n_img] != nq)
+    return ctx->fail(SEGVLAD_ERR_ARG, "match_pairs: qseg_offsets must run from 0 to nq=%d", nq);
+  for (int b = 0; b < n_img; ++b)
+    if (qseg_offsets[b + 1] < qseg_offsets[b]) return ctx->fail(SEGVLAD_ERR_ARG, "match_pairs: qseg_offsets decrease at %d", b);
+  if (n_img > 0 && !cand) return ctx->fail(SEGVLAD_ERR_ARG, "match_pairs: null cand");
+  if (cand && sv_is_device_ptr(cand)) return ctx->fail(SEGVLAD_ERR_ARG, "match_pairs: cand must be host memory");
+  if (ctx->db_d == 0) return ctx->fail(SEGVLAD_ERR_STATE, "match_pairs: the index is empty and has no dimension yet");
+  if (!ctx->db_has_img) return ctx->fail(SEGVLAD_ERR_STATE, "match_pairs: no img_of_seg map: give it to segvlad_db_add");
+  if (n_img == 0) return SEGVLAD_OK;   // (then nq == 0 too: nothing to write)
+  if ((nq > 0 && !Q) || !n_mutual_out || !score_out) return ctx->fail(SEGVLAD_ERR_ARG, "match_pairs: null pointer");
+  const int d = ctx->db_d;
+  if (nq > 0 && d % 32 != 0) return ctx->fail(SEGVLAD_ERR_LIMIT, "match_pairs: d=%d (the exact GEMM takes d %% 32 == 0)", d);
+  if (ctx->db_n > 0x7fffffffll) return ctx->fail(SEGVLAD_ERR_LIMIT, "match_pairs: more than 2^31 - 1 rows");
+  const void* dq = nullptr;
+  void *dn, *ds, *dord = nullptr, *dfi = nullptr, *dfd = nullptr, *dmu = nullptr;
+  SV_TRY(sv_out(ctx, n_mutual_out, (size_t)n_img * C * 4, &dn));
+  SV_TRY(sv_out(ctx, score_out, (size_t)n_img * C * 8, &ds));
+  if (order_out) SV_TRY(sv_out(ctx, order_out, (size_t)n_img * C * 4, &dord));
+  if (nq > 0) {   // (no query rows at all: every image is empty, the finish pass alone writes the zeros and the order)
+    SV_TRY(sv_in(ctx, Q, (size_t)nq * d * 4, &dq));
+    if ((reinterpret_cast<uintptr_t>(dq) & 15) != 0) {   // (a row-offset view of a device tensor: the GEMM loads 16-byte pieces)
+      SV_HIP(ctx->s_sl_q.reserve((size_t)nq * d * 4));
+      SV_HIP(hipMemcpyAsync(ctx->s_sl_q.p, dq, (size_t)nq * d * 4, hipMemcpyDeviceToDevice, ctx->stream));
+      dq = ctx->s_sl_q.p;
+    }
+    if (fwd_idx_out) SV_TRY(sv_out(ctx, fwd_idx_out, (size_t)nq * C * 8, &dfi));
+    if (fwd_d2_out) SV_TRY(sv_out(ctx, fwd_d2_out, (size_t)nq * C * 4, &dfd));
+    if (mutual_out) SV_TRY(sv_out(ctx, mutual_out, (size_t)nq * C, &dmu));
+    SV_HIP(ctx->s_qnorm.reserve((size_t)nq * 4));
+    SV_TRY(sv_launch_row_sumsq(ctx, (const float*)dq, nq, d, ctx->s_qnorm.as<float>()));
+  }
+  SV_TRY(sv_match_pairs(ctx, (const float*)dq, nq, ctx->s_qnorm.as<float>(), qseg_offsets, n_img, cand, C, max_d2, (int32_t*)dn,
+                        (double*)ds, (int32_t*)dord, (int64_t*)dfi, (float*)dfd, (uint8_t*)dmu));
+  return sv_finish(ctx);
+}
+
 int segvlad_search_excluding(segvlad_ctx* ctx, const float* Q, int nq, const int32_t* qseg_offsets, int n_img,
                              const int32_t* excl, int E, int k, float* d2_out, int64_t* idx_out) {
   CHECK_CTX();

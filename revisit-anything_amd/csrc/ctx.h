@@ -321,7 +321,8 @@ struct segvlad_ctx {
   //  segvlad_search_excluding (exclude_kernels.hip); s_rs_*: segvlad_range_search (range_kernels.hip) -- the effective radii and
   //  filter thresholds, the long-row flags (+ the query preparation's flag block), per-row hit counts, where a short row's ordered
   //  words sit in s_rs_stage, the long rows' offsets / cursors / words before and after their ordering, the dense query block of
-  //  the exact sweeps, the device lims of a host caller and a few counters
+  //  the exact sweeps, the device lims of a host caller and a few counters; s_mp_min: segvlad_match_pairs (match_kernels.hip) --
+  //  the row minima [nq][C], then the live slots' column minima, 64-bit keys
 #define SV_SCRATCH_BUFS(X)                                                                                                       \
   X(s_xt) X(s_labels) X(s_rnorm) X(s_gap) X(s_colmask) X(s_gscale) X(s_segimg) X(s_segoff) X(s_adjoff) X(s_dist) X(s_qnorm)      \
   X(s_misc) X(s_minmax) X(s_voteoff) X(s_cand_cnt) X(s_cand_d2) X(s_cand_id) X(s_thr_d2) X(s_thr_idx) X(s_flag) X(s_qh) X(s_ql)  \
@@ -333,7 +334,8 @@ struct segvlad_ctx {
   X(s_ex_d2) X(s_ex_idx) X(s_ex_flag) X(s_ex_qn) X(s_ex_td2) X(s_ex_tidx)                                                          \
   X(s_rm_row) X(s_rm_img) X(s_rm_blk) X(s_rm_src) X(s_rm_misc)                                                                    \
   X(s_rs_thr) X(s_rs_flag) X(s_rs_fb) X(s_rs_cnt) X(s_rs_soff) X(s_rs_stage) X(s_rs_loff) X(s_rs_cur) X(s_rs_words) X(s_rs_sorted)  \
-  X(s_rs_tmp) X(s_rs_rows) X(s_rs_q) X(s_rs_misc)
+  X(s_rs_tmp) X(s_rs_rows) X(s_rs_q) X(s_rs_misc)                                                                                 \
+  X(s_mp_min)
 #define SV_DECL_BUF(n) DevBuf n;
   SV_PERSISTENT_BUFS(SV_DECL_BUF)
   SV_SCRATCH_BUFS(SV_DECL_BUF)
@@ -584,6 +586,12 @@ int sv_launch_exclude_tail(segvlad_ctx* ctx, const float* Q, const float* qn, co
 // exclude_kernels.hip: segvlad_search_excluding after the argument checks (Q on the device, qoff / excl host, outputs on the device)
 int sv_search_excluding(segvlad_ctx* ctx, const float* Q, int nq, const int32_t* qoff, int n_img, const int32_t* excl, int E, int k,
                         float* d2_out, int64_t* idx_out);
+
+// match_kernels.hip: segvlad_match_pairs after the argument checks (Q on the device and 16-byte aligned, qn its squared norms, qoff /
+// cand host, outputs on the device; order_out / fwd_idx_out / fwd_d2_out / mutual_out may be null)
+int sv_match_pairs(segvlad_ctx* ctx, const float* Q, int nq, const float* qn, const int32_t* qoff, int n_img, const int32_t* cand, int C,
+                   float max_d2, int32_t* n_mutual_out, double* score_out, int32_t* order_out, int64_t* fwd_idx_out, float* fwd_d2_out,
+                   uint8_t* mutual_out);
 
 // range_kernels.hip (segvlad_range_search; see the kernels): thresholds and long-row flags from the radii; one chunk's list
 // statistics out_dev = {stage words needed, sum, max, long rows}; the exact evaluation + ordering of the short rows' lists into

@@ -68,6 +68,47 @@ def check_shortlist(shortlist: np.ndarray, n_img: int, n_img_ref: int) -> None:
             raise ValueError(f"shortlist id {hi} >= the number of reference images {n_img_ref}")
 
 
+MAX_CANDIDATES = 64   # C of segvlad_match_pairs
+
+
+def pad_candidates(lists, C: Optional[int] = None) -> np.ndarray:
+    """Ragged per-image candidate lists (a sequence of sequences of reference image ids, best first) -> the padded
+    ``int32 [n_img][C]`` array of segvlad_match_pairs: each row's ids in their given order, then -1.  C defaults to the longest
+    list (at least 1); more than 64 raise ValueError."""
+    rows = [np.asarray(x, dtype=np.int64).reshape(-1) for x in lists]
+    longest = max((len(r) for r in rows), default=0)
+    C = max(1, longest) if C is None else int(C)
+    if not 1 <= C <= MAX_CANDIDATES:
+        raise ValueError(f"C={C} candidates per image outside 1 .. {MAX_CANDIDATES}")
+    if longest > C:
+        raise ValueError(f"a candidate list holds {longest} ids, more than C={C}")
+    out = np.full((len(rows), C), -1, dtype=np.int32)
+    info = np.iinfo(np.int32)
+    for b, r in enumerate(rows):
+        if r.size and (r.min() < info.min or r.max() > info.max):
+            raise ValueError(f"candidate list {b}: id out of the int32 range")
+        out[b, :len(r)] = r
+    return out
+
+
+def check_candidates(cand: np.ndarray, n_img: int) -> None:
+    """Host-side validation of a padded candidate array: integers, shape [n_img][C] with 1 <= C <= 64, ids in -1 .. 2^31 - 1
+    (-1 is padding; an id no row carries is allowed and behaves like padding); raises ValueError otherwise."""
+    cand = np.asarray(cand)
+    if cand.dtype.kind not in "iu":
+        raise ValueError(f"candidates must be integers, got dtype {cand.dtype}")
+    if cand.ndim != 2 or cand.shape[0] != n_img:
+        raise ValueError(f"candidates must be [n_img={n_img}][C], got shape {tuple(cand.shape)}")
+    if not 1 <= cand.shape[1] <= MAX_CANDIDATES:
+        raise ValueError(f"candidate width C={cand.shape[1]} outside 1 .. {MAX_CANDIDATES}")
+    if cand.size:
+        lo, hi = int(cand.min()), int(cand.max())
+        if lo < -1:
+            raise ValueError(f"candidate id {lo} < -1 (-1 is the only padding value)")
+        if hi > np.iinfo(np.int32).max:
+            raise ValueError(f"candidate id {hi} out of the int32 range")
+
+
 MAX_EXCLUDE_INTERVALS = 8   # E of segvlad_search_excluding
 
 
@@ -821,6 +862,42 @@ class SegVLADEngine:
                                                       _ptr(d2), _ptr(idx)), "search_excluding")
         self._keep = [q]
         return d2, idx
+
+    def match_pairs(self, Q, qseg_offsets, cand, max_d2: float = float("inf"), want_rows: bool = False) -> dict:
+        """segvlad_match_pairs: for every query image b and candidate slot j, the mutual nearest pairs between the image's
+        query rows and the index rows of reference image ``cand[b][j]`` -- q and r pair up when r is q's nearest row of that
+        image, q is r's nearest row of the query image, and ``d2 < max_d2``.  ``qseg_offsets`` [n_img + 1] (host);
+        ``cand``: host ``int32 [n_img][C]`` (-1 padded, C <= 64; vote()'s ``pred`` as it is) or a ragged list of lists (padded
+        by pad_candidates); malformed input raises ValueError.  Returns device tensors: ``n_mutual`` int32 [n_img][C], ``score``
+        fp64 [n_img][C] (the pairs' summed ``2 - d2``), ``order`` int32 [n_img][C] (the slots by (n_mutual desc, score desc,
+        slot asc), slots without rows last); with ``want_rows`` also ``fwd_idx`` int64 / ``fwd_d2`` fp32 / ``mutual`` uint8
+        [nq][C]: every query row's nearest row of the slot's image, (-1, +inf) where it has none, and whether the pair is mutual."""
+        q = _as(Q, np.float32, torch.float32)
+        nq = int(q.shape[0])
+        qo = np.ascontiguousarray(qseg_offsets, dtype=np.int32)
+        n_img = len(qo) - 1
+        if isinstance(cand, torch.Tensor):
+            cand = cand.cpu().numpy()
+        if isinstance(cand, np.ndarray) and cand.ndim == 2:
+            cd = cand
+        else:
+            cd = pad_candidates(cand)
+        check_candidates(cd, n_img)
+        cd = np.ascontiguousarray(cd, dtype=np.int32)
+        Cw = int(cd.shape[1])
+        out = {"n_mutual": self._empty((n_img, Cw), torch.int32), "score": self._empty((n_img, Cw), torch.float64),
+               "order": self._empty((n_img, Cw), torch.int32)}
+        if want_rows:
+            out["fwd_idx"] = self._empty((nq, Cw), torch.int64)
+            out["fwd_d2"] = self._empty((nq, Cw), torch.float32)
+            out["mutual"] = self._empty((nq, Cw), torch.uint8)
+        self._stream()
+        self._check(self.lib.segvlad_match_pairs(self._h, _ptr(q), nq, _ptr(qo), n_img, _ptr(cd), Cw, float(max_d2),
+                                                 _ptr(out["n_mutual"]), _ptr(out["score"]), _ptr(out["order"]),
+                                                 _ptr(out.get("fwd_idx")), _ptr(out.get("fwd_d2")), _ptr(out.get("mutual"))),
+                    "match_pairs")
+        self._keep = [q]
+        return out
 
     def exclude_stats(self) -> dict:
         """Statistics of the last search_excluding(): the depth of the inner search, the largest number of index rows a query

@@ -220,6 +220,20 @@ class SegVLADPipeline:
         pred, sc = self.eng.vote(m, sims, qseg_offsets, n_top=n_top, mode=mode, want_scores=want_scores, smin=smin, smax=smax)
         return pred, sc, m, sims
 
+    # ---- behind the vote: candidate images re-ranked by one-to-one segment matching ------------------------------------------
+    def rerank(self, qdesc: torch.Tensor, qseg_offsets: np.ndarray, pred, max_d2: float = float("inf")):
+        """Re-ranks every query image's candidate reference images -- ``pred`` [n_img][C]: retrieve()'s predictions, -1 padded
+        -- by the mutual nearest segments between the query image and each candidate (engine.match_pairs; the use case of
+        get_matches_for_single_image_pair, func_vpr.py:247-270): more mutual pairs first, then the larger summed similarity,
+        then the vote's own order; candidates without rows last.  Returns ``(pred_reranked, n_mutual, score)``, each
+        [n_img][C] in the NEW order: ``pred_reranked[b] = pred[b][order[b]]``."""
+        cand = pred.cpu().numpy() if isinstance(pred, torch.Tensor) else np.asarray(pred)   # (the call takes its candidates on the host)
+        out = self.eng.match_pairs(qdesc, qseg_offsets, cand, max_d2=max_d2)
+        order = out["order"].to(torch.int64)
+        if not (isinstance(pred, torch.Tensor) and pred.device == order.device):
+            pred = torch.as_tensor(np.ascontiguousarray(cand), device=order.device)
+        return torch.gather(pred, 1, order), torch.gather(out["n_mutual"], 1, order), torch.gather(out["score"], 1, order)
+
 
 def recall_at(preds: np.ndarray, gt: List[Sequence[int]], n: int) -> List[float]:
     """calc_recall (func_vpr.py:396-422) without the print: first correct rank, queries with empty GT skipped."""

@@ -274,34 +274,30 @@ int segvlad_set_option(segvlad_ctx* ctx, const char* key, const char* value) {
     else return ctx->fail(SEGVLAD_ERR_ARG, "set_option(pca_path): want auto|planes|project, got '%s'", value);
     return SEGVLAD_OK;
   }
-  // Switches that select one of the fp16 filter's measured-and-not-kept kernel variants (csrc/segvlad_dev.h): the shipped
-  // library holds the default kernels only and accepts just the values that mean "the default"; development builds
-  // (-DSEGVLAD_ABLATIONS: lib/libsegvlad_hip_abl.so) hold every variant.
-  auto as_dev = [&](int* dst, std::initializer_list<int> product_values) -> int {
+  // Switches that select one of the fp16 filter's kernels (csrc/segvlad_dev.h): only the values that name a kernel the library
+  // holds are accepted -- the measured-and-not-kept variants are gone from the tree (DESIGN.md 4 / 7 keep their numbers); the
+  // development build (-DSEGVLAD_ABLATIONS: lib/libsegvlad_hip_abl.so) adds the probes of the batch kernel.
+  auto as_dev = [&](int* dst, std::initializer_list<int> product_values, std::initializer_list<int> probe_values = {}) -> int {
     int v = *dst;
     SV_TRY(as_int(&v));
-#ifndef SEGVLAD_ABLATIONS
     bool ok = false;
     for (int a : product_values) ok = ok || a == v;
-    if (!ok)
-      return ctx->fail(SEGVLAD_ERR_ARG, "set_option(%s=%d): a development switch -- this library holds the default kernel only "
-                       "(SEGVLAD_BUILD_ABLATIONS=1 builds lib/libsegvlad_hip_abl.so)", key, v);
+#ifdef SEGVLAD_ABLATIONS
+    for (int a : probe_values) ok = ok || a == v;
 #else
-    (void)product_values;
+    (void)probe_values;
 #endif
+    if (!ok)
+      return ctx->fail(SEGVLAD_ERR_ARG, "set_option(%s=%d): a development switch -- this library holds the default kernels only "
+                       "(SEGVLAD_BUILD_ABLATIONS=1 builds lib/libsegvlad_hip_abl.so with the probes of csrc/segvlad_dev.h)", key, v);
     *dst = v;
     return SEGVLAD_OK;
   };
-  if (!strcmp(key, "f16_cfg")) return as_dev(&o.f16_cfg, {-1, 250, 300, 62, 63});
+  if (!strcmp(key, "f16_cfg")) return as_dev(&o.f16_cfg, {-1, 250, 300, 62, 63}, {93, 94, 95});
   if (!strcmp(key, "f16_gm")) return as_int(&o.f16_gm);
   if (!strcmp(key, "f16_walk")) return as_int(&o.f16_walk);
-  if (!strcmp(key, "f16_epi")) return as_dev(&o.f16_epi, {-1, 1});
-  if (!strcmp(key, "f16_mf")) return as_dev(&o.f16_mf, {-1, 1});
   if (!strcmp(key, "f16_deep_cfg")) return as_dev(&o.f16_deep_cfg, {-1, 4, 5});
-  if (!strcmp(key, "f16_pp")) return as_dev(&o.f16_pp, {-1, 2});
-  if (!strcmp(key, "f16_small_mf")) return as_dev(&o.f16_small_mf, {0});
   if (!strcmp(key, "f16_buf")) return as_dev(&o.f16_buf, {-1, 0});
-  if (!strcmp(key, "f16_dsplit")) return as_dev(&o.f16_dsplit, {0});
   if (!strcmp(key, "tnk_gram")) return as_int(&o.tnk_gram);
   if (!strcmp(key, "tnk_fork")) return as_int(&o.tnk_fork);
   if (!strcmp(key, "x3_tile")) return as_int(&o.x3_tile);

@@ -139,21 +139,13 @@ struct SvOptions {
                           // launch_f16_filter); never changes a result
   int f16_persist_wgs = 32;   // resident workgroups per XCD of the persistent batch filter (1 .. 32): fewer leave CUs free for the whole
                           // launch to kernels of OTHER streams (the next batch's describe stage, bench.py --pipeline); never changes a result
-  int f16_mf = -1;        // MFMA shape of the persistent biased fp16 filter: 0 = 32 x 32 x 16, otherwise 16 x 16 x 32 (needs f16_epi != 0)
   int f16_deep_cfg = -1;  // deep rows (blocked accumulation): -1 / 5 = the persistent 256 x 256 ping-pong kernel with blocks flushed to a global
-                          // scratch where the launch fills it (>= 1024 tiles), 4 elsewhere; 4 = 8 waves of 64 x 64 on 256 x 128 tiles, 16 x 16 x 32 MFMA, plain loop;
-                          // 0 = 4 waves of 64 x 64 on 128 x 128 tiles, 32 x 32 x 16 MFMA (rounds 2-3); 1, 2, 3: measured variants
-                          // (sv_launch_f16_filter)
-  int f16_buf = -1;       // operand DMA as buffer_load ... lds: -1 = the deep-row kernel only (measured faster there, slower in the
-                          // batch kernel), 1 = both, 0 = neither
+                          // scratch where the launch fills it (>= 1024 tiles), 4 elsewhere; 4 = 8 waves of 64 x 64 on 256 x 128 tiles, 16 x 16 x 32 MFMA, plain loop
+                          // (sv_choose_f16_kernel)
+  int f16_buf = -1;       // operand DMA of the register-blocked deep-row kernel as buffer_load ... lds (measured faster there): -1 = yes, 0 = no
   int tnk_gram = 1;       // fused VLAD -> PCA, project form: block norms of tasks with <= 64 tokens from their Gram matrix on the
                           // 16-bit matrix pipe (gram_norms_kernel); 0 = the fp32 block sums for every task
   int tnk_fork = 1;       // the two-tile Gram kernel on the context's side stream, beside the one-tile kernel (0: one after the other)
-  int f16_dsplit = 0;     // batch kernel: pieces per phase whose DMA is issued from the MFMA segment instead of the load segment; -1: four of a phase's fragment reads issued from the previous MFMA segment; -2: a load segment's DMAs ahead of its fragment reads (A/B)
-  int f16_small_mf = 0;   // 1: the batch filter's small (non-persistent) levels on the 16 x 16 x 32 shape + wave-private epilogue (A/B)
-  int f16_pp = -1;        // main batch kernel: 0 = plain loop instead of the ping-pong loop (A/B)
-  int f16_epi = -1;       // epilogue of the persistent biased fp16 filter: 0 = workgroup-level reservation (one global atomic per
-                          // row and tile, two workgroup barriers), 1 = wave-private (one global atomic per survivor, no barrier)
   int x3_tile = 0;        // PCA split GEMM tile (0 = from the shape, 128, 256)
   int x3_gm = -1;         // PCA split GEMM XCD-aware block height (-1 = default of the kernel, 0 = plain order)
   int search_stats = 0;   // 1: segvlad_search records list occupancies (synchronises once per chunk)
@@ -200,11 +192,25 @@ inline int sv_f16_kblock(const SvOptions& o, int d) {
 // SV_F16_KFLUSH k-tiles of 64 flushed into a global scratch (knn_f16_filter_kernel, KFL) -- the block length the error constant
 // of a search has to cover (the smaller levels run the register-blocked kernel, whose bound is smaller).
 constexpr int SV_F16_KFLUSH = 64;
-inline int sv_f16_eps_kblock(const SvOptions& o, int d) {
-  const int kb = sv_f16_kblock(o, d);
-  if (!kb) return 0;
-  return (o.f16_deep_cfg < 0 || o.f16_deep_cfg == 5) ? SV_F16_KFLUSH * 64 : kb;
-}
+int sv_f16_eps_kblock(const SvOptions& o, int d);   // knn_filter_kernels.hip: from the configuration of the kernel that runs
+// May a search of nq query rows take a biased-accumulator kernel (batches on the default configurations)?  Then it reads back
+// min ||q||^2 with the scale: the bias enters the margin (sv_f16_c_eps, bias_mult).
+inline bool sv_f16_bias_possible(const SvOptions& o, int64_t nq) { return nq > 128 && (o.f16_cfg < 0 || o.f16_cfg == 250 || o.f16_cfg == 300); }
+// The kernels of the fp16 filter (knn_filter_kernels.hip holds one configuration type per name) and the rule that picks one
+// for a launch: sv_launch_f16_filter, sv_f16_filter_skip_ok and sv_f16_eps_kblock all ask sv_choose_f16_kernel.
+enum class F16Kernel {
+  None, BatchDefault, BatchComplement, BatchSmall, BatchUnbiased, BatchUnbiasedSmall, DeepFlush, DeepFlushComplement, DeepBlockedBuf, DeepBlocked,
+  DeepBlockedBufComplement, DeepBlockedComplement, DeepUnbiased, OneImage64, OneImage128,
+#ifdef SEGVLAD_ABLATIONS
+  ProbePhases, ProbeNoEpilogue, ProbeNoEpilogueNoDma,
+#endif
+};
+struct F16Choice {
+  F16Kernel kernel;
+  const char* why;   // kernel == None: the reason
+};
+// M x n_rows: the launch; skip = 16: over the complement of the stride-16 sample; bias_ok: segvlad_ctx::f16_bias_ok of the search
+F16Choice sv_choose_f16_kernel(const SvOptions& o, bool bias_ok, int M, int64_t n_rows, int d, int b_stride, int skip);
 // |d2~ - d2| <= sv_f16_c_eps * ||q|| * ||r|| for the single-product fp16 filter (25 % slack included):
 //   2^-10        both operands rounded to fp16 (relative 2^-11 each; products of two fp16 are exact in fp32),
 //   2^-22        power-of-two scaling, sub-normal operands, second-order terms,
@@ -462,6 +468,7 @@ int sv_launch_bf16_filter(segvlad_ctx* ctx, const uint16_t* Qh, const uint16_t* 
                           int M, int n_sample, int d, int b_stride, const float* qn, const float* rn, const float* thr,
                           int64_t thr_ld, float eps_mult, float c_eps, float rn_max, uint32_t* cand_cnt, float* cand_d2,
                           uint32_t* cand_id, int cap);
+// knn_candidate_kernels.hip (the filters' candidate lists: select, exact refinement; sv_launch_l0_reduce_rank above lives there too)
 // rank: which order statistic of the list is A (mode 0: the next level's threshold; mode 1: k).  check != 0 (heuristic
 // thresholds): mode 0 flags a list shorter than rank, mode 1 flags A > thr_in[row * thr_in_ld] (the threshold the list was
 // collected under).  Flagged rows (also: list overflow) are marked in fail_rows and counted once in *fail_count.

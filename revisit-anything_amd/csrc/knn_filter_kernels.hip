@@ -17,18 +17,15 @@
 //                            16-B coalesced global loads -> registers -> XOR-swizzled LDS (conflict-free
 //                            ds_read_b128 fragments), double-buffered LDS, two register stages in flight;
 //                            epilogue appends (d2~, id) with d2~ <= thr + margin to the candidate lists
-//   select_approx_kernel     per query: sort candidates by d2~; intermediate level: A_k (k-th smallest);
-//                            last level: the refine list {d2~ <= A_k + 2 eps}
-//   refine_exact_kernel      per query: exact fp32 distances of the refine list, sort, top-k
-//   select_wg_kernel / refine_exact_small_kernel   the same two steps for ONE query image per pass (<= 128 lists): a
-//                            workgroup per list, refinement lists shared by workgroups
+//   knn_f16_filter_kernel    the default filter: one fp16 product, one configuration type per kernel the library holds,
+//                            sv_choose_f16_kernel picks one per launch
+// (select_approx_kernel, refine_exact_kernel and the single-image forms of both: knn_candidate_kernels.hip)
 #include <stdlib.h>
 
 #include <stdio.h>
 
 #include "ctx.h"
 #include "knn_dev.h"
-#include "small_pass_dev.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
@@ -473,31 +470,18 @@ __device__ __forceinline__ void wait_vm_lgkm0() {  // s_waitcnt needs a literal 
 // wave-instruction fills 1 KiB of the LDS image, lane l landing at base + 16 l, i.e. RP = 1024 / row_bytes rows
 // of HBK fp16.  The LDS image must be lane-linear, so the bank-conflict swizzle is applied on the SOURCE side:
 // the lane that owns physical chunk p of row r fetches logical chunk p ^ f(r), and the MFMA fragment reads apply
-// the same involution (f(r) = (r >> 1) & 7 for 128-B rows, (r >> 2) & 3 for 64-B rows: a 16-lane ds_read_b128
-// group then covers all 16 bank slots).
-//   BM x BN tile, WM x WN waves, HBK k per tile, two A stages (queries: L2 resident) and NB B stages (database
-//   rows stream from HBM/MALL; NB = 3 keeps their DMA two k-tiles ahead via a counted vmcnt).
-// ABL == 9: phase timing (s_memtime of wave 0 at the phase boundaries, summed over workgroups; SEGVLAD_F16_CFG=90 prints it)
+// the same involution (f(r) = (r >> 1) & 7 for the 128-byte rows of a k-tile: a 16-lane ds_read_b128 group then covers
+// all 16 bank slots).
+//   BM x BN tile, WM x WN waves, HBK = 64 k per tile, two A stages (queries: L2 resident) and NB = 3 B stages (database
+//   rows stream from HBM/MALL; their DMA runs two k-tiles ahead via a counted vmcnt).
+// PROBE == 1 (development build): phase timing (s_memtime of wave 0 at the phase boundaries, summed over workgroups; f16_cfg = 93 prints it)
 __device__ unsigned long long sv_f16_phase_cycles[8];
 #define SV_PHASE(k)                                                                          \
-  if (ABL == 9 || ABL == 12) {                                                                            \
+  if (PROBE == 1) {                                                                          \
     const unsigned long long now_ = __builtin_amdgcn_s_memtime();                            \
     if (threadIdx.x == 0) atomicAdd(&sv_f16_phase_cycles[k], now_ - phase_t0);               \
     phase_t0 = now_;                                                                         \
   }
-
-// Accumulator element for the epilogue.  FROM_AGPR (the 128 x 128 wave tiles: 256 accumulator registers per lane, held in
-// AGPRs by the MFMA loop): read through an explicit v_accvgpr_read so that the value STAYS in its AGPR until this use --
-// left to itself the register allocator copies all 256 to VGPRs at the loop exit and spills half of them to scratch.
-template <bool FROM_AGPR>
-__device__ __forceinline__ float acc_elem(const f32x16& v, int r) {
-  if (FROM_AGPR) {
-    float x;
-    asm volatile("v_accvgpr_read_b32 %0, %1" : "=v"(x) : "a"(v[r]));
-    return x;
-  }
-  return v[r];
-}
 
 // fire-and-forget fp32 add at L2 (`global_atomic_add_f32` without return: no register, no wait)
 __device__ __forceinline__ void sv_atomic_add_noret(float* p, float v) {
@@ -509,15 +493,16 @@ __device__ __forceinline__ void sv_atomic_add_noret(float* p, float v) {
 #endif
 }
 
-// POL: cache policy of the operand DMA (never changes a result): bit 0 = database rows (B) non-temporal, bit 1 = queries (A)
-// PP : 0 = every wave runs the k-tile as one segment (one barrier per k-tile); PP > 0 = "ping-pong": the k-tile is cut
-//      into PP phases of [load segment: LDS fragment reads + DMA issue][barrier][MFMA segment][barrier], and the second
+// The members of a configuration type (below: one type per kernel the library holds):
+// POL: cache policy of the operand DMA (never changes a result): 1 = database rows (B) non-temporal
+// PP : 0 = every wave runs the k-tile as one segment (one barrier per k-tile); 2 = "ping-pong": the k-tile is cut
+//      into two phases of [load segment: LDS fragment reads + DMA issue][barrier][MFMA segment][barrier], and the second
 //      half of the waves (the SIMD partners of the first half: waves w and w + NW/2 share a SIMD) runs one barrier
 //      behind, so that on every SIMD one wave feeds the matrix pipe while its partner reads LDS and issues DMA.
 // KBT: > 0 = BLOCKED accumulation (deep rows, e.g. raw K*D = 98 304-d descriptors): every KBT k-tiles the MFMA accumulators
 //      are added into a second register set and cleared, so that the fp32 accumulation error of a dot product is bounded
 //      by (2 KBT HBK + d / (KBT HBK)) 2^-24 sum|q_i r_i| instead of 2 d 2^-24 sum|q_i r_i| -- whatever the matrix pipe's
-//      internal summation order is (see sv_f16_c_eps).  Needs the plain loop (PP == 0) and 2 x TM x TN x 16 accumulators.
+//      internal summation order is (see sv_f16_c_eps).  Needs the plain loop (PP == 0) and a second set of accumulators.
 // BIAS: the accumulators START at -||r||^2 / 2 (in the scaled domain) instead of 0, so that at the end of the k-loop they
 //      hold dot - ||r||^2 / 2 -- the quantity the epilogue screens -- and the per-element subtraction of pass 1 (four of its
 //      seven VALU instructions per four elements) disappears; d2~ = ||q||^2 - 2 acc / scale.  The column norms are fetched
@@ -554,9 +539,58 @@ typedef int sv_rsrc_t;
 //      every piece offset of a tile below 4 GiB (the launcher checks).  tools/ubench/mfma_peak: 1317 -> 1345 TF for the loop
 //      of this kernel's byte : flop ratio; the deep-row kernel 126.4 -> 125.2 ms; the ping-pong batch kernel 18.19 -> 18.70 ms
 //      (slower: its default stays global_load_lds).
-template <int BM, int BN, int WM, int WN, int HBK, int NB, int ABL = 0, bool PERSIST = false, int POL = 0, int PP = 0, int KBT = 0,
-          bool BIAS = false, int EPI = 0, int MF = 0, bool BUF = false, int DSPLIT = 0, int SKIP = 0, int KFL = 0>
-__global__ __launch_bounds__(64 * WM * WN) void knn_f16_filter_kernel(
+// ---- the kernels the library holds: one configuration type per kernel, variants derived from their base ----------------
+// (every kernel: k-tiles of SV_F16_HBK = 64, SV_F16_NB = 3 database stages, wave tiles of 64 rows.  The variants that were
+//  measured on the way and not kept -- other tile shapes, 32-deep k-tiles, a software-pipelined loop, other DMA placements --
+//  are described in DESIGN.md 4 / 7 with their numbers.)
+constexpr int SV_F16_HBK = 64, SV_F16_NB = 3;
+struct F16BatchUnbiasedSmall {   // 8 waves of 64 x 128 on a 256 x 256 tile, ping-pong loop, 32 x 32 x 16 MFMA, workgroup-level epilogue
+  static constexpr int BM = 256, BN = 256, WM = 4, WN = 2;
+  static constexpr bool PERSIST = false;
+  static constexpr int POL = 0, PP = 2, KBT = 0;
+  static constexpr bool BIAS = false;
+  static constexpr int EPI = 0, MF = 0;
+  static constexpr bool BUF = false;
+  static constexpr int SKIP = 0, KFL = 0;
+  static constexpr int PROBE = 0;   // development build: 1 = phase timing, 2 = no epilogue, 3 = no epilogue and no DMA in the k-loop
+};
+struct F16BatchUnbiased : F16BatchUnbiasedSmall { static constexpr bool PERSIST = true; };   // launches of >= 1024 tiles
+struct F16BatchSmall : F16BatchUnbiasedSmall { static constexpr bool BIAS = true; };          // the small levels of a batch search
+struct F16BatchDefault : F16BatchSmall {   // the batch kernel: persistent, 16 x 16 x 32 MFMA, wave-private epilogue
+  static constexpr bool PERSIST = true;
+  static constexpr int EPI = 1, MF = 1;
+};
+struct F16BatchComplement : F16BatchDefault { static constexpr int SKIP = 16; };   // the last level over the rows the stride-16 level has not seen
+struct F16DeepFlush : F16BatchDefault { static constexpr int KFL = SV_F16_KFLUSH; };   // deep rows: the batch kernel, blocks flushed to a scratch
+struct F16DeepFlushComplement : F16DeepFlush { static constexpr int SKIP = 16; };
+struct F16DeepBlocked : F16BatchSmall {    // deep rows, launches that do not fill the batch kernel: 8 waves of 64 x 64 on 256 x 128 tiles,
+  static constexpr int BN = 128;           // plain loop, a second accumulator set for the block sums
+  static constexpr int PP = 0, KBT = SV_F16_KBLOCK / SV_F16_HBK;
+  static constexpr int EPI = 1, MF = 1;
+};
+struct F16DeepBlockedBuf : F16DeepBlocked { static constexpr bool BUF = true; };   // its default form: operand DMA through buffer resources
+struct F16DeepBlockedComplement : F16DeepBlocked { static constexpr int SKIP = 16; };
+struct F16DeepBlockedBufComplement : F16DeepBlockedBuf { static constexpr int SKIP = 16; };
+struct F16DeepUnbiased : F16BatchUnbiasedSmall {   // deep rows, norms too unbalanced for the bias: 4 waves of 64 x 64 on 128 x 128 tiles
+  static constexpr int BM = 128, BN = 128, WM = 2, WN = 2;
+  static constexpr int PP = 0, KBT = SV_F16_KBLOCK / SV_F16_HBK;
+};
+struct F16OneImage128 : F16BatchUnbiasedSmall {    // one query image per pass, <= 128 rows (f16_cfg 63): streams the database once,
+  static constexpr int BM = 128, BN = 128, WM = 2, WN = 2;   // its rows non-temporal
+  static constexpr int POL = 1, PP = 0;
+};
+struct F16OneImage64 : F16OneImage128 { static constexpr int BM = 64, WM = 1; };   // <= 64 rows (f16_cfg 62)
+#ifdef SEGVLAD_ABLATIONS   // development build: three probes of the batch kernel (tools/probe_phases.py, tools/probe_ablate.py)
+struct F16ProbePhases : F16BatchDefault { static constexpr int PROBE = 1; };          // f16_cfg 93: right results, prints the phase shares
+struct F16ProbeNoEpilogue : F16BatchDefault { static constexpr int PROBE = 2; };      // f16_cfg 94: WRONG results
+struct F16ProbeNoEpilogueNoDma : F16BatchDefault { static constexpr int PROBE = 3; }; // f16_cfg 95: WRONG results
+#endif
+// accumulation-block length of a kernel in elements (0 = one running accumulator): what sv_f16_c_eps has to cover
+template <class C>
+constexpr int f16_kblock_of() { return (C::KBT > C::KFL ? C::KBT : C::KFL) * SV_F16_HBK; }
+
+template <class C>
+__global__ __launch_bounds__(64 * C::WM * C::WN) void knn_f16_filter_kernel(
     const uint16_t* __restrict__ Qh, const uint16_t* __restrict__ Rh, int M, int N, int d, int b_stride, int tiles_m, int gm,
     int seq_total, int walk,
     float inv_scale, const float* __restrict__ qn, const float* __restrict__ rn, const float* __restrict__ thr,
@@ -566,20 +600,25 @@ __global__ __launch_bounds__(64 * WM * WN) void knn_f16_filter_kernel(
   // single-image searches leave the query scale on the device (no host round trip in front of the pass): [0] = scale,
   // [1] = 1 / (query scale x database scale)
   if (inv_scale_dev) inv_scale = inv_scale_dev[1];
+  constexpr int BM = C::BM, BN = C::BN, WM = C::WM, WN = C::WN, PP = C::PP, KBT = C::KBT, EPI = C::EPI, MF = C::MF, SKIP = C::SKIP, KFL = C::KFL,
+                PROBE = C::PROBE;
+  constexpr bool PERSIST = C::PERSIST, BIAS = C::BIAS, BUF = C::BUF;
+  constexpr int HBK = SV_F16_HBK, NB = SV_F16_NB;
   constexpr int NW = WM * WN;
-  constexpr int AUXA = (POL & 2) ? 2 : 0, AUXB = (POL & 1) ? 2 : 0;   // aux = 2: "nt" (streaming) hint
+  constexpr int AUXB = C::POL ? 2 : 0;   // aux = 2: "nt" (streaming) hint
   constexpr int TM = BM / (32 * WM), TN = BN / (32 * WN);
-  constexpr bool ACC_A = TM * TN > 8;   // 256 accumulator registers per lane: they live in AGPRs (see acc_elem)
-  static_assert(KBT == 0 || ((PP == 0 || MF == 1) && !ACC_A), "blocked accumulation: two accumulator sets in VGPRs; plain loop, or the 16 x 16 x 32 loops");
-  constexpr int RB = HBK * 2;            // row bytes per k-tile
-  constexpr int CH = RB / 16;            // 16-B chunks per row (4 or 8)
+  static_assert(PP == 0 || PP == 2, "the plain loop or two ping-pong phases");
+  static_assert(TM == 2 && (TN == 4 || TN == 2), "wave tiles of 64 rows x 128 or 64 columns: 128 or 64 accumulators per lane, in VGPRs");
+  static_assert(KBT == 0 || PP == 0, "blocked accumulation (two accumulator sets): the plain loop");
+  constexpr int RB = HBK * 2;            // row bytes per k-tile (128)
+  constexpr int CH = RB / 16;            // 16-B chunks per row (8)
   constexpr int RP = 1024 / RB;          // rows per 1-KiB DMA piece
   constexpr int KS = HBK / 16;           // MFMA k-steps per tile
   constexpr int PA = BM * RB, PB = BN * RB;
   constexpr int JA = BM / RP / NW, JB = BN / RP / NW;  // DMA pieces per wave and operand
   static_assert(JA * RP * NW == BM && JB * RP * NW == BN && (PP > 0 || (JA + JB) % (MF ? 2 : KS) == 0), "tile/wave geometry");
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
-  unsigned long long phase_t0 = (ABL == 9 || ABL == 12) ? __builtin_amdgcn_s_memtime() : 0ull;
+  unsigned long long phase_t0 = PROBE == 1 ? __builtin_amdgcn_s_memtime() : 0ull;
   // XCD-aware tile order.  Workgroup ids are dealt round-robin to the 8 XCDs (each with its own 4 MiB L2); the 32
   // workgroups an XCD runs side by side form one gm x (32/gm) block of tiles, so that they share their query and
   // database rows in that L2 while they march over k (tm-fastest order made every XCD fetch every database row).
@@ -607,7 +646,7 @@ __global__ __launch_bounds__(64 * WM * WN) void knn_f16_filter_kernel(
   const int64_t ldr = (int64_t)d;   // fp16 elements per database row: operand row j starts at Rh + grow(j) * ldr
   const int ntiles = d / HBK;
   const int tiles_n = (N + BN - 1) / BN;
-  auto swz = [](int r, int c) { return CH == 8 ? (c ^ ((r >> 1) & 7)) : (c ^ ((r >> 2) & 3)); };
+  auto swz = [](int r, int c) { return c ^ ((r >> 1) & 7); };
   // walk bit 0 ("query-block-resident"): an XCD keeps ONE block of gm query tiles while it steps through its share of the
   // database blocks (blocks xcd, xcd + 8, ... -- the direction alternates from one query block to the next), instead of
   // meeting a different query block at every step: the gm query tiles (gm x 512 KiB of fp16 rows at d = 1024) are then
@@ -685,11 +724,11 @@ __global__ __launch_bounds__(64 * WM * WN) void knn_f16_filter_kernel(
   // LDS stages.  Plain: A stages at 0, PA; B stages behind them.  PERSIST (five 32-KiB slots): the first stages of both
   // operands and B's second sit in slots 3, 4, 2 -- outside the epilogue's scratch (slots 0, 1) -- so that the next
   // tile's head can land while the epilogue runs.
-  static_assert(!PERSIST || (PA == PB && NB == 3 && 5 * PA <= 160 * 1024), "persistent layout: five equal slots");
+  static_assert(!PERSIST || (PA == PB && 5 * PA <= 160 * 1024), "persistent layout: five equal slots");
   auto a_off = [](int st_) { return PERSIST ? (st_ == 0 ? 3 * PA : 0) : st_ * PA; };
   auto b_off = [](int st_) { return PERSIST ? (st_ == 0 ? 4 * PA : (st_ == 1 ? 2 * PA : PA)) : 2 * PA + st_ * PB; };
   const int lrow_p = l / CH, lch = l % CH;
-  // head of a tile: A(0), B(0) and (NB == 3) B(1), by global->LDS DMA
+  // head of a tile: A(0), B(0) and B(1), by global->LDS DMA
   // BUF: byte offset of this lane's 16 bytes of piece j inside its tile (rows beyond the operand clamp to its last row: they
   // are never emitted), and the tile's buffer resource
   auto voff_a = [&](int64_t m0_, int j) -> unsigned {
@@ -711,13 +750,13 @@ __global__ __launch_bounds__(64 * WM * WN) void knn_f16_filter_kernel(
       const sv_rsrc_t ra = rsrc_of(Qh + m0_ * d), rb_ = rsrc_of(Rh + grow(n0_) * ldr);
 #pragma unroll
       for (int j = 0; j < JA; ++j)
-        SV_BUF_LOAD_LDS(ra, (lptr_t)(lds + a_off(0) + (w * JA + j) * 1024), voff_a(m0_, j), 2 * k0_, AUXA);
+        SV_BUF_LOAD_LDS(ra, (lptr_t)(lds + a_off(0) + (w * JA + j) * 1024), voff_a(m0_, j), 2 * k0_, 0);
 #pragma unroll
       for (int j = 0; j < JB; ++j) {
         const unsigned vo = voff_b(n0_, j);
         SV_BUF_LOAD_LDS(rb_, (lptr_t)(lds + b_off(0) + (w * JB + j) * 1024), vo, 2 * k0_, AUXB);
       }
-      if (NB == 3 && ntiles > 1) {
+      if (ntiles > 1) {
 #pragma unroll
         for (int j = 0; j < JB; ++j)
           SV_BUF_LOAD_LDS(rb_, (lptr_t)(lds + b_off(1) + (w * JB + j) * 1024), voff_b(n0_, j), 2 * k1_, AUXB);
@@ -729,7 +768,7 @@ __global__ __launch_bounds__(64 * WM * WN) void knn_f16_filter_kernel(
       const int row = (w * JA + j) * RP + lrow_p;
       const int64_t qa = (m0_ + row < M) ? (m0_ + row) : (int64_t)(M - 1);
       __builtin_amdgcn_global_load_lds((gptr_t)(Qh + qa * d + 8 * swz(row, lch) + k0_), (lptr_t)(lds + a_off(0) + (w * JA + j) * 1024), 16,
-                                       0, AUXA);
+                                       0, 0);
     }
 #pragma unroll
     for (int j = 0; j < JB; ++j) {
@@ -738,7 +777,7 @@ __global__ __launch_bounds__(64 * WM * WN) void knn_f16_filter_kernel(
       __builtin_amdgcn_global_load_lds((gptr_t)(Rh + grow(rb) * ldr + 8 * swz(row, lch) + k0_), (lptr_t)(lds + b_off(0) + (w * JB + j) * 1024), 16,
                                        0, AUXB);
     }
-    if (NB == 3 && ntiles > 1) {
+    if (ntiles > 1) {
 #pragma unroll
       for (int j = 0; j < JB; ++j) {
         const int row = (w * JB + j) * RP + lrow_p;
@@ -749,8 +788,7 @@ __global__ __launch_bounds__(64 * WM * WN) void knn_f16_filter_kernel(
     }
   };
   // BIAS: this lane's column norms of the (next) tile, requested BEFORE the tile's head so that the head's wait covers them
-  static_assert(MF == 0 || (PP >= 0 && BIAS && EPI == 1 && BM / (32 * WM) == 2 && (BN / (32 * WN) == 4 || BN / (32 * WN) == 2) && HBK == 64),
-                "16 x 16 x 32 MFMA: the biased kernels with the wave-private epilogue, wave tiles of 64 rows x 128 or 64 columns");
+  static_assert((MF == 1) == (EPI == 1) && (MF == 0 || BIAS), "16 x 16 x 32 MFMA <=> the wave-private epilogue, both on biased accumulators");
   constexpr int TN16 = (BN / WN) / 16;                // MF = 1: column tiles of 16 per wave (8, or 4 with blocked accumulation)
   constexpr int CW = MF ? 16 : 32;                    // columns (and rows) per MFMA tile
   constexpr int NCN = (BN / WN) / CW;                 // column tiles per wave = column norms per lane
@@ -765,7 +803,7 @@ __global__ __launch_bounds__(64 * WM * WN) void knn_f16_filter_kernel(
   if (BIAS) load_cn(tn);
   int rev = PERSIST ? rev_of(seq) : 0;   // (only the persistent walk has steps to alternate / rotate)
   issue_head(tm, tn, rev);
-  if (NB == 3 && ntiles > 1)
+  if (ntiles > 1)
     wait_vm_lgkm0<JB>();
   else
     wait_vm_lgkm0<0>();
@@ -873,13 +911,11 @@ __global__ __launch_bounds__(64 * WM * WN) void knn_f16_filter_kernel(
   constexpr int BAHEAD = NB - 1;  // how many k-tiles ahead the B DMA runs (A always runs one ahead)
   // DMA piece p of iteration kt: pieces 0..JA-1 belong to A(kt+1), JA..JA+JB-1 to B(kt+BAHEAD)
   auto dma_piece = [&](int piece, int kt, int ia_next, int ib_next) {
-    if (ABL == 3) return;  // ablation: no DMA in the loop
-    if (ABL == 13 && piece < JA) return;    // ablation: B only
-    if (ABL == 14 && piece >= JA) return;   // ablation: A only
+    if (PROBE == 3) return;  // (development build) no DMA in the loop
     if constexpr (BUF) {
       if (piece < JA) {
         if (kt + 1 < ntiles)
-          SV_BUF_LOAD_LDS(rsA, (lptr_t)(lds + a_off(ia_next) + (w * JA + piece) * 1024), voA[piece], 2 * kofs(rev, kt + 1), AUXA);
+          SV_BUF_LOAD_LDS(rsA, (lptr_t)(lds + a_off(ia_next) + (w * JA + piece) * 1024), voA[piece], 2 * kofs(rev, kt + 1), 0);
       } else {
         const int j = piece - JA;
         if (kt + BAHEAD < ntiles)
@@ -888,7 +924,7 @@ __global__ __launch_bounds__(64 * WM * WN) void knn_f16_filter_kernel(
     } else if (piece < JA) {
       if (kt + 1 < ntiles)
         __builtin_amdgcn_global_load_lds((gptr_t)(srcA[piece] + kofs(rev, kt + 1)),
-                                         (lptr_t)(lds + a_off(ia_next) + (w * JA + piece) * 1024), 16, 0, AUXA);
+                                         (lptr_t)(lds + a_off(ia_next) + (w * JA + piece) * 1024), 16, 0, 0);
     } else {
       const int j = piece - JA;
       if (kt + BAHEAD < ntiles)
@@ -901,34 +937,11 @@ __global__ __launch_bounds__(64 * WM * WN) void knn_f16_filter_kernel(
   int ia = 0, ib = 0;
   const int fa0 = wm * (32 * TM) + i, fb0 = wn * (32 * TN) + i;
   if constexpr (PP > 0) {
-    constexpr int PPn = PP > 0 ? PP : 1;
-    constexpr int PH = KS / PPn;            // MFMA k-steps per phase
-    constexpr int DPP = (JA + JB) / PPn;    // DMA pieces per phase and wave
-    static_assert(PP == 0 || (KS % PPn == 0 && (JA + JB) % PPn == 0 && PH >= 1), "phase geometry");
+    constexpr int PH = KS / 2;            // MFMA k-steps per phase
+    constexpr int DPP = (JA + JB) / 2;    // DMA pieces per phase and wave
+    static_assert(KS % 2 == 0 && (JA + JB) % 2 == 0, "phase geometry");
     const bool lag = w >= NW / 2;           // wave-uniform (w comes from readfirstlane)
     if (lag) __builtin_amdgcn_s_barrier(); // the second half of the waves runs one barrier (= one segment) behind
-    // DSPLIT < 0 (APF): four of a phase's twelve fragments are read at the END of the previous phase's MFMA segment (16 more
-    // live registers) -- a load segment is then 8 fragment reads + the DMA issue, and the partner's 32 MFMAs have less to
-    // cover.  Phase 1 takes its A fragments that way (same stages as phase 0: landed).  Phase 0 of the NEXT k-tile takes its
-    // first four B fragments: B(kt+1) was requested a whole k-tile earlier, and a vmcnt(JA) added to phase 0's load segment
-    // (behind the issue of A(kt+1)) makes every wave's pieces of it certain one barrier before the earliest such read --
-    // the A stage of the next tile would not do, the lagging half only waits for it one segment after the leading half's
-    // MFMA segment that would read it.
-    constexpr bool APF = DSPLIT == -1;
-    // DSPLIT == -2 (DFIRST): a load segment issues its DMA pieces FIRST and its twelve fragment reads behind them (raw
-    // ds_read_b128: the compiler would put s_waitcnt vmcnt(0) in front of any LDS read it can see behind a DMA) -- asks
-    // whether a DMA's issue is cheaper with no LDS read of the wave in flight (A/B).
-    constexpr bool DFIRST = DSPLIT == -2;
-    constexpr int DSP = DSPLIT > 0 ? DSPLIT : 0;
-    static_assert(!APF || (MF == 1 && PPn == 2 && TN16 >= 4 && NB == 3), "fragment prefetch: the 16 x 16 x 32 ping-pong loop");
-    f16x8 apf[4];
-    if constexpr (APF) {
-#pragma unroll
-      for (int t = 0; t < 4; ++t) {
-        const int rb = wn * (16 * TN16) + 16 * t + (l & 15);
-        apf[t] = *reinterpret_cast<const f16x8*>(lds + b_off(ib) + rb * RB + swz(rb, l >> 4) * 16);
-      }
-    }
     // (KFL: the k-tiles run in blocks of KFL; the flush sits BETWEEN two runs of the inner loop, not behind a branch inside it -- with
     //  the branch inside, the 128 accumulators met a zeroed copy of themselves at the loop's back edge and 40 registers spilled)
     int kt = 0;
@@ -938,7 +951,7 @@ __global__ __launch_bounds__(64 * WM * WN) void knn_f16_filter_kernel(
       const unsigned char* SA = lds + a_off(ia);
       const unsigned char* SB = lds + b_off(ib);
 #pragma unroll
-      for (int ph = 0; ph < PPn; ++ph) {
+      for (int ph = 0; ph < 2; ++ph) {
         // ---- load segment: fragments of this phase's k-steps, this phase's share of the DMA pieces ----
         f16x8 a[MF ? 1 : PH][MF ? 4 : TM], b[MF ? 1 : PH][MF ? TN16 : TN];
         if constexpr (MF == 0) {
@@ -960,67 +973,31 @@ __global__ __launch_bounds__(64 * WM * WN) void knn_f16_filter_kernel(
           // one k-step of 32 per phase: lane l holds row / column (l & 15) of a 16-wide tile, k-chunk (l >> 4) of the step's four
           // (the source-side swizzle of the 128-byte rows is conflict-free for this pattern too: a 16-lane ds_read_b128 group
           //  covers rows {0-3, 12-15} of one chunk and rows {4-11} of the next, 16 distinct bank groups)
-          static_assert(MF == 0 || (PH == 2 && CH == 8), "a phase = 32 k of 128-byte rows");
+          static_assert(PH == 2 && CH == 8, "a phase = 32 k of 128-byte rows");
           const int cl = 4 * ph + (l >> 4);
-          if constexpr (DFIRST) {
-            static_assert(!DFIRST || TN16 == 8, "DMA-first load segment: 64 x 128 wave tiles");
-#pragma unroll
-            for (int pz = 0; pz < DPP; ++pz) dma_piece(ph * DPP + pz, kt, ia ^ 1, ibn);
-            // (rows 16 t apart: the swizzle term (row >> 1) & 7 does not depend on t -> one lane address per operand, t in the offset)
-            const int ra0 = wm * 64 + (l & 15), rb0 = wn * (16 * TN16) + (l & 15);
-            const unsigned aa = (unsigned)(size_t)(lptr_t)lds + a_off(ia) + ra0 * RB + swz(ra0, cl) * 16;
-            const unsigned ab = (unsigned)(size_t)(lptr_t)lds + b_off(ib) + rb0 * RB + swz(rb0, cl) * 16;
-            asm volatile("ds_read_b128 %0, %4\n\tds_read_b128 %1, %4 offset:2048\n\tds_read_b128 %2, %4 offset:4096\n\t"
-                         "ds_read_b128 %3, %4 offset:6144"
-                         : "=&v"(a[0][0]), "=&v"(a[0][1]), "=&v"(a[0][2]), "=&v"(a[0][3]) : "v"(aa));
-            asm volatile("ds_read_b128 %0, %4\n\tds_read_b128 %1, %4 offset:2048\n\tds_read_b128 %2, %4 offset:4096\n\t"
-                         "ds_read_b128 %3, %4 offset:6144"
-                         : "=&v"(b[0][0]), "=&v"(b[0][1]), "=&v"(b[0][2]), "=&v"(b[0][3]) : "v"(ab));
-            asm volatile("ds_read_b128 %0, %4 offset:8192\n\tds_read_b128 %1, %4 offset:10240\n\tds_read_b128 %2, %4 offset:12288\n\t"
-                         "ds_read_b128 %3, %4 offset:14336"
-                         : "=&v"(b[0][4 % TN16]), "=&v"(b[0][5 % TN16]), "=&v"(b[0][6 % TN16]), "=&v"(b[0][7 % TN16]) : "v"(ab));
-          } else {
 #pragma unroll
           for (int t = 0; t < 4; ++t) {
             const int ra = wm * 64 + 16 * t + (l & 15);
-            if (APF && ph == 1) a[0][t] = apf[t];
-            else a[0][t] = *reinterpret_cast<const f16x8*>(SA + ra * RB + swz(ra, cl) * 16);
+            a[0][t] = *reinterpret_cast<const f16x8*>(SA + ra * RB + swz(ra, cl) * 16);
           }
 #pragma unroll
           for (int t = 0; t < TN16; ++t) {
             const int rb = wn * (16 * TN16) + 16 * t + (l & 15);
-            if (APF && ph == 0 && t < 4) b[0][t] = apf[t];
-            else b[0][t] = *reinterpret_cast<const f16x8*>(SB + rb * RB + swz(rb, cl) * 16);
-          }
+            b[0][t] = *reinterpret_cast<const f16x8*>(SB + rb * RB + swz(rb, cl) * 16);
           }
         }
-        // DSPLIT > 0: the last DSPLIT pieces of a phase are issued from its MFMA segment (between the MFMAs) instead of its
-        // load segment -- the load segment (12 fragment reads + the DMA issue) is what the partner's 32 MFMAs have to cover.
-        // The pieces of the LAST phase that move are B(kt+2)'s (pieces >= JA): they are issued behind the k-tile's wait, so
-        // the wait leaves only the JB - DSPLIT of them that are in flight by then (older ones retire first: in order).
-        static_assert(DSP == 0 || (MF == 1 && PPn == 2 && DPP > DSP && JB >= DSP && NB == 3), "split DMA issue: the 16 x 16 x 32 ping-pong loop");
-        if constexpr (!DFIRST) {
 #pragma unroll
-          for (int pz = 0; pz < DPP - DSP; ++pz) dma_piece(ph * DPP + pz, kt, ia ^ 1, ibn);
-        }
-        if (ph == PPn - 1) {
+        for (int pz = 0; pz < DPP; ++pz) dma_piece(ph * DPP + pz, kt, ia ^ 1, ibn);
+        if (ph == 1) {
           // last load segment of the k-tile: this wave's pieces of A(kt+1) and B(kt+1) have landed (B(kt+2), the
           // youngest JB DMA instructions, may still fly).  The barriers between here and the first read of tile kt+1
           // (one for the leading half, two for the lagging half) make that true for every wave's pieces.
-          if (NB == 3 && kt + 2 < ntiles)
-            wait_vm_lgkm0<JB - DSP>();
+          if (kt + 2 < ntiles)
+            wait_vm_lgkm0<JB>();
           else
             wait_vm_lgkm0<0>();
-        } else if (APF && ph == 0) {
-          if (kt + 1 < ntiles) wait_vm_lgkm0<JA>();   // B(kt+1) landed (A(kt+1), just issued, may fly)
-          else wait_vm_lgkm0<0>();
         } else {
           asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        }
-        if constexpr (DFIRST && MF == 1) {   // (the raw reads' registers are final only behind the wait above)
-          asm volatile("" : "+v"(a[0][0]), "+v"(a[0][1]), "+v"(a[0][2]), "+v"(a[0][3]));
-#pragma unroll
-          for (int t = 0; t < TN16; ++t) asm volatile("" : "+v"(b[0][t]));
         }
         __builtin_amdgcn_sched_barrier(0);
         __builtin_amdgcn_s_barrier();
@@ -1036,35 +1013,10 @@ __global__ __launch_bounds__(64 * WM * WN) void knn_f16_filter_kernel(
               for (int nt = 0; nt < TN; ++nt) acc[mt][nt] = MFMA_F16(a[k2][mt], b[k2][nt], acc[mt][nt]);
         } else {
 #pragma unroll
-          for (int mt = 0; mt < 4; ++mt) {
+          for (int mt = 0; mt < 4; ++mt)
 #pragma unroll
             for (int nt = 0; nt < TN16; ++nt)
               acc16[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[0][mt], b[0][nt], acc16[mt][nt], 0, 0, 0);
-            if constexpr (DSP > 0) {   // one moved piece behind each of the first DSPLIT rows of MFMAs
-              if (mt < DSP) {
-                __builtin_amdgcn_sched_barrier(0);
-                dma_piece(ph * DPP + (DPP - DSP) + mt, kt, ia ^ 1, ibn);
-                __builtin_amdgcn_sched_barrier(0);
-              }
-            }
-          }
-          if constexpr (APF) {
-            __builtin_amdgcn_sched_barrier(0);
-            if (ph == 0) {           // phase 1's A fragments
-#pragma unroll
-              for (int t = 0; t < 4; ++t) {
-                const int ra = wm * 64 + 16 * t + (l & 15);
-                apf[t] = *reinterpret_cast<const f16x8*>(SA + ra * RB + swz(ra, 4 + (l >> 4)) * 16);
-              }
-            } else if (kt + 1 < ntiles) {   // the next k-tile's first four B fragments of phase 0
-              const unsigned char* SN = lds + b_off((ib + 1 >= NB) ? 0 : ib + 1);
-#pragma unroll
-              for (int t = 0; t < 4; ++t) {
-                const int rb = wn * (16 * TN16) + 16 * t + (l & 15);
-                apf[t] = *reinterpret_cast<const f16x8*>(SN + rb * RB + swz(rb, l >> 4) * 16);
-              }
-            }
-          }
         }
         __builtin_amdgcn_s_setprio(0);
         __builtin_amdgcn_sched_barrier(0);
@@ -1073,23 +1025,10 @@ __global__ __launch_bounds__(64 * WM * WN) void knn_f16_filter_kernel(
       }
       ia ^= 1;
       ib = (ib + 1 >= NB) ? 0 : ib + 1;
-      if constexpr (MF == 1 && KBT > 0) {   // close a k-block (this wave's registers only: no synchronisation; wave-uniform)
-        if ((kt + 1) % (KBT > 0 ? KBT : 1) == 0 || kt + 1 == ntiles) {
-#pragma unroll
-          for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-            for (int nt = 0; nt < TN16; ++nt)
-#pragma unroll
-              for (int r = 0; r < 4; ++r) {
-                accb16[mt][nt][r] += acc16[mt][nt][r];
-                acc16[mt][nt][r] = (kt + 1 == ntiles) ? accb16[mt][nt][r] : 0.f;   // last block: acc = the total
-              }
-        }
-      }
     }
     if (KFL == 0 || kt >= ntiles) break;
     if constexpr (KFL > 0) {   // close a k-block into the wave's global scratch slice (see KFL)
-      static_assert(KFL == 0 || (MF == 1 && PP > 0 && KBT == 0 && PERSIST && TN16 == 8), "flushed blocks: the persistent 16 x 16 x 32 ping-pong kernel");
+      static_assert(MF == 1 && KBT == 0 && PERSIST && TN16 == 8, "flushed blocks: the persistent 16 x 16 x 32 ping-pong kernel");
       float* const kscr_w = kscr_base() + l;
 #pragma unroll
       for (int mt = 0; mt < 4; ++mt)
@@ -1125,111 +1064,9 @@ __global__ __launch_bounds__(64 * WM * WN) void knn_f16_filter_kernel(
         for (int j = 0; j < 16 * TN16; ++j) __hip_atomic_store(kscr_w + 64 * j, 0.f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       }
     }
-  } else if constexpr (PP < 0) {
-    // One wave per SIMD (4 waves of 128 x 128: 0.5 LDS fragment reads per MFMA instead of 0.75): nothing else hides a
-    // wave's LDS latency, so the loop is software-pipelined -- the fragments of k-step s+1 are read (into the other half
-    // of a register double buffer) before the MFMAs of step s are issued, and the ONE barrier of a k-tile sits before
-    // its last MFMA group: every wave has then finished reading the tile's LDS stages (they may be overwritten), the
-    // next tile's operands have landed for every wave, and its first fragments are fetched under that MFMA group.
-    static_assert(PP >= 0 || (KS % 2 == 0 && TM == 4 && TN == 4 && CH == 8), "register double buffer; 128 x 128 wave tiles of 128-B rows");
-    // The fragment reads are raw ds_read_b128 (inline asm) with counted s_waitcnt lgkmcnt: while a global->LDS DMA is
-    // pending the compiler only ever waits with lgkmcnt(0) / vmcnt(0) before an LDS read it can see (it cannot tell the
-    // DMA'd stages from the fragments' addresses), which would serialise the prefetch behind the MFMA group it is meant
-    // to overlap.  The waits below carry the fragment registers as operands so that no MFMA can be scheduled above them.
-    constexpr int DPS = (JA + JB) / KS;   // DMA pieces per k-step and wave
-    f16x8 fa[2][4], fb[2][4];
-    // row ra = fa0 + 32 t: the swizzle term (ra >> 1) & 7 does not depend on t -> one lane address per k-step, t in the
-    // instruction's immediate offset (32 rows x 128 B = 4096)
-    unsigned offa[KS], offb[KS];
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) {
-      offa[ks] = (unsigned)(fa0 * RB + swz(fa0, 2 * ks + kk) * 16);
-      offb[ks] = (unsigned)(fb0 * RB + swz(fb0, 2 * ks + kk) * 16);
-    }
-    const unsigned lds0 = (unsigned)(size_t)(lptr_t)lds;
-#define SV_RD4(dst, addr)                                                                                      \
-    asm volatile("ds_read_b128 %0, %4\n\tds_read_b128 %1, %4 offset:4096\n\tds_read_b128 %2, %4 offset:8192\n\t" \
-                 "ds_read_b128 %3, %4 offset:12288"                                                            \
-                 : "=&v"(dst[0]), "=&v"(dst[1]), "=&v"(dst[2]), "=&v"(dst[3])                                  \
-                 : "v"(addr))
-#define SV_RD1(dst, addr, OFF) asm volatile("ds_read_b128 %0, %1 offset:" #OFF : "=v"(dst) : "v"(addr))
-#define SV_WAIT_FRAGS(N, A, B)                                                                                 \
-    asm volatile("s_waitcnt lgkmcnt(" #N ")"                                                                   \
-                 : "+v"(A[0]), "+v"(A[1]), "+v"(A[2]), "+v"(A[3]), "+v"(B[0]), "+v"(B[1]), "+v"(B[2]), "+v"(B[3]))
-    {
-      const unsigned aa = lds0 + a_off(ia) + offa[0], ab = lds0 + b_off(ib) + offb[0];
-      SV_RD4(fa[0], aa);
-      SV_RD4(fb[0], ab);
-    }
-    // DMA schedule: the stages of tile kt are free from that tile's barrier on, so the pieces of "slot 0" of the NEXT tile's
-    // quota (its first A pieces) are issued right behind the barrier, one k-step earlier than their tile starts
-    {
-      const int ibn0 = (ib + BAHEAD >= NB) ? ib + BAHEAD - NB : ib + BAHEAD;
-#pragma unroll
-      for (int pz = 0; pz < DPS; ++pz) dma_piece(pz, 0, ia ^ 1, ibn0);
-    }
-    for (int kt = 0; kt < ntiles; ++kt) {
-      const int ibn = (ib + BAHEAD >= NB) ? ib + BAHEAD - NB : ib + BAHEAD;
-      const int ib1 = (ib + 1 >= NB) ? 0 : ib + 1;
-      const int ibn1 = (ib1 + BAHEAD >= NB) ? ib1 + BAHEAD - NB : ib1 + BAHEAD;
-      const unsigned SAo = lds0 + a_off(ia), SBo = lds0 + b_off(ib);
-#pragma unroll
-      for (int ks = 0; ks < KS; ++ks) {
-        const int cur = ks & 1, nxt = cur ^ 1;
-        const bool last = ks + 1 == KS;
-        bool fetched = true;
-        unsigned aa, ab;
-        if (!last) {
-          aa = SAo + offa[ks + 1];
-          ab = SBo + offb[ks + 1];
-        } else {
-          // A(kt+1) and B(kt+1) have landed (B(kt+2), the youngest JB DMA instructions, may still fly) and this wave's
-          // reads of tile kt are complete (they were waited for at the top of the previous step ... and below)
-          if (NB == 3 && kt + 2 < ntiles)
-            wait_vm_lgkm0<JB>();
-          else
-            wait_vm_lgkm0<0>();
-          __builtin_amdgcn_s_barrier();
-          fetched = kt + 1 < ntiles;
-          aa = lds0 + a_off(ia ^ 1) + offa[0];
-          ab = lds0 + b_off(ib1) + offb[0];
-        }
-        // this step's fragments were requested under the previous MFMA group
-        SV_WAIT_FRAGS(0, fa[cur], fb[cur]);
-        __builtin_amdgcn_sched_barrier(0);
-        // 16 MFMAs; the next step's 8 fragment reads and this step's DMA pieces are issued in the gaps between them (the
-        // matrix pipe takes a new MFMA every 32 cycles: a lone wave that issues its loads in a block leaves it idle)
-#pragma unroll
-        for (int j = 0; j < 16; ++j) {
-          const int mt = j >> 2, nt = j & 3;
-          acc[mt][nt] = MFMA_F16(fa[cur][mt], fb[cur][nt], acc[mt][nt]);
-          __builtin_amdgcn_sched_barrier(0);
-          if (fetched) {
-            if (j == 0) SV_RD1(fa[nxt][0], aa, 0);
-            if (j == 1) SV_RD1(fa[nxt][1], aa, 4096);
-            if (j == 2) SV_RD1(fa[nxt][2], aa, 8192);
-            if (j == 3) SV_RD1(fa[nxt][3], aa, 12288);
-            if (j == 4) SV_RD1(fb[nxt][0], ab, 0);
-            if (j == 5) SV_RD1(fb[nxt][1], ab, 4096);
-            if (j == 6) SV_RD1(fb[nxt][2], ab, 8192);
-            if (j == 7) SV_RD1(fb[nxt][3], ab, 12288);
-          }
-          if (j >= 8 && j < 8 + DPS) {
-            if (!last) dma_piece((ks + 1) * DPS + (j - 8), kt, ia ^ 1, ibn);
-            else if (fetched) dma_piece(j - 8, kt + 1, ia, ibn1);   // A(kt+2) -> tile kt's A stage (free since the barrier)
-          }
-          __builtin_amdgcn_sched_barrier(0);
-        }
-      }
-      ia ^= 1;
-      ib = ib1;
-    }
-#undef SV_RD1
-#undef SV_RD4
-#undef SV_WAIT_FRAGS
   } else if constexpr (MF == 1) {
     // the plain loop (one barrier per k-tile) on the 16 x 16 x 32 shape: two k-steps of 32 per k-tile
-    static_assert(MF == 0 || PP != 0 || (KS == 4 && (JA + JB) % 2 == 0), "two k-steps of 32 per 64-deep k-tile");
+    static_assert(KS == 4 && (JA + JB) % 2 == 0, "two k-steps of 32 per 64-deep k-tile");
     for (int kt = 0; kt < ntiles; ++kt) {
       const int ibn = (ib + BAHEAD >= NB) ? ib + BAHEAD - NB : ib + BAHEAD;
       const unsigned char* SA = lds + a_off(ia);
@@ -1255,7 +1092,7 @@ __global__ __launch_bounds__(64 * WM * WN) void knn_f16_filter_kernel(
 #pragma unroll
           for (int nt = 0; nt < TN16; ++nt) acc16[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[mt], b[nt], acc16[mt][nt], 0, 0, 0);
       }
-      if (NB == 3 && kt + 2 < ntiles)
+      if (kt + 2 < ntiles)
         wait_vm_lgkm0<JB>();
       else
         wait_vm_lgkm0<0>();
@@ -1300,18 +1137,12 @@ __global__ __launch_bounds__(64 * WM * WN) void knn_f16_filter_kernel(
   #pragma unroll
         for (int mt = 0; mt < TM; ++mt)
   #pragma unroll
-          for (int nt = 0; nt < TN; ++nt) {
-            if (ABL == 2) {  // ablation: no MFMA (operands stay live)
-              acc[mt][nt][0] += (float)a[mt][0] + (float)b[nt][0];
-            } else {
-              acc[mt][nt] = MFMA_F16(a[mt], b[nt], acc[mt][nt]);
-            }
-          }
+          for (int nt = 0; nt < TN; ++nt) acc[mt][nt] = MFMA_F16(a[mt], b[nt], acc[mt][nt]);
       }
-      // this wave's pieces of A(kt+1) and B(kt+1) have landed (with NB = 3, B(kt+2) -- the youngest JB DMA
+      // this wave's pieces of A(kt+1) and B(kt+1) have landed (B(kt+2) -- the youngest JB DMA
       // instructions -- may still fly: vmcnt retires in order) and its LDS reads are done; after the barrier that
       // holds for every wave, so the stages of tile kt may be overwritten
-      if (NB == 3 && kt + 2 < ntiles)
+      if (kt + 2 < ntiles)
         wait_vm_lgkm0<JB>();
       else
         wait_vm_lgkm0<0>();
@@ -1333,29 +1164,20 @@ __global__ __launch_bounds__(64 * WM * WN) void knn_f16_filter_kernel(
   }
 
   SV_PHASE(1)  // main loop
-  if ((ABL >= 1 && ABL <= 3) || ABL == 16) {  // ablation: no epilogue (accumulators stay live; 16: DMA skeleton only)
+  if constexpr (PROBE >= 2) {  // (development build) no epilogue: WRONG results (the accumulators stay live)
+    static_assert(PROBE < 2 || (MF == 1 && PERSIST), "the probes are forms of the default batch kernel");
     float t = 0.f;
-    if (ABL != 16) {
-      if constexpr (MF == 0) {
 #pragma unroll
-        for (int mt = 0; mt < TM; ++mt)
+    for (int mt = 0; mt < 4; ++mt)
 #pragma unroll
-          for (int nt = 0; nt < TN; ++nt) t += acc[mt][nt][0] + acc[mt][nt][15];
-      } else {
-#pragma unroll
-        for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-          for (int nt = 0; nt < TN16; ++nt) t += acc16[mt][nt][0] + acc16[mt][nt][3];
-      }
-    }
+      for (int nt = 0; nt < TN16; ++nt) t += acc16[mt][nt][0] + acc16[mt][nt][3];
     if (t == 12345.678f) cand_cnt[0] = 1;
-    if (!PERSIST) return;
-    // persistent ablations: on to the workgroup's next tile (its head requested here, waited for at once)
+    // on to the workgroup's next tile (its head requested here, waited for at once)
     int tm_n = 0, tn_n = 0, sq_n = seq + pstep;
     while (sq_n < seq_total && !tile_of(sq_n, tm_n, tn_n)) sq_n += pstep;
     if (sq_n >= seq_total) return;
     if (BIAS) load_cn(tn_n);
-    if (ABL != 3) issue_head(tm_n, tn_n, rev_of(sq_n));
+    if (PROBE != 3) issue_head(tm_n, tn_n, rev_of(sq_n));
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     seq = sq_n;
     tm = tm_n;
@@ -1390,7 +1212,7 @@ __global__ __launch_bounds__(64 * WM * WN) void knn_f16_filter_kernel(
     }
   }
   // ---- epilogue: keep d2~ <= thr + eps_mult * eps(q) -----------------------------------------------------------
-  // The epilogue is VALU-issue bound (s_memtime phase timing, SEGVLAD_F16_CFG=90: every instruction of the sparse
+  // The epilogue is VALU-issue bound (s_memtime phase timing, see PROBE: every instruction of the sparse
   // per-survivor paths is paid by the whole wave), so it is organised around instruction count and everything
   // per-survivor happens on DENSE lanes:
   //  * per-row quantities {||q||^2, exact limit, screening bound} and the tile's column norms are staged once per
@@ -1421,7 +1243,7 @@ __global__ __launch_bounds__(64 * WM * WN) void knn_f16_filter_kernel(
     // trip per flush.  (First version: one returning global atomic per survivor, 64 at a time -- fine at ~6 survivors per
     // block, 150 round trips for such a block.  A re-entrant screening pass -- flush, then jump back in -- turns the pass
     // into a loop whose invariants the compiler hoists and spills: 80 dwords.)
-    static_assert(BIAS && TM == 2 && (TN == 4 || (MF == 1 && TN == 2)) && !ACC_A, "wave-private epilogue: 64-row wave tiles of the biased kernels");
+    static_assert(BIAS && MF == 1, "wave-private epilogue: the biased kernels on the 16 x 16 x 32 shape");
     constexpr int LCAPE = 864;   // records per wave list
     constexpr int WSZ = (1024 + (LCAPE + 1) * 8 + 15) & ~15;
     static_assert((size_t)NW * WSZ <= (PERSIST ? 2 * (size_t)PA : 2 * (size_t)PA + (size_t)NB * PB), "epilogue scratch");
@@ -1440,30 +1262,19 @@ __global__ __launch_bounds__(64 * WM * WN) void knn_f16_filter_kernel(
                    : "memory");
     }
     SV_PHASE(2)
-    // this lane's screening bounds: 32 x 32 tiles: element r of tile mt is row mt*32 + 8*(r>>2) + 4*kk + (r&3) -- 8 groups of 4
-    // consecutive rows; 16 x 16 tiles: element j of tile mt is row mt*16 + 4*(lane>>4) + j -- 4 groups of 4
-    float4 tqw[MF ? 1 : 2][4];
-    if constexpr (MF == 0) {
-      const unsigned ta = wb_a + 512u + 16u * (unsigned)kk;
-      asm volatile(
-          "ds_read_b128 %0, %8\n\tds_read_b128 %1, %8 offset:32\n\tds_read_b128 %2, %8 offset:64\n\tds_read_b128 %3, %8 offset:96\n\t"
-          "ds_read_b128 %4, %8 offset:128\n\tds_read_b128 %5, %8 offset:160\n\tds_read_b128 %6, %8 offset:192\n\tds_read_b128 %7, %8 offset:224\n\t"
-          "s_waitcnt lgkmcnt(0)"
-          : "=&v"(tqw[0][0]), "=&v"(tqw[0][1]), "=&v"(tqw[0][2]), "=&v"(tqw[0][3]), "=&v"(tqw[MF ? 0 : 1][0]), "=&v"(tqw[MF ? 0 : 1][1]),
-            "=&v"(tqw[MF ? 0 : 1][2]), "=&v"(tqw[MF ? 0 : 1][3])
-          : "v"(ta)
-          : "memory");
-    } else {
+    // this lane's screening bounds: element j of tile mt is row mt*16 + 4*(lane>>4) + j -- 4 groups of 4 consecutive rows
+    float4 tqw[4];
+    {
       const unsigned ta = wb_a + 512u + 16u * (unsigned)(l >> 4);
       asm volatile(
           "ds_read_b128 %0, %4\n\tds_read_b128 %1, %4 offset:64\n\tds_read_b128 %2, %4 offset:128\n\tds_read_b128 %3, %4 offset:192\n\t"
           "s_waitcnt lgkmcnt(0)"
-          : "=&v"(tqw[0][0]), "=&v"(tqw[0][1]), "=&v"(tqw[0][2]), "=&v"(tqw[0][3])
+          : "=&v"(tqw[0]), "=&v"(tqw[1]), "=&v"(tqw[2]), "=&v"(tqw[3])
           : "v"(ta)
           : "memory");
     }
     uint32_t wave_cnt = 0;   // wave-uniform
-    const uint32_t colbase = (uint32_t)(wn * (32 * TN) + (MF ? (l & 15) : i)), rowsel = (uint32_t)(4 * (MF ? (l >> 4) : kk));
+    const uint32_t colbase = (uint32_t)(wn * (32 * TN) + (l & 15)), rowsel = (uint32_t)(4 * (l >> 4));
     const int64_t rowbase = m0 + wm * 64;
     // dense exact test of the list, one returning global atomic per row with survivors, the stores left in flight
     auto flush = [&]() {
@@ -1517,13 +1328,13 @@ __global__ __launch_bounds__(64 * WM * WN) void knn_f16_filter_kernel(
       asm volatile("ds_write_b32 %0, %1 offset:768" ::"v"(wb_a + 4u * (unsigned)l), "v"(0u) : "memory");
       wave_cnt = 0u;
     };
-    if constexpr (MF == 1) {
+    {
       // 16 screening steps of 8 elements (one row of the wave tile across its 8 column tiles)
 #pragma unroll
       for (int mt = 0; mt < 4; ++mt)
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-          const float4 tq4 = tqw[0][mt];
+          const float4 tq4 = tqw[mt];
           const float tau = j == 0 ? tq4.x : j == 1 ? tq4.y : j == 2 ? tq4.z : tq4.w;
           float best;
           asm volatile("v_max3_f32 %0, %1, %2, %3" : "=v"(best) : "v"(acc16[mt][0][j]), "v"(acc16[mt][1][j]), "v"(acc16[mt][2][j]));
@@ -1552,35 +1363,6 @@ __global__ __launch_bounds__(64 * WM * WN) void knn_f16_filter_kernel(
             if (wave_cnt > (uint32_t)(LCAPE - 64 * TN16)) flush();   // (a step adds up to TN16 x 64 records)
           }
         }
-    } else {
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const float4 tq4 = tqw[mt][r >> 2];
-        const float tau = (r & 3) == 0 ? tq4.x : (r & 3) == 1 ? tq4.y : (r & 3) == 2 ? tq4.z : tq4.w;
-        float best;
-        asm volatile("v_max3_f32 %0, %1, %2, %3" : "=v"(best) : "v"(acc[mt][0][r]), "v"(acc[mt][1][r]), "v"(acc[mt][2][r]));
-        asm volatile("v_max_f32 %0, %1, %2" : "=v"(best) : "v"(best), "v"(acc[mt][3][r]));
-        if (__builtin_amdgcn_ballot_w64(best >= tau) != 0ull) {
-          const uint32_t rc = (((uint32_t)(mt * 32 + (r & 3) + 8 * (r >> 2)) + rowsel) << 16) | colbase;
-#pragma unroll
-          for (int nt = 0; nt < 4; ++nt) {
-            const bool hit = acc[mt][nt][r] >= tau;
-            const uint64_t mk = __builtin_amdgcn_ballot_w64(hit);
-            if (mk != 0ull) {
-              const uint32_t pos = wave_cnt + __builtin_amdgcn_mbcnt_hi((uint32_t)(mk >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mk, 0u));
-              if (hit) {
-                const uint2 rec = make_uint2(__float_as_uint(acc[mt][nt][r]), rc + (uint32_t)(nt * 32));
-                asm volatile("ds_write_b64 %0, %1 offset:1024" ::"v"(wb_a + 8u * pos), "v"(rec) : "memory");
-              }
-              wave_cnt += (uint32_t)__popcll(mk);
-            }
-          }
-          // the next step could overflow the list (spatially coherent databases): flush it here and go on
-          if (wave_cnt > (uint32_t)(LCAPE - 256)) flush();
-        }
-      }
     }
     SV_PHASE(3)
     flush();
@@ -1605,46 +1387,33 @@ __global__ __launch_bounds__(64 * WM * WN) void knn_f16_filter_kernel(
     if (!BIAS && wm == 0) cnl[wn * (32 * TN) + nt * 32 + i] = cn[nt];   // both half-waves hold the same value
   }
   __syncthreads();
-  SV_PHASE(2)  // row records staged
   uint32_t wave_cnt = 0;  // wave-uniform: only updated under wave-uniform control flow
-  uint32_t dbg_bodies = 0;
   // this lane's 16 * TM screening bounds, fetched up front with 16-B reads (accumulator element r of tile mt belongs to
   // row mt*32 + 8*(r>>2) + 4*kk + (r&3): four consecutive rows per (mt, r>>2)) -- a per-iteration LDS read put ~100
   // cycles of latency into each of the 32 screening steps (two waves per SIMD cannot hide it)
-  // (TM > 2 -- the 128 x 128 wave tiles -- fetches them per 32-row tile instead: 64 registers would not fit)
-  constexpr bool TQ_UPFRONT = TM <= 2;
-  float4 tq[TQ_UPFRONT ? TM : 1][4];
-  if (TQ_UPFRONT) {
+  float4 tq[TM][4];
 #pragma unroll
-    for (int mt = 0; mt < (TQ_UPFRONT ? TM : 1); ++mt)
+  for (int mt = 0; mt < TM; ++mt)
 #pragma unroll
-      for (int g = 0; g < 4; ++g)
-        tq[mt][g] = *reinterpret_cast<const float4*>(taul + wm * (32 * TM) + mt * 32 + 8 * g + 4 * kk);
-  }
+    for (int g = 0; g < 4; ++g)
+      tq[mt][g] = *reinterpret_cast<const float4*>(taul + wm * (32 * TM) + mt * 32 + 8 * g + 4 * kk);
 #pragma unroll
   for (int mt = 0; mt < TM; ++mt) {
-    if (!TQ_UPFRONT) {
-#pragma unroll
-      for (int g = 0; g < 4; ++g)
-        tq[0][g] = *reinterpret_cast<const float4*>(taul + wm * (32 * TM) + mt * 32 + 8 * g + 4 * kk);
-      __builtin_amdgcn_sched_barrier(0);   // one tile's bounds at a time
-    }
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       const uint32_t lrow16 = (uint32_t)(wm * (32 * TM) + mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * kk) << 16;
-      const float4 tq4 = tq[TQ_UPFRONT ? mt : 0][r >> 2];
+      const float4 tq4 = tq[mt][r >> 2];
       const float tau = (r & 3) == 0 ? tq4.x : (r & 3) == 1 ? tq4.y : (r & 3) == 2 ? tq4.z : tq4.w;
       float av[TN], dd[TN];
 #pragma unroll
       for (int nt = 0; nt < TN; ++nt) {
-        av[nt] = acc_elem<ACC_A>(acc[mt][nt], r);
+        av[nt] = acc[mt][nt][r];
         dd[nt] = BIAS ? av[nt] : av[nt] - cnh[nt];
       }
       float best = dd[0];
 #pragma unroll
       for (int nt = 1; nt < TN; ++nt) best = fmaxf(best, dd[nt]);
-      if (ABL < 12 && __builtin_amdgcn_ballot_w64(best >= tau) != 0ull) {   // ABL >= 12: timing ablations (wrong results)
-        if (ABL == 9 || ABL == 12) ++dbg_bodies;
+      if (__builtin_amdgcn_ballot_w64(best >= tau) != 0ull) {
 #pragma unroll
         for (int nt = 0; nt < TN; ++nt) {
           const bool hit = dd[nt] >= tau;
@@ -1660,8 +1429,6 @@ __global__ __launch_bounds__(64 * WM * WN) void knn_f16_filter_kernel(
       }
     }
   }
-  if ((ABL == 9 || ABL == 12) && tid == 0) atomicAdd(&sv_f16_phase_cycles[6], (unsigned long long)dbg_bodies);
-  SV_PHASE(3)  // pass 1
   // pass 2a: exact test of this wave's hits, dense (the list is wave-private: no barrier needed before reading it)
   const uint32_t n_w = wave_cnt <= (uint32_t)LCAP ? wave_cnt : 0u;   // a dense block abandons its (truncated) list
   for (uint32_t t = (uint32_t)l; t < n_w; t += 64u) {
@@ -1692,8 +1459,8 @@ __global__ __launch_bounds__(64 * WM * WN) void knn_f16_filter_kernel(
 #pragma unroll
         for (int nt = 0; nt < TN; ++nt) {
           const float4 rr = rrec[lrow];
-          const float v = BIAS ? __fmaf_rn(-2.f, acc_elem<ACC_A>(acc[mt][nt], r) * isc, rr.x)
-                               : sv_d2(rr.x, cn[nt], acc_elem<ACC_A>(acc[mt][nt], r) * isc);
+          const float v = BIAS ? __fmaf_rn(-2.f, acc[mt][nt][r] * isc, rr.x)
+                               : sv_d2(rr.x, cn[nt], acc[mt][nt][r] * isc);
           if (v <= rr.y && v < INFINITY) atomicAdd(&rowcnt[lrow], 1u);
         }
         __builtin_amdgcn_sched_barrier(0);   // keep the 32 row-record loads from being hoisted (register pressure)
@@ -1703,7 +1470,6 @@ __global__ __launch_bounds__(64 * WM * WN) void knn_f16_filter_kernel(
   // in order); the barrier below makes that true for every wave, so the next tile starts without a memory wait
   if (PERSIST) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
-  SV_PHASE(4)  // pass 2a
   if (tid < BM) {
     const uint32_t c = rowcnt[tid];
     rowcnt[tid] = (c > 0u) ? atomicAdd(&cand_cnt[m0 + tid], c) : 0u;  // rows >= M never count
@@ -1733,8 +1499,8 @@ __global__ __launch_bounds__(64 * WM * WN) void knn_f16_filter_kernel(
         for (int nt = 0; nt < TN; ++nt) {
           const float4 rr = rrec[lrow];
           {
-            const float v = BIAS ? __fmaf_rn(-2.f, acc_elem<ACC_A>(acc[mt][nt], r) * isc, rr.x)
-                                 : sv_d2(rr.x, cn[nt], acc_elem<ACC_A>(acc[mt][nt], r) * isc);
+            const float v = BIAS ? __fmaf_rn(-2.f, acc[mt][nt][r] * isc, rr.x)
+                                 : sv_d2(rr.x, cn[nt], acc[mt][nt][r] * isc);
             if (v <= rr.y && v < INFINITY) {
               const uint32_t slot = atomicAdd(&rowcnt[lrow], 1u);
               if (slot < (uint32_t)cap) {
@@ -1758,12 +1524,13 @@ __global__ __launch_bounds__(64 * WM * WN) void knn_f16_filter_kernel(
   }   // tile loop
 }
 
-template <int BM, int BN, int WM, int WN, int HBK, int NB, int ABL = 0, bool PERSIST = false, int POL = 0, int PP = 0, int KBT = 0,
-          bool BIAS = false, int EPI = 0, int MF = 0, bool BUF = false, int DSPLIT = 0, int SKIP = 0, int KFL = 0>
+template <class C>
 static int launch_f16_filter(segvlad_ctx* ctx, const uint16_t* Qh, const uint16_t* Rh, int M, int n_sample, int d, int b_stride,
                              float inv_scale, const float* qn, const float* rn, const float* thr, int64_t thr_ld,
                              float eps_mult, float c_eps, float rn_max, uint32_t* cand_cnt, float* cand_d2, uint32_t* cand_id,
                              int cap) {
+  constexpr int BM = C::BM, BN = C::BN, WM = C::WM, WN = C::WN, HBK = SV_F16_HBK, NB = SV_F16_NB, KFL = C::KFL;
+  constexpr bool PERSIST = C::PERSIST;
   const int tiles_m = (M + BM - 1) / BM, tiles_n = (n_sample + BN - 1) / BN;
   int64_t tiles = (int64_t)tiles_m * tiles_n;
   // tile-block height of the XCD-aware order (0 = plain tm-fastest order).  Every database tile is fetched once per
@@ -1800,13 +1567,13 @@ static int launch_f16_filter(segvlad_ctx* ctx, const uint16_t* Qh, const uint16_
   }
   if (tiles > 0x7fffffffLL) return ctx->fail(SEGVLAD_ERR_LIMIT, "f16 filter: too many tiles");
   size_t lds = 2 * (size_t)BM * HBK * 2 + (size_t)NB * BN * HBK * 2;  // two A stages + NB B stages
-  if (!PERSIST && EPI == 0) {  // epilogue: row records + per-row counters + one survivor list per wave
+  if (!PERSIST && C::EPI == 0) {  // epilogue: row records + per-row counters + one survivor list per wave
     constexpr int TMl = BM / (32 * WM), TNl = BN / (32 * WN);
     constexpr int LCAPl = (TMl * TNl * 256 < 2048) ? TMl * TNl * 256 : 2048;
     const size_t elds = (size_t)BM * 24 + (size_t)BN * 4 + (size_t)WM * WN * (LCAPl + 1) * 8;
     if (lds < elds) lds = elds;
   }
-  auto kern = knn_f16_filter_kernel<BM, BN, WM, WN, HBK, NB, ABL, PERSIST, POL, PP, KBT, BIAS, EPI, MF, BUF, DSPLIT, SKIP, KFL>;
+  auto kern = knn_f16_filter_kernel<C>;
   float* kscr = nullptr;
   if (KFL > 0) {   // one slice of 128 x 64 fp32 per resident wave, all zero between tiles (the kernel leaves it so); zeroed here as well
     const size_t bytes = (size_t)tiles * (WM * WN) * 128 * 64 * 4;
@@ -1823,1451 +1590,123 @@ static int launch_f16_filter(segvlad_ctx* ctx, const uint16_t* Qh, const uint16_
   return SEGVLAD_OK;
 }
 
-// Can the LAST level of a batch search run over the complement of the stride-16 sample (skip = 16)?  Only the two default batch
-// kernels have that form; the answer mirrors sv_launch_f16_filter's choice for (M, n_rows, d) under the context's options.
-// deep rows: does this launch take the persistent 256 x 256 kernel with flushed blocks (KFL)?
-static bool deep_flush_ok(const segvlad_ctx* ctx, int M, int64_t n_rows) {
-  const SvOptions& o = ctx->opt;
-  return (o.f16_deep_cfg < 0 || o.f16_deep_cfg == 5) && ctx->f16_bias_ok && o.f16_mf != 0 && o.f16_epi != 0 && M > 128 &&
-         (int64_t)((M + 255) / 256) * ((n_rows + 255) / 256) >= 1024;
+// ---- which kernel a launch takes: the ONE place that knows the rule ---------------------------------------------------
+// Measurements behind it: batches (M > 128) whose launch has >= 1024 tiles of 256 x 256 fill the persistent
+// kernel (10 000 x 1 M x 1024: 21.5 ms of filter launches against 22.5 for the plain 256 x 256 kernel in round 2, 18 ms since
+// round 4), smaller levels take its non-persistent form; one query image per pass (M <= 128) streams the database once: 0.41 ms
+// on 128 x 128 tiles against 0.51 on 256 x 256.  Deep rows (sv_f16_kblock: d >= 4096, raw K*D descriptors) accumulate in
+// blocks, which keeps the filter's error margin -- and with it the refine band -- as tight as at d = 1024 (sv_f16_c_eps):
+// 10 000 x 50 000 x 98 304, filter launches: 147 ms for 4 waves of 64 x 64 on 128 x 128 tiles (rounds 2-3; still the kernel
+// when the norms are too unbalanced for the bias), 126 ms for 8 waves on 256 x 128 tiles with a second accumulator set
+// (round 4; 125 ms with the DMA through buffer resources), and launches that fill the persistent batch kernel take THAT with
+// the blocks flushed into a global scratch (round 6b, KFL: 780 vs 667 TF algorithmic).
+// The biased kernels need the search's norms balanced (bias_ok: prepare_queries, search.hip).  skip = 16: the launch runs over
+// the complement of the stride-16 sample (option level_carry); only the biased batch and deep-row kernels have that form.
+F16Choice sv_choose_f16_kernel(const SvOptions& o, bool bias_ok, int M, int64_t n_rows, int d, int b_stride, int skip) {
+  const bool deep = sv_f16_kblock(o, d) != 0;
+  const bool fills = (int64_t)((M + 255) / 256) * ((n_rows + 255) / 256) >= 1024;   // the persistent 256 x 256 kernels
+  const bool flush = deep && (o.f16_deep_cfg < 0 || o.f16_deep_cfg == 5) && bias_ok && M > 128 && fills;
+  // BUF kernels: every piece offset of a 256-row tile in 32 bits (row pitch d * b_stride fp16 on the database side; the complement
+  // form steps over one row in 16: twice the pitch bounds it)
+  const bool buf_ok = o.f16_buf != 0 && (int64_t)256 * d * (skip ? 2 : b_stride) * 2 + 4096 < (int64_t)0xffffffffLL;
+  if (skip) {
+    if (skip != 16 || b_stride != 1) return {F16Kernel::None, "the complement form exists for the stride-16 sample of contiguous rows only"};
+    if (!o.level_carry || M <= 128 || n_rows <= 0 || !bias_ok) return {F16Kernel::None, "the complement form needs level_carry and a biased batch kernel"};
+    if (deep) return {flush ? F16Kernel::DeepFlushComplement : buf_ok ? F16Kernel::DeepBlockedBufComplement : F16Kernel::DeepBlockedComplement, nullptr};
+    if ((o.f16_cfg >= 0 && o.f16_cfg != 250) || !fills) return {F16Kernel::None, "the complement form needs the persistent batch kernel"};
+    return {F16Kernel::BatchComplement, nullptr};
+  }
+  if (deep) {
+    if (flush) return {F16Kernel::DeepFlush, nullptr};
+    if (bias_ok && M > 128) return {buf_ok ? F16Kernel::DeepBlockedBuf : F16Kernel::DeepBlocked, nullptr};
+    return {F16Kernel::DeepUnbiased, nullptr};
+  }
+  switch (o.f16_cfg >= 0 ? o.f16_cfg : (M > 128 ? 250 : M > 64 ? 63 : 62)) {
+    case 250:
+      if (!bias_ok) return {fills ? F16Kernel::BatchUnbiased : F16Kernel::BatchUnbiasedSmall, nullptr};
+      return {fills ? F16Kernel::BatchDefault : F16Kernel::BatchSmall, nullptr};
+    case 62: return {F16Kernel::OneImage64, nullptr};
+    case 63: return {F16Kernel::OneImage128, nullptr};
+#ifdef SEGVLAD_ABLATIONS
+    case 93: return {F16Kernel::ProbePhases, nullptr};
+    case 94: return {F16Kernel::ProbeNoEpilogue, nullptr};
+    case 95: return {F16Kernel::ProbeNoEpilogueNoDma, nullptr};
+#endif
+    default: return {F16Kernel::None, "no such fp16 filter configuration (option f16_cfg)"};
+  }
 }
 
+// f(C{}) for the configuration type C of kernel k
+template <class F>
+static auto f16_with_config(F16Kernel k, F&& f) -> decltype(f(F16BatchDefault{})) {
+  switch (k) {
+    case F16Kernel::BatchDefault: return f(F16BatchDefault{});
+    case F16Kernel::BatchComplement: return f(F16BatchComplement{});
+    case F16Kernel::BatchSmall: return f(F16BatchSmall{});
+    case F16Kernel::BatchUnbiased: return f(F16BatchUnbiased{});
+    case F16Kernel::BatchUnbiasedSmall: return f(F16BatchUnbiasedSmall{});
+    case F16Kernel::DeepFlush: return f(F16DeepFlush{});
+    case F16Kernel::DeepFlushComplement: return f(F16DeepFlushComplement{});
+    case F16Kernel::DeepBlockedBuf: return f(F16DeepBlockedBuf{});
+    case F16Kernel::DeepBlocked: return f(F16DeepBlocked{});
+    case F16Kernel::DeepBlockedBufComplement: return f(F16DeepBlockedBufComplement{});
+    case F16Kernel::DeepBlockedComplement: return f(F16DeepBlockedComplement{});
+    case F16Kernel::DeepUnbiased: return f(F16DeepUnbiased{});
+    case F16Kernel::OneImage64: return f(F16OneImage64{});
+    case F16Kernel::OneImage128: return f(F16OneImage128{});
+#ifdef SEGVLAD_ABLATIONS
+    case F16Kernel::ProbePhases: return f(F16ProbePhases{});
+    case F16Kernel::ProbeNoEpilogue: return f(F16ProbeNoEpilogue{});
+    case F16Kernel::ProbeNoEpilogueNoDma: return f(F16ProbeNoEpilogueNoDma{});
+#endif
+    case F16Kernel::None: break;
+  }
+  return decltype(f(F16BatchDefault{}))();
+}
+
+// Can the LAST level of a batch search run over the complement of the stride-16 sample (skip = 16)?
 bool sv_f16_filter_skip_ok(const segvlad_ctx* ctx, int M, int64_t n_rows, int d) {
-  const SvOptions& o = ctx->opt;
-  if (!o.level_carry || M <= 128 || n_rows <= 0 || !ctx->f16_bias_ok || o.f16_mf == 0 || o.f16_epi == 0) return false;
-  if (sv_f16_kblock(o, d)) return o.f16_deep_cfg < 0 || o.f16_deep_cfg == 4 || o.f16_deep_cfg == 5;
-  if (o.f16_cfg >= 0 && o.f16_cfg != 250) return false;
-  if (o.f16_pp == 0 || o.f16_dsplit != 0 || o.f16_buf == 1) return false;   // (the A/B variants of the batch kernel)
-  return (int64_t)((M + 255) / 256) * ((n_rows + 255) / 256) >= 1024;
+  return sv_choose_f16_kernel(ctx->opt, ctx->f16_bias_ok, M, n_rows, d, 1, 16).kernel != F16Kernel::None;
+}
+
+// The accumulation-block length the error constant of a search over rows of d has to cover: that of the kernel a launch takes
+// which fills the machine, with the bias allowed -- the longest of any launch of the search (the flushed blocks of the
+// persistent deep-row kernel are longer than the register-blocked kernels' that the smaller levels run).
+int sv_f16_eps_kblock(const SvOptions& o, int d) {
+  static_assert(f16_kblock_of<F16DeepFlush>() >= f16_kblock_of<F16DeepBlocked>() && f16_kblock_of<F16DeepBlocked>() == f16_kblock_of<F16DeepUnbiased>() &&
+                    f16_kblock_of<F16DeepBlocked>() == SV_F16_KBLOCK,
+                "the largest launch has the longest blocks");
+  const F16Choice c = sv_choose_f16_kernel(o, true, 1 << 20, (int64_t)1 << 40, d, 1, 0);
+  return f16_with_config(c.kernel, [](auto cfg) { return f16_kblock_of<decltype(cfg)>(); });
 }
 
 int sv_launch_f16_filter(segvlad_ctx* ctx, const uint16_t* Qh, const uint16_t* Rh, int M, int n_sample, int d, int b_stride,
                          float inv_scale, const float* qn, const float* rn, const float* thr, int64_t thr_ld, float eps_mult,
                          float c_eps, float rn_max, uint32_t* cand_cnt, float* cand_d2, uint32_t* cand_id, int cap, int skip) {
   if (M <= 0 || n_sample <= 0) return SEGVLAD_OK;
-#define SV_F16_ARGS ctx, Qh, Rh, M, n_sample, d, b_stride, inv_scale, qn, rn, thr, thr_ld, eps_mult, c_eps, rn_max, cand_cnt, cand_d2, cand_id, cap
-  if (skip) {
-    // operand row j = database row j + j / 15 + 1 (n_sample = the number of rows that are not multiples of 16): see the kernel's SKIP
-    if (skip != 16 || b_stride != 1 || !sv_f16_filter_skip_ok(ctx, M, n_sample, d))
-      return ctx->fail(SEGVLAD_ERR_STATE, "f16 filter: no complement-of-sample form for this configuration");
-    if (sv_f16_kblock(ctx->opt, d)) {
-      if (deep_flush_ok(ctx, M, n_sample))
-        return launch_f16_filter<256, 256, 4, 2, 64, 3, 0, true, 0, 2, 0, true, 1, 1, false, 0, 16, SV_F16_KFLUSH>(SV_F16_ARGS);
-      if (ctx->opt.f16_buf != 0 && (int64_t)256 * d * 2 * 2 + 4096 < (int64_t)0xffffffffLL)
-        return launch_f16_filter<256, 128, 4, 2, 64, 3, 0, false, 0, 0, 16, true, 1, 1, true, 0, 16>(SV_F16_ARGS);
-      return launch_f16_filter<256, 128, 4, 2, 64, 3, 0, false, 0, 0, 16, true, 1, 1, false, 0, 16>(SV_F16_ARGS);
-    }
-    return launch_f16_filter<256, 256, 4, 2, 64, 3, 0, true, 0, 2, 0, true, 1, 1, false, 0, 16>(SV_F16_ARGS);
-  }
-  // tile configuration: option "f16_cfg" (default chosen from measurements)
-  // r02 measurements (10 000 x 1 M x 1024, random unit vectors, filter launches only): 0 -> 22.5 ms, 50 (ping-pong) -> 21.7,
-  // 200 (persistent) -> 21.7, 250 (persistent + ping-pong) -> 21.5; HBK = 32 variants (4, 1) 24.1 / 25.3
-  // 4 waves of 128 x 128 (a third fewer LDS fragment reads per MFMA; accumulators in AGPRs, epilogue through acc_elem):
-  // 5 (compiler-scheduled loop) -> 21.8 ms, 55 (software-pipelined: reads / DMA issued between the MFMAs, one barrier per
-  // k-tile) -> 21.9, 255 (55 + persistent) -> 22.1, against 20.9-21.1 for 250 in the same sessions: with one wave per SIMD
-  // nothing covers the per-tile barrier and the epilogue, and the kernel sits at the same power-limited clock either way.
-  // streaming regime (M <= 128, e.g. one 50-segment query image per pass over 1 M rows): 2 -> 0.41 ms, 3 -> 0.51 ms
-  // deep rows (raw K*D descriptors, d >= 4096): blocked accumulation (configuration 300), which is what keeps the
-  // filter's error margin -- and with it the refine band -- as tight as at d = 1024 (sv_f16_c_eps)
-  const int c = sv_f16_kblock(ctx->opt, d) ? 300 : ctx->opt.f16_cfg >= 0 ? ctx->opt.f16_cfg : (M > 128 ? 250 : M > 64 ? 63 : 62);
-  // BUF kernels: every piece offset of a 256-row tile (row pitch d * b_stride fp16 for the database side) in 32 bits
-  const bool buf_ok = ctx->opt.f16_buf != 0 && (int64_t)256 * d * b_stride * 2 + 4096 < (int64_t)0xffffffffLL;
-  switch (c) {
-    case 300:   // blocked accumulation (deep rows): two accumulator sets, a k-block of SV_F16_KBLOCK = 16 k-tiles of 64
-      static_assert(SV_F16_KBLOCK == 16 * 64, "k-block = KBT x HBK");
-      // round 4: 8 waves of 64 x 64 on a 256 x 128 tile, 16 x 16 x 32 MFMA, the plain loop (one barrier per k-tile), biased
-      // accumulators (the bias sits in the block-sum set), wave-private epilogue -- 1.5 x the operand bytes per flop of the
-      // 256 x 256 kernel instead of 2 x, two waves per SIMD instead of one.  Measured, 10 000 x 50 000 x 98 304 (filter launches):
-      // rounds 2-3's 4 waves of 64 x 64 on 128 x 128 tiles with the 32 x 32 x 16 shape 147 ms (f16_deep_cfg = 0; also the
-      // fallback when the norms are too unbalanced for the bias), this kernel 126 ms; the same with the ping-pong loop 165 ms
-      // (1: half the MFMAs per phase of the 64 x 128 wave tiles behind the same barriers), 128 x 128 tiles with the 16 x 16 x 32
-      // shape 234 ms ping-pong / 198 ms plain (2 / 3: one wave per SIMD)
-      // round 6b: launches that fill the persistent 256 x 256 ping-pong kernel (the batch kernel of the 1024-d searches) take it, with the
-      // accumulation blocked by FLUSHING: every 64 k-tiles the accumulators are added into a global scratch slice and cleared (KFL) --
-      // the second register set that kept the 256-row tiles out of reach is gone; measured 10 000 x 46 875 x 98 304: see DESIGN.md
-      if (deep_flush_ok(ctx, M, n_sample))
-        return launch_f16_filter<256, 256, 4, 2, 64, 3, 0, true, 0, 2, 0, true, 1, 1, false, 0, 0, SV_F16_KFLUSH>(SV_F16_ARGS);
-      if (ctx->f16_bias_ok && ctx->opt.f16_mf != 0 && ctx->opt.f16_epi != 0 && M > 128) {
-        if (ctx->opt.f16_deep_cfg < 0 || ctx->opt.f16_deep_cfg == 4 || ctx->opt.f16_deep_cfg == 5) {   // the default: 780 vs 667 TF algorithmic at 10 000 x 50 000 x 98 304
-          if (buf_ok) return launch_f16_filter<256, 128, 4, 2, 64, 3, 0, false, 0, 0, 16, true, 1, 1, true>(SV_F16_ARGS);
-          return launch_f16_filter<256, 128, 4, 2, 64, 3, 0, false, 0, 0, 16, true, 1, 1>(SV_F16_ARGS);
-        }
-#ifdef SEGVLAD_ABLATIONS   // measured and not kept (development build; the shipped library holds the default only)
-        if (ctx->opt.f16_deep_cfg == 1) return launch_f16_filter<256, 128, 4, 2, 64, 3, 0, false, 0, 2, 16, true, 1, 1>(SV_F16_ARGS);
-        if (ctx->opt.f16_deep_cfg == 2) return launch_f16_filter<128, 128, 2, 2, 64, 3, 0, false, 0, 2, 16, true, 1, 1>(SV_F16_ARGS);
-        if (ctx->opt.f16_deep_cfg == 3) return launch_f16_filter<128, 128, 2, 2, 64, 3, 0, false, 0, 0, 16, true, 1, 1>(SV_F16_ARGS);   // plain loop
-#endif
-      }
-      return launch_f16_filter<128, 128, 2, 2, 64, 3, 0, false, 0, 0, 16>(SV_F16_ARGS);
-#ifdef SEGVLAD_ABLATIONS   // development builds only: the configurations measured on the way (rounds 1-4, DESIGN.md 4 / 7.1: correct
-                           // results, not kept), timing ablations (WRONG results) and phase timing
-    case 0: return launch_f16_filter<256, 256, 4, 2, 64, 3>(SV_F16_ARGS);  // 160 KiB LDS, 1 workgroup / CU
-    case 200:   // persistent workgroups that request the next tile's head before their epilogue
-      if ((int64_t)((M + 255) / 256) * ((n_sample + 255) / 256) >= 1024)
-        return launch_f16_filter<256, 256, 4, 2, 64, 3, 0, true>(SV_F16_ARGS);
-      return launch_f16_filter<256, 256, 4, 2, 64, 3>(SV_F16_ARGS);
-    case 10: return launch_f16_filter<256, 256, 4, 2, 64, 3, 1>(SV_F16_ARGS);  // ablations of config 0 (WRONG results)
-    case 20: return launch_f16_filter<256, 256, 4, 2, 64, 3, 2>(SV_F16_ARGS);
-    case 30: return launch_f16_filter<256, 256, 4, 2, 64, 3, 3>(SV_F16_ARGS);
-    case 130: return launch_f16_filter<256, 256, 4, 2, 64, 3, 13>(SV_F16_ARGS);   // DMA only, B pieces only
-    case 140: return launch_f16_filter<256, 256, 4, 2, 64, 3, 14>(SV_F16_ARGS);   // DMA only, A pieces only
-    case 121: return launch_f16_filter<256, 256, 4, 2, 64, 3, 15>(SV_F16_ARGS);   // DMA only (no phase timing)
-    case 160: return launch_f16_filter<256, 256, 4, 2, 64, 3, 16>(SV_F16_ARGS);   // DMA only, no epilogue
-    case 94: ctx->f16_bias_ok = true; return launch_f16_filter<256, 256, 4, 2, 64, 3, 1, true, 0, 2, 0, true, 1, 1>(SV_F16_ARGS);   // default kernel, no epilogue
-    case 95: ctx->f16_bias_ok = true; return launch_f16_filter<256, 256, 4, 2, 64, 3, 3, true, 0, 2, 0, true, 1, 1>(SV_F16_ARGS);   // + no DMA in the loop
-    case 91:
-    case 92:
-    case 93: {  // phase timing of the default batch kernel (persistent + ping-pong + bias), epilogue 0 / 1 / 1 + 16x16x32 MFMA
-      unsigned long long z[8] = {0, 0, 0, 0, 0, 0, 0, 0}, c8[8];
-      SV_HIP(hipMemcpyToSymbol(HIP_SYMBOL(sv_f16_phase_cycles), z, sizeof(z)));
-      ctx->f16_bias_ok = true;
-      const int rc = c == 91   ? launch_f16_filter<256, 256, 4, 2, 64, 3, 9, true, 0, 2, 0, true, 0>(SV_F16_ARGS)
-                     : c == 92 ? launch_f16_filter<256, 256, 4, 2, 64, 3, 9, true, 0, 2, 0, true, 1>(SV_F16_ARGS)
-                               : launch_f16_filter<256, 256, 4, 2, 64, 3, 9, true, 0, 2, 0, true, 1, 1>(SV_F16_ARGS);
-      SV_HIP(hipStreamSynchronize(ctx->stream));
-      SV_HIP(hipMemcpyFromSymbol(c8, HIP_SYMBOL(sv_f16_phase_cycles), sizeof(c8)));
-      double tot = 0;
-      for (int k = 0; k < 6; ++k) tot += (double)c8[k];
-      fprintf(stderr, "[f16 filter phases, cfg %d] M=%d n=%d: head-wait %.1f%% main %.1f%% stage %.1f%% pass1 %.1f%% pass2a %.1f%% rest %.1f%% (%.3g cycles/WG-sum)\n",
-              c, M, n_sample, 100 * c8[0] / tot, 100 * c8[1] / tot, 100 * c8[2] / tot, 100 * c8[3] / tot, 100 * c8[4] / tot,
-              100 * c8[5] / tot, tot);
-      return rc;
-    }
-    case 90:
-    case 120: {  // phase timing of config 0 (debug: synchronises and prints; 110 / 120 also ablate pass 1)
-      unsigned long long z[8] = {0, 0, 0, 0, 0, 0, 0, 0}, c8[8];
-      SV_HIP(hipMemcpyToSymbol(HIP_SYMBOL(sv_f16_phase_cycles), z, sizeof(z)));
-      const int rc = c == 90 ? launch_f16_filter<256, 256, 4, 2, 64, 3, 9>(SV_F16_ARGS)
-                             : launch_f16_filter<256, 256, 4, 2, 64, 3, 12>(SV_F16_ARGS);
-      SV_HIP(hipStreamSynchronize(ctx->stream));
-      SV_HIP(hipMemcpyFromSymbol(c8, HIP_SYMBOL(sv_f16_phase_cycles), sizeof(c8)));
-      double tot = 0;
-      for (int k = 0; k < 6; ++k) tot += (double)c8[k];
-      fprintf(stderr, "[f16 filter phases] M=%d n=%d: prologue %.1f%% main %.1f%% stage %.1f%% pass1 %.1f%% pass2a %.1f%% reserve+pass2b %.1f%% (%.3g cycles/WG-sum)\n",
-              M, n_sample, 100 * c8[0] / tot, 100 * c8[1] / tot, 100 * c8[2] / tot, 100 * c8[3] / tot, 100 * c8[4] / tot,
-              100 * c8[5] / tot, tot);
-      fprintf(stderr, "[f16 filter phases]   wave 0: %.2f hit bodies per tile\n",
-              (double)c8[6] / ((double)((M + 255) / 256) * ((n_sample + 255) / 256)));
-      return rc;
-    }
-    case 50: return launch_f16_filter<256, 256, 4, 2, 64, 3, 0, false, 0, 2>(SV_F16_ARGS);  // ping-pong, 2 phases per k-tile
-    case 51: return launch_f16_filter<256, 256, 4, 2, 64, 3, 0, false, 0, 4>(SV_F16_ARGS);  // ping-pong, 4 phases per k-tile
-    case 52: return launch_f16_filter<256, 256, 4, 2, 64, 3, 0, false, 0, 1>(SV_F16_ARGS);  // ping-pong, 1 phase per k-tile
-#endif
-    case 250:   // the default for batches: biased accumulators (see BIAS) when segvlad_search found the norms balanced enough
-      if (!ctx->f16_bias_ok) goto unbiased_250;
-      if ((int64_t)((M + 255) / 256) * ((n_sample + 255) / 256) >= 1024) {
-#ifdef SEGVLAD_ABLATIONS   // the A/B variants of the batch kernel (development build)
-        if (ctx->opt.f16_epi == 0)
-          return launch_f16_filter<256, 256, 4, 2, 64, 3, 0, true, 0, 2, 0, true>(SV_F16_ARGS);      // persistent + ping-pong
-        if (ctx->opt.f16_mf == 0)
-          return launch_f16_filter<256, 256, 4, 2, 64, 3, 0, true, 0, 2, 0, true, 1>(SV_F16_ARGS);   // + wave-private epilogue
-        if (ctx->opt.f16_pp == 0)
-          return launch_f16_filter<256, 256, 4, 2, 64, 3, 0, true, 0, 0, 0, true, 1, 1>(SV_F16_ARGS);   // plain loop (A/B)
-        // (buffer_load lds is SLOWER in this kernel -- 18.70 vs 18.19 ms -- although faster in the micro-benchmark's loop and in
-        //  the deep-row kernel, 125.2 vs 126.4 ms: only on request here)
-        if (ctx->opt.f16_dsplit == -1)
-          return launch_f16_filter<256, 256, 4, 2, 64, 3, 0, true, 0, 2, 0, true, 1, 1, false, -1>(SV_F16_ARGS);   // fragment prefetch (A/B)
-        if (ctx->opt.f16_dsplit == -2)
-          return launch_f16_filter<256, 256, 4, 2, 64, 3, 0, true, 0, 2, 0, true, 1, 1, false, -2>(SV_F16_ARGS);   // DMA-first load segment (A/B)
-        if (ctx->opt.f16_dsplit == 2)
-          return launch_f16_filter<256, 256, 4, 2, 64, 3, 0, true, 0, 2, 0, true, 1, 1, false, 2>(SV_F16_ARGS);   // split DMA issue (A/B)
-        if (ctx->opt.f16_dsplit == 1)
-          return launch_f16_filter<256, 256, 4, 2, 64, 3, 0, true, 0, 2, 0, true, 1, 1, false, 1>(SV_F16_ARGS);
-        if (buf_ok && ctx->opt.f16_buf == 1)
-          return launch_f16_filter<256, 256, 4, 2, 64, 3, 0, true, 0, 2, 0, true, 1, 1, true>(SV_F16_ARGS);   // + buffer_load lds
-#endif
-        return launch_f16_filter<256, 256, 4, 2, 64, 3, 0, true, 0, 2, 0, true, 1, 1>(SV_F16_ARGS);  // + 16 x 16 x 32 MFMA
-      }
+  // (skip: operand row j = database row j + j / 15 + 1, n_sample = the number of rows that are not multiples of 16: see the kernel's SKIP)
+  const F16Choice c = sv_choose_f16_kernel(ctx->opt, ctx->f16_bias_ok, M, n_sample, d, b_stride, skip);
+  if (c.kernel == F16Kernel::None)
+    return ctx->fail(skip ? SEGVLAD_ERR_STATE : SEGVLAD_ERR_ARG, "f16 filter (f16_cfg %d, %d x %d x %d, skip %d): %s", ctx->opt.f16_cfg, M, n_sample, d, skip, c.why);
+  auto launch = [&](auto cfg) {
+    return launch_f16_filter<decltype(cfg)>(ctx, Qh, Rh, M, n_sample, d, b_stride, inv_scale, qn, rn, thr, thr_ld, eps_mult, c_eps, rn_max, cand_cnt,
+                                            cand_d2, cand_id, cap);
+  };
 #ifdef SEGVLAD_ABLATIONS
-      if (ctx->opt.f16_small_mf == 1)   // (A/B: the small levels on the new shape + wave-private epilogue, non-persistent)
-        return launch_f16_filter<256, 256, 4, 2, 64, 3, 0, false, 0, 2, 0, true, 1, 1>(SV_F16_ARGS);
+  if (c.kernel == F16Kernel::ProbePhases) {   // synchronises and prints the shares of the kernel's phases
+    unsigned long long z[8] = {0, 0, 0, 0, 0, 0, 0, 0}, c8[8];
+    SV_HIP(hipMemcpyToSymbol(HIP_SYMBOL(sv_f16_phase_cycles), z, sizeof(z)));
+    const int rc = launch(F16ProbePhases{});
+    SV_HIP(hipStreamSynchronize(ctx->stream));
+    SV_HIP(hipMemcpyFromSymbol(c8, HIP_SYMBOL(sv_f16_phase_cycles), sizeof(c8)));
+    double tot = 0;
+    for (int k = 0; k < 6; ++k) tot += (double)c8[k];
+    fprintf(stderr, "[f16 filter phases] M=%d n=%d: head-wait %.1f%% main %.1f%% stage %.1f%% pass1 %.1f%% pass2a %.1f%% rest %.1f%% (%.3g cycles/WG-sum)\n",
+            M, n_sample, 100 * c8[0] / tot, 100 * c8[1] / tot, 100 * c8[2] / tot, 100 * c8[3] / tot, 100 * c8[4] / tot, 100 * c8[5] / tot, tot);
+    return rc;
+  }
 #endif
-      return launch_f16_filter<256, 256, 4, 2, 64, 3, 0, false, 0, 2, 0, true>(SV_F16_ARGS);
-    case 251:   // 250 without the bias (A/B; norms too unbalanced for the biased margin)
-    unbiased_250:
-      if ((int64_t)((M + 255) / 256) * ((n_sample + 255) / 256) >= 1024)
-        return launch_f16_filter<256, 256, 4, 2, 64, 3, 0, true, 0, 2>(SV_F16_ARGS);
-      return launch_f16_filter<256, 256, 4, 2, 64, 3, 0, false, 0, 2>(SV_F16_ARGS);
-#ifdef SEGVLAD_ABLATIONS
-    case 40: return launch_f16_filter<256, 256, 4, 2, 64, 3, 0, false, 1>(SV_F16_ARGS);  // database rows non-temporal
-    case 41: return launch_f16_filter<256, 256, 4, 2, 64, 3, 0, false, 2>(SV_F16_ARGS);  // queries non-temporal
-    case 42: return launch_f16_filter<256, 256, 4, 2, 64, 3, 0, false, 3>(SV_F16_ARGS);  // both
-    case 1: return launch_f16_filter<256, 256, 4, 2, 32, 2>(SV_F16_ARGS);  //  64 KiB LDS, 2 workgroups / CU
-    case 2: return launch_f16_filter<128, 128, 2, 2, 64, 3>(SV_F16_ARGS);  //  80 KiB
-    case 4: return launch_f16_filter<256, 256, 4, 2, 32, 3>(SV_F16_ARGS);  //  80 KiB
-    case 60: return launch_f16_filter<64, 128, 1, 2, 64, 3>(SV_F16_ARGS);   //  64 KiB, 2 waves: one query image (<= 64 rows) per pass
-#endif
-    case 62: return launch_f16_filter<64, 128, 1, 2, 64, 3, 0, false, 1>(SV_F16_ARGS);   // 60 + database rows non-temporal
-    case 63: return launch_f16_filter<128, 128, 2, 2, 64, 3, 0, false, 1>(SV_F16_ARGS);  // 2 + database rows non-temporal
-#ifdef SEGVLAD_ABLATIONS
-    case 5: return launch_f16_filter<256, 256, 2, 2, 64, 3>(SV_F16_ARGS);  // 4 waves of 128 x 128: 0.5 LDS fragment / MFMA
-    case 55: return launch_f16_filter<256, 256, 2, 2, 64, 3, 0, false, 0, -1>(SV_F16_ARGS);  // + software-pipelined loop
-    case 255:
-      if ((int64_t)((M + 255) / 256) * ((n_sample + 255) / 256) >= 1024)
-        return launch_f16_filter<256, 256, 2, 2, 64, 3, 0, true, 0, -1>(SV_F16_ARGS);       // + persistent
-      return launch_f16_filter<256, 256, 2, 2, 64, 3, 0, false, 0, -1>(SV_F16_ARGS);
-    case 15: return launch_f16_filter<256, 256, 2, 2, 64, 3, 1>(SV_F16_ARGS);
-    case 155: return launch_f16_filter<256, 256, 2, 2, 64, 3, 1, false, 0, -1>(SV_F16_ARGS);
-    case 6: return launch_f16_filter<256, 256, 2, 2, 32, 3>(SV_F16_ARGS);
-    case 7: return launch_f16_filter<256, 128, 4, 1, 32, 3>(SV_F16_ARGS);  // 56 KiB, 4 waves: 2 independent workgroups / CU
-    case 17: return launch_f16_filter<256, 128, 4, 1, 32, 3, 1>(SV_F16_ARGS);
-    case 8: return launch_f16_filter<256, 128, 4, 1, 32, 2>(SV_F16_ARGS);
-    case 9: return launch_f16_filter<128, 256, 2, 2, 32, 3>(SV_F16_ARGS);
-    default: return launch_f16_filter<128, 128, 2, 2, 32, 2>(SV_F16_ARGS); //  32 KiB
-#else
-    default: return ctx->fail(SEGVLAD_ERR_ARG, "fp16 filter configuration %d exists in development builds only (SEGVLAD_BUILD_ABLATIONS=1)", c);
-#endif
-  }
-#undef SV_F16_ARGS
-}
-
-// ---- candidate handling ----------------------------------------------------------------------------------
-// wave-aggregated LDS histogram increment (keys cluster on few digits: a plain atomicAdd would serialise)
-__device__ __forceinline__ void hist_add_(uint32_t* hist, bool active, uint32_t bin) {
-  uint64_t todo = __ballot(active);
-  while (todo) {
-    const int leader = __ffsll((unsigned long long)todo) - 1;
-    const uint32_t lb = __shfl(bin, leader);
-    const uint64_t same = __ballot(active && bin == lb) & todo;
-    if ((int)(threadIdx.x & 63) == leader) atomicAdd(&hist[lb], (uint32_t)__popcll(same));
-    todo &= ~same;
-  }
-}
-
-// Candidate lists are only RANKED here, never sorted: an MSB-first radix select over the keys held in LDS
-// yields A_k, the k-th smallest approximate distance (+inf if fewer than k candidates).
-//   mode 0: thr_out[q] = A_k
-//   mode 1: refine list = ids with d2~ <= A_k + 2 eps(q) (unordered; at most rcap, more -> the row is flagged in ovf_rows)
-__global__ __launch_bounds__(256) void select_approx_kernel(uint32_t* __restrict__ cnt, float* __restrict__ cd2,
-                                                            uint32_t* __restrict__ cid, int cap, int k, int mode, int check,
-                                                            const float* __restrict__ thr_in, int64_t thr_in_ld,
-                                                            const float* __restrict__ qn, float c_eps, float rn_max,
-                                                            float* __restrict__ thr_out, uint32_t* __restrict__ ref_cnt,
-                                                            uint32_t* __restrict__ ref_id, int rcap,
-                                                            uint32_t* __restrict__ ovf_rows,
-                                                            uint32_t* __restrict__ ovf_count,
-                                                            const uint32_t* __restrict__ todo,
-                                                            uint32_t* __restrict__ rovf_rows,
-                                                            uint32_t* __restrict__ rovf_count,
-                                                            float* __restrict__ ref_lim) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  uint32_t* keys = reinterpret_cast<uint32_t*>(smem);  // [cap]
-  __shared__ uint32_t hist[256];
-  __shared__ uint32_t s_digit, s_krem, s_n;
-  const int tid = threadIdx.x;
-  const int64_t row = blockIdx.x;
-  if (todo && !todo[row]) return;   // already ranked by select_small_kernel
-  __shared__ uint32_t s_c;
-  if (tid == 0) {
-    s_c = cnt[row];
-    if (mode != 1) cnt[row] = 0u;   // the next level's filter appends from zero (no memset launch between the levels); mode 2: below
-  }
-  __syncthreads();
-  const uint32_t c = s_c;
-  // the threshold this list was collected under (read before thr_out -- possibly the same word -- is overwritten)
-  const float t_in = ((check && mode == 1) || mode == 2) ? thr_in[row * thr_in_ld] : 0.f;
-  auto flag_row = [&]() {
-    // this query is redone later (rigorous thresholds / exact matrix path): a threshold of -inf keeps its candidate
-    // list empty at the finer levels, an empty refine list makes the refinement a no-op
-    if (tid == 0) {
-      if (atomicExch(&ovf_rows[row], 1u) == 0u) atomicAdd(ovf_count, 1u);
-      if (mode == 1) ref_cnt[row] = 0;
-      else thr_out[row] = -INFINITY;
-    }
-  };
-  if (c > (uint32_t)cap || ovf_rows[row] || (check && (int)c < k)) {   // overflow / flagged at a coarser level / too few
-    flag_row();
-    return;
-  }
-  for (int j = tid; j < (int)c; j += 256) keys[j] = f2key_(cd2[row * cap + j]);
-  float ak = INFINITY;
-  if ((int)c >= k) {
-    uint32_t prefix = 0, mask = 0, krem = (uint32_t)k;
-    for (int pass = 3; pass >= 0; --pass) {
-      hist[tid] = 0;
-      __syncthreads();
-      const int shift = 8 * pass;
-      for (int j0 = 0; j0 < (int)c; j0 += 256) {
-        const int j = j0 + tid;
-        const uint32_t key = (j < (int)c) ? keys[j] : 0u;
-        hist_add_(hist, (j < (int)c) && ((key & mask) == prefix), (key >> shift) & 255u);
-      }
-      __syncthreads();
-      if (tid == 0) {
-        uint32_t cum = 0, dsel = 255;
-        for (uint32_t b = 0; b < 256; ++b) {
-          const uint32_t h = hist[b];
-          if (cum + h >= krem) {
-            dsel = b;
-            break;
-          }
-          cum += h;
-        }
-        s_digit = dsel;
-        s_krem = krem - cum;
-      }
-      __syncthreads();
-      prefix |= s_digit << shift;
-      mask |= 255u << shift;
-      krem = s_krem;
-      __syncthreads();
-    }
-    ak = key2f_(prefix);
-  } else {
-    __syncthreads();
-  }
-  if (mode == 0) {
-    if (tid == 0) thr_out[row] = ak;
-    return;
-  }
-  if (mode == 2) {   // carry (see select_small_body): in place, 256 entries at a time -- a chunk's survivors land below its own start + 256
-    const float t2 = fminf(ak, t_in);
-    const float lim2 = t2 + 2.f * c_eps * sqrtf(qn[row] * rn_max);
-    if (tid == 0) s_n = 0;
-    __syncthreads();
-    for (int j0 = 0; j0 < (int)c; j0 += 256) {
-      const int j = j0 + tid;
-      const float v = (j < (int)c) ? key2f_(keys[j]) : INFINITY;
-      const uint32_t id = (j < (int)c) ? cid[row * cap + j] : 0u;
-      __syncthreads();   // the chunk is in registers
-      if (j < (int)c && v <= lim2) {
-        const uint32_t pos = atomicAdd(&s_n, 1u);
-        cd2[row * cap + pos] = v;
-        cid[row * cap + pos] = id;
-      }
-      __syncthreads();   // (the next chunk's reads start at j0 + 256 >= every position written so far)
-    }
-    if (tid == 0) {
-      thr_out[row] = t2;
-      cnt[row] = s_n;
-    }
-    return;
-  }
-  // heuristic thresholds: the list holds every row with d2~ <= t_in + 2 eps; the refine set {d2~ <= A_k + 2 eps} is
-  // contained in it iff A_k <= t_in
-  if (check && !(ak <= t_in)) {
-    flag_row();
-    return;
-  }
-  const float flim = ak + 2.f * c_eps * sqrtf(qn[row] * rn_max);
-  const uint32_t klim = f2key_(flim);
-  if (tid == 0) s_n = 0;
-  __syncthreads();
-  for (int j = tid; j < (int)c; j += 256) {
-    if (keys[j] <= klim) {
-      const uint32_t slot = atomicAdd(&s_n, 1u);
-      if (slot < (uint32_t)rcap) ref_id[row * rcap + slot] = cid[row * cap + j];
-    }
-  }
-  __syncthreads();
-  if (tid == 0) {
-    if (s_n > (uint32_t)rcap) {
-      // the band holds more rows than the first-tier refine list: second tier (refine2_compact_kernel + a refinement
-      // pass straight from the candidate list), or -- without one -- the exact matrix path
-      if (rovf_rows) {
-        rovf_rows[row] = 1u;
-        ref_lim[row] = flim;
-        atomicAdd(rovf_count, 1u);
-      } else if (atomicExch(&ovf_rows[row], 1u) == 0u) {
-        atomicAdd(ovf_count, 1u);
-      }
-      ref_cnt[row] = 0;
-    } else {
-      ref_cnt[row] = s_n;
-    }
-  }
-}
-
-// The same ranking for lists of up to 4096 candidates (every list of the low-rank level scheme, and nearly every list of
-// the rigorous one), one WAVE per query instead of one 256-thread workgroup: the keys live in registers (4, 16 or 64 per
-// lane, by the list's length), the rank-th smallest is found by a binary MSB-first radix select whose per-bit counts are
-// per-lane sums + one DPP wave reduction, the refine list is compacted by ballots.  No LDS, no barriers.  Longer lists are
-// left to select_approx_kernel (todo[row] = 1).
-// select_small_body: the ranking itself for lists of at most 64 * PER keys (PER register slots per lane, loops fully
-// unrolled: a run-time bound on the slot loops cost a scalar branch per slot and bit -- 40 us per launch).
-template <int PER>
-__device__ __forceinline__ void select_small_body(uint32_t* __restrict__ cnt, float* __restrict__ cd2, uint32_t* __restrict__ cid, int64_t row, int l,
-                                                  uint32_t c, int cap, int k, int mode, int check, float t_in,
-                                                  const float* __restrict__ qn, float c_eps, float rn_max,
-                                                  float* __restrict__ thr_out, uint32_t* __restrict__ ref_cnt,
-                                                  uint32_t* __restrict__ ref_id, int rcap, uint32_t* __restrict__ ovf_rows,
-                                                  uint32_t* __restrict__ ovf_count, uint32_t* __restrict__ rovf_rows,
-                                                  uint32_t* __restrict__ rovf_count, float* __restrict__ ref_lim) {
-  auto flag_row = [&]() {
-    if (l == 0) {
-      if (atomicExch(&ovf_rows[row], 1u) == 0u) atomicAdd(ovf_count, 1u);
-      if (mode == 1) ref_cnt[row] = 0;
-      else thr_out[row] = -INFINITY;
-    }
-  };
-  constexpr uint32_t PAD = 0xffffffffu;   // padding sorts last (a real key is never all ones: NaN-free)
-  uint32_t key[PER], cidv[PER];
-#pragma unroll
-  for (int i = 0; i < PER; ++i) {
-    const int j = l + 64 * i;
-    key[i] = PAD;
-    cidv[i] = 0u;
-    if (j < (int)c) {
-      key[i] = f2key_(cd2[row * cap + j]);
-      // mode 1: the ids travel with the keys (fetched behind a ballot branch, slot by slot, each was a round trip of its own:
-      // 12 of the 19 us of a pass's last select)
-      if (mode != 0) cidv[i] = cid[row * cap + j];
-    }
-  }
-  float ak = INFINITY;
-  if ((int)c >= k) {
-    // The keys of a list share their leading bits (distances of one query: same sign, a handful of exponents), and after a
-    // dozen more only one key still matches the prefix: the bit loop starts below the common prefix of the list's smallest and
-    // largest key and stops as soon as a single candidate is left (32 bits x 2 PER VALU instructions were 7 of the ~10 us of a
-    // 4096-key launch).  All of it is wave-uniform.
-    uint32_t kmn = 0xffffffffu, kmx = 0u;
-#pragma unroll
-    for (int i = 0; i < PER; ++i) {
-      kmn = min(kmn, key[i]);
-      kmx = key[i] != PAD ? max(kmx, key[i]) : kmx;
-    }
-    kmn = wave_min_u32_(kmn);
-    kmx = wave_max_u32_(kmx);
-    const uint32_t diff = kmn ^ kmx;
-    uint32_t prefix = kmn, mask = 0xffffffffu, rem = (uint32_t)k, m = c;   // diff == 0: every key is kmn
-    int bit = -1;
-    if (diff) {
-      bit = 31 - __builtin_clz(diff);
-      mask = (bit == 31) ? 0u : ~((2u << bit) - 1u);
-      prefix = kmn & mask;
-    }
-    for (; bit >= 0 && m > 1u; --bit) {
-      const uint32_t b = 1u << bit;
-      // keys that match the prefix so far and have this bit clear: counted per lane (a compare + an add per key slot), then
-      // ONE wave sum per bit by DPP row reductions + four readlanes.  (The butterfly of six ds_bpermute shuffles it replaces
-      // was ~8 us of LDS-crossbar latency per launch; a ballot + scalar popcount per slot stalls on the VALU -> SALU
-      // hand-over of every compare: 42 us for 64 slots.)
-      uint32_t zl = 0;
-#pragma unroll
-      for (int i = 0; i < PER; ++i) zl += ((key[i] & (mask | b)) == prefix) ? 1u : 0u;
-      const uint32_t zeros = wave_sum_u32_(zl);
-      if (rem > zeros) {
-        rem -= zeros;
-        m -= zeros;
-        prefix |= b;
-      } else {
-        m = zeros;
-      }
-      mask |= b;
-    }
-    if (bit >= 0) {   // one key left under the prefix: it is the answer, whatever its remaining bits
-      uint32_t v = 0;
-#pragma unroll
-      for (int i = 0; i < PER; ++i) v |= (key[i] != PAD && (key[i] & mask) == prefix) ? key[i] : 0u;
-      prefix = wave_max_u32_(v);
-    }
-    ak = key2f_(prefix);
-  }
-  if (mode == 0) {
-    if (l == 0) thr_out[row] = ak;
-    return;
-  }
-  if (mode == 2) {
-    // carry: the next level runs over the rows this level has NOT seen (the complement of its sample), under the threshold
-    // t2 = min(A_k, t_in).  This list holds every sampled row with d2~ <= t_in + 2 eps, hence every one with d2~ <= t2 + 2 eps --
-    // exactly the rows the next level's filter would append for the sample: they are compacted to the front and the counter is
-    // left at their number.  (A threshold below A_k is as good a guess as A_k: the last level's check is against the value stored.)
-    const float t2 = fminf(ak, t_in);
-    const float lim2 = t2 + 2.f * c_eps * sqrtf(qn[row] * rn_max);
-    uint32_t kept = 0;
-#pragma unroll
-    for (int i = 0; i < PER; ++i) {
-      const float v = key2f_(key[i]);
-      const bool hit = key[i] != PAD && v <= lim2;
-      const uint64_t mk = __builtin_amdgcn_ballot_w64(hit);
-      if (mk != 0ull) {
-        const uint32_t pos = kept + __builtin_amdgcn_mbcnt_hi((uint32_t)(mk >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mk, 0u));
-        if (hit) {   // (every key of the list is in registers: writing in place races with nothing)
-          cd2[row * cap + pos] = v;
-          cid[row * cap + pos] = cidv[i];
-        }
-        kept += (uint32_t)__popcll(mk);
-      }
-    }
-    if (l == 0) {
-      thr_out[row] = t2;
-      cnt[row] = kept;
-    }
-    return;
-  }
-  if (check && !(ak <= t_in)) {
-    flag_row();
-    return;
-  }
-  const float flim = ak + 2.f * c_eps * sqrtf(qn[row] * rn_max);
-  const uint32_t klim = f2key_(flim);
-  uint32_t total = 0;
-#pragma unroll
-  for (int i = 0; i < PER; ++i) {
-    const bool hit = key[i] <= klim;   // (klim is a finite float's key: the padding never hits)
-    const uint64_t mk = __builtin_amdgcn_ballot_w64(hit);
-    if (mk != 0ull) {
-      const uint32_t pos = total + __builtin_amdgcn_mbcnt_hi((uint32_t)(mk >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mk, 0u));
-      if (hit && pos < (uint32_t)rcap) ref_id[row * rcap + pos] = cidv[i];
-      total += (uint32_t)__popcll(mk);
-    }
-  }
-  if (l == 0) {
-    if (total > (uint32_t)rcap) {
-      if (rovf_rows) {   // second tier (see select_approx_kernel)
-        rovf_rows[row] = 1u;
-        ref_lim[row] = flim;
-        atomicAdd(rovf_count, 1u);
-      } else if (atomicExch(&ovf_rows[row], 1u) == 0u) {
-        atomicAdd(ovf_count, 1u);
-      }
-      ref_cnt[row] = 0;
-    } else {
-      ref_cnt[row] = total;
-    }
-  }
-}
-
-// k-th smallest of a workgroup's keys (PER per thread, padding = all ones), c >= 1 real keys among them; +inf if c < k.
-// xs: [2][4] LDS exchange slots.  Every thread returns the same value.
-template <int PER>
-__device__ __forceinline__ float wg_kth_smallest_(const uint32_t (&key)[PER], uint32_t c, int k, uint32_t (*xs)[4], int tid) {
-  constexpr uint32_t PAD = 0xffffffffu;
-  const int w = tid >> 6;
-  int turn = 0;
-  auto exchange = [&](uint32_t v_wave) {   // v_wave: this wave's (uniform) partial; returns the four partials
-    if ((tid & 63) == 0) xs[turn][w] = v_wave;
-    __syncthreads();
-    const uint4 r = make_uint4(xs[turn][0], xs[turn][1], xs[turn][2], xs[turn][3]);
-    turn ^= 1;
-    return r;
-  };
-  float ak = INFINITY;
-  if ((int)c >= k) {
-    uint32_t kmn = PAD, kmx = 0u;
-#pragma unroll
-    for (int i = 0; i < PER; ++i) {
-      kmn = min(kmn, key[i]);
-      kmx = key[i] != PAD ? max(kmx, key[i]) : kmx;
-    }
-    {
-      const uint4 r = exchange(wave_min_u32_(kmn));
-      kmn = min(min(r.x, r.y), min(r.z, r.w));
-    }
-    {
-      const uint4 r = exchange(wave_max_u32_(kmx));
-      kmx = max(max(r.x, r.y), max(r.z, r.w));
-    }
-    const uint32_t diff = kmn ^ kmx;
-    uint32_t prefix = kmn, mask = 0xffffffffu, rem = (uint32_t)k, m = c;   // diff == 0: every key is kmn
-    int bit = -1;
-    if (diff) {
-      bit = 31 - __builtin_clz(diff);
-      mask = (bit == 31) ? 0u : ~((2u << bit) - 1u);
-      prefix = kmn & mask;
-    }
-    for (; bit >= 0 && m > 1u; --bit) {
-      const uint32_t b = 1u << bit;
-      uint32_t zl = 0;
-#pragma unroll
-      for (int i = 0; i < PER; ++i) zl += ((key[i] & (mask | b)) == prefix) ? 1u : 0u;
-      const uint4 r = exchange(wave_sum_u32_(zl));
-      const uint32_t zeros = r.x + r.y + r.z + r.w;
-      if (rem > zeros) {
-        rem -= zeros;
-        m -= zeros;
-        prefix |= b;
-      } else {
-        m = zeros;
-      }
-      mask |= b;
-    }
-    if (bit >= 0) {   // one key left under the prefix: it is the answer, whatever its remaining bits
-      uint32_t v = 0;
-#pragma unroll
-      for (int i = 0; i < PER; ++i) v |= (key[i] != PAD && (key[i] & mask) == prefix) ? key[i] : 0u;
-      const uint4 r = exchange(wave_max_u32_(v));
-      prefix = max(max(r.x, r.y), max(r.z, r.w));
-    }
-    ak = key2f_(prefix);
-  }
-  return ak;
-}
-
-// One query image per pass (<= 128 lists): a whole workgroup per list instead of a wave -- 32 keys per thread (lists of up
-// to 8192 entries, the capacity of the candidate lists; longer ones are flagged for the exact path), the same
-// binary MSB-first radix select below the common prefix of the list's smallest and largest key, stopping when one key is
-// left; the per-bit count is a DPP wave sum + a four-entry LDS exchange (one barrier per bit: the exchange slots alternate).
-// The wave kernel's 64-keys-per-lane instantiation is ~8000 straight-line instructions that a pass runs through ONCE --
-// instruction fetch, not arithmetic: 29 us for a 3906-entry sample row; this kernel takes ~10.
-// PERK: keys per thread.  32 covers the candidate lists' capacity (8192); 16 (lists of <= 4096 entries -- every list the
-// single-image plan produces in practice) halves the slot loops of the load and of every radix step: the kernel picks the
-// body by the list's length (workgroup-uniform).
-template <int PERK>
-__device__ __forceinline__ void select_wg_body(uint32_t* __restrict__ cnt, const float* __restrict__ cd2,
-                                                        const uint32_t* __restrict__ cid, int cap, int k, int mode, int check,
-                                                        const float* __restrict__ thr_in, int64_t thr_in_ld,
-                                                        const float* __restrict__ qn, float c_eps, float rn_max,
-                                                        float* __restrict__ thr_out, uint32_t* __restrict__ ref_cnt,
-                                                        uint32_t* __restrict__ ref_id, int rcap, uint32_t* __restrict__ ovf_rows,
-                                                        uint32_t* __restrict__ ovf_count, uint32_t* __restrict__ rovf_rows,
-                                                        uint32_t* __restrict__ rovf_count, float* __restrict__ ref_lim, int fixed_cnt,
-                                                        const uint32_t c, const float (&pre_d2)[16], const uint32_t (&pre_id)[16],
-                                                        const uint32_t flagged, const float t_in) {
-  constexpr uint32_t PAD = 0xffffffffu;
-  constexpr int PER = PERK;   // 32: 8192 keys, the candidate lists' capacity (SV_CAP)
-  __shared__ uint32_t xs[2][4];
-  __shared__ uint32_t s_n;
-  const int tid = threadIdx.x;
-  const int64_t row = blockIdx.x;
-  uint32_t key[PER], cidv[PER];
-#pragma unroll
-  for (int i = 0; i < PER; ++i) {
-    const int j = tid + 256 * i;
-    key[i] = PAD;
-    cidv[i] = 0u;
-    if (j < (int)c && c <= (uint32_t)(256 * PER)) {
-      // (the first 16 slots per thread were requested by the kernel together with the list's length: one round trip, not two)
-      key[i] = f2key_(i < 16 ? pre_d2[i < 16 ? i : 0] : cd2[row * cap + j]);
-      if (mode == 1) cidv[i] = i < 16 ? pre_id[i < 16 ? i : 0] : cid[row * cap + j];
-    }
-  }
-  if (tid == 0) s_n = 0u;
-  __syncthreads();   // every thread has read cnt[row]
-  if (tid == 0 && mode == 0) cnt[row] = 0u;   // the next level's filter appends from zero
-  if (c > (uint32_t)cap || c > (uint32_t)(256 * PER) || flagged || (check && (int)c < k)) {
-    if (tid == 0) {
-      if (atomicExch(&ovf_rows[row], 1u) == 0u) atomicAdd(ovf_count, 1u);
-      if (mode == 1) ref_cnt[row] = 0;
-      else thr_out[row] = -INFINITY;
-    }
-    return;
-  }
-  const float ak = wg_kth_smallest_<PER>(key, c, k, xs, tid);
-  if (mode == 0) {
-    if (tid == 0) thr_out[row] = ak;
-    return;
-  }
-  if (check && !(ak <= t_in)) {   // see select_approx_kernel
-    if (tid == 0) {
-      if (atomicExch(&ovf_rows[row], 1u) == 0u) atomicAdd(ovf_count, 1u);
-      ref_cnt[row] = 0;
-    }
-    return;
-  }
-  const float flim = ak + 2.f * c_eps * sqrtf(qn[row] * rn_max);
-  const uint32_t klim = f2key_(flim);
-#pragma unroll
-  for (int i = 0; i < PER; ++i)
-    if (key[i] <= klim) {   // (a finite float's key: the padding never hits)
-      const uint32_t pos = atomicAdd(&s_n, 1u);
-      if (pos < (uint32_t)rcap) ref_id[row * rcap + pos] = cidv[i];
-    }
-  __syncthreads();
-  if (tid == 0) {
-    const uint32_t total = s_n;
-    if (total > (uint32_t)rcap) {
-      if (rovf_rows) {   // second tier (see select_approx_kernel)
-        rovf_rows[row] = 1u;
-        ref_lim[row] = flim;
-        atomicAdd(rovf_count, 1u);
-      } else if (atomicExch(&ovf_rows[row], 1u) == 0u) {
-        atomicAdd(ovf_count, 1u);
-      }
-      ref_cnt[row] = 0;
-    } else {
-      ref_cnt[row] = total;
-    }
-  }
-}
-
-__global__ __launch_bounds__(256) void select_wg_kernel(uint32_t* __restrict__ cnt, const float* __restrict__ cd2,
-                                                        const uint32_t* __restrict__ cid, int cap, int k, int mode, int check,
-                                                        const float* __restrict__ thr_in, int64_t thr_in_ld,
-                                                        const float* __restrict__ qn, float c_eps, float rn_max,
-                                                        float* __restrict__ thr_out, uint32_t* __restrict__ ref_cnt,
-                                                        uint32_t* __restrict__ ref_id, int rcap, uint32_t* __restrict__ ovf_rows,
-                                                        uint32_t* __restrict__ ovf_count, uint32_t* __restrict__ rovf_rows,
-                                                        uint32_t* __restrict__ rovf_count, float* __restrict__ ref_lim, int fixed_cnt) {
-  // Everything the list's length decides is REQUESTED before the length is known: the first 16 slots of every thread (lists of
-  // <= 4096 entries -- every list the single-image plan produces in practice -- are complete with them; the slots lie inside the
-  // row's `cap` entries whatever the length, entries beyond it are never looked at), the row's flag, its threshold.  The length
-  // used to be a round trip of its own in front of them (round 6: ~1.5 us of a 20-us kernel that is a chain of such trips).
-  const int64_t row = blockIdx.x;
-  float pre_d2[16];
-  uint32_t pre_id[16];
-#pragma unroll
-  for (int i = 0; i < 16; ++i) {
-    const int j = threadIdx.x + 256 * i;
-    const bool in = j < cap;
-    pre_d2[i] = in ? cd2[row * cap + j] : 0.f;
-    pre_id[i] = (in && mode == 1) ? cid[row * cap + j] : 0u;
-  }
-  const uint32_t flagged = ovf_rows[row];
-  const float t_in = (check && mode == 1) ? thr_in[row * thr_in_ld] : 0.f;
-  const uint32_t c = fixed_cnt >= 0 ? (uint32_t)fixed_cnt : cnt[row];
-  if (c <= 4096u)
-    select_wg_body<16>(cnt, cd2, cid, cap, k, mode, check, thr_in, thr_in_ld, qn, c_eps, rn_max, thr_out, ref_cnt, ref_id, rcap, ovf_rows,
-                       ovf_count, rovf_rows, rovf_count, ref_lim, fixed_cnt, c, pre_d2, pre_id, flagged, t_in);
-  else
-    select_wg_body<32>(cnt, cd2, cid, cap, k, mode, check, thr_in, thr_in_ld, qn, c_eps, rn_max, thr_out, ref_cnt, ref_id, rcap, ovf_rows,
-                       ovf_count, rovf_rows, rovf_count, ref_lim, fixed_cnt, c, pre_d2, pre_id, flagged, t_in);
-}
-
-// The sampled exact level of a single-image pass: the K-split partial dot products of <= 128 query rows against <= 4096
-// sample rows are reduced (slices added in index order, sv_d2 with the norms: splitk_reduce_d2_kernel's arithmetic, value for
-// value) and the row's rank-th smallest distance is selected in the same workgroup -- one launch instead of two in a pass
-// that is a chain of dependent launches.
-__global__ __launch_bounds__(256) void l0_reduce_rank_kernel(const float* __restrict__ part, int splits, int M, int N, int64_t ldc,
-                                                             const float* __restrict__ row_add, const float* __restrict__ col_add,
-                                                             int b_stride, int rank, float* __restrict__ thr_out,
-                                                             uint32_t* __restrict__ cnt, const uint32_t* __restrict__ ovf_rows) {
-  constexpr uint32_t PAD = 0xffffffffu;
-  constexpr int PER = 16;
-  __shared__ uint32_t xs[2][4];
-  const int tid = threadIdx.x;
-  const int64_t row = blockIdx.x;
-  const int64_t mn = (int64_t)M * ldc;
-  const float q2 = row_add[row];
-  // slice-major: the 16 loads of a slice are in flight together, two slices per round trip (one load after the other down a
-  // column is 8 dependent round trips per key: 35 us for this kernel)
-  float sum[PER], rn[PER];
-  const float* p0 = part + row * ldc + tid;
-#pragma unroll
-  for (int i = 0; i < PER; ++i) {
-    const bool in = tid + 256 * i < N;
-    sum[i] = in ? p0[256 * i] : 0.f;
-    rn[i] = in ? col_add[(int64_t)(tid + 256 * i) * b_stride] : 0.f;
-  }
-  int t = 1;
-  for (; t + 1 < splits; t += 2) {
-    float a[PER], b[PER];
-#pragma unroll
-    for (int i = 0; i < PER; ++i) {
-      const bool in = tid + 256 * i < N;
-      a[i] = in ? p0[(int64_t)t * mn + 256 * i] : 0.f;
-      b[i] = in ? p0[(int64_t)(t + 1) * mn + 256 * i] : 0.f;
-    }
-#pragma unroll
-    for (int i = 0; i < PER; ++i) sum[i] = (sum[i] + a[i]) + b[i];   // (index order, as splitk_reduce_d2_kernel adds them)
-  }
-  if (t < splits) {
-#pragma unroll
-    for (int i = 0; i < PER; ++i) sum[i] += (tid + 256 * i < N) ? p0[(int64_t)t * mn + 256 * i] : 0.f;
-  }
-  uint32_t key[PER];
-#pragma unroll
-  for (int i = 0; i < PER; ++i) key[i] = (tid + 256 * i < N) ? f2key_(sv_d2(q2, rn[i], sum[i])) : PAD;
-  if (tid == 0) cnt[row] = 0u;   // the next level's filter appends from zero
-  if (ovf_rows[row] || N < rank) {   // (workgroup-uniform)
-    if (tid == 0) thr_out[row] = -INFINITY;
-    return;
-  }
-  const float ak = wg_kth_smallest_<PER>(key, (uint32_t)N, rank, xs, tid);
-  if (tid == 0) thr_out[row] = ak;
-}
-
-int sv_launch_l0_reduce_rank(segvlad_ctx* ctx, const float* parts, int splits, int M, int n_sample, int64_t ldc, const float* qn,
-                             const float* rn, int b_stride, int rank, float* thr_out, uint32_t* cand_cnt, const uint32_t* fail_rows) {
-  if (M <= 0) return SEGVLAD_OK;
-  if (n_sample > 4096) return ctx->fail(SEGVLAD_ERR_LIMIT, "l0_reduce_rank: rows of at most 4096 columns");
-  hipLaunchKernelGGL(l0_reduce_rank_kernel, dim3(M), dim3(256), 0, ctx->stream, parts, splits, M, n_sample, ldc, qn, rn, b_stride, rank,
-                     thr_out, cand_cnt, fail_rows);
-  SV_HIP(hipGetLastError());
-  return SEGVLAD_OK;
-}
-
-__global__ __launch_bounds__(256) void select_small_kernel(uint32_t* __restrict__ cnt, float* __restrict__ cd2,
-                                                           uint32_t* __restrict__ cid, int nq, int cap, int k, int mode, int check,
-                                                           const float* __restrict__ thr_in, int64_t thr_in_ld,
-                                                           const float* __restrict__ qn, float c_eps, float rn_max,
-                                                           float* __restrict__ thr_out, uint32_t* __restrict__ ref_cnt,
-                                                           uint32_t* __restrict__ ref_id, int rcap, uint32_t* __restrict__ ovf_rows,
-                                                           uint32_t* __restrict__ ovf_count, uint32_t* __restrict__ todo,
-                                                           uint32_t* __restrict__ rovf_rows, uint32_t* __restrict__ rovf_count,
-                                                           float* __restrict__ ref_lim, int fixed_cnt) {
-  constexpr int PER = 64;   // up to 4096 keys per wave, in registers
-  const int l = threadIdx.x & 63;
-  const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= nq) return;
-  const uint32_t c = fixed_cnt >= 0 ? (uint32_t)fixed_cnt : cnt[row];   // fixed_cnt: every row is a list of that length
-  if (todo && c > (uint32_t)(64 * PER) && c <= (uint32_t)cap && !ovf_rows[row]) {   // long list: the workgroup kernel ranks it
-    if (l == 0) todo[row] = 1u;
-    return;
-  }
-  if (l == 0) {
-    if (todo) todo[row] = 0u;
-    if (mode != 1) cnt[row] = 0u;   // the next level's filter appends from zero (no memset launch between the levels); mode 2: see the body
-  }
-  const float t_in = ((check && mode == 1) || mode == 2) ? thr_in[row * thr_in_ld] : 0.f;
-  auto flag_row = [&]() {
-    if (l == 0) {
-      if (atomicExch(&ovf_rows[row], 1u) == 0u) atomicAdd(ovf_count, 1u);
-      if (mode == 1) ref_cnt[row] = 0;
-      else thr_out[row] = -INFINITY;
-    }
-  };
-  // todo == null (a handful of queries: the workgroup kernel is not even launched): a list beyond the wave's 4096 keys is
-  // treated like an overflowing one -- the query is redone on the exact path
-  if (c > (uint32_t)cap || (!todo && c > (uint32_t)(64 * PER)) || ovf_rows[row] || (check && (int)c < k)) {
-    flag_row();
-    return;
-  }
-  if (c <= 256u)
-    select_small_body<4>(cnt, cd2, cid, row, l, c, cap, k, mode, check, t_in, qn, c_eps, rn_max, thr_out, ref_cnt, ref_id, rcap, ovf_rows,
-                         ovf_count, rovf_rows, rovf_count, ref_lim);
-  else if (c <= 1024u)
-    select_small_body<16>(cnt, cd2, cid, row, l, c, cap, k, mode, check, t_in, qn, c_eps, rn_max, thr_out, ref_cnt, ref_id, rcap, ovf_rows,
-                          ovf_count, rovf_rows, rovf_count, ref_lim);
-  else if (c <= 2048u)
-    select_small_body<32>(cnt, cd2, cid, row, l, c, cap, k, mode, check, t_in, qn, c_eps, rn_max, thr_out, ref_cnt, ref_id, rcap, ovf_rows,
-                          ovf_count, rovf_rows, rovf_count, ref_lim);
-  else
-    select_small_body<64>(cnt, cd2, cid, row, l, c, cap, k, mode, check, t_in, qn, c_eps, rn_max, thr_out, ref_cnt, ref_id, rcap, ovf_rows,
-                          ovf_count, rovf_rows, rovf_count, ref_lim);
-}
-
-int sv_launch_select_approx(segvlad_ctx* ctx, uint32_t* cand_cnt, float* cand_d2, uint32_t* cand_id, int nq,
-                            int cap, int rank, int mode, int check, const float* thr_in, int64_t thr_in_ld, const float* qn,
-                            float c_eps, float rn_max, float* thr_out, uint32_t* ref_cnt, uint32_t* ref_id, int rcap,
-                            uint32_t* fail_rows, uint32_t* fail_count, uint32_t* rovf_rows, uint32_t* rovf_count, float* ref_lim,
-                            int fixed_cnt) {
-  if (nq <= 0) return SEGVLAD_OK;
-  if (mode == 2 && nq <= 128) return ctx->fail(SEGVLAD_ERR_STATE, "select: the carrying form exists for batches only");
-  if (nq <= 128) {   // one query image per pass: a workgroup per list
-    hipLaunchKernelGGL(select_wg_kernel, dim3(nq), dim3(256), 0, ctx->stream, cand_cnt, cand_d2, cand_id, cap, rank, mode, check, thr_in,
-                       thr_in_ld, qn, c_eps, rn_max, thr_out, ref_cnt, ref_id, rcap, fail_rows, fail_count, rovf_rows, rovf_count,
-                       ref_lim, fixed_cnt);
-    SV_HIP(hipGetLastError());
-    return SEGVLAD_OK;
-  }
-  const bool wave_only = fixed_cnt >= 0 && fixed_cnt <= 4096;
-  uint32_t* todo = nullptr;
-  if (!wave_only) {
-    SV_HIP(ctx->s_sel_todo.reserve((size_t)nq * 4));
-    todo = ctx->s_sel_todo.as<uint32_t>();
-  }
-  hipLaunchKernelGGL(select_small_kernel, dim3((nq + 3) / 4), dim3(256), 0, ctx->stream, cand_cnt, cand_d2, cand_id, nq, cap, rank, mode,
-                     check, thr_in, thr_in_ld, qn, c_eps, rn_max, thr_out, ref_cnt, ref_id, rcap, fail_rows, fail_count, todo,
-                     rovf_rows, rovf_count, ref_lim, fixed_cnt);
-  if (wave_only) {   // every list is ranked (or flagged) by the wave kernel
-    SV_HIP(hipGetLastError());
-    return SEGVLAD_OK;
-  }
-  const size_t lds = (size_t)cap * 4;
-  hipLaunchKernelGGL(select_approx_kernel, dim3(nq), dim3(256), lds, ctx->stream, cand_cnt, cand_d2, cand_id, cap, rank, mode, check,
-                     thr_in, thr_in_ld, qn, c_eps, rn_max, thr_out, ref_cnt, ref_id, rcap, fail_rows, fail_count, todo,
-                     rovf_rows, rovf_count, ref_lim);
-  SV_HIP(hipGetLastError());
-  return SEGVLAD_OK;
-}
-
-// Second refinement tier.  A query whose band {d2~ <= A_k + 2 eps} holds more rows than the first-tier list (SV_RCAP) --
-// temporally redundant databases: every reference segment comes with its ~30 near-duplicates from the neighbouring video
-// frames, so whole clumps of rows sit inside the band -- keeps its candidate list (<= cap entries, a superset of the band):
-// this kernel compacts the band's ids to the front of that list, in place, and the exact refinement then runs straight
-// from it (rcap = cap).  Only the flagged rows do any work; nobody is sent to the distance-matrix path for this.
-__global__ __launch_bounds__(256) void refine2_compact_kernel(const uint32_t* __restrict__ rovf_rows, const float* __restrict__ ref_lim,
-                                                              uint32_t* __restrict__ cnt, const float* __restrict__ cd2,
-                                                              uint32_t* __restrict__ cid, int cap) {
-  __shared__ uint32_t wtot[4];
-  const int64_t row = blockIdx.x;
-  if (!rovf_rows[row]) return;
-  const int tid = threadIdx.x, l = tid & 63, w = tid >> 6;
-  const uint32_t c = cnt[row];
-  const float lim = ref_lim[row];
-  uint32_t base = 0;
-  for (uint32_t j0 = 0; j0 < c; j0 += 256) {
-    const uint32_t j = j0 + tid;
-    const bool hit = j < c && cd2[row * cap + j] <= lim;
-    const uint32_t id = hit ? cid[row * cap + j] : 0u;
-    const uint64_t mk = __builtin_amdgcn_ballot_w64(hit);
-    if (l == 0) wtot[w] = (uint32_t)__popcll(mk);
-    __syncthreads();   // every read of this chunk precedes its writes (which land at positions <= the reads': in place is safe)
-    uint32_t off = base;
-    for (int x = 0; x < w; ++x) off += wtot[x];
-    const uint32_t pos = off + __builtin_amdgcn_mbcnt_hi((uint32_t)(mk >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mk, 0u));
-    if (hit) cid[row * cap + pos] = id;
-    base += wtot[0] + wtot[1] + wtot[2] + wtot[3];
-    __syncthreads();
-  }
-  if (tid == 0) cnt[row] = base;
-}
-
-int sv_launch_refine2_compact(segvlad_ctx* ctx, const uint32_t* rovf_rows, const float* ref_lim, uint32_t* cand_cnt,
-                              const float* cand_d2, uint32_t* cand_id, int nq, int cap) {
-  if (nq <= 0) return SEGVLAD_OK;
-  hipLaunchKernelGGL(refine2_compact_kernel, dim3(nq), dim3(256), 0, ctx->stream, rovf_rows, ref_lim, cand_cnt, cand_d2, cand_id, cap);
-  SV_HIP(hipGetLastError());
-  return SEGVLAD_OK;
-}
-
-// exact distances of the refine list: the sequential fp32 fma chain over k = 0..d-1 (bit-identical to the
-// v_mfma_f32_32x32x2_f32 chain of the matrix path), then (distance, id) sort and top-k.  One thread per candidate row; the
-// query row is cached in LDS (QLDS; d up to ~38k).  The row is walked with THIRTY-TWO 16-byte loads in flight per thread:
-// a 50-query pass has fewer waves than the chip has SIMDs, so the loop is pure load latency -- one round trip per
-// 32 x 16 B (an 8-deep register double buffer still paid one round trip per 128 B: 78 us per pass).
-// only_rows != null: rows whose flag is clear are left untouched (second refinement tier).
-template <bool QLDS>
-__global__ __launch_bounds__(256) void refine_exact_kernel(const float* __restrict__ Q, const float* __restrict__ R, int d,
-                                                           const float* __restrict__ qn, const float* __restrict__ rn,
-                                                           const uint32_t* __restrict__ ref_cnt,
-                                                           const uint32_t* __restrict__ ref_id, int rcap, int rpad, int k,
-                                                           float* __restrict__ d2_out, int64_t* __restrict__ idx_out,
-                                                           const uint32_t* __restrict__ only_rows) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  float* qs = reinterpret_cast<float*>(smem);                                     // [d] when QLDS
-  uint64_t* a = reinterpret_cast<uint64_t*>(smem + (QLDS ? (size_t)d * 4 : 0));   // [rpad]
-  const int tid = threadIdx.x;
-  const int64_t row = blockIdx.x;
-  if (only_rows && !only_rows[row]) return;
-  const int n = (int)ref_cnt[row];
-  int np2 = 2;   // sort length: the smallest power of two holding the list (<= rpad)
-  while (np2 < n) np2 <<= 1;
-  if (QLDS)
-    for (int j = tid; j < d; j += 256) qs[j] = Q[row * d + j];
-  for (int j = tid; j < np2; j += 256) a[j] = ~0ull;
-  __syncthreads();
-  const float q2 = qn[row];
-  const float4* qp = QLDS ? reinterpret_cast<const float4*>(qs) : reinterpret_cast<const float4*>(Q + row * d);
-  const int n4 = d >> 2;
-  for (int j = tid; j < n; j += 256) {
-    const uint32_t id = ref_id[row * rcap + j];
-    const float4* rp = reinterpret_cast<const float4*>(R + (size_t)id * d);
-    float acc = 0.f;
-    int t = 0;
-    if ((n4 & 31) == 0) {
-      for (; t < n4; t += 32) {   // 512 B of the row in flight per lane: 8 round trips for a 1024-d row
-        float4 buf[32];
-#pragma unroll
-        for (int u = 0; u < 32; ++u) buf[u] = rp[t + u];
-        __builtin_amdgcn_sched_barrier(0);   // all 32 loads are issued before the first fma (the scheduler otherwise
-                                             // sinks them next to their uses to save registers -- and pays the latency 32 times)
-#pragma unroll
-        for (int u = 0; u < 32; ++u) {
-          const float4 qv = qp[t + u];
-          acc = fmaf(qv.x, buf[u].x, acc);
-          acc = fmaf(qv.y, buf[u].y, acc);
-          acc = fmaf(qv.z, buf[u].z, acc);
-          acc = fmaf(qv.w, buf[u].w, acc);
-        }
-      }
-    } else {
-      for (; t < n4; ++t) {
-        const float4 rv = rp[t];
-        const float4 qv = qp[t];
-        acc = fmaf(qv.x, rv.x, acc);
-        acc = fmaf(qv.y, rv.y, acc);
-        acc = fmaf(qv.z, rv.z, acc);
-        acc = fmaf(qv.w, rv.w, acc);
-      }
-    }
-    const float v = sv_d2(q2, rn[id], acc);
-    a[j] = ((uint64_t)f2key_(v) << 32) | id;
-  }
-  bitonic64(a, np2, tid);
-  for (int j = tid; j < k; j += 256) {
-    float dd = INFINITY;
-    int64_t id = -1;
-    if (j < n) {
-      dd = key2f_((uint32_t)(a[j] >> 32));
-      id = (int64_t)(uint32_t)a[j];
-    }
-    d2_out[row * k + j] = dd;
-    idx_out[row * k + j] = id;
-  }
-}
-
-// Deep rows (raw K*D descriptors: d = 98 304 is 384 KiB per row, far beyond the LDS and -- one row per lane -- beyond what
-// L1 can keep of 256 private streams): the same sequential chain, with the candidate rows fetched COALESCED (KC * 4 bytes
-// of a row per step: C4 lanes x 16 B) into an LDS tile [64 rows][KC (+4 pad)], double buffered, which the 64 lanes of wave 0
-// then walk ONE ROW EACH (conflict-free ds_read_b128: the row stride is 4 banks mod 64); all four waves load.
-// What bounds it is bytes in flight: one workgroup per CU (the tile) with one step of 32 KiB outstanding ran at 1.4-1.8 TB/s
-// -- piece size, a time skew between the rows and the 3 * 2^17-byte row pitch made no difference, and
-// tools/ubench/gather_bw.hip reaches 7 TB/s on the same addresses with 256 KiB per CU in flight.  So the loads run DEPTH
-// steps ahead in a register ring (DEPTH x NP float4 per thread: 128 KiB per CU at DEPTH = 4), and only the step that is due
-// is written to the LDS tile.  d % KC == 0.
-template <int KC, int DEPTH>
-__global__ __launch_bounds__(256) void refine_exact_wide_kernel(const float* __restrict__ Q, const float* __restrict__ R, int d,
-                                                                const float* __restrict__ qn, const float* __restrict__ rn,
-                                                                const uint32_t* __restrict__ ref_cnt,
-                                                                const uint32_t* __restrict__ ref_id, int rcap, int rpad, int k,
-                                                                float* __restrict__ d2_out, int64_t* __restrict__ idx_out,
-                                                                const uint32_t* __restrict__ only_rows) {
-  constexpr int ROWS = 64, LDR = KC + 4, C4 = KC / 4;    // C4 16-byte pieces per row and step
-  constexpr int NP = ROWS * C4 / 256;                    // pieces per thread and step
-  constexpr int RSTEP = 256 / C4;                        // tile rows between two pieces of a thread
-  static_assert(C4 <= 64 && 64 % C4 == 0 && NP * 256 == ROWS * C4, "a wave covers whole rows");
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  float* tile = reinterpret_cast<float*>(smem);                                 // [2][ROWS][LDR]
-  float* qs = tile + 2 * ROWS * LDR;                                            // [2][KC]
-  uint32_t* ids = reinterpret_cast<uint32_t*>(qs + 2 * KC);                     // [ROWS]
-  uint64_t* a = reinterpret_cast<uint64_t*>(ids + ROWS);                        // [rpad]
-  const int tid = threadIdx.x;
-  const int64_t row = blockIdx.x;
-  if (only_rows && !only_rows[row]) return;
-  const int n = (int)ref_cnt[row];
-  int np2 = 2;
-  while (np2 < n) np2 <<= 1;
-  for (int j = tid; j < np2; j += 256) a[j] = ~0ull;
-  const float q2 = qn[row];
-  const float* qrow = Q + row * d + (tid < C4 ? tid * 4 : 0);
-  const int nch = d / KC;
-  const int seg = tid % C4, lrow0 = tid / C4;   // piece u of this thread: tile row lrow0 + RSTEP u, 16-byte segment seg
-  for (int base = 0; base < n; base += ROWS) {
-    const int cnt = (n - base < ROWS) ? (n - base) : ROWS;
-    __syncthreads();   // the previous pass is done with ids[] and the tile
-    if (tid < cnt) ids[tid] = ref_id[row * rcap + base + tid];
-    __syncthreads();
-    // (no per-piece predication: a branch around every load makes the compiler wait for each one.  Tile rows beyond the
-    //  list re-read candidate 0 -- L2 hits -- and are never looked at; every thread carries a query piece, lanes >= C4 a
-    //  duplicate of piece 0 that is never stored)
-    const float* src[NP];
-#pragma unroll
-    for (int u = 0; u < NP; ++u) {
-      const int lr = lrow0 + RSTEP * u;
-      src[u] = R + (size_t)ids[lr < cnt ? lr : 0] * d + seg * 4;
-    }
-    // The ring is four NAMED register sets and the step is a macro instantiated once per set: hipcc 7.2 sends a
-    // [DEPTH][NP] array that is indexed through a lambda parameter to scratch memory (seen in the ISA: scratch_load/_store
-    // around every piece, vmcnt(0) after every load).
-    static_assert(DEPTH == 4 && NP == 8, "four named ring sets of eight named pieces");
-#define SV_WG_DECL(X) float4 g##X##0, g##X##1, g##X##2, g##X##3, g##X##4, g##X##5, g##X##6, g##X##7, q##X
-    SV_WG_DECL(A);
-    SV_WG_DECL(B);
-    SV_WG_DECL(C);
-    SV_WG_DECL(D);
-#define SV_WG_LOAD(X, c_)                                                          \
-    do {                                                                           \
-      const size_t o_ = (size_t)(c_) * KC;                                         \
-      g##X##0 = *reinterpret_cast<const float4*>(src[0] + o_);                     \
-      g##X##1 = *reinterpret_cast<const float4*>(src[1] + o_);                     \
-      g##X##2 = *reinterpret_cast<const float4*>(src[2] + o_);                     \
-      g##X##3 = *reinterpret_cast<const float4*>(src[3] + o_);                     \
-      g##X##4 = *reinterpret_cast<const float4*>(src[4] + o_);                     \
-      g##X##5 = *reinterpret_cast<const float4*>(src[5] + o_);                     \
-      g##X##6 = *reinterpret_cast<const float4*>(src[6] + o_);                     \
-      g##X##7 = *reinterpret_cast<const float4*>(src[7] + o_);                     \
-      q##X = *reinterpret_cast<const float4*>(qrow + o_);                          \
-    } while (0)
-#define SV_WG_STORE(X, buf_)                                                       \
-    do {                                                                           \
-      float* t_ = tile + ((size_t)(buf_) * ROWS + lrow0) * LDR + seg * 4;          \
-      *reinterpret_cast<float4*>(t_ + (size_t)RSTEP * 0 * LDR) = g##X##0;          \
-      *reinterpret_cast<float4*>(t_ + (size_t)RSTEP * 1 * LDR) = g##X##1;          \
-      *reinterpret_cast<float4*>(t_ + (size_t)RSTEP * 2 * LDR) = g##X##2;          \
-      *reinterpret_cast<float4*>(t_ + (size_t)RSTEP * 3 * LDR) = g##X##3;          \
-      *reinterpret_cast<float4*>(t_ + (size_t)RSTEP * 4 * LDR) = g##X##4;          \
-      *reinterpret_cast<float4*>(t_ + (size_t)RSTEP * 5 * LDR) = g##X##5;          \
-      *reinterpret_cast<float4*>(t_ + (size_t)RSTEP * 6 * LDR) = g##X##6;          \
-      *reinterpret_cast<float4*>(t_ + (size_t)RSTEP * 7 * LDR) = g##X##7;          \
-      if (tid < C4) *reinterpret_cast<float4*>(qs + (buf_) * KC + tid * 4) = q##X; \
-    } while (0)
-    // one step: multiply step c out of tile buffer c & 1, move step c + 1 (ring set XN) into the other buffer, request
-    // step c + 1 + DEPTH into the set that just became free
-#define SV_WG_MUL(c)                                                                                       \
-    if (tid < cnt) {                                                                                       \
-      const float* tr = tile + ((size_t)((c) & 1) * ROWS + tid) * LDR;                                     \
-      const float* qb = qs + ((c) & 1) * KC;                                                               \
-      _Pragma("unroll 8") for (int s4 = 0; s4 < C4; ++s4) {                                                \
-        const float4 rv = *reinterpret_cast<const float4*>(tr + s4 * 4);                                   \
-        const float4 qv = *reinterpret_cast<const float4*>(qb + s4 * 4);                                   \
-        acc = fmaf(qv.x, rv.x, acc);                                                                       \
-        acc = fmaf(qv.y, rv.y, acc);                                                                       \
-        acc = fmaf(qv.z, rv.z, acc);                                                                       \
-        acc = fmaf(qv.w, rv.w, acc);                                                                       \
-      }                                                                                                    \
-    }
-    // steady state (no conditions on the loads: the compiler's wait counts then leave the three younger steps in flight)
-#define SV_WG_STEP_FULL(c_, XN)                                                                            \
-    do {                                                                                                   \
-      const int c = (c_);                                                                                  \
-      SV_WG_MUL(c)                                                                                         \
-      SV_WG_STORE(XN, (c + 1) & 1);                                                                        \
-      SV_WG_LOAD(XN, c + 1 + DEPTH);                                                                       \
-      __syncthreads();                                                                                     \
-    } while (0)
-#define SV_WG_STEP(c_, XN)                                                                                 \
-    do {                                                                                                   \
-      const int c = (c_);                                                                                  \
-      if (c < nch) {                                                                                       \
-        if (tid < cnt) {                                                                                   \
-          const float* tr = tile + ((size_t)(c & 1) * ROWS + tid) * LDR;                                   \
-          const float* qb = qs + (c & 1) * KC;                                                             \
-          _Pragma("unroll 8") for (int s4 = 0; s4 < C4; ++s4) {                                            \
-            const float4 rv = *reinterpret_cast<const float4*>(tr + s4 * 4);                               \
-            const float4 qv = *reinterpret_cast<const float4*>(qb + s4 * 4);                               \
-            acc = fmaf(qv.x, rv.x, acc);                                                                   \
-            acc = fmaf(qv.y, rv.y, acc);                                                                   \
-            acc = fmaf(qv.z, rv.z, acc);                                                                   \
-            acc = fmaf(qv.w, rv.w, acc);                                                                   \
-          }                                                                                                \
-        }                                                                                                  \
-        if (c + 1 < nch) {                                                                                 \
-          SV_WG_STORE(XN, (c + 1) & 1);   /* waits for the loads of step c + 1 only */                     \
-          if (c + 1 + DEPTH < nch) SV_WG_LOAD(XN, c + 1 + DEPTH);                                          \
-        }                                                                                                  \
-        __syncthreads();                                                                                   \
-      }                                                                                                    \
-    } while (0)
-    float acc = 0.f;
-    // set A holds steps 0, 4, 8, ...; B 1, 5, ...; C 2, 6, ...; D 3, 7, ...
-    SV_WG_LOAD(A, 0);
-    if (1 < nch) SV_WG_LOAD(B, 1);
-    if (2 < nch) SV_WG_LOAD(C, 2);
-    if (3 < nch) SV_WG_LOAD(D, 3);
-    SV_WG_STORE(A, 0);
-    if (4 < nch) SV_WG_LOAD(A, 4);
-    __syncthreads();
-    int c0 = 0;
-    for (; c0 + 3 + 1 + DEPTH < nch; c0 += 4) {   // every load of these four steps exists
-      SV_WG_STEP_FULL(c0, B);
-      SV_WG_STEP_FULL(c0 + 1, C);
-      SV_WG_STEP_FULL(c0 + 2, D);
-      SV_WG_STEP_FULL(c0 + 3, A);
-    }
-    for (; c0 < nch; c0 += 4) {                    // the last steps: nothing (or not everything) left to request
-      SV_WG_STEP(c0, B);
-      SV_WG_STEP(c0 + 1, C);
-      SV_WG_STEP(c0 + 2, D);
-      SV_WG_STEP(c0 + 3, A);
-    }
-#undef SV_WG_STEP
-#undef SV_WG_STEP_FULL
-#undef SV_WG_MUL
-#undef SV_WG_STORE
-#undef SV_WG_LOAD
-#undef SV_WG_DECL
-    if (tid < cnt) {
-      const uint32_t id = ids[tid];
-      a[base + tid] = ((uint64_t)f2key_(sv_d2(q2, rn[id], acc)) << 32) | id;
-    }
-  }
-  bitonic64(a, np2, tid);
-  for (int j = tid; j < k; j += 256) {
-    float dd = INFINITY;
-    int64_t id = -1;
-    if (j < n) {
-      dd = key2f_((uint32_t)(a[j] >> 32));
-      id = (int64_t)(uint32_t)a[j];
-    }
-    d2_out[row * k + j] = dd;
-    idx_out[row * k + j] = id;
-  }
-}
-
-// A handful of queries (one query image per pass): fewer lists than CUs, and a list walked by ONE workgroup is one memory
-// round trip after the other (59 us for 240 rows of 1024 floats).  Here a list is dealt to `parts` workgroups, 32 rows each:
-// a workgroup requests 1024 floats of each of its 32 rows in ONE burst (thread t: 16 bytes of row 2 j + (t >> 7), in both
-// 512-float halves: 32 coalesced loads in flight per thread, one round trip per 1024 floats), parks one half at a time in an
-// LDS tile [32][516], and 32 lanes walk one row each (the same sequential fp32 chain; the query's floats are LDS
-// broadcasts).  The keys go to global memory as device-scope stores; the workgroup that takes the last ticket of its query
-// reads them back, sorts them and writes the top k.  d % 1024 == 0.  tick[] is all zero before and after.
-// Measured (50 queries x ~240 rows, 1 M x 1024 index): 59 us -> 34-38 us; what is left is a chain of ~7 dependent memory
-// round trips (list length + ids, rows, key stores, ticket, key loads, results) around 5 us of arithmetic.
-constexpr int SV_TICK_ROWS = 128, SV_TICK_POISON = SV_TICK_ROWS;   // tick[0..127]: one ticket counter per query; [128]: sticky failure word
-__global__ __launch_bounds__(256) void refine_exact_small_kernel(const float* __restrict__ Q, const float* __restrict__ R, int d,
-                                                                 const float* __restrict__ qn, const float* __restrict__ rn,
-                                                                 const uint32_t* __restrict__ ref_cnt,
-                                                                 const uint32_t* __restrict__ ref_id, int rcap, int rpad, int k,
-                                                                 float* __restrict__ d2_out, int64_t* __restrict__ idx_out, int parts,
-                                                                 uint64_t* __restrict__ gkeys, uint32_t* __restrict__ tick,
-                                                                 uint32_t* __restrict__ fail_rows, uint32_t* __restrict__ fail_count,
-                                                                 SvSmallFinish fz) {
-  constexpr int ROWS = 32, KC = 512, LDR = KC + 4;
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  float* tile = reinterpret_cast<float*>(smem);                  // [ROWS][LDR]
-  uint64_t* a = reinterpret_cast<uint64_t*>(tile + ROWS * LDR);  // [rpad]
-  __shared__ uint32_t ids[ROWS];
-  __shared__ int last;
-  const int tid = threadIdx.x;
-#ifdef SV_REFINE_TIMING
-  unsigned long long T[12];
-  int ti = 0;
-#define RTICK() T[ti++] = __builtin_amdgcn_s_memtime()
-#else
-#define RTICK()
-#endif
-  RTICK();
-  // part-major: the first workgroups of the grid are part 0 of EVERY list, then part 1, ... -- the parts that hold rows (a band of ~270
-  // rows: parts 0-8 of 16) are all resident in the first round of workgroups, the empty ones come last and leave at once.  Row-major
-  // (rounds 3-5) put all 16 parts of lists 0-31 into the 512 resident slots and made lists 32-49 wait for them (round 6: 40 -> 33 us).
-  const int nlists = (int)(gridDim.x / parts);
-  const int64_t row = blockIdx.x % nlists;
-  const int base = (int)(blockIdx.x / nlists) * ROWS;
-  // the list's length and this workgroup's slice of it are requested together (the slice lies inside the list's rcap slots
-  // whatever the length; entries beyond it are not looked at)
-  const uint32_t idv = tid < ROWS ? ref_id[row * rcap + base + tid] : 0u;
-  // fz.on (round 6, second step: the pass WITHOUT small_tail_kernel -- every kernel boundary of this chain costs 4-5 us, whatever the
-  // kernel does): the rows the select flagged are finished HERE, by the row's own `parts` workgroups -- a band that outgrew the
-  // first tier: every part evaluates its slice of the candidate list, the last one sorts; a row flagged for the redo: exact brute
-  // force, every part a slice of the index, the last one merges (small_pass_dev.h; the same chain, sv_d2, (distance, id) order).
-  // The two flags are requested with the list's length: no extra round trip on the common path.
-  const uint32_t f_fail = fz.on ? fail_rows[row] : 0u, f_rovf = fz.on ? fz.rovf_rows[row] : 0u;
-  const int n = (int)ref_cnt[row];
-  if (f_fail | f_rovf) {   // (workgroup-uniform)
-    const int p = (int)(blockIdx.x / nlists);
-    uint64_t* a2 = reinterpret_cast<uint64_t*>(smem);                 // <= 8192 words of sort scratch
-    float* qs2 = reinterpret_cast<float*>(smem + 65536);              // 1024 floats
-    uint64_t* best2 = a2 + 2048;                                      // (brute force: the sort scratch is 2048 words)
-    uint64_t* slot = fz.part2 + (size_t)row * fz.row_words;           // this row's words of the exchange buffer
-    if (f_fail) sp_brute_slice(Q, R, qn, rn, fz.n_db, d, k, fz.kp, row, p, parts, slot, a2, best2, qs2, tid);
-    else sp_tier2_slice(Q, R, qn, rn, d, row, p, parts, min(fz.cand_cnt[row], (uint32_t)fz.cap), fz.ref_lim[row], fz.cand_d2, fz.cand_id, fz.cap, slot,
-                        qs2, tid);
-    __threadfence();
-    __syncthreads();
-    if (tid == 0) last = (__hip_atomic_fetch_add(&tick[row], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (uint32_t)(parts - 1));
-    __syncthreads();
-    if (!last) return;
-    __threadfence();
-    if (f_fail) {
-      sp_brute_merge(slot, k, fz.kp, parts, a2, best2, tid);
-      for (int j = tid; j < k; j += 256) {
-        const uint64_t v = best2[j];
-        d2_out[row * k + j] = v != ~0ull ? key2f_((uint32_t)(v >> 32)) : INFINITY;
-        idx_out[row * k + j] = v != ~0ull ? (int64_t)(uint32_t)v : -1;
-      }
-    } else {
-      const int c = (int)min(fz.cand_cnt[row], (uint32_t)fz.cap);
-      int np2 = 2;
-      while (np2 < c) np2 <<= 1;
-      for (int j = tid; j < np2; j += 256)
-        a2[j] = j < c ? __hip_atomic_load(&slot[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : ~0ull;
-      bitonic64(a2, np2, tid);
-      for (int j = tid; j < k; j += 256) {
-        const uint64_t v = j < np2 ? a2[j] : ~0ull;
-        d2_out[row * k + j] = v != ~0ull ? key2f_((uint32_t)(v >> 32)) : INFINITY;
-        idx_out[row * k + j] = v != ~0ull ? (int64_t)(uint32_t)v : -1;
-      }
-    }
-    if (tid == 0) {
-      __hip_atomic_store(&tick[row], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      atomicAdd(&fz.stats[f_fail ? 0 : 1], 1u);
-      const uint32_t tot = atomicAdd(&fz.totals[f_fail ? 0 : 1], 1u) + 1u;
-      if (fz.host_totals) fz.host_totals[f_fail ? 0 : 1] = tot;   // (the pinned mirror: the latest writer's total)
-    }
-    return;
-  }
-  const int cnt = min(ROWS, n - base);
-  RTICK();   // T1: list length + ids
-  if (cnt > 0) {
-    if (tid < ROWS) ids[tid] = idv;
-    __syncthreads();
-    if (tid >= cnt && tid < ROWS) ids[tid] = ids[0];   // rows beyond the list re-read its first one
-    __syncthreads();
-    const int h = tid >> 7, off = (tid & 127) * 4;
-    // (named registers: hipcc 7.2 sends a float4 g[..] filled in an unrolled loop to scratch memory here, with a vmcnt(0)
-    //  behind every load)
-#define SV_RS_J(F) F(0) F(1) F(2) F(3) F(4) F(5) F(6) F(7) F(8) F(9) F(10) F(11) F(12) F(13) F(14) F(15)
-#define SV_RS_SRC(j) const float* src##j = R + (size_t)ids[2 * j + h] * d + off;
-#define SV_RS_LOAD(j)                                                       \
-  const float4 gA##j = *reinterpret_cast<const float4*>(src##j + c0);        \
-  const float4 gB##j = *reinterpret_cast<const float4*>(src##j + c0 + KC);
-#define SV_RS_STORE_A(j) *reinterpret_cast<float4*>(tile + (2 * j + h) * LDR + off) = gA##j;
-#define SV_RS_STORE_B(j) *reinterpret_cast<float4*>(tile + (2 * j + h) * LDR + off) = gB##j;
-#define SV_RS_WALK(c_)                                                      \
-  if (tid < cnt) {                                                          \
-    const float* tr = tile + tid * LDR;                                     \
-    const float* qb = qs + (c_);                                            \
-    _Pragma("unroll 16") for (int s4 = 0; s4 < KC / 4; ++s4) {              \
-      const float4 rv = *reinterpret_cast<const float4*>(tr + s4 * 4);      \
-      const float4 qv = *reinterpret_cast<const float4*>(qb + s4 * 4);      \
-      acc = fmaf(qv.x, rv.x, acc);                                          \
-      acc = fmaf(qv.y, rv.y, acc);                                          \
-      acc = fmaf(qv.z, rv.z, acc);                                          \
-      acc = fmaf(qv.w, rv.w, acc);                                          \
-    }                                                                       \
-  }
-    SV_RS_J(SV_RS_SRC)
-    // (the query's 1024 floats of the step sit in LDS beside the tile, read as broadcasts: through the scalar cache every
-    //  batch of 64 floats was a cold ~0.7 us miss in front of its fmas)
-    float* qs = reinterpret_cast<float*>(a + rpad);   // [2 KC]
-    const float* qsrc = Q + row * d + tid * 4;
-    float acc = 0.f;
-    for (int c0 = 0; c0 < d; c0 += 2 * KC) {
-      SV_RS_J(SV_RS_LOAD)
-      const float4 qv4 = *reinterpret_cast<const float4*>(qsrc + c0);
-      if (c0) __syncthreads();   // the walkers are done with the previous half
-      SV_RS_J(SV_RS_STORE_A)
-      *reinterpret_cast<float4*>(qs + tid * 4) = qv4;
-      __syncthreads();
-      SV_RS_WALK(0)
-      __syncthreads();
-      SV_RS_J(SV_RS_STORE_B)
-      __syncthreads();
-      SV_RS_WALK(KC)
-    }
-#undef SV_RS_WALK
-#undef SV_RS_STORE_B
-#undef SV_RS_STORE_A
-#undef SV_RS_LOAD
-#undef SV_RS_SRC
-#undef SV_RS_J
-    RTICK();   // T2: rows loaded and walked
-    if (tid < cnt) {
-      const uint32_t id = ids[tid];
-      __hip_atomic_store(&gkeys[row * rcap + base + tid], ((uint64_t)f2key_(sv_d2(qn[row], rn[id], acc)) << 32) | id, __ATOMIC_RELAXED,
-                         __HIP_MEMORY_SCOPE_AGENT);
-    }
-  }
-  // The keys are device-scope (write-through) stores and device-scope loads; each wave waits for its stores to be
-  // acknowledged before the barrier that precedes the ticket.  (A __threadfence() on either side is an L2 write-back +
-  // invalidate on this eight-L2 part.)
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (tid == 0) last = (__hip_atomic_fetch_add(&tick[row], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (uint32_t)(parts - 1));
-  __syncthreads();
-  RTICK();   // T3: key stores acknowledged + ticket
-  if (!last) return;
-  int np2 = 2;
-  while (np2 < n) np2 <<= 1;
-  // Ordering.  Every access to gkeys / tick is an agent-scope atomic (sc1: performed at the memory side, never served from
-  // an XCD's own L2), the writers wait for their key stores to be ACKNOWLEDGED (vmcnt(0)) before the barrier in front of the
-  // ticket, and the reader issues its loads after its ticket returned: on this hardware that is a release / acquire chain
-  // through the ticket.  The C++ model does not promise it for relaxed atomics, and a formal acq_rel ticket costs an L2
-  // write-back + invalidate per workgroup (see above) -- so the protocol is CHECKED instead of trusted: gkeys holds all ones
-  // wherever no key of this launch has landed (the launcher fills a new buffer so, the reader puts the fill back behind
-  // every key it takes; a key is never all ones: finite distance, 32-bit id); a slot still all ones is re-read a bounded
-  // number of times, and a slot that never fills FLAGS its query (fail_rows: the caller redoes flagged rows on another
-  // path, exactly) and raises the sticky word tick[SV_TICK_POISON], on which the host re-initialises both buffers before
-  // their next use (a key landing after the reader gave up would otherwise pass for a key of the next launch).
-  int holes = 0;
-  for (int j = tid; j < np2; j += 256) {
-    uint64_t v = ~0ull;
-    if (j < n) {
-      for (int spin = 0; spin < 4096; ++spin) {
-        v = __hip_atomic_load(&gkeys[row * rcap + j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (v != ~0ull) break;
-      }
-      if (v == ~0ull) ++holes;
-      __hip_atomic_store(&gkeys[row * rcap + j], ~0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    a[j] = v;
-  }
-  if (tid == 0) __hip_atomic_store(&tick[row], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  if (fz.on && (fz.debug & 8) && row == 1) holes = 1;   // (tests: the path below has never been taken by the hardware)
-  if (__syncthreads_or(holes)) {   // (never observed)
-    if (tid == 0) __hip_atomic_store(&tick[SV_TICK_POISON], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (!fz.on) {   // the row's output is left to the redo (the caller's read-back, or small_tail_kernel)
-      if (tid == 0 && fail_rows && atomicExch(&fail_rows[row], 1u) == 0u) atomicAdd(fail_count, 1u);
-      return;
-    }
-    // fused finish: nobody comes after this kernel -- this workgroup re-evaluates the row's whole band itself (<= rcap rows, a thread
-    // per row: the same chain); the sticky word makes the NEXT pass's head refill the hand-over buffers (a key that lands late must
-    // not pass for a key of that pass)
-    float* qs2 = reinterpret_cast<float*>(smem);   // (the row tile is free: every part has drawn its ticket)
-    for (int j0 = 0; j0 < n; j0 += 256) {
-      const int j = j0 + tid;
-      const uint32_t id = ref_id[row * rcap + min(j, n - 1)];
-      float acc2[1] = {0.f};
-      for (int c0 = 0; c0 < d; c0 += ST_KC) {
-        const int kc = min(ST_KC, d - c0);
-        __syncthreads();
-        for (int t = tid; t < kc; t += 256) qs2[t] = Q[row * d + c0 + t];
-        __syncthreads();
-        chain_step<1>(R + (size_t)id * d + c0, kc, qs2, acc2);
-      }
-      if (j < n) a[j] = ((uint64_t)f2key_(sv_d2(qn[row], rn[id], acc2[0])) << 32) | id;
-    }
-    __syncthreads();
-    if (tid == 0) atomicAdd(&fz.stats[2], 1u);
-  }
-  RTICK();   // T4: keys read back
-  // (distance, id) order WITHOUT a sort: the keys are distinct (the id is part of them), so a key's place in the sorted list is the
-  // number of smaller keys -- every thread counts that for its own one or two keys against the n keys in LDS (broadcast reads, no
-  // barrier) and writes its result straight to that place.  The bitonic sort of 512 words was 45 barrier-separated stages: 9.6 us of
-  // the last workgroup's 25 (round 6); the count is ~2.
-  for (int j = tid; j < n; j += 256) {
-    const uint64_t v = a[j];
-    int place = 0;
-#pragma unroll 8
-    for (int t = 0; t < n; ++t) place += (a[t] < v) ? 1 : 0;
-    if (place < k) {
-      d2_out[row * k + place] = key2f_((uint32_t)(v >> 32));
-      idx_out[row * k + place] = (int64_t)(uint32_t)v;
-    }
-  }
-  for (int j = n + tid; j < k; j += 256) {   // a list shorter than k pads with (inf, -1)
-    d2_out[row * k + j] = INFINITY;
-    idx_out[row * k + j] = -1;
-  }
-  RTICK();   // T5: placed
-#ifdef SV_REFINE_TIMING
-  if (tid == 0 && row == 0 && cnt > 0)
-    printf("refine row0 last wg: ids %llu rows+walk %llu store+ticket %llu readback %llu sort %llu cycles (n=%d)\n", T[1]-T[0], T[2]-T[1], T[3]-T[2], T[4]-T[3], T[5]-T[4], n);
-#endif
-#undef RTICK
-}
-
-int sv_refine_small_repair(segvlad_ctx* ctx) {
-  // the hand-over buffers of refine_exact_small_kernel back to their initial state (all ones / all zero)
-  if (ctx->s_ref_tick.p) SV_HIP(hipMemsetAsync(ctx->s_ref_tick.p, 0, ctx->s_ref_tick.cap, ctx->stream));
-  if (ctx->s_ref_keys.p) SV_HIP(hipMemsetAsync(ctx->s_ref_keys.p, 0xff, ctx->s_ref_keys.cap, ctx->stream));
-  return SEGVLAD_OK;
-}
-
-int sv_launch_refine_exact(segvlad_ctx* ctx, const float* Q, const float* R, int nq, int d, const float* qn, const float* rn,
-                           const uint32_t* ref_cnt, const uint32_t* ref_id, int rcap, int k, float* d2_out, int64_t* idx_out,
-                           const uint32_t* only_rows, uint32_t* fail_rows, uint32_t* fail_count, const uint32_t** poison_dev,
-                           const SvSmallFinish* fz, bool* fused_done) {
-  if (poison_dev) *poison_dev = nullptr;
-  if (fused_done) *fused_done = false;
-  if (nq <= 0) return SEGVLAD_OK;
-  int rpad = 2;
-  while (rpad < rcap) rpad <<= 1;
-  size_t lds = (size_t)d * 4 + (size_t)rpad * 8;
-  if (nq <= SV_TICK_ROWS && d % 1024 == 0 && rcap <= 1024 && rcap % 32 == 0 && !only_rows) {   // one query image: lists shared by workgroups
-    const int parts = rcap / 32;
-    const size_t tick_cap = ctx->s_ref_tick.cap;
-    SV_HIP(ctx->s_ref_tick.reserve((size_t)(SV_TICK_ROWS + 1) * 4));
-    if (ctx->s_ref_tick.cap != tick_cap) SV_HIP(hipMemsetAsync(ctx->s_ref_tick.p, 0, ctx->s_ref_tick.cap, ctx->stream));
-    const size_t keys_cap = ctx->s_ref_keys.cap;
-    SV_HIP(ctx->s_ref_keys.reserve((size_t)nq * rcap * 8));
-    if (ctx->s_ref_keys.cap != keys_cap) SV_HIP(hipMemsetAsync(ctx->s_ref_keys.p, 0xff, ctx->s_ref_keys.cap, ctx->stream));
-    lds = (size_t)(32 * 516 + 1024) * 4 + (size_t)rpad * 8;
-    if (lds > 64 * 1024) SV_HIP(sv_max_dyn_lds(reinterpret_cast<const void*>(refine_exact_small_kernel), lds));
-    SvSmallFinish f;   // (off)
-    if (fz && fz->on && fail_rows && fused_done && k <= 1024) {
-      // the flagged rows' exchange words: a row's `parts` lists of kp keys (brute force) or its `cap` candidate keys (second tier)
-      f = *fz;
-      f.kp = 256;
-      while (f.kp < k) f.kp <<= 1;
-      f.row_words = std::max<int64_t>((int64_t)parts * f.kp, f.cap);
-      SV_HIP(ctx->s_tail_part.reserve((size_t)nq * f.row_words * 8));
-      SV_TRY(sv_small_words(ctx));
-      SV_TRY(sv_ensure_pinned_words(ctx));
-      f.part2 = ctx->s_tail_part.as<uint64_t>();
-      f.totals = ctx->s_tail_tick.as<uint32_t>() + 129;
-      f.host_totals = ctx->h_pin + 8;
-      f.debug = ctx->opt.debug_small_tail;
-      *fused_done = true;
-    }
-    hipLaunchKernelGGL(refine_exact_small_kernel, dim3(nq * parts), dim3(256), lds, ctx->stream, Q, R, d, qn, rn, ref_cnt, ref_id, rcap,
-                       rpad, k, d2_out, idx_out, parts, ctx->s_ref_keys.as<uint64_t>(), ctx->s_ref_tick.as<uint32_t>(), fail_rows, fail_count, f);
-    SV_HIP(hipGetLastError());
-    if (poison_dev) *poison_dev = ctx->s_ref_tick.as<uint32_t>() + SV_TICK_POISON;
-    return SEGVLAD_OK;
-  }
-#define SV_REFINE_ARGS dim3(nq), dim3(256), lds, ctx->stream, Q, R, d, qn, rn, ref_cnt, ref_id, rcap, rpad, k, d2_out, idx_out, only_rows
-  if (lds <= 160 * 1024) {
-    if (lds > 64 * 1024) SV_HIP(sv_max_dyn_lds(reinterpret_cast<const void*>(refine_exact_kernel<true>), lds));
-    hipLaunchKernelGGL(refine_exact_kernel<true>, SV_REFINE_ARGS);
-  } else if (d % 128 == 0) {
-    // [2][64 rows][132] floats + [2][128] query floats + [64] ids + the sort keys (<= 64 KiB for a second-tier list)
-    lds = (size_t)(2 * 64 * 132 + 2 * 128 + 64) * 4 + (size_t)rpad * 8;
-    if (lds > 160 * 1024) return ctx->fail(SEGVLAD_ERR_LIMIT, "refine: a %d-entry list of %d-d rows exceeds the LDS", rcap, d);
-    auto kern = refine_exact_wide_kernel<128, 4>;
-    if (lds > 64 * 1024) SV_HIP(sv_max_dyn_lds(reinterpret_cast<const void*>(kern), lds));
-    hipLaunchKernelGGL(kern, SV_REFINE_ARGS);
-  } else {
-    lds = (size_t)rpad * 8;
-    if (lds > 64 * 1024) SV_HIP(sv_max_dyn_lds(reinterpret_cast<const void*>(refine_exact_kernel<false>), lds));
-    hipLaunchKernelGGL(refine_exact_kernel<false>, SV_REFINE_ARGS);
-  }
-#undef SV_REFINE_ARGS
-  SV_HIP(hipGetLastError());
-  return SEGVLAD_OK;
+  return f16_with_config(c.kernel, launch);
 }
 
 // ---- max of the database row norms (margin scale) -------------------------------------------------------------

@@ -433,7 +433,7 @@ static SearchPlan plan_search(const segvlad_ctx* ctx, int nq, int k, const void*
       s.device_tail = small && o.small_tail && o.debug_search == 0 && n <= 0xffffffffLL;
     } else {
       // batches on the default configuration take the biased-accumulator kernel when the norms allow it: min ||q||^2
-      p.q2min = nq > 128 && (o.f16_cfg < 0 || o.f16_cfg == 250 || o.f16_cfg == 300);
+      p.q2min = sv_f16_bias_possible(o, nq);
       // level 0 of the first chunk goes out BEFORE the host waits for the scale: it needs neither the query plane nor the margin,
       // and the device runs it during the round trip -- not when level 0 runs on the fp16 product (batch_l0_f16: that needs the
       // plane; it is ten times cheaper than the exact GEMM it replaces, which is worth more than hiding that GEMM)
@@ -1219,7 +1219,7 @@ static int range_search_dev(segvlad_ctx* ctx, const float* q, int nq, const floa
     // that runs -- the forms that only prepare, whatever the number of rows
     p.filter = Filter::F16;
     p.prep = Prep::BatchF16;
-    p.q2min = nq > 128 && (o.f16_cfg < 0 || o.f16_cfg == 250 || o.f16_cfg == 300);
+    p.q2min = sv_f16_bias_possible(o, nq);
     p.mrows = std::min(nq, SV_CHUNK);
     FlagBlock fb{&ctx->s_rs_fb, nq, p.mrows, false};
     SV_TRY(prepare_index_planes(ctx, Filter::F16));

@@ -4,23 +4,23 @@
  * (tests/test_gpu_filter_variants.py holds each variant to the bits of the all-fp32 filter), the VLAD / PCA switches select
  * kernels that agree to ~1e-6 relative (tests/test_gpu_parity.py).
  *
- * Builds.  The SHIPPED library (revisit-anything_amd/build.py; lib/libsegvlad_hip.so) instantiates only the kernels the switches
- * default to; a value that selects another one is rejected with SEGVLAD_ERR_ARG.  The DEVELOPMENT build
+ * Builds.  The SHIPPED library (revisit-anything_amd/build.py; lib/libsegvlad_hip.so) and the DEVELOPMENT build
  * (`python revisit-anything_amd/build.py --ablations`, -DSEGVLAD_ABLATIONS -> lib/libsegvlad_hip_abl.so, loaded with
- * SEGVLAD_LIB_PATH) holds every measured-and-not-kept variant (DESIGN.md 4 / 7.1 has the measurements), the timing ablations
- * with WRONG results (f16_cfg 10 .. 160, SEGVLAD_ASSIGN_ABL, SEGVLAD_AGG_ABL) and the phase timers.
+ * SEGVLAD_LIB_PATH) hold the same kernels; the development build adds three probes of the batch filter kernel (f16_cfg 93:
+ * phase timing; 94 / 95: timing ablations with WRONG results), the timing ablations of the VLAD kernels (SEGVLAD_ASSIGN_ABL,
+ * SEGVLAD_AGG_ABL, WRONG results) and their phase timers.  A value that names no kernel of the build is rejected with
+ * SEGVLAD_ERR_ARG.  (The fp16 filter's measured-and-not-kept variants -- "f16_mf", "f16_epi", "f16_pp", "f16_dsplit",
+ * "f16_small_mf", f16_deep_cfg 0 - 3, f16_buf 1, the other f16_cfg values -- left the tree; DESIGN.md 4 / 7 has their
+ * measurements and names the commit that last held them.)
  *
- *   fp16 candidate filter of the exact kNN (knn_filter_kernels.hip)                                shipped library accepts
- *     "f16_cfg"       tile configuration; -1 = from the shape: 250 batches, 300 deep rows (d >= 4096), 62 / 63 one query
+ *   fp16 candidate filter of the exact kNN (knn_filter_kernels.hip: sv_choose_f16_kernel)           accepted values
+ *     "f16_cfg"       kernel family; -1 = from the shape: 250 batches, 300 deep rows (d >= 4096), 62 / 63 one query
  *                     image per pass                                                             -1, 250, 300, 62, 63
- *     "f16_mf"        MFMA shape of the batch kernels: 0 = 32 x 32 x 16, else 16 x 16 x 32       -1, 1
- *     "f16_epi"       epilogue: 0 = workgroup-level reservation, 1 = wave-private                -1, 1
- *     "f16_pp"        main loop of the batch kernel: 0 = plain, else ping-pong                   -1, 2
- *     "f16_deep_cfg"  deep-row geometry: -1 / 4 = 256 x 128 tiles, 8 waves, 16 x 16 x 32; 0 = rounds 2-3's kernel;
- *                     1, 2, 3 = measured variants                                                -1, 4
- *     "f16_buf"       operand DMA as buffer_load ... lds: -1 = the deep-row kernel only, 1 = both, 0 = neither   -1, 0
- *     "f16_dsplit"    placement of a phase's DMA / fragment reads (1, 2, -1, -2: measured variants)   0
- *     "f16_small_mf"  1 = the small (non-persistent) levels on the 16 x 16 x 32 shape            0
+ *                     development build: 93 = phase timing of the batch kernel, 94 = no epilogue, 95 = no epilogue and
+ *                     no DMA in the k-loop                                                       + 93, 94, 95
+ *     "f16_deep_cfg"  deep rows: -1 / 5 = the persistent batch kernel with flushed blocks where the launch fills it, 4
+ *                     elsewhere; 4 = 256 x 128 tiles, 8 waves, 16 x 16 x 32, a second accumulator set   -1, 4, 5
+ *     "f16_buf"       operand DMA of the register-blocked deep-row kernel as buffer_load ... lds: -1 = yes, 0 = no   -1, 0
  *     "f16_walk"      tile walk of the persistent kernel: bit 0 = an XCD keeps its block of query tiles, bit 1 = odd steps run
  *                     their k-tiles backwards, bit 2 = rotated k start per workgroup (-1 = 3)    any (a launch parameter)
  *     "f16_gm"        tile-block height of the XCD-aware order                                    any (a launch parameter)

@@ -1,4 +1,4 @@
-// Device helpers of the single-image pass's exact finish (small_pass_kernels.hip: small_tail_kernel; knn_filter_kernels.hip:
+// Device helpers of the single-image pass's exact finish (small_pass_kernels.hip: small_tail_kernel; knn_candidate_kernels.hip:
 // refine_exact_small_kernel's fused finish) -- round 6.  Everything here evaluates a distance as the sequential chain
 // acc = fma(q[j], r[j], acc), j = 0 .. d-1, then sv_d2 with the same norms, and orders by (distance, id): the bits of every exact path.
 #pragma once

@@ -1,7 +1,7 @@
 """A/B of fp16 filter variants inside ONE process (box-to-box and run-to-run spreads are +-3 %: decisions between variants
 2 % apart need interleaved measurements).  Every variant's result is asserted bit-identical to the first one's.
-   python tools/probe_cfg_ab.py 250 50                      (f16_cfg values)
-   python tools/probe_cfg_ab.py f16_walk=0,f16_epi=0 f16_walk=3,f16_epi=1 ...   (option sets; unnamed options keep their defaults)
+   python tools/probe_cfg_ab.py 250 300                     (f16_cfg values)
+   python tools/probe_cfg_ab.py f16_walk=0,f16_gm=4 f16_walk=3,f16_deep_cfg=4 ...   (option sets; unnamed options keep their defaults)
 Environment: NR / NQ / D / K (default 1 000 000 / 10 000 / 1024 / 200), ROUNDS (7), DATA=planted|random."""
 import os
 import sys
@@ -11,7 +11,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from revisit_anything_amd.engine import SegVLADEngine  # noqa: E402
 
-DEFAULTS = {"f16_cfg": -1, "f16_gm": -1, "f16_walk": -1, "f16_epi": -1, "f16_mf": -1, "f16_deep_cfg": -1, "f16_pp": -1, "f16_small_mf": 0, "f16_buf": -1, "f16_dsplit": 0}
+DEFAULTS = {"f16_cfg": -1, "f16_gm": -1, "f16_walk": -1, "f16_deep_cfg": -1, "f16_buf": -1}
 
 
 def parse(spec):
@@ -20,7 +20,7 @@ def parse(spec):
     return {kv.split("=")[0]: int(kv.split("=")[1]) for kv in spec.split(",")}
 
 
-specs = sys.argv[1:] or ["250", "50"]
+specs = sys.argv[1:] or ["f16_walk=3", "f16_walk=0"]
 variants = [parse(s) for s in specs]
 dev = torch.device("cuda:0")
 eng = SegVLADEngine(0)

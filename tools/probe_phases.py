@@ -1,5 +1,5 @@
 """Phase timing of the default batch filter kernel (development build with the ablations: SEGVLAD_LIB_PATH must point at
-lib/libsegvlad_hip_abl.so -- `python revisit-anything_amd/build.py --ablations`).  f16_cfg 91 / 92 = epilogue 0 / 1."""
+lib/libsegvlad_hip_abl.so -- `python revisit-anything_amd/build.py --ablations`): f16_cfg 93, one line per filter launch on stderr."""
 import os
 import sys
 
@@ -20,8 +20,7 @@ Q = torch.nn.functional.normalize(R[torch.arange(nq, device=dev) * 97] + 0.03 * 
 eng.search(Q, k)
 for walk in (0, 3):
     eng.set_option("f16_walk", walk)
-    for cfg in (91, 92, 93):
-        eng.set_option("f16_cfg", cfg)
-        print(f"--- f16_cfg {cfg} walk {walk}", file=sys.stderr, flush=True)
-        eng.search(Q, k)
-        torch.cuda.synchronize()
+    eng.set_option("f16_cfg", 93)
+    print(f"--- f16_cfg 93 walk {walk}", file=sys.stderr, flush=True)
+    eng.search(Q, k)
+    torch.cuda.synchronize()

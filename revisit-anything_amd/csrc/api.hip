@@ -219,7 +219,8 @@ int segvlad_create(segvlad_ctx** out, int device_id) {
                                             {"SEGVLAD_X3_GM", "x3_gm"},             {"SEGVLAD_SEARCH_STATS", "search_stats"},
                                             {"SEGVLAD_ASSIGN_NARROW", "assign_narrow"}, {"SEGVLAD_DEBUG_SEARCH", "debug_search"},
                                             {"SEGVLAD_AGG_KPB", "agg_kpb"},
-                                            {"SEGVLAD_KNN_HEURISTIC", "knn_heuristic"}, {"SEGVLAD_PCA_PATH", "pca_path"}};
+                                            {"SEGVLAD_KNN_HEURISTIC", "knn_heuristic"}, {"SEGVLAD_PCA_PATH", "pca_path"},
+                                            {"SEGVLAD_COVER_ROWS", "cover_rows"}};
   for (auto& kv : env_keys)
     if (const char* v = getenv(kv[0])) (void)segvlad_set_option(c, kv[1], v);
 #define SV_TAG_P(n) c->n.tag = #n; c->n.fixed = true;
@@ -308,6 +309,7 @@ int segvlad_set_option(segvlad_ctx* ctx, const char* key, const char* value) {
   if (!strcmp(key, "agg_kpb")) return as_int(&o.agg_kpb);
   if (!strcmp(key, "pj_nw")) return as_int(&o.pj_nw);
   if (!strcmp(key, "pj_f16")) return as_int(&o.pj_f16);
+  if (!strcmp(key, "cover_rows")) return as_int(&o.cover_rows);
   if (!strcmp(key, "small_plan")) return as_int(&o.small_plan);
   if (!strcmp(key, "small_tail")) return as_int(&o.small_tail);
   if (!strcmp(key, "small_head")) return as_int(&o.small_head);
@@ -624,6 +626,8 @@ static int images_impl(segvlad_ctx* ctx, const float* tokens, int B, int N, cons
     SV_HIP(ctx->s_pz.reserve((size_t)rows_pad * ctx->P * sizeof(float)));
     SV_HIP(ctx->s_rowbase.reserve((size_t)B * K * sizeof(int32_t)));
     SV_HIP(ctx->s_tilegrp.reserve((size_t)(rows_pad >> 8) * sizeof(int32_t)));
+    SV_HIP(ctx->s_phys.reserve((size_t)B * N * sizeof(int32_t)));
+    SV_HIP(ctx->s_covcnt.reserve((size_t)B * K * sizeof(int32_t)));
     SV_HIP(ctx->s_bn.reserve((size_t)S_tot * K * sizeof(float)));
     SV_TRY(sv_out(ctx, pca_y, (size_t)S_tot * ctx->P * sizeof(float), &d_y));
     if (!ctx->pca_cproj_valid) {
@@ -683,18 +687,20 @@ static int images_impl(segvlad_ctx* ctx, const float* tokens, int B, int N, cons
       StageScope sc(ctx, "prep");
       SV_TRY(sv_launch_prep(ctx, (const uint8_t*)d_lab, (const uint64_t*)d_inc, ctx->s_segoff.as<int32_t>(),
                             ctx->s_adjoff.as<int64_t>(), (const uint8_t*)d_adj, B, N, K, S_max, SC,
-                            ctx->s_colmask.as<uint64_t>(), ctx->s_gscale.as<float>()));
+                            ctx->s_colmask.as<uint64_t>(), ctx->s_gscale.as<float>(), project ? ctx->s_phys.as<int32_t>() : nullptr,
+                            project ? ctx->s_covcnt.as<int32_t>() : nullptr, ctx->opt.cover_rows != 0 ? 1 : 0));
       sc.count();
     }
     if (project) {
       float* bn = d_bn ? (float*)d_bn : ctx->s_bn.as<float>();
       {
         StageScope sc(ctx, "aggregate");   // block norms + the normalised tokens' fp16 planes, grouped by cluster
-        SV_TRY(sv_launch_group_plan(ctx, ctx->s_laboff.as<int32_t>(), B, K, ctx->s_rowbase.as<int32_t>(),
+        SV_TRY(sv_launch_group_plan(ctx, ctx->s_covcnt.as<int32_t>(), B, K, ctx->s_rowbase.as<int32_t>(),
                                     ctx->s_tilegrp.as<int32_t>(), (int)(rows_pad >> 8)));
         SV_TRY(sv_launch_token_norms(ctx, ctx->s_xt.as<float>(), ctx->s_colmask.as<uint64_t>(), ctx->vocab.as<float>(), K, D,
                                      ctx->s_segoff.as<int32_t>(), B, N, SC, bn, xscale, ctx->s_xh1.as<uint16_t>(),
-                                     ctx->s_xh2.as<uint16_t>(), ctx->s_rowbase.as<int32_t>(), ctx->opt.debug_search == 7 ? -rows_pad : rows_pad));
+                                     ctx->s_xh2.as<uint16_t>(), ctx->s_rowbase.as<int32_t>(), ctx->opt.debug_search == 7 ? -rows_pad : rows_pad,
+                                     ctx->s_phys.as<int32_t>()));
         sc.count(2);
       }
       StageScope sc(ctx, "pca");
@@ -718,7 +724,7 @@ static int images_impl(segvlad_ctx* ctx, const float* tokens, int B, int N, cons
       }
       SV_TRY(sv_launch_project_aggregate(ctx, ctx->s_pz.as<float>(), ctx->pca_cproj.as<float>(), bn, ctx->s_gscale.as<float>(),
                                          ctx->s_colmask.as<uint64_t>(), ctx->s_laboff.as<int32_t>(), ctx->s_rowbase.as<int32_t>(),
-                                         ctx->s_segoff.as<int32_t>(), B, N, K, ctx->P, SC, S_max, ctx->pca_scale.as<float>(),
+                                         ctx->s_phys.as<int32_t>(), ctx->s_segoff.as<int32_t>(), B, N, K, ctx->P, SC, S_max, ctx->pca_scale.as<float>(),
                                          (float*)d_y, zscale));
       sc.count(2);
       if (l2norm) {
@@ -1021,7 +1027,7 @@ int segvlad_cluster_aggregate(segvlad_ctx* ctx, int num_c, const float* res, con
   hipLaunchKernelGGL(fill_ones_kernel, dim3((N + 255) / 256), dim3(256), 0, ctx->stream, ctx->s_rnorm.as<float>(), N);
   SV_TRY(sv_launch_prep(ctx, (const uint8_t*)d_lab, (const uint64_t*)d_inc, ctx->s_segoff.as<int32_t>(),
                         ctx->s_adjoff.as<int64_t>(), (const uint8_t*)d_adj, 1, N, num_c, S, SC, ctx->s_colmask.as<uint64_t>(),
-                        ctx->s_gscale.as<float>()));
+                        ctx->s_gscale.as<float>(), nullptr, nullptr, 0));
   SV_TRY(sv_launch_aggregate(ctx, (const float*)d_res, ctx->s_rnorm.as<float>(), (const uint8_t*)d_lab,
                              ctx->s_colmask.as<uint64_t>(), nullptr, num_c, D, ctx->s_segoff.as<int32_t>(),
                              ctx->s_gscale.as<float>(), 1, N, SC, (float*)d_out, nullptr));

@@ -178,6 +178,8 @@ struct SvOptions {
   int query_group = 0;    // hint: the query rows of a batch come in runs of this many rows per query image (1 .. 64; else unknown):
                           // the grouped refinement then takes an image's rows as one group instead of 32-row blocks
   int pca_path = 0;       // fused images_pca: 0 auto, 1 "planes" (descriptor planes x W), 2 "project" (project tokens, then aggregate)
+  int cover_rows = 1;     // project form: only the tokens some segment covers get a row of the grouped planes and of Z (prep_kernel's
+                          // `phys` map; same bits: every kernel keeps its logical positions); 0 = every token gets a row
 };
 
 // fp16 filter of the exact kNN: length of the accumulation blocks (0 = one running fp32 accumulator over the whole row).
@@ -334,7 +336,7 @@ struct segvlad_ctx {
   X(s_misc) X(s_minmax) X(s_voteoff) X(s_cand_cnt) X(s_cand_d2) X(s_cand_id) X(s_thr_d2) X(s_thr_idx) X(s_flag) X(s_qh) X(s_ql)  \
   X(s_ref_cnt) X(s_ref_id) X(s_qscale) X(s_qf16) X(s_xh1) X(s_xh2) X(s_desc) X(s_tokorder) X(s_laboff) X(s_rnsorted) X(s_ovf)     \
   X(s_fb_q) X(s_fb_d2) X(s_fb_idx) X(s_fb_rows) X(s_rd_rows) X(s_rd_q) X(s_rd_d2) X(s_rd_idx) X(s_rd_flags) X(s_rd_p1) X(s_rd_p2)  \
-  X(s_sel_todo) X(s_vote_keys) X(s_pz) X(s_rowbase) X(s_tilegrp) X(s_bn) X(s_l0part) X(s_ref_lim) X(s_sh_d2) X(s_sh_idx)          \
+  X(s_sel_todo) X(s_vote_keys) X(s_pz) X(s_rowbase) X(s_tilegrp) X(s_phys) X(s_covcnt) X(s_bn) X(s_l0part) X(s_ref_lim) X(s_sh_d2) X(s_sh_idx)          \
   X(s_sh_rec) X(s_sh_all) X(s_sh_d2c) X(s_sh_idc) X(s_grp_cnt) X(s_grp_ids) X(s_grp_rows) X(s_grp_keys) X(s_grp_work) X(s_grp_pos) X(s_tnk_redo) X(s_tail_part) X(s_km_part) X(s_km_cnt) X(s_kflush) \
   X(s_sl_misc) X(s_sl_q) X(s_sl_cur) X(s_sl_uids) X(s_sl_uoff) X(s_sl_unum) X(s_sl_cand) X(s_sl_lens)                            \
   X(s_ex_d2) X(s_ex_idx) X(s_ex_flag) X(s_ex_qn) X(s_ex_td2) X(s_ex_tidx)                                                          \
@@ -417,7 +419,8 @@ int sv_launch_assign(segvlad_ctx* ctx, const float* tokens, int B, int N, float*
                      float* gap);
 int sv_launch_prep(segvlad_ctx* ctx, const uint8_t* labels, const uint64_t* inc_bits, const int32_t* seg_off_dev,
                    const int64_t* adj_off_dev, const uint8_t* adj, int B, int N, int K, int S_max, int SC,
-                   uint64_t* colmask, float* gscale);
+                   uint64_t* colmask, float* gscale, int32_t* phys /* [B][N], or null */, int32_t* cov_cnt /* [B][K] */,
+                   int cover /* 0: every token counts as covered */);
 // centres == nullptr: the inputs are residuals already (x * rnorm - 0)
 int sv_launch_aggregate(segvlad_ctx* ctx, const float* xt, const float* rnorm, const uint8_t* labels,
                         const uint64_t* colmask, const float* centres, int K, int D, const int32_t* seg_off_dev,
@@ -427,7 +430,8 @@ int sv_launch_aggregate(segvlad_ctx* ctx, const float* xt, const float* rnorm, c
 // block norms + the fp16 planes of the token residuals x^ - C_k, grouped by cluster (rowbase from sv_launch_group_plan); after sv_launch_prep
 int sv_launch_token_norms(segvlad_ctx* ctx, const float* xt, const uint64_t* colmask, const float* centres, int K, int D,
                           const int32_t* seg_off_dev, int B, int N, int SC, float* block_norms, float xscale, uint16_t* h1,
-                          uint16_t* h2, const int32_t* rowbase, int64_t dummy_row /* a plane row nobody reads */);
+                          uint16_t* h2, const int32_t* rowbase, int64_t dummy_row /* first row of a 256-row tile nobody reads */,
+                          const int32_t* phys /* sv_launch_prep */);
 
 // kmeans_kernels.hip: per-cluster sums of the normalised tokens + label counts of a batch, ACCUMULATED into sums / counts
 int sv_launch_centroid_sums(segvlad_ctx* ctx, const float* xt, const float* rnorm, const uint8_t* labels, int B, int N, int D, int K,
@@ -543,11 +547,12 @@ int sv_launch_gemm_f16x3(segvlad_ctx* ctx, const uint16_t* A1, const uint16_t* A
 int sv_launch_gemm_f16x3_grouped(segvlad_ctx* ctx, const uint16_t* A1, const uint16_t* A2, const uint16_t* B1, const uint16_t* B2,
                                  int M_pad, int N, int Kd, int n_groups, const int32_t* tile_group, float out_scale, float* C);
 // project_kernels.hip ("project then aggregate" form of segvlad_images_pca)
-int sv_launch_group_plan(segvlad_ctx* ctx, const int32_t* lab_off, int B, int K, int32_t* rowbase, int32_t* tile_group, int max_tiles);
+int sv_launch_group_plan(segvlad_ctx* ctx, const int32_t* cov_cnt, int B, int K, int32_t* rowbase, int32_t* tile_group, int max_tiles);
 int sv_launch_project_consts(segvlad_ctx* ctx, const float* comps, const float* mean, int P, int64_t KD, float* wmu /*[P] = W mean*/);
 int sv_launch_project_aggregate(segvlad_ctx* ctx, const float* Z, const float* wmu, const float* block_norms, const float* gscale,
-                                const uint64_t* colmask, const int32_t* lab_off, const int32_t* rowbase, const int32_t* seg_off_dev,
-                                int B, int N, int K, int P, int SC, int S_max, const float* col_scale, float* Y, float zscale);
+                                const uint64_t* colmask, const int32_t* lab_off, const int32_t* rowbase, const int32_t* phys,
+                                const int32_t* seg_off_dev, int B, int N, int K, int P, int SC, int S_max, const float* col_scale,
+                                float* Y, float zscale);
 int sv_launch_to_f16(segvlad_ctx* ctx, const float* X, int64_t n_elems, float scale, uint16_t* out);
 // single-image searches: the query plane and its scales without a host round trip (scales_dev[0] = query scale,
 // [1] = 1 / (query scale x db_scale)); ctx->f16_scale_dev != null makes the filter kernel read [1] instead of its argument

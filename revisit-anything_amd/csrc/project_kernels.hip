@@ -15,7 +15,7 @@
 // Projecting the RESIDUAL (not the token, with the centre term subtracted afterwards) keeps the sums free of cancellation:
 // the result is as accurate as projecting the finished descriptor.
 //
-//   group_plan_kernel          lab_off [B][K+1] -> rowbase [B][K] (grouped row of (image, cluster)), tile_group [tiles]
+//   group_plan_kernel          cov_cnt [B][K] -> rowbase [B][K] (grouped row of (image, cluster)), tile_group [tiles]
 //   project_consts_kernel      W mu ([P])                                         (once per PCA model)
 //   project_aggregate_kernel   the weighted sums above on fp32 MFMA (exact fp32 chains), mean term and whitening scale fused
 #include "ctx.h"
@@ -27,9 +27,11 @@ __device__ __forceinline__ int pj_frag_row(int r, int kk) { return (r & 3) + 8 *
 // ---- grouping plan ---------------------------------------------------------------------------------------------------
 // One workgroup.  Cluster k's tokens of all images occupy rows [base_k, base_k + M_k) of the grouped planes, base_k a
 // multiple of 256 (a GEMM row tile never straddles two clusters); inside, image b's tokens of that cluster start at
-// rowbase[b][k], in the label-grouped order of prep_kernel.  Thread (k, c) owns cluster k for the c-th slice of the images:
+// rowbase[b][k], in the label-grouped order of prep_kernel.  Only the tokens that some segment covers have a row (cov_cnt[b][k]
+// of them, row = rowbase + prep_kernel's phys): nothing reads the projection of the others, and the GEMM's time follows its
+// row tiles.  Thread (k, c) owns cluster k for the c-th slice of the images:
 // slice sums -> exclusive scan over the slices (per cluster) and over the padded cluster totals -> slice walk.
-__global__ __launch_bounds__(1024) void group_plan_kernel(const int32_t* __restrict__ lab_off, int B, int K,
+__global__ __launch_bounds__(1024) void group_plan_kernel(const int32_t* __restrict__ cov_cnt, int B, int K,
                                                           int32_t* __restrict__ rowbase, int32_t* __restrict__ tile_group,
                                                           int max_tiles) {
   __shared__ int32_t part[1024], base[257];
@@ -40,7 +42,7 @@ __global__ __launch_bounds__(1024) void group_plan_kernel(const int32_t* __restr
   for (int t = threadIdx.x; t < max_tiles; t += blockDim.x) tile_group[t] = -1;
   int sum = 0;
   if (act)
-    for (int b = b0; b < b1; ++b) sum += lab_off[(size_t)b * (K + 1) + k + 1] - lab_off[(size_t)b * (K + 1) + k];
+    for (int b = b0; b < b1; ++b) sum += cov_cnt[(size_t)b * K + k];
   part[threadIdx.x] = act ? sum : 0;
   __syncthreads();
   if ((int)threadIdx.x < K) {                     // exclusive scan over this cluster's slices; total M_k
@@ -62,7 +64,7 @@ __global__ __launch_bounds__(1024) void group_plan_kernel(const int32_t* __restr
     int run = base[k] + part[threadIdx.x];
     for (int b = b0; b < b1; ++b) {
       rowbase[(size_t)b * K + k] = run;
-      run += lab_off[(size_t)b * (K + 1) + k + 1] - lab_off[(size_t)b * (K + 1) + k];
+      run += cov_cnt[(size_t)b * K + k];
     }
   }
   __syncthreads();   // the -1 fill above is complete
@@ -70,10 +72,10 @@ __global__ __launch_bounds__(1024) void group_plan_kernel(const int32_t* __restr
     for (int t = base[threadIdx.x] >> 8; t < (base[threadIdx.x + 1] >> 8) && t < max_tiles; ++t) tile_group[t] = threadIdx.x;
 }
 
-int sv_launch_group_plan(segvlad_ctx* ctx, const int32_t* lab_off, int B, int K, int32_t* rowbase, int32_t* tile_group,
+int sv_launch_group_plan(segvlad_ctx* ctx, const int32_t* cov_cnt, int B, int K, int32_t* rowbase, int32_t* tile_group,
                          int max_tiles) {
   if (K > 256) return ctx->fail(SEGVLAD_ERR_LIMIT, "group_plan: K=%d > 256", K);
-  hipLaunchKernelGGL(group_plan_kernel, dim3(1), dim3(1024), 0, ctx->stream, lab_off, B, K, rowbase, tile_group, max_tiles);
+  hipLaunchKernelGGL(group_plan_kernel, dim3(1), dim3(1024), 0, ctx->stream, cov_cnt, B, K, rowbase, tile_group, max_tiles);
   SV_HIP(hipGetLastError());
   return SEGVLAD_OK;
 }
@@ -108,7 +110,10 @@ int sv_launch_project_consts(segvlad_ctx* ctx, const float* comps, const float* 
 // spans clusters: the segment weights a_sk are per-tile constants held in registers) staged through a DOUBLE-BUFFERED LDS
 // tile: the tile list is built once, the global loads of tile t+1 are issued before the MFMAs of tile t and stored behind
 // them -- one barrier per tile and no exposed load latency (a cluster holds ~24 tokens of an image: ~64 tiles per image,
-// each previously paying a full load round trip between two barriers).  MFMA 32x32x2 f32 with A = the segment's weight
+// each previously paying a full load round trip between two barriers).  Tiles are made of LOGICAL positions; the row of Z behind
+// position j of cluster k is rowbase + phys[j] (prep_kernel: the covered tokens only have one).  The image's slice of phys is
+// staged in LDS once, beside the tile list; a position without a row is staged as zeros WITHOUT a load (its mask words are
+// all zero, but the pad rows of Z hold any bit pattern and 0 x NaN would poison the sum).  MFMA 32x32x2 f32 with A = the segment's weight
 // where its column-mask bit is set, else 0, B = z.  The mean term W mu and the whitening scale are applied in the epilogue.
 constexpr int PJ_T = 32;   // rows per tile (an image has at most K + N / 32 tiles: `maxt`)
 
@@ -127,6 +132,7 @@ __global__ __launch_bounds__(64 * NW) void project_aggregate_kernel(const float*
                                                                 const uint64_t* __restrict__ colmask,
                                                                 const int32_t* __restrict__ lab_off,
                                                                 const int32_t* __restrict__ rowbase,
+                                                                const int32_t* __restrict__ phys,
                                                                 const int32_t* __restrict__ seg_off, int N, int K, int P, int SC,
                                                                 int maxt, const float* __restrict__ col_scale,
                                                                 float* __restrict__ Y, float zscale) {
@@ -140,10 +146,11 @@ __global__ __launch_bounds__(64 * NW) void project_aggregate_kernel(const float*
   uint64_t* mk = reinterpret_cast<uint64_t*>(zt + 2 * PJ_T * NC);  // [2][PJ_T] column masks of the staged tokens
   int32_t* tl_k = reinterpret_cast<int32_t*>(mk + 2 * PJ_T);       // [maxt] cluster of tile t
   int32_t* tl_j = tl_k + maxt;                                     // [maxt] first token (label-grouped order) of tile t
-  int32_t* tl_z = tl_j + maxt;                                     // [maxt] first row of Z of tile t
+  int32_t* tl_z = tl_j + maxt;                                     // [maxt] row of Z of the cluster's first covered token
   int32_t* tl_n = tl_z + maxt;                                     // [maxt] rows in tile t
-  // F16: [2 buffers][k-step][segment half][64 lanes] 16-byte mask fragments, behind the lists (+ K + 1 tile offsets)
-  uint4* af = reinterpret_cast<uint4*>((reinterpret_cast<uintptr_t>(tl_n + maxt + K + 1) + 15) & ~(uintptr_t)15);
+  int32_t* phl = tl_n + maxt + K + 1;                              // [N] the image's phys, behind the lists (+ K + 1 tile offsets)
+  // F16: [2 buffers][k-step][segment half][64 lanes] 16-byte mask fragments, behind them
+  uint4* af = reinterpret_cast<uint4*>((reinterpret_cast<uintptr_t>(phl + N) + 15) & ~(uintptr_t)15);
   __shared__ int s_tiles;
   const int b = blockIdx.y, p0 = blockIdx.x * NC;
   const int tid = threadIdx.x, w = tid >> 6, l = tid & 63, i = l & 31, kk = l >> 5;
@@ -162,6 +169,7 @@ __global__ __launch_bounds__(64 * NW) void project_aggregate_kernel(const float*
     my_g0 = rowbase[(size_t)b * K + tid];
     tl_pre[tid + 1] = (my_n + PJ_T - 1) / PJ_T;
   }
+  for (int j = tid; j < N; j += NT_) phl[j] = phys[(size_t)b * N + j];
   __syncthreads();
   if (tid == 0) {
     int run = 0;
@@ -178,7 +186,7 @@ __global__ __launch_bounds__(64 * NW) void project_aggregate_kernel(const float*
     for (int j0 = 0; j0 < my_n && t < maxt; j0 += PJ_T, ++t) {
       tl_k[t] = tid;
       tl_j[t] = my_o0 + j0;
-      tl_z[t] = my_g0 + j0;
+      tl_z[t] = my_g0;
       tl_n[t] = min(PJ_T, my_n - j0);
     }
   }
@@ -215,10 +223,12 @@ __global__ __launch_bounds__(64 * NW) void project_aggregate_kernel(const float*
     do {                                                                                                        \
       const int nt_ = tl_n[t_];                                                                                 \
       const float* src_ = Z + (size_t)tl_z[t_] * P;                                                             \
+      const int32_t* ph_ = phl + tl_j[t_];                                                                      \
       _Pragma("unroll") for (int q = 0; q < 4; ++q) {                                                           \
         const int idx4 = tid + NT_ * q, row = idx4 / C4W, c4 = idx4 % C4W;                                      \
+        const int pr_ = row < nt_ ? ph_[row] : -1;                                                              \
         V[q] = make_float4(0.f, 0.f, 0.f, 0.f);                                                                 \
-        if (row < nt_ && p0 + 4 * c4 < P) V[q] = *reinterpret_cast<const float4*>(src_ + (size_t)row * P + p0 + 4 * c4); \
+        if (pr_ >= 0 && p0 + 4 * c4 < P) V[q] = *reinterpret_cast<const float4*>(src_ + (size_t)pr_ * P + p0 + 4 * c4); \
       }                                                                                                         \
       if (tid < PJ_T) M = tid < nt_ ? colmask[((size_t)b * N + tl_j[t_] + tid) * SC + sc] : 0ull;               \
     } while (0)
@@ -388,8 +398,9 @@ __global__ __launch_bounds__(64 * NW) void project_aggregate_kernel(const float*
 }
 
 int sv_launch_project_aggregate(segvlad_ctx* ctx, const float* Z, const float* wmu, const float* block_norms, const float* gscale,
-                                const uint64_t* colmask, const int32_t* lab_off, const int32_t* rowbase, const int32_t* seg_off_dev,
-                                int B, int N, int K, int P, int SC, int S_max, const float* col_scale, float* Y, float zscale) {
+                                const uint64_t* colmask, const int32_t* lab_off, const int32_t* rowbase, const int32_t* phys,
+                                const int32_t* seg_off_dev, int B, int N, int K, int P, int SC, int S_max, const float* col_scale,
+                                float* Y, float zscale) {
   if (B <= 0 || S_max <= 0) return SEGVLAD_OK;
   if (P % 4) return ctx->fail(SEGVLAD_ERR_ARG, "project_aggregate: P=%d must be a multiple of 4", P);
   const int maxt = K + (N + PJ_T - 1) / PJ_T;   // every cluster may end in a partial tile
@@ -398,7 +409,7 @@ int sv_launch_project_aggregate(segvlad_ctx* ctx, const float* Z, const float* w
   // zscale > 0: the tile sums on the 16-bit pipe (8-wave workgroups; + the mask-fragment image: 2 x 4 KiB, 16-byte aligned)
   const bool f16 = zscale > 0.f && nw == 8 && ctx->opt.pj_f16 != 0;
   const size_t lds = (size_t)64 * (K + 1 + (K & 1)) * 4 + (size_t)2 * PJ_T * 32 * nw * 4 + (size_t)2 * PJ_T * 8 + (size_t)4 * maxt * 4 +
-                     (size_t)(K + 1) * 4 + (f16 ? 16 + 2 * 256 * 16 : 0);
+                     (size_t)(K + 1) * 4 + (size_t)N * 4 + (f16 ? 16 + 2 * 256 * 16 : 0);
   if (lds > 160 * 1024)
     return ctx->fail(SEGVLAD_ERR_LIMIT, "project_aggregate: K=%d, N=%d need %zu B of LDS", K, N, lds);
   const void* fn = f16 ? reinterpret_cast<const void*>(project_aggregate_kernel<8, true>)
@@ -407,13 +418,13 @@ int sv_launch_project_aggregate(segvlad_ctx* ctx, const float* Z, const float* w
   const dim3 grid((P + 32 * nw - 1) / (32 * nw), B), block(64 * nw);
   if (f16)
     hipLaunchKernelGGL((project_aggregate_kernel<8, true>), grid, block, lds, ctx->stream, Z, wmu, block_norms, gscale, colmask, lab_off,
-                       rowbase, seg_off_dev, N, K, P, SC, maxt, col_scale, Y, zscale);
+                       rowbase, phys, seg_off_dev, N, K, P, SC, maxt, col_scale, Y, zscale);
   else if (nw == 8)
     hipLaunchKernelGGL(project_aggregate_kernel<8>, grid, block, lds, ctx->stream, Z, wmu, block_norms, gscale, colmask, lab_off, rowbase,
-                       seg_off_dev, N, K, P, SC, maxt, col_scale, Y, 0.f);
+                       phys, seg_off_dev, N, K, P, SC, maxt, col_scale, Y, 0.f);
   else
     hipLaunchKernelGGL(project_aggregate_kernel<4>, grid, block, lds, ctx->stream, Z, wmu, block_norms, gscale, colmask, lab_off, rowbase,
-                       seg_off_dev, N, K, P, SC, maxt, col_scale, Y, 0.f);
+                       phys, seg_off_dev, N, K, P, SC, maxt, col_scale, Y, 0.f);
   SV_HIP(hipGetLastError());
   return SEGVLAD_OK;
 }

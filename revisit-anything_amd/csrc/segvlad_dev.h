@@ -29,6 +29,8 @@
  *     "tnk_fork"      1 | 0   the two-tile Gram launch on the context's side stream | in line
  *     "pj_f16"        1 | 0   P-space tile sums on the 16-bit matrix pipe | fp32 MFMA
  *     "pj_nw"         8 | 4   waves per workgroup of the P-space aggregation
+ *     "cover_rows"    1 | 0   project form: only the tokens that some segment covers get a row of the grouped planes and of Z
+ *                             (same bits: tests/test_gpu_cover_rows.py) | every token gets a row
  *     "x3_tile", "x3_gm", "agg_kpb", "assign_narrow"   tile / order / geometry of the projection GEMM, the descriptor
  *                     aggregation and the assignment kernel
  *     "f16_persist_wgs" 1..32 resident workgroups per XCD of the persistent batch filter (32 = every CU; fewer leave CUs to other streams)
@@ -52,7 +54,7 @@
  *     "debug_fail_search"  segvlad_search fails at once (the sharded entry's error path)
  *     "guard_undersize"    "<buffer>:<bytes>": guard-mode tests (include/segvlad.h, SEGVLAD_GUARD)
  *   Environment read once by segvlad_create for these: SEGVLAD_F16_CFG, SEGVLAD_F16_GM, SEGVLAD_X3_TILE, SEGVLAD_X3_GM,
- *   SEGVLAD_ASSIGN_NARROW, SEGVLAD_DEBUG_SEARCH, SEGVLAD_AGG_KPB.
+ *   SEGVLAD_ASSIGN_NARROW, SEGVLAD_DEBUG_SEARCH, SEGVLAD_AGG_KPB, SEGVLAD_COVER_ROWS.
  */
 #ifndef SEGVLAD_DEV_H
 #define SEGVLAD_DEV_H

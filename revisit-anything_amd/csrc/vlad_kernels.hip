@@ -762,6 +762,11 @@ int sv_launch_assign(segvlad_ctx* ctx, const float* tokens, int B, int N, float*
 //   inc2[s] = OR_{u : adj[s][u]} inc[u]                       (adj . inc) > 0
 //   colmask[t][sc] bit (s - 64 sc) = inc2[s][t]               column form consumed by the aggregation
 //   gscale[s] = 1/sqrt(#clusters k with a token t: label_t = k and inc2[s][t])
+//   phys[p], cov_cnt[k]   (phys != null: the "project" form) the PHYSICAL row of position p inside its (image, cluster) list
+//                         of the grouped planes and of Z: its rank among the list's COVERED positions (a position is covered
+//                         when some segment's inc2 holds its token), -1 for an uncovered one -- no segment reads its projected
+//                         row, so it gets none; cov_cnt = covered positions of the list.  cover == 0: every position counts as
+//                         covered (phys = p - lab_off[k], cov_cnt = the list's length).  Logical positions stay what they are.
 // ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void prep_kernel(const uint8_t* __restrict__ labels, const uint64_t* __restrict__ inc,
                                                    const int32_t* __restrict__ seg_off,
@@ -769,7 +774,8 @@ __global__ __launch_bounds__(256) void prep_kernel(const uint8_t* __restrict__ l
                                                    int N, int K, int S_max, int SC, uint64_t* __restrict__ colmask,
                                                    float* __restrict__ gscale, int32_t* __restrict__ tok_order,
                                                    int32_t* __restrict__ lab_off, const float* __restrict__ rnorm,
-                                                   float* __restrict__ rn_sorted, int stage, int ord_n) {
+                                                   float* __restrict__ rn_sorted, int stage, int ord_n,
+                                                   int32_t* __restrict__ phys, int32_t* __restrict__ cov_cnt, int cover) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int b = blockIdx.x;
   const int nw = (N + 63) >> 6;
@@ -861,24 +867,56 @@ __global__ __launch_bounds__(256) void prep_kernel(const uint8_t* __restrict__ l
     }
   }
   __syncthreads();
+  // covered positions as bit rows (word q = positions 64 q .. 64 q + 63: one wave's ballot) and their running counts, behind the
+  // token order (the staged union's rows, dead by now, or the launcher's extra bytes)
+  uint64_t* cbits = reinterpret_cast<uint64_t*>(ord + ord_n);   // [nw]
+  int* cpre = reinterpret_cast<int*>(cbits + nw);               // [nw + 1] covered positions before word q
   for (int p = tid; p < N; p += 256) {
     const int t = ord[p];
     const int w = t >> 6, bit = t & 63;
     tok_order[(size_t)b * N + p] = t;
     rn_sorted[(size_t)b * N + p] = rnorm[(size_t)b * N + t];
+    uint64_t any = 0;
     for (int sc = 0; sc < SC; ++sc) {
       uint64_t m = 0;
       const int lo = sc * 64, hi = min(S, lo + 64);
       for (int s = lo; s < hi; ++s) m |= ((inc2[s * nw + w] >> bit) & 1ull) << (s - lo);
       colmask[((size_t)b * N + p) * SC + sc] = m;   // indexed by POSITION in the label-grouped order
+      any |= m;
+    }
+    if (phys) {   // (p = tid + 256 it: the wave's active lanes are the positions of ONE word)
+      const uint64_t cw = __builtin_amdgcn_ballot_w64(any != 0 || !cover);
+      if ((tid & 63) == 0) cbits[p >> 6] = cw;
     }
   }
   __syncthreads();
+  if (phys && tid == 0) {
+    int a = 0;
+    for (int q = 0; q < nw; ++q) {
+      cpre[q] = a;
+      a += __popcll(cbits[q]);
+    }
+    cpre[nw] = a;
+  }
   // number of non-empty (segment, cluster) blocks per segment: one thread per PAIR (a thread per segment walked K * nw
   // word pairs alone while 200 threads idled), counted in the (now free) token-order array
   int* nnz = ord;
   for (int s = tid; s < S; s += 256) nnz[s] = 0;
   __syncthreads();
+  if (phys) {
+    // covered positions before position p (p <= N)
+    auto crank = [&](int p) { return (p >> 6) < nw ? cpre[p >> 6] + __popcll(cbits[p >> 6] & ((1ull << (p & 63)) - 1ull)) : cpre[nw]; };
+    for (int p = tid; p < N; p += 256) {
+      int lo = 0, hi = K - 1;   // the list of p: the last k with kcnt[k] <= p (an empty list shares its start with the next one)
+      while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (kcnt[mid] <= p) lo = mid;
+        else hi = mid - 1;
+      }
+      phys[(size_t)b * N + p] = ((cbits[p >> 6] >> (p & 63)) & 1ull) ? crank(p) - crank(kcnt[lo]) : -1;
+    }
+    for (int k = tid; k < K; k += 256) cov_cnt[(size_t)b * K + k] = crank(kcnt[k + 1]) - crank(kcnt[k]);
+  }
   for (int idx = tid; idx < S * K; idx += 256) {
     const int s = idx / K, k = idx - s * K;
     uint64_t any = 0;
@@ -891,14 +929,15 @@ __global__ __launch_bounds__(256) void prep_kernel(const uint8_t* __restrict__ l
 
 int sv_launch_prep(segvlad_ctx* ctx, const uint8_t* labels, const uint64_t* inc_bits, const int32_t* seg_off_dev,
                    const int64_t* adj_off_dev, const uint8_t* adj, int B, int N, int K, int S_max, int SC,
-                   uint64_t* colmask, float* gscale) {
+                   uint64_t* colmask, float* gscale, int32_t* phys, int32_t* cov_cnt, int cover) {
   const int nw = (N + 63) / 64;
   if (K > 256) return ctx->fail(SEGVLAD_ERR_LIMIT, "prep: K=%d > 256", K);
   SV_HIP(ctx->s_tokorder.reserve((size_t)B * N * sizeof(int32_t)));
   SV_HIP(ctx->s_laboff.reserve((size_t)B * (K + 1) * sizeof(int32_t)));
   SV_HIP(ctx->s_rnsorted.reserve((size_t)B * N * sizeof(float)));
   const int ord_n = ((N > S_max ? N : S_max) + 1) & ~1;   // token order, later the per-segment block counts
-  size_t lds = ((size_t)S_max + K) * nw * sizeof(uint64_t) + (size_t)ord_n * sizeof(int);
+  // (+ the covered-position words and their running counts, behind the token order)
+  size_t lds = ((size_t)S_max + K) * nw * sizeof(uint64_t) + (size_t)ord_n * sizeof(int) + (size_t)nw * 8 + (size_t)(nw + 2) * 4;
   if (lds > 160 * 1024)
     return ctx->fail(SEGVLAD_ERR_LIMIT, "prep: (S_max=%d + K=%d) x %d token words needs %zu B of LDS (limit 160 KiB)", S_max,
                      K, nw, lds);
@@ -906,12 +945,12 @@ int sv_launch_prep(segvlad_ctx* ctx, const uint8_t* labels, const uint64_t* inc_
   const size_t lds_staged = ((size_t)S_max + K) * nw * 8 + (size_t)ord_n * 4 + (size_t)S_max * nw * 8 +
                             (size_t)S_max * ((S_max + 63) / 64) * 8;
   const int stage = (adj != nullptr && lds_staged <= 150 * 1024) ? 1 : 0;
-  if (stage) lds = lds_staged;
+  if (stage && lds_staged > lds) lds = lds_staged;
   if (lds > 64 * 1024)
     SV_HIP(sv_max_dyn_lds(reinterpret_cast<const void*>(prep_kernel), (size_t)lds));
   hipLaunchKernelGGL(prep_kernel, dim3(B), dim3(256), lds, ctx->stream, labels, inc_bits, seg_off_dev, adj_off_dev, adj, N,
                      K, S_max, SC, colmask, gscale, ctx->s_tokorder.as<int32_t>(), ctx->s_laboff.as<int32_t>(),
-                     ctx->s_rnorm.as<float>(), ctx->s_rnsorted.as<float>(), stage, ord_n);
+                     ctx->s_rnorm.as<float>(), ctx->s_rnsorted.as<float>(), stage, ord_n, phys, cov_cnt, cover);
   SV_HIP(hipGetLastError());
   return SEGVLAD_OK;
 }
@@ -1179,19 +1218,21 @@ __global__ __launch_bounds__(64 * TNK_WAVES, 2) void token_norms_kernel(const fl
                                                                     int Dpad, float* __restrict__ block_norms, float xscale,
                                                                     _Float16* __restrict__ h1, _Float16* __restrict__ h2,
                                                                     const int32_t* __restrict__ rowbase, int64_t dummy_row,
-                                                                    int skip_le, const uint8_t* __restrict__ redo_task) {
+                                                                    int skip_le, const uint8_t* __restrict__ redo_task,
+                                                                    const int32_t* __restrict__ phys) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int b = blockIdx.y;
   const int tid = threadIdx.x, l = tid & 63, i = l & 31, kk = l >> 5;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int k = (int)blockIdx.x * TNK_WAVES + w;
   if (k >= K) return;   // (no barriers in this kernel)
-  const size_t wsz = (size_t)TNK_QD * 1024 + (size_t)TNK_LCAP * 16 + (size_t)Dpad * 4;
+  const size_t wsz = (size_t)TNK_QD * 1024 + (size_t)TNK_LCAP * 20 + (size_t)Dpad * 4;
   unsigned char* qbase = smem + (size_t)w * wsz;                                  // [QD][1 KiB] DMA queue
   uint64_t* mskl = reinterpret_cast<uint64_t*>(qbase + TNK_QD * 1024);            // [LCAP]
   int* tokl = reinterpret_cast<int*>(mskl + TNK_LCAP);                            // [LCAP]
   float* rnl = reinterpret_cast<float*>(tokl + TNK_LCAP);                         // [LCAP]
-  float* cl = rnl + TNK_LCAP;                                                     // [Dpad] centre k
+  int* rowl = reinterpret_cast<int*>(rnl + TNK_LCAP);                             // [LCAP] plane row of the token, -1: it has none
+  float* cl = reinterpret_cast<float*>(rowl + TNK_LCAP);                          // [Dpad] centre k
   const int o0 = lab_off[(size_t)b * (K + 1) + k];
   const int n = lab_off[(size_t)b * (K + 1) + k + 1] - o0;
   const int s0 = seg_off[b], S = seg_off[b + 1] - s0;
@@ -1209,19 +1250,25 @@ __global__ __launch_bounds__(64 * TNK_WAVES, 2) void token_norms_kernel(const fl
   for (int d = 4 * l; d < Dpad; d += 256)
     *reinterpret_cast<float4*>(cl + d) = d < D ? *reinterpret_cast<const float4*>(C + (size_t)k * D + d) : make_float4(0.f, 0.f, 0.f, 0.f);
   constexpr bool single = !BIG;   // the token list fits the wave's LDS lists
+  // a token's plane row: rowbase + its rank among the task's covered tokens (prep_kernel's phys; -1: no segment covers it --
+  // nothing reads its row, it has none)
+  const int grow0 = rowbase[(size_t)b * K + k];
   if (single) {
     for (int j = l; j < n; j += 64) {
       tokl[j] = tok_order[tb + j];
       rnl[j] = rnorm[tb + j];
+      const int ph = phys[tb + j];
+      rowl[j] = ph >= 0 ? grow0 + ph : -1;
     }
     if (l == 0 && (n & 1)) {
       tokl[n] = 0;
       rnl[n] = 0.f;
+      rowl[n] = -1;
     }
   }
-  const int64_t grow0 = rowbase[(size_t)b * K + k];
   const size_t nkb_d = (size_t)(D >> 5);
-  const size_t ob_dummy = sv_x3_off(dummy_row < 0 ? -dummy_row : dummy_row, (4 * i) % D, D);
+  // lanes without a row store to the dummy tile (256 rows behind the planes; spread over its rows: one address would be a hot spot)
+  const size_t ob_dummy = sv_x3_off((dummy_row < 0 ? -dummy_row : dummy_row) + ((64 * k + l) & 255), (4 * i) % D, D);
   const float* Xb = Xt + (size_t)b * N * D;
 
   for (int sc = 0; sc < SCb; ++sc) {
@@ -1268,12 +1315,15 @@ __global__ __launch_bounds__(64 * TNK_WAVES, 2) void token_norms_kernel(const fl
         float rn = 0.f;
         uint64_t m = 0ull;
         f32x4 x;
+        int prw = -1;   // the token's plane row (first segment chunk)
         if (!single) {
           rn = j < n ? rnorm[tb + j] : 0.f;
           m = j < n ? colmask[(tb + j) * SC + sc] : 0ull;
+          const int ph = (sc == 0 && j < n) ? phys[tb + j] : -1;
+          prw = ph >= 0 ? grow0 + ph : -1;
         }
         // ops issued after step f's DMA: min(QD - 1, rem) later DMAs and, on the first segment chunk, two plane stores for
-        // each of the last min(QD, f) steps (always issued: lanes without a valid element write the dummy row)
+        // each of the last min(QD, f) steps (always issued: lanes without a valid element or without a row write the dummy tile)
         const int rem = total - 1 - f;
         if (single && dummy_row >= 0) {
           // steady state (a full queue behind and ahead): the count is the constant QD - 1 (+ 2 QD plane stores)
@@ -1304,9 +1354,11 @@ __global__ __launch_bounds__(64 * TNK_WAVES, 2) void token_norms_kernel(const fl
             p1[e] = (_Float16)fv[e];
             p2[e] = (_Float16)(fv[e] - (float)p1[e]);
           }
-          const bool real = dvalid && j < n;
-          // sv_x3_off(grow0 + j, dcol, D) with the lane / chunk constants of this 128-column chunk taken out of the loop
-          const unsigned rr = (unsigned)(grow0 + j);
+          // (the row list is read on the first chunk only; these stores are never predicated away: the counted waits count them)
+          if (single) prw = lds_read_i32(lds_addr(rowl + j));
+          const bool real = dvalid && prw >= 0;
+          // sv_x3_off(row, dcol, D) with the lane / chunk constants of this 128-column chunk taken out of the loop
+          const unsigned rr = (unsigned)prw;
           const size_t ob = real ? ((size_t)(rr >> 7) * nkb_d + kb_dc) * 4096 + (size_t)(((rr & 127u) << 5) + (((lane_c ^ (unsigned)sv_x3_swz(rr)) << 3) | lane_o))
                                  : ob_dummy;
           *reinterpret_cast<h4*>(h1 + ob) = p1;
@@ -1384,7 +1436,8 @@ __global__ __launch_bounds__(T == 1 ? 256 : 128, 2) void gram_norms_kernel(const
                                                                          float* __restrict__ block_norms, float xscale,
                                                                          _Float16* __restrict__ h1, _Float16* __restrict__ h2,
                                                                          const int32_t* __restrict__ rowbase, int safe_waits,
-                                                                         uint8_t* __restrict__ redo_task) {
+                                                                         uint8_t* __restrict__ redo_task,
+                                                                         const int32_t* __restrict__ phys, int64_t dummy_row) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
   constexpr int WAVES = T == 1 ? 4 : 2;
@@ -1447,7 +1500,11 @@ __global__ __launch_bounds__(T == 1 ? 256 : 128, 2) void gram_norms_kernel(const
   unsigned pswz[T];
 #pragma unroll
   for (int tt = 0; tt < T; ++tt) {
-    const int64_t rr = (int64_t)rowbase[(size_t)b * K + k] + 32 * tt + i;   // this lane's row of the grouped planes
+    // this lane's row of the grouped planes: rowbase + the token's rank among the task's covered tokens (prep_kernel's phys).  A
+    // token no segment covers has no row -- nothing reads it -- and stores to the dummy tile behind the planes (spread over its 256
+    // rows), NOT nowhere: a tile whose tokens are all uncovered would skip the store instruction, and the counted waits count it
+    const int ph = real[tt] ? phys[tb + 32 * tt + i] : 0;
+    const int64_t rr = ph >= 0 ? (int64_t)rowbase[(size_t)b * K + k] + ph : dummy_row + ((32 * (k + tt) + i) & 255);
     prow[tt] = (size_t)(rr >> 7) * (size_t)(D >> 5) * 4096 + (size_t)(rr & 127) * 32;
     pswz[tt] = (unsigned)sv_x3_swz(rr);
   }
@@ -1581,10 +1638,10 @@ __global__ __launch_bounds__(T == 1 ? 256 : 128, 2) void gram_norms_kernel(const
 
 int sv_launch_token_norms(segvlad_ctx* ctx, const float* xt, const uint64_t* colmask, const float* centres, int K, int D,
                           const int32_t* seg_off_dev, int B, int N, int SC, float* block_norms, float xscale, uint16_t* h1,
-                          uint16_t* h2, const int32_t* rowbase, int64_t dummy_row) {
+                          uint16_t* h2, const int32_t* rowbase, int64_t dummy_row, const int32_t* phys) {
   if (D % 4) return ctx->fail(SEGVLAD_ERR_ARG, "token_norms: D=%d must be a multiple of 4", D);
   const int Dpad = (D + 127) & ~127;
-  const size_t lds = (size_t)TNK_WAVES * ((size_t)TNK_QD * 1024 + (size_t)TNK_LCAP * 16 + (size_t)Dpad * 4);
+  const size_t lds = (size_t)TNK_WAVES * ((size_t)TNK_QD * 1024 + (size_t)TNK_LCAP * 20 + (size_t)Dpad * 4);
   if (lds > 160 * 1024) return ctx->fail(SEGVLAD_ERR_LIMIT, "token_norms: D=%d needs %zu B of LDS", D, lds);
   // tasks of <= 64 tokens: the Gram kernels (option tnk_gram, default on; D a multiple of 32); the rest: the block-sum kernels
   const bool gram = ctx->opt.tnk_gram != 0 && (D % 32) == 0;
@@ -1608,7 +1665,8 @@ int sv_launch_token_norms(segvlad_ctx* ctx, const float* xt, const uint64_t* col
       hipLaunchKernelGGL(gk, dim3((K + waves - 1) / waves, B), dim3(64 * waves), glds, (T == 2 && fork) ? ctx->side : ctx->stream, xt,
                          ctx->s_rnsorted.as<float>(), ctx->s_tokorder.as<int32_t>(), ctx->s_laboff.as<int32_t>(), colmask, centres,
                          seg_off_dev, N, D, K, SC, block_norms, xscale, reinterpret_cast<_Float16*>(h1),
-                         reinterpret_cast<_Float16*>(h2), rowbase, dummy_row < 0 ? 1 : 0, redo_task);
+                         reinterpret_cast<_Float16*>(h2), rowbase, dummy_row < 0 ? 1 : 0, redo_task, phys,
+                         dummy_row < 0 ? -dummy_row : dummy_row);
       SV_HIP(hipGetLastError());
     }
     if (fork) SV_TRY(sv_join_side(ctx));
@@ -1621,7 +1679,7 @@ int sv_launch_token_norms(segvlad_ctx* ctx, const float* xt, const uint64_t* col
     hipLaunchKernelGGL(kern, dim3((K + TNK_WAVES - 1) / TNK_WAVES, B), dim3(64 * TNK_WAVES), lds, ctx->stream, xt,
                        ctx->s_rnsorted.as<float>(), ctx->s_tokorder.as<int32_t>(), ctx->s_laboff.as<int32_t>(), colmask, centres,
                        seg_off_dev, N, D, K, SC, Dpad, block_norms, xscale, reinterpret_cast<_Float16*>(h1),
-                       reinterpret_cast<_Float16*>(h2), rowbase, dummy_row, skip_le, redo_task);
+                       reinterpret_cast<_Float16*>(h2), rowbase, dummy_row, skip_le, redo_task, phys);
     SV_HIP(hipGetLastError());
   }
   return SEGVLAD_OK;

@@ -182,7 +182,18 @@ int segvlad_cluster_aggregate(segvlad_ctx* ctx, int num_c, const float* res, con
  *      Y = ((X - mean) @ comps^T) / sqrt(expl_var) when whiten!=0.  comps [P][KD] fp32.          */
 int segvlad_pca_set(segvlad_ctx* ctx, const float* mean, const float* comps, const float* expl_var, int P, int KD,
                     int whiten);
-/*      X [n][KD] -> Y [n][P]; l2norm!=0 additionally applies normalizeFeat (func_vpr.py:1673-1676) */
+/*      X [n][KD] -> Y [n][P]; l2norm!=0 additionally applies normalizeFeat (func_vpr.py:1673-1676).
+ *      Accuracy.  With KD % 32 == 0 (and option pca_arith != fp32) the product runs as a two-term fp16 split on the 16-bit
+ *      matrix pipe, with ONE power-of-two scale per batch (from max|X| + max|mean| over the finite entries) and ONE per model
+ *      (from max|comps|).  A row of X - mean (a row of comps) whose largest element is at least 2^-12 of that maximum comes
+ *      out fp32-class relative to ITS OWN magnitude, like an fp32 product.  Below that the second fp16 terms are sub-normal:
+ *      the absolute error per element is bounded by 2^-25 of the scaled unit (2^-38 of the batch / model maximum), so the
+ *      row's relative error grows as the row shrinks -- about 1e-5 at 2^-20 and 2e-4 at 2^-24 of the maximum (K = 2048)
+ *      against 1e-6 for fp32.  With a mean, X - mean keeps the rows of a descriptor batch at one scale; a caller whose rows
+ *      (or whose components: the PCA fit's X^T operand) span more than 2^12 and who needs the small ones to full relative
+ *      accuracy sets pca_arith=fp32.  A NaN / Inf row of X gives a non-finite row of Y and leaves the other rows alone.
+ *      (tests/test_gpu_projection.py holds every output entry to this.)  On that path a device pointer X must be 16-byte
+ *      aligned (SEGVLAD_ERR_ARG otherwise; nothing is staged: X may be far larger than any scratch buffer).        */
 int segvlad_pca_apply(segvlad_ctx* ctx, const float* X, int n, float* Y, int l2norm);
 
 /* ---- row L2 normalisation: normalizeFeat                             func_vpr.py:1673-1676

@@ -1094,10 +1094,16 @@ int segvlad_pca_apply(segvlad_ctx* ctx, const float* X, int n, float* Y, int l2n
   SV_TRY(sv_in(ctx, X, (size_t)n * ctx->KD * sizeof(float), &dx));
   SV_TRY(sv_out(ctx, Y, (size_t)n * ctx->P * sizeof(float), &dy));
   const bool x3 = ctx->pca_w_scale > 0.f && !ctx->opt.pca_fp32;
+  // the split kernel loads 16-byte pieces.  Refused rather than staged as segvlad_search_shortlist stages its queries: X can be
+  // the PCA fit's resident matrix (tens of GB), a copy of which the context cannot promise; the fp32 kernel takes any pointer.
+  if (x3 && (reinterpret_cast<uintptr_t>(dx) & 15) != 0)
+    return ctx->fail(SEGVLAD_ERR_ARG, "pca_apply: X must be 16-byte aligned for the fp16x3 projection (or set pca_arith=fp32)");
   float xscale = 1.f;
-  if (x3) {  // scale so that |x - mean| * s < 2^15: no fp16 overflow, sub-normal losses far below fp32 epsilon
+  if (x3) {  // ONE scale for the batch, so that |x - mean| * s < 2^15: no fp16 overflow; rows down to 2^-12 of the batch maximum keep
+             // both fp16 terms normal (include/segvlad.h).  The maximum is taken over the FINITE entries: a NaN / Inf row gives a
+             // non-finite row of Y and must not cost the other rows their scale.
     float xmax = 0.f;
-    SV_TRY(sv_maxabs(ctx, (const float*)dx, (int64_t)n * ctx->KD, &xmax));
+    SV_TRY(sv_maxabs(ctx, (const float*)dx, (int64_t)n * ctx->KD, &xmax, /*finite_only=*/true));
     const float bound = xmax + ctx->pca_mean_maxabs;
     if (bound > 0.f && std::isfinite(bound)) {
       int e;

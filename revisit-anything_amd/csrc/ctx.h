@@ -534,7 +534,7 @@ int sv_launch_refine_grouped(segvlad_ctx* ctx, const float* Q, const float* R, i
 int sv_refine_group_stats(segvlad_ctx* ctx, int nq, int64_t* groups, int64_t* grouped, int64_t* union_sum);
 int sv_row_norm_max(segvlad_ctx* ctx, const float* norms, int64_t n, float* out_host);
 int sv_row_norm_min(segvlad_ctx* ctx, const float* norms, int64_t n, float* out_host);
-int sv_maxabs(segvlad_ctx* ctx, const float* x, int64_t n, float* out_host);
+int sv_maxabs(segvlad_ctx* ctx, const float* x, int64_t n, float* out_host, bool finite_only = false);
 int sv_maxabs_and_norm_min(segvlad_ctx* ctx, const float* x, int64_t n, const float* norms, int64_t n_norms, float* maxabs_host,
                            float* norm_min_host);
 int sv_maxabs_and_norm_min_begin(segvlad_ctx* ctx, const float* x, int64_t n, const float* norms, int64_t n_norms);

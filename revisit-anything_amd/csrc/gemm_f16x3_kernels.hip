@@ -9,6 +9,15 @@
 // replaces, at 3/16 of the matrix-pipe time.  (The kNN filter can afford a single product because it only needs
 // a rigorous bound; here the value itself is the output, hence the two-term split.)
 //
+// Dynamic range.  "fp32-class" holds per ROW only within 2^12 of the maximum: there is ONE scale per batch (max|X| + max|mean|
+// brought into [2^13, 2^14)) and ONE per model.  A row whose largest element is >= 2^-12 of that maximum has both fp16 terms
+// of every significant element in the normal range and is fp32-class relative to its own magnitude.  Below that h2 falls into
+// the fp16 sub-normals (steps of 2^-24): every element then carries an absolute error of up to 2^-25 in scaled units, and the
+// row's relative error grows as the row shrinks (K = 2048: 3e-7 at 2^-12, 1e-5 at 2^-20, 2e-4 at 2^-24 of the maximum; an
+// fp32 product stays at 1e-6).  With a mean, x - mean keeps a descriptor batch at one scale; the PCA fit's X^T operand (a
+// descriptor column of tiny variance beside large ones) can meet it: pca_arith=fp32 is the way out.
+// tests/projection_ref.py derives the per-entry bound, tests/test_gpu_projection.py holds every entry to it.
+//
 //   split_f16x2_kernel   (X - sub) * scale -> h1, h2 planes in the blocked layout of ctx.h (sv_x3_off); sub = PCA mean on
 //                        the A side, none on the W side
 //   gemm_f16x3_kernel    C = (A1+A2).(B1+B2)^T * col_scale: BM x BN x 32 tiles, global->LDS DMA with source-side

@@ -287,9 +287,16 @@ typedef float f32x4v __attribute__((ext_vector_type(4)));
 // max |x| of a block of floats.  16-byte loads where the pointer allows, ONE atomic per workgroup: the first version's 4-byte
 // loads and one atomicMax per WAVE (16 384 of them on one word for a 10 000 x 1024 query batch) took 190 us in front of every
 // batch search (round 5 kernel trace) for 41 MB -- 10 us of reading.
+// FINITE_ONLY: NaN and Inf entries do not count (their |x| bit patterns sort above every finite value's): the maximum a
+// power-of-two scale is derived from must not be taken over by one bad row (segvlad_pca_apply).
+template <bool FINITE_ONLY>
 __global__ __launch_bounds__(256) void maxabs_kernel(const float* __restrict__ x, int64_t n, uint32_t* __restrict__ out) {
   __shared__ uint32_t wmax[4];
   uint32_t m = 0;
+  auto mag = [](uint32_t u) -> uint32_t {
+    u &= 0x7fffffffu;
+    return (FINITE_ONLY && u >= 0x7f800000u) ? 0u : u;
+  };
   const int64_t tid = (int64_t)blockIdx.x * 256 + threadIdx.x, nth = (int64_t)gridDim.x * 256;
   int64_t head = 0;   // elements in front of the first 16-byte boundary
   if ((reinterpret_cast<uintptr_t>(x) & 15) != 0) head = min<int64_t>(n, (int64_t)((16 - (reinterpret_cast<uintptr_t>(x) & 15)) >> 2));
@@ -297,24 +304,27 @@ __global__ __launch_bounds__(256) void maxabs_kernel(const float* __restrict__ x
   const uint4* x4 = reinterpret_cast<const uint4*>(x + head);
   for (int64_t j = tid; j < n4; j += nth) {
     const uint4 v = x4[j];
-    m = max(max(m, v.x & 0x7fffffffu), max(max(v.y & 0x7fffffffu, v.z & 0x7fffffffu), v.w & 0x7fffffffu));  // |x| bit pattern orders like the value
+    m = max(max(m, mag(v.x)), max(max(mag(v.y), mag(v.z)), mag(v.w)));  // |x| bit pattern orders like the value
   }
-  if (tid < head) m = max(m, __float_as_uint(x[tid]) & 0x7fffffffu);
+  if (tid < head) m = max(m, mag(__float_as_uint(x[tid])));
   const int64_t tail0 = head + 4 * n4;
-  if (tid < n - tail0) m = max(m, __float_as_uint(x[tail0 + tid]) & 0x7fffffffu);
+  if (tid < n - tail0) m = max(m, mag(__float_as_uint(x[tail0 + tid])));
   for (int o = 32; o > 0; o >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, o));
   if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = m;
   __syncthreads();
   if (threadIdx.x == 0) atomicMax(out, max(max(wmax[0], wmax[1]), max(wmax[2], wmax[3])));
 }
 
-int sv_maxabs(segvlad_ctx* ctx, const float* x, int64_t n, float* out_host) {
+int sv_maxabs(segvlad_ctx* ctx, const float* x, int64_t n, float* out_host, bool finite_only) {
   SV_HIP(ctx->s_minmax.reserve(32));
   uint32_t* mm = ctx->s_minmax.as<uint32_t>() + 4;
   SV_HIP(hipMemsetAsync(mm, 0, 4, ctx->stream));
   int64_t blocks = (n + 1023) / 1024;
   if (blocks > 1024) blocks = 1024;
-  if (n > 0) hipLaunchKernelGGL(maxabs_kernel, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, x, n, mm);
+  if (n > 0 && finite_only)
+    hipLaunchKernelGGL(maxabs_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, x, n, mm);
+  else if (n > 0)
+    hipLaunchKernelGGL(maxabs_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, x, n, mm);
   uint32_t u = 0;
   SV_HIP(hipMemcpyAsync(&u, mm, 4, hipMemcpyDeviceToHost, ctx->stream));
   SV_HIP(hipStreamSynchronize(ctx->stream));
@@ -1752,7 +1762,7 @@ int sv_maxabs_and_norm_min(segvlad_ctx* ctx, const float* x, int64_t n, const fl
   SV_HIP(hipMemcpyAsync(mm, init, 8, hipMemcpyHostToDevice, ctx->stream));
   int64_t blocks = (n + 1023) / 1024;
   if (blocks > 1024) blocks = 1024;
-  if (n > 0) hipLaunchKernelGGL(maxabs_kernel, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, x, n, mm);
+  if (n > 0) hipLaunchKernelGGL(maxabs_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, x, n, mm);
   int nb = (int)((n_norms + 255) / 256);
   if (nb > 1024) nb = 1024;
   if (n_norms > 0) hipLaunchKernelGGL(min_kernel, dim3(nb), dim3(256), 0, ctx->stream, norms, n_norms, mm + 1);
@@ -1787,7 +1797,7 @@ int sv_maxabs_and_norm_min_begin(segvlad_ctx* ctx, const float* x, int64_t n, co
   SV_HIP(hipMemcpyAsync(mm, init, 8, hipMemcpyHostToDevice, ctx->stream));
   int64_t blocks = (n + 1023) / 1024;
   if (blocks > 1024) blocks = 1024;
-  if (n > 0) hipLaunchKernelGGL(maxabs_kernel, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, x, n, mm);
+  if (n > 0) hipLaunchKernelGGL(maxabs_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, x, n, mm);
   int nb = (int)((n_norms + 255) / 256);
   if (nb > 1024) nb = 1024;
   if (n_norms > 0) hipLaunchKernelGGL(min_kernel, dim3(nb), dim3(256), 0, ctx->stream, norms, n_norms, mm + 1);

@@ -63,7 +63,10 @@ class EnginePcaBackend:
     """The same two products on the device through the C-ABI's projection GEMM: ``X V = pca_apply(X)`` with the model
     ``comps = V^T``; ``X^T U = pca_apply(U^T)^T`` with ``comps = X^T`` (rows = descriptor columns).  X stays resident
     in HBM ([n, KD] fp32; 50 000 x 98 304 = 19.7 GB).  GPU-tested against sklearn's exact solver
-    (tests/test_gpu_frows.py); the CPU tests cover the algorithm through NumpyBackend."""
+    (tests/test_gpu_frows.py); the CPU tests cover the algorithm through NumpyBackend.
+    The split GEMM has one power-of-two scale per batch and one per model: rows of ``X^T`` (descriptor columns) below 2^-12
+    of ``max|X|`` lose relative accuracy (absolute error per element <= 2^-25 of the scaled unit, include/segvlad.h) --
+    ``engine.set_option("pca_arith", "fp32")`` before the fit is the way out where such columns matter."""
 
     def __init__(self, engine, X):
         import torch

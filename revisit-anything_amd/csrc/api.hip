@@ -1,5 +1,7 @@
 // C-ABI of libsegvlad_hip.so (see include/segvlad.h).  Host-side orchestration only: argument
 // checks, host/device pointer staging, scratch sizing and kernel sequencing on the context stream.
+// This unit: context, options, staging, guard mode, stage timers, vocabulary, PCA model, pca_apply, normalise, the small search entry
+// points, vote.  describe.hip: the describe stage (plan_describe and its staged passes); search.hip: the index and the exact search.
 #include <stdarg.h>
 #include <stdlib.h>
 #include <string.h>
@@ -162,9 +164,9 @@ int sv_guard_check(segvlad_ctx* ctx) {
   return SEGVLAD_OK;
 }
 
-StageScope::StageScope(segvlad_ctx* c, const char* name) : ctx(c) {
-  if (!c->profiling || c->scope_mute) return;
-  t = &c->timers[name];
+StageTimer* sv_stage_open(segvlad_ctx* c, const char* name, int* slot) {
+  if (!c->profiling || c->scope_mute) return nullptr;
+  StageTimer* t = &c->timers[name];
   if (t->used * 2 >= (int)t->ev.size()) {
     hipEvent_t a = nullptr, b = nullptr;
     (void)hipEventCreate(&a);
@@ -172,19 +174,10 @@ StageScope::StageScope(segvlad_ctx* c, const char* name) : ctx(c) {
     t->ev.push_back(a);
     t->ev.push_back(b);
   }
-  slot = t->used++;
-  (void)hipEventRecord(t->ev[2 * slot], c->stream);
+  *slot = t->used++;
+  (void)hipEventRecord(t->ev[2 * *slot], c->stream);
+  return t;
 }
-StageScope::~StageScope() {
-  if (t) (void)hipEventRecord(t->ev[2 * slot + 1], ctx->stream);
-}
-
-// Between segvlad_describe_begin and segvlad_describe_end the context's per-batch scratch (segment / adjacency offsets, the
-// token-major copy, the labels) belongs to THAT batch, and the mask branch is in flight on the side stream: every other entry
-// point that would write them refuses instead of describing a different batch with the open one's offsets.
-#define CHECK_NO_OPEN_DESCRIBE(what)                                                                                        \
-  if (ctx->mask_branch_on_side)                                                                                             \
-  return ctx->fail(SEGVLAD_ERR_STATE, what ": a segvlad_describe_begin is open on this context (call segvlad_describe_end first)")
 
 hipError_t sv_max_dyn_lds(const void* fn, size_t bytes) {
   static std::mutex mu;
@@ -430,7 +423,7 @@ int segvlad_set_vocab(segvlad_ctx* ctx, const float* C, int K, int D) {
   ctx->D = D;
   ctx->Kpad = Kpad;
   SV_TRY(sv_launch_vocab_prepare(ctx));
-  // largest centre component: bounds the token residuals x^ - C_k whose fp16 planes the "project" form builds (images_impl)
+  // largest centre component: bounds the token residuals x^ - C_k whose fp16 planes the "project" form builds (plan_describe)
   SV_TRY(sv_maxabs(ctx, ctx->vocab.as<float>(), (int64_t)K * D, &ctx->vocab_maxabs));
   // largest centre norm: ||x^ - C_k|| <= 1 + max ||C_k||, the bound behind the fp16 split of the PROJECTED residuals (the P-space
   // sums of the "project" form on the 16-bit pipe)
@@ -441,597 +434,6 @@ int segvlad_set_vocab(segvlad_ctx* ctx, const float* C, int K, int D) {
     SV_TRY(sv_row_norm_max(ctx, ctx->s_qnorm.as<float>(), K, &n2));
     ctx->vocab_norm_max = std::sqrt(n2 > 0.f ? n2 : 0.f);
   }
-  return sv_finish(ctx);
-}
-
-// ---- incidence / centroids -------------------------------------------------------------------------
-static int incidence_impl(segvlad_ctx* ctx, const uint8_t* masks, int S, int Hm, int Wm, int H, int W, int patch,
-                          uint64_t* inc_bits, double* centroids, bool want_centroids) {
-  if (S < 0 || Hm <= 0 || Wm <= 0 || H <= 0 || W <= 0 || patch <= 0 || H / patch <= 0 || W / patch <= 0)
-    return ctx->fail(SEGVLAD_ERR_ARG, "incidence: bad geometry S=%d masks %dx%d image %dx%d patch %d", S, Hm, Wm, H, W, patch);
-  if (S == 0) return SEGVLAD_OK;
-  if (!masks || !inc_bits || (want_centroids && !centroids)) return ctx->fail(SEGVLAD_ERR_ARG, "incidence: null pointer");
-  const int N = (H / patch) * (W / patch), nw = (N + 63) / 64;
-  const void* dm;
-  void *dout, *dcent = nullptr;
-  SV_TRY(sv_in(ctx, masks, (size_t)S * Hm * Wm, &dm));
-  SV_TRY(sv_out(ctx, inc_bits, (size_t)S * nw * 8, &dout));
-  if (want_centroids) SV_TRY(sv_out(ctx, centroids, (size_t)S * 2 * sizeof(double), &dcent));
-  {
-    StageScope sc(ctx, "incidence");
-    SV_TRY(sv_launch_incidence(ctx, (const uint8_t*)dm, S, Hm, Wm, H, W, patch, (uint64_t*)dout, (double*)dcent));
-    sc.count();
-  }
-  return sv_finish(ctx);
-}
-
-int segvlad_incidence(segvlad_ctx* ctx, const uint8_t* masks, int S, int Hm, int Wm, int H, int W, int patch,
-                      uint64_t* inc_bits) {
-  CHECK_CTX();
-  CHECK_NO_OPEN_DESCRIBE("incidence");
-  return incidence_impl(ctx, masks, S, Hm, Wm, H, W, patch, inc_bits, nullptr, false);
-}
-
-int segvlad_incidence_centroids(segvlad_ctx* ctx, const uint8_t* masks, int S, int Hm, int Wm, int H, int W, int patch,
-                                uint64_t* inc_bits, double* centroids) {
-  CHECK_CTX();
-  CHECK_NO_OPEN_DESCRIBE("incidence_centroids");
-  return incidence_impl(ctx, masks, S, Hm, Wm, H, W, patch, inc_bits, centroids, true);
-}
-
-int segvlad_mask_centroids(segvlad_ctx* ctx, const uint8_t* masks, int S, int Hm, int Wm, double* centroids) {
-  CHECK_CTX();
-  if (S < 0 || Hm <= 0 || Wm <= 0) return ctx->fail(SEGVLAD_ERR_ARG, "mask_centroids: bad geometry");
-  if (S == 0) return SEGVLAD_OK;
-  if (!masks || !centroids) return ctx->fail(SEGVLAD_ERR_ARG, "mask_centroids: null pointer");
-  const void* dm;
-  void* dout;
-  SV_TRY(sv_in(ctx, masks, (size_t)S * Hm * Wm, &dm));
-  SV_TRY(sv_out(ctx, centroids, (size_t)S * 2 * sizeof(double), &dout));
-  SV_TRY(sv_launch_centroids(ctx, (const uint8_t*)dm, S, Hm, Wm, (double*)dout));
-  return sv_finish(ctx);
-}
-
-static int adjacency_impl(segvlad_ctx* ctx, const double* centroids, const int32_t* seg_offsets, int B, int order,
-                          uint8_t* adj_out, uint32_t* n_empty_out, uint8_t* img_flags_out) {
-  if (B < 0 || order < 1) return ctx->fail(SEGVLAD_ERR_ARG, "adjacency: need B>=0 and order>=1 (order 0 = pass adj=NULL)");
-  if (B == 0) return SEGVLAD_OK;
-  if (!centroids || !seg_offsets || !adj_out) return ctx->fail(SEGVLAD_ERR_ARG, "adjacency: null pointer");
-  if (sv_is_device_ptr(seg_offsets)) return ctx->fail(SEGVLAD_ERR_ARG, "adjacency: seg_offsets must be host memory");
-  int S_max = 0;
-  std::vector<int64_t> adj_off(B + 1, 0);
-  for (int b = 0; b < B; ++b) {
-    const int s = seg_offsets[b + 1] - seg_offsets[b];
-    if (s < 0) return ctx->fail(SEGVLAD_ERR_ARG, "adjacency: seg_offsets must be non-decreasing");
-    if (s > S_max) S_max = s;
-    adj_off[b + 1] = adj_off[b] + (int64_t)s * s;
-  }
-  const int S_tot = seg_offsets[B];
-  if (S_tot == 0) return SEGVLAD_OK;
-  const void* dc;
-  void* dout;
-  SV_TRY(sv_in(ctx, centroids, (size_t)S_tot * 2 * sizeof(double), &dc));
-  SV_TRY(sv_out(ctx, adj_out, (size_t)adj_off[B], &dout));
-  SV_HIP(ctx->s_segoff.reserve((size_t)(B + 1) * sizeof(int32_t)));
-  SV_HIP(ctx->s_adjoff.reserve((size_t)(B + 1) * sizeof(int64_t)));
-  SV_HIP(ctx->s_flag.reserve(64));
-  SV_HIP(hipMemcpyAsync(ctx->s_segoff.p, seg_offsets, (size_t)(B + 1) * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-  SV_HIP(hipMemcpyAsync(ctx->s_adjoff.p, adj_off.data(), (size_t)(B + 1) * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
-  uint32_t* bad = ctx->s_flag.as<uint32_t>() + 4;
-  SV_HIP(hipMemsetAsync(bad, 0, 4, ctx->stream));
-  void* dflags = nullptr;
-  if (img_flags_out) {
-    SV_TRY(sv_out(ctx, img_flags_out, (size_t)B, &dflags));
-    SV_HIP(hipMemsetAsync(dflags, 0, (size_t)B, ctx->stream));
-  }
-  {
-    StageScope sc(ctx, "adjacency");
-    SV_TRY(sv_launch_adjacency(ctx, (const double*)dc, ctx->s_segoff.as<int32_t>(), ctx->s_adjoff.as<int64_t>(), B, S_max, order,
-                               (uint8_t*)dout, bad, (uint8_t*)dflags));
-    sc.count();
-  }
-  if (n_empty_out) {
-    SV_HIP(hipMemcpyAsync(n_empty_out, bad, 4, hipMemcpyDeviceToHost, ctx->stream));
-    SV_HIP(hipStreamSynchronize(ctx->stream));
-  }
-  return sv_finish(ctx);
-}
-
-int segvlad_adjacency(segvlad_ctx* ctx, const double* centroids, const int32_t* seg_offsets, int B, int order,
-                      uint8_t* adj_out, uint32_t* n_empty_out) {
-  CHECK_CTX();
-  CHECK_NO_OPEN_DESCRIBE("adjacency");
-  return adjacency_impl(ctx, centroids, seg_offsets, B, order, adj_out, n_empty_out, nullptr);
-}
-
-int segvlad_adjacency_flagged(segvlad_ctx* ctx, const double* centroids, const int32_t* seg_offsets, int B, int order,
-                              uint8_t* adj_out, uint8_t* img_flags_out) {
-  CHECK_CTX();
-  CHECK_NO_OPEN_DESCRIBE("adjacency_flagged");
-  if (B > 0 && !img_flags_out) return ctx->fail(SEGVLAD_ERR_ARG, "adjacency_flagged: null img_flags_out");
-  return adjacency_impl(ctx, centroids, seg_offsets, B, order, adj_out, nullptr, img_flags_out);
-}
-
-// ---- segment VLAD -----------------------------------------------------------------------------------
-// pca_y != NULL: fused projection (segvlad_images_pca); out may then be NULL
-// The assignment pass on its own (segvlad_describe_begin): its outputs -- token-major copy, norms, labels -- stay in the
-// context's scratch for images_impl(phase = 2).
-static int assign_phase(segvlad_ctx* ctx, const float* tokens, int B, int N) {
-  if (ctx->K == 0) return ctx->fail(SEGVLAD_ERR_STATE, "images: call segvlad_set_vocab first");
-  if (B <= 0 || N <= 0 || !tokens) return ctx->fail(SEGVLAD_ERR_ARG, "images: B=%d N=%d", B, N);
-  const int D = ctx->D;
-  const void* d_tok;
-  SV_TRY(sv_in(ctx, tokens, (size_t)B * D * N * sizeof(float), &d_tok));
-  SV_HIP(ctx->s_xt.reserve((size_t)B * N * D * sizeof(float)));
-  SV_HIP(ctx->s_rnorm.reserve((size_t)B * N * sizeof(float)));
-  SV_HIP(ctx->s_labels.reserve((size_t)B * N));
-  StageScope sc(ctx, "assign");
-  SV_TRY(sv_launch_assign(ctx, (const float*)d_tok, B, N, ctx->s_xt.as<float>(), ctx->s_labels.as<uint8_t>(), ctx->s_rnorm.as<float>(), nullptr));
-  sc.count();
-  return SEGVLAD_OK;
-}
-
-// phase 0: everything.  2: from `prep` on, the assignment pass having run in an earlier call (assign_phase, same tokens) -- its
-// outputs live in the context's scratch, every reservation below is idempotent.
-static int images_impl(segvlad_ctx* ctx, const float* tokens, int B, int N, const uint64_t* inc_bits,
-                       const int32_t* seg_offsets, const uint8_t* adj, float* out, uint8_t* labels_out, float* gap_out,
-                       float* block_norms_out, float* pca_y, int l2norm, int phase = 0) {
-  if (ctx->K == 0) return ctx->fail(SEGVLAD_ERR_STATE, "images: call segvlad_set_vocab first");
-  if (B < 0 || N <= 0) return ctx->fail(SEGVLAD_ERR_ARG, "images: B=%d N=%d", B, N);
-  if (B == 0) return SEGVLAD_OK;
-  if (!tokens || !seg_offsets) return ctx->fail(SEGVLAD_ERR_ARG, "images: null pointer");
-  if (sv_is_device_ptr(seg_offsets)) return ctx->fail(SEGVLAD_ERR_ARG, "images: seg_offsets must be host memory");
-  const int K = ctx->K, D = ctx->D;
-  const int nw = (N + 63) / 64;
-  int S_max = 0;
-  std::vector<int64_t> adj_off(B + 1, 0);
-  if (seg_offsets[0] != 0) return ctx->fail(SEGVLAD_ERR_ARG, "images: seg_offsets[0] must be 0");
-  for (int b = 0; b < B; ++b) {
-    const int s = seg_offsets[b + 1] - seg_offsets[b];
-    if (s < 0) return ctx->fail(SEGVLAD_ERR_ARG, "images: seg_offsets must be non-decreasing");
-    if (s > S_max) S_max = s;
-    adj_off[b + 1] = adj_off[b] + (int64_t)s * s;
-  }
-  const int S_tot = seg_offsets[B];
-  if (S_tot > 0 && (!inc_bits || (!out && !pca_y))) return ctx->fail(SEGVLAD_ERR_ARG, "images: null inc_bits/out");
-  const int SC = S_max > 0 ? (S_max + 63) / 64 : 1;
-  // fused projection: the descriptor entries are <= 1 in magnitude by construction, so the fp16 split scale is known
-  // before the data exists (pca_apply has to measure max|x| first)
-  const bool fused = pca_y != nullptr && S_tot > 0;
-  float xscale = 1.f;
-  void* d_y = nullptr;
-  // "project then aggregate" (project_kernels.hip): when the descriptor itself is not asked for, project every token with
-  // its cluster's slice of the components and aggregate the segments in the P-dimensional space
-  // (auto: when it is the smaller product -- N D P per image against S K D P: 2.1 x fewer flops at S = 50, K = 64, N = 1530
-  //  -- and the batch holds >= 128 tokens per cluster on average: every cluster's rows are padded to whole 256-row GEMM
-  //  tiles, and below that the split-K descriptor GEMM is quicker -- 1 image: 0.62 against 0.84 ms, 16 images: 1.45 against 1.02)
-  const bool project = fused && out == nullptr && D % 32 == 0 && ctx->P % 4 == 0 && ctx->opt.pca_path != 1 &&
-                       (ctx->opt.pca_path == 2 ||
-                        ((double)S_tot * K >= 1.25 * (double)B * N && (double)B * N >= 128.0 * K));
-  int64_t rows_pad = 0;   // grouped token rows: every cluster's rows padded to whole 256-row GEMM tiles
-  if (fused && project) {
-    // residuals of unit tokens against the centres: |r| <= 1 + max|C|.  Centres that are means of unit tokens (every
-    // k-means vocabulary) give 2^13, like the planes form's data-derived scale; arbitrary centres (segvlad_set_vocab takes
-    // any) get the scale their magnitude needs instead of overflowing fp16 silently
-    {
-      int e;
-      const float bound = 1.f + ctx->vocab_maxabs;
-      if (!std::isfinite(bound)) return ctx->fail(SEGVLAD_ERR_ARG, "images_pca: the vocabulary holds a non-finite centre");
-      frexpf(bound, &e);
-      xscale = ldexpf(1.f, 14 - e);
-    }
-    rows_pad = (((int64_t)B * N + 255) & ~255ll) + 256ll * K;
-    SV_HIP(ctx->s_xh1.reserve((size_t)(rows_pad + 256) * D * 2));   // + one tile: the dummy row of sv_launch_token_norms
-    SV_HIP(ctx->s_xh2.reserve((size_t)(rows_pad + 256) * D * 2));
-    SV_HIP(ctx->s_pz.reserve((size_t)rows_pad * ctx->P * sizeof(float)));
-    SV_HIP(ctx->s_rowbase.reserve((size_t)B * K * sizeof(int32_t)));
-    SV_HIP(ctx->s_tilegrp.reserve((size_t)(rows_pad >> 8) * sizeof(int32_t)));
-    SV_HIP(ctx->s_phys.reserve((size_t)B * N * sizeof(int32_t)));
-    SV_HIP(ctx->s_covcnt.reserve((size_t)B * K * sizeof(int32_t)));
-    SV_HIP(ctx->s_bn.reserve((size_t)S_tot * K * sizeof(float)));
-    SV_TRY(sv_out(ctx, pca_y, (size_t)S_tot * ctx->P * sizeof(float), &d_y));
-    if (!ctx->pca_cproj_valid) {
-      SV_HIP(ctx->pca_cproj.reserve((size_t)ctx->P * sizeof(float)));
-      SV_TRY(sv_launch_project_consts(ctx, ctx->pca_comps.as<float>(), ctx->pca_mean.as<float>(), ctx->P, ctx->KD,
-                                      ctx->pca_cproj.as<float>()));
-      ctx->pca_cproj_valid = true;
-    }
-  } else if (fused) {
-    int e;
-    frexpf(1.f + ctx->pca_mean_maxabs, &e);
-    xscale = ldexpf(1.f, 14 - e);
-    SV_HIP(ctx->s_xh1.reserve((size_t)sv_x3_rows(S_tot) * ctx->KD * 2));   // blocked planes, rows padded to whole tiles
-    SV_HIP(ctx->s_xh2.reserve((size_t)sv_x3_rows(S_tot) * ctx->KD * 2));
-    SV_TRY(sv_out(ctx, pca_y, (size_t)S_tot * ctx->P * sizeof(float), &d_y));
-  }
-
-  const void *d_tok, *d_inc = nullptr, *d_adj = nullptr;
-  void *d_out = nullptr, *d_lab = nullptr, *d_gap = nullptr, *d_bn = nullptr;
-  SV_TRY(sv_in(ctx, tokens, (size_t)B * D * N * sizeof(float), &d_tok));
-  if (S_tot > 0) SV_TRY(sv_in(ctx, inc_bits, (size_t)S_tot * nw * 8, &d_inc));
-  if (adj && S_tot > 0) SV_TRY(sv_in(ctx, adj, (size_t)adj_off[B], &d_adj));
-  if (S_tot > 0 && out) SV_TRY(sv_out(ctx, out, (size_t)S_tot * K * D * sizeof(float), &d_out));
-  if (labels_out) SV_TRY(sv_out(ctx, labels_out, (size_t)B * N, &d_lab));
-  if (gap_out) SV_TRY(sv_out(ctx, gap_out, (size_t)B * N * sizeof(float), &d_gap));
-  if (block_norms_out && S_tot > 0) SV_TRY(sv_out(ctx, block_norms_out, (size_t)S_tot * K * sizeof(float), &d_bn));
-
-  SV_HIP(ctx->s_xt.reserve((size_t)B * N * D * sizeof(float)));
-  SV_HIP(ctx->s_rnorm.reserve((size_t)B * N * sizeof(float)));
-  if (!d_lab) {
-    SV_HIP(ctx->s_labels.reserve((size_t)B * N));
-    d_lab = ctx->s_labels.p;
-  }
-  SV_HIP(ctx->s_colmask.reserve((size_t)B * N * SC * 8));
-  SV_HIP(ctx->s_gscale.reserve((size_t)(S_tot + 1) * sizeof(float)));
-  SV_HIP(ctx->s_segoff.reserve((size_t)(B + 1) * sizeof(int32_t)));
-  SV_HIP(ctx->s_adjoff.reserve((size_t)(B + 1) * sizeof(int64_t)));
-  if (!ctx->mask_branch_on_side) {   // (segvlad_describe: the adjacency call on the side stream has put both in place)
-    SV_HIP(hipMemcpyAsync(ctx->s_segoff.p, seg_offsets, (size_t)(B + 1) * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-    SV_HIP(hipMemcpyAsync(ctx->s_adjoff.p, adj_off.data(), (size_t)(B + 1) * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
-  }
-  // (pageable sources: the runtime stages them before hipMemcpyAsync returns, so the local vector
-  //  and the caller's array may be reused as soon as this call returns)
-
-  if (phase != 2) {
-    StageScope sc(ctx, "assign");
-    SV_TRY(sv_launch_assign(ctx, (const float*)d_tok, B, N, ctx->s_xt.as<float>(), (uint8_t*)d_lab, ctx->s_rnorm.as<float>(),
-                            (float*)d_gap));
-    sc.count();
-  }
-  if (ctx->mask_branch_on_side) {   // segvlad_describe: incidence + centroids + adjacency ran beside the assignment pass
-    ctx->mask_branch_on_side = false;
-    SV_TRY(sv_join_side(ctx));
-  }
-  if (S_tot > 0) {
-    {
-      StageScope sc(ctx, "prep");
-      SV_TRY(sv_launch_prep(ctx, (const uint8_t*)d_lab, (const uint64_t*)d_inc, ctx->s_segoff.as<int32_t>(),
-                            ctx->s_adjoff.as<int64_t>(), (const uint8_t*)d_adj, B, N, K, S_max, SC,
-                            ctx->s_colmask.as<uint64_t>(), ctx->s_gscale.as<float>(), project ? ctx->s_phys.as<int32_t>() : nullptr,
-                            project ? ctx->s_covcnt.as<int32_t>() : nullptr, ctx->opt.cover_rows != 0 ? 1 : 0));
-      sc.count();
-    }
-    if (project) {
-      float* bn = d_bn ? (float*)d_bn : ctx->s_bn.as<float>();
-      {
-        StageScope sc(ctx, "aggregate");   // block norms + the normalised tokens' fp16 planes, grouped by cluster
-        SV_TRY(sv_launch_group_plan(ctx, ctx->s_covcnt.as<int32_t>(), B, K, ctx->s_rowbase.as<int32_t>(),
-                                    ctx->s_tilegrp.as<int32_t>(), (int)(rows_pad >> 8)));
-        SV_TRY(sv_launch_token_norms(ctx, ctx->s_xt.as<float>(), ctx->s_colmask.as<uint64_t>(), ctx->vocab.as<float>(), K, D,
-                                     ctx->s_segoff.as<int32_t>(), B, N, SC, bn, xscale, ctx->s_xh1.as<uint16_t>(),
-                                     ctx->s_xh2.as<uint16_t>(), ctx->s_rowbase.as<int32_t>(), ctx->opt.debug_search == 7 ? -rows_pad : rows_pad,
-                                     ctx->s_phys.as<int32_t>()));
-        sc.count(2);
-      }
-      StageScope sc(ctx, "pca");
-      SV_TRY(sv_launch_gemm_f16x3_grouped(ctx, ctx->s_xh1.as<uint16_t>(), ctx->s_xh2.as<uint16_t>(), ctx->pca_w1.as<uint16_t>(),
-                                          ctx->pca_w2.as<uint16_t>(), (int)rows_pad, ctx->P, D, K, ctx->s_tilegrp.as<int32_t>(),
-                                          1.f / (xscale * ctx->pca_w_scale), ctx->s_pz.as<float>()));
-      // |z_tp| = |W_k[p, :] . r_t| <= sqrt(D) max|W| (1 + max ||C_k||): a power-of-two scale that keeps z * zscale inside fp16.
-      // Both premises hold BY CONSTRUCTION, not by the caller's grace: r_t = x^_t - C_k with x^_t normalised by the kernels
-      // themselves (||x^_t|| = 1 whatever the caller's tokens are), and vocab_norm_max is set by the one function that can change the
-      // centres (segvlad_set_vocab); a bound that is not finite and positive switches the 16-bit form off (zscale = 0: fp32 MFMA)
-      // (the elementwise bound of W is the one pca_set left in pca_w_scale; typical |z| sits ~2^-7 below the bound, still
-      // 2^10 above the point where the low half of the split would go subnormal)
-      float zscale = 0.f;
-      if (ctx->pca_w_scale > 0.f) {
-        const float zb = std::sqrt((float)D) * (16384.f / ctx->pca_w_scale) * (1.f + ctx->vocab_norm_max);
-        if (std::isfinite(zb) && zb > 0.f) {
-          int e;
-          frexpf(zb, &e);
-          zscale = ldexpf(1.f, 14 - e);
-        }
-      }
-      SV_TRY(sv_launch_project_aggregate(ctx, ctx->s_pz.as<float>(), ctx->pca_cproj.as<float>(), bn, ctx->s_gscale.as<float>(),
-                                         ctx->s_colmask.as<uint64_t>(), ctx->s_laboff.as<int32_t>(), ctx->s_rowbase.as<int32_t>(),
-                                         ctx->s_phys.as<int32_t>(), ctx->s_segoff.as<int32_t>(), B, N, K, ctx->P, SC, S_max, ctx->pca_scale.as<float>(),
-                                         (float*)d_y, zscale));
-      sc.count(2);
-      if (l2norm) {
-        SV_TRY(sv_launch_normalize_rows(ctx, (const float*)d_y, S_tot, ctx->P, (float*)d_y));
-        sc.count();
-      }
-    } else {
-    {
-      StageScope sc(ctx, "aggregate");
-      SV_TRY(sv_launch_aggregate(ctx, ctx->s_xt.as<float>(), ctx->s_rnorm.as<float>(), (const uint8_t*)d_lab,
-                                 ctx->s_colmask.as<uint64_t>(), ctx->vocab.as<float>(), K, D, ctx->s_segoff.as<int32_t>(),
-                                 ctx->s_gscale.as<float>(), B, N, SC, (float*)d_out, (float*)d_bn,
-                                 fused ? ctx->pca_mean.as<float>() : nullptr, xscale,
-                                 fused ? ctx->s_xh1.as<uint16_t>() : nullptr, fused ? ctx->s_xh2.as<uint16_t>() : nullptr));
-      sc.count();
-    }
-    if (fused) {
-      StageScope sc(ctx, "pca");
-      SV_TRY(sv_launch_gemm_f16x3(ctx, ctx->s_xh1.as<uint16_t>(), ctx->s_xh2.as<uint16_t>(), ctx->pca_w1.as<uint16_t>(),
-                                  ctx->pca_w2.as<uint16_t>(), S_tot, ctx->P, ctx->KD, 1.f / (xscale * ctx->pca_w_scale),
-                                  ctx->pca_scale.as<float>(), (float*)d_y));
-      sc.count(2);
-      if (l2norm) {
-        SV_TRY(sv_launch_normalize_rows(ctx, (const float*)d_y, S_tot, ctx->P, (float*)d_y));
-        sc.count();
-      }
-    }
-    }
-  }
-  return sv_finish(ctx);
-}
-
-int segvlad_images(segvlad_ctx* ctx, const float* tokens, int B, int N, const uint64_t* inc_bits,
-                   const int32_t* seg_offsets, const uint8_t* adj, float* out, uint8_t* labels_out, float* gap_out,
-                   float* block_norms_out) {
-  CHECK_CTX();
-  CHECK_NO_OPEN_DESCRIBE("images");
-  return images_impl(ctx, tokens, B, N, inc_bits, seg_offsets, adj, out, labels_out, gap_out, block_norms_out, nullptr, 0);
-}
-
-static int images_pca_impl(segvlad_ctx* ctx, const float* tokens, int B, int N, const uint64_t* inc_bits,
-                           const int32_t* seg_offsets, const uint8_t* adj, float* y, int l2norm, float* desc_out,
-                           uint8_t* labels_out, float* gap_out, int phase = 0) {
-  if (ctx->P == 0) return ctx->fail(SEGVLAD_ERR_STATE, "images_pca: call segvlad_pca_set first");
-  if (ctx->K == 0) return ctx->fail(SEGVLAD_ERR_STATE, "images_pca: call segvlad_set_vocab first");
-  if (ctx->KD != ctx->K * ctx->D)
-    return ctx->fail(SEGVLAD_ERR_ARG, "images_pca: the PCA model expects %d-d rows, the vocabulary gives %d", ctx->KD,
-                     ctx->K * ctx->D);
-  if (B > 0 && seg_offsets && !sv_is_device_ptr(seg_offsets) && seg_offsets[B] > 0 && !y)
-    return ctx->fail(SEGVLAD_ERR_ARG, "images_pca: null y");
-  const bool x3 = ctx->pca_w_scale > 0.f && !ctx->opt.pca_fp32;
-  if (x3) return images_impl(ctx, tokens, B, N, inc_bits, seg_offsets, adj, desc_out, labels_out, gap_out, nullptr, y, l2norm, phase);
-  if (phase != 0) return ctx->fail(SEGVLAD_ERR_STATE, "describe: the split call needs the fp16x3 projection (pca_arith)");
-  // shapes the split GEMM does not take (or the fp32 knob): descriptor to HBM, then the plain projection
-  if (B <= 0 || !seg_offsets || sv_is_device_ptr(seg_offsets))
-    return images_impl(ctx, tokens, B, N, inc_bits, seg_offsets, adj, desc_out, labels_out, gap_out, nullptr, nullptr, 0);
-  const int S_tot = seg_offsets[B];
-  float* desc = desc_out;
-  if (!desc && S_tot > 0) {
-    SV_HIP(ctx->s_desc.reserve((size_t)S_tot * ctx->KD * sizeof(float)));
-    desc = ctx->s_desc.as<float>();
-  }
-  SV_TRY(images_impl(ctx, tokens, B, N, inc_bits, seg_offsets, adj, desc, labels_out, gap_out, nullptr, nullptr, 0));
-  return S_tot > 0 ? segvlad_pca_apply(ctx, desc, S_tot, y, l2norm) : SEGVLAD_OK;
-}
-
-int segvlad_images_pca(segvlad_ctx* ctx, const float* tokens, int B, int N, const uint64_t* inc_bits,
-                       const int32_t* seg_offsets, const uint8_t* adj, float* y, int l2norm, float* desc_out,
-                       uint8_t* labels_out, float* gap_out) {
-  CHECK_CTX();
-  CHECK_NO_OPEN_DESCRIBE("images_pca");
-  return images_pca_impl(ctx, tokens, B, N, inc_bits, seg_offsets, adj, y, l2norm, desc_out, labels_out, gap_out);
-}
-
-// ---- the whole describe stage of a batch in ONE call: masks + tokens -> (projected) segment descriptors ----------------------
-// place_rec_main.py:244-270 per image (masks -> adjacency -> seg_vlad_gpu_single) and per batch (apply_pca_transform_from_pkl).
-// The mask branch (incidence + centroids -> adjacency: two latency-bound launches, 0.34 ms per 200 images) does not depend on
-// the tokens, the assignment pass (0.95 ms, HBM-bound) does not depend on the masks: the former runs on the context's side
-// stream BESIDE the latter and is joined in front of `prep`, the first kernel that needs both.
-static int describe_begin_impl(segvlad_ctx* ctx, const uint8_t* masks, int Hm, int Wm, int H, int W, int patch, const float* tokens, int B,
-                               int N, const int32_t* seg_offsets, int order, uint64_t* inc_bits_out, double* centroids_out,
-                               uint8_t* adj_out, uint8_t* img_flags_out, bool pca) {
-  if (ctx->mask_branch_on_side) return ctx->fail(SEGVLAD_ERR_STATE, "describe_begin: the previous describe_begin has no describe_end yet");
-  if (B < 0 || order < 1) return ctx->fail(SEGVLAD_ERR_ARG, "describe: need B >= 0 and order >= 1");
-  if (!masks || !tokens || !seg_offsets || !inc_bits_out || !centroids_out || !adj_out || !img_flags_out)
-    return ctx->fail(SEGVLAD_ERR_ARG, "describe: null pointer");
-  if (sv_is_device_ptr(seg_offsets)) return ctx->fail(SEGVLAD_ERR_ARG, "describe: seg_offsets must be host memory");
-  const void* bulk[] = {masks, tokens, inc_bits_out, centroids_out, adj_out, img_flags_out};
-  for (const void* p : bulk)
-    if (!sv_is_device_ptr(p))
-      return ctx->fail(SEGVLAD_ERR_ARG, "describe: bulk pointers must be device memory (the separate entry points stage host data)");
-  if (patch <= 0 || N != (H / patch) * (W / patch))
-    return ctx->fail(SEGVLAD_ERR_ARG, "describe: N=%d tokens do not match the %dx%d image at patch %d", N, H, W, patch);
-  const int S_tot = B > 0 ? seg_offsets[B] : 0;
-  // Configurations the split call does not take are reported as SEGVLAD_ERR_LIMIT -- the code of "this entry point cannot, the
-  // separate ones (incidence_centroids -> adjacency -> images[_pca]) can": an empty batch, and a PCA model without the fp16x3
-  // form (option pca_arith=fp32, or K*D not a multiple of 32: images_pca then writes the descriptor and projects it with the
-  // plain GEMM).  ADVICE r05: both used to come back as ERR_ARG / ERR_STATE, which a caller cannot tell from misuse.
-  if (B == 0 || S_tot <= 0) return ctx->fail(SEGVLAD_ERR_LIMIT, "describe: no images / no segments (use the separate entry points)");
-  if (pca && ctx->P == 0) return ctx->fail(SEGVLAD_ERR_STATE, "describe: call segvlad_pca_set first");
-  if (pca && (ctx->pca_w_scale <= 0.f || ctx->opt.pca_fp32))
-    return ctx->fail(SEGVLAD_ERR_LIMIT, "describe: the split call needs the fp16x3 projection (pca_arith; K*D %% 32 == 0): use the separate entry points");
-  // pinned landing zone of the flags and the centroids (read by segvlad_describe_flags while the assignment pass runs)
-  const size_t need = (size_t)B + (size_t)S_tot * 16 + 64;
-  if (need > ctx->h_desc_cap) {
-    if (ctx->h_desc) SV_HIP(hipHostFree(ctx->h_desc));
-    ctx->h_desc = nullptr;
-    ctx->h_desc_cap = 0;
-    SV_HIP(hipHostMalloc(reinterpret_cast<void**>(&ctx->h_desc), need + need / 2, hipHostMallocDefault));
-    ctx->h_desc_cap = need + need / 2;
-  }
-  if (!ctx->ev_desc) SV_HIP(hipEventCreateWithFlags(&ctx->ev_desc, hipEventDisableTiming));
-  // stage "describe": from here to the end of segvlad_describe_end, as the context's stream sees it (the parts overlap)
-  ctx->desc_timer = nullptr;
-  if (ctx->profiling && !ctx->scope_mute) {
-    StageTimer* t = &ctx->timers["describe"];
-    if (t->used * 2 >= (int)t->ev.size()) {
-      hipEvent_t a = nullptr, b = nullptr;
-      (void)hipEventCreate(&a);
-      (void)hipEventCreate(&b);
-      t->ev.push_back(a);
-      t->ev.push_back(b);
-    }
-    ctx->desc_slot = t->used++;
-    ctx->desc_timer = t;
-    (void)hipEventRecord(t->ev[2 * ctx->desc_slot], ctx->stream);
-  }
-  // ---- mask branch on the side stream: the same two calls as the separate entry points, issued there -----------------------
-  SV_TRY(sv_fork_side(ctx));
-  hipStream_t main_stream = ctx->stream;
-  ctx->stream = ctx->side;
-  int rc = incidence_impl(ctx, masks, S_tot, Hm, Wm, H, W, patch, inc_bits_out, centroids_out, true);
-  if (rc == SEGVLAD_OK) rc = adjacency_impl(ctx, centroids_out, seg_offsets, B, order, adj_out, nullptr, img_flags_out);
-  if (rc == SEGVLAD_OK) {
-    hipError_t e = hipMemcpyAsync(ctx->h_desc, img_flags_out, (size_t)B, hipMemcpyDeviceToHost, ctx->side);
-    if (e == hipSuccess)
-      e = hipMemcpyAsync(ctx->h_desc + (((size_t)B + 63) & ~(size_t)63), centroids_out, (size_t)S_tot * 16, hipMemcpyDeviceToHost, ctx->side);
-    if (e == hipSuccess) e = hipEventRecord(ctx->ev_desc, ctx->side);
-    if (e != hipSuccess) rc = ctx->fail(SEGVLAD_ERR_HIP, "describe: flags read-back: %s", hipGetErrorString(e));
-  }
-  ctx->stream = main_stream;
-  auto close_timer = [&]() {
-    if (ctx->desc_timer) (void)hipEventRecord(ctx->desc_timer->ev[2 * ctx->desc_slot + 1], ctx->stream);
-    ctx->desc_timer = nullptr;
-  };
-  if (rc != SEGVLAD_OK) {
-    (void)sv_join_side(ctx);   // (nothing of the branch stays behind on the side stream unobserved)
-    close_timer();
-    return rc;
-  }
-  ctx->mask_branch_on_side = true;   // images_impl (phase 2 / 0) joins in front of prep
-  ctx->desc_B = B;
-  ctx->desc_S = S_tot;
-  // ---- main stream: the assignment pass -------------------------------------------------------------------------------------------
-  rc = assign_phase(ctx, tokens, B, N);
-  if (rc != SEGVLAD_OK) {
-    ctx->mask_branch_on_side = false;
-    (void)sv_join_side(ctx);
-    close_timer();
-  }
-  return rc;
-}
-
-int segvlad_describe_begin(segvlad_ctx* ctx, const uint8_t* masks, int Hm, int Wm, int H, int W, int patch, const float* tokens, int B,
-                           int N, const int32_t* seg_offsets, int order, uint64_t* inc_bits_out, double* centroids_out, uint8_t* adj_out,
-                           uint8_t* img_flags_out, int pca) {
-  CHECK_CTX();
-  return describe_begin_impl(ctx, masks, Hm, Wm, H, W, patch, tokens, B, N, seg_offsets, order, inc_bits_out, centroids_out, adj_out,
-                             img_flags_out, pca != 0);
-}
-
-int segvlad_describe_flags(segvlad_ctx* ctx, uint8_t* flags_host, double* centroids_host) {
-  CHECK_CTX();
-  if (!ctx->mask_branch_on_side) return ctx->fail(SEGVLAD_ERR_STATE, "describe_flags: call segvlad_describe_begin first");
-  if (!flags_host) return ctx->fail(SEGVLAD_ERR_ARG, "describe_flags: null pointer");
-  SV_HIP(hipEventSynchronize(ctx->ev_desc));   // the MASK BRANCH only: the assignment pass on the main stream keeps running
-  memcpy(flags_host, ctx->h_desc, (size_t)ctx->desc_B);
-  if (centroids_host) memcpy(centroids_host, ctx->h_desc + (((size_t)ctx->desc_B + 63) & ~(size_t)63), (size_t)ctx->desc_S * 16);
-  return SEGVLAD_OK;
-}
-
-int segvlad_describe_end(segvlad_ctx* ctx, const float* tokens, int B, int N, const uint64_t* inc_bits, const int32_t* seg_offsets,
-                         uint8_t* adj, int n_patch, const int32_t* patch_images, const uint8_t* patch_blocks, float* desc_out, float* y,
-                         int l2norm) {
-  CHECK_CTX();
-  if (!ctx->mask_branch_on_side) return ctx->fail(SEGVLAD_ERR_STATE, "describe_end: call segvlad_describe_begin first");
-  auto bail = [&](int rc) {   // leaves the context usable: the mask branch is joined, the split call is over
-    if (ctx->desc_timer) {
-      (void)hipEventRecord(ctx->desc_timer->ev[2 * ctx->desc_slot + 1], ctx->stream);
-      ctx->desc_timer = nullptr;
-    }
-    ctx->mask_branch_on_side = false;
-    (void)sv_join_side(ctx);
-    return rc;
-  };
-  if (!tokens || !inc_bits || !seg_offsets || !adj || (!desc_out && !y) || B != ctx->desc_B || seg_offsets[B] != ctx->desc_S ||
-      n_patch < 0 || (n_patch > 0 && (!patch_images || !patch_blocks)))
-    return bail(ctx->fail(SEGVLAD_ERR_ARG, "describe_end: arguments do not match segvlad_describe_begin's"));
-  if (n_patch > 0) {
-    // adjacency blocks the caller recomputed on the host (Qhull, for images whose centroids are in a non-generic configuration):
-    // written over the device kernel's behind the mask branch, in front of prep
-    if (sv_join_side(ctx) != SEGVLAD_OK) return bail(SEGVLAD_ERR_HIP);
-    std::vector<int64_t> aoff((size_t)B + 1, 0);
-    for (int b = 0; b < B; ++b) {
-      const int64_t sb = seg_offsets[b + 1] - seg_offsets[b];
-      aoff[(size_t)b + 1] = aoff[(size_t)b] + sb * sb;
-    }
-    size_t src = 0;
-    for (int j = 0; j < n_patch; ++j) {
-      const int b = patch_images[j];
-      if (b < 0 || b >= B) return bail(ctx->fail(SEGVLAD_ERR_ARG, "describe_end: patch image %d out of range", b));
-      const size_t bytes = (size_t)(aoff[(size_t)b + 1] - aoff[(size_t)b]);
-      const hipError_t e = hipMemcpyAsync(adj + aoff[(size_t)b], patch_blocks + src, bytes, hipMemcpyHostToDevice, ctx->stream);
-      if (e != hipSuccess) return bail(ctx->fail(SEGVLAD_ERR_HIP, "describe_end: adjacency patch: %s", hipGetErrorString(e)));
-      src += bytes;
-    }
-  }
-  const int rc = y ? images_pca_impl(ctx, tokens, B, N, inc_bits, seg_offsets, adj, y, l2norm, desc_out, nullptr, nullptr, 2)
-                   : images_impl(ctx, tokens, B, N, inc_bits, seg_offsets, adj, desc_out, nullptr, nullptr, nullptr, nullptr, 0, 2);
-  if (ctx->desc_timer) {
-    (void)hipEventRecord(ctx->desc_timer->ev[2 * ctx->desc_slot + 1], ctx->stream);
-    ctx->desc_timer->launches += 1;
-    ctx->desc_timer = nullptr;
-  }
-  if (ctx->mask_branch_on_side) return bail(rc);   // an early return in front of the join
-  return rc;
-}
-
-int segvlad_describe(segvlad_ctx* ctx, const uint8_t* masks, int Hm, int Wm, int H, int W, int patch, const float* tokens, int B, int N,
-                     const int32_t* seg_offsets, int order, uint64_t* inc_bits_out, double* centroids_out, uint8_t* adj_out,
-                     uint8_t* img_flags_out, float* desc_out, float* y, int l2norm) {
-  CHECK_CTX();
-  if (!desc_out && !y) return ctx->fail(SEGVLAD_ERR_ARG, "describe: null pointer");
-  if ((desc_out && !sv_is_device_ptr(desc_out)) || (y && !sv_is_device_ptr(y)))
-    return ctx->fail(SEGVLAD_ERR_ARG, "describe: bulk pointers must be device memory (the separate entry points stage host data)");
-  SV_TRY(describe_begin_impl(ctx, masks, Hm, Wm, H, W, patch, tokens, B, N, seg_offsets, order, inc_bits_out, centroids_out, adj_out,
-                             img_flags_out, y != nullptr));
-  return segvlad_describe_end(ctx, tokens, B, N, inc_bits_out, seg_offsets, adj_out, 0, nullptr, nullptr, desc_out, y, l2norm);
-}
-
-// ---- vocabulary k-means: one Lloyd half-step over a batch of images (utilities.py:749-791, vlad_c_centers_pt_gen.py:86-158) -------
-int segvlad_kmeans_step(segvlad_ctx* ctx, const float* tokens, int B, int N, double* sums, int64_t* counts, uint8_t* labels_out) {
-  CHECK_CTX();
-  CHECK_NO_OPEN_DESCRIBE("kmeans_step");
-  if (ctx->K == 0) return ctx->fail(SEGVLAD_ERR_STATE, "kmeans_step: call segvlad_set_vocab with the current centres first");
-  if (B < 0 || N <= 0) return ctx->fail(SEGVLAD_ERR_ARG, "kmeans_step: B=%d N=%d", B, N);
-  if (B == 0) return SEGVLAD_OK;
-  if (!tokens || !sums || !counts) return ctx->fail(SEGVLAD_ERR_ARG, "kmeans_step: null pointer");
-  const int K = ctx->K, D = ctx->D;
-  void *d_sums, *d_cnt, *d_lab = nullptr;
-  if (!sv_is_device_ptr(sums) || !sv_is_device_ptr(counts))
-    return ctx->fail(SEGVLAD_ERR_ARG, "kmeans_step: sums / counts are accumulated into and must be device memory");
-  d_sums = sums;
-  d_cnt = counts;
-  SV_TRY(assign_phase(ctx, tokens, B, N));   // labels (cosine arg-max against the normalised centres, first maximum), Xt, 1 / ||x||
-  {
-    StageScope sc(ctx, "kmeans");
-    SV_TRY(sv_launch_centroid_sums(ctx, ctx->s_xt.as<float>(), ctx->s_rnorm.as<float>(), ctx->s_labels.as<uint8_t>(), B, N, D, K,
-                                   (double*)d_sums, (int64_t*)d_cnt));
-    sc.count(2);
-  }
-  if (labels_out) {
-    SV_TRY(sv_out(ctx, labels_out, (size_t)B * N, &d_lab));
-    SV_HIP(hipMemcpyAsync(d_lab, ctx->s_labels.p, (size_t)B * N, hipMemcpyDeviceToDevice, ctx->stream));
-  }
-  return sv_finish(ctx);
-}
-
-// ---- K-parametric aggregation of given residuals + labels (vlad_matmuls_per_cluster) --------------------
-__global__ void fill_ones_kernel(float* p, int n) {
-  const int j = blockIdx.x * blockDim.x + threadIdx.x;
-  if (j < n) p[j] = 1.f;
-}
-
-int segvlad_cluster_aggregate(segvlad_ctx* ctx, int num_c, const float* res, const uint8_t* labels, int N, int D,
-                              const uint64_t* inc_bits, int S, const uint8_t* adj, float* out) {
-  CHECK_CTX();
-  CHECK_NO_OPEN_DESCRIBE("cluster_aggregate");
-  if (num_c <= 0 || num_c > 256 || N <= 0 || D <= 0 || (D % 4) || S < 0)
-    return ctx->fail(SEGVLAD_ERR_ARG, "cluster_aggregate: bad shape num_c=%d N=%d D=%d S=%d", num_c, N, D, S);
-  if (S == 0) return SEGVLAD_OK;
-  if (!res || !labels || !inc_bits || !out) return ctx->fail(SEGVLAD_ERR_ARG, "cluster_aggregate: null pointer");
-  const int nw = (N + 63) / 64, SC = (S + 63) / 64;
-  const void *d_res, *d_lab, *d_inc, *d_adj = nullptr;
-  void* d_out;
-  SV_TRY(sv_in(ctx, res, (size_t)N * D * 4, &d_res));
-  SV_TRY(sv_in(ctx, labels, (size_t)N, &d_lab));
-  SV_TRY(sv_in(ctx, inc_bits, (size_t)S * nw * 8, &d_inc));
-  if (adj) SV_TRY(sv_in(ctx, adj, (size_t)S * S, &d_adj));
-  SV_TRY(sv_out(ctx, out, (size_t)S * num_c * D * 4, &d_out));
-  SV_HIP(ctx->s_rnorm.reserve((size_t)N * 4));
-  SV_HIP(ctx->s_colmask.reserve((size_t)N * SC * 8));
-  SV_HIP(ctx->s_gscale.reserve((size_t)(S + 1) * 4));
-  SV_HIP(ctx->s_segoff.reserve(2 * sizeof(int32_t)));
-  SV_HIP(ctx->s_adjoff.reserve(2 * sizeof(int64_t)));
-  const int32_t so[2] = {0, S};
-  const int64_t ao[2] = {0, (int64_t)S * S};
-  SV_HIP(hipMemcpyAsync(ctx->s_segoff.p, so, sizeof(so), hipMemcpyHostToDevice, ctx->stream));
-  SV_HIP(hipMemcpyAsync(ctx->s_adjoff.p, ao, sizeof(ao), hipMemcpyHostToDevice, ctx->stream));
-  hipLaunchKernelGGL(fill_ones_kernel, dim3((N + 255) / 256), dim3(256), 0, ctx->stream, ctx->s_rnorm.as<float>(), N);
-  SV_TRY(sv_launch_prep(ctx, (const uint8_t*)d_lab, (const uint64_t*)d_inc, ctx->s_segoff.as<int32_t>(),
-                        ctx->s_adjoff.as<int64_t>(), (const uint8_t*)d_adj, 1, N, num_c, S, SC, ctx->s_colmask.as<uint64_t>(),
-                        ctx->s_gscale.as<float>(), nullptr, nullptr, 0));
-  SV_TRY(sv_launch_aggregate(ctx, (const float*)d_res, ctx->s_rnorm.as<float>(), (const uint8_t*)d_lab,
-                             ctx->s_colmask.as<uint64_t>(), nullptr, num_c, D, ctx->s_segoff.as<int32_t>(),
-                             ctx->s_gscale.as<float>(), 1, N, SC, (float*)d_out, nullptr));
-  SV_HIP(hipStreamSynchronize(ctx->stream));  // so[] / ao[] live on this frame
   return sv_finish(ctx);
 }
 
@@ -1069,9 +471,7 @@ int segvlad_pca_set(segvlad_ctx* ctx, const float* mean, const float* comps, con
     SV_TRY(sv_maxabs(ctx, ctx->pca_comps.as<float>(), (int64_t)P * KD, &wmax));
     SV_TRY(sv_maxabs(ctx, ctx->pca_mean.as<float>(), KD, &mmax));
     if (wmax > 0.f && std::isfinite(wmax)) {
-      int e;
-      frexpf(wmax, &e);
-      ctx->pca_w_scale = ldexpf(1.f, 14 - e);
+      ctx->pca_w_scale = sv_fp16_scale(wmax);
       ctx->pca_mean_maxabs = mmax;
       SV_HIP(ctx->pca_w1.reserve((size_t)sv_x3_rows(P) * KD * 2));   // blocked planes, rows padded to whole tiles
       SV_HIP(ctx->pca_w2.reserve((size_t)sv_x3_rows(P) * KD * 2));
@@ -1105,11 +505,7 @@ int segvlad_pca_apply(segvlad_ctx* ctx, const float* X, int n, float* Y, int l2n
     float xmax = 0.f;
     SV_TRY(sv_maxabs(ctx, (const float*)dx, (int64_t)n * ctx->KD, &xmax, /*finite_only=*/true));
     const float bound = xmax + ctx->pca_mean_maxabs;
-    if (bound > 0.f && std::isfinite(bound)) {
-      int e;
-      frexpf(bound, &e);
-      xscale = ldexpf(1.f, 14 - e);
-    }
+    if (bound > 0.f && std::isfinite(bound)) xscale = sv_fp16_scale(bound);
     SV_HIP(ctx->s_xh1.reserve((size_t)sv_x3_rows(n) * ctx->KD * 2));
     SV_HIP(ctx->s_xh2.reserve((size_t)sv_x3_rows(n) * ctx->KD * 2));
   }

@@ -1,6 +1,7 @@
 // Context, scratch management and launch declarations shared by the SegVLAD HIP translation units.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <math.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
@@ -67,6 +68,12 @@ inline size_t sv_x3_off(int64_t row, int64_t k, int64_t Kd) {
          (size_t)((((k & 31) >> 3) ^ sv_x3_swz(row)) << 3) + (size_t)(k & 7);
 }
 inline int64_t sv_x3_rows(int64_t n) { return (n + 255) & ~255ll; }
+// the power-of-two scale of an fp16 split: 2^(14 - e) for a finite bound > 0 in [2^(e-1), 2^e), so that bound * scale < 2^15
+inline float sv_fp16_scale(float bound) {
+  int e;
+  frexpf(bound, &e);
+  return ldexpf(1.f, 14 - e);
+}
 
 // grow-only device buffer
 //
@@ -246,6 +253,15 @@ struct SvSearchStats {
   int64_t carry_rows = 0;       // database rows the last filter level did not compute again (taken over from the stride-16 level: level_carry)
 };
 
+// An open describe (describe.hip): set by segvlad_describe_begin, cleared by close_describe -- the one way out of begin, end and cancel
+struct OpenDescribe {
+  bool open = false;           // the context's per-batch describe scratch belongs to this batch: other describe-side entry points refuse
+  bool side_pending = false;   // the mask branch on the side stream has not been joined yet (read by join_mask_branch alone)
+  int B = 0, S_tot = 0;        // what segvlad_describe_end's arguments must match
+  StageTimer* timer = nullptr; // the "describe" stage's open event pair (null: profiling off) and its slot
+  int slot = 0;
+};
+
 struct segvlad_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -258,10 +274,7 @@ struct segvlad_ctx {
   unsigned char* h_desc = nullptr;    // pinned: the per-image flags and the centroids of a segvlad_describe_begin
   size_t h_desc_cap = 0;
   hipEvent_t ev_desc = nullptr;       // behind their copies on the side stream
-  int desc_B = 0, desc_S = 0;
-  StageTimer* desc_timer = nullptr;   // the "describe" stage's open event pair (begin -> end)
-  int desc_slot = 0;
-  bool mask_branch_on_side = false;   // segvlad_describe: incidence / adjacency are in flight on `side`; images_impl joins before prep
+  OpenDescribe desc;                  // describe.hip: the batch between segvlad_describe_begin and segvlad_describe_end
   char err[512] = {0};
   bool profiling = false;
   bool scope_mute = false;   // set while a redo / fallback pass runs: its inner stages are part of "knn_redo" / "knn_fallback" only
@@ -392,18 +405,26 @@ int sv_finish(segvlad_ctx* ctx);
 int sv_guard_check(segvlad_ctx* ctx);
 int sv_fork_side(segvlad_ctx* ctx);   // side stream waits for everything enqueued on `stream` so far
 int sv_join_side(segvlad_ctx* ctx);   // `stream` waits for everything enqueued on the side stream so far
+struct StreamSwitch {   // ctx->stream replaced for a scope: a branch is issued on the side stream by the code that serves the main one
+  segvlad_ctx* ctx;
+  hipStream_t saved;
+  StreamSwitch(segvlad_ctx* c, hipStream_t s) : ctx(c), saved(c->stream) { ctx->stream = s; }
+  ~StreamSwitch() { ctx->stream = saved; }
+};
 void sv_begin(segvlad_ctx* ctx);
 // first line of every entry point that takes a context
 #define CHECK_CTX()                 \
   if (!ctx) return SEGVLAD_ERR_ARG; \
   sv_begin(ctx)
 
+// a fresh (start, stop) event pair of stage `name`, its start recorded on the context's stream; null when profiling is off or muted
+StageTimer* sv_stage_open(segvlad_ctx* ctx, const char* name, int* slot);
 struct StageScope {
   segvlad_ctx* ctx;
   StageTimer* t = nullptr;
   int slot = 0;
-  StageScope(segvlad_ctx* c, const char* name);
-  ~StageScope();
+  StageScope(segvlad_ctx* c, const char* name) : ctx(c) { t = sv_stage_open(c, name, &slot); }
+  ~StageScope() { if (t) (void)hipEventRecord(t->ev[2 * slot + 1], ctx->stream); }
   void count(int n = 1) { if (t) t->launches += n; }
 };
 

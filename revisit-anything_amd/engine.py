@@ -581,50 +581,9 @@ class SegVLADEngine:
             res["gap"] = gap
         return res
 
-    def describe(self, masks, tokens, seg_offsets: Sequence[int], H: int, W: int, patch: int = 14, order: int = 3, pca: bool = True,
-                 l2norm: bool = True, want_desc: bool = False) -> dict:
-        """segvlad_describe: the describe stage of a batch in one call -- incidence + centroids + device adjacency on the
-        context's side stream beside the token-assignment pass, then seg-VLAD (+ PCA).  Device tensors only.  Returns
-        dict(out=[S_tot,P] or [S_tot,K*D], bits, cent, adj, flags [B] uint8 on the device: bit 0 empty mask, bit 1 non-generic
-        centroids -- pipeline.py patches flagged images with Qhull), desc? with pca and want_desc."""
-        if self.K == 0:
-            raise SegVLADError("describe: set_vocab first")
-        if pca and self.P == 0:
-            raise SegVLADError("describe: pca_set first")
-        m = masks if masks.dtype == torch.uint8 else masks.to(torch.uint8)
-        m = m.contiguous()
-        t = tokens.to(torch.float32).contiguous()
-        if t.ndim == 2:
-            t = t[None]
-        B, D, N = t.shape
-        if D != self.D:
-            raise ValueError(f"tokens have D={D}, vocabulary has D={self.D}")
-        so = np.ascontiguousarray(seg_offsets, dtype=np.int32)
-        assert so.shape == (B + 1,)
-        S_tot = int(so[-1])
-        assert m.shape[0] == S_tot
-        sizes = (so[1:] - so[:-1]).astype(np.int64)
-        bits = self._empty((S_tot, (N + 63) // 64), torch.int64)
-        cent = self._empty((S_tot, 2), torch.float64)
-        adj = self._empty((int((sizes * sizes).sum()),), torch.uint8)
-        flags = self._empty((B,), torch.uint8)
-        y = self._empty((S_tot, self.P), torch.float32) if pca else None
-        desc = self._empty((S_tot, self.K * self.D), torch.float32) if (want_desc or not pca) else None
-        self._stream()
-        self._check(self.lib.segvlad_describe(self._h, _ptr(m), int(m.shape[1]), int(m.shape[2]), int(H), int(W), int(patch), _ptr(t), B, N,
-                                              _ptr(so), int(order), _ptr(bits), _ptr(cent), _ptr(adj), _ptr(flags), _ptr(desc), _ptr(y),
-                                              int(bool(l2norm))), "describe")
-        self._keep = [m, t]
-        res = {"out": y if pca else desc, "bits": bits, "cent": cent, "adj": adj, "flags": flags}
-        if pca and want_desc:
-            res["desc"] = desc
-        return res
-
-    # ---- the same stage as begin / flags / end: the caller patches flagged images with Qhull WHILE the assignment pass runs ----
-    def describe_begin(self, masks, tokens, seg_offsets: Sequence[int], H: int, W: int, patch: int = 14, order: int = 3,
-                       pca: bool = True) -> dict:
-        """segvlad_describe_begin: enqueues the mask branch (side stream) and the assignment pass, returns the handle
-        describe_flags / describe_end take (it owns the intermediates: bits, cent, adj, flags)."""
+    def _describe_operands(self, masks, tokens, seg_offsets, pca: bool) -> dict:
+        """The checks of describe / describe_begin, their operands as the C-ABI takes them and the mask branch's outputs (bits, cent,
+        adj, flags): the handle of a describe_begin."""
         if self.K == 0:
             raise SegVLADError("describe: set_vocab first")
         if pca and self.P == 0:
@@ -640,12 +599,42 @@ class SegVLADEngine:
         assert so.shape == (B + 1,) and m.shape[0] == int(so[-1])
         S_tot = int(so[-1])
         sizes = (so[1:] - so[:-1]).astype(np.int64)
-        h = {"m": m, "t": t, "so": so, "B": B, "N": N, "S_tot": S_tot, "pca": bool(pca), "order": int(order),
-             "bits": self._empty((S_tot, (N + 63) // 64), torch.int64), "cent": self._empty((S_tot, 2), torch.float64),
-             "adj": self._empty((int((sizes * sizes).sum()),), torch.uint8), "flags": self._empty((B,), torch.uint8)}
+        return {"m": m, "t": t, "so": so, "B": B, "N": N, "S_tot": S_tot, "pca": bool(pca),
+                "bits": self._empty((S_tot, (N + 63) // 64), torch.int64), "cent": self._empty((S_tot, 2), torch.float64),
+                "adj": self._empty((int((sizes * sizes).sum()),), torch.uint8), "flags": self._empty((B,), torch.uint8)}
+
+    def describe(self, masks, tokens, seg_offsets: Sequence[int], H: int, W: int, patch: int = 14, order: int = 3, pca: bool = True,
+                 l2norm: bool = True, want_desc: bool = False) -> dict:
+        """segvlad_describe: the describe stage of a batch in one call -- incidence + centroids + device adjacency on the
+        context's side stream beside the token-assignment pass, then seg-VLAD (+ PCA).  Device tensors only.  Returns
+        dict(out=[S_tot,P] or [S_tot,K*D], bits, cent, adj, flags [B] uint8 on the device: bit 0 empty mask, bit 1 non-generic
+        centroids -- pipeline.py patches flagged images with Qhull), desc? with pca and want_desc."""
+        h = self._describe_operands(masks, tokens, seg_offsets, pca)
+        m, t, S_tot = h["m"], h["t"], h["S_tot"]
+        bits, cent, adj, flags = h["bits"], h["cent"], h["adj"], h["flags"]
+        y = self._empty((S_tot, self.P), torch.float32) if pca else None
+        desc = self._empty((S_tot, self.K * self.D), torch.float32) if (want_desc or not pca) else None
+        self._stream()
+        self._check(self.lib.segvlad_describe(self._h, _ptr(m), int(m.shape[1]), int(m.shape[2]), int(H), int(W), int(patch), _ptr(t), h["B"],
+                                              h["N"], _ptr(h["so"]), int(order), _ptr(bits), _ptr(cent), _ptr(adj), _ptr(flags), _ptr(desc),
+                                              _ptr(y), int(bool(l2norm))), "describe")
+        self._keep = [m, t]
+        res = {"out": y if pca else desc, "bits": bits, "cent": cent, "adj": adj, "flags": flags}
+        if pca and want_desc:
+            res["desc"] = desc
+        return res
+
+    # ---- the same stage as begin / flags / end: the caller patches flagged images with Qhull WHILE the assignment pass runs ----
+    def describe_begin(self, masks, tokens, seg_offsets: Sequence[int], H: int, W: int, patch: int = 14, order: int = 3,
+                       pca: bool = True) -> dict:
+        """segvlad_describe_begin: enqueues the mask branch (side stream) and the assignment pass, returns the handle
+        describe_flags / describe_end take (it owns the intermediates: bits, cent, adj, flags)."""
+        h = self._describe_operands(masks, tokens, seg_offsets, pca)
+        h["order"] = int(order)
+        m, t = h["m"], h["t"]
         self._stream()
         self._check(self.lib.segvlad_describe_begin(self._h, _ptr(m), int(m.shape[1]), int(m.shape[2]), int(H), int(W), int(patch), _ptr(t),
-                                                    B, N, _ptr(so), int(order), _ptr(h["bits"]), _ptr(h["cent"]), _ptr(h["adj"]),
+                                                    h["B"], h["N"], _ptr(h["so"]), int(order), _ptr(h["bits"]), _ptr(h["cent"]), _ptr(h["adj"]),
                                                     _ptr(h["flags"]), int(bool(pca))), "describe_begin")
         return h
 

@@ -31,11 +31,14 @@ def _batch(C, B, S_list, H, W, seed):
     return torch.from_numpy(tok).cuda(), torch.from_numpy(masks.astype(np.uint8)).cuda(), off
 
 
-@pytest.mark.parametrize("pca", [True, False])
-def test_describe_equals_the_separate_calls_bit_for_bit(pca):
+# (auto never picks the project form at these sizes: the begin / end split of that form is only reached by the option;
+#  [70, 6, 9]: one image with more than 64 segments -- two words of segment columns per token -- next to small ones)
+@pytest.mark.parametrize("pca,pca_path", [(True, "auto"), (True, "planes"), (True, "project"), (False, "auto")])
+def test_describe_equals_the_separate_calls_bit_for_bit(pca, pca_path):
     eng, C = _setup()
+    eng.set_option("pca_path", pca_path)
     H, W = 112, 140
-    for rep, S_list in enumerate(([12, 7, 15, 9], [5, 5, 5, 5, 5, 5], [20])):
+    for rep, S_list in enumerate(([12, 7, 15, 9], [5, 5, 5, 5, 5, 5], [20], [70, 6, 9])):
         tok, masks, off = _batch(C, len(S_list), S_list, H, W, seed=10 * rep)
         bits, cent = eng.incidence_centroids(masks, H, W, 14)
         adj, flags = eng.adjacency_flagged(cent, off, 3, device_flags=True)
@@ -171,4 +174,83 @@ def test_other_entry_points_refuse_while_a_describe_is_open():
         assert ei.value.code == SEGVLAD_ERR_STATE
     assert torch.equal(eng.describe_end(h, None, None, l2norm=True)["out"], ref)
     assert torch.equal(eng.seg_vlad_pca(tok, bits, off, adj, l2norm=True)["out"], ref)     # and the context is free again
+    eng.close()
+
+
+def _launches(eng, stages):
+    """declared launches per stage since the last profile_reset (a stage that did not run: 0)"""
+    from revisit_anything_amd._lib import SEGVLAD_ERR_STATE, SegVLADError
+
+    out = {}
+    for st in stages:
+        try:
+            out[st] = eng.stage_ms(st)[1]
+        except SegVLADError as e:
+            assert e.code == SEGVLAD_ERR_STATE
+            out[st] = 0
+    return out
+
+
+_STAGES = ("incidence", "adjacency", "describe", "assign", "prep", "aggregate", "pca")
+
+
+@pytest.mark.parametrize("form", ["descriptor", "planes", "project", "fp32"])
+def test_declared_launch_counts_per_form(form):
+    """What bench.py reports as launches_per_step: every form of the stage declares the launches it issues, through the
+    separate entry points and through segvlad_describe (which adds the mask branch and its own pair)."""
+    eng, C = _setup(seed=7)
+    if form in ("planes", "project"):
+        eng.set_option("pca_path", form)
+    if form == "fp32":
+        eng.set_option("pca_arith", "fp32")
+    H, W = 112, 140
+    tok, masks, off = _batch(C, 3, [7, 11, 5], H, W, seed=41)
+    bits, cent = eng.incidence_centroids(masks, H, W, 14)
+    adj, _ = eng.adjacency_flagged(cent, off, 3, device_flags=True)
+    eng.set_profiling(True)
+    for l2 in ((False,) if form == "descriptor" else (False, True)):
+        want = {"incidence": 0, "adjacency": 0, "describe": 0, "assign": 1, "prep": 1, "aggregate": 2 if form == "project" else 1,
+                "pca": {"descriptor": 0, "planes": 2 + l2, "project": 2 + l2, "fp32": 1 + l2}[form]}
+        eng.profile_reset()
+        if form == "descriptor":
+            eng.seg_vlad(tok, bits, off, adj)
+        else:
+            eng.seg_vlad_pca(tok, bits, off, adj, l2norm=l2)
+        got = _launches(eng, _STAGES)
+        print(form, "l2norm", l2, "separate", got)
+        assert got == want
+        if form == "fp32":
+            continue          # (segvlad_describe does not take the plain projection: SEGVLAD_ERR_LIMIT, tested above)
+        eng.profile_reset()
+        eng.describe(masks, tok, off, H, W, 14, 3, pca=form != "descriptor", l2norm=l2)
+        got = _launches(eng, _STAGES)
+        print(form, "l2norm", l2, "describe", got)
+        assert got == dict(want, incidence=1, adjacency=1, describe=1)
+    eng.close()
+
+
+def test_a_closed_describe_leaves_the_context_as_it_found_it():
+    """Every way out of an open describe -- an end whose arguments do not match the begin's, a cancel (three in a row) -- closes it:
+    afterwards the separate entry points and a fresh segvlad_describe both give the reference rows bit for bit."""
+    from revisit_anything_amd._lib import SEGVLAD_ERR_ARG, SegVLADError
+
+    eng, C = _setup(seed=8)
+    H, W = 112, 140
+    tok, masks, off = _batch(C, 4, [8, 12, 5, 9], H, W, seed=53)
+    bits, cent = eng.incidence_centroids(masks, H, W, 14)
+    adj, _ = eng.adjacency_flagged(cent, off, 3, device_flags=True)
+    ref = eng.seg_vlad_pca(tok, bits, off, adj, l2norm=True)["out"].clone()
+
+    def check():
+        assert torch.equal(eng.seg_vlad_pca(tok, bits, off, adj, l2norm=True)["out"], ref)
+        assert torch.equal(eng.describe(masks, tok, off, H, W, 14, 3, pca=True, l2norm=True)["out"], ref)
+
+    h = eng.describe_begin(masks, tok, off, H, W, 14, 3, pca=True)
+    with pytest.raises(SegVLADError) as ei:
+        eng.describe_end(dict(h, B=h["B"] - 1), None, None, l2norm=True)        # B does not match the begin's
+    assert ei.value.code == SEGVLAD_ERR_ARG
+    check()
+    for _ in range(3):
+        eng.describe_cancel(eng.describe_begin(masks, tok, off, H, W, 14, 3, pca=True))
+        check()
     eng.close()

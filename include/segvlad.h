@@ -264,6 +264,40 @@ int segvlad_search_excluding(segvlad_ctx* ctx, const float* Q, int nq, const int
                              const int32_t* excl, int E, int k, float* d2_out, int64_t* idx_out);
 int segvlad_exclude_stats(segvlad_ctx* ctx, int64_t* stats_out, int n);
 
+/* ---- grouped search: top-k with at most per_image rows per reference image (no reference counterpart: the reference's vote
+ *      adds one similarity per HIT, get_matches / max_seg_topk_wt_borda_Im, func_vpr.py:207-224, so on a map with revisited
+ *      places one query segment gives one image dozens of votes; retrieval engines call this a grouped or collapsed search).
+ *      Q [nq][d] device or host.  1 <= k <= 1024, 1 <= per_image <= 16.  d2_out / idx_out [nq][k], device or host.
+ *      Let L(q) be the unbounded segvlad_search list of row q: every index row in ascending (squared L2, lower id) order, the
+ *      distances the search's exact fp32 chain (sequential fma dot product in k order, the stored row norms,
+ *      fmaf(-2, dot, |q|^2 + |r|^2), negatives set to 0).  An entry of L(q) is KEPT when fewer than per_image EARLIER entries
+ *      of L(q) carry its image id (the img_of_seg value given to segvlad_db_add); a row whose image id is negative is a group
+ *      of its own and is always kept.  The output is the first k kept entries, in their order; slots behind them hold
+ *      (+inf, -1).  Hence: with per_image at least every image's row count, and on an index whose image ids are all distinct,
+ *      the call returns segvlad_search(Q, k) bit for bit; with per_image = 1 the ids of a row name k different images.
+ *      How: the search runs once at depth k_fetch = min(1024, 4 k) and each row's list is collapsed on the device; a row that
+ *      neither kept k entries nor reached the index's end within k_fetch is finished by an exact pass -- the exact distance
+ *      blocks of segvlad_range_search over the whole index, ordered, collapsed by the same rule (in batches whose scratch --
+ *      two word buffers of 8 bytes per index row, and one byte per image id up to the largest, per query row -- stays within
+ *      1 GiB, at least one row).  That pass takes a hit as the range search does, d2 < +inf: an index row whose fp32 distance
+ *      to the query row overflows to +inf or is NaN is not listed for a row the exact pass finishes, while the collapse of the
+ *      fetched list keeps whatever segvlad_search lists.  A query row holding a non-finite value is never sent to the exact
+ *      pass: it returns the collapse of whatever segvlad_search lists for it at depth k_fetch.
+ *      Cost: what a caller pays is the depth of the inner search, 4 k: any k >= 245 fetches >= 977 entries, where on a
+ *      1 M-row index the search plan leaves its filter levels for the distance-matrix path (tens of times slower; see
+ *      segvlad_search_excluding); and every open row streams the whole index once more.  Keep k below that where it matters.
+ *      SEGVLAD_ERR_STATE without an img_of_seg map or with no dimension yet; SEGVLAD_ERR_ARG on null pointers, negative nq, k
+ *      or per_image out of range; more than 2^32 - 1 index rows: SEGVLAD_ERR_LIMIT, as in the range search.  nq == 0: OK.  An
+ *      index that removal has emptied: (+inf, -1) everywhere.  Works after any sequence of segvlad_db_add / segvlad_db_remove.
+ *      Deterministic: two calls return the same bits.  Synchronises once (the number of rows the collapse left open has to
+ *      reach the host; the exact pass synchronises again).  Stage timer "knn_group": the kernels this call adds to the inner
+ *      search's own stages.  One index, one context: the row-sharded and query-sharded classes have no counterpart yet.
+ *      segvlad_group_stats: HOST array, up to 3 values, of the last segvlad_search_grouped -- [0] the depth the inner search
+ *      ran at (k_fetch), [1] query rows finished by the exact pass, [2] the largest number of list entries any row read
+ *      before the collapse declared it complete (rows the exact pass finished do not count).                              */
+int segvlad_search_grouped(segvlad_ctx* ctx, const float* Q, int nq, int k, int per_image, float* d2_out, int64_t* idx_out);
+int segvlad_group_stats(segvlad_ctx* ctx, int64_t* stats_out, int n);
+
 /* ---- exact range search: faiss IndexFlat::range_search (no reference counterpart: the reference only searches top-k,
  *      place_rec_main.py:53-60, and turns distances into similarities with 2 - d^2, place_rec_main.py:78-81 -- a similarity
  *      floor s on unit rows is the squared radius 2 - s).  Loop closure and map upkeep ask "which rows are closer than this?".
@@ -357,7 +391,7 @@ int segvlad_vote(segvlad_ctx* ctx, const int64_t* idx, const float* sims, const 
                  int32_t* pred_out, double* score_out);
 
 /* ---- instrumentation: with profiling on, every kernel group of a stage ("incidence", "adjacency",
- *      "assign", "prep", "aggregate", "pca", "describe" (segvlad_describe as a whole: its parts overlap), "knn_level0", "knn_gemm", "knn_select", "knn_fallback", "knn_shortlist" (segvlad_search_shortlist), "knn_exclude" (the kernels segvlad_search_excluding adds to its inner search), "knn_range" (the kernels of segvlad_range_search), "match_pairs" (segvlad_match_pairs), "db_remove" (segvlad_db_remove), "vote") is bracketed by a HIP event pair
+ *      "assign", "prep", "aggregate", "pca", "describe" (segvlad_describe as a whole: its parts overlap), "knn_level0", "knn_gemm", "knn_select", "knn_fallback", "knn_shortlist" (segvlad_search_shortlist), "knn_exclude" (the kernels segvlad_search_excluding adds to its inner search), "knn_group" (the kernels segvlad_search_grouped adds to its inner search), "knn_range" (the kernels of segvlad_range_search), "match_pairs" (segvlad_match_pairs), "db_remove" (segvlad_db_remove), "vote") is bracketed by a HIP event pair
  *      on the context stream.  segvlad_stage_ms returns the SUM of the elapsed times (ms) and the number
  *      of kernel launches recorded for the stage since the last segvlad_profile_reset; it returns
  *      SEGVLAD_ERR_STATE if the stage has not run.  Replaces the (discarded) time.time() pair of

@@ -312,6 +312,7 @@ int segvlad_set_option(segvlad_ctx* ctx, const char* key, const char* value) {
   if (!strcmp(key, "debug_small_tail")) return as_int(&o.debug_small_tail);
   if (!strcmp(key, "refine_group")) return as_int(&o.refine_group);
   if (!strcmp(key, "query_group")) return as_int(&o.query_group);
+  if (!strcmp(key, "group_fetch")) return as_int(&o.group_fetch);
   if (!strcmp(key, "debug_search")) return as_int(&o.debug_search);
   if (!strcmp(key, "debug_fail_search")) return as_int(&o.debug_fail_search);
   if (!strcmp(key, "guard_undersize")) {
@@ -680,6 +681,37 @@ int segvlad_exclude_stats(segvlad_ctx* ctx, int64_t* stats_out, int n) {
     SV_HIP(hipStreamSynchronize(ctx->stream));
   }
   for (int i = 0; i < n && i < 4; ++i) stats_out[i] = ctx->ex_stats[i];
+  return SEGVLAD_OK;
+}
+
+int segvlad_search_grouped(segvlad_ctx* ctx, const float* Q, int nq, int k, int per_image, float* d2_out, int64_t* idx_out) {
+  CHECK_CTX();
+  if (nq < 0 || k < 1 || k > 1024 || per_image < 1 || per_image > 16)
+    return ctx->fail(SEGVLAD_ERR_ARG, "search_grouped: need nq >= 0, 1<=k<=1024, 1<=per_image<=16 (k=%d, per_image=%d)", k, per_image);
+  if (ctx->db_d == 0) return ctx->fail(SEGVLAD_ERR_STATE, "search_grouped: the index is empty and has no dimension yet");
+  if (!ctx->db_has_img) return ctx->fail(SEGVLAD_ERR_STATE, "search_grouped: no img_of_seg map: give it to segvlad_db_add");
+  if (ctx->db_n > 0xffffffffLL) return ctx->fail(SEGVLAD_ERR_LIMIT, "search_grouped: %lld index rows (candidate ids are 32-bit)", (long long)ctx->db_n);
+  ctx->gr_stats[0] = ctx->gr_stats[1] = ctx->gr_stats[2] = 0;
+  if (nq == 0) return SEGVLAD_OK;
+  if (!Q || !d2_out || !idx_out) return ctx->fail(SEGVLAD_ERR_ARG, "search_grouped: null pointer");
+  const void* dq;
+  void *dd2, *didx;
+  SV_TRY(sv_in(ctx, Q, (size_t)nq * ctx->db_d * 4, &dq));
+  SV_TRY(sv_out(ctx, d2_out, (size_t)nq * k * 4, &dd2));
+  SV_TRY(sv_out(ctx, idx_out, (size_t)nq * k * 8, &didx));
+  if (ctx->db_n == 0) {   // emptied by segvlad_db_remove: no row anywhere
+    SV_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(dd2), 0x7f800000, (size_t)nq * k, ctx->stream));
+    SV_HIP(hipMemsetAsync(didx, 0xff, (size_t)nq * k * 8, ctx->stream));
+    return sv_finish(ctx);
+  }
+  SV_TRY(sv_search_grouped(ctx, (const float*)dq, nq, k, per_image, (float*)dd2, (int64_t*)didx));
+  return sv_finish(ctx);
+}
+
+int segvlad_group_stats(segvlad_ctx* ctx, int64_t* stats_out, int n) {
+  if (!ctx) return SEGVLAD_ERR_ARG;
+  if (!stats_out || n < 0) return ctx->fail(SEGVLAD_ERR_ARG, "group_stats: bad arguments");
+  for (int i = 0; i < n && i < 3; ++i) stats_out[i] = ctx->gr_stats[i];
   return SEGVLAD_OK;
 }
 

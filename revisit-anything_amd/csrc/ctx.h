@@ -187,6 +187,8 @@ struct SvOptions {
   int pca_path = 0;       // fused images_pca: 0 auto, 1 "planes" (descriptor planes x W), 2 "project" (project tokens, then aggregate)
   int cover_rows = 1;     // project form: only the tokens some segment covers get a row of the grouped planes and of Z (prep_kernel's
                           // `phys` map; same bits: every kernel keeps its logical positions); 0 = every token gets a row
+  int group_fetch = 0;    // segvlad_search_grouped: depth of the inner search, clamped to k .. 1024 (0 = min(1024, 4 k)); never changes a
+                          // result, only which rows the exact tail finishes (tests reach the tail on a small index with it)
 };
 
 // fp16 filter of the exact kNN: length of the accumulation blocks (0 = one running fp32 accumulator over the whole row).
@@ -318,6 +320,7 @@ struct segvlad_ctx {
   bool sl_off_host_valid = false;
   int64_t ex_stats[4] = {0, 0, 0, 0};
   int64_t rs_stats[5] = {0, 0, 0, 0, 0};   // segvlad_range_stats: total hits, long rows, max / sum of the candidate lists, path
+  int64_t gr_stats[3] = {0, 0, 0};         // segvlad_group_stats: k_fetch, rows the exact tail finished, the longest read of a complete row
   const uint32_t* ex_short_dev = nullptr;
   // device-driven single-image passes (small_pass_kernels.hip): the tail kernel's counters of the LAST such search live in device
   // memory and are fetched by segvlad_search_stats (the search itself never reads them back); its running totals reach the host
@@ -343,7 +346,9 @@ struct segvlad_ctx {
   //  filter thresholds, the long-row flags (+ the query preparation's flag block), per-row hit counts, where a short row's ordered
   //  words sit in s_rs_stage, the long rows' offsets / cursors / words before and after their ordering, the dense query block of
   //  the exact sweeps, the device lims of a host caller and a few counters; s_mp_min: segvlad_match_pairs (match_kernels.hip) --
-  //  the row minima [nq][C], then the live slots' column minima, 64-bit keys
+  //  the row minima [nq][C], then the live slots' column minima, 64-bit keys; s_gr_*: segvlad_search_grouped (group_kernels.hip) --
+  //  the deep lists, the counters + row flags, query norms, and the exact tail's open rows, their dense query block, a batch's
+  //  slots / word offsets, cursors, words before and after their ordering, per-image counts
 #define SV_SCRATCH_BUFS(X)                                                                                                       \
   X(s_xt) X(s_labels) X(s_rnorm) X(s_gap) X(s_colmask) X(s_gscale) X(s_segimg) X(s_segoff) X(s_adjoff) X(s_dist) X(s_qnorm)      \
   X(s_misc) X(s_minmax) X(s_voteoff) X(s_cand_cnt) X(s_cand_d2) X(s_cand_id) X(s_thr_d2) X(s_thr_idx) X(s_flag) X(s_qh) X(s_ql)  \
@@ -356,7 +361,8 @@ struct segvlad_ctx {
   X(s_rm_row) X(s_rm_img) X(s_rm_blk) X(s_rm_src) X(s_rm_misc)                                                                    \
   X(s_rs_thr) X(s_rs_flag) X(s_rs_fb) X(s_rs_cnt) X(s_rs_soff) X(s_rs_stage) X(s_rs_loff) X(s_rs_cur) X(s_rs_words) X(s_rs_sorted)  \
   X(s_rs_tmp) X(s_rs_rows) X(s_rs_q) X(s_rs_misc)                                                                                 \
-  X(s_mp_min)
+  X(s_mp_min)                                                                                                                      \
+  X(s_gr_d2) X(s_gr_idx) X(s_gr_flag) X(s_gr_qn) X(s_gr_rows) X(s_gr_q) X(s_gr_plan) X(s_gr_cur) X(s_gr_words) X(s_gr_sorted) X(s_gr_tab)
 #define SV_DECL_BUF(n) DevBuf n;
   SV_PERSISTENT_BUFS(SV_DECL_BUF)
   SV_SCRATCH_BUFS(SV_DECL_BUF)
@@ -620,6 +626,10 @@ int sv_launch_exclude_tail(segvlad_ctx* ctx, const float* Q, const float* qn, co
 int sv_search_excluding(segvlad_ctx* ctx, const float* Q, int nq, const int32_t* qoff, int n_img, const int32_t* excl, int E, int k,
                         float* d2_out, int64_t* idx_out);
 
+// group_kernels.hip: segvlad_search_grouped after the argument checks (Q / outputs on the device, nq >= 1, the index holds rows
+// and an img_of_seg map); fills ctx->gr_stats; synchronises
+int sv_search_grouped(segvlad_ctx* ctx, const float* Q, int nq, int k, int per_image, float* d2_out, int64_t* idx_out);
+
 // match_kernels.hip: segvlad_match_pairs after the argument checks (Q on the device and 16-byte aligned, qn its squared norms, qoff /
 // cand host, outputs on the device; order_out / fwd_idx_out / fwd_d2_out / mutual_out may be null)
 int sv_match_pairs(segvlad_ctx* ctx, const float* Q, int nq, const float* qn, const int32_t* qoff, int n_img, const int32_t* cand, int C,
@@ -641,6 +651,11 @@ int sv_launch_range_gather(segvlad_ctx* ctx, const float* Q, const float* qn, co
 int sv_launch_range_block(segvlad_ctx* ctx, const float* dist, int64_t ld, int mq, int ns, int64_t col0, const float* eff,
                           const int32_t* rows, uint32_t* cnt, const int64_t* woff, uint32_t* cur, uint64_t* words);
 int sv_range_sort_segments(segvlad_ctx* ctx, const uint64_t* words, uint64_t* sorted, int64_t n_words, int nq, const int64_t* off);
+// search.hip: one sweep of the exact distance blocks of nl dense query rows (qx, norms qnx, effective radii effx; rows_dev: the
+// row of cnt / woff / cur each one is) over the whole index -- counted into cnt (words == null) or emitted at
+// words[woff[row] + cur[row]++]; also the exact tail of segvlad_search_grouped
+int sv_range_exact_sweep(segvlad_ctx* ctx, const float* qx, const float* qnx, const float* effx, const int32_t* rows_dev, int nl,
+                         uint32_t* cnt, const int64_t* woff, uint32_t* cur, uint64_t* words, int* launches);
 int sv_launch_range_unpack(segvlad_ctx* ctx, const uint64_t* src, const int64_t* srcoff, const uint32_t* flags, uint32_t want, int nq,
                            const int64_t* lims, float* d2_out, int64_t* idx_out);
 

@@ -1162,9 +1162,10 @@ static hipError_t regrow_keep(segvlad_ctx* ctx, DevBuf& b, size_t keep, size_t b
 }
 
 // One sweep of the exact distance blocks of the nl dense query rows (qx, their norms qnx, their radii effx; rows_dev: the row of
-// the call each one is) over the whole index: counted into cnt (words == null) or emitted.
-static int range_exact_sweep(segvlad_ctx* ctx, const float* qx, const float* qnx, const float* effx, const int32_t* rows_dev, int nl,
-                             uint32_t* cnt, const int64_t* woff, uint32_t* cur, uint64_t* words, int* launches) {
+// the call each one is) over the whole index: counted into cnt (words == null) or emitted.  (Also the exact tail of
+// segvlad_search_grouped, group_kernels.hip.)
+int sv_range_exact_sweep(segvlad_ctx* ctx, const float* qx, const float* qnx, const float* effx, const int32_t* rows_dev, int nl,
+                         uint32_t* cnt, const int64_t* woff, uint32_t* cur, uint64_t* words, int* launches) {
   const int d = ctx->db_d;
   const int64_t n = ctx->db_n;
   const int64_t ld = (std::min(n, SV_RS_SLAB) + 3) & ~3ll;
@@ -1290,7 +1291,7 @@ static int range_search_dev(segvlad_ctx* ctx, const float* q, int nq, const floa
     effx = qxw + nl * d + nl;
     SV_TRY(sv_launch_range_gather(ctx, q, qn, eff, ctx->s_rs_rows.as<int32_t>(), (int)nl, d, qxw, qxw + nl * d, qxw + nl * d + nl));
     int launches = 1;
-    SV_TRY(range_exact_sweep(ctx, qx, qnx, effx, ctx->s_rs_rows.as<int32_t>(), (int)nl, cnt, nullptr, nullptr, nullptr, &launches));
+    SV_TRY(sv_range_exact_sweep(ctx, qx, qnx, effx, ctx->s_rs_rows.as<int32_t>(), (int)nl, cnt, nullptr, nullptr, nullptr, &launches));
     sc.count(launches);
   }
 
@@ -1325,7 +1326,7 @@ static int range_search_dev(segvlad_ctx* ctx, const float* q, int nq, const floa
     SV_HIP(ctx->s_rs_sorted.reserve((size_t)total_long * 8));
     SV_HIP(hipMemsetAsync(ctx->s_rs_cur.p, 0, (size_t)nq * 4, ctx->stream));
     int launches = 0;
-    SV_TRY(range_exact_sweep(ctx, qx, qnx, effx, ctx->s_rs_rows.as<int32_t>(), (int)rows.size(), cnt, loff, ctx->s_rs_cur.as<uint32_t>(),
+    SV_TRY(sv_range_exact_sweep(ctx, qx, qnx, effx, ctx->s_rs_rows.as<int32_t>(), (int)rows.size(), cnt, loff, ctx->s_rs_cur.as<uint32_t>(),
                              ctx->s_rs_words.as<uint64_t>(), &launches));
     SV_TRY(sv_range_sort_segments(ctx, ctx->s_rs_words.as<uint64_t>(), ctx->s_rs_sorted.as<uint64_t>(), total_long, nq, loff));
     SV_TRY(sv_launch_range_unpack(ctx, ctx->s_rs_sorted.as<uint64_t>(), loff, flags, 1u, nq, lims, (float*)dd2, (int64_t*)didx));

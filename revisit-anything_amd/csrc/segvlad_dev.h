@@ -51,6 +51,8 @@
  *                          as failed (the fused finish recomputes the band); bits 8..: grid of small_tail_kernel (A/B)
  *     "debug_search"       1 = per-level candidate statistics on stderr (synchronises); 7 = the Gram kernel waits for every
  *                          outstanding memory operation at every step (verification of its counted waits)
+ *     "group_fetch"        segvlad_search_grouped: depth of the inner search, clamped to k .. 1024 (0 = min(1024, 4 k)); the tests reach
+ *                          the exact tail on a small index with it
  *     "debug_fail_search"  segvlad_search fails at once (the sharded entry's error path)
  *     "guard_undersize"    "<buffer>:<bytes>": guard-mode tests (include/segvlad.h, SEGVLAD_GUARD)
  *   Environment read once by segvlad_create for these: SEGVLAD_F16_CFG, SEGVLAD_F16_GM, SEGVLAD_X3_TILE, SEGVLAD_X3_GM,

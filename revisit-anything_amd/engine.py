@@ -246,6 +246,41 @@ def range_image_counts(lims, idx, img_of_seg, qseg_offsets) -> list:
     return out
 
 
+def collapse_lists(d2, idx, img_of_seg, k: int, per_image: int = 1):
+    """The rule of segvlad_search_grouped, stated on the host: ``d2`` / ``idx`` ``[nq][L]`` are ordered lists as search()
+    returns them (ascending (d2, lower id); slots with ``idx < 0`` are padding and skipped), ``img_of_seg [n_ref_seg]`` the
+    image id of every index row.  An entry is kept when fewer than ``per_image`` EARLIER entries of its row carry its image
+    id; a row with a negative image id is a group of its own, always kept.  Returns ``(d2 [nq][k] fp32, idx [nq][k] int64)``:
+    each row's first ``k`` kept entries in their order, (+inf, -1) behind them.  With unbounded lists (L = the index size)
+    this IS the grouped search's result; with shorter ones, a row that neither fills its k slots nor meets a padding slot is
+    undecided at that depth."""
+    d2 = np.asarray(d2, dtype=np.float32)
+    idx = np.asarray(idx, dtype=np.int64)
+    img = np.asarray(img_of_seg, dtype=np.int64).reshape(-1)
+    if d2.ndim != 2 or idx.shape != d2.shape:
+        raise ValueError(f"d2 / idx must be [nq][L] of one shape, got {d2.shape} and {idx.shape}")
+    if k < 1 or per_image < 1:
+        raise ValueError("k and per_image must be >= 1")
+    if idx.size and int(idx.max()) >= img.size:
+        raise ValueError("idx names a row img_of_seg does not cover")
+    nq = d2.shape[0]
+    out_d = np.full((nq, k), np.inf, dtype=np.float32)
+    out_i = np.full((nq, k), -1, dtype=np.int64)
+    for q in range(nq):
+        pos = np.nonzero(idx[q] >= 0)[0]
+        g = img[idx[q, pos]]
+        order = np.argsort(g, kind="stable")               # equal ids stay in list order
+        gs = g[order]
+        first = np.r_[True, gs[1:] != gs[:-1]] if gs.size else np.zeros(0, bool)
+        run_start = np.maximum.accumulate(np.where(first, np.arange(gs.size), 0)) if gs.size else gs
+        earlier = np.empty(gs.size, dtype=np.int64)
+        earlier[order] = np.arange(gs.size) - run_start    # earlier entries of the same image
+        kept = pos[(g < 0) | (earlier < per_image)][:k]
+        out_d[q, :kept.size] = d2[q, kept]
+        out_i[q, :kept.size] = idx[q, kept]
+    return out_d, out_i
+
+
 def expand_radius2(radius2, nq: int, qseg_offsets=None) -> np.ndarray:
     """``radius2`` of range_search as one fp32 value per query row: a scalar, ``[nq]``, or -- with ``qseg_offsets`` --
     ``[n_img]`` (repeated over each image's rows).  Raises ValueError on any other shape."""
@@ -851,6 +886,30 @@ class SegVLADEngine:
                                                       _ptr(d2), _ptr(idx)), "search_excluding")
         self._keep = [q]
         return d2, idx
+
+    def search_grouped(self, Q, k: int, per_image: int = 1):
+        """segvlad_search_grouped: per query row the nearest index rows such that no reference image (the img_of_seg of db_add)
+        appears more than ``per_image`` times (1 .. 16) -- collapse_lists() over the unbounded search() list, bit for bit.  A row
+        with a negative image id is a group of its own.  Returns device tensors (d2 [nq][k] fp32, idx [nq][k] int64) like
+        search(); (+inf, -1) once the index runs out of admissible rows.  ``per_image=1`` gives k DIFFERENT images per query
+        segment: one segment, one vote per image -- and distinct candidates for match_pairs().
+        Cost: one search at depth ``min(1024, 4 k)`` plus a collapse kernel; a row whose nearest ``k_fetch`` rows hold fewer
+        than k admissible ones is finished by an exact pass over the whole index (group_stats()["tail_rows"])."""
+        q = _as(Q, np.float32, torch.float32)
+        nq = q.shape[0]
+        d2 = self._empty((nq, k), torch.float32)
+        idx = self._empty((nq, k), torch.int64)
+        self._stream()
+        self._check(self.lib.segvlad_search_grouped(self._h, _ptr(q), nq, k, int(per_image), _ptr(d2), _ptr(idx)), "search_grouped")
+        self._keep = [q]
+        return d2, idx
+
+    def group_stats(self) -> dict:
+        """Statistics of the last search_grouped(): the depth of the inner search, the query rows the exact tail finished, the
+        largest number of list entries a row read before the collapse declared it complete."""
+        v = (C.c_int64 * 3)()
+        self._check(self.lib.segvlad_group_stats(self._h, v, 3), "group_stats")
+        return dict(zip(("k_fetch", "tail_rows", "max_read"), [int(x) for x in v]))
 
     def match_pairs(self, Q, qseg_offsets, cand, max_d2: float = float("inf"), want_rows: bool = False) -> dict:
         """segvlad_match_pairs: for every query image b and candidate slot j, the mutual nearest pairs between the image's

@@ -204,6 +204,7 @@ int segvlad_normalize_rows(segvlad_ctx* ctx, const float* X, int n, int d, float
  *      The index keeps a device copy of the rows.  img_of_seg (imIndsRef / imInds1,
  *      place_rec_main.py:252) may be NULL if segvlad_vote is given the map explicitly.            */
 int segvlad_db_reset(segvlad_ctx* ctx);
+/*      Rows holding NaN / +-Inf are stored like any other and are never listed: "Non-finite rows" at segvlad_search.    */
 int segvlad_db_add(segvlad_ctx* ctx, const float* R, int n, int d, const int32_t* img_of_seg);
 int segvlad_db_size(segvlad_ctx* ctx, int64_t* n_rows, int* d);
 
@@ -223,7 +224,19 @@ int segvlad_db_size(segvlad_ctx* ctx, int64_t* n_rows, int* d);
 int segvlad_db_remove(segvlad_ctx* ctx, const int64_t* row_ids, int64_t n_row_ids, const int32_t* img_ids, int n_img_ids,
                       int64_t* new_id_out, int64_t* n_removed_out);
 /*      d2_out [nq][k] fp32 ascending squared L2; idx_out [nq][k] int64 (ties -> lower id; slots
- *      beyond the database size hold (+inf, -1) like faiss).  1 <= k <= 1024.                      */
+ *      beyond the database size hold (+inf, -1) like faiss).  1 <= k <= 1024.
+ *      Non-finite rows.  NaN and +-Inf are ordinary input of segvlad_db_add and segvlad_search (segvlad_normalize_rows turns an
+ *      all-zero row into a NaN row on purpose), in any number, whether they arrive with the first segvlad_db_add or a later one:
+ *      - never listed: a pair whose fp32 distance is NaN or +inf is never listed (the hit rule of segvlad_range_search, and of
+ *        faiss, whose heap admits neither).  An index row holding NaN or +-Inf is in nobody's list; a query row holding one
+ *        returns (+inf, -1) in every slot; a list with fewer than k finite distances is padded with (+inf, -1).  No slot holds a
+ *        NaN distance, or a valid id beside a non-finite distance.
+ *      - isolation: a query row whose values are all finite gets, ids and distance bits, what segvlad_search returns on an index
+ *        holding only the finite rows (ids as segvlad_db_remove would renumber them) -- on every plan and under every option.
+ *        A row is never listed exactly when its fp32 squared norm is not finite: it holds NaN / +-Inf, or it is all finite and
+ *        its norm overflows.  The fp16 scales of the index and of the queries, max |r|^2 of the filters' margins and min |q|^2
+ *        are all taken over the other rows alone, whatever finite entries a never-listed row holds.
+ *      - no collateral cost: the bad rows send no other row to the redo or the matrix fallback (a bad query row itself may go).  */
 int segvlad_search(segvlad_ctx* ctx, const float* Q, int nq, int k, float* d2_out, int64_t* idx_out);
 
 /* ---- shortlist-restricted exact search (no reference counterpart: the reference searches the whole index,
@@ -236,6 +249,7 @@ int segvlad_search(segvlad_ctx* ctx, const float* Q, int nq, int k, float* d2_ou
  *      ordered by (squared L2, lower id) as segvlad_search; (+inf, -1) beyond the number of allowed rows.  Every distance is
  *      the exact fp32 chain of segvlad_search (sequential fma dot product in k order, the stored row norms, negatives set to
  *      0): a pair's value is bit for bit segvlad_search's, and a shortlist of every image returns segvlad_search(Q, k).
+ *      Non-finite rows: the rule of segvlad_search (never listed, isolation).
  *      SEGVLAD_ERR_STATE without an img_of_seg map; SEGVLAD_ERR_LIMIT when d % 32 != 0.  The image -> row map is built on
  *      the device by the first call after segvlad_db_add / segvlad_db_reset.                                          */
 int segvlad_search_shortlist(segvlad_ctx* ctx, const float* Q, int nq, const int32_t* qseg_offsets, int n_img,
@@ -252,6 +266,7 @@ int segvlad_search_shortlist(segvlad_ctx* ctx, const float* Q, int nq, const int
  *      d2_out / idx_out [nq][k]: per query row the top-k rows of the index whose image id lies in none of its image's intervals,
  *      ordered by (squared L2, lower id); (+inf, -1) beyond the number of allowed rows -- bit for bit what segvlad_search
  *      returns on an index without those images (ids aside).  All intervals empty: exactly segvlad_search(Q, k).
+ *      Non-finite rows: the rule of segvlad_search (never listed, isolation).
  *      The search runs once at depth k_fetch = min(1024, k + the largest number of rows any query image excludes) and keeps
  *      each row's first k allowed entries; rows of an image whose window holds more than 1024 - k rows AND fills the row's
  *      nearest 1024 are finished by an exact fp32 pass over the allowed rows (needs every row's image id >= 0: a call whose
@@ -279,10 +294,10 @@ int segvlad_exclude_stats(segvlad_ctx* ctx, int64_t* stats_out, int n);
  *      neither kept k entries nor reached the index's end within k_fetch is finished by an exact pass -- the exact distance
  *      blocks of segvlad_range_search over the whole index, ordered, collapsed by the same rule (in batches whose scratch --
  *      two word buffers of 8 bytes per index row, and one byte per image id up to the largest, per query row -- stays within
- *      1 GiB, at least one row).  That pass takes a hit as the range search does, d2 < +inf: an index row whose fp32 distance
- *      to the query row overflows to +inf or is NaN is not listed for a row the exact pass finishes, while the collapse of the
- *      fetched list keeps whatever segvlad_search lists.  A query row holding a non-finite value is never sent to the exact
- *      pass: it returns the collapse of whatever segvlad_search lists for it at depth k_fetch.
+ *      1 GiB, at least one row).  Non-finite rows: the rule of segvlad_search (never listed, isolation), in the fetched lists
+ *      and in the exact pass alike -- that pass takes a hit as the range search does, d2 < +inf, and the fetched list ends at its
+ *      first (+inf, -1) slot.  A query row holding a non-finite value is never sent to the exact pass: its fetched list is
+ *      empty, it returns (+inf, -1) in every slot.
  *      Cost: what a caller pays is the depth of the inner search, 4 k: any k >= 245 fetches >= 977 entries, where on a
  *      1 M-row index the search plan leaves its filter levels for the distance-matrix path (tens of times slower; see
  *      segvlad_search_excluding); and every open row streams the whole index once more.  Keep k below that where it matters.

@@ -31,11 +31,20 @@
 // filtered GEMM, exact refinement) rounds identically: fma(-2, dot, ||q||^2 + ||r||^2), negative results set to zero --
 // faiss's IndexFlatL2 (1.7.3, utils/distances.cpp, exhaustive_L2sqr_blas: `if (dis < 0) dis = 0`, "negative values can occur
 // for identical vectors due to roundoff errors") does the same BEFORE its heap sees the value, so an exact duplicate is at
-// distance 0 and `2 - d2` (place_rec_main.py:78-81) never exceeds 2 (round 6).  The comparison form keeps a NaN a NaN, as
-// faiss's does.  max(0, .) is monotone and 1-Lipschitz: order statistics and the filters' margins |d2~ - d2| <= eps carry
-// over to the clamped values unchanged.
+// distance 0 and `2 - d2` (place_rec_main.py:78-81) never exceeds 2 (round 6).  max(0, .) is monotone and 1-Lipschitz: order
+// statistics and the filters' margins |d2~ - d2| <= eps carry over to the clamped values unchanged.
+// A NaN (a row or a query holding NaN / Inf) leaves here as +inf: every select orders the values by their bit patterns
+// (f2key), where a NaN with the sign bit set -- what 0/0 gives -- would sort in FRONT of 0.0 and take the first slot of every
+// list.  As +inf such a pair sorts last with the other pairs that are never listed (segvlad.h, "Non-finite rows"); finite
+// values keep their bits.
 #if defined(__HIPCC__)
 __device__ __forceinline__ float sv_d2(float q2, float r2, float dot) {
+  const float v = __fmaf_rn(-2.f, dot, q2 + r2);
+  return v < 0.f ? 0.f : (v == v ? v : INFINITY);
+}
+// The same value with a NaN left a NaN, for the 16-bit filters' epilogues alone: they compare the value with a threshold (false for a
+// NaN: never a candidate) and never order it.
+__device__ __forceinline__ float sv_d2_screen(float q2, float r2, float dot) {
   const float v = __fmaf_rn(-2.f, dot, q2 + r2);
   return v < 0.f ? 0.f : v;
 }
@@ -559,13 +568,13 @@ int sv_launch_refine_grouped(segvlad_ctx* ctx, const float* Q, const float* R, i
                              const uint32_t* ref_cnt, const uint32_t* ref_id, int rcap, int k, float* d2_out, int64_t* idx_out,
                              int* launches, const uint32_t* only_rows = nullptr, int live_groups_hint = 0);
 int sv_refine_group_stats(segvlad_ctx* ctx, int nq, int64_t* groups, int64_t* grouped, int64_t* union_sum);
-int sv_row_norm_max(segvlad_ctx* ctx, const float* norms, int64_t n, float* out_host);
+int sv_row_norm_max(segvlad_ctx* ctx, const float* norms, int64_t n, float* out_host, bool finite_only = false);
 int sv_row_norm_min(segvlad_ctx* ctx, const float* norms, int64_t n, float* out_host);
-int sv_maxabs(segvlad_ctx* ctx, const float* x, int64_t n, float* out_host, bool finite_only = false);
-int sv_maxabs_and_norm_min(segvlad_ctx* ctx, const float* x, int64_t n, const float* norms, int64_t n_norms, float* maxabs_host,
-                           float* norm_min_host);
+int sv_maxabs(segvlad_ctx* ctx, const float* x, int64_t n, float* out_host, bool finite_only = false, bool* nonfinite_host = nullptr);
 int sv_maxabs_and_norm_min_begin(segvlad_ctx* ctx, const float* x, int64_t n, const float* norms, int64_t n_norms);
-int sv_maxabs_and_norm_min_end(segvlad_ctx* ctx, int64_t n, int64_t n_norms, float* maxabs_host, float* norm_min_host);
+// (the scalars over the finite values alone; *nonfinite_host: x holds a NaN or an Inf; *norm_max_host: the largest finite norm)
+int sv_maxabs_and_norm_min_end(segvlad_ctx* ctx, int64_t n, int64_t n_norms, float* maxabs_host, float* norm_min_host, bool* nonfinite_host,
+                               float* norm_max_host);
 // gemm_f16x3_kernels.hip
 int sv_launch_split_f16x2(segvlad_ctx* ctx, const float* X, int64_t n_rows, int d, const float* sub, float scale, uint16_t* h1,
                           uint16_t* h2);

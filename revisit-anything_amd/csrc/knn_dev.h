@@ -15,6 +15,30 @@ __device__ __forceinline__ float key2f_(uint32_t k) {
   return __uint_as_float(u);
 }
 
+// Single-image query preparations: the power-of-two scale of the fp16 plane comes from max |x| over the rows whose squared norm is
+// finite -- the rows that can be listed, the set the filters' margins are taken over ("Non-finite rows").  A norm can
+// only fail to be finite when some |x| >= 2^55 (d <= 2^18): below that bit pattern of the plain maximum nothing needs a second look.
+constexpr uint32_t SV_BIG_BITS = 0x5B000000u;   // 2^55
+// wave-uniform: is the squared norm of the row (d4 float4s, 16-byte aligned) NOT finite?
+__device__ __forceinline__ bool row_norm_bad_(const float* __restrict__ row, int d4, int lane) {
+  const float4* x4 = reinterpret_cast<const float4*>(row);
+  float s = 0.f;
+  for (int j = lane; j < d4; j += 64) {
+    const float4 v = x4[j];
+    s = fmaf(v.x, v.x, s);
+    s = fmaf(v.y, v.y, s);
+    s = fmaf(v.z, v.z, s);
+    s = fmaf(v.w, v.w, s);
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+  return !(fabsf(s) < INFINITY);
+}
+__device__ __forceinline__ uint32_t mag4_(const float4& v) {
+  return max(max(__float_as_uint(v.x) & 0x7fffffffu, __float_as_uint(v.y) & 0x7fffffffu),
+             max(__float_as_uint(v.z) & 0x7fffffffu, __float_as_uint(v.w) & 0x7fffffffu));
+}
+
 // ascending bitonic sort of n (a power of two) 64-bit words in LDS by a 256-thread workgroup
 __device__ __forceinline__ void bitonic64(uint64_t* a, int n, int tid) {
   for (int size = 2; size <= n; size <<= 1) {

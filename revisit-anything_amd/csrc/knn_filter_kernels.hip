@@ -233,7 +233,7 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void knn_bf16_filter_kernel(
         const int64_t row = m0 + wm * (32 * TM) + mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * kk;
         if (row < M) {
           const float q2 = qn[row];
-          const float v = sv_d2(q2, cn, acc[mt][nt][r]);
+          const float v = sv_d2_screen(q2, cn, acc[mt][nt][r]);
           const float lim = thr[row * thr_ld] + eps_mult * c_eps * sqrtf(q2 * rn_max);
           if (v <= lim) {
             const uint32_t slot = atomicAdd(&cand_cnt[row], 1u);
@@ -288,13 +288,15 @@ typedef float f32x4v __attribute__((ext_vector_type(4)));
 // loads and one atomicMax per WAVE (16 384 of them on one word for a 10 000 x 1024 query batch) took 190 us in front of every
 // batch search (round 5 kernel trace) for 41 MB -- 10 us of reading.
 // FINITE_ONLY: NaN and Inf entries do not count (their |x| bit patterns sort above every finite value's): the maximum a
-// power-of-two scale is derived from must not be taken over by one bad row (segvlad_pca_apply).
-template <bool FINITE_ONLY>
+// power-of-two scale is derived from must not be taken over by one bad row (segvlad_pca_apply, the index and the queries of
+// segvlad_search).  FLAG (with FINITE_ONLY): out[2] is raised when such an entry was seen.
+template <bool FINITE_ONLY, bool FLAG = false>
 __global__ __launch_bounds__(256) void maxabs_kernel(const float* __restrict__ x, int64_t n, uint32_t* __restrict__ out) {
   __shared__ uint32_t wmax[4];
-  uint32_t m = 0;
-  auto mag = [](uint32_t u) -> uint32_t {
+  uint32_t m = 0, bad = 0;
+  auto mag = [&bad](uint32_t u) -> uint32_t {
     u &= 0x7fffffffu;
+    if (FLAG) bad |= (uint32_t)(u >= 0x7f800000u);
     return (FINITE_ONLY && u >= 0x7f800000u) ? 0u : u;
   };
   const int64_t tid = (int64_t)blockIdx.x * 256 + threadIdx.x, nth = (int64_t)gridDim.x * 256;
@@ -313,24 +315,29 @@ __global__ __launch_bounds__(256) void maxabs_kernel(const float* __restrict__ x
   if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = m;
   __syncthreads();
   if (threadIdx.x == 0) atomicMax(out, max(max(wmax[0], wmax[1]), max(wmax[2], wmax[3])));
+  if (FLAG && __ballot(bad != 0u) != 0ull && (threadIdx.x & 63) == 0) atomicOr(out + 2, 1u);
 }
 
-int sv_maxabs(segvlad_ctx* ctx, const float* x, int64_t n, float* out_host, bool finite_only) {
+// nonfinite_host != null (finite_only): set when the block holds a NaN or an Inf
+int sv_maxabs(segvlad_ctx* ctx, const float* x, int64_t n, float* out_host, bool finite_only, bool* nonfinite_host) {
   SV_HIP(ctx->s_minmax.reserve(32));
-  uint32_t* mm = ctx->s_minmax.as<uint32_t>() + 4;
-  SV_HIP(hipMemsetAsync(mm, 0, 4, ctx->stream));
+  uint32_t* mm = ctx->s_minmax.as<uint32_t>() + 4;   // [4] = max |x| bits, [6] = the non-finite flag
+  SV_HIP(hipMemsetAsync(mm, 0, 12, ctx->stream));
   int64_t blocks = (n + 1023) / 1024;
   if (blocks > 1024) blocks = 1024;
-  if (n > 0 && finite_only)
+  if (n > 0 && finite_only && nonfinite_host)
+    hipLaunchKernelGGL((maxabs_kernel<true, true>), dim3((unsigned)blocks), dim3(256), 0, ctx->stream, x, n, mm);
+  else if (n > 0 && finite_only)
     hipLaunchKernelGGL(maxabs_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, x, n, mm);
   else if (n > 0)
     hipLaunchKernelGGL(maxabs_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, x, n, mm);
-  uint32_t u = 0;
-  SV_HIP(hipMemcpyAsync(&u, mm, 4, hipMemcpyDeviceToHost, ctx->stream));
+  uint32_t u[3] = {0, 0, 0};
+  SV_HIP(hipMemcpyAsync(u, mm, 12, hipMemcpyDeviceToHost, ctx->stream));
   SV_HIP(hipStreamSynchronize(ctx->stream));
   float f;
-  memcpy(&f, &u, 4);
+  memcpy(&f, &u[0], 4);
   *out_host = f;
+  if (nonfinite_host) *nonfinite_host = u[2] != 0u;
   return SEGVLAD_OK;
 }
 
@@ -360,6 +367,7 @@ __global__ __launch_bounds__(1024) void query_f16_small_kernel(const float* __re
                                                                float* __restrict__ qn_out, int nq, int d,
                                                                uint32_t* __restrict__ zero, int zero_words) {
   __shared__ uint32_t wmax[16];
+  __shared__ uint32_t badrow[128];   // (nq <= 128)
   __shared__ float s_scale;
   const int tid = threadIdx.x;
   // the search's flag block, zeroed here instead of by a fill launch of its own in front of the pass's dependent chain
@@ -384,12 +392,26 @@ __global__ __launch_bounds__(1024) void query_f16_small_kernel(const float* __re
   uint32_t m = 0;
   for (int64_t j = tid; j < n4; j += 1024) {
     const float4 v = reinterpret_cast<const float4*>(X)[j];
-    m = max(max(m, __float_as_uint(v.x) & 0x7fffffffu), max(__float_as_uint(v.y) & 0x7fffffffu, __float_as_uint(v.z) & 0x7fffffffu));
-    m = max(m, __float_as_uint(v.w) & 0x7fffffffu);
+    m = max(m, mag4_(v));
   }
   for (int o = 32; o > 0; o >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, o));
   if ((tid & 63) == 0) wmax[tid >> 6] = m;
   __syncthreads();
+  for (int w = 0; w < 16; ++w) m = max(m, wmax[w]);
+  if (m >= SV_BIG_BITS) {   // (uniform) a NaN, an Inf or a huge value: the maximum again, over the rows with a finite norm (knn_dev.h)
+    const int d4 = d >> 2;
+    for (int row = tid >> 6; row < nq; row += 16) {
+      const bool bad = row_norm_bad_(X + (int64_t)row * d, d4, tid & 63);
+      if ((tid & 63) == 0) badrow[row] = bad ? 1u : 0u;
+    }
+    __syncthreads();
+    m = 0;
+    for (int64_t j = tid; j < n4; j += 1024)
+      if (!badrow[j / d4]) m = max(m, mag4_(reinterpret_cast<const float4*>(X)[j]));
+    for (int o = 32; o > 0; o >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, o));
+    if ((tid & 63) == 0) wmax[tid >> 6] = m;
+    __syncthreads();
+  }
   if (tid == 0) {
     for (int w = 1; w < 16; ++w) m = max(m, wmax[w]);
     const float maxabs = __uint_as_float(m);
@@ -1446,7 +1468,7 @@ __global__ __launch_bounds__(64 * C::WM * C::WN) void knn_f16_filter_kernel(
     const int lrow = (int)(rec.y >> 16);
     const float4 rr = rrec[lrow];
     const float v = BIAS ? __fmaf_rn(-2.f, __uint_as_float(rec.x) * inv_scale, rr.x)
-                         : sv_d2(rr.x, cnl[rec.y & 0xffffu], __uint_as_float(rec.x) * inv_scale);
+                         : sv_d2_screen(rr.x, cnl[rec.y & 0xffffu], __uint_as_float(rec.x) * inv_scale);
     if (v <= rr.y && v < INFINITY) {   // +inf: padding columns beyond N (admitted by the screen when thr = +inf)
       atomicAdd(&rowcnt[lrow], 1u);
       rec.x = __float_as_uint(v);
@@ -1470,7 +1492,7 @@ __global__ __launch_bounds__(64 * C::WM * C::WN) void knn_f16_filter_kernel(
         for (int nt = 0; nt < TN; ++nt) {
           const float4 rr = rrec[lrow];
           const float v = BIAS ? __fmaf_rn(-2.f, acc[mt][nt][r] * isc, rr.x)
-                               : sv_d2(rr.x, cn[nt], acc[mt][nt][r] * isc);
+                               : sv_d2_screen(rr.x, cn[nt], acc[mt][nt][r] * isc);
           if (v <= rr.y && v < INFINITY) atomicAdd(&rowcnt[lrow], 1u);
         }
         __builtin_amdgcn_sched_barrier(0);   // keep the 32 row-record loads from being hoisted (register pressure)
@@ -1510,7 +1532,7 @@ __global__ __launch_bounds__(64 * C::WM * C::WN) void knn_f16_filter_kernel(
           const float4 rr = rrec[lrow];
           {
             const float v = BIAS ? __fmaf_rn(-2.f, acc[mt][nt][r] * isc, rr.x)
-                                 : sv_d2(rr.x, cn[nt], acc[mt][nt][r] * isc);
+                                 : sv_d2_screen(rr.x, cn[nt], acc[mt][nt][r] * isc);
             if (v <= rr.y && v < INFINITY) {
               const uint32_t slot = atomicAdd(&rowcnt[lrow], 1u);
               if (slot < (uint32_t)cap) {
@@ -1720,16 +1742,27 @@ int sv_launch_f16_filter(segvlad_ctx* ctx, const uint16_t* Qh, const uint16_t* R
 }
 
 // ---- max of the database row norms (margin scale) -------------------------------------------------------------
+// Both reductions order the values by their keys, where a NaN sorts above +inf or -- sign bit set -- below 0.0.  For the search
+// (FINITE_ONLY; min_kernel always) NaN and Inf norms -- rows that are never listed -- do not count, or one such row would take the
+// margin's scale from every other row; segvlad_set_vocab keeps the plain maximum.
+__device__ __forceinline__ bool norm_counts_(float v) { return (__float_as_uint(v) & 0x7fffffffu) < 0x7f800000u; }
+template <bool FINITE_ONLY>
 __global__ __launch_bounds__(256) void max_kernel(const float* __restrict__ x, int64_t n, uint32_t* __restrict__ out) {
   uint32_t m = 0;
-  for (int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x; j < n; j += (int64_t)gridDim.x * 256) m = max(m, f2key_(x[j]));
+  for (int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x; j < n; j += (int64_t)gridDim.x * 256) {
+    const float v = x[j];
+    if (!FINITE_ONLY || norm_counts_(v)) m = max(m, f2key_(v));
+  }
   for (int o = 32; o > 0; o >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, o));
   if ((threadIdx.x & 63) == 0) atomicMax(out, m);
 }
 
 __global__ __launch_bounds__(256) void min_kernel(const float* __restrict__ x, int64_t n, uint32_t* __restrict__ out) {
   uint32_t m = 0xffffffffu;
-  for (int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x; j < n; j += (int64_t)gridDim.x * 256) m = min(m, f2key_(x[j]));
+  for (int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x; j < n; j += (int64_t)gridDim.x * 256) {
+    const float v = x[j];
+    if (norm_counts_(v)) m = min(m, f2key_(v));
+  }
   for (int o = 32; o > 0; o >>= 1) m = min(m, (uint32_t)__shfl_xor((int)m, o));
   if ((threadIdx.x & 63) == 0) atomicMin(out, m);
 }
@@ -1752,31 +1785,6 @@ int sv_row_norm_min(segvlad_ctx* ctx, const float* norms, int64_t n, float* out_
   return SEGVLAD_OK;
 }
 
-// max |x| of a block and the smallest of a list of row norms behind ONE read-back (a batch search needs both before its first
-// filter launch: two synchronisations in a row otherwise)
-int sv_maxabs_and_norm_min(segvlad_ctx* ctx, const float* x, int64_t n, const float* norms, int64_t n_norms, float* maxabs_host,
-                           float* norm_min_host) {
-  SV_HIP(ctx->s_minmax.reserve(32));
-  uint32_t* mm = ctx->s_minmax.as<uint32_t>() + 4;   // [4] = max |x| bits (init 0), [5] = min key (init all ones)
-  static const uint32_t init[2] = {0u, 0xffffffffu};
-  SV_HIP(hipMemcpyAsync(mm, init, 8, hipMemcpyHostToDevice, ctx->stream));
-  int64_t blocks = (n + 1023) / 1024;
-  if (blocks > 1024) blocks = 1024;
-  if (n > 0) hipLaunchKernelGGL(maxabs_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, x, n, mm);
-  int nb = (int)((n_norms + 255) / 256);
-  if (nb > 1024) nb = 1024;
-  if (n_norms > 0) hipLaunchKernelGGL(min_kernel, dim3(nb), dim3(256), 0, ctx->stream, norms, n_norms, mm + 1);
-  uint32_t h[2] = {0u, 0u};
-  SV_HIP(hipMemcpyAsync(h, mm, 8, hipMemcpyDeviceToHost, ctx->stream));
-  SV_HIP(hipStreamSynchronize(ctx->stream));
-  memcpy(maxabs_host, &h[0], 4);
-  const uint32_t u = (h[1] & 0x80000000u) ? (h[1] & 0x7fffffffu) : ~h[1];
-  float f;
-  memcpy(&f, &u, 4);
-  *norm_min_host = (n_norms > 0 && h[1] != 0xffffffffu) ? f : 0.f;
-  return SEGVLAD_OK;
-}
-
 int sv_ensure_pinned_words(segvlad_ctx* ctx) {
   if (!ctx->h_pin) {
     SV_HIP(hipHostMalloc(reinterpret_cast<void**>(&ctx->h_pin), 64, hipHostMallocDefault));
@@ -1786,32 +1794,44 @@ int sv_ensure_pinned_words(segvlad_ctx* ctx) {
   return SEGVLAD_OK;
 }
 
-// The same two scalars WITHOUT the wait in between: _begin enqueues the reductions and the copy into pinned words of the
+// max |x| of a block (finite values), the smallest and the largest finite of a list of row norms and the block's non-finite flag
+// behind ONE read-back, WITHOUT a wait in between: _begin enqueues the reductions and the copy into pinned words of the
 // context and records an event behind them; _end blocks on that event only.  What the caller enqueues between the two runs on
 // the device while the host waits.
 int sv_maxabs_and_norm_min_begin(segvlad_ctx* ctx, const float* x, int64_t n, const float* norms, int64_t n_norms) {
   SV_HIP(ctx->s_minmax.reserve(32));
   SV_TRY(sv_ensure_pinned_words(ctx));
-  uint32_t* mm = ctx->s_minmax.as<uint32_t>() + 4;   // [4] = max |x| bits (init 0), [5] = min key (init all ones)
-  static const uint32_t init[2] = {0u, 0xffffffffu};
-  SV_HIP(hipMemcpyAsync(mm, init, 8, hipMemcpyHostToDevice, ctx->stream));
+  uint32_t* mm = ctx->s_minmax.as<uint32_t>() + 4;   // [4] = finite max |x| bits (init 0), [5] = min key (init all ones), [6] = non-finite flag
+  static const uint32_t init[4] = {0u, 0xffffffffu, 0u, 0u};   // ..., [7] = max finite norm key
+  SV_HIP(hipMemcpyAsync(mm, init, 16, hipMemcpyHostToDevice, ctx->stream));
   int64_t blocks = (n + 1023) / 1024;
   if (blocks > 1024) blocks = 1024;
-  if (n > 0) hipLaunchKernelGGL(maxabs_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, x, n, mm);
+  if (n > 0) hipLaunchKernelGGL((maxabs_kernel<true, true>), dim3((unsigned)blocks), dim3(256), 0, ctx->stream, x, n, mm);
   int nb = (int)((n_norms + 255) / 256);
   if (nb > 1024) nb = 1024;
   if (n_norms > 0) hipLaunchKernelGGL(min_kernel, dim3(nb), dim3(256), 0, ctx->stream, norms, n_norms, mm + 1);
+  if (n_norms > 0) hipLaunchKernelGGL(max_kernel<true>, dim3(nb), dim3(256), 0, ctx->stream, norms, n_norms, mm + 3);
   SV_HIP(hipGetLastError());
-  SV_HIP(hipMemcpyAsync(ctx->h_pin, mm, 8, hipMemcpyDeviceToHost, ctx->stream));
+  SV_HIP(hipMemcpyAsync(ctx->h_pin, mm, 16, hipMemcpyDeviceToHost, ctx->stream));
   SV_HIP(hipEventRecord(ctx->ev_scalars, ctx->stream));
   return SEGVLAD_OK;
 }
 
-int sv_maxabs_and_norm_min_end(segvlad_ctx* ctx, int64_t n, int64_t n_norms, float* maxabs_host, float* norm_min_host) {
+static float key_to_float(uint32_t key) {
+  const uint32_t u = (key & 0x80000000u) ? (key & 0x7fffffffu) : ~key;
+  float f;
+  memcpy(&f, &u, 4);
+  return f;
+}
+
+int sv_maxabs_and_norm_min_end(segvlad_ctx* ctx, int64_t n, int64_t n_norms, float* maxabs_host, float* norm_min_host, bool* nonfinite_host,
+                               float* norm_max_host) {
   SV_HIP(hipEventSynchronize(ctx->ev_scalars));
   const uint32_t h0 = ctx->h_pin[0], h1 = ctx->h_pin[1];
   memcpy(maxabs_host, &h0, 4);
   if (n <= 0) *maxabs_host = 0.f;
+  *nonfinite_host = n > 0 && ctx->h_pin[2] != 0u;
+  *norm_max_host = (n_norms > 0 && ctx->h_pin[3] != 0u) ? key_to_float(ctx->h_pin[3]) : 0.f;
   const uint32_t u = (h1 & 0x80000000u) ? (h1 & 0x7fffffffu) : ~h1;
   float f;
   memcpy(&f, &u, 4);
@@ -1819,13 +1839,14 @@ int sv_maxabs_and_norm_min_end(segvlad_ctx* ctx, int64_t n, int64_t n_norms, flo
   return SEGVLAD_OK;
 }
 
-int sv_row_norm_max(segvlad_ctx* ctx, const float* norms, int64_t n, float* out_host) {
+int sv_row_norm_max(segvlad_ctx* ctx, const float* norms, int64_t n, float* out_host, bool finite_only) {
   SV_HIP(ctx->s_minmax.reserve(16));
   uint32_t* mm = ctx->s_minmax.as<uint32_t>() + 2;
   SV_HIP(hipMemsetAsync(mm, 0, 4, ctx->stream));
   int blocks = (int)((n + 255) / 256);
   if (blocks > 1024) blocks = 1024;
-  if (n > 0) hipLaunchKernelGGL(max_kernel, dim3(blocks), dim3(256), 0, ctx->stream, norms, n, mm);
+  if (n > 0 && finite_only) hipLaunchKernelGGL(max_kernel<true>, dim3(blocks), dim3(256), 0, ctx->stream, norms, n, mm);
+  else if (n > 0) hipLaunchKernelGGL(max_kernel<false>, dim3(blocks), dim3(256), 0, ctx->stream, norms, n, mm);
   uint32_t key = 0;
   SV_HIP(hipMemcpyAsync(&key, mm, 4, hipMemcpyDeviceToHost, ctx->stream));
   SV_HIP(hipStreamSynchronize(ctx->stream));

@@ -173,7 +173,7 @@ __global__ __launch_bounds__(256) void mp_gemm_kernel(const float* __restrict__ 
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const int lr2 = 32 * u + mp_frag_row(r, kk);
-          if (q0 + lr2 < q_end) dk[lr2 * 128 + col] = mp_f2key(sv_d2(qn[q0 + lr2], r2, acc[u][r]));
+          if (q0 + lr2 < q_end) dk[lr2 * 128 + col] = mp_f2key(sv_d2_screen(qn[q0 + lr2], r2, acc[u][r]));
         }
     }
     __syncthreads();

@@ -271,7 +271,30 @@ __global__ __launch_bounds__(256) void scatter_topk_kernel(const float* __restri
     idx_out[dst * k + j] = idx[(int64_t)r * k + j];
   }
 }
+// The last kernel of every search (segvlad.h, "Non-finite rows"): a pair whose distance is not < +inf is never listed.  Such
+// values sort behind every finite one (sv_d2 turns a NaN into +inf), so they are the tail of a list: their slots become
+// (+inf, -1), and so does every slot of a query row whose squared norm is not finite -- a row holding NaN or Inf, whatever the
+// passes before made of it.
+__global__ __launch_bounds__(256) void unlisted_slots_kernel(const float* __restrict__ qn, int64_t total, int k, float* __restrict__ d2,
+                                                             int64_t* __restrict__ idx) {
+  const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (j >= total) return;
+  const bool bad_row = !(fabsf(qn[j / k]) < INFINITY);
+  if (bad_row || !(d2[j] < INFINITY)) {
+    d2[j] = INFINITY;
+    idx[j] = -1;
+  }
+}
 }  // extern "C"
+
+static int unlist_nonfinite(segvlad_ctx* ctx, const float* qn, int nq, int k, float* d2, int64_t* idx) {
+  const int64_t total = (int64_t)nq * k;
+  StageScope sc(ctx, "knn_select");
+  hipLaunchKernelGGL(unlisted_slots_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, qn, total, k, d2, idx);
+  SV_HIP(hipGetLastError());
+  sc.count();
+  return SEGVLAD_OK;
+}
 
 // ---- the search plan ----------------------------------------------------------------------------------------------
 constexpr int SV_RATIO = 16, SV_CAP = 8192, SV_RCAP = 512, SV_CHUNK = 16384;
@@ -450,7 +473,7 @@ static SearchPlan plan_search(const segvlad_ctx* ctx, int nq, int k, const void*
 // with the defaults.
 struct PassScalars {
   float c_eps = 0.f, inv_scale = 1.f, rn_max = 0.f, qscale = 1.f;
-  float qmax = 0.f;   // batch preparations: max |q| as read back (NaN / inf when a query holds one: segvlad_range_search looks at it)
+  float qmax = 0.f;   // batch preparations: max |q| over the finite entries, or NaN when a query holds NaN / Inf (segvlad_range_search looks at it)
 };
 
 // Flag block of one pass: [nrows] row flags, 2 counts (flagged rows, second-tier rows: ONE read-back per chunk), [mrows]
@@ -927,13 +950,18 @@ static int prepare_index_planes(segvlad_ctx* ctx, Filter kind) {
   const float* R = ctx->db_rows.as<float>();
   if (ctx->db_rn_max_rows < n) {
     float m = 0.f;
-    SV_TRY(sv_row_norm_max(ctx, ctx->db_norms.as<float>() + ctx->db_rn_max_rows, n - ctx->db_rn_max_rows, &m));
+    SV_TRY(sv_row_norm_max(ctx, ctx->db_norms.as<float>() + ctx->db_rn_max_rows, n - ctx->db_rn_max_rows, &m, /*finite_only=*/true));
     if (m > ctx->db_rn_max) ctx->db_rn_max = m;
     ctx->db_rn_max_rows = n;
   }
   if (kind == Filter::F16 && ctx->db_f16_rows < n) {
     float m_new = 0.f;
-    SV_TRY(sv_maxabs(ctx, R + (size_t)ctx->db_f16_rows * d, (n - ctx->db_f16_rows) * d, &m_new));
+    // The scale is taken over the SAME rows as max ||r||^2 above -- those whose squared norm is finite, the rows that can be listed:
+    // the fp16 error bound (ctx.h, sv_f16_c_eps) rests on max |R| <= max ||r||.  A row that is never listed (it holds NaN / Inf, or
+    // its norm overflowed) may hold finite entries of any size; they are cut at sqrt(max ||r||^2), which every listed row's entries
+    // stay below and which is max |R| itself when all rows are finite.  (Such a row's own plane may overflow: its column is dropped.)
+    SV_TRY(sv_maxabs(ctx, R + (size_t)ctx->db_f16_rows * d, (n - ctx->db_f16_rows) * d, &m_new, /*finite_only=*/true));
+    m_new = std::min(m_new, std::sqrt(ctx->db_rn_max));
     const bool rescale = ctx->db_f16_rows == 0 || m_new * ctx->db_f16_scale >= 32768.f;
     if (m_new > ctx->db_maxabs) ctx->db_maxabs = m_new;
     int64_t r0 = ctx->db_f16_rows;
@@ -1012,6 +1040,8 @@ static int prepare_queries(segvlad_ctx* ctx, const SearchPlan& p, const float* q
     case Prep::BatchF16EarlyL0: {
       SV_TRY(sv_launch_row_sumsq(ctx, q, nq, d, qn));
       float qmax = 0.f;
+      float q2max = 0.f;
+      bool q_nonfinite = false;   // the scale and min ||q||^2 are those of the finite entries / rows: one bad row must not cost the others their plane
       if (p.q2min) {   // both scalars behind one read-back
         SV_TRY(sv_maxabs_and_norm_min_begin(ctx, q, ne, qn, nq));
         if (p.prep == Prep::BatchF16EarlyL0) {
@@ -1020,11 +1050,14 @@ static int prepare_queries(segvlad_ctx* ctx, const SearchPlan& p, const float* q
           Chunk c{q, nullptr, nullptr, qn, p.mrows, nullptr, nullptr, &fb, 0, {}};
           SV_TRY(level0(ctx, p, p.pass, PassScalars{}, c, chunk_path(ctx, p, p.pass, p.mrows)));
         }
-        SV_TRY(sv_maxabs_and_norm_min_end(ctx, ne, nq, &qmax, &q2min));
+        SV_TRY(sv_maxabs_and_norm_min_end(ctx, ne, nq, &qmax, &q2min, &q_nonfinite, &q2max));
       } else {
-        SV_TRY(sv_maxabs(ctx, q, ne, &qmax));
+        SV_TRY(sv_row_norm_max(ctx, qn, nq, &q2max, /*finite_only=*/true));
+        SV_TRY(sv_maxabs(ctx, q, ne, &qmax, /*finite_only=*/true, &q_nonfinite));
       }
-      v.qmax = qmax;
+      // (as for the index: the scale of the rows whose norm is finite -- a bad row's finite entries are cut at the largest finite ||q||)
+      qmax = std::min(qmax, std::sqrt(q2max));
+      v.qmax = q_nonfinite ? NAN : qmax;
       v.qscale = pow2_scale(qmax);
       SV_TRY(sv_launch_to_f16(ctx, q, ne, v.qscale, ctx->s_qf16.as<uint16_t>()));
       v.inv_scale = 1.f / (v.qscale * ctx->db_f16_scale);
@@ -1103,7 +1136,7 @@ int sv_search_dev(segvlad_ctx* ctx, const float* q, int nq, int k, float* d2, in
   if (p.matrix) {
     SV_TRY(sv_launch_row_sumsq(ctx, q, nq, p.d, qn));
     SV_TRY(search_matrix(ctx, q, nq, p.n, p.d, k, qn, d2, idx));
-    return SEGVLAD_OK;
+    return unlist_nonfinite(ctx, qn, nq, k, d2, idx);
   }
   ctx->sstats.filter = (int)p.filter;
   ctx->sstats.levels = p.pass.levels;
@@ -1123,7 +1156,7 @@ int sv_search_dev(segvlad_ctx* ctx, const float* q, int nq, int k, float* d2, in
   // flags list overflows (-> exact distance-matrix path, alone)
   if (fb.flagged && !p.pass.guessed) SV_TRY(fallback_rows(ctx, p, q, qn, fb.rows(), nq, d2, idx));
   else if (fb.flagged) SV_TRY(redo_rows(ctx, p, v, q, qn, fb, d2, idx));
-  return SEGVLAD_OK;
+  return unlist_nonfinite(ctx, qn, nq, k, d2, idx);
 }
 
 // ---- segvlad_range_search ------------------------------------------------------------------------------------------

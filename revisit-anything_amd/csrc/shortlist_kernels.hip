@@ -438,6 +438,7 @@ __global__ __launch_bounds__(256) void sl_final_kernel(const uint64_t* __restric
     if (j < total) {
       dd = sl_key2f((uint32_t)(a[j] >> 32));
       id = (int64_t)(uint32_t)a[j];
+      if (!(dd < INFINITY)) id = -1;   // (never listed: segvlad.h, "Non-finite rows"; sv_d2 has made a NaN +inf)
     }
     d2_out[q * k + j] = dd;
     idx_out[q * k + j] = id;

@@ -251,6 +251,7 @@ __global__ __launch_bounds__(SH_T) void small_head_kernel(const float* __restric
 #endif
   TICK();
   __shared__ uint32_t s_wmax[SH_W];
+  __shared__ uint32_t s_badrow[128];   // (only when the block holds a value >= 2^55) rows whose squared norm is not finite
   __shared__ int s_last;
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, i16 = lane & 15, kq = lane >> 4;
   const int w = blockIdx.x, NW = gridDim.x;
@@ -307,6 +308,24 @@ __global__ __launch_bounds__(SH_T) void small_head_kernel(const float* __restric
   __syncthreads();
 #pragma unroll
   for (int v = 0; v < SH_W; ++v) mx = max(mx, s_wmax[v]);
+  if (mx >= SV_BIG_BITS) {   // (workgroup-uniform) a NaN, an Inf or a huge value: the maximum again, over the rows with a finite norm
+    for (int row = wv; row < m; row += SH_W) {
+      const bool bad = row_norm_bad_(X + (size_t)row * d, d4, lane);
+      if (lane == 0) s_badrow[row] = bad ? 1u : 0u;
+    }
+    __syncthreads();
+    mx = 0;
+#pragma unroll
+    for (int j = 0; j < SH_NX; ++j) {
+      const int idx = tid + SH_T * j;
+      if (idx < n4 && !s_badrow[idx / d4]) mx = max(mx, mag4_(xv[j]));
+    }
+    mx = wave_max_u32_(mx);
+    if (lane == 0) s_wmax[wv] = mx;
+    __syncthreads();
+#pragma unroll
+    for (int v = 0; v < SH_W; ++v) mx = max(mx, s_wmax[v]);
+  }
   float scale = 1.f;
   {   // (query_f16_small_kernel's rule: the largest magnitude lands in [8192, 16384))
     const float maxabs = __uint_as_float(mx);
@@ -400,6 +419,27 @@ __global__ __launch_bounds__(SH_T) void small_head_kernel(const float* __restric
     __syncthreads();
 #pragma unroll
     for (int v = 0; v < SH_W; ++v) mx = max(mx, s_wmax[v]);
+    if (mx >= SV_BIG_BITS) {   // (workgroup-uniform) as in the staged form above
+      for (int row = wv; row < m; row += SH_W) {
+        const bool bad = row_norm_bad_(X + (size_t)row * d, d4, lane);
+        if (lane == 0) s_badrow[row] = bad ? 1u : 0u;
+      }
+      __syncthreads();
+      mx = 0;
+#pragma unroll
+      for (int t = 0; t < FRC; ++t) {
+        const int row = t * 16 + i16;
+        const bool counts = row < m && !s_badrow[min(row, m - 1)];
+#pragma unroll
+        for (int s_ = 0; s_ < STEPS; ++s_)
+          if (s_ < steps_v && counts) mx = max(mx, max(mag4_(xf[t][s_][0]), mag4_(xf[t][s_][1])));
+      }
+      mx = wave_max_u32_(mx);
+      if (lane == 0) s_wmax[wv] = mx;
+      __syncthreads();
+#pragma unroll
+      for (int v = 0; v < SH_W; ++v) mx = max(mx, s_wmax[v]);
+    }
     float scale = 1.f;
     {
       const float maxabs = __uint_as_float(mx);

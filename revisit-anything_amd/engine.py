@@ -815,6 +815,12 @@ class SegVLADEngine:
         return n.value, d.value
 
     def search(self, Q, k: int):
+        """segvlad_search: device tensors (d2 [nq][k] fp32 ascending, idx [nq][k] int64; ties to the lower id, (+inf, -1) beyond the
+        index).  Non-finite rows (an all-zero descriptor normalises to a NaN row) are ordinary input: a pair whose fp32 distance
+        is NaN or +inf is never listed -- an index row holding NaN or +-Inf is in nobody's list, a query row holding one returns
+        (+inf, -1) in every slot, a list with fewer than k finite distances is padded with (+inf, -1) -- and every finite query
+        row gets, bit for bit, what an index of the finite rows alone returns (ids as db_remove would renumber them), at no extra
+        cost.  search_shortlist, search_excluding and search_grouped hold the same rule."""
         q = _as(Q, np.float32, torch.float32)
         nq = q.shape[0]
         d2 = self._empty((nq, k), torch.float32)

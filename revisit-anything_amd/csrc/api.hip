@@ -1,7 +1,8 @@
 // C-ABI of libsegvlad_hip.so (see include/segvlad.h).  Host-side orchestration only: argument
 // checks, host/device pointer staging, scratch sizing and kernel sequencing on the context stream.
-// This unit: context, options, staging, guard mode, stage timers, vocabulary, PCA model, pca_apply, normalise, the small search entry
-// points, vote.  describe.hip: the describe stage (plan_describe and its staged passes); search.hip: the index and the exact search.
+// This unit: context, options, staging, guard mode, stage timers, vocabulary, PCA model, pca_apply, normalise, merge_topk / sims /
+// minmax, vote.  describe.hip: the describe stage (plan_describe and its staged passes); search.hip: the index and the exact search;
+// the searches derived from it (shortlist, match_pairs, excluding, grouped) have their entry points next to their kernels.
 #include <stdarg.h>
 #include <stdlib.h>
 #include <string.h>
@@ -543,176 +544,6 @@ int segvlad_normalize_rows(segvlad_ctx* ctx, const float* X, int n, int d, float
   SV_TRY(sv_out(ctx, Y, (size_t)n * d * sizeof(float), &dy));
   SV_TRY(sv_launch_normalize_rows(ctx, (const float*)dx, n, d, (float*)dy));
   return sv_finish(ctx);
-}
-
-int segvlad_search_shortlist(segvlad_ctx* ctx, const float* Q, int nq, const int32_t* qseg_offsets, int n_img,
-                             const int32_t* shortlist, int M, int k, float* d2_out, int64_t* idx_out) {
-  CHECK_CTX();
-  if (nq < 0 || n_img < 0 || k < 1 || k > 1024 || M < 1 || M > 4096)
-    return ctx->fail(SEGVLAD_ERR_ARG, "search_shortlist: need nq, n_img >= 0, 1<=k<=1024, 1<=M<=4096 (k=%d, M=%d)", k, M);
-  if (!qseg_offsets) return ctx->fail(SEGVLAD_ERR_ARG, "search_shortlist: null qseg_offsets");
-  if (sv_is_device_ptr(qseg_offsets)) return ctx->fail(SEGVLAD_ERR_ARG, "search_shortlist: qseg_offsets must be host memory");
-  if (qseg_offsets[0] != 0 || qseg_offsets[n_img] != nq)
-    return ctx->fail(SEGVLAD_ERR_ARG, "search_shortlist: qseg_offsets must run from 0 to nq=%d", nq);
-  for (int b = 0; b < n_img; ++b)
-    if (qseg_offsets[b + 1] < qseg_offsets[b]) return ctx->fail(SEGVLAD_ERR_ARG, "search_shortlist: qseg_offsets decrease at %d", b);
-  if (ctx->db_d == 0) return ctx->fail(SEGVLAD_ERR_STATE, "search_shortlist: the index is empty and has no dimension yet");
-  if (!ctx->db_has_img) return ctx->fail(SEGVLAD_ERR_STATE, "search_shortlist: no img_of_seg map: give it to segvlad_db_add");
-  if (nq == 0) return SEGVLAD_OK;
-  if (!Q || !shortlist || !d2_out || !idx_out) return ctx->fail(SEGVLAD_ERR_ARG, "search_shortlist: null pointer");
-  const int d = ctx->db_d;
-  if (d % 32 != 0) return ctx->fail(SEGVLAD_ERR_LIMIT, "search_shortlist: d=%d (the exact GEMM takes d %% 32 == 0)", d);
-  if (ctx->db_n > 0x7fffffffll) return ctx->fail(SEGVLAD_ERR_LIMIT, "search_shortlist: more than 2^31 - 1 rows");
-  const void *dq, *dsl;
-  void *dd2, *didx;
-  SV_TRY(sv_in(ctx, Q, (size_t)nq * d * 4, &dq));
-  if ((reinterpret_cast<uintptr_t>(dq) & 15) != 0) {   // (a row-offset view of a device tensor: the GEMM loads 16-byte pieces)
-    SV_HIP(ctx->s_sl_q.reserve((size_t)nq * d * 4));
-    SV_HIP(hipMemcpyAsync(ctx->s_sl_q.p, dq, (size_t)nq * d * 4, hipMemcpyDeviceToDevice, ctx->stream));
-    dq = ctx->s_sl_q.p;
-  }
-  SV_TRY(sv_in(ctx, shortlist, (size_t)n_img * M * 4, &dsl));
-  SV_TRY(sv_out(ctx, d2_out, (size_t)nq * k * 4, &dd2));
-  SV_TRY(sv_out(ctx, idx_out, (size_t)nq * k * 8, &didx));
-  if (ctx->db_n == 0) {   // emptied by segvlad_db_remove: no row is allowed anywhere
-    SV_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(dd2), 0x7f800000, (size_t)nq * k, ctx->stream));
-    SV_HIP(hipMemsetAsync(didx, 0xff, (size_t)nq * k * 8, ctx->stream));
-    return sv_finish(ctx);
-  }
-  SV_HIP(ctx->s_qnorm.reserve((size_t)nq * 4));
-  SV_TRY(sv_launch_row_sumsq(ctx, (const float*)dq, nq, d, ctx->s_qnorm.as<float>()));
-  SV_TRY(sv_search_shortlist(ctx, (const float*)dq, nq, ctx->s_qnorm.as<float>(), qseg_offsets, n_img, (const int32_t*)dsl, M, k,
-                             (float*)dd2, (int64_t*)didx));
-  return sv_finish(ctx);
-}
-
-int segvlad_match_pairs(segvlad_ctx* ctx, const float* Q, int nq, const int32_t* qseg_offsets, int n_img, const int32_t* cand, int C,
-                        float max_d2, int32_t* n_mutual_out, double* score_out, int32_t* order_out, int64_t* fwd_idx_out,
-                        float* fwd_d2_out, uint8_t* mutual_out) {
-  CHECK_CTX();
-  if (nq < 0 || n_img < 0 || C < 1 || C > 64)
-    return ctx->fail(SEGVLAD_ERR_ARG, "match_pairs: need nq, n_img >= 0, 1<=C<=64 (C=%d)", C);
-  if (!qseg_offsets) return ctx->fail(SEGVLAD_ERR_ARG, "match_pairs: null qseg_offsets");
-  if (sv_is_device_ptr(qseg_offsets)) return ctx->fail(SEGVLAD_ERR_ARG, "match_pairs: qseg_offsets must be host memory");
-  if (qseg_offsets[0] != 0 || qseg_offsets[n_img] != nq)
-    return ctx->fail(SEGVLAD_ERR_ARG, "match_pairs: qseg_offsets must run from 0 to nq=%d", nq);
-  for (int b = 0; b < n_img; ++b)
-    if (qseg_offsets[b + 1] < qseg_offsets[b]) return ctx->fail(SEGVLAD_ERR_ARG, "match_pairs: qseg_offsets decrease at %d", b);
-  if (n_img > 0 && !cand) return ctx->fail(SEGVLAD_ERR_ARG, "match_pairs: null cand");
-  if (cand && sv_is_device_ptr(cand)) return ctx->fail(SEGVLAD_ERR_ARG, "match_pairs: cand must be host memory");
-  if (ctx->db_d == 0) return ctx->fail(SEGVLAD_ERR_STATE, "match_pairs: the index is empty and has no dimension yet");
-  if (!ctx->db_has_img) return ctx->fail(SEGVLAD_ERR_STATE, "match_pairs: no img_of_seg map: give it to segvlad_db_add");
-  if (n_img == 0) return SEGVLAD_OK;   // (then nq == 0 too: nothing to write)
-  if ((nq > 0 && !Q) || !n_mutual_out || !score_out) return ctx->fail(SEGVLAD_ERR_ARG, "match_pairs: null pointer");
-  const int d = ctx->db_d;
-  if (nq > 0 && d % 32 != 0) return ctx->fail(SEGVLAD_ERR_LIMIT, "match_pairs: d=%d (the exact GEMM takes d %% 32 == 0)", d);
-  if (ctx->db_n > 0x7fffffffll) return ctx->fail(SEGVLAD_ERR_LIMIT, "match_pairs: more than 2^31 - 1 rows");
-  const void* dq = nullptr;
-  void *dn, *ds, *dord = nullptr, *dfi = nullptr, *dfd = nullptr, *dmu = nullptr;
-  SV_TRY(sv_out(ctx, n_mutual_out, (size_t)n_img * C * 4, &dn));
-  SV_TRY(sv_out(ctx, score_out, (size_t)n_img * C * 8, &ds));
-  if (order_out) SV_TRY(sv_out(ctx, order_out, (size_t)n_img * C * 4, &dord));
-  if (nq > 0) {   // (no query rows at all: every image is empty, the finish pass alone writes the zeros and the order)
-    SV_TRY(sv_in(ctx, Q, (size_t)nq * d * 4, &dq));
-    if ((reinterpret_cast<uintptr_t>(dq) & 15) != 0) {   // (a row-offset view of a device tensor: the GEMM loads 16-byte pieces)
-      SV_HIP(ctx->s_sl_q.reserve((size_t)nq * d * 4));
-      SV_HIP(hipMemcpyAsync(ctx->s_sl_q.p, dq, (size_t)nq * d * 4, hipMemcpyDeviceToDevice, ctx->stream));
-      dq = ctx->s_sl_q.p;
-    }
-    if (fwd_idx_out) SV_TRY(sv_out(ctx, fwd_idx_out, (size_t)nq * C * 8, &dfi));
-    if (fwd_d2_out) SV_TRY(sv_out(ctx, fwd_d2_out, (size_t)nq * C * 4, &dfd));
-    if (mutual_out) SV_TRY(sv_out(ctx, mutual_out, (size_t)nq * C, &dmu));
-    SV_HIP(ctx->s_qnorm.reserve((size_t)nq * 4));
-    SV_TRY(sv_launch_row_sumsq(ctx, (const float*)dq, nq, d, ctx->s_qnorm.as<float>()));
-  }
-  SV_TRY(sv_match_pairs(ctx, (const float*)dq, nq, ctx->s_qnorm.as<float>(), qseg_offsets, n_img, cand, C, max_d2, (int32_t*)dn,
-                        (double*)ds, (int32_t*)dord, (int64_t*)dfi, (float*)dfd, (uint8_t*)dmu));
-  return sv_finish(ctx);
-}
-
-int segvlad_search_excluding(segvlad_ctx* ctx, const float* Q, int nq, const int32_t* qseg_offsets, int n_img,
-                             const int32_t* excl, int E, int k, float* d2_out, int64_t* idx_out) {
-  CHECK_CTX();
-  if (nq < 0 || n_img < 0 || k < 1 || k > 1024 || E < 1 || E > SV_EX_MAX_E)
-    return ctx->fail(SEGVLAD_ERR_ARG, "search_excluding: need nq, n_img >= 0, 1<=k<=1024, 1<=E<=%d (k=%d, E=%d)", SV_EX_MAX_E, k, E);
-  if (!qseg_offsets) return ctx->fail(SEGVLAD_ERR_ARG, "search_excluding: null qseg_offsets");
-  if (sv_is_device_ptr(qseg_offsets)) return ctx->fail(SEGVLAD_ERR_ARG, "search_excluding: qseg_offsets must be host memory");
-  if (qseg_offsets[0] != 0 || qseg_offsets[n_img] != nq)
-    return ctx->fail(SEGVLAD_ERR_ARG, "search_excluding: qseg_offsets must run from 0 to nq=%d", nq);
-  for (int b = 0; b < n_img; ++b)
-    if (qseg_offsets[b + 1] < qseg_offsets[b]) return ctx->fail(SEGVLAD_ERR_ARG, "search_excluding: qseg_offsets decrease at %d", b);
-  if (n_img > 0 && !excl) return ctx->fail(SEGVLAD_ERR_ARG, "search_excluding: null excl");
-  if (excl && sv_is_device_ptr(excl)) return ctx->fail(SEGVLAD_ERR_ARG, "search_excluding: excl must be host memory");
-  if (ctx->db_d == 0) return ctx->fail(SEGVLAD_ERR_STATE, "search_excluding: the index is empty and has no dimension yet");
-  if (!ctx->db_has_img) return ctx->fail(SEGVLAD_ERR_STATE, "search_excluding: no img_of_seg map: give it to segvlad_db_add");
-  const int d = ctx->db_d;
-  if (d % 32 != 0) return ctx->fail(SEGVLAD_ERR_LIMIT, "search_excluding: d=%d (the exact GEMM of the tail takes d %% 32 == 0)", d);
-  if (ctx->db_n > 0x7fffffffll) return ctx->fail(SEGVLAD_ERR_LIMIT, "search_excluding: more than 2^31 - 1 rows");
-  if (ctx->opt.debug_fail_search == 1) return ctx->fail(SEGVLAD_ERR_STATE, "search_excluding: failing on request (option debug_fail_search)");
-  ctx->ex_stats[0] = ctx->ex_stats[1] = ctx->ex_stats[2] = ctx->ex_stats[3] = 0;
-  ctx->ex_short_dev = nullptr;
-  if (nq == 0) return SEGVLAD_OK;
-  if (!Q || !d2_out || !idx_out) return ctx->fail(SEGVLAD_ERR_ARG, "search_excluding: null pointer");
-  const void* dq;
-  void *dd2, *didx;
-  SV_TRY(sv_in(ctx, Q, (size_t)nq * d * 4, &dq));
-  SV_TRY(sv_out(ctx, d2_out, (size_t)nq * k * 4, &dd2));
-  SV_TRY(sv_out(ctx, idx_out, (size_t)nq * k * 8, &didx));
-  if (ctx->db_n == 0) {   // emptied by segvlad_db_remove: no row is allowed anywhere
-    ctx->ex_stats[0] = k;
-    SV_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(dd2), 0x7f800000, (size_t)nq * k, ctx->stream));
-    SV_HIP(hipMemsetAsync(didx, 0xff, (size_t)nq * k * 8, ctx->stream));
-    return sv_finish(ctx);
-  }
-  SV_TRY(sv_search_excluding(ctx, (const float*)dq, nq, qseg_offsets, n_img, excl, E, k, (float*)dd2, (int64_t*)didx));
-  return sv_finish(ctx);
-}
-
-int segvlad_exclude_stats(segvlad_ctx* ctx, int64_t* stats_out, int n) {
-  CHECK_CTX();
-  if (!stats_out || n < 0) return ctx->fail(SEGVLAD_ERR_ARG, "exclude_stats: bad arguments");
-  if (ctx->ex_short_dev) {   // the rows the last call's tail finished: fetched once
-    uint32_t w = 0;
-    SV_HIP(hipMemcpyAsync(&w, ctx->ex_short_dev, 4, hipMemcpyDeviceToHost, ctx->stream));
-    SV_HIP(hipStreamSynchronize(ctx->stream));
-    ctx->ex_stats[2] = w;
-    ctx->ex_short_dev = nullptr;
-  } else {
-    SV_HIP(hipStreamSynchronize(ctx->stream));
-  }
-  for (int i = 0; i < n && i < 4; ++i) stats_out[i] = ctx->ex_stats[i];
-  return SEGVLAD_OK;
-}
-
-int segvlad_search_grouped(segvlad_ctx* ctx, const float* Q, int nq, int k, int per_image, float* d2_out, int64_t* idx_out) {
-  CHECK_CTX();
-  if (nq < 0 || k < 1 || k > 1024 || per_image < 1 || per_image > 16)
-    return ctx->fail(SEGVLAD_ERR_ARG, "search_grouped: need nq >= 0, 1<=k<=1024, 1<=per_image<=16 (k=%d, per_image=%d)", k, per_image);
-  if (ctx->db_d == 0) return ctx->fail(SEGVLAD_ERR_STATE, "search_grouped: the index is empty and has no dimension yet");
-  if (!ctx->db_has_img) return ctx->fail(SEGVLAD_ERR_STATE, "search_grouped: no img_of_seg map: give it to segvlad_db_add");
-  if (ctx->db_n > 0xffffffffLL) return ctx->fail(SEGVLAD_ERR_LIMIT, "search_grouped: %lld index rows (candidate ids are 32-bit)", (long long)ctx->db_n);
-  ctx->gr_stats[0] = ctx->gr_stats[1] = ctx->gr_stats[2] = 0;
-  if (nq == 0) return SEGVLAD_OK;
-  if (!Q || !d2_out || !idx_out) return ctx->fail(SEGVLAD_ERR_ARG, "search_grouped: null pointer");
-  const void* dq;
-  void *dd2, *didx;
-  SV_TRY(sv_in(ctx, Q, (size_t)nq * ctx->db_d * 4, &dq));
-  SV_TRY(sv_out(ctx, d2_out, (size_t)nq * k * 4, &dd2));
-  SV_TRY(sv_out(ctx, idx_out, (size_t)nq * k * 8, &didx));
-  if (ctx->db_n == 0) {   // emptied by segvlad_db_remove: no row anywhere
-    SV_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(dd2), 0x7f800000, (size_t)nq * k, ctx->stream));
-    SV_HIP(hipMemsetAsync(didx, 0xff, (size_t)nq * k * 8, ctx->stream));
-    return sv_finish(ctx);
-  }
-  SV_TRY(sv_search_grouped(ctx, (const float*)dq, nq, k, per_image, (float*)dd2, (int64_t*)didx));
-  return sv_finish(ctx);
-}
-
-int segvlad_group_stats(segvlad_ctx* ctx, int64_t* stats_out, int n) {
-  if (!ctx) return SEGVLAD_ERR_ARG;
-  if (!stats_out || n < 0) return ctx->fail(SEGVLAD_ERR_ARG, "group_stats: bad arguments");
-  for (int i = 0; i < n && i < 3; ++i) stats_out[i] = ctx->gr_stats[i];
-  return SEGVLAD_OK;
 }
 
 int segvlad_merge_topk(segvlad_ctx* ctx, const float* d2_parts, const int64_t* idx_parts, int nq, int parts, int k,

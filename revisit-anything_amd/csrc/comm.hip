@@ -321,8 +321,7 @@ int segvlad_search_sharded(segvlad_ctx* ctx, const float* Q, int nq, int k, int6
     }                                                                                                       \
   } while (0)
   if (ctx->db_n <= 0 || local_rc != SEGVLAD_OK) {   // an empty (or failed) shard contributes (inf, -1)
-    SV_PRE(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(ld2), 0x7f800000, (size_t)total, ctx->stream));
-    SV_PRE(hipMemsetAsync(lidx, 0xff, (size_t)total * 8, ctx->stream));
+    SV_PRE(sv_fill_none(ctx, ld2, lidx, (size_t)total));
   }
   void *od, *oi;
   int rc_out = sv_out(ctx, d2_out, (size_t)total * 4, &od);

@@ -350,14 +350,15 @@ struct segvlad_ctx {
   X(db_hi) X(db_lo) X(db_f16) X(s_ref_keys) X(s_ref_tick) X(s_tail_tick) X(sl_img_off) X(sl_img_rows)
   //  scratch: grow-only, reused across calls, nothing in them is read after the call that wrote it; s_sh_*: exchange buffers of
   //  the row-sharded index (comm.hip); s_rm_*: removal flags, block counts / offsets and the source of every surviving row
-  //  (remove_kernels.hip); s_ex_*: the deep lists, row flags (+ the short-row counter), query norms and the tail's slot results of
-  //  segvlad_search_excluding (exclude_kernels.hip); s_rs_*: segvlad_range_search (range_kernels.hip) -- the effective radii and
-  //  filter thresholds, the long-row flags (+ the query preparation's flag block), per-row hit counts, where a short row's ordered
-  //  words sit in s_rs_stage, the long rows' offsets / cursors / words before and after their ordering, the dense query block of
-  //  the exact sweeps, the device lims of a host caller and a few counters; s_mp_min: segvlad_match_pairs (match_kernels.hip) --
-  //  the row minima [nq][C], then the live slots' column minima, 64-bit keys; s_gr_*: segvlad_search_grouped (group_kernels.hip) --
-  //  the deep lists, the counters + row flags, query norms, and the exact tail's open rows, their dense query block, a batch's
-  //  slots / word offsets, cursors, words before and after their ordering, per-image counts
+  //  (remove_kernels.hip); s_deep_*: the deep lists of the inner search and the query norms of segvlad_search_excluding and
+  //  segvlad_search_grouped (one call at a time uses them); s_ex_*: the row flags (+ the short-row counter, which
+  //  segvlad_exclude_stats reads after the call) and the tail's slot results of segvlad_search_excluding (exclude_kernels.hip);
+  //  s_rs_*: segvlad_range_search (range_kernels.hip) -- the effective radii and filter thresholds, the long-row flags (+ the query
+  //  preparation's flag block), per-row hit counts, where a short row's ordered words sit in s_rs_stage, the long rows' offsets /
+  //  cursors / words before and after their ordering, the dense query block of the exact sweeps, the device lims of a host caller
+  //  and a few counters; s_mp_min: segvlad_match_pairs (match_kernels.hip) -- the row minima [nq][C], then the live slots' column
+  //  minima, 64-bit keys; s_gr_*: segvlad_search_grouped (group_kernels.hip) -- the counters + row flags, and the exact tail's open
+  //  rows, their dense query block, a batch's slots / word offsets, cursors, words before and after their ordering, per-image counts
 #define SV_SCRATCH_BUFS(X)                                                                                                       \
   X(s_xt) X(s_labels) X(s_rnorm) X(s_gap) X(s_colmask) X(s_gscale) X(s_segimg) X(s_segoff) X(s_adjoff) X(s_dist) X(s_qnorm)      \
   X(s_misc) X(s_minmax) X(s_voteoff) X(s_cand_cnt) X(s_cand_d2) X(s_cand_id) X(s_thr_d2) X(s_thr_idx) X(s_flag) X(s_qh) X(s_ql)  \
@@ -366,12 +367,12 @@ struct segvlad_ctx {
   X(s_sel_todo) X(s_vote_keys) X(s_pz) X(s_rowbase) X(s_tilegrp) X(s_phys) X(s_covcnt) X(s_bn) X(s_l0part) X(s_ref_lim) X(s_sh_d2) X(s_sh_idx)          \
   X(s_sh_rec) X(s_sh_all) X(s_sh_d2c) X(s_sh_idc) X(s_grp_cnt) X(s_grp_ids) X(s_grp_rows) X(s_grp_keys) X(s_grp_work) X(s_grp_pos) X(s_tnk_redo) X(s_tail_part) X(s_km_part) X(s_km_cnt) X(s_kflush) \
   X(s_sl_misc) X(s_sl_q) X(s_sl_cur) X(s_sl_uids) X(s_sl_uoff) X(s_sl_unum) X(s_sl_cand) X(s_sl_lens)                            \
-  X(s_ex_d2) X(s_ex_idx) X(s_ex_flag) X(s_ex_qn) X(s_ex_td2) X(s_ex_tidx)                                                          \
+  X(s_deep_d2) X(s_deep_idx) X(s_deep_qn) X(s_ex_flag) X(s_ex_td2) X(s_ex_tidx)                                                        \
   X(s_rm_row) X(s_rm_img) X(s_rm_blk) X(s_rm_src) X(s_rm_misc)                                                                    \
   X(s_rs_thr) X(s_rs_flag) X(s_rs_fb) X(s_rs_cnt) X(s_rs_soff) X(s_rs_stage) X(s_rs_loff) X(s_rs_cur) X(s_rs_words) X(s_rs_sorted)  \
   X(s_rs_tmp) X(s_rs_rows) X(s_rs_q) X(s_rs_misc)                                                                                 \
   X(s_mp_min)                                                                                                                      \
-  X(s_gr_d2) X(s_gr_idx) X(s_gr_flag) X(s_gr_qn) X(s_gr_rows) X(s_gr_q) X(s_gr_plan) X(s_gr_cur) X(s_gr_words) X(s_gr_sorted) X(s_gr_tab)
+  X(s_gr_flag) X(s_gr_rows) X(s_gr_q) X(s_gr_plan) X(s_gr_cur) X(s_gr_words) X(s_gr_sorted) X(s_gr_tab)
 #define SV_DECL_BUF(n) DevBuf n;
   SV_PERSISTENT_BUFS(SV_DECL_BUF)
   SV_SCRATCH_BUFS(SV_DECL_BUF)
@@ -615,11 +616,8 @@ int sv_launch_sims(segvlad_ctx* ctx, const float* d2, const int64_t* idx, int nq
                    int64_t* idx_out);
 int sv_launch_minmax(segvlad_ctx* ctx, const float* sims, int64_t count, float* minmax_dev);
 
-// shortlist_kernels.hip: the largest id of img_dev[0, n) (synchronises), and segvlad_search_shortlist after its checks (Q on the
-// device and 16-byte aligned, qn its squared norms, qoff host, shortlist / outputs on the device)
+// shortlist_kernels.hip: the largest id of img_dev[0, n) (synchronises)
 int sv_img_max(segvlad_ctx* ctx, const int32_t* img_dev, int64_t n, int* out);
-int sv_search_shortlist(segvlad_ctx* ctx, const float* Q, int nq, const float* qn, const int32_t* qoff, int n_img,
-                        const int32_t* shortlist, int M, int k, float* d2_out, int64_t* idx_out);
 
 // search.hip: segvlad_search behind its checks and staging (q / d2 / idx on the device, nq >= 1, the index has a dimension)
 int sv_search_dev(segvlad_ctx* ctx, const float* q, int nq, int k, float* d2, int64_t* idx);
@@ -631,19 +629,15 @@ int sv_sl_map_host(segvlad_ctx* ctx);
 int sv_launch_exclude_tail(segvlad_ctx* ctx, const float* Q, const float* qn, const int32_t* groups, int ng, int gmax, int n_slots,
                            const uint32_t* unum, const uint32_t* uoff, const uint32_t* ustart, int n_tab, const uint32_t* flags,
                            int k, float* d2_tmp, int64_t* idx_tmp);
-// exclude_kernels.hip: segvlad_search_excluding after the argument checks (Q on the device, qoff / excl host, outputs on the device)
-int sv_search_excluding(segvlad_ctx* ctx, const float* Q, int nq, const int32_t* qoff, int n_img, const int32_t* excl, int E, int k,
-                        float* d2_out, int64_t* idx_out);
 
-// group_kernels.hip: segvlad_search_grouped after the argument checks (Q / outputs on the device, nq >= 1, the index holds rows
-// and an img_of_seg map); fills ctx->gr_stats; synchronises
-int sv_search_grouped(segvlad_ctx* ctx, const float* Q, int nq, int k, int per_image, float* d2_out, int64_t* idx_out);
-
-// match_kernels.hip: segvlad_match_pairs after the argument checks (Q on the device and 16-byte aligned, qn its squared norms, qoff /
-// cand host, outputs on the device; order_out / fwd_idx_out / fwd_d2_out / mutual_out may be null)
-int sv_match_pairs(segvlad_ctx* ctx, const float* Q, int nq, const float* qn, const int32_t* qoff, int n_img, const int32_t* cand, int C,
-                   float max_d2, int32_t* n_mutual_out, double* score_out, int32_t* order_out, int64_t* fwd_idx_out, float* fwd_d2_out,
-                   uint8_t* mutual_out);
+// search.hip: the entry preamble of the searches derived from segvlad_search; `entry` is the name the messages start with.
+// SEGVLAD_ERR_ARG unless qseg_offsets [n_img + 1] is there, host memory, runs from 0 to nq and never decreases; SEGVLAD_ERR_STATE
+// unless the index has a dimension and an img_of_seg map; *out = dq [nq][db_d] itself or -- a row-offset view of a device tensor,
+// off the 16-byte boundary the exact GEMMs load by -- its copy in ctx->s_sl_q; every one of n slots (+inf, -1): an emptied index
+int sv_check_qseg_offsets(segvlad_ctx* ctx, const char* entry, const int32_t* qseg_offsets, int n_img, int nq);
+int sv_check_img_index(segvlad_ctx* ctx, const char* entry);
+int sv_aligned_queries(segvlad_ctx* ctx, const float* dq, int nq, const float** out);
+hipError_t sv_fill_none(segvlad_ctx* ctx, float* d2, int64_t* idx, size_t n);
 
 // range_kernels.hip (segvlad_range_search; see the kernels): thresholds and long-row flags from the radii; one chunk's list
 // statistics out_dev = {stage words needed, sum, max, long rows}; the exact evaluation + ordering of the short rows' lists into

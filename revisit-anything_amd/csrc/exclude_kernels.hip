@@ -8,7 +8,7 @@
 //                   change).  k_fetch = min(1024, k + max_b X_b).  No read-back per call
 //   inner search    segvlad_search's body, unchanged, at depth k_fetch into scratch.  A list of k_fetch entries holds at most X_b
 //                   excluded ones: where k + X_b <= k_fetch the first k allowed entries of the list ARE the answer
-//   ex_compact_kernel   one wave per query row: walks the row's k_fetch entries in order, drops those whose image (db_img) lies in
+//   ex_compact_kernel   one wave per row walks (list_walk_dev.h) the k_fetch entries in order, drops those whose image (db_img) lies in
 //                   one of the image's merged intervals, writes the first k kept in their order -- a subsequence of a (distance, id)
 //                   ordered list is ordered -- and (+inf, -1) behind them.  A row that kept k, or whose list ran into the index's
 //                   end (a -1 slot), or whose image has k + X_b <= k_fetch is complete; any other row is SHORT: flagged and counted
@@ -19,11 +19,13 @@
 //                   row leaves at once, nothing is read back.  sl_final_kernel orders the lists, ex_scatter_kernel moves the flagged
 //                   rows' results into place.  This is the correctness backstop, not the fast path: a group that runs streams the
 //                   allowed part of the index in fp32 once (4 GB at 1 M x 1024).
+// The entry points (segvlad_search_excluding, segvlad_exclude_stats) are at the end of this file.
 #include <algorithm>
 #include <utility>
 #include <vector>
 
 #include "ctx.h"
+#include "list_walk_dev.h"
 
 namespace {
 
@@ -49,42 +51,20 @@ __global__ __launch_bounds__(256) void ex_compact_kernel(const float* __restrict
     else a = mid + 1;
   }
   const ExImg im = imgs[a - 1];
-  const float* sd = d2f + (size_t)q * kf;
-  const int64_t* si = idxf + (size_t)q * kf;
-  float* od = d2_out + (size_t)q * k;
-  int64_t* oi = idx_out + (size_t)q * k;
-  int kept = 0;
-  bool ended = false;
-  for (int c = 0; c < kf && kept < k; c += 64) {
-    const int j = c + l;
-    int64_t id = -1;
-    float dd = INFINITY;
-    if (j < kf) {
-      id = si[j];
-      dd = sd[j];
-    }
+  const SvListArrays list = {d2f + (size_t)q * kf, idxf + (size_t)q * kf, kf};
+  // the rule: an entry is kept unless its image lies in one of the merged intervals
+  const auto w = sv_list_walk(list, [&](int64_t id, bool real) {
     bool keep = false;
-    if (id >= 0) {
+    if (real) {
       const int g = db_img[id];
       keep = true;
 #pragma unroll
       for (int e = 0; e < SV_EX_MAX_E; ++e) keep = keep && !(g >= im.lo[e] && g <= im.hi[e]);
     }
-    ended = ended || __builtin_amdgcn_ballot_w64(j < kf && id < 0) != 0ull;
-    const uint64_t mk = __builtin_amdgcn_ballot_w64(keep);
-    const int pos = kept + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mk >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mk, 0u));
-    if (keep && pos < k) {
-      od[pos] = dd;
-      oi[pos] = id;
-    }
-    kept += (int)__popcll(mk);
-  }
-  for (int j = min(kept, k) + l; j < k; j += 64) {
-    od[j] = INFINITY;
-    oi[j] = -1;
-  }
+    return keep;
+  }, k, l, d2_out + (size_t)q * k, idx_out + (size_t)q * k);
   if (flags && l == 0) {
-    const bool is_short = kept < k && !ended && !im.safe;
+    const bool is_short = w.kept < k && !w.ended && !im.safe;
     flags[q] = is_short ? 1u : 0u;
     if (is_short) atomicAdd(n_short, 1u);
   }
@@ -122,8 +102,9 @@ int merge_intervals(const int32_t* iv, int E, int nimg, std::pair<int, int>* out
 
 }   // namespace
 
-int sv_search_excluding(segvlad_ctx* ctx, const float* Q, int nq, const int32_t* qoff, int n_img, const int32_t* excl, int E, int k,
-                        float* d2_out, int64_t* idx_out) {
+// segvlad_search_excluding after the argument checks: Q on the device, qoff / excl host, outputs on the device, the index holds rows
+static int search_excluding(segvlad_ctx* ctx, const float* Q, int nq, const int32_t* qoff, int n_img, const int32_t* excl, int E, int k,
+                            float* d2_out, int64_t* idx_out) {
   const int d = ctx->db_d;
   SV_TRY(sv_sl_map_host(ctx));
   const int nimg = ctx->db_img_max + 1;
@@ -145,14 +126,12 @@ int sv_search_excluding(segvlad_ctx* ctx, const float* Q, int nq, const int32_t*
     }
   }
   const int kf = (int)std::min<int64_t>(1024, k + xmax);
-  ctx->ex_stats[0] = kf;
+  ctx->ex_stats[0] = kf;   // ([2] and ctx->ex_short_dev: cleared by the entry point)
   ctx->ex_stats[1] = xmax;
-  ctx->ex_stats[2] = 0;
   ctx->ex_stats[3] = n_excl;
-  ctx->ex_short_dev = nullptr;
   if (xmax == 0) return sv_search_dev(ctx, Q, nq, k, d2_out, idx_out);   // nothing is excluded anywhere: the plain search
 
-  // images that can leave a row short, their groups (as sv_search_shortlist's) and allowed ranges of map positions
+  // images that can leave a row short, their groups (as segvlad_search_shortlist's) and allowed ranges of map positions
   std::vector<int32_t> groups, slot_q;
   std::vector<uint32_t> unum, uoff, ustart;
   int gmax = 0, n_slots = 0;
@@ -193,9 +172,9 @@ int sv_search_excluding(segvlad_ctx* ctx, const float* Q, int nq, const int32_t*
     return ctx->fail(SEGVLAD_ERR_LIMIT, "search_excluding: the index holds rows with negative image ids, which the exact tail's "
                      "image -> row map does not cover (a window of %lld rows at k=%d needs the tail)", (long long)xmax, k);
 
-  SV_HIP(ctx->s_ex_d2.reserve((size_t)nq * kf * 4));
-  SV_HIP(ctx->s_ex_idx.reserve((size_t)nq * kf * 8));
-  SV_TRY(sv_search_dev(ctx, Q, nq, kf, ctx->s_ex_d2.as<float>(), ctx->s_ex_idx.as<int64_t>()));
+  SV_HIP(ctx->s_deep_d2.reserve((size_t)nq * kf * 4));
+  SV_HIP(ctx->s_deep_idx.reserve((size_t)nq * kf * 8));
+  SV_TRY(sv_search_dev(ctx, Q, nq, kf, ctx->s_deep_d2.as<float>(), ctx->s_deep_idx.as<int64_t>()));
 
   // launch metadata in one copy: qoff [n_img + 1], then the images' records
   static_assert(sizeof(ExImg) % 4 == 0, "records follow the offsets as int32 words");
@@ -218,36 +197,32 @@ int sv_search_excluding(segvlad_ctx* ctx, const float* Q, int nq, const int32_t*
   uint32_t *flags = nullptr, *n_short = nullptr;
   if (tail) {   // word 0: the short-row counter (segvlad_exclude_stats), words 4 ..: the rows' flags
     SV_HIP(ctx->s_ex_flag.reserve(((size_t)nq + 4) * 4));
-    SV_HIP(ctx->s_ex_qn.reserve((size_t)nq * 4));
+    SV_HIP(ctx->s_deep_qn.reserve((size_t)nq * 4));
     SV_HIP(ctx->s_ex_td2.reserve((size_t)n_slots * k * 4));
     SV_HIP(ctx->s_ex_tidx.reserve((size_t)n_slots * k * 8));
     n_short = ctx->s_ex_flag.as<uint32_t>();
     flags = n_short + 4;
   }
   const float* Qt = Q;   // the tail's GEMM loads 16-byte pieces: a row-offset view of a device tensor is copied for it
-  if (tail && (reinterpret_cast<uintptr_t>(Q) & 15) != 0) {
-    SV_HIP(ctx->s_sl_q.reserve((size_t)nq * d * 4));
-    SV_HIP(hipMemcpyAsync(ctx->s_sl_q.p, Q, (size_t)nq * d * 4, hipMemcpyDeviceToDevice, ctx->stream));
-    Qt = ctx->s_sl_q.as<float>();
-  }
+  if (tail) SV_TRY(sv_aligned_queries(ctx, Q, nq, &Qt));
   {
     StageScope sc(ctx, "knn_exclude");
     if (tail) {
       SV_HIP(hipMemsetAsync(n_short, 0, 4, ctx->stream));
       // (from Q itself, not the copy: the norms of a view that is not 16-byte aligned are summed in another order, and the tail's
       //  rows must carry the values segvlad_search gives the same pointer)
-      SV_TRY(sv_launch_row_sumsq(ctx, Q, nq, d, ctx->s_ex_qn.as<float>()));
+      SV_TRY(sv_launch_row_sumsq(ctx, Q, nq, d, ctx->s_deep_qn.as<float>()));
       sc.count();
     }
-    hipLaunchKernelGGL(ex_compact_kernel, dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, ctx->stream, ctx->s_ex_d2.as<float>(),
-                       ctx->s_ex_idx.as<int64_t>(), nq, kf, k, dqoff, n_img, dimgs, ctx->db_img.as<int32_t>(), d2_out, idx_out, flags,
+    hipLaunchKernelGGL(ex_compact_kernel, dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, ctx->stream, ctx->s_deep_d2.as<float>(),
+                       ctx->s_deep_idx.as<int64_t>(), nq, kf, k, dqoff, n_img, dimgs, ctx->db_img.as<int32_t>(), d2_out, idx_out, flags,
                        n_short);
     SV_HIP(hipGetLastError());
     sc.count();
     if (tail) {
       const void* dslot;
       SV_TRY(sv_in(ctx, slot_q.data(), (size_t)n_slots * 4, &dslot));
-      SV_TRY(sv_launch_exclude_tail(ctx, Qt, ctx->s_ex_qn.as<float>(), groups.data(), (int)(groups.size() / 4), gmax, n_slots,
+      SV_TRY(sv_launch_exclude_tail(ctx, Qt, ctx->s_deep_qn.as<float>(), groups.data(), (int)(groups.size() / 4), gmax, n_slots,
                                     unum.data(), uoff.data(), ustart.data(), (int)unum.size(), flags, k, ctx->s_ex_td2.as<float>(),
                                     ctx->s_ex_tidx.as<int64_t>()));
       hipLaunchKernelGGL(ex_scatter_kernel, dim3((unsigned)n_slots), dim3(64), 0, ctx->stream, (const int32_t*)dslot, flags, k,
@@ -257,5 +232,52 @@ int sv_search_excluding(segvlad_ctx* ctx, const float* Q, int nq, const int32_t*
       ctx->ex_short_dev = n_short;
     }
   }
+  return SEGVLAD_OK;
+}
+
+extern "C" int segvlad_search_excluding(segvlad_ctx* ctx, const float* Q, int nq, const int32_t* qseg_offsets, int n_img,
+                                        const int32_t* excl, int E, int k, float* d2_out, int64_t* idx_out) {
+  CHECK_CTX();
+  if (nq < 0 || n_img < 0 || k < 1 || k > 1024 || E < 1 || E > SV_EX_MAX_E)
+    return ctx->fail(SEGVLAD_ERR_ARG, "search_excluding: need nq, n_img >= 0, 1<=k<=1024, 1<=E<=%d (k=%d, E=%d)", SV_EX_MAX_E, k, E);
+  SV_TRY(sv_check_qseg_offsets(ctx, "search_excluding", qseg_offsets, n_img, nq));
+  if (n_img > 0 && !excl) return ctx->fail(SEGVLAD_ERR_ARG, "search_excluding: null excl");
+  if (excl && sv_is_device_ptr(excl)) return ctx->fail(SEGVLAD_ERR_ARG, "search_excluding: excl must be host memory");
+  SV_TRY(sv_check_img_index(ctx, "search_excluding"));
+  const int d = ctx->db_d;
+  if (d % 32 != 0) return ctx->fail(SEGVLAD_ERR_LIMIT, "search_excluding: d=%d (the exact GEMM of the tail takes d %% 32 == 0)", d);
+  if (ctx->db_n > 0x7fffffffll) return ctx->fail(SEGVLAD_ERR_LIMIT, "search_excluding: more than 2^31 - 1 rows");
+  if (ctx->opt.debug_fail_search == 1) return ctx->fail(SEGVLAD_ERR_STATE, "search_excluding: failing on request (option debug_fail_search)");
+  ctx->ex_stats[0] = ctx->ex_stats[1] = ctx->ex_stats[2] = ctx->ex_stats[3] = 0;
+  ctx->ex_short_dev = nullptr;
+  if (nq == 0) return SEGVLAD_OK;
+  if (!Q || !d2_out || !idx_out) return ctx->fail(SEGVLAD_ERR_ARG, "search_excluding: null pointer");
+  const void* dq;
+  void *dd2, *didx;
+  SV_TRY(sv_in(ctx, Q, (size_t)nq * d * 4, &dq));
+  SV_TRY(sv_out(ctx, d2_out, (size_t)nq * k * 4, &dd2));
+  SV_TRY(sv_out(ctx, idx_out, (size_t)nq * k * 8, &didx));
+  if (ctx->db_n == 0) {   // emptied by segvlad_db_remove: no row is allowed anywhere
+    ctx->ex_stats[0] = k;
+    SV_HIP(sv_fill_none(ctx, (float*)dd2, (int64_t*)didx, (size_t)nq * k));
+    return sv_finish(ctx);
+  }
+  SV_TRY(search_excluding(ctx, (const float*)dq, nq, qseg_offsets, n_img, excl, E, k, (float*)dd2, (int64_t*)didx));
+  return sv_finish(ctx);
+}
+
+extern "C" int segvlad_exclude_stats(segvlad_ctx* ctx, int64_t* stats_out, int n) {
+  CHECK_CTX();
+  if (!stats_out || n < 0) return ctx->fail(SEGVLAD_ERR_ARG, "exclude_stats: bad arguments");
+  if (ctx->ex_short_dev) {   // the rows the last call's tail finished: fetched once
+    uint32_t w = 0;
+    SV_HIP(hipMemcpyAsync(&w, ctx->ex_short_dev, 4, hipMemcpyDeviceToHost, ctx->stream));
+    SV_HIP(hipStreamSynchronize(ctx->stream));
+    ctx->ex_stats[2] = w;
+    ctx->ex_short_dev = nullptr;
+  } else {
+    SV_HIP(hipStreamSynchronize(ctx->stream));
+  }
+  for (int i = 0; i < n && i < 4; ++i) stats_out[i] = ctx->ex_stats[i];
   return SEGVLAD_OK;
 }

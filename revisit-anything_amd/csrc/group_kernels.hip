@@ -8,7 +8,7 @@
 // per_image or more earlier entries of its image has per_image earlier KEPT ones, so the decision is a function of the list alone.
 //
 //   inner search         segvlad_search's body, unchanged, at depth k_fetch = min(1024, 4 k) into scratch (option group_fetch, tests)
-//   group_collapse_kernel  one wave per query row walks the k_fetch entries in chunks of 64.  Earlier entries of an entry's image =
+//   group_collapse_kernel  one wave per row walks (list_walk_dev.h) the k_fetch entries in chunks of 64.  Earlier entries of an entry's image =
 //                        the count the earlier chunks left in the wave's LDS table + the lower lanes of this chunk with the same
 //                        id.  Both depend on list positions only; the one atomic (claiming a table slot) decides WHERE an id's
 //                        count lives, never its value.  Kept entries are placed by ballot + mbcnt, the walk stops at k kept.
@@ -26,11 +26,12 @@
 // 12 KiB; four waves per workgroup, 48 KiB of the CU's 160: three workgroups per CU.  The slot of an id is the top 11 bits of
 // id x 0x9E3779B1: consecutive image ids -- neighbours in time, what crowds a list -- land a golden-ratio step apart, spread over
 // the 32 banks of the 4-byte reads; lanes of one image read one address, which broadcasts.
+// The entry points (segvlad_search_grouped, segvlad_group_stats) are at the end of this file.
 #include <algorithm>
 #include <vector>
 
 #include "ctx.h"
-#include "knn_dev.h"
+#include "list_walk_dev.h"
 
 namespace {
 
@@ -68,22 +69,9 @@ __global__ __launch_bounds__(64 * GR_WAVES) void group_collapse_kernel(const flo
   uint16_t* cnt = s_cnt[w];
   for (int j = l; j < GR_SLOTS; j += 64) key[j] = -1;
   __threadfence_block();
-  const float* sd = d2f + (size_t)q * kf;
-  const int64_t* si = idxf + (size_t)q * kf;
-  float* od = d2_out + (size_t)q * k;
-  int64_t* oi = idx_out + (size_t)q * k;
-  int kept = 0, read = kf;
-  bool ended = whole != 0;
-  for (int c = 0; c < kf && kept < k; c += 64) {
-    const int j = c + l;
-    int64_t id = -1;
-    float dd = INFINITY;
-    if (j < kf) {
-      id = si[j];
-      dd = sd[j];
-    }
-    const uint64_t endm = __builtin_amdgcn_ballot_w64(j < kf && id < 0);
-    const int g = id >= 0 ? db_img[id] : -1;
+  const SvListArrays list = {d2f + (size_t)q * kf, idxf + (size_t)q * kf, kf};
+  const auto wk = sv_list_walk(list, [&](int64_t id, bool real) {
+    const int g = real ? db_img[id] : -1;
     // the count the earlier chunks left for this image
     int prior = 0;
     uint32_t h = 0;
@@ -95,7 +83,6 @@ __global__ __launch_bounds__(64 * GR_WAVES) void group_collapse_kernel(const flo
     }
     int rank, tot;
     gr_chunk_counts(g, l, rank, tot);
-    const bool keep = id >= 0 && (g < 0 || prior + rank < per_image);
     // the image's first lane of the chunk leaves the new count (h: the first slot that was free or the image's own at the lookup;
     // another image's leader may take a free one first -- then this one moves on, and only the place differs)
     if (g >= 0 && rank == 0) {
@@ -107,44 +94,14 @@ __global__ __launch_bounds__(64 * GR_WAVES) void group_collapse_kernel(const flo
       cnt[h] = (uint16_t)(prior + tot);
     }
     __threadfence_block();
-    const uint64_t mk = __builtin_amdgcn_ballot_w64(keep);
-    const int pos = kept + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mk >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mk, 0u));
-    if (keep && pos < k) {
-      od[pos] = dd;
-      oi[pos] = id;
-    }
-    kept += (int)__popcll(mk);
-    const uint64_t lastm = __builtin_amdgcn_ballot_w64(keep && pos == k - 1);
-    if (lastm) read = c + (int)__builtin_ctzll(lastm) + 1;
-    else if (endm) {
-      read = c + (int)__builtin_ctzll(endm);
-      ended = true;
-      break;
-    }
-  }
-  for (int j = min(kept, k) + l; j < k; j += 64) {
-    od[j] = INFINITY;
-    oi[j] = -1;
-  }
+    return real && (g < 0 || prior + rank < per_image);
+  }, k, l, d2_out + (size_t)q * k, idx_out + (size_t)q * k);
   if (l == 0) {
-    const bool complete = kept >= k || ended;
+    const bool complete = wk.kept >= k || wk.ended || whole != 0;
     const bool open = !complete && fabsf(qn[q]) < INFINITY;   // (false for a NaN norm, too)
     flags[q] = open ? 1u : 0u;
     if (open) atomicAdd(&head[0], 1u);
-    if (complete) atomicMax(&head[1], (uint32_t)read);
-  }
-}
-
-// the open rows of (Q, qn), dense, each with an infinite radius: the query block of the exact sweep
-__global__ __launch_bounds__(256) void group_gather_kernel(const float* __restrict__ Q, const float* __restrict__ qn,
-                                                           const int32_t* __restrict__ rows, int d, float* __restrict__ Y,
-                                                           float* __restrict__ yn, float* __restrict__ yeff) {
-  const int r = blockIdx.x;
-  const int64_t src = rows[r];
-  for (int j = threadIdx.x; j < d; j += 256) Y[(int64_t)r * d + j] = Q[src * d + j];
-  if (threadIdx.x == 0) {
-    yn[r] = qn[src];
-    yeff[r] = INFINITY;
+    if (complete) atomicMax(&head[1], (uint32_t)wk.read);
   }
 }
 
@@ -163,58 +120,40 @@ __global__ __launch_bounds__(64) void group_tail_kernel(const unsigned long long
                                                         const int32_t* __restrict__ rows, float* __restrict__ d2_out,
                                                         int64_t* __restrict__ idx_out) {
   const int l = threadIdx.x;
-  const unsigned long long* s = sorted + (size_t)blockIdx.x * (size_t)n;
+  const SvListWords list = {sorted + (size_t)blockIdx.x * (size_t)n, n};
   uint8_t* tb = tab + (size_t)blockIdx.x * (size_t)nimg;
   const int64_t q = rows[blockIdx.x];
-  float* od = d2_out + (size_t)q * k;
-  int64_t* oi = idx_out + (size_t)q * k;
-  int kept = 0;
-  for (int64_t c = 0; c < n && kept < k; c += 64) {
-    const int64_t j = c + l;
-    const unsigned long long wd = j < n ? s[j] : ~0ull;
-    const bool valid = wd != ~0ull;
-    if (!__builtin_amdgcn_ballot_w64(valid)) break;
-    const uint32_t id = (uint32_t)wd;
-    const int g = valid ? db_img[id] : -1;
+  sv_list_walk(list, [&](int64_t id, bool real) {
+    const int g = real ? db_img[id] : -1;
     const int prior = g >= 0 ? (int)tb[g] : 0;
     int rank, tot;
     gr_chunk_counts(g, l, rank, tot);
-    const bool keep = valid && (g < 0 || prior + rank < per_image);
     if (g >= 0 && rank == 0) tb[g] = (uint8_t)min(prior + tot, 255);
     __threadfence_block();   // (the next chunk's lanes read what this chunk's leaders wrote: one wave, one L1)
-    const uint64_t mk = __builtin_amdgcn_ballot_w64(keep);
-    const int pos = kept + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mk >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mk, 0u));
-    if (keep && pos < k) {
-      od[pos] = key2f_((uint32_t)(wd >> 32));
-      oi[pos] = (int64_t)id;
-    }
-    kept += (int)__popcll(mk);
-  }
-  for (int j = min(kept, k) + l; j < k; j += 64) {
-    od[j] = INFINITY;
-    oi[j] = -1;
-  }
+    return real && (g < 0 || prior + rank < per_image);
+  }, k, l, d2_out + (size_t)q * k, idx_out + (size_t)q * k);
 }
 
 }   // namespace
 
-int sv_search_grouped(segvlad_ctx* ctx, const float* Q, int nq, int k, int per_image, float* d2_out, int64_t* idx_out) {
+// segvlad_search_grouped after the argument checks: Q / outputs on the device, nq >= 1, the index holds rows and an img_of_seg map;
+// fills ctx->gr_stats; synchronises
+static int search_grouped(segvlad_ctx* ctx, const float* Q, int nq, int k, int per_image, float* d2_out, int64_t* idx_out) {
   const int d = ctx->db_d;
   const int64_t n = ctx->db_n;
   const int gf = ctx->opt.group_fetch;
   const int kf = gf > 0 ? std::min(1024, std::max(k, gf)) : std::min(1024, 4 * k);
-  ctx->gr_stats[0] = kf;
-  ctx->gr_stats[1] = ctx->gr_stats[2] = 0;
+  ctx->gr_stats[0] = kf;   // ([1], [2]: cleared by the entry point)
 
-  SV_HIP(ctx->s_gr_d2.reserve((size_t)nq * kf * 4));
-  SV_HIP(ctx->s_gr_idx.reserve((size_t)nq * kf * 8));
-  SV_TRY(sv_search_dev(ctx, Q, nq, kf, ctx->s_gr_d2.as<float>(), ctx->s_gr_idx.as<int64_t>()));
+  SV_HIP(ctx->s_deep_d2.reserve((size_t)nq * kf * 4));
+  SV_HIP(ctx->s_deep_idx.reserve((size_t)nq * kf * 8));
+  SV_TRY(sv_search_dev(ctx, Q, nq, kf, ctx->s_deep_d2.as<float>(), ctx->s_deep_idx.as<int64_t>()));
 
   // words 0 .. 3: the open-row counter and the longest read (segvlad_group_stats); words 4 ..: the rows' flags
   SV_HIP(ctx->s_gr_flag.reserve(((size_t)nq + 4) * 4));
-  SV_HIP(ctx->s_gr_qn.reserve((size_t)nq * 4));
+  SV_HIP(ctx->s_deep_qn.reserve((size_t)nq * 4));
   uint32_t* head = ctx->s_gr_flag.as<uint32_t>();
-  float* qn = ctx->s_gr_qn.as<float>();
+  float* qn = ctx->s_deep_qn.as<float>();
   std::vector<uint32_t> hf((size_t)nq + 4);
   StageScope sc(ctx, "knn_group");
   SV_HIP(hipMemsetAsync(head, 0, 16, ctx->stream));
@@ -222,7 +161,7 @@ int sv_search_grouped(segvlad_ctx* ctx, const float* Q, int nq, int k, int per_i
   //  the values segvlad_search gives the same pointer)
   SV_TRY(sv_launch_row_sumsq(ctx, Q, nq, d, qn));
   hipLaunchKernelGGL(group_collapse_kernel, dim3((unsigned)((nq + GR_WAVES - 1) / GR_WAVES)), dim3(64 * GR_WAVES), 0, ctx->stream,
-                     ctx->s_gr_d2.as<float>(), ctx->s_gr_idx.as<int64_t>(), nq, kf, k, per_image, (int64_t)kf >= n ? 1 : 0,
+                     ctx->s_deep_d2.as<float>(), ctx->s_deep_idx.as<int64_t>(), nq, kf, k, per_image, (int64_t)kf >= n ? 1 : 0,
                      ctx->db_img.as<int32_t>(), qn, d2_out, idx_out, head, head + 4);
   SV_HIP(hipGetLastError());
   sc.count(2);
@@ -257,8 +196,7 @@ int sv_search_grouped(segvlad_ctx* ctx, const float* Q, int nq, int k, int per_i
   uint64_t* words = ctx->s_gr_words.as<uint64_t>();
   uint64_t* sorted = ctx->s_gr_sorted.as<uint64_t>();
   SV_HIP(hipMemcpyAsync(drows, rows.data(), nf * 4, hipMemcpyHostToDevice, ctx->stream));
-  hipLaunchKernelGGL(group_gather_kernel, dim3((unsigned)nf), dim3(256), 0, ctx->stream, Q, qn, drows, d, qx, qnx, effx);
-  SV_HIP(hipGetLastError());
+  SV_TRY(sv_launch_range_gather(ctx, Q, qn, /*eff=*/nullptr, drows, (int)nf, d, qx, qnx, effx));   // every open row: an infinite radius
   hipLaunchKernelGGL(group_plan_kernel, dim3((unsigned)(nb / 256 + 1)), dim3(256), 0, ctx->stream, (int)nb, n, woff, slot);
   SV_HIP(hipGetLastError());
   sc.count(2);
@@ -278,5 +216,35 @@ int sv_search_grouped(segvlad_ctx* ctx, const float* Q, int nq, int k, int per_i
     sc.count(launches + 2);
   }
   SV_HIP(hipStreamSynchronize(ctx->stream));   // rows[] lives on this frame
+  return SEGVLAD_OK;
+}
+
+extern "C" int segvlad_search_grouped(segvlad_ctx* ctx, const float* Q, int nq, int k, int per_image, float* d2_out,
+                                      int64_t* idx_out) {
+  CHECK_CTX();
+  if (nq < 0 || k < 1 || k > 1024 || per_image < 1 || per_image > 16)
+    return ctx->fail(SEGVLAD_ERR_ARG, "search_grouped: need nq >= 0, 1<=k<=1024, 1<=per_image<=16 (k=%d, per_image=%d)", k, per_image);
+  SV_TRY(sv_check_img_index(ctx, "search_grouped"));
+  if (ctx->db_n > 0xffffffffLL) return ctx->fail(SEGVLAD_ERR_LIMIT, "search_grouped: %lld index rows (candidate ids are 32-bit)", (long long)ctx->db_n);
+  ctx->gr_stats[0] = ctx->gr_stats[1] = ctx->gr_stats[2] = 0;
+  if (nq == 0) return SEGVLAD_OK;
+  if (!Q || !d2_out || !idx_out) return ctx->fail(SEGVLAD_ERR_ARG, "search_grouped: null pointer");
+  const void* dq;
+  void *dd2, *didx;
+  SV_TRY(sv_in(ctx, Q, (size_t)nq * ctx->db_d * 4, &dq));
+  SV_TRY(sv_out(ctx, d2_out, (size_t)nq * k * 4, &dd2));
+  SV_TRY(sv_out(ctx, idx_out, (size_t)nq * k * 8, &didx));
+  if (ctx->db_n == 0) {   // emptied by segvlad_db_remove: no row anywhere
+    SV_HIP(sv_fill_none(ctx, (float*)dd2, (int64_t*)didx, (size_t)nq * k));
+    return sv_finish(ctx);
+  }
+  SV_TRY(search_grouped(ctx, (const float*)dq, nq, k, per_image, (float*)dd2, (int64_t*)didx));
+  return sv_finish(ctx);
+}
+
+extern "C" int segvlad_group_stats(segvlad_ctx* ctx, int64_t* stats_out, int n) {
+  if (!ctx) return SEGVLAD_ERR_ARG;
+  if (!stats_out || n < 0) return ctx->fail(SEGVLAD_ERR_ARG, "group_stats: bad arguments");
+  for (int i = 0; i < n && i < 3; ++i) stats_out[i] = ctx->gr_stats[i];
   return SEGVLAD_OK;
 }

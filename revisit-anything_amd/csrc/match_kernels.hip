@@ -20,7 +20,7 @@
 //                         (n_mutual desc, score desc, slot asc), slots without rows last.
 // The positions of B ascend with the row ids (the map keeps an image's rows ascending), so (distance, position) orders like
 // (distance, row id).  A NaN distance gets the key of "none" and is never a minimum.  Nothing is read back: the grid and the scratch
-// sizes come from cand and the host mirror of the map's offsets (sv_sl_map_host).
+// sizes come from cand and the host mirror of the map's offsets (sv_sl_map_host).  The entry point is at the end of this file.
 #include <algorithm>
 
 #include "ctx.h"
@@ -277,9 +277,9 @@ __global__ __launch_bounds__(256) void mp_finish_kernel(const int32_t* __restric
 
 // segvlad_match_pairs after the argument checks: Q on the device, 16-byte aligned, qn its squared norms; qoff / cand host; outputs on
 // the device (n_mutual_out and score_out always, the others may be null); the index may be empty
-int sv_match_pairs(segvlad_ctx* ctx, const float* Q, int nq, const float* qn, const int32_t* qoff, int n_img, const int32_t* cand, int C,
-                   float max_d2, int32_t* n_mutual_out, double* score_out, int32_t* order_out, int64_t* fwd_idx_out, float* fwd_d2_out,
-                   uint8_t* mutual_out) {
+static int match_pairs(segvlad_ctx* ctx, const float* Q, int nq, const float* qn, const int32_t* qoff, int n_img, const int32_t* cand,
+                       int C, float max_d2, int32_t* n_mutual_out, double* score_out, int32_t* order_out, int64_t* fwd_idx_out,
+                       float* fwd_d2_out, uint8_t* mutual_out) {
   static_assert(sizeof(MpTask) == 32 && sizeof(MpSlot) == 16, "tables are handed over as plain words");
   const int d = ctx->db_d;
   SV_TRY(sv_sl_map_host(ctx));
@@ -303,7 +303,7 @@ int sv_match_pairs(segvlad_ctx* ctx, const float* Q, int nq, const float* qn, co
         if (ncol + s.U > 0x7fffffffull) return ctx->fail(SEGVLAD_ERR_LIMIT, "match_pairs: the candidates' rows exceed 2^31 - 1 in all");
         s.colbase = (uint32_t)ncol;
         ncol += s.U;
-        for (int g = 0; g < ng; ++g) {   // an image's rows in ceil(rows / 64) near-equal runs (sv_search_shortlist's groups)
+        for (int g = 0; g < ng; ++g) {   // an image's rows in ceil(rows / 64) near-equal runs (segvlad_search_shortlist's groups)
           const int a0 = qoff[b] + (int)((int64_t)rws * g / ng), a1 = qoff[b] + (int)((int64_t)rws * (g + 1) / ng);
           tasks.push_back({a0, a1 - a0, b * C + j, s.roff, s.U, s.colbase, {0u, 0u}});
           gmax = std::max(gmax, a1 - a0);
@@ -346,4 +346,39 @@ int sv_match_pairs(segvlad_ctx* ctx, const float* Q, int nq, const float* qn, co
   SV_HIP(hipGetLastError());
   sc.count(launches);
   return SEGVLAD_OK;
+}
+
+extern "C" int segvlad_match_pairs(segvlad_ctx* ctx, const float* Q, int nq, const int32_t* qseg_offsets, int n_img, const int32_t* cand,
+                                   int C, float max_d2, int32_t* n_mutual_out, double* score_out, int32_t* order_out,
+                                   int64_t* fwd_idx_out, float* fwd_d2_out, uint8_t* mutual_out) {
+  CHECK_CTX();
+  if (nq < 0 || n_img < 0 || C < 1 || C > 64)
+    return ctx->fail(SEGVLAD_ERR_ARG, "match_pairs: need nq, n_img >= 0, 1<=C<=64 (C=%d)", C);
+  SV_TRY(sv_check_qseg_offsets(ctx, "match_pairs", qseg_offsets, n_img, nq));
+  if (n_img > 0 && !cand) return ctx->fail(SEGVLAD_ERR_ARG, "match_pairs: null cand");
+  if (cand && sv_is_device_ptr(cand)) return ctx->fail(SEGVLAD_ERR_ARG, "match_pairs: cand must be host memory");
+  SV_TRY(sv_check_img_index(ctx, "match_pairs"));
+  if (n_img == 0) return SEGVLAD_OK;   // (then nq == 0 too: nothing to write)
+  if ((nq > 0 && !Q) || !n_mutual_out || !score_out) return ctx->fail(SEGVLAD_ERR_ARG, "match_pairs: null pointer");
+  const int d = ctx->db_d;
+  if (nq > 0 && d % 32 != 0) return ctx->fail(SEGVLAD_ERR_LIMIT, "match_pairs: d=%d (the exact GEMM takes d %% 32 == 0)", d);
+  if (ctx->db_n > 0x7fffffffll) return ctx->fail(SEGVLAD_ERR_LIMIT, "match_pairs: more than 2^31 - 1 rows");
+  const void* dq = nullptr;
+  const float* q = nullptr;
+  void *dn, *ds, *dord = nullptr, *dfi = nullptr, *dfd = nullptr, *dmu = nullptr;
+  SV_TRY(sv_out(ctx, n_mutual_out, (size_t)n_img * C * 4, &dn));
+  SV_TRY(sv_out(ctx, score_out, (size_t)n_img * C * 8, &ds));
+  if (order_out) SV_TRY(sv_out(ctx, order_out, (size_t)n_img * C * 4, &dord));
+  if (nq > 0) {   // (no query rows at all: every image is empty, the finish pass alone writes the zeros and the order)
+    SV_TRY(sv_in(ctx, Q, (size_t)nq * d * 4, &dq));
+    SV_TRY(sv_aligned_queries(ctx, (const float*)dq, nq, &q));
+    if (fwd_idx_out) SV_TRY(sv_out(ctx, fwd_idx_out, (size_t)nq * C * 8, &dfi));
+    if (fwd_d2_out) SV_TRY(sv_out(ctx, fwd_d2_out, (size_t)nq * C * 4, &dfd));
+    if (mutual_out) SV_TRY(sv_out(ctx, mutual_out, (size_t)nq * C, &dmu));
+    SV_HIP(ctx->s_qnorm.reserve((size_t)nq * 4));
+    SV_TRY(sv_launch_row_sumsq(ctx, q, nq, d, ctx->s_qnorm.as<float>()));
+  }
+  SV_TRY(match_pairs(ctx, q, nq, ctx->s_qnorm.as<float>(), qseg_offsets, n_img, cand, C, max_d2, (int32_t*)dn, (double*)ds,
+                     (int32_t*)dord, (int64_t*)dfi, (float*)dfd, (uint8_t*)dmu));
+  return sv_finish(ctx);
 }

@@ -159,7 +159,8 @@ __global__ __launch_bounds__(1024) void range_scan_kernel(const uint32_t* __rest
   }
 }
 
-// the listed rows of (Q, qn, eff), dense: the query block of the exact distance sweeps
+// the listed rows of (Q, qn, eff), dense: the query block of the exact distance sweeps.  eff == null: every row gets an infinite
+// radius (the exact tail of segvlad_search_grouped)
 __global__ __launch_bounds__(256) void range_gather_kernel(const float* __restrict__ Q, const float* __restrict__ qn,
                                                            const float* __restrict__ eff, const int32_t* __restrict__ rows, int d,
                                                            float* __restrict__ Y, float* __restrict__ yn, float* __restrict__ yeff) {
@@ -168,7 +169,7 @@ __global__ __launch_bounds__(256) void range_gather_kernel(const float* __restri
   for (int j = threadIdx.x; j < d; j += 256) Y[(int64_t)r * d + j] = Q[src * d + j];
   if (threadIdx.x == 0) {
     yn[r] = qn[src];
-    yeff[r] = eff[src];
+    yeff[r] = eff ? eff[src] : INFINITY;
   }
 }
 

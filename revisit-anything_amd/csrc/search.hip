@@ -1,5 +1,6 @@
 // The index and the exact kNN search of the C-ABI (segvlad_db_*, segvlad_search, segvlad_search_stats): host-side
-// orchestration only -- the search plan, scratch sizing and the kernel sequence of each pass on the context stream.
+// orchestration only -- the search plan, scratch sizing and the kernel sequence of each pass on the context stream.  Also the
+// entry preamble (sv_check_qseg_offsets ... sv_fill_none) of the searches derived from it, which live with their kernels.
 #include <algorithm>
 #include <cmath>
 #include <vector>
@@ -1091,6 +1092,38 @@ static int prepare_queries(segvlad_ctx* ctx, const SearchPlan& p, const float* q
   return SEGVLAD_OK;
 }
 
+// The entry preamble of the searches derived from segvlad_search (ctx.h): each entry runs these in the order its own checks had.
+int sv_check_qseg_offsets(segvlad_ctx* ctx, const char* entry, const int32_t* qseg_offsets, int n_img, int nq) {
+  if (!qseg_offsets) return ctx->fail(SEGVLAD_ERR_ARG, "%s: null qseg_offsets", entry);
+  if (sv_is_device_ptr(qseg_offsets)) return ctx->fail(SEGVLAD_ERR_ARG, "%s: qseg_offsets must be host memory", entry);
+  if (qseg_offsets[0] != 0 || qseg_offsets[n_img] != nq)
+    return ctx->fail(SEGVLAD_ERR_ARG, "%s: qseg_offsets must run from 0 to nq=%d", entry, nq);
+  for (int b = 0; b < n_img; ++b)
+    if (qseg_offsets[b + 1] < qseg_offsets[b]) return ctx->fail(SEGVLAD_ERR_ARG, "%s: qseg_offsets decrease at %d", entry, b);
+  return SEGVLAD_OK;
+}
+
+int sv_check_img_index(segvlad_ctx* ctx, const char* entry) {
+  if (ctx->db_d == 0) return ctx->fail(SEGVLAD_ERR_STATE, "%s: the index is empty and has no dimension yet", entry);
+  if (!ctx->db_has_img) return ctx->fail(SEGVLAD_ERR_STATE, "%s: no img_of_seg map: give it to segvlad_db_add", entry);
+  return SEGVLAD_OK;
+}
+
+int sv_aligned_queries(segvlad_ctx* ctx, const float* dq, int nq, const float** out) {
+  *out = dq;
+  if ((reinterpret_cast<uintptr_t>(dq) & 15) == 0) return SEGVLAD_OK;
+  const size_t bytes = (size_t)nq * ctx->db_d * 4;
+  SV_HIP(ctx->s_sl_q.reserve(bytes));
+  SV_HIP(hipMemcpyAsync(ctx->s_sl_q.p, dq, bytes, hipMemcpyDeviceToDevice, ctx->stream));
+  *out = ctx->s_sl_q.as<float>();
+  return SEGVLAD_OK;
+}
+
+hipError_t sv_fill_none(segvlad_ctx* ctx, float* d2, int64_t* idx, size_t n) {
+  const hipError_t e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d2), 0x7f800000, n, ctx->stream);
+  return e != hipSuccess ? e : hipMemsetAsync(idx, 0xff, n * 8, ctx->stream);
+}
+
 extern "C" int segvlad_search(segvlad_ctx* ctx, const float* Q, int nq, int k, float* d2_out, int64_t* idx_out) {
   CHECK_CTX();
   if (nq < 0 || k < 1 || k > 1024) return ctx->fail(SEGVLAD_ERR_ARG, "search: need nq>=0 and 1<=k<=1024 (k=%d)", k);
@@ -1108,7 +1141,7 @@ extern "C" int segvlad_search(segvlad_ctx* ctx, const float* Q, int nq, int k, f
 }
 
 // segvlad_search behind its argument checks and staging: q / d2 / idx on the device, nq >= 1, the index has a dimension.  Also the
-// inner search of segvlad_search_excluding (exclude_kernels.hip), which runs it at a larger depth into scratch of its own.
+// inner search of segvlad_search_excluding and segvlad_search_grouped, which run it at a larger depth into ctx->s_deep_*.
 int sv_search_dev(segvlad_ctx* ctx, const float* q, int nq, int k, float* d2, int64_t* idx) {
   const void* dq = q;
   ctx->f16_scale_dev = nullptr;
@@ -1128,8 +1161,7 @@ int sv_search_dev(segvlad_ctx* ctx, const float* q, int nq, int k, float* d2, in
   }
 
   if (ctx->db_n == 0) {   // emptied by segvlad_db_remove: every slot beyond the (zero) rows is (+inf, -1)
-    SV_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d2), 0x7f800000, (size_t)nq * k, ctx->stream));
-    SV_HIP(hipMemsetAsync(idx, 0xff, (size_t)nq * k * 8, ctx->stream));
+    SV_HIP(sv_fill_none(ctx, d2, idx, (size_t)nq * k));
     return SEGVLAD_OK;
   }
   const SearchPlan p = plan_search(ctx, nq, k, dq);

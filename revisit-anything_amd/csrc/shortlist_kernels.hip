@@ -24,7 +24,7 @@
 //     sl_final_kernel     per query row: its S slices' lists, (distance, id) sort, top k; (+inf, -1) beyond the allowed rows
 // Nothing is read back during a call: the grid sizes come from qseg_offsets, n_img, M and k (host), the union sizes stay on the device.
 // sl_gemm_kernel and sl_final_kernel also are the exact tail of segvlad_search_excluding (exclude_kernels.hip), whose "union" is the
-// complement of a few intervals of image ids: sv_launch_exclude_tail, at the end of this file.
+// complement of a few intervals of image ids: sv_launch_exclude_tail, at the end of this file, behind the entry point.
 #include <algorithm>
 
 #include "ctx.h"
@@ -505,9 +505,10 @@ int sv_sl_map_host(segvlad_ctx* ctx) {
   return SEGVLAD_OK;
 }
 
-// segvlad_search_shortlist after the argument checks: Q on the device, 16-byte aligned; qoff host; outputs on the device
-int sv_search_shortlist(segvlad_ctx* ctx, const float* Q, int nq, const float* qn, const int32_t* qoff, int n_img,
-                        const int32_t* shortlist, int M, int k, float* d2_out, int64_t* idx_out) {
+// segvlad_search_shortlist after the argument checks: Q on the device, 16-byte aligned, qn its squared norms; qoff host; shortlist /
+// outputs on the device
+static int search_shortlist(segvlad_ctx* ctx, const float* Q, int nq, const float* qn, const int32_t* qoff, int n_img,
+                            const int32_t* shortlist, int M, int k, float* d2_out, int64_t* idx_out) {
   const int d = ctx->db_d;
   {
     StageScope sc(ctx, "knn_shortlist");
@@ -568,6 +569,37 @@ int sv_search_shortlist(segvlad_ctx* ctx, const float* Q, int nq, const float* q
     sc.count(rebuilt ? 8 : 3);
   }
   return SEGVLAD_OK;
+}
+
+extern "C" int segvlad_search_shortlist(segvlad_ctx* ctx, const float* Q, int nq, const int32_t* qseg_offsets, int n_img,
+                                        const int32_t* shortlist, int M, int k, float* d2_out, int64_t* idx_out) {
+  CHECK_CTX();
+  if (nq < 0 || n_img < 0 || k < 1 || k > 1024 || M < 1 || M > 4096)
+    return ctx->fail(SEGVLAD_ERR_ARG, "search_shortlist: need nq, n_img >= 0, 1<=k<=1024, 1<=M<=4096 (k=%d, M=%d)", k, M);
+  SV_TRY(sv_check_qseg_offsets(ctx, "search_shortlist", qseg_offsets, n_img, nq));
+  SV_TRY(sv_check_img_index(ctx, "search_shortlist"));
+  if (nq == 0) return SEGVLAD_OK;
+  if (!Q || !shortlist || !d2_out || !idx_out) return ctx->fail(SEGVLAD_ERR_ARG, "search_shortlist: null pointer");
+  const int d = ctx->db_d;
+  if (d % 32 != 0) return ctx->fail(SEGVLAD_ERR_LIMIT, "search_shortlist: d=%d (the exact GEMM takes d %% 32 == 0)", d);
+  if (ctx->db_n > 0x7fffffffll) return ctx->fail(SEGVLAD_ERR_LIMIT, "search_shortlist: more than 2^31 - 1 rows");
+  const void *dq, *dsl;
+  const float* q;
+  void *dd2, *didx;
+  SV_TRY(sv_in(ctx, Q, (size_t)nq * d * 4, &dq));
+  SV_TRY(sv_aligned_queries(ctx, (const float*)dq, nq, &q));
+  SV_TRY(sv_in(ctx, shortlist, (size_t)n_img * M * 4, &dsl));
+  SV_TRY(sv_out(ctx, d2_out, (size_t)nq * k * 4, &dd2));
+  SV_TRY(sv_out(ctx, idx_out, (size_t)nq * k * 8, &didx));
+  if (ctx->db_n == 0) {   // emptied by segvlad_db_remove: no row is allowed anywhere
+    SV_HIP(sv_fill_none(ctx, (float*)dd2, (int64_t*)didx, (size_t)nq * k));
+    return sv_finish(ctx);
+  }
+  SV_HIP(ctx->s_qnorm.reserve((size_t)nq * 4));
+  SV_TRY(sv_launch_row_sumsq(ctx, q, nq, d, ctx->s_qnorm.as<float>()));
+  SV_TRY(search_shortlist(ctx, q, nq, ctx->s_qnorm.as<float>(), qseg_offsets, n_img, (const int32_t*)dsl, M, k, (float*)dd2,
+                          (int64_t*)didx));
+  return sv_finish(ctx);
 }
 
 // The exact tail of segvlad_search_excluding: sl_gemm_kernel<., true> over the allowed rows of every group that holds a flagged

@@ -329,6 +329,30 @@ def test_the_tail(eng, eng2, variant):
     _check(got, _fresh(eng2, R, img, Q, qoff, ex, k))
 
 
+def test_exclude_stats_fetched_after_a_grouped_search(eng):
+    """search_excluding and search_grouped keep their deep lists and query norms in the same scratch, and exclude_stats() reads the
+    tail's row counter from the device when it is asked: a grouped search in between -- its own tail running too -- changes neither
+    the counter nor the exclusion's outputs."""
+    rng = np.random.default_rng(7)
+    R, img, Q = _crowded(rng, 6000, 64, 40, 40, 50)
+    qoff = np.array([0, 50], np.int32)
+    ex = np.array([[[40, 79]]], np.int32)
+    eng.db_reset()
+    eng.db_add(R, img)
+    alone = eng.search_excluding(Q, qoff, ex, 50)
+    st_alone = eng.exclude_stats()
+    assert st_alone["tail_rows"] == 50                  # (test_the_tail[50_rows]: every row is short)
+    got = eng.search_excluding(Q, qoff, ex, 50)
+    eng.set_option("group_fetch", 64)
+    try:
+        eng.search_grouped(Q, 50, 1)
+        assert eng.group_stats()["tail_rows"] > 0       # 64 entries of <= 40 images cannot hold 50 different ones
+    finally:
+        eng.set_option("group_fetch", 0)
+    assert eng.exclude_stats() == st_alone
+    _check(got, tuple(t.cpu().numpy() for t in alone))
+
+
 # ---- 6 ---------------------------------------------------------------------------------------------------------------------
 def test_everything_excluded_and_fewer_allowed_rows_than_k(eng):
     rng, R, img, qoff, Q = _oracle_case()
@@ -519,6 +543,11 @@ def test_argument_errors(eng):
     assert raw(np.array([0, 9], np.int32), 1, ex, 1, 5) == SEGVLAD_ERR_ARG
     assert raw(np.array([1, 10], np.int32), 1, ex, 1, 5) == SEGVLAD_ERR_ARG
     assert raw(np.array([0, 12, 10], np.int32), 2, np.tile(ex, (2, 1, 1)), 1, 5) == SEGVLAD_ERR_ARG
+    dev_qoff = torch.from_numpy(qoff).cuda()
+    for bad_qoff in (None, dev_qoff.data_ptr()):   # null; a device pointer
+        assert eng.lib.segvlad_search_excluding(eng._h, Q.ctypes.data, 10, bad_qoff, 1, ex.ctypes.data, 1, 5, d2.data_ptr(),
+                                                idx.data_ptr()) == SEGVLAD_ERR_ARG
+        assert eng.lib.segvlad_last_error(eng._h).decode().startswith("search_excluding: ")
     for bad in (np.zeros((1, 9, 2), np.int32), np.zeros((2, 1, 2), np.int32), np.zeros((1, 2), np.int32), [[(1, 2, 3)]]):
         with pytest.raises(ValueError):
             eng.search_excluding(Q, qoff, bad, 5)

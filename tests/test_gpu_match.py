@@ -271,6 +271,8 @@ def test_errors(eng):
     assert call(Q, 10, np.array([1, 10], np.int32), 1, cand, 2) == SEGVLAD_ERR_ARG     # does not start at 0
     assert call(Q, 10, np.array([0, 12, 10], np.int32), 2, np.zeros((2, 2), np.int32), 2) == SEGVLAD_ERR_ARG   # decreasing
     assert call(Q, 10, None, 1, cand, 2) == SEGVLAD_ERR_ARG
+    assert call(Q, 10, torch.from_numpy(qoff).cuda(), 1, cand, 2) == SEGVLAD_ERR_ARG   # qseg_offsets is host memory
+    assert eng.lib.segvlad_last_error(eng._h).decode().startswith("match_pairs: ")
     assert call(Q, 10, qoff, 1, None, 2) == SEGVLAD_ERR_ARG
     assert call(None, 10, qoff, 1, cand, 2) == SEGVLAD_ERR_ARG
     assert call(Q, 10, qoff, 1, cand, 2, nm=None) == SEGVLAD_ERR_ARG

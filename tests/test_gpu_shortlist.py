@@ -157,6 +157,14 @@ def test_argument_errors(eng):
         with pytest.raises(SegVLADError) as e:
             eng.search_shortlist(Q, bad_qoff, sl, k)
         assert e.value.code == SEGVLAD_ERR_ARG
+    d2 = torch.empty((10, 5), dtype=torch.float32, device="cuda:0")
+    idx = torch.empty((10, 5), dtype=torch.int64, device="cuda:0")
+    dec, dev_qoff = np.array([0, 12, 10], np.int32), torch.from_numpy(qoff).cuda()
+    for bad_qoff, n_img in ((dec.ctypes.data, 2), (None, 1), (dev_qoff.data_ptr(), 1)):   # a decrease; null; a device pointer
+        sl = torch.zeros((n_img, 1), dtype=torch.int32, device="cuda:0")
+        assert eng.lib.segvlad_search_shortlist(eng._h, Q.ctypes.data, 10, bad_qoff, n_img, sl.data_ptr(), 1, 5, d2.data_ptr(),
+                                                idx.data_ptr()) == SEGVLAD_ERR_ARG
+        assert eng.lib.segvlad_last_error(eng._h).decode().startswith("search_shortlist: ")
     for ids in ([[-2]], [[10]]):
         with pytest.raises(ValueError):
             eng.search_shortlist(Q, qoff, np.array(ids, np.int32), 5)

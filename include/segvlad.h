@@ -381,7 +381,11 @@ int segvlad_match_pairs(segvlad_ctx* ctx, const float* Q, int nq, const int32_t*
 
 /* ---- merge of per-shard top-k lists (no reference counterpart: the reference is single-process).
  *      d2_parts/idx_parts [nq][parts*k] (shard-major within a row, global ids); output top-k by
- *      (distance, lower id).                                                                       */
+ *      (distance, lower id).  An entry with id < 0 is an empty slot whatever its distance: it comes
+ *      last and is returned as (+inf, -1).  The parts need not be sorted: sorted parts (the per-shard
+ *      lists) are rank-merged, anything else -- an empty slot inside a part included -- is sorted, with
+ *      the same result.  Limit: parts * k <= 8192 candidates per row (the LDS sort; 9 x 1024 returns
+ *      SEGVLAD_ERR_LIMIT and leaves the context usable).                                              */
 int segvlad_merge_topk(segvlad_ctx* ctx, const float* d2_parts, const int64_t* idx_parts, int nq, int parts, int k,
                        float* d2_out, int64_t* idx_out);
 
@@ -390,7 +394,8 @@ int segvlad_sims_from_d2(segvlad_ctx* ctx, const float* d2, const int64_t* idx, 
                          float* sims_out, int64_t* idx_out);
 
 /* ---- global min / max of the kept similarities                        func_vpr.py:212-213
- *      minmax_out [2] fp32 = {min, max}.                                                          */
+ *      minmax_out [2] fp32 = {min, max}; +-inf take part like any value.  The empty list
+ *      (count == 0) gives (NaN, NaN).                                                             */
 int segvlad_minmax(segvlad_ctx* ctx, const float* sims, int64_t count, float* minmax_out);
 
 /* ---- image vote: get_matches + weighted_borda_count                   func_vpr.py:61-77, 207-224
@@ -400,7 +405,14 @@ int segvlad_minmax(segvlad_ctx* ctx, const float* sims, int64_t count, float* mi
  *      smin/smax: the GLOBAL extrema (func_vpr.py:212-213); pass NaN to have them computed from
  *      `sims`.  pred_out [n_img][n_top] int32 (-1 padded), score_out [n_img][n_top] fp64 or NULL
  *      (mode COUNT: the integer vote count as a double).  Ties: first appearance (rank-major, then
- *      segment) for WT_BORDA_IM; (count desc, image id asc) for COUNT.                             */
+ *      segment) for WT_BORDA_IM; (count desc, image id asc) for COUNT.
+ *      An entry whose id lies outside [0, n_ref_seg) -- the -1 of an empty slot of a derived search --
+ *      is skipped: it votes for nothing in either mode.  Its `sims` value still enters the extrema
+ *      that the call computes itself (NaN smin/smax), so a caller whose lists carry empty slots passes
+ *      the extrema of the kept entries (pipeline.py does).  A weight below 0 or above 1 (explicit
+ *      extrema inside the data's range) is added like any other.  A query image's row of pred_out /
+ *      score_out depends on that image's entries and the extrema alone, bit for bit: not on the other
+ *      images of the call, whose sizes only choose the kernel's code path.                           */
 int segvlad_vote(segvlad_ctx* ctx, const int64_t* idx, const float* sims, const int32_t* img_of_seg,
                  int64_t n_ref_seg, const int32_t* qseg_offsets, int n_img, int k, float smin, float smax, int n_top, int mode,
                  int32_t* pred_out, double* score_out);

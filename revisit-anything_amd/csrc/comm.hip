@@ -33,6 +33,7 @@ const char* ncclGetErrorString(ncclResult_t result);
 #include <mutex>
 
 #include "ctx.h"
+#include "knn_dev.h"
 
 namespace {
 
@@ -142,13 +143,8 @@ __global__ __launch_bounds__(256) void unpack_topk_kernel(const uint32_t* __rest
 }
 
 // ---- the vote's exchange (segvlad_vote_global): one 16-byte record per rank {min bits, max bits, status, query segments} ----
-// min / max on the order-preserving key of select_kernels.hip's reduction: exact and order-independent, so the reduction of
-// the ranks' records gives the bits one process gets from all the similarities
-__device__ __forceinline__ uint32_t vote_f2key(float f) {
-  const uint32_t u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float vote_key2f(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
+// min / max on the order-preserving key of select_kernels.hip's reduction (f2key_, knn_dev.h): exact and order-independent, so the
+// reduction of the ranks' records gives the bits one process gets from all the similarities
 
 // this rank's record: the local extrema from the vote's extrema slot, or (+inf, -inf) when it has none to contribute
 __global__ void vote_record_kernel(const float* __restrict__ mm, int have_mm, uint32_t status, uint32_t nseg, uint32_t* __restrict__ rec) {
@@ -168,8 +164,8 @@ __global__ __launch_bounds__(64) void vote_extrema_reduce_kernel(const uint32_t*
     const uint32_t* x = rec + 4 * (int64_t)r;
     flags[r] = x[2];
     if (x[3] != 0u) {
-      lo = min(lo, vote_f2key(__uint_as_float(x[0])));
-      hi = max(hi, vote_f2key(__uint_as_float(x[1])));
+      lo = min(lo, f2key_(__uint_as_float(x[0])));
+      hi = max(hi, f2key_(__uint_as_float(x[1])));
     }
   }
   for (int o = 32; o > 0; o >>= 1) {
@@ -177,8 +173,8 @@ __global__ __launch_bounds__(64) void vote_extrema_reduce_kernel(const uint32_t*
     hi = max(hi, (uint32_t)__shfl_xor((int)hi, o));
   }
   if (threadIdx.x == 0) {
-    gmm[0] = vote_key2f(lo);
-    gmm[1] = vote_key2f(hi);
+    gmm[0] = key2f_(lo);
+    gmm[1] = key2f_(hi);
   }
 }
 

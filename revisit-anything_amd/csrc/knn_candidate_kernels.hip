@@ -758,7 +758,7 @@ __global__ __launch_bounds__(256) void refine_exact_kernel(const float* __restri
     const float v = sv_d2(q2, rn[id], acc);
     a[j] = ((uint64_t)f2key_(v) << 32) | id;
   }
-  bitonic64(a, np2, tid);
+  sv_bitonic(a, np2, tid);
   for (int j = tid; j < k; j += 256) {
     float dd = INFINITY;
     int64_t id = -1;
@@ -936,7 +936,7 @@ __global__ __launch_bounds__(256) void refine_exact_wide_kernel(const float* __r
       a[base + tid] = ((uint64_t)f2key_(sv_d2(q2, rn[id], acc)) << 32) | id;
     }
   }
-  bitonic64(a, np2, tid);
+  sv_bitonic(a, np2, tid);
   for (int j = tid; j < k; j += 256) {
     float dd = INFINITY;
     int64_t id = -1;
@@ -1026,7 +1026,7 @@ __global__ __launch_bounds__(256) void refine_exact_small_kernel(const float* __
       while (np2 < c) np2 <<= 1;
       for (int j = tid; j < np2; j += 256)
         a2[j] = j < c ? __hip_atomic_load(&slot[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : ~0ull;
-      bitonic64(a2, np2, tid);
+      sv_bitonic(a2, np2, tid);
       for (int j = tid; j < k; j += 256) {
         const uint64_t v = j < np2 ? a2[j] : ~0ull;
         d2_out[row * k + j] = v != ~0ull ? key2f_((uint32_t)(v >> 32)) : INFINITY;

@@ -1,6 +1,5 @@
-// Device helpers shared by the kNN translation units (knn_filter_kernels.hip, knn_candidate_kernels.hip, small_pass_kernels.hip): the order-preserving
-// float <-> key map, the workgroup bitonic sort of (key << 32 | id) words, DPP wave reductions.  Moved out of
-// knn_filter_kernels.hip in round 6, unchanged.
+// Device helpers shared by the search's translation units: the order-preserving float <-> key map (its only definition), the
+// workgroup bitonic sort of keys or (key << 32 | id) words, DPP wave reductions.
 #pragma once
 #include <stdint.h>
 
@@ -39,16 +38,17 @@ __device__ __forceinline__ uint32_t mag4_(const float4& v) {
              max(__float_as_uint(v.z) & 0x7fffffffu, __float_as_uint(v.w) & 0x7fffffffu));
 }
 
-// ascending bitonic sort of n (a power of two) 64-bit words in LDS by a 256-thread workgroup
-__device__ __forceinline__ void bitonic64(uint64_t* a, int n, int tid) {
+// ascending bitonic sort of n (a power of two) words in LDS by a workgroup of NTH threads
+template <class T, int NTH = 256>
+__device__ __forceinline__ void sv_bitonic(T* a, int n, int tid) {
   for (int size = 2; size <= n; size <<= 1) {
     for (int stride = size >> 1; stride > 0; stride >>= 1) {
       __syncthreads();
-      for (int t = tid; t < (n >> 1); t += 256) {
+      for (int t = tid; t < (n >> 1); t += NTH) {
         const int lo = 2 * t - (t & (stride - 1));
         const int hi = lo + stride;
         const bool up = ((lo & size) == 0);
-        const uint64_t x = a[lo], y = a[hi];
+        const T x = a[lo], y = a[hi];
         if ((y < x) == up) {
           a[lo] = y;
           a[hi] = x;

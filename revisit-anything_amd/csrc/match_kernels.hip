@@ -8,9 +8,9 @@
 //     (memset)            the row minima [nq][C] and the column minima [sum of |B| over the live slots]: all ones = "none"
 //     mp_gemm_kernel      1-D grid over a HOST-built task table that holds only live slots: a task is (a group of <= 64 consecutive
 //                         query rows of one image -- the groups of sl_gemm_kernel --, one slot).  It walks B in 128-row tiles through
-//                         the exact fp32 tile of sl_gemm_kernel (shortlist_kernels.hip), restated here: v_mfma_f32_32x32x2_f32 in k
-//                         order, the same operand staging, sv_d2 with the stored norms -- per pair the chain segvlad_search evaluates,
-//                         bit for bit.  From the key block in LDS: every query row's running minimum (distance bits, position in B),
+//                         the gathered-row exact fp32 tile (group_tile_dev.h, the one sl_gemm_kernel and refine_group_gemm_kernel
+//                         use): v_mfma_f32_32x32x2_f32 in k order, then sv_d2 with the stored norms -- per pair the chain
+//                         segvlad_search evaluates, bit for bit.  From the key block in LDS: every query row's running minimum (distance bits, position in B),
 //                         kept in LDS across the tiles and written once; every column's minimum (distance bits, query row) goes to the
 //                         slot's column array by a 64-bit unsigned atomic minimum -- an image of more than 64 segments spans several
 //                         tasks, and a minimum does not depend on the order of arrival.
@@ -24,37 +24,18 @@
 #include <algorithm>
 
 #include "ctx.h"
-
-typedef float mp_f32x16 __attribute__((ext_vector_type(16)));
-typedef float mp_f32x4 __attribute__((ext_vector_type(4)));
-typedef float mp_f32x2 __attribute__((ext_vector_type(2)));
+#include "group_tile_dev.h"
+#include "knn_dev.h"
 
 namespace {
 
 constexpr int MP_GMAX = 64;   // query rows per group, at most (SL_GMAX)
-constexpr int MP_KS = 32;     // floats of a row piece (SL_KS)
 constexpr uint32_t MP_NONE = 0xffffffffu;
 
-__device__ __forceinline__ uint32_t mp_f2key(float f) {   // (sl_f2key; a NaN is nobody's nearest)
-  if (f != f) return MP_NONE;
-  const uint32_t u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float mp_key2f(uint32_t k) {
-  const uint32_t u = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k;
-  return __uint_as_float(u);
+__device__ __forceinline__ uint32_t mp_f2key(float f) {   // (f2key_; a NaN is nobody's nearest)
+  return f != f ? MP_NONE : f2key_(f);
 }
 __device__ __forceinline__ uint64_t mp_min64(uint64_t a, uint64_t b) { return b < a ? b : a; }
-__device__ __forceinline__ int mp_frag_row(int r, int kk) { return (r & 3) + 8 * (r >> 2) + 4 * kk; }
-
-// The row pieces are requested and waited for exactly as in sl_gemm_kernel / refine_group_gemm_kernel (see there).
-#if defined(__clang_major__) && __clang_major__ == 22 && !defined(SEGVLAD_RG_PLAIN_LOADS)
-#define MP_GLOAD(dst, ptr) asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(dst) : "v"(ptr) : "memory")
-#define MP_WAIT_LOADS() asm volatile("s_waitcnt vmcnt(0)" ::: "memory")
-#else
-#define MP_GLOAD(dst, ptr) (dst) = *reinterpret_cast<const mp_f32x4*>(ptr)
-#define MP_WAIT_LOADS() do { } while (0)
-#endif
 
 struct MpTask {    // one workgroup of mp_gemm_kernel
   int32_t q0, nrows;        // the group's query rows
@@ -72,17 +53,10 @@ __global__ __launch_bounds__(256) void mp_gemm_kernel(const float* __restrict__ 
                                                       const float* __restrict__ qn, const float* __restrict__ rn,
                                                       const MpTask* __restrict__ tasks, int C, const uint32_t* __restrict__ rows,
                                                       uint64_t* __restrict__ rowmin, uint64_t* __restrict__ colmin) {
-  constexpr int KS = MP_KS;
-  constexpr int LDR = KS + 4;
-  constexpr int LPR = KS / 4;
-  constexpr int RPI = 64 / LPR;
-  constexpr int NR = 32 * MT + 128;
-  constexpr int NLD = NR / (4 * RPI);
-  static_assert(NR % (4 * RPI) == 0 && (32 * MT) % (4 * RPI) == 0, "whole instructions of query rows / of index rows");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   // [staging image] [dk: 32 MT x 128 distance keys]
   float* tile = reinterpret_cast<float*>(smem);
-  uint32_t* dk = reinterpret_cast<uint32_t*>(smem + (size_t)NR * LDR * 4);
+  uint32_t* dk = reinterpret_cast<uint32_t*>(smem + sv_group_tile_bytes(MT));
   __shared__ uint32_t ids[128];
   __shared__ uint64_t s_rmin[32 * MT];
   const MpTask tk = tasks[blockIdx.x];
@@ -92,79 +66,17 @@ __global__ __launch_bounds__(256) void mp_gemm_kernel(const float* __restrict__ 
   const uint32_t* brows = rows + tk.roff;
   uint64_t* cmin = colmin + tk.colbase;
   const int tid = threadIdx.x, w = tid >> 6, l = tid & 63, i = l & 31, kk = l >> 5;
-  const int lp = l % LPR, lr = l / LPR;
   // initialised by wave 0, made visible to the row's owner by the barrier at the top of the first tile (every task has one: U > 0);
   // from there on row r is only touched by wave r & 3, so the tiles' updates need no barrier of their own
   if (tid < 32 * MT) s_rmin[tid] = ~0ull;
+  const SvGroupTileQ<MT> qrows = sv_group_tile_query_rows<MT>(Q, d, q0, q_end);   // (the same for every tile)
   const int ntile = (U + 127) >> 7;
   for (int t = 0; t < ntile; ++t) {
     const int c0 = t * 128;
     if (tid < 128) ids[tid] = c0 + tid < U ? brows[c0 + tid] : 0u;   // (columns beyond U: row 0, computed and never used)
     __syncthreads();
-    const float* src[NLD];
-#pragma unroll
-    for (int j = 0; j < NLD; ++j) {
-      const int rr = 4 * RPI * j + RPI * w + lr;
-      src[j] = (rr < 32 * MT ? Q + (size_t)min(q0 + rr, q_end - 1) * d : R + (size_t)ids[rr - 32 * MT] * d) + 4 * lp;
-    }
-    mp_f32x4 v[NLD];
-    auto gload = [&](int st) {
-#pragma unroll
-      for (int j = 0; j < NLD; ++j) MP_GLOAD(v[j], src[j] + (size_t)st * KS);
-    };
-    float* st_base = tile + (RPI * w + lr) * LDR + 8 * (lp >> 1) + 2 * (lp & 1);
-    auto sstore = [&]() {
-#pragma unroll
-      for (int j = 0; j < NLD; ++j) asm volatile("" : "+v"(v[j]));
-#pragma unroll
-      for (int j = 0; j < NLD; ++j) {
-        float* p = st_base + 4 * RPI * j * LDR;
-        mp_f32x2 ev, od;
-        ev[0] = v[j][0];
-        ev[1] = v[j][2];
-        od[0] = v[j][1];
-        od[1] = v[j][3];
-        *reinterpret_cast<mp_f32x2*>(p) = ev;
-        *reinterpret_cast<mp_f32x2*>(p + 4) = od;
-      }
-    };
-    mp_f32x16 acc[MT];
-#pragma unroll
-    for (int u = 0; u < MT; ++u)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[u][r] = 0.f;
-    const float* a_frag = tile + i * LDR + 4 * kk;
-    const float* b_frag = tile + (32 * MT + 32 * w + i) * LDR + 4 * kk;
-    const int nst = d / KS;
-    gload(0);
-    MP_WAIT_LOADS();
-    sstore();
-    __syncthreads();
-    for (int st = 0; st < nst; ++st) {
-      if (st + 1 < nst) gload(st + 1);
-      mp_f32x4 fa[2][MT], fb[2];
-      fb[0] = *reinterpret_cast<const mp_f32x4*>(b_frag);
-#pragma unroll
-      for (int u = 0; u < MT; ++u) fa[0][u] = *reinterpret_cast<const mp_f32x4*>(a_frag + 32 * u * LDR);
-#pragma unroll
-      for (int gg = 0; gg < KS / 8; ++gg) {
-        if (gg + 1 < KS / 8) {
-          fb[(gg + 1) & 1] = *reinterpret_cast<const mp_f32x4*>(b_frag + 8 * (gg + 1));
-#pragma unroll
-          for (int u = 0; u < MT; ++u) fa[(gg + 1) & 1][u] = *reinterpret_cast<const mp_f32x4*>(a_frag + 32 * u * LDR + 8 * (gg + 1));
-        }
-#pragma unroll
-        for (int x = 0; x < 4; ++x)
-#pragma unroll
-          for (int u = 0; u < MT; ++u) acc[u] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[gg & 1][u][x], fb[gg & 1][x], acc[u], 0, 0, 0);
-      }
-      __syncthreads();
-      if (st + 1 < nst) {
-        MP_WAIT_LOADS();
-        sstore();
-        __syncthreads();
-      }
-    }
+    f32x16 acc[MT];
+    sv_group_tile_dots<MT>(tile, ids, qrows, R, d, acc);
     {
       const int col = 32 * w + i;
       const float r2 = rn[ids[col]];
@@ -172,7 +84,7 @@ __global__ __launch_bounds__(256) void mp_gemm_kernel(const float* __restrict__ 
       for (int u = 0; u < MT; ++u)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int lr2 = 32 * u + mp_frag_row(r, kk);
+          const int lr2 = 32 * u + sv_frag_row(r, kk);
           if (q0 + lr2 < q_end) dk[lr2 * 128 + col] = mp_f2key(sv_d2_screen(qn[q0 + lr2], r2, acc[u][r]));
         }
     }
@@ -229,7 +141,7 @@ __global__ __launch_bounds__(256) void mp_finish_kernel(const int32_t* __restric
         const uint64_t key = sl.U ? rowmin[(size_t)q * C + j] : ~0ull;
         if (key != ~0ull) {
           const uint32_t p = (uint32_t)key;
-          dd = mp_key2f((uint32_t)(key >> 32));
+          dd = key2f_((uint32_t)(key >> 32));
           id = (int64_t)rows[sl.roff + p];
           m = (uint32_t)colmin[sl.colbase + p] == (uint32_t)q && dd < max_d2;
         }
@@ -332,7 +244,7 @@ static int match_pairs(segvlad_ctx* ctx, const float* Q, int nq, const float* qn
   int launches = 1;
   if (!tasks.empty()) {
     const int mt = gmax > 32 ? 2 : 1;
-    const size_t glds = (size_t)(32 * mt + 128) * (MP_KS + 4) * 4 + (size_t)32 * mt * 128 * 4;
+    const size_t glds = sv_group_tile_bytes(mt) + (size_t)32 * mt * 128 * 4;
     auto gk = mt == 2 ? mp_gemm_kernel<2> : mp_gemm_kernel<1>;
     SV_HIP(sv_max_dyn_lds(reinterpret_cast<const void*>(gk), glds));
     hipLaunchKernelGGL(gk, dim3((unsigned)tasks.size()), dim3(256), glds, ctx->stream, Q, ctx->db_rows.as<float>(), d, qn,

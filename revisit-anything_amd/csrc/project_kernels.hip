@@ -19,10 +19,9 @@
 //   project_consts_kernel      W mu ([P])                                         (once per PCA model)
 //   project_aggregate_kernel   the weighted sums above on fp32 MFMA (exact fp32 chains), mean term and whitening scale fused
 #include "ctx.h"
+#include "group_tile_dev.h"   // f32x16, sv_frag_row
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 #define MFMA32(a, b, c) __builtin_amdgcn_mfma_f32_32x32x2f32((a), (b), (c), 0, 0, 0)
-__device__ __forceinline__ int pj_frag_row(int r, int kk) { return (r & 3) + 8 * (r >> 2) + 4 * kk; }
 
 // ---- grouping plan ---------------------------------------------------------------------------------------------------
 // One workgroup.  Cluster k's tokens of all images occupy rows [base_k, base_k + M_k) of the grouped planes, base_k a
@@ -389,7 +388,7 @@ __global__ __launch_bounds__(64 * NW) void project_aggregate_kernel(const float*
         if (mt == 1 && !two) break;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int s = 32 * mt + pj_frag_row(r, kk);
+          const int s = 32 * mt + sv_frag_row(r, kk);
           if (s < Sc) Y[(size_t)(s0 + 64 * sc + s) * P + pcol] = ((F16 ? acc[mt][r] * (1.f / zscale) : acc[mt][r]) - mu) * cs;
         }
       }

@@ -69,7 +69,7 @@ __global__ __launch_bounds__(1024) void range_cand_stats_kernel(const uint32_t* 
 
 // A short row's candidate list, evaluated exactly and ordered: one workgroup per query row, one candidate per thread and
 // sweep (its row walked with U 16-byte loads in flight, as refine_exact_kernel's), the words of the hits ordered in LDS
-// (bitonic64 over the smallest power of two that holds the list), then written to `stage` behind a reservation on *cursor:
+// (sv_bitonic over the smallest power of two that holds the list), then written to `stage` behind a reservation on *cursor:
 // soff[row] = where, cnt[row] = how many.  Where a row's words sit in `stage` depends on the order the workgroups finish in;
 // nothing that leaves the call does (the unpack reads them through soff).  Flagged (long) rows: cnt = 0, soff = -1.
 // Dynamic LDS: [d] floats, then [np2 of the chunk's longest short list] words.
@@ -115,7 +115,7 @@ __global__ __launch_bounds__(256) void range_refine_kernel(const float* __restri
       atomicAdd(&s_hits, 1u);
     }
   }
-  bitonic64(a, np2, tid);   // (the empty slots, all ones, sort behind every hit: a NaN is never a hit)
+  sv_bitonic(a, np2, tid);   // (the empty slots, all ones, sort behind every hit: a NaN is never a hit)
   const uint32_t hits = s_hits;
   if (tid == 0) {
     s_off = hits ? atomicAdd(cursor, (unsigned long long)hits) : 0ull;

@@ -13,55 +13,21 @@
 //                              is not cheaper to evaluate than its bands row by row (a cost model with measured constants:
 //                              nothing shared -- random queries --, or short bands against a long union), or longer than
 //                              RG_UCAP, keeps the per-row kernels (its rows are flagged in `perrow`)
-//   refine_group_gemm_kernel   exact distances of ALL 32 x U pairs of a grouped group on v_mfma_f32_32x32x2_f32: per output
-//                              element the sequential chain acc = fma(q[k], r[k], acc), k = 0 .. d - 1, from acc = 0 --
-//                              bit for bit the chain of refine_exact_kernel and of the distance-matrix path
-//                              (gemm_kernels.hip, same instruction, same k order) -- then sv_d2 with the same norms.
+//   refine_group_gemm_kernel   exact distances of ALL 32 x U pairs of a grouped group: per 128 union rows one gathered-row tile
+//                              (sv_group_tile_dots, group_tile_dev.h: per output element the sequential chain
+//                              acc = fma(q[k], r[k], acc), k = 0 .. d - 1, from acc = 0 -- bit for bit the chain of
+//                              refine_exact_kernel and of the distance-matrix path), then sv_d2 with the same norms.
 //                              (The pairs outside a query's own band are computed and never read.)
 //   refine_group_select_kernel per query row: the keys of its OWN band out of the group's key matrix (the union kernel leaves the
 //                              union column of every band entry), (distance, id) sort, top k.
-// Workgroup of the GEMM: 4 waves, wave w owns 32 union rows (MT = 1 or 2 accumulator tiles of 32 x 32: groups of <= 32 / <= 64
-// query rows), the query rows are shared through LDS; operands staged k-major ([k][row], odd row stride) exactly like
-// gemm_kernels.hip; global loads run THREE k-tiles ahead in three named register stages (a step's loads carry no condition in
-// the steady-state loop: with one, the compiler waits for every outstanding load before it reuses a stage -- measured: 2 TB/s),
-// one barrier per k-tile.  d % 32 == 0.
+// The operand staging, the load pipeline and the workgroup's shape are the tile's: group_tile_dev.h.  d % 32 == 0.
 #include "ctx.h"
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+#include "group_tile_dev.h"
+#include "knn_dev.h"
 
 namespace {
 
 constexpr int RG_GMAX = 64;      // query rows per group, at most
-
-__device__ __forceinline__ uint32_t rg_f2key(float f) {
-  const uint32_t u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float rg_key2f(uint32_t k) {
-  const uint32_t u = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k;
-  return __uint_as_float(u);
-}
-__device__ __forceinline__ int rg_frag_row(int r, int kk) { return (r & 3) + 8 * (r >> 2) + 4 * kk; }
-
-template <class T, int NTH = 256>
-__device__ __forceinline__ void rg_bitonic(T* a, int n, int tid) {
-  for (int size = 2; size <= n; size <<= 1) {
-    for (int stride = size >> 1; stride > 0; stride >>= 1) {
-      __syncthreads();
-      for (int t = tid; t < (n >> 1); t += NTH) {
-        const int lo = 2 * t - (t & (stride - 1));
-        const int hi = lo + stride;
-        const bool up = ((lo & size) == 0);
-        const T x = a[lo], y = a[hi];
-        if ((y < x) == up) {
-          a[lo] = y;
-          a[hi] = x;
-        }
-      }
-    }
-  }
-  __syncthreads();
-}
 
 // ---- union of a group's band lists ---------------------------------------------------------------------------------------
 constexpr int RG_UT = 1024;   // threads of the union kernel (the sort is its time)
@@ -143,7 +109,7 @@ __global__ __launch_bounds__(RG_UT) void refine_union_kernel(const uint32_t* __r
       int np2 = 64;
       while (np2 < U) np2 <<= 1;
       for (int j = U + tid; j < np2; j += RG_UT) uniq[j] = 0xffffffffu;
-      rg_bitonic<uint32_t, RG_UT>(uniq, np2, tid);
+      sv_bitonic<uint32_t, RG_UT>(uniq, np2, tid);
       for (int j = tid; j < U; j += RG_UT) grp_ids[(size_t)b * ucap + j] = uniq[j];
     }
     // Is the union cheaper?  Measured on MI355X (ns, d = 1024; the first two terms grow with d): the per-row kernels ~0.39 per
@@ -188,133 +154,28 @@ __global__ __launch_bounds__(RG_UT) void refine_union_kernel(const uint32_t* __r
 }
 
 // ---- G query rows x the union's rows: exact fp32 distances as sortable keys -----------------------------------------------
-// Every row is fetched in pieces of RG_KS floats (128 B): one load instruction of a wave covers eight rows x 128 contiguous
-// bytes.  A super-tile of RG_KS k travels in ONE register stage ((MT + 4) x 4 / 4 sixteen-byte loads per thread, in flight
-// while the previous super-tile is multiplied out of LDS) and is parked in a single LDS buffer between two barriers; with
-// 27 KiB of LDS a CU holds five workgroups, which hide each other's load / store / barrier phases.  (Measured, 200 groups of
-// 200-row unions: 512-byte pieces and one workgroup per CU 8.63 ms at d = 98 304 / 0.384 ms at d = 1024, 256-byte pieces
-// 7.70 / 0.378, 128-byte pieces 7.51 / 0.362.)  The loads are inline asm with an explicit wait: a compiler-visible load with
-// a condition on it makes every LDS access behind it wait for all of them.
-// LDS image: ROW-major, row stride KS + 4 floats, and inside every group of 8 k the even k first, then the odd:
-// [k0 k2 k4 k6 | k1 k3 k5 k7].  v_mfma_f32_32x32x2_f32 takes k = 2 s from lanes 0-31 and k = 2 s + 1 from lanes 32-63, so a
-// lane's operands of FOUR consecutive k-steps are one aligned 16-byte read (rows 16 apart share a bank group, which the
-// 16-lane service groups of a ds_read_b128 never hold together), and a loaded float4 goes out as two 8-byte writes.
-// (Measured on the way, 10 000 x 200-row bands of 98 304-d rows: k-major [k][row] tiles fed by ds_read_b32 -- one or two reads,
-//  a wait and one or two MFMAs per k-step, one wave per SIMD -- 63 ms with the matrix pipes 8 % busy: a chain of LDS latencies,
-//  half of the LDS cycles bank conflicts of the transposing 4-byte stores; 128-byte row pieces three tiles ahead: 32-40 ms.)
-typedef float rg_f32x4 __attribute__((ext_vector_type(4)));
-typedef float rg_f32x2 __attribute__((ext_vector_type(2)));
-// The row pieces are requested by inline asm and waited for by a hand-placed s_waitcnt: the compiler takes the destination
-// registers for defined when the asm statement ends, so nothing but today's register allocation keeps it from copying or spilling
-// them between the request and the wait.  That form is therefore tied to the toolchain it was verified on -- ISA
-// inspected, and tests/test_gpu_refine_group.py holds the kernel to the per-row kernels' bits: AMD clang 22 (ROCm 7.2).  Any
-// other compiler gets plain loads, whose waits it places itself (measured slower: it waits for every outstanding load in front
-// of every LDS access behind a conditional load -- but correct by construction).  -DSEGVLAD_RG_PLAIN_LOADS forces that form.
-#if defined(__clang_major__) && __clang_major__ == 22 && !defined(SEGVLAD_RG_PLAIN_LOADS)
-#define RG_ASM_LOADS 1
-#define RG_GLOAD(dst, ptr) asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(dst) : "v"(ptr) : "memory")
-#define RG_WAIT_LOADS() asm volatile("s_waitcnt vmcnt(0)" ::: "memory")
-#else
-#define RG_ASM_LOADS 0
-#define RG_GLOAD(dst, ptr) (dst) = *reinterpret_cast<const rg_f32x4*>(ptr)
-#define RG_WAIT_LOADS() do { } while (0)
-#endif
-constexpr int RG_KS = 32;
-
-template <int MT, int KS>
+// A work item is (group, 128 rows of its union): the ids into LDS, the tile (group_tile_dev.h), the key matrix.
+template <int MT>
 __global__ __launch_bounds__(256) void refine_group_gemm_kernel(const float* __restrict__ Q, const float* __restrict__ R, int d, int m,
                                                                 int G, const float* __restrict__ qn, const float* __restrict__ rn,
                                                                 const uint32_t* __restrict__ grp_cnt,
                                                                 const uint32_t* __restrict__ grp_ids, int ucap,
                                                                 uint64_t* __restrict__ keys, const uint32_t* __restrict__ work) {
-  constexpr int LDR = KS + 4;         // row stride of the LDS image
-  constexpr int LPR = KS / 4;         // lanes (16-byte loads) per row piece
-  constexpr int RPI = 64 / LPR;       // rows per load instruction of a wave
-  constexpr int NR = 32 * MT + 128;   // rows of a super-tile: the group's query rows, then 128 union rows
-  constexpr int NLD = NR / (4 * RPI); // 16-byte loads per thread and super-tile
-  static_assert(NR % (4 * RPI) == 0 && (32 * MT) % (4 * RPI) == 0, "whole instructions of query rows / of union rows");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  float* tile = reinterpret_cast<float*>(smem);                     // [NR][LDR]
-  uint32_t* ids = reinterpret_cast<uint32_t*>(tile + NR * LDR);     // [128]
+  float* tile = reinterpret_cast<float*>(smem);                                             // the tile's staging image
+  uint32_t* ids = reinterpret_cast<uint32_t*>(smem + sv_group_tile_bytes(MT));              // [128]
   if (blockIdx.x >= work[0]) return;
   const uint32_t item = work[1 + blockIdx.x];
   const int b = (int)(item >> 5), c0 = (int)(item & 31u) * 128;
   const int U = (int)grp_cnt[b];
   const int tid = threadIdx.x, w = tid >> 6, l = tid & 63, i = l & 31, kk = l >> 5;
-  const int lp = l % LPR, lr = l / LPR;   // loader coordinates: 16-byte piece of a row, row of the instruction
   const int q0 = b * G;
   const int q_end = min(q0 + G, m);
   if (tid < 128) ids[tid] = grp_ids[(size_t)b * ucap + (c0 + tid < U ? c0 + tid : 0)];   // (columns beyond U: a valid row, never stored)
   __syncthreads();
-  // load j of this thread: staged row rr = 4 RPI j + RPI w + lr, floats 4 lp .. + 3 of the super-tile
-  const float* src[NLD];
-#pragma unroll
-  for (int j = 0; j < NLD; ++j) {
-    const int rr = 4 * RPI * j + RPI * w + lr;
-    src[j] = (rr < 32 * MT ? Q + (size_t)min(q0 + rr, q_end - 1) * d   // (rows beyond the group: never stored)
-                           : R + (size_t)ids[rr - 32 * MT] * d) + 4 * lp;
-  }
-  rg_f32x4 v[NLD];
-  auto gload = [&](int st) {
-#pragma unroll
-    for (int j = 0; j < NLD; ++j) RG_GLOAD(v[j], src[j] + (size_t)st * KS);
-  };
-  // floats 4 lp .. 4 lp + 3 = k-group lp >> 1, half lp & 1: the even k to slots 2 (lp & 1) .. + 1, the odd k four slots further
-  float* st_base = tile + (RPI * w + lr) * LDR + 8 * (lp >> 1) + 2 * (lp & 1);
-  auto sstore = [&]() {
-#pragma unroll
-    for (int j = 0; j < NLD; ++j) asm volatile("" : "+v"(v[j]));   // (the values exist from HERE on: behind the caller's wait; the
-                                                                   //  re-packing moves below are not memory operations)
-#pragma unroll
-    for (int j = 0; j < NLD; ++j) {
-      float* p = st_base + 4 * RPI * j * LDR;
-      rg_f32x2 ev, od;
-      ev[0] = v[j][0];
-      ev[1] = v[j][2];
-      od[0] = v[j][1];
-      od[1] = v[j][3];
-      *reinterpret_cast<rg_f32x2*>(p) = ev;
-      *reinterpret_cast<rg_f32x2*>(p + 4) = od;
-    }
-  };
+  const SvGroupTileQ<MT> qrows = sv_group_tile_query_rows<MT>(Q, d, q0, q_end);
   f32x16 acc[MT];
-#pragma unroll
-  for (int t = 0; t < MT; ++t)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
-  const float* a_frag = tile + i * LDR + 4 * kk;                       // + 32 t rows, + 8 g floats
-  const float* b_frag = tile + (32 * MT + 32 * w + i) * LDR + 4 * kk;
-  const int nst = d / KS;
-  gload(0);
-  RG_WAIT_LOADS();
-  sstore();
-  __syncthreads();
-  for (int st = 0; st < nst; ++st) {
-    if (st + 1 < nst) gload(st + 1);   // in flight while this super-tile is multiplied
-    // KS / 8 groups of 8 k; the fragments of group g + 1 are requested before the MFMAs of group g are issued
-    rg_f32x4 fa[2][MT], fb[2];
-    fb[0] = *reinterpret_cast<const rg_f32x4*>(b_frag);
-#pragma unroll
-    for (int t = 0; t < MT; ++t) fa[0][t] = *reinterpret_cast<const rg_f32x4*>(a_frag + 32 * t * LDR);
-#pragma unroll
-    for (int g = 0; g < KS / 8; ++g) {
-      if (g + 1 < KS / 8) {
-        fb[(g + 1) & 1] = *reinterpret_cast<const rg_f32x4*>(b_frag + 8 * (g + 1));
-#pragma unroll
-        for (int t = 0; t < MT; ++t) fa[(g + 1) & 1][t] = *reinterpret_cast<const rg_f32x4*>(a_frag + 32 * t * LDR + 8 * (g + 1));
-      }
-#pragma unroll
-      for (int u = 0; u < 4; ++u)
-#pragma unroll
-        for (int t = 0; t < MT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[g & 1][t][u], fb[g & 1][u], acc[t], 0, 0, 0);
-    }
-    __syncthreads();   // every wave is done with the LDS image
-    if (st + 1 < nst) {
-      RG_WAIT_LOADS();
-      sstore();
-      __syncthreads();
-    }
-  }
+  sv_group_tile_dots<MT>(tile, ids, qrows, R, d, acc);
   const int col = c0 + 32 * w + i;
   if (col < U) {
     const uint32_t id = ids[32 * w + i];
@@ -323,8 +184,8 @@ __global__ __launch_bounds__(256) void refine_group_gemm_kernel(const float* __r
     for (int t = 0; t < MT; ++t)
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int q = q0 + 32 * t + rg_frag_row(r, kk);
-        if (q < q_end) keys[(size_t)q * ucap + col] = ((uint64_t)rg_f2key(sv_d2(qn[q], r2, acc[t][r])) << 32) | id;
+        const int q = q0 + 32 * t + sv_frag_row(r, kk);
+        if (q < q_end) keys[(size_t)q * ucap + col] = ((uint64_t)f2key_(sv_d2(qn[q], r2, acc[t][r])) << 32) | id;
       }
   }
 }
@@ -344,12 +205,12 @@ __global__ __launch_bounds__(256) void refine_group_select_kernel(const uint32_t
   int np2 = 2;
   while (np2 < n) np2 <<= 1;
   for (int j = tid; j < np2; j += 256) a[j] = j < n ? keys[(size_t)row * ucap + grp_pos[(size_t)row * rcap + j]] : ~0ull;
-  rg_bitonic<uint64_t>(a, np2, tid);
+  sv_bitonic<uint64_t>(a, np2, tid);
   for (int j = tid; j < k; j += 256) {
     float dd = INFINITY;
     int64_t id = -1;
     if (j < n) {
-      dd = rg_key2f((uint32_t)(a[j] >> 32));
+      dd = key2f_((uint32_t)(a[j] >> 32));
       id = (int64_t)(uint32_t)a[j];
     }
     d2_out[row * k + j] = dd;
@@ -380,7 +241,7 @@ int sv_launch_refine_grouped(segvlad_ctx* ctx, const float* Q, const float* R, i
   // a group with more band entries than 0.75 x that stays with the per-row kernels)
   int tcap = 1024;
   while (tcap < 32768 && 3 * (int64_t)tcap < 4 * (int64_t)G * rcap) tcap <<= 1;
-  const bool can = ctx->opt.refine_group != 0 && d % RG_KS == 0 && nq > 128 && (rcap <= 4096 || only_rows) &&
+  const bool can = ctx->opt.refine_group != 0 && d % SV_GT_KS == 0 && nq > 128 && (rcap <= 4096 || only_rows) &&
                    (reinterpret_cast<uintptr_t>(Q) & 15) == 0 && (reinterpret_cast<uintptr_t>(R) & 15) == 0;
   if (!can) {
     if (launches) *launches = 1;
@@ -410,8 +271,8 @@ int sv_launch_refine_grouped(segvlad_ctx* ctx, const float* Q, const float* R, i
   SV_HIP(hipGetLastError());
   {
     const int mt = G > 32 ? 2 : 1;
-    const size_t glds = (size_t)(32 * mt + 128) * (RG_KS + 4) * 4 + 128 * 4;
-    auto gk = mt == 2 ? refine_group_gemm_kernel<2, RG_KS> : refine_group_gemm_kernel<1, RG_KS>;
+    const size_t glds = sv_group_tile_bytes(mt) + 128 * 4;
+    auto gk = mt == 2 ? refine_group_gemm_kernel<2> : refine_group_gemm_kernel<1>;
     SV_HIP(sv_max_dyn_lds(reinterpret_cast<const void*>(gk), glds));
     hipLaunchKernelGGL(gk, dim3(max_items), dim3(256), glds, ctx->stream, Q, R, d, nq, G, qn, rn, gcnt, gids, ucap, gkeys, work);
     SV_HIP(hipGetLastError());

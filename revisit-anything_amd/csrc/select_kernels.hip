@@ -8,15 +8,7 @@
 // serialise 64-way); one more pass collects the k candidates, a bitonic sort on (key, index) orders
 // them.  Ties are resolved towards the lower index, like a stable argsort.
 #include "ctx.h"
-
-__device__ __forceinline__ uint32_t f2key(float f) {
-  const uint32_t u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float key2f(uint32_t k) {
-  const uint32_t u = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k;
-  return __uint_as_float(u);
-}
+#include "knn_dev.h"
 
 // wave-aggregated histogram increment: lanes that share a bin elect one leader per round
 __device__ __forceinline__ void hist_add(uint32_t* hist, bool active, uint32_t bin) {
@@ -68,10 +60,10 @@ __global__ __launch_bounds__(256) void select_topk_kernel(const float* __restric
   const float* x = dist + row * ld;
   const int kk = (int)((int64_t)k < n ? k : n);
   if (STAGED) {
-    for (int64_t j = tid; j < n; j += 256) skey[j] = f2key(x[j]);
+    for (int64_t j = tid; j < n; j += 256) skey[j] = f2key_(x[j]);
     __syncthreads();
   }
-  auto key_at = [&](int64_t j) -> uint32_t { return STAGED ? skey[j] : f2key(x[j]); };
+  auto key_at = [&](int64_t j) -> uint32_t { return STAGED ? skey[j] : f2key_(x[j]); };
 
   uint32_t prefix = 0, mask = 0, krem = (uint32_t)kk, ceq = 0;
   if (kk > 0) {
@@ -162,7 +154,7 @@ __global__ __launch_bounds__(256) void select_topk_kernel(const float* __restric
     int64_t id = -1;
     if (j < kk) {
       const uint64_t c = cand[j];
-      d = key2f((uint32_t)(c >> 32));
+      d = key2f_((uint32_t)(c >> 32));
       id = id_base + (int64_t)(uint32_t)c;
     }
     d2_out[row * out_ld + j] = d;
@@ -219,13 +211,13 @@ __global__ __launch_bounds__(256) void select_cand_kernel(const uint32_t* __rest
   int npad = 2;
   while (npad < (int)c) npad <<= 1;
   for (int j = tid; j < npad; j += 256)
-    a[j] = (j < (int)c) ? (((uint64_t)f2key(cd2[row * cap + j]) << 32) | cid[row * cap + j]) : ~0ull;
+    a[j] = (j < (int)c) ? (((uint64_t)f2key_(cd2[row * cap + j]) << 32) | cid[row * cap + j]) : ~0ull;
   bitonic_sort_lds(a, npad, tid, 256);
   for (int j = tid; j < k; j += 256) {
     float d = INFINITY;
     int64_t id = -1;
     if (j < (int)c) {
-      d = key2f((uint32_t)(a[j] >> 32));
+      d = key2f_((uint32_t)(a[j] >> 32));
       id = (int64_t)(uint32_t)a[j];
     }
     d2_out[row * k + j] = d;
@@ -271,7 +263,7 @@ __global__ __launch_bounds__(256) void merge_topk_kernel(const float* __restrict
     if (j < cand) {
       const int64_t id = idp[row * cand + j];
       if (id >= 0) {
-        e.key = f2key(d2p[row * cand + j]);
+        e.key = f2key_(d2p[row * cand + j]);
         e.id = id;
       }
     }
@@ -313,7 +305,7 @@ __global__ __launch_bounds__(256) void merge_topk_kernel(const float* __restrict
         }
         if (rank < k) {
           const bool valid = e.id != INT64_MAX;
-          d2_out[row * k + rank] = valid ? key2f(e.key) : INFINITY;
+          d2_out[row * k + rank] = valid ? key2f_(e.key) : INFINITY;
           idx_out[row * k + rank] = valid ? e.id : -1;
         }
       }
@@ -325,7 +317,7 @@ __global__ __launch_bounds__(256) void merge_topk_kernel(const float* __restrict
     float d = INFINITY;
     int64_t id = -1;
     if (j < cand && a[j].id != INT64_MAX) {
-      d = key2f(a[j].key);
+      d = key2f_(a[j].key);
       id = a[j].id;
     }
     d2_out[row * k + j] = d;
@@ -379,7 +371,7 @@ __global__ void minmax_init_kernel(uint32_t* mm) {
 __global__ __launch_bounds__(256) void minmax_kernel(const float* __restrict__ x, int64_t n, uint32_t* mm) {
   uint32_t lo = ~0u, hi = 0u;
   for (int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x; j < n; j += (int64_t)gridDim.x * 256) {
-    const uint32_t key = f2key(x[j]);
+    const uint32_t key = f2key_(x[j]);
     lo = min(lo, key);
     hi = max(hi, key);
   }
@@ -400,8 +392,8 @@ __global__ __launch_bounds__(256) void minmax_kernel(const float* __restrict__ x
   }
 }
 __global__ void minmax_final_kernel(const uint32_t* mm, float* out) {
-  out[0] = key2f(mm[0]);
-  out[1] = key2f(mm[1]);
+  out[0] = key2f_(mm[0]);
+  out[1] = key2f_(mm[1]);
 }
 
 int sv_launch_minmax(segvlad_ctx* ctx, const float* sims, int64_t count, float* minmax_dev) {

@@ -14,61 +14,29 @@
 //                         prefix sums of the kept images' row counts: union position p -> (image j, row off[j] + p - uoff[j]).
 //                         The union is never materialised (a shortlist may cover the whole index)
 //     sl_gemm_kernel      1-D grid of (group, slice) workgroups: a group is <= 64 consecutive query rows of one image (the group
-//                         bound of refine_group_kernels.hip), slice s takes the union's 128-row tiles s, s + S, s + 2S, ...  Per tile
-//                         the exact fp32 distances of all group x 128 pairs -- v_mfma_f32_32x32x2_f32 in k order, operands staged
-//                         exactly like refine_group_gemm_kernel, so per pair the sequential chain acc = fma(q[k], r[k], acc) from 0,
-//                         then sv_d2 with the stored norms: bit for bit segvlad_search's value -- then every key (distance bits,
+//                         bound of the tile, group_tile_dev.h), slice s takes the union's 128-row tiles s, s + S, s + 2S, ...  Per tile
+//                         the exact fp32 distances of all group x 128 pairs -- the gathered-row tile of group_tile_dev.h: per pair the
+//                         sequential chain acc = fma(q[k], r[k], acc) from 0 on v_mfma_f32_32x32x2_f32 in k order, then sv_d2 with
+//                         the stored norms: bit for bit segvlad_search's value -- then every key (distance bits,
 //                         row id) below the row's threshold is appended to the row's candidate buffer in global memory.  A buffer
 //                         that could not take another tile is cut to its k best by a workgroup sort, which also sets the threshold
 //                         (the k-th key); at the end every buffer is cut to <= k
 //     sl_final_kernel     per query row: its S slices' lists, (distance, id) sort, top k; (+inf, -1) beyond the allowed rows
 // Nothing is read back during a call: the grid sizes come from qseg_offsets, n_img, M and k (host), the union sizes stay on the device.
 // sl_gemm_kernel and sl_final_kernel also are the exact tail of segvlad_search_excluding (exclude_kernels.hip), whose "union" is the
-// complement of a few intervals of image ids: sv_launch_exclude_tail, at the end of this file, behind the entry point.
+// complement of a few intervals of image ids: sv_launch_exclude_tail, at the end of this file, behind the entry point.  Both launch the
+// pair through sl_launch_gemm.
 #include <algorithm>
 
 #include "ctx.h"
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float sl_f32x4 __attribute__((ext_vector_type(4)));
-typedef float sl_f32x2 __attribute__((ext_vector_type(2)));
+#include "group_tile_dev.h"
+#include "knn_dev.h"
 
 namespace {
 
 constexpr int SL_GMAX = 64;        // query rows per group, at most
 constexpr int SL_SORT_CAP = 4096;  // rows of an image sorted in LDS by the map build (larger images: ordered scan)
-constexpr int SL_KS = 32;          // floats of a row piece (as refine_group_gemm_kernel)
 constexpr int SL_SLICES_MAX = 8;
-
-__device__ __forceinline__ uint32_t sl_f2key(float f) {
-  const uint32_t u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float sl_key2f(uint32_t k) {
-  const uint32_t u = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k;
-  return __uint_as_float(u);
-}
-__device__ __forceinline__ int sl_frag_row(int r, int kk) { return (r & 3) + 8 * (r >> 2) + 4 * kk; }
-
-template <class T, int NTH = 256>
-__device__ __forceinline__ void sl_bitonic(T* a, int n, int tid) {
-  for (int size = 2; size <= n; size <<= 1) {
-    for (int stride = size >> 1; stride > 0; stride >>= 1) {
-      __syncthreads();
-      for (int t = tid; t < (n >> 1); t += NTH) {
-        const int lo = 2 * t - (t & (stride - 1));
-        const int hi = lo + stride;
-        const bool up = ((lo & size) == 0);
-        const T x = a[lo], y = a[hi];
-        if ((y < x) == up) {
-          a[lo] = y;
-          a[hi] = x;
-        }
-      }
-    }
-  }
-  __syncthreads();
-}
 
 // ---- image -> row map -------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void sl_imax_kernel(const int32_t* __restrict__ img, int64_t n, int* __restrict__ out) {
@@ -134,7 +102,7 @@ __global__ __launch_bounds__(256) void sl_sort_kernel(const int32_t* __restrict_
     int np2 = 2;
     while (np2 < c) np2 <<= 1;
     for (int j = tid; j < np2; j += 256) a[j] = j < c ? rows[o + j] : 0xffffffffu;
-    sl_bitonic<uint32_t>(a, np2, tid);
+    sv_bitonic<uint32_t>(a, np2, tid);
     for (int j = tid; j < c; j += 256) rows[o + j] = a[j];
     return;
   }
@@ -173,7 +141,7 @@ __global__ __launch_bounds__(256) void sl_union_kernel(const int32_t* __restrict
     }
     a[j] = v;
   }
-  sl_bitonic<uint32_t>(a, np2, tid);
+  sv_bitonic<uint32_t>(a, np2, tid);
   const int per = np2 / 256 > 0 ? np2 / 256 : 1;
   const int j0 = tid * per, j1 = min(np2, j0 + per);
   uint32_t nk = 0, rs = 0;
@@ -214,16 +182,6 @@ __global__ __launch_bounds__(256) void sl_union_kernel(const int32_t* __restrict
 }
 
 // ---- group x union tiles: exact fp32 distances, candidates below the running threshold ----------------------------------
-// The row pieces are requested and waited for exactly as in refine_group_gemm_kernel (see there: inline asm with a hand-placed
-// wait on the toolchain that form was verified on, plain loads elsewhere or with -DSEGVLAD_RG_PLAIN_LOADS).
-#if defined(__clang_major__) && __clang_major__ == 22 && !defined(SEGVLAD_RG_PLAIN_LOADS)
-#define SL_GLOAD(dst, ptr) asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(dst) : "v"(ptr) : "memory")
-#define SL_WAIT_LOADS() asm volatile("s_waitcnt vmcnt(0)" ::: "memory")
-#else
-#define SL_GLOAD(dst, ptr) (dst) = *reinterpret_cast<const sl_f32x4*>(ptr)
-#define SL_WAIT_LOADS() do { } while (0)
-#endif
-
 struct SlGroup {
   int q0, nrows, img, pad;   // (pad: the group's first list slot in the exclusion's tail, unused by the shortlist search)
 };
@@ -231,8 +189,8 @@ struct SlGroup {
 // EX (the exact tail of segvlad_search_excluding, exclude_kernels.hip): the "union" of group image b is the complement of its merged
 // exclusion intervals -- nu <= 9 contiguous ranges of sl_img_rows POSITIONS, uids[j] the first position of range j (not an image id)
 // and uoff the prefix sums of the ranges' lengths; a group none of whose rows is marked in ex_flags writes empty lists and leaves;
-// a group's lists go to cand / lens at its slot base (SlGroup::pad) instead of its query rows.  Everything else -- the operand
-// staging, the chain, sv_d2, the candidate buffers -- is the one code for both.
+// a group's lists go to cand / lens at its slot base (SlGroup::pad) instead of its query rows.  Everything else -- the tile
+// (group_tile_dev.h), sv_d2, the candidate buffers -- is the one code for both.
 template <int MT, bool EX>
 __global__ __launch_bounds__(256) void sl_gemm_kernel(const float* __restrict__ Q, const float* __restrict__ R, int d,
                                                       const float* __restrict__ qn, const float* __restrict__ rn,
@@ -242,16 +200,9 @@ __global__ __launch_bounds__(256) void sl_gemm_kernel(const float* __restrict__ 
                                                       const uint32_t* __restrict__ unum, int k, int cap,
                                                       uint64_t* __restrict__ cand, uint32_t* __restrict__ lens,
                                                       const uint32_t* __restrict__ ex_flags) {
-  constexpr int KS = SL_KS;
-  constexpr int LDR = KS + 4;
-  constexpr int LPR = KS / 4;
-  constexpr int RPI = 64 / LPR;
-  constexpr int NR = 32 * MT + 128;
-  constexpr int NLD = NR / (4 * RPI);
-  static_assert(NR % (4 * RPI) == 0 && (32 * MT) % (4 * RPI) == 0, "whole instructions of query rows / of union rows");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   // [max(staging image, compaction scratch)] [dk: 32 MT x 128 distance keys]
-  const size_t stage_bytes = max((size_t)NR * LDR * 4, (size_t)cap * 8);
+  const size_t stage_bytes = max(sv_group_tile_bytes(MT), (size_t)cap * 8);
   float* tile = reinterpret_cast<float*>(smem);
   uint64_t* scratch = reinterpret_cast<uint64_t*>(smem);
   uint32_t* dk = reinterpret_cast<uint32_t*>(smem + stage_bytes);
@@ -274,7 +225,6 @@ __global__ __launch_bounds__(256) void sl_gemm_kernel(const float* __restrict__ 
   const uint32_t* ui = uids + (size_t)b * M;
   const int U = (int)uo[nu];
   const int tid = threadIdx.x, w = tid >> 6, l = tid & 63, i = l & 31, kk = l >> 5;
-  const int lp = l % LPR, lr = l / LPR;
   if (tid < 32 * MT) {
     s_thr[tid] = ~0ull;
     s_cnt[tid] = 0u;
@@ -287,7 +237,7 @@ __global__ __launch_bounds__(256) void sl_gemm_kernel(const float* __restrict__ 
     int np2 = 2;
     while (np2 < n) np2 <<= 1;
     for (int j = tid; j < np2; j += 256) scratch[j] = j < n ? buf[j] : ~0ull;
-    sl_bitonic<uint64_t>(scratch, np2, tid);
+    sv_bitonic<uint64_t>(scratch, np2, tid);
     const int nn = min(n, keep);
     for (int j = tid; j < nn; j += 256) buf[j] = scratch[j];
     if (tid == 0) {
@@ -296,6 +246,7 @@ __global__ __launch_bounds__(256) void sl_gemm_kernel(const float* __restrict__ 
     }
     __syncthreads();
   };
+  const SvGroupTileQ<MT> qrows = sv_group_tile_query_rows<MT>(Q, d, q0, q_end);   // (the same for every tile)
   const int ntile = (U + 127) >> 7;
   for (int t = s; t < ntile; t += S) {
     const int c0 = t * 128;
@@ -314,70 +265,8 @@ __global__ __launch_bounds__(256) void sl_gemm_kernel(const float* __restrict__ 
       ids[tid] = id;   // (columns beyond U: row 0, computed and never used)
     }
     __syncthreads();
-    const float* src[NLD];
-#pragma unroll
-    for (int j = 0; j < NLD; ++j) {
-      const int rr = 4 * RPI * j + RPI * w + lr;
-      src[j] = (rr < 32 * MT ? Q + (size_t)min(q0 + rr, q_end - 1) * d : R + (size_t)ids[rr - 32 * MT] * d) + 4 * lp;
-    }
-    sl_f32x4 v[NLD];
-    auto gload = [&](int st) {
-#pragma unroll
-      for (int j = 0; j < NLD; ++j) SL_GLOAD(v[j], src[j] + (size_t)st * KS);
-    };
-    float* st_base = tile + (RPI * w + lr) * LDR + 8 * (lp >> 1) + 2 * (lp & 1);
-    auto sstore = [&]() {
-#pragma unroll
-      for (int j = 0; j < NLD; ++j) asm volatile("" : "+v"(v[j]));
-#pragma unroll
-      for (int j = 0; j < NLD; ++j) {
-        float* p = st_base + 4 * RPI * j * LDR;
-        sl_f32x2 ev, od;
-        ev[0] = v[j][0];
-        ev[1] = v[j][2];
-        od[0] = v[j][1];
-        od[1] = v[j][3];
-        *reinterpret_cast<sl_f32x2*>(p) = ev;
-        *reinterpret_cast<sl_f32x2*>(p + 4) = od;
-      }
-    };
     f32x16 acc[MT];
-#pragma unroll
-    for (int u = 0; u < MT; ++u)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[u][r] = 0.f;
-    const float* a_frag = tile + i * LDR + 4 * kk;
-    const float* b_frag = tile + (32 * MT + 32 * w + i) * LDR + 4 * kk;
-    const int nst = d / KS;
-    gload(0);
-    SL_WAIT_LOADS();
-    sstore();
-    __syncthreads();
-    for (int st = 0; st < nst; ++st) {
-      if (st + 1 < nst) gload(st + 1);
-      sl_f32x4 fa[2][MT], fb[2];
-      fb[0] = *reinterpret_cast<const sl_f32x4*>(b_frag);
-#pragma unroll
-      for (int u = 0; u < MT; ++u) fa[0][u] = *reinterpret_cast<const sl_f32x4*>(a_frag + 32 * u * LDR);
-#pragma unroll
-      for (int gg = 0; gg < KS / 8; ++gg) {
-        if (gg + 1 < KS / 8) {
-          fb[(gg + 1) & 1] = *reinterpret_cast<const sl_f32x4*>(b_frag + 8 * (gg + 1));
-#pragma unroll
-          for (int u = 0; u < MT; ++u) fa[(gg + 1) & 1][u] = *reinterpret_cast<const sl_f32x4*>(a_frag + 32 * u * LDR + 8 * (gg + 1));
-        }
-#pragma unroll
-        for (int x = 0; x < 4; ++x)
-#pragma unroll
-          for (int u = 0; u < MT; ++u) acc[u] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[gg & 1][u][x], fb[gg & 1][x], acc[u], 0, 0, 0);
-      }
-      __syncthreads();
-      if (st + 1 < nst) {
-        SL_WAIT_LOADS();
-        sstore();
-        __syncthreads();
-      }
-    }
+    sv_group_tile_dots<MT>(tile, ids, qrows, R, d, acc);   // (on return `tile` is free: compact() below sorts in it)
     {
       const int col = 32 * w + i;
       const float r2 = rn[ids[col]];
@@ -385,8 +274,8 @@ __global__ __launch_bounds__(256) void sl_gemm_kernel(const float* __restrict__ 
       for (int u = 0; u < MT; ++u)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int lr2 = 32 * u + sl_frag_row(r, kk);
-          if (q0 + lr2 < q_end) dk[lr2 * 128 + col] = sl_f2key(sv_d2(qn[q0 + lr2], r2, acc[u][r]));
+          const int lr2 = 32 * u + sv_frag_row(r, kk);
+          if (q0 + lr2 < q_end) dk[lr2 * 128 + col] = f2key_(sv_d2(qn[q0 + lr2], r2, acc[u][r]));
         }
     }
     __syncthreads();
@@ -431,12 +320,12 @@ __global__ __launch_bounds__(256) void sl_final_kernel(const uint64_t* __restric
     total += n;
   }
   for (int j = total + tid; j < np2; j += 256) a[j] = ~0ull;
-  if (S > 1 || total > 1) sl_bitonic<uint64_t>(a, np2, tid);
+  if (S > 1 || total > 1) sv_bitonic<uint64_t>(a, np2, tid);
   for (int j = tid; j < k; j += 256) {
     float dd = INFINITY;
     int64_t id = -1;
     if (j < total) {
-      dd = sl_key2f((uint32_t)(a[j] >> 32));
+      dd = key2f_((uint32_t)(a[j] >> 32));
       id = (int64_t)(uint32_t)a[j];
       if (!(dd < INFINITY)) id = -1;   // (never listed: segvlad.h, "Non-finite rows"; sv_d2 has made a NaN +inf)
     }
@@ -505,11 +394,44 @@ int sv_sl_map_host(segvlad_ctx* ctx) {
   return SEGVLAD_OK;
 }
 
+// The exact GEMM and the final sort, for both searches: sl_gemm_kernel<., EX> over the groups [ng] (HOST; gmax = the longest), then
+// sl_final_kernel over the n_lists candidate lists (the query rows; EX: the list slots).  uids / uoff [.][M], [.][M + 1] / unum are
+// the device tables the kernel reads in its mode, flags the EX row flags (else null).  Two launches, nothing read back.
+static int sl_launch_gemm(segvlad_ctx* ctx, bool ex, const float* Q, const float* qn, const SlGroup* groups, int ng, int gmax,
+                          int n_lists, int M, const uint32_t* uids, const uint32_t* uoff, const uint32_t* unum, const uint32_t* flags,
+                          int k, float* d2_out, int64_t* idx_out) {
+  // slices per group: ~1536 workgroups (256 CUs x 2 resident x 3: the GEMM is latency-bound at one or two waves per SIMD),
+  // the lists of a row bounded by 8 k keys (the final sort) and the candidate buffers by ~512 MB
+  const int cap = k <= 256 ? 1024 : 2048;
+  int S = std::max(1, std::min(SL_SLICES_MAX, (1536 + ng - 1) / std::max(ng, 1)));
+  while (S > 1 && (S * k > 8192 || (size_t)n_lists * S * cap * 8 > ((size_t)512 << 20))) --S;
+  const void* dgrp;
+  SV_TRY(sv_in(ctx, groups, (size_t)ng * sizeof(SlGroup), &dgrp));
+  SV_HIP(ctx->s_sl_cand.reserve((size_t)n_lists * S * cap * 8));
+  SV_HIP(ctx->s_sl_lens.reserve((size_t)n_lists * S * 4));
+  uint64_t* cand = ctx->s_sl_cand.as<uint64_t>();
+  uint32_t* lens = ctx->s_sl_lens.as<uint32_t>();
+  const int mt = gmax > 32 ? 2 : 1;
+  const size_t glds = std::max(sv_group_tile_bytes(mt), (size_t)cap * 8) + (size_t)32 * mt * 128 * 4;
+  auto gk = ex ? (mt == 2 ? sl_gemm_kernel<2, true> : sl_gemm_kernel<1, true>) : (mt == 2 ? sl_gemm_kernel<2, false> : sl_gemm_kernel<1, false>);
+  SV_HIP(sv_max_dyn_lds(reinterpret_cast<const void*>(gk), glds));
+  hipLaunchKernelGGL(gk, dim3((unsigned)(ng * S)), dim3(256), glds, ctx->stream, Q, ctx->db_rows.as<float>(), ctx->db_d, qn,
+                     ctx->db_norms.as<float>(), (const SlGroup*)dgrp, S, M, ctx->sl_img_off.as<uint32_t>(),
+                     ctx->sl_img_rows.as<uint32_t>(), uids, uoff, unum, k, cap, cand, lens, flags);
+  SV_HIP(hipGetLastError());
+  int np2 = 2;
+  while (np2 < S * k) np2 <<= 1;
+  const size_t flds = (size_t)np2 * 8;
+  if (flds > 48 * 1024) SV_HIP(sv_max_dyn_lds(reinterpret_cast<const void*>(sl_final_kernel), flds));
+  hipLaunchKernelGGL(sl_final_kernel, dim3((unsigned)n_lists), dim3(256), flds, ctx->stream, cand, lens, S, cap, k, np2, d2_out, idx_out);
+  SV_HIP(hipGetLastError());
+  return SEGVLAD_OK;
+}
+
 // segvlad_search_shortlist after the argument checks: Q on the device, 16-byte aligned, qn its squared norms; qoff host; shortlist /
 // outputs on the device
 static int search_shortlist(segvlad_ctx* ctx, const float* Q, int nq, const float* qn, const int32_t* qoff, int n_img,
                             const int32_t* shortlist, int M, int k, float* d2_out, int64_t* idx_out) {
-  const int d = ctx->db_d;
   {
     StageScope sc(ctx, "knn_shortlist");
     const bool rebuilt = !ctx->sl_map_valid;
@@ -539,33 +461,8 @@ static int search_shortlist(segvlad_ctx* ctx, const float* Q, int nq, const floa
                        ctx->sl_img_off.as<uint32_t>(), ctx->s_sl_uids.as<uint32_t>(), ctx->s_sl_uoff.as<uint32_t>(),
                        ctx->s_sl_unum.as<uint32_t>());
     SV_HIP(hipGetLastError());
-    // slices per group: ~1536 workgroups (256 CUs x 2 resident x 3: the GEMM is latency-bound at one or two waves per SIMD),
-    // the lists of a row bounded by 8 k keys (the final sort) and the candidate buffers by ~512 MB
-    const int cap = k <= 256 ? 1024 : 2048;
-    int S = std::max(1, std::min(SL_SLICES_MAX, (1536 + ng - 1) / std::max(ng, 1)));
-    while (S > 1 && (S * k > 8192 || (size_t)nq * S * cap * 8 > ((size_t)512 << 20))) --S;
-    const void* dgrp;
-    SV_TRY(sv_in(ctx, grp.data(), (size_t)ng * sizeof(SlGroup), &dgrp));
-    SV_HIP(ctx->s_sl_cand.reserve((size_t)nq * S * cap * 8));
-    SV_HIP(ctx->s_sl_lens.reserve((size_t)nq * S * 4));
-    const int mt = gmax > 32 ? 2 : 1;
-    const size_t stage_bytes = std::max((size_t)(32 * mt + 128) * (SL_KS + 4) * 4, (size_t)cap * 8);
-    const size_t glds = stage_bytes + (size_t)32 * mt * 128 * 4;
-    auto gk = mt == 2 ? sl_gemm_kernel<2, false> : sl_gemm_kernel<1, false>;
-    SV_HIP(sv_max_dyn_lds(reinterpret_cast<const void*>(gk), glds));
-    hipLaunchKernelGGL(gk, dim3((unsigned)(ng * S)), dim3(256), glds, ctx->stream, Q, ctx->db_rows.as<float>(), d, qn,
-                       ctx->db_norms.as<float>(), (const SlGroup*)dgrp, S, M, ctx->sl_img_off.as<uint32_t>(),
-                       ctx->sl_img_rows.as<uint32_t>(), ctx->s_sl_uids.as<uint32_t>(), ctx->s_sl_uoff.as<uint32_t>(),
-                       ctx->s_sl_unum.as<uint32_t>(), k, cap, ctx->s_sl_cand.as<uint64_t>(), ctx->s_sl_lens.as<uint32_t>(),
-                       (const uint32_t*)nullptr);
-    SV_HIP(hipGetLastError());
-    int np2 = 2;
-    while (np2 < S * k) np2 <<= 1;
-    const size_t flds = (size_t)np2 * 8;
-    if (flds > 48 * 1024) SV_HIP(sv_max_dyn_lds(reinterpret_cast<const void*>(sl_final_kernel), flds));
-    hipLaunchKernelGGL(sl_final_kernel, dim3((unsigned)nq), dim3(256), flds, ctx->stream, ctx->s_sl_cand.as<uint64_t>(),
-                       ctx->s_sl_lens.as<uint32_t>(), S, cap, k, np2, d2_out, idx_out);
-    SV_HIP(hipGetLastError());
+    SV_TRY(sl_launch_gemm(ctx, false, Q, qn, grp.data(), ng, gmax, nq, M, ctx->s_sl_uids.as<uint32_t>(), ctx->s_sl_uoff.as<uint32_t>(),
+                          ctx->s_sl_unum.as<uint32_t>(), nullptr, k, d2_out, idx_out));
     sc.count(rebuilt ? 8 : 3);
   }
   return SEGVLAD_OK;
@@ -611,33 +508,10 @@ int sv_launch_exclude_tail(segvlad_ctx* ctx, const float* Q, const float* qn, co
                            int k, float* d2_tmp, int64_t* idx_tmp) {
   static_assert(sizeof(SlGroup) == 16, "groups are handed over as int32 quadruples");
   constexpr int M = SV_EX_RANGES;
-  const int d = ctx->db_d;
-  const void *dgrp, *dnum, *doff, *dst;
-  SV_TRY(sv_in(ctx, groups, (size_t)ng * sizeof(SlGroup), &dgrp));
+  const void *dnum, *doff, *dst;
   SV_TRY(sv_in(ctx, unum, (size_t)n_tab * 4, &dnum));
   SV_TRY(sv_in(ctx, uoff, (size_t)n_tab * (M + 1) * 4, &doff));
   SV_TRY(sv_in(ctx, ustart, (size_t)n_tab * M * 4, &dst));
-  const int cap = k <= 256 ? 1024 : 2048;
-  int S = std::max(1, std::min(SL_SLICES_MAX, (1536 + ng - 1) / std::max(ng, 1)));
-  while (S > 1 && (S * k > 8192 || (size_t)n_slots * S * cap * 8 > ((size_t)512 << 20))) --S;
-  SV_HIP(ctx->s_sl_cand.reserve((size_t)n_slots * S * cap * 8));
-  SV_HIP(ctx->s_sl_lens.reserve((size_t)n_slots * S * 4));
-  const int mt = gmax > 32 ? 2 : 1;
-  const size_t stage_bytes = std::max((size_t)(32 * mt + 128) * (SL_KS + 4) * 4, (size_t)cap * 8);
-  const size_t glds = stage_bytes + (size_t)32 * mt * 128 * 4;
-  auto gk = mt == 2 ? sl_gemm_kernel<2, true> : sl_gemm_kernel<1, true>;
-  SV_HIP(sv_max_dyn_lds(reinterpret_cast<const void*>(gk), glds));
-  hipLaunchKernelGGL(gk, dim3((unsigned)(ng * S)), dim3(256), glds, ctx->stream, Q, ctx->db_rows.as<float>(), d, qn,
-                     ctx->db_norms.as<float>(), (const SlGroup*)dgrp, S, M, ctx->sl_img_off.as<uint32_t>(),
-                     ctx->sl_img_rows.as<uint32_t>(), (const uint32_t*)dst, (const uint32_t*)doff, (const uint32_t*)dnum, k, cap,
-                     ctx->s_sl_cand.as<uint64_t>(), ctx->s_sl_lens.as<uint32_t>(), flags);
-  SV_HIP(hipGetLastError());
-  int np2 = 2;
-  while (np2 < S * k) np2 <<= 1;
-  const size_t flds = (size_t)np2 * 8;
-  if (flds > 48 * 1024) SV_HIP(sv_max_dyn_lds(reinterpret_cast<const void*>(sl_final_kernel), flds));
-  hipLaunchKernelGGL(sl_final_kernel, dim3((unsigned)n_slots), dim3(256), flds, ctx->stream, ctx->s_sl_cand.as<uint64_t>(),
-                     ctx->s_sl_lens.as<uint32_t>(), S, cap, k, np2, d2_tmp, idx_tmp);
-  SV_HIP(hipGetLastError());
-  return SEGVLAD_OK;
+  return sl_launch_gemm(ctx, true, Q, qn, reinterpret_cast<const SlGroup*>(groups), ng, gmax, n_slots, M, (const uint32_t*)dst,
+                        (const uint32_t*)doff, (const uint32_t*)dnum, flags, k, d2_tmp, idx_tmp);
 }

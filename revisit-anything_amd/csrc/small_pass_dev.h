@@ -60,7 +60,7 @@ __device__ __forceinline__ void merge_best(uint64_t* __restrict__ best, int kp, 
   for (int j = tid; j < kp; j += 256) a[j] = best[j];
   a[kp + tid] = better ? mine : ~0ull;
   for (int j = kp + 256 + tid; j < ns; j += 256) a[j] = ~0ull;
-  bitonic64(a, ns, tid);
+  sv_bitonic(a, ns, tid);
   for (int j = tid; j < kp; j += 256) best[j] = a[j];
   __syncthreads();
 }

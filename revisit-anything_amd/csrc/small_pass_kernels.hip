@@ -107,7 +107,7 @@ __global__ __launch_bounds__(256) void small_tail_kernel(const float* __restrict
         }
         if (j < nb) a[j] = ((uint64_t)f2key_(sv_d2(q2, rn[id], acc[0])) << 32) | id;
       }
-      bitonic64(a, np2, tid);
+      sv_bitonic(a, np2, tid);
       for (int j = tid; j < k; j += 256) {
         const bool in = j < nb;
         d2_out[(size_t)row * k + j] = in ? key2f_((uint32_t)(a[j] >> 32)) : INFINITY;

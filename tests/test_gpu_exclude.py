@@ -301,18 +301,34 @@ def _crowded(rng, n, d, n_excl_img, first, nq):
     return _unit(R), img, _unit(Q)
 
 
-@pytest.mark.parametrize("variant", ["50_rows", "130_rows_three_groups", "d1024_n20000"])
+@pytest.mark.parametrize("variant", ["50_rows", "130_rows_three_groups", "d1024_n20000", "d32_single_row_range"])
 def test_the_tail(eng, eng2, variant):
     rng = np.random.default_rng(7)
     n, d, nq = (20000, 1024, 50) if variant == "d1024_n20000" else (6000, 64, 130 if variant.startswith("130") else 50)
+    single = variant == "d32_single_row_range"
+    if single:
+        d = 32                                          # one k-tile of the tail's GEMM (csrc/group_tile_dev.h)
     R, img, Q = _crowded(rng, n, d, 40, 40, nq)
     qoff = np.array([0, nq], np.int32)
     ex = np.array([[[40, 79]]], np.int32)
+    x_max = 2000
+    if single:
+        # image 60, inside the cluster, keeps ONE row (3000); the windows 40 .. 59 and 61 .. 119 leave two allowed ranges of map
+        # positions: the 2000 rows of the images 0 .. 39, and that row
+        img[3001:3050] = 61
+        ex = np.array([[[40, 59], [61, 119]]], np.int32)
+        x_max = 3999
     k = 50
     D = _emu_d2(Q, R)
-    # the input's property, not the library's: no allowed row is among a query row's nearest 1024
+    # the input's property, not the library's: no allowed row is among a query row's nearest 1024 (single: at most that one row,
+    # which is every query row's nearest allowed row)
     near = np.argsort(D, axis=1, kind="stable")[:, :1024]
-    assert (~_excluded(img, ex[0]))[near].sum() == 0
+    allowed = ~_excluded(img, ex[0])
+    if single:
+        assert allowed.sum() == 2001 and allowed[3000] and (allowed[near].sum(axis=1) <= 1).all()
+        assert (_brute(D, img, qoff, ex, k)[1][:, 0] == 3000).all()
+    else:
+        assert allowed[near].sum() == 0
     eng.db_reset()
     eng.db_add(R, img)
     eng.set_profiling(True)
@@ -323,7 +339,7 @@ def test_the_tail(eng, eng2, variant):
     eng.set_profiling(False)
     assert launches == 5                                # query norms, compaction, the tail's GEMM, its final sort, the scatter
     st = eng.exclude_stats()
-    assert st["k_fetch"] == 1024 and st["x_max"] == 2000
+    assert st["k_fetch"] == 1024 and st["x_max"] == x_max
     assert st["tail_rows"] == nq                        # EVERY row must have gone through the tail
     _check(got, _brute(D, img, qoff, ex, k))
     _check(got, _fresh(eng2, R, img, Q, qoff, ex, k))

@@ -208,6 +208,39 @@ def test_reranking_puts_the_true_image_first(eng, seed):
     assert np.array_equal(re_h.cpu().numpy(), re.cpu().numpy())
 
 
+def _tile_edges(d, two_tiles):
+    """Shapes at the edges of the gathered-row tile's pipeline (csrc/group_tile_dev.h).  d = 32 is ONE k-tile -- the prologue's load
+    alone, the loop body runs once without a prefetch --, d = 96 an odd count of three.  Reference images of 1, 128 and 129 rows: one
+    live column, a full 128-row tile, a tile and one column (and 42 more rows in a fourth image that no slot names).  Query images
+    of 1 and 32 rows take one accumulator tile per wave, of 33 and 64 rows two: the kernel is chosen per CALL by the longest group,
+    so the two pairs are two cases.  Every query image meets every reference image."""
+    rng = np.random.default_rng(300 + d + int(two_tiles))
+    img = np.repeat(np.arange(4, dtype=np.int32), [1, 128, 129, 42])
+    R = _unit(rng.standard_normal((len(img), d)).astype(np.float32))
+    rows = (33, 64) if two_tiles else (1, 32)
+    qoff = np.array([0, rows[0], rows[0] + rows[1]], np.int32)
+    Q = _unit(R[rng.integers(0, len(R), qoff[-1])] + 0.2 * rng.standard_normal((qoff[-1], d)).astype(np.float32))
+    cand = np.array([[0, 1, 2], [2, 0, 1]], np.int32)
+    return R, img, qoff, Q, cand
+
+
+@pytest.mark.parametrize("two_tiles", [False, True], ids=["rows_1_32", "rows_33_64"])
+@pytest.mark.parametrize("d", [32, 96])
+def test_tile_edges_against_the_yardstick(eng, d, two_tiles):
+    R, img, qoff, Q, cand = _tile_edges(d, two_tiles)
+    eng.db_reset()
+    eng.db_add(R, img)
+    want = _yardstick(Q, R, img, qoff, cand, np.inf)
+    share = float(want["mutual"].mean())
+    print(f"[match] tile edges d={d} rows {np.diff(qoff).tolist()}: {want['mutual'].size} (row, slot) entries, {share:.3f} mutual")
+    assert (want["fwd_idx"] >= 0).all() and 0.10 <= share <= 0.90, share   # otherwise the flags test nothing
+    got = eng.match_pairs(Q, qoff, cand, want_rows=True)
+    _check(got, want)
+    _forward_half_equals_the_shortlist_search(eng, Q, qoff, cand, got)
+    lim = 1.0 if d == 32 else 1.5                       # (cuts the mutual pairs to 0.29 .. 0.49 of the entries)
+    _check(eng.match_pairs(Q, qoff, cand, max_d2=lim, want_rows=True), _yardstick(Q, R, img, qoff, cand, lim))
+
+
 def test_live_index(eng):
     R, img, qoff, Q, cand = _ragged(4)
     eng.db_reset()

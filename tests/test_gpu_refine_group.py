@@ -108,10 +108,11 @@ def test_duplicates_and_second_tier_rows_beside_grouped_rows():
     assert st["n_refine2"] > 0, st
 
 
-@pytest.mark.parametrize("hint,d", [(50, 1024), (50, 256), (7, 256), (64, 128), (33, 1024), (50, 160)])
+@pytest.mark.parametrize("hint,d", [(50, 1024), (50, 256), (7, 256), (64, 128), (33, 1024), (50, 160), (33, 32), (64, 32), (50, 96)])
 def test_image_sized_groups_via_the_hint(hint, d):
     """option query_group: a query image's rows (here `hint` noisy copies of one place's rows) form one group -- two 32-row
-    accumulator tiles per wave beyond 32 rows -- and the last group of the batch is cut."""
+    accumulator tiles per wave beyond 32 rows -- and the last group of the batch is cut.  d = 32 is a single k-tile of the
+    gathered-row tile (csrc/group_tile_dev.h: the prologue's load alone), d = 96 an odd count of three."""
     g = torch.Generator(device="cuda:0")
     g.manual_seed(60 + hint)
     places, per = 1200, 64

@@ -379,6 +379,49 @@ int segvlad_match_pairs(segvlad_ctx* ctx, const float* Q, int nq, const int32_t*
                         float max_d2, int32_t* n_mutual_out, double* score_out, int32_t* order_out, int64_t* fwd_idx_out,
                         float* fwd_d2_out, uint8_t* mutual_out);
 
+/* ---- spatial verification of matched segments: how many correspondences of a query image / candidate pair agree on one 2-D
+ *      similarity transform of their centroids (no reference counterpart: the reference stops at the vote, func_vpr.py:207-224, and
+ *      looks at the matches of ONE image pair by eye, func_vpr.py:247-270).  The step behind segvlad_match_pairs: a count of mutual
+ *      pairs says two images hold similar-looking segments, this call says whether they are laid out the same way.  It does not
+ *      touch the index and works on any correspondences.
+ *      q_xy [nq][2] fp64 (x, y) centroid of every query row, r_xy [n_r][2] fp64 centroid of every index row id (the caller's
+ *      table -- segvlad_mask_centroids / segvlad_incidence_centroids produce such centroids --, compacted with new_id_out after
+ *      segvlad_db_remove); both device or host.  qseg_offsets [n_img+1] int32 HOST as in segvlad_match_pairs (0 rows allowed).
+ *      fwd_idx [nq][C] int64 and mutual [nq][C] uint8, device or host: segvlad_match_pairs' fwd_idx_out / mutual_out, 1 <= C <= 64.
+ *      Correspondences of slot (b, j): the query rows q of image b, in ascending q, with mutual[q][j] != 0 and
+ *      0 <= fwd_idx[q][j] < n_r and all four coordinates (q_xy[q], r_xy[fwd_idx[q][j]]) finite.  Any other row is dropped: not a
+ *      correspondence, not an inlier, inlier_out 0.  M = their number, (p_m, s_m) the m-th: p the query point, s the reference point.
+ *      Hypotheses: every pair i < j of the M correspondences, numbered h = 0, 1, ... in lexicographic (i, j) order.  The search is
+ *      exhaustive: no sampling, no seed.
+ *      Arithmetic, fp64, every operation separately rounded (no fused multiply-add) and in exactly this order.  Hypothesis (i, j):
+ *        dx = p_j.x - p_i.x, dy = p_j.y - p_i.y;  ex = s_j.x - s_i.x, ey = s_j.y - s_i.y
+ *        n = dx*dx + dy*dy, m = ex*ex + ey*ey;  ar = ex*dx + ey*dy, ai = ey*dx - ex*dy
+ *      It is ELIGIBLE when n > 0 && (min_scale*min_scale)*n <= m && m <= (max_scale*max_scale)*n.  Correspondence t is an INLIER when, with
+ *        px = p_t.x - p_i.x, py = p_t.y - p_i.y;  sx = s_t.x - s_i.x, sy = s_t.y - s_i.y
+ *        ux = (ar*px - ai*py) - n*sx, uy = (ar*py + ai*px) - n*sy
+ *      ux*ux + uy*uy < ((tol*tol)*n)*n, strictly: |a (p_t - p_i) - (s_t - s_i)| < tol for the similarity a = ds conj(dp) / |dp|^2,
+ *      multiplied through by n -- no division and no square root on the decision path, so a host loop in fp64 reproduces every
+ *      decision bit for bit.
+ *      Winner: the eligible hypothesis with the most inliers, ties to the lowest h.  Outputs, device or host; all but
+ *      n_inlier_out may be NULL:
+ *        n_inlier_out [n_img][C] int32     the winner's inlier count; 0 when M < 2 or no hypothesis is eligible
+ *        pair_out     [n_img][C][2] int32  the query rows (q_i, q_j) of the winner's sample; (-1, -1) when there is none
+ *        model_out    [n_img][C][4] fp64   (a_re, a_im, t_x, t_y): a = (ar/n, ai/n), t = s_i - a p_i; NaN when there is none.
+ *                                          Informative only: it plays no part in any decision
+ *        order_out    [n_img][C] int32     image b's slots sorted by (n_inlier desc, slot asc)
+ *        inlier_out   [nq][C] uint8        1 where the row is an inlier of its slot's winner, else 0
+ *      SEGVLAD_ERR_ARG on null required pointers, negative sizes, C outside 1 .. 64, bad offsets or nq != qseg_offsets[n_img],
+ *      qseg_offsets in device memory, tol not finite or <= 0, or unless 0 < min_scale <= max_scale < inf.  SEGVLAD_ERR_LIMIT when
+ *      a query image owns more than 256 rows: the exhaustive search is cubic in M (about 14 M * M (M - 1) / 2 fp64 operations
+ *      per slot).  n_img == 0: OK.  nq == 0 with n_img > 0: the per-image outputs are still written (zeros, (-1, -1), NaN, the
+ *      identity order).  Deterministic: two calls return the same bits.  The call does not synchronise when every output is
+ *      device memory (the grid is sized on the host from qseg_offsets alone; host outputs are copied back behind one
+ *      synchronisation).  Stage timer "verify_pairs".                                                                       */
+int segvlad_verify_pairs(segvlad_ctx* ctx, const double* q_xy, int nq, const double* r_xy, int64_t n_r, const int32_t* qseg_offsets,
+                         int n_img, int C, const int64_t* fwd_idx, const uint8_t* mutual, double tol, double min_scale,
+                         double max_scale, int32_t* n_inlier_out, int32_t* pair_out, double* model_out, int32_t* order_out,
+                         uint8_t* inlier_out);
+
 /* ---- merge of per-shard top-k lists (no reference counterpart: the reference is single-process).
  *      d2_parts/idx_parts [nq][parts*k] (shard-major within a row, global ids); output top-k by
  *      (distance, lower id).  An entry with id < 0 is an empty slot whatever its distance: it comes
@@ -418,7 +461,7 @@ int segvlad_vote(segvlad_ctx* ctx, const int64_t* idx, const float* sims, const 
                  int32_t* pred_out, double* score_out);
 
 /* ---- instrumentation: with profiling on, every kernel group of a stage ("incidence", "adjacency",
- *      "assign", "prep", "aggregate", "pca", "describe" (segvlad_describe as a whole: its parts overlap), "knn_level0", "knn_gemm", "knn_select", "knn_fallback", "knn_shortlist" (segvlad_search_shortlist), "knn_exclude" (the kernels segvlad_search_excluding adds to its inner search), "knn_group" (the kernels segvlad_search_grouped adds to its inner search), "knn_range" (the kernels of segvlad_range_search), "match_pairs" (segvlad_match_pairs), "db_remove" (segvlad_db_remove), "vote") is bracketed by a HIP event pair
+ *      "assign", "prep", "aggregate", "pca", "describe" (segvlad_describe as a whole: its parts overlap), "knn_level0", "knn_gemm", "knn_select", "knn_fallback", "knn_shortlist" (segvlad_search_shortlist), "knn_exclude" (the kernels segvlad_search_excluding adds to its inner search), "knn_group" (the kernels segvlad_search_grouped adds to its inner search), "knn_range" (the kernels of segvlad_range_search), "match_pairs" (segvlad_match_pairs), "verify_pairs" (segvlad_verify_pairs), "db_remove" (segvlad_db_remove), "vote") is bracketed by a HIP event pair
  *      on the context stream.  segvlad_stage_ms returns the SUM of the elapsed times (ms) and the number
  *      of kernel launches recorded for the stage since the last segvlad_profile_reset; it returns
  *      SEGVLAD_ERR_STATE if the stage has not run.  Replaces the (discarded) time.time() pair of

@@ -109,6 +109,16 @@ def check_candidates(cand: np.ndarray, n_img: int) -> None:
             raise ValueError(f"candidate id {hi} out of the int32 range")
 
 
+MAX_VERIFY_ROWS = 256   # rows per query image of segvlad_verify_pairs
+
+
+def _is_integral(x) -> bool:
+    """Integers or booleans, as a tensor, an array or anything NumPy makes an array of?"""
+    if isinstance(x, torch.Tensor):
+        return not (x.dtype.is_floating_point or x.dtype.is_complex)
+    return np.asarray(x).dtype.kind in "iub"
+
+
 MAX_EXCLUDE_INTERVALS = 8   # E of segvlad_search_excluding
 
 
@@ -951,6 +961,57 @@ class SegVLADEngine:
                                                  _ptr(out.get("fwd_idx")), _ptr(out.get("fwd_d2")), _ptr(out.get("mutual"))),
                     "match_pairs")
         self._keep = [q]
+        return out
+
+    def verify_pairs(self, q_xy, r_xy, qseg_offsets, fwd_idx, mutual, tol: float, min_scale: float = 0.5, max_scale: float = 2.0,
+                     want_rows: bool = False) -> dict:
+        """segvlad_verify_pairs: for every query image b and slot j, how many of the slot's correspondences -- the query rows
+        with ``mutual[q][j] != 0`` and their ``fwd_idx[q][j]``, match_pairs(want_rows=True)'s outputs -- agree on one 2-D
+        similarity transform of their centroids.  ``q_xy`` fp64 [nq][2] and ``r_xy`` fp64 [n_r][2]: the (x, y) centroid of every
+        query row and of every index row id; ``qseg_offsets`` [n_img + 1] (host); ``fwd_idx`` [nq][C] int64, ``mutual`` [nq][C]
+        uint8, C <= 64.  Every pair of correspondences is a hypothesis (exhaustive, deterministic); a correspondence is an inlier
+        when the similarity moves its query centroid to within ``tol`` of its reference centroid; hypotheses whose scale lies
+        outside ``min_scale .. max_scale`` are not eligible.  At most 256 rows per query image.  Malformed input raises
+        ValueError.  Returns device tensors: ``n_inlier`` int32 [n_img][C], ``pair`` int32 [n_img][C][2] (the winner's two query
+        rows, (-1, -1): none), ``model`` fp64 [n_img][C][4] ((a_re, a_im, t_x, t_y), NaN: none), ``order`` int32 [n_img][C] (the
+        slots by (n_inlier desc, slot asc)); with ``want_rows`` also ``inlier`` uint8 [nq][C]."""
+        qx = _as(q_xy, np.float64, torch.float64)
+        rx = _as(r_xy, np.float64, torch.float64)
+        qo = np.ascontiguousarray(qseg_offsets, dtype=np.int64).reshape(-1)
+        if qx.ndim != 2 or qx.shape[1] != 2:
+            raise ValueError(f"q_xy must be [nq][2], got shape {tuple(qx.shape)}")
+        if rx.ndim != 2 or rx.shape[1] != 2:
+            raise ValueError(f"r_xy must be [n_r][2], got shape {tuple(rx.shape)}")
+        nq, n_r = int(qx.shape[0]), int(rx.shape[0])
+        if len(qo) < 1 or qo[0] != 0 or qo[-1] != nq or (np.diff(qo) < 0).any():
+            raise ValueError(f"qseg_offsets must run from 0 to nq={nq} and never decrease")
+        if (np.diff(qo) > MAX_VERIFY_ROWS).any():
+            raise ValueError(f"a query image owns {int(np.diff(qo).max())} rows, more than {MAX_VERIFY_ROWS}")
+        for name, x in (("fwd_idx", fwd_idx), ("mutual", mutual)):
+            if not _is_integral(x):
+                raise ValueError(f"{name} must be integers")
+        fi = _as(fwd_idx, np.int64, torch.int64)
+        mu = _as(mutual, np.uint8, torch.uint8)
+        if fi.ndim != 2 or fi.shape[0] != nq or not 1 <= fi.shape[1] <= MAX_CANDIDATES:
+            raise ValueError(f"fwd_idx must be [nq={nq}][C] with 1 <= C <= {MAX_CANDIDATES}, got shape {tuple(fi.shape)}")
+        if tuple(mu.shape) != tuple(fi.shape):
+            raise ValueError(f"mutual must have fwd_idx's shape {tuple(fi.shape)}, got {tuple(mu.shape)}")
+        tol, min_scale, max_scale = float(tol), float(min_scale), float(max_scale)
+        if not (np.isfinite(tol) and tol > 0):
+            raise ValueError(f"tol={tol} must be finite and > 0")
+        if not (0 < min_scale <= max_scale < float("inf")):
+            raise ValueError(f"need 0 < min_scale <= max_scale < inf, got {min_scale}, {max_scale}")
+        qo = np.ascontiguousarray(qo, dtype=np.int32)
+        n_img, Cw = len(qo) - 1, int(fi.shape[1])
+        out = {"n_inlier": self._empty((n_img, Cw), torch.int32), "pair": self._empty((n_img, Cw, 2), torch.int32),
+               "model": self._empty((n_img, Cw, 4), torch.float64), "order": self._empty((n_img, Cw), torch.int32)}
+        if want_rows:
+            out["inlier"] = self._empty((nq, Cw), torch.uint8)
+        self._stream()
+        self._check(self.lib.segvlad_verify_pairs(self._h, _ptr(qx), nq, _ptr(rx), n_r, _ptr(qo), n_img, Cw, _ptr(fi), _ptr(mu), tol,
+                                                  min_scale, max_scale, _ptr(out["n_inlier"]), _ptr(out["pair"]), _ptr(out["model"]),
+                                                  _ptr(out["order"]), _ptr(out.get("inlier"))), "verify_pairs")
+        self._keep = [qx, rx, fi, mu]
         return out
 
     def exclude_stats(self) -> dict:

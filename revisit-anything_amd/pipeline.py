@@ -55,6 +55,8 @@ class SegVLADPipeline:
         # check_empty the device adjacency reports it (one 4-byte read-back per batch) and describe() raises ValueError
         self.check_empty = check_empty
         self.N = (H // patch) * (W // patch)
+        self._index_xy = None                # fp64 [rows][2] on the device: the index rows' centroids (index_add(..., xy=...))
+        self._index_rows_without_xy = False  # rows were added without them since the last index_reset
         self._eager_flags = 0   # > 0: read the adjacency flags BEFORE describing (set after a batch that needed a Qhull patch)
 
     # ---- a2..a9: images -> (normalised) segment descriptors ------------------------------------------
@@ -176,14 +178,36 @@ class SegVLADPipeline:
     # ---- a10: index ------------------------------------------------------------------------------------
     def index_reset(self):
         self.eng.db_reset()
+        self._index_xy = None
+        self._index_rows_without_xy = False
 
-    def index_add(self, desc: torch.Tensor, img_of_seg):
+    def index_add(self, desc: torch.Tensor, img_of_seg, xy=None):
+        """Adds rows to the index.  ``xy`` (optional, fp64 [rows][2]): the rows' segment centroids (x, y), kept in a device tensor
+        beside the index -- row id for row id -- for verify()."""
+        n = int(desc.shape[0])
+        if xy is not None:
+            xy = torch.as_tensor(xy, dtype=torch.float64, device=self.eng.device)
+            if tuple(xy.shape) != (n, 2):
+                raise ValueError(f"xy must be [rows={n}][2], got shape {tuple(xy.shape)}")
         self.eng.db_add(desc, img_of_seg)
+        if n == 0:
+            return
+        if xy is None or self._index_rows_without_xy:
+            self._index_rows_without_xy = True   # (until index_reset: the table would no longer be one row per row id)
+            self._index_xy = None
+            return
+        self._index_xy = xy.clone() if self._index_xy is None else torch.cat([self._index_xy, xy])
 
     def index_remove_images(self, img_ids) -> int:
         """Drops every segment row of the listed reference images (stale, mis-registered or withdrawn) from the index on the
-        device; later rows move down (engine.db_remove).  Returns the number of rows removed."""
-        return self.eng.db_remove(img_ids=img_ids)
+        device; later rows move down (engine.db_remove), and so do their centroids when index_add received them.  Returns the
+        number of rows removed."""
+        xy = self._index_xy
+        if xy is None:
+            return self.eng.db_remove(img_ids=img_ids)
+        removed, new_id = self.eng.db_remove(img_ids=img_ids, want_new_ids=True)
+        self._index_xy = xy[new_id >= 0].contiguous()   # (the survivors keep their order)
+        return removed
 
     # ---- a10..a12: descriptors -> ranked reference images ----------------------------------------------
     def retrieve(self, qdesc: torch.Tensor, qseg_offsets: np.ndarray, k_search: int = 200, k_vote: int = 50, n_top: int = 5,
@@ -242,6 +266,33 @@ class SegVLADPipeline:
         if not (isinstance(pred, torch.Tensor) and pred.device == order.device):
             pred = torch.as_tensor(np.ascontiguousarray(cand), device=order.device)
         return torch.gather(pred, 1, order), torch.gather(out["n_mutual"], 1, order), torch.gather(out["score"], 1, order)
+
+    # ---- behind the re-ranking: do the matched segments lie the same way in both images? ------------------------------------
+    def verify(self, qdesc: torch.Tensor, qseg_offsets: np.ndarray, pred, q_xy, tol: float, max_d2: float = float("inf"),
+               min_scale: float = 0.5, max_scale: float = 2.0):
+        """Spatial verification of every query image's candidate reference images -- ``pred`` [n_img][C] as for rerank() --:
+        the mutual nearest segments of each candidate (engine.match_pairs), then the largest set of them whose centroids one
+        2-D similarity transform maps onto each other within ``tol`` (engine.verify_pairs; ``q_xy`` fp64 [nq][2]: the query
+        rows' centroids, the index rows' are those given to index_add).  The candidates are ordered by (inliers desc, then
+        rerank()'s order: mutual pairs, summed similarity, the vote).  Returns ``(pred_verified, n_inlier, n_mutual)``, each
+        [n_img][C] in the NEW order.  ValueError when rows were added to the index without ``xy``."""
+        if self._index_rows_without_xy:
+            raise ValueError("verify: rows were added to the index without their centroids (index_add(..., xy=...))")
+        r_xy = self._index_xy
+        if r_xy is None:
+            r_xy = torch.zeros((0, 2), dtype=torch.float64, device=self.eng.device)
+        cand = pred.cpu().numpy() if isinstance(pred, torch.Tensor) else np.asarray(pred)
+        mp = self.eng.match_pairs(qdesc, qseg_offsets, cand, max_d2=max_d2, want_rows=True)
+        o1 = mp["order"].to(torch.int64)                       # [n_img][C]: rerank()'s order of the slots
+        per_img = torch.as_tensor(np.diff(np.asarray(qseg_offsets, dtype=np.int64)), device=o1.device)
+        row_o1 = torch.repeat_interleave(o1, per_img, dim=0, output_size=int(mp["mutual"].shape[0]))  # [nq][C]: every query row's slot columns in that order
+        vp = self.eng.verify_pairs(q_xy, r_xy, qseg_offsets, torch.gather(mp["fwd_idx"], 1, row_o1).contiguous(),
+                                   torch.gather(mp["mutual"], 1, row_o1).contiguous(), tol, min_scale=min_scale, max_scale=max_scale)
+        order = torch.gather(o1, 1, vp["order"].to(torch.int64))   # slots of `pred`, best verified first
+        if not (isinstance(pred, torch.Tensor) and pred.device == order.device):
+            pred = torch.as_tensor(np.ascontiguousarray(cand), device=order.device)
+        self.last_verify = {"match": mp, "verify": vp, "order": order}
+        return torch.gather(pred, 1, order), torch.gather(vp["n_inlier"], 1, vp["order"].to(torch.int64)), torch.gather(mp["n_mutual"], 1, order)
 
 
 def recall_at(preds: np.ndarray, gt: List[Sequence[int]], n: int) -> List[float]:

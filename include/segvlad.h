@@ -422,6 +422,48 @@ int segvlad_verify_pairs(segvlad_ctx* ctx, const double* q_xy, int nq, const dou
                          double max_scale, int32_t* n_inlier_out, int32_t* pair_out, double* model_out, int32_t* order_out,
                          uint8_t* inlier_out);
 
+/* ---- re-ranking by consistency along the query sequence: a candidate of query frame t is believed when the frames around t hold
+ *      candidates that lie on one line through the map (no reference counterpart: the reference judges every query image alone,
+ *      func_vpr.py:207-224).  SeqSLAM's trajectory search, restricted to the candidate lists: the last stage behind segvlad_vote,
+ *      segvlad_match_pairs and segvlad_verify_pairs, all of which look at one query image.  It never reads the d-wide rows and
+ *      does not touch the index or the vocabulary.
+ *      Image ids MUST be frame numbers along the map -- consecutive ids are consecutive places, the assumption of
+ *      engine.window_intervals and segvlad_search_excluding --, and the query frames of a sequence are in time order.
+ *      The lists' truncation to C candidates is the approximation: a frame's vote is zero outside the images it voted for, so a
+ *      frame supports a line only through the C images it lists (the dense frame x map score matrix is not built).
+ *      cand [T][C] int32, device or host: the candidate reference image ids of query frame t -- segvlad_vote's pred_out as it
+ *      is --, 1 <= C <= 64.  score [T][C] fp64, device or host: one evidence value per slot, meant to be >= 0 -- the vote's
+ *      score_out, or n_mutual / n_inlier as doubles.  A slot is EMPTY when cand < 0 or its score is not finite; every other slot
+ *      is evaluated on its own (a duplicate id in a frame gets the same answer twice).
+ *      seq_offsets [n_seq+1] int32 HOST, ascending, seq_offsets[0] == 0, seq_offsets[n_seq] == T: sequence s owns the frames
+ *      seq_offsets[s] .. seq_offsets[s+1]-1 in time order (empty sequences allowed); a window never crosses a sequence boundary.
+ *      0 <= back, fwd <= 32: the frames before and after t that are asked.  vel [n_vel] fp64 HOST: map frames per query frame,
+ *      1 <= n_vel <= 16, every value finite with |v| <= 2^20; a negative value describes a reverse traversal.  0 <= tol <= 2^30:
+ *      how far, in map frames, a neighbour's candidate may lie from the line.
+ *      Arithmetic: fp64 and int64, every operation separately rounded and in exactly this order, so a host loop reproduces every
+ *      bit.  For a non-empty slot (t, c) with r = cand[t][c] and velocity index u:
+ *        acc = 0.0, hits = 0; for tau = -back .. fwd, ascending:
+ *          tau == 0:  acc = acc + score[t][c]
+ *          tau != 0 and frame t' = t + tau lies in t's sequence:
+ *            p = (int64)r + (int64)rint(vel[u] * (double)tau)       -- one multiplication, rounded half to even
+ *            sup = the LARGEST score among the non-empty slots j of frame t' with |(int64)cand[t'][j] - p| <= tol
+ *            if there is such a slot: acc = acc + sup, hits += 1; otherwise nothing is added
+ *      Winner: the u with the largest acc, ties to the lowest u.  Outputs, device or host; all but seq_score_out may be NULL:
+ *        seq_score_out [T][C] fp64   the winner's acc; 0.0 for an empty slot
+ *        n_hit_out     [T][C] int32  the winner's hits; 0 for an empty slot
+ *        vel_out       [T][C] int32  the winner's u; -1 for an empty slot
+ *        order_out     [T][C] int32  the frame's slots sorted by (seq_score descending, slot ascending), empty slots last in
+ *                                    slot order: cand[t][order[t][j]] is the re-ranked list.  (A NaN sum -- infinite sums of
+ *                                    both signs, which scores >= 0 never produce -- sorts behind every number.)
+ *      SEGVLAD_ERR_ARG on null required pointers, negative sizes, C outside 1 .. 64, back or fwd outside 0 .. 32, n_vel outside
+ *      1 .. 16, tol outside 0 .. 2^30, a velocity that is not finite or beyond 2^20 in magnitude, bad offsets or
+ *      T != seq_offsets[n_seq], seq_offsets or vel in device memory.  T == 0: OK.  Deterministic: two calls return the same
+ *      bits.  The call does not synchronise when every output is device memory (host outputs are copied back behind one
+ *      synchronisation).  Stage timer "sequence_rerank".                                                                    */
+int segvlad_sequence_rerank(segvlad_ctx* ctx, const int32_t* cand, const double* score, int T, int C, const int32_t* seq_offsets,
+                            int n_seq, int back, int fwd, const double* vel, int n_vel, int tol, double* seq_score_out,
+                            int32_t* n_hit_out, int32_t* vel_out, int32_t* order_out);
+
 /* ---- merge of per-shard top-k lists (no reference counterpart: the reference is single-process).
  *      d2_parts/idx_parts [nq][parts*k] (shard-major within a row, global ids); output top-k by
  *      (distance, lower id).  An entry with id < 0 is an empty slot whatever its distance: it comes
@@ -461,7 +503,7 @@ int segvlad_vote(segvlad_ctx* ctx, const int64_t* idx, const float* sims, const 
                  int32_t* pred_out, double* score_out);
 
 /* ---- instrumentation: with profiling on, every kernel group of a stage ("incidence", "adjacency",
- *      "assign", "prep", "aggregate", "pca", "describe" (segvlad_describe as a whole: its parts overlap), "knn_level0", "knn_gemm", "knn_select", "knn_fallback", "knn_shortlist" (segvlad_search_shortlist), "knn_exclude" (the kernels segvlad_search_excluding adds to its inner search), "knn_group" (the kernels segvlad_search_grouped adds to its inner search), "knn_range" (the kernels of segvlad_range_search), "match_pairs" (segvlad_match_pairs), "verify_pairs" (segvlad_verify_pairs), "db_remove" (segvlad_db_remove), "vote") is bracketed by a HIP event pair
+ *      "assign", "prep", "aggregate", "pca", "describe" (segvlad_describe as a whole: its parts overlap), "knn_level0", "knn_gemm", "knn_select", "knn_fallback", "knn_shortlist" (segvlad_search_shortlist), "knn_exclude" (the kernels segvlad_search_excluding adds to its inner search), "knn_group" (the kernels segvlad_search_grouped adds to its inner search), "knn_range" (the kernels of segvlad_range_search), "match_pairs" (segvlad_match_pairs), "verify_pairs" (segvlad_verify_pairs), "sequence_rerank" (segvlad_sequence_rerank), "db_remove" (segvlad_db_remove), "vote") is bracketed by a HIP event pair
  *      on the context stream.  segvlad_stage_ms returns the SUM of the elapsed times (ms) and the number
  *      of kernel launches recorded for the stage since the last segvlad_profile_reset; it returns
  *      SEGVLAD_ERR_STATE if the stage has not run.  Replaces the (discarded) time.time() pair of

@@ -63,6 +63,8 @@ SIGNATURES = {
     "segvlad_verify_pairs": (C.c_int, [c_ctx_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
                                         C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_void_p]),
+    "segvlad_sequence_rerank": (C.c_int, [c_ctx_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                           C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "segvlad_exclude_stats": (C.c_int, [c_ctx_p, C.POINTER(C.c_int64), C.c_int]),
     "segvlad_search_grouped": (C.c_int, [c_ctx_p, _f32p, C.c_int, C.c_int, C.c_int, _f32p, C.c_void_p]),
     "segvlad_group_stats": (C.c_int, [c_ctx_p, C.POINTER(C.c_int64), C.c_int]),

@@ -2,7 +2,7 @@
 // checks, host/device pointer staging, scratch sizing and kernel sequencing on the context stream.
 // This unit: context, options, staging, guard mode, stage timers, vocabulary, PCA model, pca_apply, normalise, merge_topk / sims /
 // minmax, vote.  describe.hip: the describe stage (plan_describe and its staged passes); search.hip: the index and the exact search;
-// the searches derived from it (shortlist, match_pairs, excluding, grouped) and verify_pairs have their entry points next to their kernels.
+// the searches derived from it (shortlist, match_pairs, excluding, grouped), verify_pairs and sequence_rerank have their entry points next to their kernels.
 #include <stdarg.h>
 #include <stdlib.h>
 #include <string.h>

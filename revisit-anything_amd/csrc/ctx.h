@@ -358,6 +358,7 @@ struct segvlad_ctx {
   //  cursors / words before and after their ordering, the dense query block of the exact sweeps, the device lims of a host caller
   //  and a few counters; s_mp_min: segvlad_match_pairs (match_kernels.hip) -- the row minima [nq][C], then the live slots' column
   //  minima, 64-bit keys; s_vp_best: segvlad_verify_pairs (verify_kernels.hip) -- every slot's best (inlier count, hypothesis) key;
+  //  s_sq_id / s_sq_sc: segvlad_sequence_rerank (sequence_kernels.hip) -- every frame's candidate ids and scores in id order;
   //  s_gr_*: segvlad_search_grouped (group_kernels.hip) -- the counters + row flags, and the exact tail's open
   //  rows, their dense query block, a batch's slots / word offsets, cursors, words before and after their ordering, per-image counts
 #define SV_SCRATCH_BUFS(X)                                                                                                       \
@@ -372,7 +373,7 @@ struct segvlad_ctx {
   X(s_rm_row) X(s_rm_img) X(s_rm_blk) X(s_rm_src) X(s_rm_misc)                                                                    \
   X(s_rs_thr) X(s_rs_flag) X(s_rs_fb) X(s_rs_cnt) X(s_rs_soff) X(s_rs_stage) X(s_rs_loff) X(s_rs_cur) X(s_rs_words) X(s_rs_sorted)  \
   X(s_rs_tmp) X(s_rs_rows) X(s_rs_q) X(s_rs_misc)                                                                                 \
-  X(s_mp_min) X(s_vp_best)                                                                                                         \
+  X(s_mp_min) X(s_vp_best) X(s_sq_id) X(s_sq_sc)                                                                                   \
   X(s_gr_flag) X(s_gr_rows) X(s_gr_q) X(s_gr_plan) X(s_gr_cur) X(s_gr_words) X(s_gr_sorted) X(s_gr_tab)
 #define SV_DECL_BUF(n) DevBuf n;
   SV_PERSISTENT_BUFS(SV_DECL_BUF)

@@ -109,6 +109,49 @@ def check_candidates(cand: np.ndarray, n_img: int) -> None:
             raise ValueError(f"candidate id {hi} out of the int32 range")
 
 
+MAX_SEQ_WINDOW = 32       # back / fwd of segvlad_sequence_rerank
+MAX_SEQ_VELOCITIES = 16   # its n_vel
+MAX_SEQ_VELOCITY = float(2 ** 20)
+MAX_SEQ_TOL = 2 ** 30
+
+
+def velocity_grid(vmin: float = 0.8, vmax: float = 1.2, n: int = 5) -> np.ndarray:
+    """``n`` evenly spaced velocities (map frames per query frame) from ``vmin`` to ``vmax``, both included, as the fp64 array
+    of segvlad_sequence_rerank; n == 1 gives ``[vmin]``.  Negative values describe a reverse traversal."""
+    n = int(n)
+    if not 1 <= n <= MAX_SEQ_VELOCITIES:
+        raise ValueError(f"n={n} velocities outside 1 .. {MAX_SEQ_VELOCITIES}")
+    vmin, vmax = float(vmin), float(vmax)
+    if not (np.isfinite(vmin) and np.isfinite(vmax)) or max(abs(vmin), abs(vmax)) > MAX_SEQ_VELOCITY or vmin > vmax:
+        raise ValueError(f"need finite vmin <= vmax within +-2^20, got {vmin}, {vmax}")
+    return np.linspace(vmin, vmax, n, dtype=np.float64)
+
+
+def check_sequence_args(T: int, C: int, seq_offsets=None, back: int = 5, fwd: int = 5, velocities=None, tol: int = 1):
+    """Host-side validation of segvlad_sequence_rerank's arguments beside the lists [T][C]: raises ValueError for what the C
+    call would reject.  Returns ``(seq_offsets, velocities)`` as the int32 / fp64 host arrays the call takes
+    (``seq_offsets=None``: one sequence; ``velocities=None``: velocity_grid())."""
+    T, C = int(T), int(C)
+    if T < 0 or not 1 <= C <= MAX_CANDIDATES:
+        raise ValueError(f"need T >= 0 and 1 <= C <= {MAX_CANDIDATES}, got T={T}, C={C}")
+    so = np.array([0, T], dtype=np.int64) if seq_offsets is None else np.asarray(seq_offsets)
+    if so.dtype.kind not in "iu" or so.ndim != 1:
+        raise ValueError("seq_offsets must be a 1-D array of integers")
+    if len(so) < 1 or so[0] != 0 or so[-1] != T or (np.diff(so.astype(np.int64)) < 0).any():
+        raise ValueError(f"seq_offsets must run from 0 to T={T} and never decrease")
+    for name, w in (("back", back), ("fwd", fwd)):
+        if int(w) != w or not 0 <= int(w) <= MAX_SEQ_WINDOW:
+            raise ValueError(f"{name}={w} outside 0 .. {MAX_SEQ_WINDOW}")
+    if int(tol) != tol or not 0 <= int(tol) <= MAX_SEQ_TOL:
+        raise ValueError(f"tol={tol} outside 0 .. 2^30 (map frames, an integer)")
+    vel = velocity_grid() if velocities is None else np.ascontiguousarray(velocities, dtype=np.float64)
+    if vel.ndim != 1 or not 1 <= len(vel) <= MAX_SEQ_VELOCITIES:
+        raise ValueError(f"velocities must be a 1-D array of 1 .. {MAX_SEQ_VELOCITIES} values, got shape {tuple(vel.shape)}")
+    if not np.isfinite(vel).all() or np.abs(vel).max() > MAX_SEQ_VELOCITY:
+        raise ValueError("every velocity must be finite and within +-2^20")
+    return np.ascontiguousarray(so, dtype=np.int32), vel
+
+
 MAX_VERIFY_ROWS = 256   # rows per query image of segvlad_verify_pairs
 
 
@@ -1012,6 +1055,36 @@ class SegVLADEngine:
                                                   min_scale, max_scale, _ptr(out["n_inlier"]), _ptr(out["pair"]), _ptr(out["model"]),
                                                   _ptr(out["order"]), _ptr(out.get("inlier"))), "verify_pairs")
         self._keep = [qx, rx, fi, mu]
+        return out
+
+    def sequence_rerank(self, cand, score, seq_offsets=None, back: int = 5, fwd: int = 5, velocities=None, tol: int = 1,
+                        want_all: bool = True) -> dict:
+        """segvlad_sequence_rerank: every candidate of every query frame scored by the support it finds in the frames around it.
+        ``cand`` int32 [T][C] (vote()'s ``pred`` as it is; -1: empty) and ``score`` fp64 [T][C] (its scores, or ``n_mutual`` /
+        ``n_inlier``; converted to fp64), device or host, C <= 64; the frames are in time order and the image ids are frame
+        numbers along the map.  ``seq_offsets`` [n_seq + 1] (host; None: one sequence) splits the frames into sequences no
+        window crosses; a candidate r of frame t collects, for each of the ``velocities`` (map frames per query frame; None:
+        velocity_grid()), the best score within ``tol`` map frames of r + rint(v tau) in every frame t + tau, -back <= tau <=
+        fwd, and keeps the best velocity.  Malformed arguments raise ValueError.  Returns device tensors: ``seq_score`` fp64
+        [T][C] and ``order`` int32 [T][C] (the slots by (seq_score desc, slot asc), empty slots last); with ``want_all`` also
+        ``n_hit`` int32 [T][C] (the frames that supported the winner) and ``vel`` int32 [T][C] (its index; -1: empty slot)."""
+        if not _is_integral(cand):
+            raise ValueError("cand must be integers")
+        c = _as(cand, np.int32, torch.int32)
+        s = _as(score, np.float64, torch.float64)
+        if c.ndim != 2 or tuple(s.shape) != tuple(c.shape):
+            raise ValueError(f"cand and score must both be [T][C], got shapes {tuple(c.shape)} and {tuple(s.shape)}")
+        T, Cw = int(c.shape[0]), int(c.shape[1])
+        so, vel = check_sequence_args(T, Cw, seq_offsets, back, fwd, velocities, tol)
+        out = {"seq_score": self._empty((T, Cw), torch.float64), "order": self._empty((T, Cw), torch.int32)}
+        if want_all:
+            out["n_hit"] = self._empty((T, Cw), torch.int32)
+            out["vel"] = self._empty((T, Cw), torch.int32)
+        self._stream()
+        self._check(self.lib.segvlad_sequence_rerank(self._h, _ptr(c), _ptr(s), T, Cw, _ptr(so), len(so) - 1, int(back), int(fwd),
+                                                     _ptr(vel), len(vel), int(tol), _ptr(out["seq_score"]), _ptr(out.get("n_hit")),
+                                                     _ptr(out.get("vel")), _ptr(out["order"])), "sequence_rerank")
+        self._keep = [c, s]
         return out
 
     def exclude_stats(self) -> dict:

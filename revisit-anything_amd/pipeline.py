@@ -294,6 +294,23 @@ class SegVLADPipeline:
         self.last_verify = {"match": mp, "verify": vp, "order": order}
         return torch.gather(pred, 1, order), torch.gather(vp["n_inlier"], 1, vp["order"].to(torch.int64)), torch.gather(mp["n_mutual"], 1, order)
 
+    # ---- behind any of them: candidates believed when the frames around them agree on one line through the map ---------------
+    def sequence(self, pred, score, seq_offsets=None, back: int = 5, fwd: int = 5, velocities=None, tol: int = 1):
+        """Temporal re-ranking of a traversal's candidates (engine.sequence_rerank): ``pred`` [T][C] holds the candidate
+        reference images of T query frames in time order, image ids being frame numbers along the map, and ``score`` [T][C]
+        one evidence value >= 0 per slot, in ``pred``'s slot order.  Accepted scores: retrieve()'s ``sc``
+        (``want_scores=True``; with ``pred`` as returned), rerank()'s ``n_mutual`` or ``score`` and verify()'s ``n_inlier``
+        or ``n_mutual`` (with the re-ranked / verified predictions those calls return, which are in the same order); integer
+        counts are converted to fp64.  A slot with ``pred < 0`` or a non-finite score is empty.  ``seq_offsets`` [n_seq + 1]
+        splits the frames into sequences (None: one).  Returns ``(pred_seq, seq_score, n_hit)``, each [T][C] in the NEW
+        order: ``pred_seq[t] = pred[t][order[t]]``, best supported first, empty slots last."""
+        out = self.eng.sequence_rerank(pred, score, seq_offsets=seq_offsets, back=back, fwd=fwd, velocities=velocities, tol=tol)
+        order = out["order"].to(torch.int64)
+        if not (isinstance(pred, torch.Tensor) and pred.device == order.device):
+            pred = torch.as_tensor(np.ascontiguousarray(pred.cpu().numpy() if isinstance(pred, torch.Tensor) else pred), device=order.device)
+        self.last_sequence = out
+        return torch.gather(pred, 1, order), torch.gather(out["seq_score"], 1, order), torch.gather(out["n_hit"], 1, order)
+
 
 def recall_at(preds: np.ndarray, gt: List[Sequence[int]], n: int) -> List[float]:
     """calc_recall (func_vpr.py:396-422) without the print: first correct rank, queries with empty GT skipped."""

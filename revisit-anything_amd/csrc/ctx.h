@@ -452,6 +452,7 @@ int sv_launch_vocab_prepare(segvlad_ctx* ctx);
 int sv_launch_incidence(segvlad_ctx* ctx, const uint8_t* masks, int S, int Hm, int Wm, int H, int W, int patch,
                         uint64_t* inc_bits, double* centroids /* may be null */);
 int sv_launch_centroids(segvlad_ctx* ctx, const uint8_t* masks, int S, int Hm, int Wm, double* out);
+bool sv_adjacency_fits(int S_max);   // an image of S_max segments fits the in-LDS Delaunay (else: SEGVLAD_ERR_LIMIT)
 int sv_launch_adjacency(segvlad_ctx* ctx, const double* cent, const int32_t* seg_off_dev, const int64_t* adj_off_dev,
                         int B, int S_max, int order, uint8_t* adj, uint32_t* n_bad, uint8_t* img_flags = nullptr);
 int sv_launch_assign(segvlad_ctx* ctx, const float* tokens, int B, int N, float* xt, uint8_t* labels, float* rnorm,

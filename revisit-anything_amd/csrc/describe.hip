@@ -383,6 +383,11 @@ static int describe_begin(segvlad_ctx* ctx, const MaskBranch& m, const float* to
   // ones (incidence_centroids -> adjacency -> images[_pca]) can", which a caller can tell from misuse: an empty batch, and a
   // PCA model without the fp16x3 form (option pca_arith=fp32, or K*D not a multiple of 32: images_pca takes its PlainProjection form)
   if (B == 0 || S_tot <= 0) return ctx->fail(SEGVLAD_ERR_LIMIT, "describe: no images / no segments (use the separate entry points)");
+  // ... and an image that sv_launch_adjacency would refuse: the same bound, asked before the mask branch is forked
+  const SegWalk w = walk_seg_offsets(m.seg_offsets, B);
+  if (w.monotone && !sv_adjacency_fits(w.S_max))
+    return ctx->fail(SEGVLAD_ERR_LIMIT, "describe: %d segments in one image exceed the in-LDS Delaunay (use the separate entry points)",
+                     w.S_max);
   if (pca && ctx->P == 0) return ctx->fail(SEGVLAD_ERR_STATE, "describe: call segvlad_pca_set first");
   if (pca && (ctx->pca_w_scale <= 0.f || ctx->opt.pca_fp32))
     return ctx->fail(SEGVLAD_ERR_LIMIT,

@@ -318,6 +318,7 @@ __global__ __launch_bounds__(1024) void adjacency_kernel(const double* __restric
   uint64_t* A1 = reinterpret_cast<uint64_t*>(py + S_max);        // [S_max][SW]
   uint64_t* P = A1 + (size_t)S_max * SW;                         // [S_max][SW]
   uint64_t* Q = P + (size_t)S_max * SW;                          // [S_max][SW]
+  int& degenerate = *reinterpret_cast<int*>(Q + (size_t)S_max * SW);   // the last SV_ADJ_LDS_TAIL bytes (sv_adjacency_lds)
   const int tid = threadIdx.x;
   if (S == 0) return;
   uint8_t* out = adj + adj_off[b];
@@ -330,7 +331,6 @@ __global__ __launch_bounds__(1024) void adjacency_kernel(const double* __restric
     }
   }
   for (int j = tid; j < S * SW; j += (int)blockDim.x) A1[j] = 0;
-  __shared__ int degenerate;
   if (tid == 0) degenerate = 0;
   __syncthreads();
   if (S <= 3) {
@@ -416,12 +416,21 @@ __global__ __launch_bounds__(1024) void adjacency_kernel(const double* __restric
   }
 }
 
+// Every byte of LDS the kernel uses for an image of S_max segments: the coordinates, the three bit matrices and the flag word.  The
+// kernel declares no __shared__ variable, so this is the whole workgroup's allocation and the one figure compared with the 160 KiB
+// of a CU (a static variable beside the dynamic block would be allocated on top of it, unseen by that comparison).
+constexpr size_t SV_ADJ_LDS_TAIL = 16;   // `degenerate`, padded to the block's alignment
+static size_t sv_adjacency_lds(int S_max) {
+  const size_t SW = ((size_t)S_max + 63) / 64;
+  return (size_t)S_max * 16 + (size_t)3 * S_max * SW * 8 + SV_ADJ_LDS_TAIL;
+}
+bool sv_adjacency_fits(int S_max) { return sv_adjacency_lds(S_max) <= 160 * 1024; }
+
 int sv_launch_adjacency(segvlad_ctx* ctx, const double* cent, const int32_t* seg_off_dev, const int64_t* adj_off_dev,
                         int B, int S_max, int order, uint8_t* adj, uint32_t* n_bad, uint8_t* img_flags) {
   if (B <= 0 || S_max <= 0) return SEGVLAD_OK;
-  const int SW = (S_max + 63) / 64;
-  const size_t lds = (size_t)S_max * 16 + (size_t)3 * S_max * SW * 8;
-  if (lds > 160 * 1024)
+  const size_t lds = sv_adjacency_lds(S_max);
+  if (!sv_adjacency_fits(S_max))
     return ctx->fail(SEGVLAD_ERR_LIMIT, "adjacency: %d segments in one image exceed the LDS budget (%zu B)", S_max, lds);
   if (lds > 64 * 1024)
     SV_HIP(sv_max_dyn_lds(reinterpret_cast<const void*>(adjacency_kernel), (size_t)lds));

@@ -126,7 +126,7 @@ class SegVLADPipeline:
                     # degenerate-configuration report are recoverable; anything else is not
                     if not isinstance(e, SegVLADDegenerateError) and e.code != SEGVLAD_ERR_LIMIT:
                         raise
-                    # an image with more segments (~620) than the in-LDS Delaunay holds (or a report from an engine
+                    # an image with more segments (> 639) than the in-LDS Delaunay holds (or a report from an engine
                     # without per-image flags): the reference's own Qhull path for this batch
                     adj = adjacency_batch(cent.cpu().numpy(), seg_offsets, self.order, self.adj_workers)
         else:

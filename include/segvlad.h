@@ -2,7 +2,7 @@
  * segvlad.h -- C-ABI of the MI355X-native SegVLAD hot path (libsegvlad_hip.so, gfx950).
  *
  * The reference (AnyLoc/Revisit-Anything, all Python) exposes no FFI; the boundary it offers is
- * the function surface of func_vpr.py / place_rec_main.py.  Each entry point below replaces the
+ * the function surface of func_vpr.py / place_rec_main.py.  Each of the 56 entry points below replaces the
  * cited reference function(s); the Python module revisit_anything_amd.func_vpr maps the reference's
  * names/arguments onto these calls (INTEGRATION.md shows the ctypes stub a maintainer would add).
  *
@@ -73,6 +73,31 @@ int segvlad_incidence_centroids(segvlad_ctx* ctx, const uint8_t* masks, int S, i
 /* ---- mask centroids: np.nonzero(mask).mean(1)[::-1]                  func_vpr.py:1314
  *      centroids [S][2] fp64 (x, y); an empty mask yields NaN (the reference raises ValueError).  */
 int segvlad_mask_centroids(segvlad_ctx* ctx, const uint8_t* masks, int S, int Hm, int Wm, double* centroids);
+
+/* ---- run-length masks: SAM's uncompressed RLE, mask_to_rle_pytorch / rle_to_mask        sam/segment_anything/utils/amg.py:107-149
+ *      A batch of S masks of one size Hm x Wm:  counts [n_runs] uint32, the runs of all masks one after the other;
+ *      run_offsets [S+1] int64, mask s owns counts[run_offsets[s] .. run_offsets[s+1]).  A mask is column-major (pixel
+ *      p = col * Hm + row) and its runs alternate zeros / ones, starting with zeros: the first count may be 0, and zero-length
+ *      runs are tolerated anywhere.  Both arrays device or host (host run_offsets are checked: non-negative, non-decreasing;
+ *      host counts under device run_offsets cost one synchronising read of run_offsets[S]).
+ *      segvlad_incidence_rle writes exactly what segvlad_incidence_centroids writes for the decoded masks, byte for byte:
+ *      inc_bits [S][ceil(N/64)] with zero pad bits and centroids [S][2] fp64 (x, y), NaN for an empty mask; centroids may be
+ *      NULL.  No Wm % 16 or alignment condition.  The mask lives as a bitmap in LDS: Wm * ceil(Hm/32) * 4 bytes above
+ *      150 KiB return SEGVLAD_ERR_LIMIT -- inflate such a batch with segvlad_rle_decode and call segvlad_incidence_centroids.
+ *      A mask whose runs do not sum to exactly Hm * Wm (a mask without runs included) is MALFORMED: it is clipped at Hm * Wm,
+ *      the pixels its runs do not reach are zero, and it adds 1 to *n_bad_out (DEVICE memory or NULL; the caller zeroes it: the
+ *      call never reads it back, so it does not synchronise when the outputs are device memory).  The other masks of the batch
+ *      are unaffected, and no count ever becomes a global address.  S == 0: OK, nothing is written.  SEGVLAD_ERR_STATE while a
+ *      segvlad_describe_begin is open; SEGVLAD_ERR_ARG on bad geometry, null pointers or a host n_bad_out.                     */
+int segvlad_incidence_rle(segvlad_ctx* ctx, const uint32_t* counts, const int64_t* run_offsets, int S, int Hm, int Wm, int H, int W,
+                          int patch, uint64_t* inc_bits, double* centroids, uint32_t* n_bad_out);
+
+/*      rle_to_mask for the batch (amg.py:107-149 again: the inverse of mask_to_rle_pytorch): masks_out [S][Hm][Wm] bytes 0 / 1,
+ *      row-major, device or host.  Malformed masks and n_bad_out as above.  Any size: masks whose bitmap exceeds the LDS are
+ *      decoded in windows of columns (up to 65535 windows per mask) -- the way in for callers of the one-call segvlad_describe
+ *      and for masks above segvlad_incidence_rle's bound.                                                                  */
+int segvlad_rle_decode(segvlad_ctx* ctx, const uint32_t* counts, const int64_t* run_offsets, int S, int Hm, int Wm, uint8_t* masks_out,
+                       uint32_t* n_bad_out);
 
 /* ---- neighbourhood adjacency for a batch: getNbrsDelaunay + nbrMasksAGGFastSingle
  *      func_vpr.py:1241-1245, 1315-1345.  centroids [S_tot][2] fp64 (x, y) from segvlad_mask_centroids,

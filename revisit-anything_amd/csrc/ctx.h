@@ -434,6 +434,13 @@ void sv_begin(segvlad_ctx* ctx);
 #define CHECK_CTX()                 \
   if (!ctx) return SEGVLAD_ERR_ARG; \
   sv_begin(ctx)
+// Between segvlad_describe_begin and segvlad_describe_end the context's per-batch scratch (segment / adjacency offsets, the
+// token-major copy, the labels) belongs to THAT batch, and the mask branch is in flight on the side stream: every other entry
+// point that would write them refuses instead of describing a different batch with the open one's offsets.
+// (describe.hip's mask entries and rle_kernels.hip's)
+#define CHECK_NO_OPEN_DESCRIBE(what)                                                                                        \
+  if (ctx->desc.open)                                                                                                       \
+  return ctx->fail(SEGVLAD_ERR_STATE, what ": a segvlad_describe_begin is open on this context (call segvlad_describe_end first)")
 
 // a fresh (start, stop) event pair of stage `name`, its start recorded on the context's stream; null when profiling is off or muted
 StageTimer* sv_stage_open(segvlad_ctx* ctx, const char* name, int* slot);

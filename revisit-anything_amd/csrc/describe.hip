@@ -5,12 +5,7 @@
 #include <cmath>
 #include "ctx.h"
 
-// Between segvlad_describe_begin and segvlad_describe_end the context's per-batch scratch (segment / adjacency offsets, the
-// token-major copy, the labels) belongs to THAT batch, and the mask branch is in flight on the side stream: every other entry
-// point that would write them refuses instead of describing a different batch with the open one's offsets.
-#define CHECK_NO_OPEN_DESCRIBE(what)                                                                                        \
-  if (ctx->desc.open)                                                                                                       \
-  return ctx->fail(SEGVLAD_ERR_STATE, what ": a segvlad_describe_begin is open on this context (call segvlad_describe_end first)")
+// (CHECK_NO_OPEN_DESCRIBE: ctx.h)
 
 // One walk over a batch's segment offsets for every caller: the largest image, the offsets of the adjacency blocks (adj_off[b] = sum of
 // S_b'^2 over the images before b), and whether every size is >= 0 -- which each caller reports in its own words.

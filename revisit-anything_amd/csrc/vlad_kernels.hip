@@ -14,6 +14,7 @@
 #include <stdlib.h>
 
 #include "ctx.h"
+#include "incidence_dev.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
@@ -90,19 +91,18 @@ __global__ __launch_bounds__(256) void incidence_kernel(const uint8_t* __restric
   const int t = word * 64 + lane;
   bool any = false;
   if (t < N) {
-    const int ty = t / dw, tx = t - ty * dw;
-    const int i0 = ty * patch, i1 = (ty == dh - 1) ? H - 1 : i0 + patch - 1;
-    const int j0 = tx * patch, j1 = (tx == dw - 1) ? W - 1 : j0 + patch - 1;
+    const SvTokenCell tc = sv_token_cell(t, dh, dw, patch, H, W);
+    const int i0 = tc.i0, i1 = tc.i1, j0 = tc.j0, j1 = tc.j1;
     const uint8_t* m = masks + (size_t)s * Hm * Wm;
     int pr = -1;
     for (int i = i0; i <= i1 && !any; ++i) {
-      int r = min((int)floorf((float)i * sh), Hm - 1);
+      int r = sv_src_index(i, sh, Hm);
       if (r == pr) continue;
       pr = r;
       const uint8_t* row = m + (size_t)r * Wm;
       int pc = -1;
       for (int j = j0; j <= j1; ++j) {
-        int c = min((int)floorf((float)j * sw), Wm - 1);
+        int c = sv_src_index(j, sw, Wm);
         if (c == pc) continue;
         pc = c;
         if (row[c]) { any = true; break; }
@@ -179,12 +179,11 @@ __global__ __launch_bounds__(256) void incidence_fused_kernel(const uint8_t* __r
     const int t = t0 + tid;
     bool any = false;
     if (t < N) {
-      const int ty = t / dw, tx = t - ty * dw;
-      const int i0 = ty * patch, i1 = (ty == dh - 1) ? H - 1 : i0 + patch - 1;
-      const int j0 = tx * patch, j1 = (tx == dw - 1) ? W - 1 : j0 + patch - 1;
+      const SvTokenCell tc = sv_token_cell(t, dh, dw, patch, H, W);
+      const int i0 = tc.i0, i1 = tc.i1, j0 = tc.j0, j1 = tc.j1;
       if (ranges) {
-        const int rlo = min((int)floorf((float)i0 * sh), Hm - 1), rhi = min((int)floorf((float)i1 * sh), Hm - 1);
-        const int clo = min((int)floorf((float)j0 * sw), Wm - 1), chi = min((int)floorf((float)j1 * sw), Wm - 1);
+        const int rlo = sv_src_index(i0, sh, Hm), rhi = sv_src_index(i1, sh, Hm);
+        const int clo = sv_src_index(j0, sw, Wm), chi = sv_src_index(j1, sw, Wm);
         const int w0 = clo >> 5, w1 = chi >> 5;
         for (int r = rlo; r <= rhi && !any; ++r) {
           for (int wv = w0; wv <= w1; ++wv) {
@@ -196,12 +195,12 @@ __global__ __launch_bounds__(256) void incidence_fused_kernel(const uint8_t* __r
       } else {
         int pr = -1;
         for (int i = i0; i <= i1 && !any; ++i) {
-          const int r = min((int)floorf((float)i * sh), Hm - 1);
+          const int r = sv_src_index(i, sh, Hm);
           if (r == pr) continue;
           pr = r;
           int pc = -1;
           for (int j = j0; j <= j1; ++j) {
-            const int c = min((int)floorf((float)j * sw), Wm - 1);
+            const int c = sv_src_index(j, sw, Wm);
             if (c == pc) continue;
             pc = c;
             if ((bits[r * wpr + (c >> 5)] >> (c & 31)) & 1u) { any = true; break; }

@@ -13,6 +13,7 @@ import torch
 
 from . import _lib
 from ._lib import SegVLADDegenerateError, SegVLADError
+from .rle import RLE_CHUNK_RUNS, RleMasks  # noqa: F401  (RLE_CHUNK_RUNS: the kernels' chunk of runs, for callers and tests)
 
 
 def _ptr(x) -> int:
@@ -551,6 +552,41 @@ class SegVLADEngine:
         self._check(self.lib.segvlad_mask_centroids(self._h, _ptr(m), S, Hm, Wm, _ptr(out)), "mask_centroids")
         self._keep = [m]
         return out
+
+    # ---- run-length masks (rle.RleMasks: SAM's uncompressed RLE) -----------------------------------------------------------
+    def _rle_args(self, rle):
+        if not isinstance(rle, RleMasks):
+            raise TypeError(f"expected an RleMasks batch, got {type(rle)}")
+        n_bad = torch.zeros(1, dtype=torch.int32, device=self.device)   # the kernel adds to it; nothing here reads it back
+        self.rle_n_bad = n_bad
+        return rle.counts, rle.run_offsets, len(rle), rle.Hm, rle.Wm, n_bad
+
+    def incidence_rle(self, rle, H: int, W: int, patch: int = 14, centroids: bool = True, want_bad: bool = False):
+        """incidence_centroids() of a run-length batch without inflating it: ``(bits, cent)`` -- incidence bit rows
+        [S, ceil(N/64)] as int64 and centroids [S, 2] fp64 (x, y), ``None`` with ``centroids=False`` -- byte for byte what the
+        dense call returns for ``rle.to_dense()``.  The number of malformed masks (runs that do not sum to Hm * Wm) stays on the
+        device: ``self.rle_n_bad`` (int32 [1]; also returned third with ``want_bad=True``) -- reading it is the caller's
+        synchronisation, not this call's.  Masks whose bitmap exceeds 150 KiB of LDS raise SegVLADError with code
+        SEGVLAD_ERR_LIMIT: ``incidence_centroids(rle_decode(rle), ...)`` then."""
+        c, o, S, Hm, Wm, n_bad = self._rle_args(rle)
+        N = (H // patch) * (W // patch)
+        out = self._empty((S, (N + 63) // 64), torch.int64)
+        cent = self._empty((S, 2), torch.float64) if centroids else None
+        self._stream()
+        self._check(self.lib.segvlad_incidence_rle(self._h, _ptr(c), _ptr(o), S, Hm, Wm, H, W, patch, _ptr(out), _ptr(cent), _ptr(n_bad)),
+                    "incidence_rle")
+        self._keep = [c, o, n_bad]
+        return (out, cent, n_bad) if want_bad else (out, cent)
+
+    def rle_decode(self, rle, want_bad: bool = False):
+        """A run-length batch inflated on the device: uint8 [S, Hm, Wm] of 0 / 1 (any size).  ``self.rle_n_bad`` /
+        ``want_bad`` as for incidence_rle."""
+        c, o, S, Hm, Wm, n_bad = self._rle_args(rle)
+        out = self._empty((S, Hm, Wm), torch.uint8)
+        self._stream()
+        self._check(self.lib.segvlad_rle_decode(self._h, _ptr(c), _ptr(o), S, Hm, Wm, _ptr(out), _ptr(n_bad)), "rle_decode")
+        self._keep = [c, o, n_bad]
+        return (out, n_bad) if want_bad else out
 
     def adjacency(self, centroids, seg_offsets, order: int, check_empty: bool = False) -> torch.Tensor:
         """centroids [S_tot,2] fp64 -> uint8 buffer with the concatenated per-image [S_b,S_b] (A1^order > 0)

@@ -15,6 +15,7 @@ from . import _lib
 from ._lib import SEGVLAD_ERR_LIMIT, SegVLADDegenerateError, SegVLADError
 from .engine import SegVLADEngine
 from .func_vpr import adjacency_from_centroids
+from .rle import RleMasks
 
 _POOL: Optional[ThreadPoolExecutor] = None
 
@@ -62,12 +63,14 @@ class SegVLADPipeline:
     # ---- a2..a9: images -> (normalised) segment descriptors ------------------------------------------
     def describe(self, tokens: torch.Tensor, masks: torch.Tensor, seg_offsets: np.ndarray, adj=None,
                  l2norm: bool = True) -> torch.Tensor:
-        """tokens [B,D,N] fp32 (device), masks [S_tot,Hm,Wm] uint8 (device), seg_offsets [B+1] (host).
+        """tokens [B,D,N] fp32 (device), masks [S_tot,Hm,Wm] uint8 (device) or an ``RleMasks`` batch of S_tot run-length masks
+        (SAM's uncompressed RLE; same results, the masks are never inflated), seg_offsets [B+1] (host).
         adj: precomputed concatenated adjacency (uint8) or None to derive it (order>0) from the masks.
         Returns [S_tot, P] (PCA'd, row-normalised when l2norm) or [S_tot, K*D]."""
         eng = self.eng
         lazy = None   # (device flags, centroids) of a device adjacency whose per-image flags have not been looked at yet
-        if (self.order and adj is None and not self.host_adjacency and hasattr(eng, "describe_begin")
+        rle = masks if isinstance(masks, RleMasks) else None   # run-length masks: the separate entry points below, never inflated
+        if (rle is None and self.order and adj is None and not self.host_adjacency and hasattr(eng, "describe_begin")
                 and isinstance(tokens, torch.Tensor) and tokens.is_cuda and isinstance(masks, torch.Tensor) and masks.is_cuda
                 and (self.fuse_pca or not self.use_pca)):
             # THREE calls (segvlad_describe_begin / _flags / _end): the mask branch (incidence + centroids -> adjacency) runs on the
@@ -102,7 +105,7 @@ class SegVLADPipeline:
                         raise
                 return eng.describe_end(h, imgs, blocks, l2norm=l2norm)["out"]
         if self.order and adj is None:
-            bits, cent = eng.incidence_centroids(masks, self.H, self.W, self.patch)   # one pass over the mask bytes
+            bits, cent = self._incidence(masks, rle, True)   # one pass over the mask bytes (or over the runs)
             if self.host_adjacency:   # scipy/Qhull on the host, exactly the reference's library (slow: ~0.4 ms/image)
                 adj = adjacency_batch(cent.cpu().numpy(), seg_offsets, self.order, self.adj_workers)
             else:                     # device kernel: no host round trip (check_empty: one flag byte per image comes back)
@@ -130,7 +133,7 @@ class SegVLADPipeline:
                     # without per-image flags): the reference's own Qhull path for this batch
                     adj = adjacency_batch(cent.cpu().numpy(), seg_offsets, self.order, self.adj_workers)
         else:
-            bits = eng.incidence(masks, self.H, self.W, self.patch)
+            bits = self._incidence(masks, rle, False)[0]
             if not self.order:
                 adj = None
         out = self._describe_with(tokens, bits, seg_offsets, adj, l2norm)
@@ -140,6 +143,21 @@ class SegVLADPipeline:
                 self._eager_flags = 16
                 out = self._describe_with(tokens, bits, seg_offsets, patched, l2norm)
         return out
+
+    def _incidence(self, masks, rle, want_centroids):
+        """(incidence bit rows, centroids or None) of dense masks or of a run-length batch.  Masks whose bitmap the run-length
+        kernel cannot hold (SEGVLAD_ERR_LIMIT) are inflated on the device and take the dense entry: the same bytes."""
+        eng = self.eng
+        if rle is not None:
+            try:
+                return eng.incidence_rle(rle, self.H, self.W, self.patch, centroids=want_centroids)
+            except SegVLADError as e:
+                if e.code != SEGVLAD_ERR_LIMIT:
+                    raise
+                masks = eng.rle_decode(rle)
+        if want_centroids:
+            return eng.incidence_centroids(masks, self.H, self.W, self.patch)
+        return eng.incidence(masks, self.H, self.W, self.patch), None
 
     def _check_flags(self, flags_dev, adj, cent, seg_offsets):
         """Reads the per-image flags of a device adjacency (a host synchronisation): raises on an empty mask; images with a

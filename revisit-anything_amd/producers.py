@@ -23,6 +23,10 @@ from typing import Optional, Union
 import numpy as np
 import torch
 
+from .rle import RleMasks
+
+OUTPUT_MODES = ("binary_mask", "uncompressed_rle")   # SamAutoMasks(output_mode=...)
+
 IMAGENET_MEAN = (0.485, 0.456, 0.406)
 IMAGENET_STD = (0.229, 0.224, 0.225)
 
@@ -211,11 +215,17 @@ def box_nms(boxes: torch.Tensor, scores: torch.Tensor, iou_threshold: float) -> 
 class SamAutoMasks:
     """``generate(img_rgb uint8 [H, W, 3]) -> list of SAM records`` (keys as automatic_mask_generator.py:150-168:
     segmentation bool [H, W], area, bbox XYWH, predicted_iou, point_coords, stability_score, crop_box), ordered by
-    decreasing predicted IoU (the order batched_nms returns)."""
+    decreasing predicted IoU (the order batched_nms returns).  ``output_mode="uncompressed_rle"`` puts SAM's run-length dict
+    ``{"size": [H, W], "counts": [...]}`` (mask_to_rle_pytorch, utils/amg.py:107-135) under ``segmentation`` instead of the bool
+    array; ``rle.RleMasks.from_sam(records)`` takes such records to the device as they are."""
 
     def __init__(self, model, points_per_side: int = 32, points_per_batch: int = 64, pred_iou_thresh: float = 0.88,
                  stability_score_thresh: float = 0.95, stability_score_offset: float = 1.0, box_nms_thresh: float = 0.7,
-                 min_mask_region_area: int = 0, mask_threshold: float = 0.0, device: Union[str, torch.device] = "cpu"):
+                 min_mask_region_area: int = 0, mask_threshold: float = 0.0, device: Union[str, torch.device] = "cpu",
+                 output_mode: str = "binary_mask"):
+        if output_mode not in OUTPUT_MODES:   # (the reference's third mode, coco_rle, needs pycocotools: not offered)
+            raise ValueError(f"output_mode must be one of {OUTPUT_MODES}, got {output_mode!r}")
+        self.output_mode = output_mode
         self.device = torch.device(device)
         self.model = model.eval().to(self.device)
         self.img_size = int(self.model.config.vision_config.image_size)
@@ -317,12 +327,15 @@ class SamAutoMasks:
         keep = box_nms(boxes, ious, self.box_nms_thresh)                                   # _process_crop: NMS by predicted IoU
         kc = keep.cpu()
         masks, ious, stab, pts, boxes = masks[keep].cpu().numpy(), ious[keep].cpu(), stab[keep].cpu(), pts[kc], boxes[keep].cpu()
+        # output_mode (automatic_mask_generator.py:150-168): the dense mask, or mask_to_rle_pytorch's dict (utils/amg.py:107-135)
+        rle_mode = getattr(self, "output_mode", "binary_mask") == "uncompressed_rle"
+        segs = RleMasks.from_dense(masks).to_sam() if rle_mode and masks.shape[0] else masks
         recs = []
         for j in range(masks.shape[0]):
             area = int(masks[j].sum())
             if area > self.min_mask_region_area:
                 x0, y0, x1, y1 = (int(v) for v in boxes[j])
-                recs.append({"segmentation": masks[j], "area": area, "bbox": [x0, y0, x1 - x0, y1 - y0],
+                recs.append({"segmentation": segs[j], "area": area, "bbox": [x0, y0, x1 - x0, y1 - y0],
                              "predicted_iou": float(ious[j]), "point_coords": [[float(pts[j, 0]), float(pts[j, 1])]],
                              "stability_score": float(stab[j]), "crop_box": [0, 0, W, H]})
         return recs

@@ -117,15 +117,36 @@ class FeatureStore(Group):
         if self.kind == "dino":
             return Group({"ift_dino": Dataset(lambda: np.load(path)["ift_dino"])})
         z = np.load(path)
-        seg = z["segmentation"]
+        if "segmentation" in z.files:
+            seg = z["segmentation"]
+            n, one = seg.shape[0], (lambda j: seg[j])
+        else:   # written with rle=True: the runs are inflated one mask at a time, when a reader asks for it
+            rle = self._rle_of(z)
+            n, one = len(rle), (lambda j: rle.mask(j))
         recs: Dict[str, object] = {}
-        for j in range(seg.shape[0]):
-            fields: Dict[str, object] = {"segmentation": Dataset(lambda j=j: seg[j])}
+        for j in range(n):
+            fields: Dict[str, object] = {"segmentation": Dataset(lambda j=j: one(j))}
             for f in MASK_FIELDS[1:]:
                 if f in z.files:
                     fields[f] = Dataset(lambda f=f, j=j: z[f][j])
             recs[str(j)] = Group(fields)
         return Group({"masks": Group(recs)})
+
+    @staticmethod
+    def _rle_of(z):
+        from .rle import RleMasks
+
+        return RleMasks(z["counts"], z["run_offsets"], int(z["size"][0]), int(z["size"][1]))
+
+    def masks_rle(self, key: str):
+        """One image's masks as an ``RleMasks`` batch (rle.py) without inflating them: what ``write_masks(..., rle=True)``
+        stored, or the encoding of a dense store's stack."""
+        if self.kind != "masks":
+            raise ValueError("masks_rle needs a store of kind 'masks'")
+        from .rle import RleMasks
+
+        z = np.load(os.path.join(self.root, _fname(key)))
+        return RleMasks.from_dense(z["segmentation"]) if "segmentation" in z.files else self._rle_of(z)
 
 
 def write_dino(root: str, key: str, ift_dino) -> str:
@@ -139,13 +160,24 @@ def write_dino(root: str, key: str, ift_dino) -> str:
     return path
 
 
-def write_masks(root: str, key: str, masks: Sequence) -> str:
+def write_masks(root: str, key: str, masks: Sequence, rle: bool = False) -> str:
     """One image's SAM records (``func_vpr.py:674-678``).  ``masks``: a list of SAM dicts (``segmentation`` + the
-    record fields), a list of 2-D arrays, or a ``[S, Hm, Wm]`` array."""
+    record fields), a list of 2-D arrays, or a ``[S, Hm, Wm]`` array.
+    ``rle=True``, an ``RleMasks`` batch, or records whose ``segmentation`` is SAM's run-length dict
+    (``output_mode="uncompressed_rle"``): the segmentation is stored as its runs (``counts`` / ``run_offsets`` / ``size``,
+    rle.py) instead of the dense stack; readers of the store see the same bool arrays."""
+    from .rle import RleMasks
+
     os.makedirs(root, exist_ok=True)
-    if len(masks) and isinstance(masks[0], Mapping):
-        seg = np.stack([np.asarray(m["segmentation"]).astype(bool) for m in masks])
-        extra = {}
+    extra = {}
+    runs = None
+    if isinstance(masks, RleMasks):
+        runs = masks
+    elif len(masks) and isinstance(masks[0], Mapping):
+        if isinstance(masks[0]["segmentation"], Mapping):
+            runs = RleMasks.from_sam(masks)
+        else:
+            seg = np.stack([np.asarray(m["segmentation"]).astype(bool) for m in masks])
         for f in MASK_FIELDS[1:]:
             if all(f in m for m in masks):
                 extra[f] = np.stack([np.asarray(m[f]) for m in masks])
@@ -153,11 +185,16 @@ def write_masks(root: str, key: str, masks: Sequence) -> str:
         seg = np.asarray(masks).astype(bool)
         if seg.ndim == 2:
             seg = seg[None]
-        extra = {}
-    if seg.ndim != 3:
+    if runs is None and seg.ndim != 3:
         raise ValueError(f"masks must stack to [S, Hm, Wm], got {seg.shape}")
     path = os.path.join(root, _fname(key))
-    np.savez_compressed(path, segmentation=seg, **extra)
+    if runs is None and rle:
+        runs = RleMasks.from_dense(seg)
+    if runs is not None:
+        counts, run_offsets = runs.arrays()
+        np.savez_compressed(path, counts=counts, run_offsets=run_offsets, size=np.array([runs.Hm, runs.Wm], np.int64), **extra)
+    else:
+        np.savez_compressed(path, segmentation=seg, **extra)
     return path
 
 

@@ -503,7 +503,7 @@ int sv_launch_l2_strided(segvlad_ctx* ctx, const float* Q, const float* R, float
 int sv_launch_l2_strided_parts(segvlad_ctx* ctx, const float* Q, const float* R, float* dist, int M, int n_sample, int Kd,
                                int64_t ldc, const float* qn, const float* rn, int b_stride, const float** parts, int* splits);
 // the reduction of such a block fused with the rank select of every row (<= 4096 columns, <= 128 rows): thr_out[row] = the
-// rank-th smallest distance of the row -- what splitk_reduce_d2_kernel + sv_launch_select_approx(mode 0, fixed_cnt) compute,
+// rank-th smallest distance of the row -- what splitk_reduce_d2_kernel + sv_launch_select_approx(Threshold, fixed_cnt) compute,
 // value for value, in one launch instead of two (the single-image pass is a chain of dependent launches); also zeroes
 // cand_cnt[row]; a row already flagged in fail_rows gets -inf
 int sv_launch_l0_reduce_rank(segvlad_ctx* ctx, const float* parts, int splits, int M, int n_sample, int64_t ldc, const float* qn,
@@ -520,22 +520,46 @@ int sv_launch_bf16_filter(segvlad_ctx* ctx, const uint16_t* Qh, const uint16_t* 
                           int64_t thr_ld, float eps_mult, float c_eps, float rn_max, uint32_t* cand_cnt, float* cand_d2,
                           uint32_t* cand_id, int cap);
 // knn_candidate_kernels.hip (the filters' candidate lists: select, exact refinement; sv_launch_l0_reduce_rank above lives there too)
-// rank: which order statistic of the list is A (mode 0: the next level's threshold; mode 1: k).  check != 0 (heuristic
-// thresholds): mode 0 flags a list shorter than rank, mode 1 flags A > thr_in[row * thr_in_ld] (the threshold the list was
-// collected under).  Flagged rows (also: list overflow) are marked in fail_rows and counted once in *fail_count.
-// mode 0 also ZEROES cand_cnt[row] (the next level's filter appends from zero).  fixed_cnt >= 0: every row is a list of that
-// length (the sampled level's distance block) and cand_cnt is not read.
-// mode 2 (batches, the level before the last one when that runs over the complement of this level's sample -- option level_carry):
-// thr_out = min(A, thr_in) and the entries with d2~ <= thr_out + 2 eps STAY in the list, compacted to its front, cand_cnt[row] =
-// their number: the last level appends behind them instead of computing the sample's rows a second time.
-int sv_launch_select_approx(segvlad_ctx* ctx, uint32_t* cand_cnt, float* cand_d2, uint32_t* cand_id, int nq,
-                            int cap, int rank, int mode, int check, const float* thr_in, int64_t thr_in_ld, const float* qn,
-                            float c_eps, float rn_max, float* thr_out, uint32_t* ref_cnt, uint32_t* ref_id, int rcap,
-                            uint32_t* fail_rows, uint32_t* fail_count, uint32_t* rovf_rows = nullptr, uint32_t* rovf_count = nullptr,
-                            float* ref_lim = nullptr, int fixed_cnt = -1);
-// rovf_rows / rovf_count / ref_lim (mode 1): a refine band longer than rcap marks its row there (with the band's upper limit)
-// instead of in fail_rows: sv_launch_refine2_compact + sv_launch_refine_exact(..., rcap = cap, only_rows = rovf_rows)
-// then refine it straight from the candidate list.
+// A select ranks every row's candidate list and then decides what its order statistic A (the k-th smallest d2~) means:
+//   Threshold  thr_out[row] = A, the next level's threshold; cnt[row] is ZEROED (the next level's filter appends from zero, no
+//              memset launch between the levels).
+//   Band       the refine list ref_id[row][0 .. ref_cnt[row]) = {d2~ <= A + 2 eps} (unordered).  A band longer than rcap marks
+//              its row in rovf_rows, with the band's limit in ref_lim, counted in *rovf_count (second tier:
+//              sv_launch_refine2_compact + sv_launch_refine_exact(..., rcap = cap, only_rows = rovf_rows) refine it straight
+//              from the candidate list) -- or, without a second tier, flags it.
+//   Carry      (batches, the level before the last one when that runs over the complement of this level's sample -- option
+//              level_carry) thr_out = min(A, thr_in) and the entries with d2~ <= thr_out + 2 eps STAY in the list, compacted to
+//              its front, cnt[row] = their number: the last level appends behind them instead of computing the sample's rows a
+//              second time.
+// check != 0 (guessed thresholds): a list shorter than k is flagged, and Band flags A > thr_in[row * thr_in_ld] (the threshold
+// the list was collected under).  Flagged rows (also: list overflow, rows flagged at a coarser level) are marked in ovf_rows and
+// counted once in *ovf_count; they get an empty refine list (Band) or a threshold of -inf.
+// Passed to the kernels by value; the row rule itself is select_dev.h.
+enum class SvSelect : int { Threshold = 0, Band = 1, Carry = 2 };
+struct SvSelectArgs {
+  uint32_t* cnt = nullptr;        // [nq] list lengths (not read when fixed_cnt >= 0)
+  float* cd2 = nullptr;           // [nq][cap] d2~
+  uint32_t* cid = nullptr;        // [nq][cap] index rows
+  int cap = 0;
+  int k = 0;                      // which order statistic of the list is A (Threshold, Carry: the next level's rank; Band: k)
+  SvSelect mode = SvSelect::Threshold;
+  int check = 0;
+  const float* thr_in = nullptr;
+  int64_t thr_in_ld = 0;
+  const float* qn = nullptr;      // eps(q) = c_eps sqrt(qn[row] rn_max)
+  float c_eps = 0.f, rn_max = 0.f;
+  float* thr_out = nullptr;
+  uint32_t* ref_cnt = nullptr;
+  uint32_t* ref_id = nullptr;     // [nq][rcap]
+  int rcap = 0;
+  uint32_t* ovf_rows = nullptr;
+  uint32_t* ovf_count = nullptr;
+  uint32_t* rovf_rows = nullptr;  // second tier (optional)
+  uint32_t* rovf_count = nullptr;
+  float* ref_lim = nullptr;
+  int fixed_cnt = -1;             // >= 0: every row is a list of that length (the sampled level's distance block)
+};
+int sv_launch_select_approx(segvlad_ctx* ctx, int nq, const SvSelectArgs& a);
 int sv_launch_refine2_compact(segvlad_ctx* ctx, const uint32_t* rovf_rows, const float* ref_lim, uint32_t* cand_cnt,
                               const float* cand_d2, uint32_t* cand_id, int nq, int cap);
 // only_rows != null: rows whose flag is clear are skipped (their outputs stay as they are)

@@ -12,287 +12,136 @@
 
 #include "ctx.h"
 #include "knn_dev.h"
+#include "select_dev.h"
 #include "small_pass_dev.h"
 
 // ---- candidate handling ----------------------------------------------------------------------------------
-// wave-aggregated LDS histogram increment (keys cluster on few digits: a plain atomicAdd would serialise)
-__device__ __forceinline__ void hist_add_(uint32_t* hist, bool active, uint32_t bin) {
-  uint64_t todo = __ballot(active);
-  while (todo) {
-    const int leader = __ffsll((unsigned long long)todo) - 1;
-    const uint32_t lb = __shfl(bin, leader);
-    const uint64_t same = __ballot(active && bin == lb) & todo;
-    if ((int)(threadIdx.x & 63) == leader) atomicAdd(&hist[lb], (uint32_t)__popcll(same));
-    todo &= ~same;
-  }
-}
-
-// Candidate lists are only RANKED here, never sorted: an MSB-first radix select over the keys held in LDS
-// yields A_k, the k-th smallest approximate distance (+inf if fewer than k candidates).
-//   mode 0: thr_out[q] = A_k
-//   mode 1: refine list = ids with d2~ <= A_k + 2 eps(q) (unordered; at most rcap, more -> the row is flagged in ovf_rows)
-__global__ __launch_bounds__(256) void select_approx_kernel(uint32_t* __restrict__ cnt, float* __restrict__ cd2,
-                                                            uint32_t* __restrict__ cid, int cap, int k, int mode, int check,
-                                                            const float* __restrict__ thr_in, int64_t thr_in_ld,
-                                                            const float* __restrict__ qn, float c_eps, float rn_max,
-                                                            float* __restrict__ thr_out, uint32_t* __restrict__ ref_cnt,
-                                                            uint32_t* __restrict__ ref_id, int rcap,
-                                                            uint32_t* __restrict__ ovf_rows,
-                                                            uint32_t* __restrict__ ovf_count,
-                                                            const uint32_t* __restrict__ todo,
-                                                            uint32_t* __restrict__ rovf_rows,
-                                                            uint32_t* __restrict__ rovf_count,
-                                                            float* __restrict__ ref_lim) {
+// Candidate lists are only RANKED here, never sorted: a radix select over the keys yields A, the k-th smallest approximate
+// distance (+inf if fewer than k candidates); what A then means is the row rule of select_dev.h (SvSelectArgs, ctx.h).
+// This kernel: lists beyond the wave kernel's 4096 keys, a 256-thread workgroup per list, the keys in LDS.
+__global__ __launch_bounds__(256) void select_approx_kernel(SvSelectArgs a, const uint32_t* __restrict__ todo) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   uint32_t* keys = reinterpret_cast<uint32_t*>(smem);  // [cap]
-  __shared__ uint32_t hist[256];
-  __shared__ uint32_t s_digit, s_krem, s_n;
+  __shared__ uint32_t s_n;
   const int tid = threadIdx.x;
   const int64_t row = blockIdx.x;
   if (todo && !todo[row]) return;   // already ranked by select_small_kernel
   __shared__ uint32_t s_c;
   if (tid == 0) {
-    s_c = cnt[row];
-    if (mode != 1) cnt[row] = 0u;   // the next level's filter appends from zero (no memset launch between the levels); mode 2: below
+    s_c = a.cnt[row];
+    if (a.mode != SvSelect::Band) a.cnt[row] = 0u;   // (Carry: set again below)
   }
   __syncthreads();
   const uint32_t c = s_c;
-  // the threshold this list was collected under (read before thr_out -- possibly the same word -- is overwritten)
-  const float t_in = ((check && mode == 1) || mode == 2) ? thr_in[row * thr_in_ld] : 0.f;
-  auto flag_row = [&]() {
-    // this query is redone later (rigorous thresholds / exact matrix path): a threshold of -inf keeps its candidate
-    // list empty at the finer levels, an empty refine list makes the refinement a no-op
-    if (tid == 0) {
-      if (atomicExch(&ovf_rows[row], 1u) == 0u) atomicAdd(ovf_count, 1u);
-      if (mode == 1) ref_cnt[row] = 0;
-      else thr_out[row] = -INFINITY;
-    }
-  };
-  if (c > (uint32_t)cap || ovf_rows[row] || (check && (int)c < k)) {   // overflow / flagged at a coarser level / too few
-    flag_row();
+  const float t_in = sel_thr_in_(a, row);
+  if (sel_rejects_(a, c, (uint32_t)a.cap, a.ovf_rows[row])) {
+    if (tid == 0) sel_flag_row_(a, row);
     return;
   }
-  for (int j = tid; j < (int)c; j += 256) keys[j] = f2key_(cd2[row * cap + j]);
+  for (int j = tid; j < (int)c; j += 256) keys[j] = f2key_(a.cd2[row * a.cap + j]);
   float ak = INFINITY;
-  if ((int)c >= k) {
-    uint32_t prefix = 0, mask = 0, krem = (uint32_t)k;
-    for (int pass = 3; pass >= 0; --pass) {
-      hist[tid] = 0;
-      __syncthreads();
-      const int shift = 8 * pass;
-      for (int j0 = 0; j0 < (int)c; j0 += 256) {
-        const int j = j0 + tid;
-        const uint32_t key = (j < (int)c) ? keys[j] : 0u;
-        hist_add_(hist, (j < (int)c) && ((key & mask) == prefix), (key >> shift) & 255u);
-      }
-      __syncthreads();
-      if (tid == 0) {
-        uint32_t cum = 0, dsel = 255;
-        for (uint32_t b = 0; b < 256; ++b) {
-          const uint32_t h = hist[b];
-          if (cum + h >= krem) {
-            dsel = b;
-            break;
-          }
-          cum += h;
-        }
-        s_digit = dsel;
-        s_krem = krem - cum;
-      }
-      __syncthreads();
-      prefix |= s_digit << shift;
-      mask |= 255u << shift;
-      krem = s_krem;
-      __syncthreads();
-    }
-    ak = key2f_(prefix);
-  } else {
-    __syncthreads();
-  }
-  if (mode == 0) {
-    if (tid == 0) thr_out[row] = ak;
+  if ((int)c >= a.k) ak = key2f_(sv_radix8_select_((int)c, (uint32_t)a.k, [&](int j) { return keys[j]; }, tid).prefix);
+  else __syncthreads();
+  if (a.mode == SvSelect::Threshold) {
+    if (tid == 0) a.thr_out[row] = ak;
     return;
   }
-  if (mode == 2) {   // carry (see select_small_body): in place, 256 entries at a time -- a chunk's survivors land below its own start + 256
-    const float t2 = fminf(ak, t_in);
-    const float lim2 = t2 + 2.f * c_eps * sqrtf(qn[row] * rn_max);
+  if (a.mode == SvSelect::Carry) {   // in place, 256 entries at a time -- a chunk's survivors land below its own start + 256
+    const float t2 = sel_carry_thr_(ak, t_in);
+    const float lim2 = sel_limit_(a, row, t2);
     if (tid == 0) s_n = 0;
     __syncthreads();
     for (int j0 = 0; j0 < (int)c; j0 += 256) {
       const int j = j0 + tid;
       const float v = (j < (int)c) ? key2f_(keys[j]) : INFINITY;
-      const uint32_t id = (j < (int)c) ? cid[row * cap + j] : 0u;
+      const uint32_t id = (j < (int)c) ? a.cid[row * a.cap + j] : 0u;
       __syncthreads();   // the chunk is in registers
       if (j < (int)c && v <= lim2) {
         const uint32_t pos = atomicAdd(&s_n, 1u);
-        cd2[row * cap + pos] = v;
-        cid[row * cap + pos] = id;
+        a.cd2[row * a.cap + pos] = v;
+        a.cid[row * a.cap + pos] = id;
       }
       __syncthreads();   // (the next chunk's reads start at j0 + 256 >= every position written so far)
     }
     if (tid == 0) {
-      thr_out[row] = t2;
-      cnt[row] = s_n;
+      a.thr_out[row] = t2;
+      a.cnt[row] = s_n;
     }
     return;
   }
-  // heuristic thresholds: the list holds every row with d2~ <= t_in + 2 eps; the refine set {d2~ <= A_k + 2 eps} is
-  // contained in it iff A_k <= t_in
-  if (check && !(ak <= t_in)) {
-    flag_row();
+  if (sel_check_fails_(a, ak, t_in)) {
+    if (tid == 0) sel_flag_row_(a, row);
     return;
   }
-  const float flim = ak + 2.f * c_eps * sqrtf(qn[row] * rn_max);
+  const float flim = sel_limit_(a, row, ak);
   const uint32_t klim = f2key_(flim);
   if (tid == 0) s_n = 0;
   __syncthreads();
   for (int j = tid; j < (int)c; j += 256) {
     if (keys[j] <= klim) {
       const uint32_t slot = atomicAdd(&s_n, 1u);
-      if (slot < (uint32_t)rcap) ref_id[row * rcap + slot] = cid[row * cap + j];
+      if (slot < (uint32_t)a.rcap) a.ref_id[row * a.rcap + slot] = a.cid[row * a.cap + j];
     }
   }
   __syncthreads();
-  if (tid == 0) {
-    if (s_n > (uint32_t)rcap) {
-      // the band holds more rows than the first-tier refine list: second tier (refine2_compact_kernel + a refinement
-      // pass straight from the candidate list), or -- without one -- the exact matrix path
-      if (rovf_rows) {
-        rovf_rows[row] = 1u;
-        ref_lim[row] = flim;
-        atomicAdd(rovf_count, 1u);
-      } else if (atomicExch(&ovf_rows[row], 1u) == 0u) {
-        atomicAdd(ovf_count, 1u);
-      }
-      ref_cnt[row] = 0;
-    } else {
-      ref_cnt[row] = s_n;
-    }
-  }
+  if (tid == 0) sel_close_band_(a, row, s_n, flim);
 }
 
 // The same ranking for lists of up to 4096 candidates (every list of the low-rank level scheme, and nearly every list of
-// the rigorous one), one WAVE per query instead of one 256-thread workgroup: the keys live in registers (4, 16 or 64 per
-// lane, by the list's length), the rank-th smallest is found by a binary MSB-first radix select whose per-bit counts are
-// per-lane sums + one DPP wave reduction, the refine list is compacted by ballots.  No LDS, no barriers.  Longer lists are
-// left to select_approx_kernel (todo[row] = 1).
-// select_small_body: the ranking itself for lists of at most 64 * PER keys (PER register slots per lane, loops fully
-// unrolled: a run-time bound on the slot loops cost a scalar branch per slot and bit -- 40 us per launch).
+// the rigorous one), one WAVE per query instead of one 256-thread workgroup: the keys live in registers (4, 16, 32 or 64 per
+// lane, by the list's length), the rank-th smallest is found by the binary radix select with DPP wave reductions, the refine
+// list is compacted by ballots.  No LDS, no barriers.  Longer lists are left to select_approx_kernel (todo[row] = 1).
+// select_small_body: the ranking itself for lists of at most 64 * PER keys; l: the lane, c: the list's length, past the entry test.
 template <int PER>
-__device__ __forceinline__ void select_small_body(uint32_t* __restrict__ cnt, float* __restrict__ cd2, uint32_t* __restrict__ cid, int64_t row, int l,
-                                                  uint32_t c, int cap, int k, int mode, int check, float t_in,
-                                                  const float* __restrict__ qn, float c_eps, float rn_max,
-                                                  float* __restrict__ thr_out, uint32_t* __restrict__ ref_cnt,
-                                                  uint32_t* __restrict__ ref_id, int rcap, uint32_t* __restrict__ ovf_rows,
-                                                  uint32_t* __restrict__ ovf_count, uint32_t* __restrict__ rovf_rows,
-                                                  uint32_t* __restrict__ rovf_count, float* __restrict__ ref_lim) {
-  auto flag_row = [&]() {
-    if (l == 0) {
-      if (atomicExch(&ovf_rows[row], 1u) == 0u) atomicAdd(ovf_count, 1u);
-      if (mode == 1) ref_cnt[row] = 0;
-      else thr_out[row] = -INFINITY;
-    }
-  };
-  constexpr uint32_t PAD = 0xffffffffu;   // padding sorts last (a real key is never all ones: NaN-free)
+__device__ __forceinline__ void select_small_body(const SvSelectArgs& a, int64_t row, int l, uint32_t c, float t_in) {
   uint32_t key[PER], cidv[PER];
 #pragma unroll
   for (int i = 0; i < PER; ++i) {
     const int j = l + 64 * i;
-    key[i] = PAD;
+    key[i] = SV_KEY_PAD;
     cidv[i] = 0u;
     if (j < (int)c) {
-      key[i] = f2key_(cd2[row * cap + j]);
-      // mode 1: the ids travel with the keys (fetched behind a ballot branch, slot by slot, each was a round trip of its own:
-      // 12 of the 19 us of a pass's last select)
-      if (mode != 0) cidv[i] = cid[row * cap + j];
+      key[i] = f2key_(a.cd2[row * a.cap + j]);
+      // Band, Carry: the ids travel with the keys (fetched behind a ballot branch, slot by slot, each was a round trip of its
+      // own: 12 of the 19 us of a pass's last select)
+      if (a.mode != SvSelect::Threshold) cidv[i] = a.cid[row * a.cap + j];
     }
   }
-  float ak = INFINITY;
-  if ((int)c >= k) {
-    // The keys of a list share their leading bits (distances of one query: same sign, a handful of exponents), and after a
-    // dozen more only one key still matches the prefix: the bit loop starts below the common prefix of the list's smallest and
-    // largest key and stops as soon as a single candidate is left (32 bits x 2 PER VALU instructions were 7 of the ~10 us of a
-    // 4096-key launch).  All of it is wave-uniform.
-    uint32_t kmn = 0xffffffffu, kmx = 0u;
-#pragma unroll
-    for (int i = 0; i < PER; ++i) {
-      kmn = min(kmn, key[i]);
-      kmx = key[i] != PAD ? max(kmx, key[i]) : kmx;
-    }
-    kmn = wave_min_u32_(kmn);
-    kmx = wave_max_u32_(kmx);
-    const uint32_t diff = kmn ^ kmx;
-    uint32_t prefix = kmn, mask = 0xffffffffu, rem = (uint32_t)k, m = c;   // diff == 0: every key is kmn
-    int bit = -1;
-    if (diff) {
-      bit = 31 - __builtin_clz(diff);
-      mask = (bit == 31) ? 0u : ~((2u << bit) - 1u);
-      prefix = kmn & mask;
-    }
-    for (; bit >= 0 && m > 1u; --bit) {
-      const uint32_t b = 1u << bit;
-      // keys that match the prefix so far and have this bit clear: counted per lane (a compare + an add per key slot), then
-      // ONE wave sum per bit by DPP row reductions + four readlanes.  (The butterfly of six ds_bpermute shuffles it replaces
-      // was ~8 us of LDS-crossbar latency per launch; a ballot + scalar popcount per slot stalls on the VALU -> SALU
-      // hand-over of every compare: 42 us for 64 slots.)
-      uint32_t zl = 0;
-#pragma unroll
-      for (int i = 0; i < PER; ++i) zl += ((key[i] & (mask | b)) == prefix) ? 1u : 0u;
-      const uint32_t zeros = wave_sum_u32_(zl);
-      if (rem > zeros) {
-        rem -= zeros;
-        m -= zeros;
-        prefix |= b;
-      } else {
-        m = zeros;
-      }
-      mask |= b;
-    }
-    if (bit >= 0) {   // one key left under the prefix: it is the answer, whatever its remaining bits
-      uint32_t v = 0;
-#pragma unroll
-      for (int i = 0; i < PER; ++i) v |= (key[i] != PAD && (key[i] & mask) == prefix) ? key[i] : 0u;
-      prefix = wave_max_u32_(v);
-    }
-    ak = key2f_(prefix);
-  }
-  if (mode == 0) {
-    if (l == 0) thr_out[row] = ak;
+  SvWaveReduce red;
+  const float ak = sv_kth_smallest_<PER>(key, c, a.k, red);
+  if (a.mode == SvSelect::Threshold) {
+    if (l == 0) a.thr_out[row] = ak;
     return;
   }
-  if (mode == 2) {
-    // carry: the next level runs over the rows this level has NOT seen (the complement of its sample), under the threshold
-    // t2 = min(A_k, t_in).  This list holds every sampled row with d2~ <= t_in + 2 eps, hence every one with d2~ <= t2 + 2 eps --
-    // exactly the rows the next level's filter would append for the sample: they are compacted to the front and the counter is
-    // left at their number.  (A threshold below A_k is as good a guess as A_k: the last level's check is against the value stored.)
-    const float t2 = fminf(ak, t_in);
-    const float lim2 = t2 + 2.f * c_eps * sqrtf(qn[row] * rn_max);
+  if (a.mode == SvSelect::Carry) {
+    const float t2 = sel_carry_thr_(ak, t_in);
+    const float lim2 = sel_limit_(a, row, t2);
     uint32_t kept = 0;
 #pragma unroll
     for (int i = 0; i < PER; ++i) {
       const float v = key2f_(key[i]);
-      const bool hit = key[i] != PAD && v <= lim2;
+      const bool hit = key[i] != SV_KEY_PAD && v <= lim2;
       const uint64_t mk = __builtin_amdgcn_ballot_w64(hit);
       if (mk != 0ull) {
         const uint32_t pos = kept + __builtin_amdgcn_mbcnt_hi((uint32_t)(mk >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mk, 0u));
         if (hit) {   // (every key of the list is in registers: writing in place races with nothing)
-          cd2[row * cap + pos] = v;
-          cid[row * cap + pos] = cidv[i];
+          a.cd2[row * a.cap + pos] = v;
+          a.cid[row * a.cap + pos] = cidv[i];
         }
         kept += (uint32_t)__popcll(mk);
       }
     }
     if (l == 0) {
-      thr_out[row] = t2;
-      cnt[row] = kept;
+      a.thr_out[row] = t2;
+      a.cnt[row] = kept;
     }
     return;
   }
-  if (check && !(ak <= t_in)) {
-    flag_row();
+  if (sel_check_fails_(a, ak, t_in)) {
+    if (l == 0) sel_flag_row_(a, row);
     return;
   }
-  const float flim = ak + 2.f * c_eps * sqrtf(qn[row] * rn_max);
+  const float flim = sel_limit_(a, row, ak);
   const uint32_t klim = f2key_(flim);
   uint32_t total = 0;
 #pragma unroll
@@ -301,114 +150,25 @@ __device__ __forceinline__ void select_small_body(uint32_t* __restrict__ cnt, fl
     const uint64_t mk = __builtin_amdgcn_ballot_w64(hit);
     if (mk != 0ull) {
       const uint32_t pos = total + __builtin_amdgcn_mbcnt_hi((uint32_t)(mk >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mk, 0u));
-      if (hit && pos < (uint32_t)rcap) ref_id[row * rcap + pos] = cidv[i];
+      if (hit && pos < (uint32_t)a.rcap) a.ref_id[row * a.rcap + pos] = cidv[i];
       total += (uint32_t)__popcll(mk);
     }
   }
-  if (l == 0) {
-    if (total > (uint32_t)rcap) {
-      if (rovf_rows) {   // second tier (see select_approx_kernel)
-        rovf_rows[row] = 1u;
-        ref_lim[row] = flim;
-        atomicAdd(rovf_count, 1u);
-      } else if (atomicExch(&ovf_rows[row], 1u) == 0u) {
-        atomicAdd(ovf_count, 1u);
-      }
-      ref_cnt[row] = 0;
-    } else {
-      ref_cnt[row] = total;
-    }
-  }
-}
-
-// k-th smallest of a workgroup's keys (PER per thread, padding = all ones), c >= 1 real keys among them; +inf if c < k.
-// xs: [2][4] LDS exchange slots.  Every thread returns the same value.
-template <int PER>
-__device__ __forceinline__ float wg_kth_smallest_(const uint32_t (&key)[PER], uint32_t c, int k, uint32_t (*xs)[4], int tid) {
-  constexpr uint32_t PAD = 0xffffffffu;
-  const int w = tid >> 6;
-  int turn = 0;
-  auto exchange = [&](uint32_t v_wave) {   // v_wave: this wave's (uniform) partial; returns the four partials
-    if ((tid & 63) == 0) xs[turn][w] = v_wave;
-    __syncthreads();
-    const uint4 r = make_uint4(xs[turn][0], xs[turn][1], xs[turn][2], xs[turn][3]);
-    turn ^= 1;
-    return r;
-  };
-  float ak = INFINITY;
-  if ((int)c >= k) {
-    uint32_t kmn = PAD, kmx = 0u;
-#pragma unroll
-    for (int i = 0; i < PER; ++i) {
-      kmn = min(kmn, key[i]);
-      kmx = key[i] != PAD ? max(kmx, key[i]) : kmx;
-    }
-    {
-      const uint4 r = exchange(wave_min_u32_(kmn));
-      kmn = min(min(r.x, r.y), min(r.z, r.w));
-    }
-    {
-      const uint4 r = exchange(wave_max_u32_(kmx));
-      kmx = max(max(r.x, r.y), max(r.z, r.w));
-    }
-    const uint32_t diff = kmn ^ kmx;
-    uint32_t prefix = kmn, mask = 0xffffffffu, rem = (uint32_t)k, m = c;   // diff == 0: every key is kmn
-    int bit = -1;
-    if (diff) {
-      bit = 31 - __builtin_clz(diff);
-      mask = (bit == 31) ? 0u : ~((2u << bit) - 1u);
-      prefix = kmn & mask;
-    }
-    for (; bit >= 0 && m > 1u; --bit) {
-      const uint32_t b = 1u << bit;
-      uint32_t zl = 0;
-#pragma unroll
-      for (int i = 0; i < PER; ++i) zl += ((key[i] & (mask | b)) == prefix) ? 1u : 0u;
-      const uint4 r = exchange(wave_sum_u32_(zl));
-      const uint32_t zeros = r.x + r.y + r.z + r.w;
-      if (rem > zeros) {
-        rem -= zeros;
-        m -= zeros;
-        prefix |= b;
-      } else {
-        m = zeros;
-      }
-      mask |= b;
-    }
-    if (bit >= 0) {   // one key left under the prefix: it is the answer, whatever its remaining bits
-      uint32_t v = 0;
-#pragma unroll
-      for (int i = 0; i < PER; ++i) v |= (key[i] != PAD && (key[i] & mask) == prefix) ? key[i] : 0u;
-      const uint4 r = exchange(wave_max_u32_(v));
-      prefix = max(max(r.x, r.y), max(r.z, r.w));
-    }
-    ak = key2f_(prefix);
-  }
-  return ak;
+  if (l == 0) sel_close_band_(a, row, total, flim);
 }
 
 // One query image per pass (<= 128 lists): a whole workgroup per list instead of a wave -- 32 keys per thread (lists of up
-// to 8192 entries, the capacity of the candidate lists; longer ones are flagged for the exact path), the same
-// binary MSB-first radix select below the common prefix of the list's smallest and largest key, stopping when one key is
-// left; the per-bit count is a DPP wave sum + a four-entry LDS exchange (one barrier per bit: the exchange slots alternate).
+// to 8192 entries, the capacity of the candidate lists; longer ones are flagged for the exact path), the binary radix select
+// with the workgroup reducer (one barrier per bit).
 // The wave kernel's 64-keys-per-lane instantiation is ~8000 straight-line instructions that a pass runs through ONCE --
 // instruction fetch, not arithmetic: 29 us for a 3906-entry sample row; this kernel takes ~10.
-// PERK: keys per thread.  32 covers the candidate lists' capacity (8192); 16 (lists of <= 4096 entries -- every list the
+// PERK: keys per thread.  32 covers the candidate lists' capacity (8192, SV_CAP); 16 (lists of <= 4096 entries -- every list the
 // single-image plan produces in practice) halves the slot loops of the load and of every radix step: the kernel picks the
 // body by the list's length (workgroup-uniform).
 template <int PERK>
-__device__ __forceinline__ void select_wg_body(uint32_t* __restrict__ cnt, const float* __restrict__ cd2,
-                                                        const uint32_t* __restrict__ cid, int cap, int k, int mode, int check,
-                                                        const float* __restrict__ thr_in, int64_t thr_in_ld,
-                                                        const float* __restrict__ qn, float c_eps, float rn_max,
-                                                        float* __restrict__ thr_out, uint32_t* __restrict__ ref_cnt,
-                                                        uint32_t* __restrict__ ref_id, int rcap, uint32_t* __restrict__ ovf_rows,
-                                                        uint32_t* __restrict__ ovf_count, uint32_t* __restrict__ rovf_rows,
-                                                        uint32_t* __restrict__ rovf_count, float* __restrict__ ref_lim, int fixed_cnt,
-                                                        const uint32_t c, const float (&pre_d2)[16], const uint32_t (&pre_id)[16],
-                                                        const uint32_t flagged, const float t_in) {
-  constexpr uint32_t PAD = 0xffffffffu;
-  constexpr int PER = PERK;   // 32: 8192 keys, the candidate lists' capacity (SV_CAP)
+__device__ __forceinline__ void select_wg_body(const SvSelectArgs& a, const uint32_t c, const float (&pre_d2)[16],
+                                               const uint32_t (&pre_id)[16], const uint32_t flagged, const float t_in) {
+  constexpr int PER = PERK;
   __shared__ uint32_t xs[2][4];
   __shared__ uint32_t s_n;
   const int tid = threadIdx.x;
@@ -417,71 +177,45 @@ __device__ __forceinline__ void select_wg_body(uint32_t* __restrict__ cnt, const
 #pragma unroll
   for (int i = 0; i < PER; ++i) {
     const int j = tid + 256 * i;
-    key[i] = PAD;
+    key[i] = SV_KEY_PAD;
     cidv[i] = 0u;
     if (j < (int)c && c <= (uint32_t)(256 * PER)) {
       // (the first 16 slots per thread were requested by the kernel together with the list's length: one round trip, not two)
-      key[i] = f2key_(i < 16 ? pre_d2[i < 16 ? i : 0] : cd2[row * cap + j]);
-      if (mode == 1) cidv[i] = i < 16 ? pre_id[i < 16 ? i : 0] : cid[row * cap + j];
+      key[i] = f2key_(i < 16 ? pre_d2[i < 16 ? i : 0] : a.cd2[row * a.cap + j]);
+      if (a.mode == SvSelect::Band) cidv[i] = i < 16 ? pre_id[i < 16 ? i : 0] : a.cid[row * a.cap + j];
     }
   }
   if (tid == 0) s_n = 0u;
   __syncthreads();   // every thread has read cnt[row]
-  if (tid == 0 && mode == 0) cnt[row] = 0u;   // the next level's filter appends from zero
-  if (c > (uint32_t)cap || c > (uint32_t)(256 * PER) || flagged || (check && (int)c < k)) {
-    if (tid == 0) {
-      if (atomicExch(&ovf_rows[row], 1u) == 0u) atomicAdd(ovf_count, 1u);
-      if (mode == 1) ref_cnt[row] = 0;
-      else thr_out[row] = -INFINITY;
-    }
+  // (no Carry in this kernel -- the host refuses it for a single image --: Threshold is the only mode that resets the counter)
+  if (tid == 0 && a.mode == SvSelect::Threshold) a.cnt[row] = 0u;
+  if (sel_rejects_(a, c, (uint32_t)(256 * PER), flagged)) {
+    if (tid == 0) sel_flag_row_(a, row);
     return;
   }
-  const float ak = wg_kth_smallest_<PER>(key, c, k, xs, tid);
-  if (mode == 0) {
-    if (tid == 0) thr_out[row] = ak;
+  SvWgReduce red{xs, tid};
+  const float ak = sv_kth_smallest_<PER>(key, c, a.k, red);
+  if (a.mode == SvSelect::Threshold) {
+    if (tid == 0) a.thr_out[row] = ak;
     return;
   }
-  if (check && !(ak <= t_in)) {   // see select_approx_kernel
-    if (tid == 0) {
-      if (atomicExch(&ovf_rows[row], 1u) == 0u) atomicAdd(ovf_count, 1u);
-      ref_cnt[row] = 0;
-    }
+  if (sel_check_fails_(a, ak, t_in)) {
+    if (tid == 0) sel_flag_row_(a, row);
     return;
   }
-  const float flim = ak + 2.f * c_eps * sqrtf(qn[row] * rn_max);
+  const float flim = sel_limit_(a, row, ak);
   const uint32_t klim = f2key_(flim);
 #pragma unroll
   for (int i = 0; i < PER; ++i)
     if (key[i] <= klim) {   // (a finite float's key: the padding never hits)
       const uint32_t pos = atomicAdd(&s_n, 1u);
-      if (pos < (uint32_t)rcap) ref_id[row * rcap + pos] = cidv[i];
+      if (pos < (uint32_t)a.rcap) a.ref_id[row * a.rcap + pos] = cidv[i];
     }
   __syncthreads();
-  if (tid == 0) {
-    const uint32_t total = s_n;
-    if (total > (uint32_t)rcap) {
-      if (rovf_rows) {   // second tier (see select_approx_kernel)
-        rovf_rows[row] = 1u;
-        ref_lim[row] = flim;
-        atomicAdd(rovf_count, 1u);
-      } else if (atomicExch(&ovf_rows[row], 1u) == 0u) {
-        atomicAdd(ovf_count, 1u);
-      }
-      ref_cnt[row] = 0;
-    } else {
-      ref_cnt[row] = total;
-    }
-  }
+  if (tid == 0) sel_close_band_(a, row, s_n, flim);
 }
 
-__global__ __launch_bounds__(256) void select_wg_kernel(uint32_t* __restrict__ cnt, const float* __restrict__ cd2,
-                                                        const uint32_t* __restrict__ cid, int cap, int k, int mode, int check,
-                                                        const float* __restrict__ thr_in, int64_t thr_in_ld,
-                                                        const float* __restrict__ qn, float c_eps, float rn_max,
-                                                        float* __restrict__ thr_out, uint32_t* __restrict__ ref_cnt,
-                                                        uint32_t* __restrict__ ref_id, int rcap, uint32_t* __restrict__ ovf_rows,
-                                                        uint32_t* __restrict__ ovf_count, uint32_t* __restrict__ rovf_rows,
-                                                        uint32_t* __restrict__ rovf_count, float* __restrict__ ref_lim, int fixed_cnt) {
+__global__ __launch_bounds__(256) void select_wg_kernel(SvSelectArgs a) {
   // Everything the list's length decides is REQUESTED before the length is known: the first 16 slots of every thread (lists of
   // <= 4096 entries -- every list the single-image plan produces in practice -- are complete with them; the slots lie inside the
   // row's `cap` entries whatever the length, entries beyond it are never looked at), the row's flag, its threshold.  The length
@@ -492,19 +226,15 @@ __global__ __launch_bounds__(256) void select_wg_kernel(uint32_t* __restrict__ c
 #pragma unroll
   for (int i = 0; i < 16; ++i) {
     const int j = threadIdx.x + 256 * i;
-    const bool in = j < cap;
-    pre_d2[i] = in ? cd2[row * cap + j] : 0.f;
-    pre_id[i] = (in && mode == 1) ? cid[row * cap + j] : 0u;
+    const bool in = j < a.cap;
+    pre_d2[i] = in ? a.cd2[row * a.cap + j] : 0.f;
+    pre_id[i] = (in && a.mode == SvSelect::Band) ? a.cid[row * a.cap + j] : 0u;
   }
-  const uint32_t flagged = ovf_rows[row];
-  const float t_in = (check && mode == 1) ? thr_in[row * thr_in_ld] : 0.f;
-  const uint32_t c = fixed_cnt >= 0 ? (uint32_t)fixed_cnt : cnt[row];
-  if (c <= 4096u)
-    select_wg_body<16>(cnt, cd2, cid, cap, k, mode, check, thr_in, thr_in_ld, qn, c_eps, rn_max, thr_out, ref_cnt, ref_id, rcap, ovf_rows,
-                       ovf_count, rovf_rows, rovf_count, ref_lim, fixed_cnt, c, pre_d2, pre_id, flagged, t_in);
-  else
-    select_wg_body<32>(cnt, cd2, cid, cap, k, mode, check, thr_in, thr_in_ld, qn, c_eps, rn_max, thr_out, ref_cnt, ref_id, rcap, ovf_rows,
-                       ovf_count, rovf_rows, rovf_count, ref_lim, fixed_cnt, c, pre_d2, pre_id, flagged, t_in);
+  const uint32_t flagged = a.ovf_rows[row];
+  const float t_in = sel_thr_in_(a, row);
+  const uint32_t c = a.fixed_cnt >= 0 ? (uint32_t)a.fixed_cnt : a.cnt[row];
+  if (c <= 4096u) select_wg_body<16>(a, c, pre_d2, pre_id, flagged, t_in);
+  else select_wg_body<32>(a, c, pre_d2, pre_id, flagged, t_in);
 }
 
 // The sampled exact level of a single-image pass: the K-split partial dot products of <= 128 query rows against <= 4096
@@ -515,7 +245,6 @@ __global__ __launch_bounds__(256) void l0_reduce_rank_kernel(const float* __rest
                                                              const float* __restrict__ row_add, const float* __restrict__ col_add,
                                                              int b_stride, int rank, float* __restrict__ thr_out,
                                                              uint32_t* __restrict__ cnt, const uint32_t* __restrict__ ovf_rows) {
-  constexpr uint32_t PAD = 0xffffffffu;
   constexpr int PER = 16;
   __shared__ uint32_t xs[2][4];
   const int tid = threadIdx.x;
@@ -550,13 +279,14 @@ __global__ __launch_bounds__(256) void l0_reduce_rank_kernel(const float* __rest
   }
   uint32_t key[PER];
 #pragma unroll
-  for (int i = 0; i < PER; ++i) key[i] = (tid + 256 * i < N) ? f2key_(sv_d2(q2, rn[i], sum[i])) : PAD;
+  for (int i = 0; i < PER; ++i) key[i] = (tid + 256 * i < N) ? f2key_(sv_d2(q2, rn[i], sum[i])) : SV_KEY_PAD;
   if (tid == 0) cnt[row] = 0u;   // the next level's filter appends from zero
   if (ovf_rows[row] || N < rank) {   // (workgroup-uniform)
     if (tid == 0) thr_out[row] = -INFINITY;
     return;
   }
-  const float ak = wg_kth_smallest_<PER>(key, (uint32_t)N, rank, xs, tid);
+  SvWgReduce red{xs, tid};
+  const float ak = sv_kth_smallest_<PER>(key, (uint32_t)N, rank, red);
   if (tid == 0) thr_out[row] = ak;
 }
 
@@ -570,87 +300,53 @@ int sv_launch_l0_reduce_rank(segvlad_ctx* ctx, const float* parts, int splits, i
   return SEGVLAD_OK;
 }
 
-__global__ __launch_bounds__(256) void select_small_kernel(uint32_t* __restrict__ cnt, float* __restrict__ cd2,
-                                                           uint32_t* __restrict__ cid, int nq, int cap, int k, int mode, int check,
-                                                           const float* __restrict__ thr_in, int64_t thr_in_ld,
-                                                           const float* __restrict__ qn, float c_eps, float rn_max,
-                                                           float* __restrict__ thr_out, uint32_t* __restrict__ ref_cnt,
-                                                           uint32_t* __restrict__ ref_id, int rcap, uint32_t* __restrict__ ovf_rows,
-                                                           uint32_t* __restrict__ ovf_count, uint32_t* __restrict__ todo,
-                                                           uint32_t* __restrict__ rovf_rows, uint32_t* __restrict__ rovf_count,
-                                                           float* __restrict__ ref_lim, int fixed_cnt) {
+__global__ __launch_bounds__(256) void select_small_kernel(SvSelectArgs a, int nq, uint32_t* __restrict__ todo) {
   constexpr int PER = 64;   // up to 4096 keys per wave, in registers
   const int l = threadIdx.x & 63;
   const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= nq) return;
-  const uint32_t c = fixed_cnt >= 0 ? (uint32_t)fixed_cnt : cnt[row];   // fixed_cnt: every row is a list of that length
-  if (todo && c > (uint32_t)(64 * PER) && c <= (uint32_t)cap && !ovf_rows[row]) {   // long list: the workgroup kernel ranks it
+  const uint32_t c = a.fixed_cnt >= 0 ? (uint32_t)a.fixed_cnt : a.cnt[row];
+  if (todo && c > (uint32_t)(64 * PER) && c <= (uint32_t)a.cap && !a.ovf_rows[row]) {   // long list: the workgroup kernel ranks it
     if (l == 0) todo[row] = 1u;
     return;
   }
   if (l == 0) {
     if (todo) todo[row] = 0u;
-    if (mode != 1) cnt[row] = 0u;   // the next level's filter appends from zero (no memset launch between the levels); mode 2: see the body
+    if (a.mode != SvSelect::Band) a.cnt[row] = 0u;   // (Carry: set again by the body)
   }
-  const float t_in = ((check && mode == 1) || mode == 2) ? thr_in[row * thr_in_ld] : 0.f;
-  auto flag_row = [&]() {
-    if (l == 0) {
-      if (atomicExch(&ovf_rows[row], 1u) == 0u) atomicAdd(ovf_count, 1u);
-      if (mode == 1) ref_cnt[row] = 0;
-      else thr_out[row] = -INFINITY;
-    }
-  };
+  const float t_in = sel_thr_in_(a, row);
   // todo == null (a handful of queries: the workgroup kernel is not even launched): a list beyond the wave's 4096 keys is
   // treated like an overflowing one -- the query is redone on the exact path
-  if (c > (uint32_t)cap || (!todo && c > (uint32_t)(64 * PER)) || ovf_rows[row] || (check && (int)c < k)) {
-    flag_row();
+  if (sel_rejects_(a, c, todo ? 0xffffffffu : (uint32_t)(64 * PER), a.ovf_rows[row])) {
+    if (l == 0) sel_flag_row_(a, row);
     return;
   }
-  if (c <= 256u)
-    select_small_body<4>(cnt, cd2, cid, row, l, c, cap, k, mode, check, t_in, qn, c_eps, rn_max, thr_out, ref_cnt, ref_id, rcap, ovf_rows,
-                         ovf_count, rovf_rows, rovf_count, ref_lim);
-  else if (c <= 1024u)
-    select_small_body<16>(cnt, cd2, cid, row, l, c, cap, k, mode, check, t_in, qn, c_eps, rn_max, thr_out, ref_cnt, ref_id, rcap, ovf_rows,
-                          ovf_count, rovf_rows, rovf_count, ref_lim);
-  else if (c <= 2048u)
-    select_small_body<32>(cnt, cd2, cid, row, l, c, cap, k, mode, check, t_in, qn, c_eps, rn_max, thr_out, ref_cnt, ref_id, rcap, ovf_rows,
-                          ovf_count, rovf_rows, rovf_count, ref_lim);
-  else
-    select_small_body<64>(cnt, cd2, cid, row, l, c, cap, k, mode, check, t_in, qn, c_eps, rn_max, thr_out, ref_cnt, ref_id, rcap, ovf_rows,
-                          ovf_count, rovf_rows, rovf_count, ref_lim);
+  if (c <= 256u) select_small_body<4>(a, row, l, c, t_in);
+  else if (c <= 1024u) select_small_body<16>(a, row, l, c, t_in);
+  else if (c <= 2048u) select_small_body<32>(a, row, l, c, t_in);
+  else select_small_body<64>(a, row, l, c, t_in);
 }
 
-int sv_launch_select_approx(segvlad_ctx* ctx, uint32_t* cand_cnt, float* cand_d2, uint32_t* cand_id, int nq,
-                            int cap, int rank, int mode, int check, const float* thr_in, int64_t thr_in_ld, const float* qn,
-                            float c_eps, float rn_max, float* thr_out, uint32_t* ref_cnt, uint32_t* ref_id, int rcap,
-                            uint32_t* fail_rows, uint32_t* fail_count, uint32_t* rovf_rows, uint32_t* rovf_count, float* ref_lim,
-                            int fixed_cnt) {
+int sv_launch_select_approx(segvlad_ctx* ctx, int nq, const SvSelectArgs& a) {
   if (nq <= 0) return SEGVLAD_OK;
-  if (mode == 2 && nq <= 128) return ctx->fail(SEGVLAD_ERR_STATE, "select: the carrying form exists for batches only");
+  if (a.mode == SvSelect::Carry && nq <= 128) return ctx->fail(SEGVLAD_ERR_STATE, "select: the carrying form exists for batches only");
   if (nq <= 128) {   // one query image per pass: a workgroup per list
-    hipLaunchKernelGGL(select_wg_kernel, dim3(nq), dim3(256), 0, ctx->stream, cand_cnt, cand_d2, cand_id, cap, rank, mode, check, thr_in,
-                       thr_in_ld, qn, c_eps, rn_max, thr_out, ref_cnt, ref_id, rcap, fail_rows, fail_count, rovf_rows, rovf_count,
-                       ref_lim, fixed_cnt);
+    hipLaunchKernelGGL(select_wg_kernel, dim3(nq), dim3(256), 0, ctx->stream, a);
     SV_HIP(hipGetLastError());
     return SEGVLAD_OK;
   }
-  const bool wave_only = fixed_cnt >= 0 && fixed_cnt <= 4096;
+  const bool wave_only = a.fixed_cnt >= 0 && a.fixed_cnt <= 4096;
   uint32_t* todo = nullptr;
   if (!wave_only) {
     SV_HIP(ctx->s_sel_todo.reserve((size_t)nq * 4));
     todo = ctx->s_sel_todo.as<uint32_t>();
   }
-  hipLaunchKernelGGL(select_small_kernel, dim3((nq + 3) / 4), dim3(256), 0, ctx->stream, cand_cnt, cand_d2, cand_id, nq, cap, rank, mode,
-                     check, thr_in, thr_in_ld, qn, c_eps, rn_max, thr_out, ref_cnt, ref_id, rcap, fail_rows, fail_count, todo,
-                     rovf_rows, rovf_count, ref_lim, fixed_cnt);
+  hipLaunchKernelGGL(select_small_kernel, dim3((nq + 3) / 4), dim3(256), 0, ctx->stream, a, nq, todo);
   if (wave_only) {   // every list is ranked (or flagged) by the wave kernel
     SV_HIP(hipGetLastError());
     return SEGVLAD_OK;
   }
-  const size_t lds = (size_t)cap * 4;
-  hipLaunchKernelGGL(select_approx_kernel, dim3(nq), dim3(256), lds, ctx->stream, cand_cnt, cand_d2, cand_id, cap, rank, mode, check,
-                     thr_in, thr_in_ld, qn, c_eps, rn_max, thr_out, ref_cnt, ref_id, rcap, fail_rows, fail_count, todo,
-                     rovf_rows, rovf_count, ref_lim);
+  hipLaunchKernelGGL(select_approx_kernel, dim3(nq), dim3(256), (size_t)a.cap * 4, ctx->stream, a, (const uint32_t*)todo);
   SV_HIP(hipGetLastError());
   return SEGVLAD_OK;
 }
@@ -1142,7 +838,7 @@ __global__ __launch_bounds__(256) void refine_exact_small_kernel(const float* __
   if (__syncthreads_or(holes)) {   // (never observed)
     if (tid == 0) __hip_atomic_store(&tick[SV_TICK_POISON], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (!fz.on) {   // the row's output is left to the redo (the caller's read-back, or small_tail_kernel)
-      if (tid == 0 && fail_rows && atomicExch(&fail_rows[row], 1u) == 0u) atomicAdd(fail_count, 1u);
+      if (tid == 0 && fail_rows) sv_flag_once_(fail_rows, fail_count, row);
       return;
     }
     // fused finish: nobody comes after this kernel -- this workgroup re-evaluates the row's whole band itself (<= rcap rows, a thread

@@ -1,5 +1,5 @@
 // Device helpers shared by the search's translation units: the order-preserving float <-> key map (its only definition), the
-// workgroup bitonic sort of keys or (key << 32 | id) words, DPP wave reductions.
+// workgroup bitonic sort of keys or (key << 32 | id) words, DPP wave reductions, the flagging of a row.
 #pragma once
 #include <stdint.h>
 
@@ -12,6 +12,11 @@ __device__ __forceinline__ uint32_t f2key_(float f) {
 __device__ __forceinline__ float key2f_(uint32_t k) {
   const uint32_t u = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k;
   return __uint_as_float(u);
+}
+
+// a row redone on another path: marked once in its flag word, counted once
+__device__ __forceinline__ void sv_flag_once_(uint32_t* rows, uint32_t* count, int64_t row) {
+  if (atomicExch(&rows[row], 1u) == 0u) atomicAdd(count, 1u);
 }
 
 // Single-image query preparations: the power-of-two scale of the fp16 plane comes from max |x| over the rows whose squared norm is

@@ -670,7 +670,7 @@ __global__ __launch_bounds__(64 * C::WM * C::WN) void knn_f16_filter_kernel(
   const int64_t ldb = (int64_t)d * b_stride;
   // SKIP > 0 ("the complement of a sample"): operand row j is database row j + j / (SKIP - 1) + 1 -- the rows that are NOT multiples
   // of SKIP, in order.  The level before the last one has already filtered the multiples of SKIP (its stride-SKIP sample) with the same
-  // arithmetic; its survivors stay in the candidate lists (select mode 0 with carry) and the last level does not compute them again.
+  // arithmetic; its survivors stay in the candidate lists (SvSelect::Carry) and the last level does not compute them again.
   auto grow = [&](int64_t j) -> int64_t {
     if constexpr (SKIP > 0) return j + (int64_t)((uint32_t)j / (uint32_t)(SKIP - 1)) + 1;
     else return j * b_stride;

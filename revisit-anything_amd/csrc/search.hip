@@ -510,6 +510,28 @@ struct Chunk {
   uint32_t* flags() const { return fb->rows() + row0; }
 };
 
+// What every select of a chunk is handed: the candidate lists, the margin, the refine list, the flag and second-tier words.
+// The caller sets mode, k, check, the thresholds in and out.
+static SvSelectArgs select_args(segvlad_ctx* ctx, const Chunk& c, const PassScalars& v) {
+  SvSelectArgs a;
+  a.cnt = ctx->s_cand_cnt.as<uint32_t>();
+  a.cd2 = ctx->s_cand_d2.as<float>();
+  a.cid = ctx->s_cand_id.as<uint32_t>();
+  a.cap = SV_CAP;
+  a.qn = c.qn;
+  a.c_eps = v.c_eps;
+  a.rn_max = v.rn_max;
+  a.ref_cnt = ctx->s_ref_cnt.as<uint32_t>();
+  a.ref_id = ctx->s_ref_id.as<uint32_t>();
+  a.rcap = SV_RCAP;
+  a.ovf_rows = c.flags();
+  a.ovf_count = c.fb->count();
+  a.rovf_rows = c.fb->tier2();
+  a.rovf_count = c.fb->count() + 1;
+  a.ref_lim = ctx->s_ref_lim.as<float>();
+  return a;
+}
+
 // ---- one chunk: level 0, the filter levels, the finish -------------------------------------------------------------
 // Level 0's form:
 //   SplitReduce  one query image: the K split's reduction and the rank select in ONE launch (l0_reduce_rank_kernel)
@@ -546,7 +568,7 @@ static ChunkPath chunk_path(const segvlad_ctx* ctx, const SearchPlan& p, const S
   else
     c.l0 = Level0::ExactGemm;
   // carry: the stride-16 level's filter has already evaluated 1/16 of the rows with the arithmetic of the last level; its
-  // survivors under the NEXT threshold stay in the lists (select mode 2).  Guessed thresholds only (every level collects under
+  // survivors under the NEXT threshold stay in the lists (SvSelect::Carry).  Guessed thresholds only (every level collects under
   // thr + 2 eps there, so the kept set is exactly what the last level would append).
   c.n_comp = p.n - (p.n + SV_RATIO - 1) / SV_RATIO;
   c.carry = f16_guess && s.levels >= 2 && s.ratio_last == SV_RATIO && batch && c.n_comp < 0x7fffffffLL &&
@@ -618,16 +640,21 @@ static int level0(segvlad_ctx* ctx, const SearchPlan& p, const Schedule& s, cons
   }
   StageScope sc(ctx, "knn_select");
   if (fused) return SEGVLAD_OK;   // (thr[q] is in place)
-  if (cp.l0 == Level0::FilterLists) {
-    SV_TRY(sv_launch_select_approx(ctx, ctx->s_cand_cnt.as<uint32_t>(), ctx->s_cand_d2.as<float>(), ctx->s_cand_id.as<uint32_t>(), m,
-                                   SV_CAP, r0, 0, 1, nullptr, 0, c.qn, v.c_eps, v.rn_max, thr, ctx->s_ref_cnt.as<uint32_t>(),
-                                   ctx->s_ref_id.as<uint32_t>(), SV_RCAP, c.flags(), c.fb->count()));
-  } else if (cp.short_sample) {
-    // a short sample row: only its r0-th smallest distance is needed -- the wave-per-query register select of the candidate
-    // lists (mode 0: thr[q] = rank-th smallest), the distance block standing in for a list of n0 entries
-    SV_TRY(sv_launch_select_approx(ctx, ctx->s_cand_cnt.as<uint32_t>(), ctx->s_dist.as<float>(), ctx->s_cand_id.as<uint32_t>(), m,
-                                   (int)cp.ld0, r0, 0, 0, nullptr, 0, c.qn, v.c_eps, v.rn_max, thr, ctx->s_ref_cnt.as<uint32_t>(),
-                                   ctx->s_ref_id.as<uint32_t>(), SV_RCAP, c.flags(), c.fb->count(), nullptr, nullptr, nullptr, (int)cp.n0));
+  if (cp.l0 == Level0::FilterLists || cp.short_sample) {
+    SvSelectArgs a = select_args(ctx, c, v);
+    a.mode = SvSelect::Threshold;
+    a.k = r0;
+    a.thr_out = thr;
+    if (cp.l0 == Level0::FilterLists) {
+      a.check = 1;
+    } else {
+      // a short sample row: only its r0-th smallest distance is needed -- the wave-per-query register select of the candidate
+      // lists, the distance block standing in for a list of n0 entries
+      a.cd2 = ctx->s_dist.as<float>();
+      a.cap = (int)cp.ld0;
+      a.fixed_cnt = (int)cp.n0;
+    }
+    SV_TRY(sv_launch_select_approx(ctx, m, a));
   } else {
     SV_TRY(sv_launch_select_topk(ctx, ctx->s_dist.as<float>(), cp.ld0, m, cp.n0, r0, thr, ctx->s_thr_idx.as<int64_t>(), r0, 0));
   }
@@ -696,10 +723,14 @@ static int filter_levels(segvlad_ctx* ctx, const SearchPlan& p, const Schedule& 
     }
     if (last) break;
     StageScope sc(ctx, "knn_select");
-    SV_TRY(sv_launch_select_approx(ctx, cand_cnt, cand_d2, cand_id, m, SV_CAP, s.rank[lv], (cp.carry && lv + 1 == s.levels) ? 2 : 0,
-                                   s.guessed ? 1 : 0, t.p, t.ld, c.qn, v.c_eps, v.rn_max, thr, ctx->s_ref_cnt.as<uint32_t>(),
-                                   ctx->s_ref_id.as<uint32_t>(), SV_RCAP, c.flags(), c.fb->count(), c.fb->tier2(), c.fb->count() + 1,
-                                   ctx->s_ref_lim.as<float>()));
+    SvSelectArgs a = select_args(ctx, c, v);
+    a.mode = (cp.carry && lv + 1 == s.levels) ? SvSelect::Carry : SvSelect::Threshold;
+    a.k = s.rank[lv];
+    a.check = s.guessed ? 1 : 0;
+    a.thr_in = t.p;
+    a.thr_in_ld = t.ld;
+    a.thr_out = thr;
+    SV_TRY(sv_launch_select_approx(ctx, m, a));
     sc.count();
   }
   return SEGVLAD_OK;
@@ -722,9 +753,14 @@ static int finish(segvlad_ctx* ctx, const SearchPlan& p, const Schedule& s, cons
   bool tail_fused = false;                // the refinement kernel finished the flagged rows itself (no small_tail_kernel)
   {
     StageScope sc(ctx, "knn_select");
-    SV_TRY(sv_launch_select_approx(ctx, cand_cnt, cand_d2, cand_id, m, SV_CAP, k, 1, s.guessed ? 1 : 0, t.p, t.ld, c.qn, v.c_eps, v.rn_max,
-                                   ctx->s_thr_d2.as<float>(), ctx->s_ref_cnt.as<uint32_t>(), ctx->s_ref_id.as<uint32_t>(), SV_RCAP,
-                                   c.flags(), fb.count(), tier2, fb.count() + 1, ref_lim));
+    SvSelectArgs a = select_args(ctx, c, v);
+    a.mode = SvSelect::Band;
+    a.k = k;
+    a.check = s.guessed ? 1 : 0;
+    a.thr_in = t.p;
+    a.thr_in_ld = t.ld;
+    a.thr_out = ctx->s_thr_d2.as<float>();
+    SV_TRY(sv_launch_select_approx(ctx, m, a));
     sc.count();
     if (cp.grouped) {
       // batches: bands of 32 consecutive query rows (the segments of an image) over the union of their rows where they

@@ -9,38 +9,7 @@
 // them.  Ties are resolved towards the lower index, like a stable argsort.
 #include "ctx.h"
 #include "knn_dev.h"
-
-// wave-aggregated histogram increment: lanes that share a bin elect one leader per round
-__device__ __forceinline__ void hist_add(uint32_t* hist, bool active, uint32_t bin) {
-  uint64_t todo = __ballot(active);
-  while (todo) {
-    const int leader = __ffsll((unsigned long long)todo) - 1;
-    const uint32_t lb = __shfl(bin, leader);
-    const uint64_t same = __ballot(active && bin == lb) & todo;
-    if ((int)(threadIdx.x & 63) == leader) atomicAdd(&hist[lb], (uint32_t)__popcll(same));
-    todo &= ~same;
-  }
-}
-
-template <class T>
-__device__ __forceinline__ void bitonic_sort_lds(T* a, int n /*pow2*/, int tid, int nthreads) {
-  for (int size = 2; size <= n; size <<= 1) {
-    for (int stride = size >> 1; stride > 0; stride >>= 1) {
-      __syncthreads();
-      for (int t = tid; t < (n >> 1); t += nthreads) {
-        const int lo = 2 * t - (t & (stride - 1));
-        const int hi = lo + stride;
-        const bool up = ((lo & size) == 0);
-        const T x = a[lo], y = a[hi];
-        if ((y < x) == up) {
-          a[lo] = y;
-          a[hi] = x;
-        }
-      }
-    }
-  }
-  __syncthreads();
-}
+#include "select_dev.h"
 
 // STAGED: the row (n <= 12288 distances: the sampled level of the large-database search) is converted to keys once
 // and kept in LDS, so the four radix passes and the collection pass do not go back to L2/HBM
@@ -52,8 +21,7 @@ __global__ __launch_bounds__(256) void select_topk_kernel(const float* __restric
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   uint64_t* cand = reinterpret_cast<uint64_t*>(smem);  // [kpad]
   uint32_t* skey = reinterpret_cast<uint32_t*>(cand + kpad);  // [n] when STAGED
-  __shared__ uint32_t hist[256];
-  __shared__ uint32_t s_digit, s_krem, s_ceq, s_nless, s_neq;
+  __shared__ uint32_t s_nless, s_neq;
   __shared__ uint32_t wcnt[4];
   const int tid = threadIdx.x;
   const int64_t row = blockIdx.x;
@@ -65,42 +33,9 @@ __global__ __launch_bounds__(256) void select_topk_kernel(const float* __restric
   }
   auto key_at = [&](int64_t j) -> uint32_t { return STAGED ? skey[j] : f2key_(x[j]); };
 
-  uint32_t prefix = 0, mask = 0, krem = (uint32_t)kk, ceq = 0;
-  if (kk > 0) {
-    for (int pass = 3; pass >= 0; --pass) {
-      hist[tid] = 0;
-      __syncthreads();
-      const int shift = 8 * pass;
-      for (int64_t j0 = 0; j0 < n; j0 += 256) {
-        const int64_t j = j0 + tid;
-        bool act = j < n;
-        uint32_t key = act ? key_at(j) : 0u;
-        act = act && ((key & mask) == prefix);
-        hist_add(hist, act, (key >> shift) & 255u);
-      }
-      __syncthreads();
-      if (tid == 0) {
-        uint32_t cum = 0, dsel = 255;
-        for (uint32_t b = 0; b < 256; ++b) {
-          const uint32_t h = hist[b];
-          if (cum + h >= krem) {
-            dsel = b;
-            break;
-          }
-          cum += h;
-        }
-        s_digit = dsel;
-        s_krem = krem - cum;
-        s_ceq = hist[dsel];
-      }
-      __syncthreads();
-      prefix |= s_digit << shift;
-      mask |= 255u << shift;
-      krem = s_krem;
-      ceq = s_ceq;
-      __syncthreads();
-    }
-  }
+  SvRadix8 sel{0u, 0u, 0u};
+  if (kk > 0) sel = sv_radix8_select_(n, (uint32_t)kk, key_at, tid);
+  const uint32_t prefix = sel.prefix, krem = sel.krem, ceq = sel.ceq;
   // prefix = k-th smallest key; krem = how many elements equal to it belong to the top-k; ceq = how many exist
   for (int j = tid; j < kpad; j += 256) cand[j] = ~0ull;
   if (tid == 0) {
@@ -148,7 +83,7 @@ __global__ __launch_bounds__(256) void select_topk_kernel(const float* __restric
     }
   }
   __syncthreads();
-  bitonic_sort_lds(cand, kpad, tid, 256);
+  sv_bitonic(cand, kpad, tid);
   for (int j = tid; j < k; j += 256) {
     float d = INFINITY;
     int64_t id = -1;
@@ -201,7 +136,8 @@ __global__ __launch_bounds__(256) void select_cand_kernel(const uint32_t* __rest
   const uint32_t c = cnt[row];
   if (c > (uint32_t)cap) {
     if (tid == 0) {
-      if (atomicExch(&ovf_rows[row], 1u) == 0u) atomicAdd(ovf_count, 1u);
+      // (this kernel writes a top-k, not a band: of the row rule it shares the flagging alone)
+      sv_flag_once_(ovf_rows, ovf_count, row);
       // this query is redone on the matrix path: a threshold of -inf keeps its list empty at the finer levels
       if (!idx_out) d2_out[row * k + (k - 1)] = -INFINITY;
     }
@@ -212,7 +148,7 @@ __global__ __launch_bounds__(256) void select_cand_kernel(const uint32_t* __rest
   while (npad < (int)c) npad <<= 1;
   for (int j = tid; j < npad; j += 256)
     a[j] = (j < (int)c) ? (((uint64_t)f2key_(cd2[row * cap + j]) << 32) | cid[row * cap + j]) : ~0ull;
-  bitonic_sort_lds(a, npad, tid, 256);
+  sv_bitonic(a, npad, tid);
   for (int j = tid; j < k; j += 256) {
     float d = INFINITY;
     int64_t id = -1;
@@ -312,7 +248,7 @@ __global__ __launch_bounds__(256) void merge_topk_kernel(const float* __restrict
       return;
     }
   }
-  bitonic_sort_lds(a, cpad, tid, 256);
+  sv_bitonic(a, cpad, tid);
   for (int j = tid; j < k; j += 256) {
     float d = INFINITY;
     int64_t id = -1;

@@ -728,7 +728,7 @@ __global__ void small_tail_debug_kernel(int bits, int m, uint32_t* fail_rows, ui
                                         uint32_t* tick, int tick_poison) {
   const int row = threadIdx.x;
   if (row >= m) return;
-  if ((bits & 1) && atomicExch(&fail_rows[row], 1u) == 0u) atomicAdd(&fail_count[0], 1u);
+  if (bits & 1) sv_flag_once_(fail_rows, fail_count, row);
   if ((bits & 2) && !rovf_rows[row] && !(bits & 1)) {   // the whole candidate list as the band: a superset, same top k
     rovf_rows[row] = 1u;
     ref_lim[row] = INFINITY;
@@ -736,7 +736,7 @@ __global__ void small_tail_debug_kernel(int bits, int m, uint32_t* fail_rows, ui
   }
   if ((bits & 4) && row == 0 && tick) {
     tick[tick_poison] = 1u;
-    if (atomicExch(&fail_rows[0], 1u) == 0u) atomicAdd(&fail_count[0], 1u);
+    sv_flag_once_(fail_rows, fail_count, 0);
   }
 }
 

@@ -14,31 +14,13 @@
 // on one place has runs of hundreds of entries: the sequential walk was 0.3 of the kernel's 0.43 ms on the bench).  A run
 // holding any other weight (or a NaN) is poisoned and summed sequentially as before.  Same bits either way.
 #include "ctx.h"
+#include "knn_dev.h"
 
 struct Run {
   double score;
   uint32_t first;  // visiting order of the first appearance
   int32_t img;
 };
-
-__device__ __forceinline__ void bitonic_u64(uint64_t* a, int n, int tid, int nthreads) {
-  for (int size = 2; size <= n; size <<= 1) {
-    for (int stride = size >> 1; stride > 0; stride >>= 1) {
-      __syncthreads();
-      for (int t = tid; t < (n >> 1); t += nthreads) {
-        const int lo = 2 * t - (t & (stride - 1));
-        const int hi = lo + stride;
-        const bool up = ((lo & size) == 0);
-        const uint64_t x = a[lo], y = a[hi];
-        if ((y < x) == up) {
-          a[lo] = y;
-          a[hi] = x;
-        }
-      }
-    }
-  }
-  __syncthreads();
-}
 
 // better(a, b): a ranks before b
 __device__ __forceinline__ bool better(double sa, uint32_t ta, double sb, uint32_t tb) {
@@ -87,7 +69,7 @@ __global__ __launch_bounds__(VOTE_THREADS) void vote_kernel(const int64_t* __res
     keys[o] = key;
   }
   if (tid == 0) s_nruns = 0;
-  bitonic_u64(keys, Epad, tid, VOTE_THREADS);
+  sv_bitonic<uint64_t, VOTE_THREADS>(keys, Epad, tid);
 
   // the weights of the sorted entries, in parallel (the fp64 run sums below must stay sequential to reproduce the
   // reference's order of additions; fetching sims[] inside that serial walk was one exposed global load per entry)

@@ -2,7 +2,7 @@
  * segvlad.h -- C-ABI of the MI355X-native SegVLAD hot path (libsegvlad_hip.so, gfx950).
  *
  * The reference (AnyLoc/Revisit-Anything, all Python) exposes no FFI; the boundary it offers is
- * the function surface of func_vpr.py / place_rec_main.py.  Each of the 56 entry points below replaces the
+ * the function surface of func_vpr.py / place_rec_main.py.  Each of the 57 entry points below replaces the
  * cited reference function(s); the Python module revisit_anything_amd.func_vpr maps the reference's
  * names/arguments onto these calls (INTEGRATION.md shows the ctypes stub a maintainer would add).
  *
@@ -98,6 +98,35 @@ int segvlad_incidence_rle(segvlad_ctx* ctx, const uint32_t* counts, const int64_
  *      and for masks above segvlad_incidence_rle's bound.                                                                  */
 int segvlad_rle_decode(segvlad_ctx* ctx, const uint32_t* counts, const int64_t* run_offsets, int S, int Hm, int Wm, uint8_t* masks_out,
                        uint32_t* n_bad_out);
+
+/*      mask_to_rle_pytorch for the batch (amg.py:107-135), with area_from_rle's areas: dense masks -> the layout above, on the device.
+ *      masks [S][Hm][Wm] uint8, row-major, device or host; a NON-ZERO byte is a set pixel (as in segvlad_incidence); any alignment,
+ *      any Wm.  The runs are exactly the reference's counts: the mask is read column-major (pixel p = col * Hm + row), the runs
+ *      alternate zeros / ones and start with zeros; the first count is 0 exactly when pixel 0 is set and no other count is 0; a mask
+ *      with n value changes has n + 1 runs, plus one more if pixel 0 is set; an all-zero mask is [P], an all-ones mask [0, P]
+ *      (P = Hm * Wm).
+ *      run_offsets_out [S + 1] int64, device or host, required: always written, always the true counts; run_offsets[0] = 0 and
+ *      mask s owns counts[run_offsets[s] .. run_offsets[s + 1]).  n_runs_out (HOST, may be NULL) = run_offsets[S].
+ *      counts_out holds `capacity` uint32 slots, device or host (may be NULL when capacity == 0: a count-only call).  When
+ *      run_offsets[S] <= capacity it receives the runs.  When run_offsets[S] > capacity it is NOT WRITTEN AT ALL, the call still
+ *      returns SEGVLAD_OK, and the caller allocates run_offsets[S] slots and calls again (the protocol of segvlad_range_search).
+ *      Slots at and beyond run_offsets[S] are never written.
+ *      area_out [S] int64, device or host, may be NULL: the set pixels of each mask = the sum of its odd-indexed runs
+ *      (area_from_rle).
+ *      Synchronisation: none when every output is device memory and n_runs_out is NULL -- the emitting kernel reads the total from
+ *      device memory and leaves, every thread alike, when it exceeds `capacity`.  Otherwise once; a host counts_out is filled by
+ *      a blocking copy behind that wait, and only when the total fits (the total is read first: a host array that is too small
+ *      stays untouched).
+ *      S == 0: OK; run_offsets_out[0] = 0 and *n_runs_out = 0 are written, nothing else.  SEGVLAD_ERR_ARG: S < 0, Hm <= 0, Wm <= 0,
+ *      capacity < 0, a NULL run_offsets_out, a NULL masks with S > 0, a NULL counts_out with capacity > 0.  SEGVLAD_ERR_LIMIT:
+ *      Hm * Wm > 2^32 - 1 (a run is a 32-bit count), decided before any pointer is looked at.  SEGVLAD_ERR_STATE while a
+ *      segvlad_describe_begin is open.  No mask is held in LDS: no other size bound (segvlad_incidence_rle's 150 KiB does not
+ *      apply).  Deterministic: two calls return the same bytes.  Stage timer "rle_encode".
+ *      How: a unit is one (mask, column, block of 256 rows); pass 1 counts every unit's value changes, a scan per mask ranks them
+ *      and carries the last change along the column-major order, pass 2 reads the bytes again and stores each change's distance
+ *      to the one before it (csrc/rle_encode_kernels.hip).                                                                     */
+int segvlad_rle_encode(segvlad_ctx* ctx, const uint8_t* masks, int S, int Hm, int Wm, int64_t* run_offsets_out, uint32_t* counts_out,
+                       int64_t capacity, int64_t* area_out, int64_t* n_runs_out);
 
 /* ---- neighbourhood adjacency for a batch: getNbrsDelaunay + nbrMasksAGGFastSingle
  *      func_vpr.py:1241-1245, 1315-1345.  centroids [S_tot][2] fp64 (x, y) from segvlad_mask_centroids,
@@ -528,7 +557,7 @@ int segvlad_vote(segvlad_ctx* ctx, const int64_t* idx, const float* sims, const 
                  int32_t* pred_out, double* score_out);
 
 /* ---- instrumentation: with profiling on, every kernel group of a stage ("incidence", "adjacency",
- *      "assign", "prep", "aggregate", "pca", "describe" (segvlad_describe as a whole: its parts overlap), "knn_level0", "knn_gemm", "knn_select", "knn_fallback", "knn_shortlist" (segvlad_search_shortlist), "knn_exclude" (the kernels segvlad_search_excluding adds to its inner search), "knn_group" (the kernels segvlad_search_grouped adds to its inner search), "knn_range" (the kernels of segvlad_range_search), "match_pairs" (segvlad_match_pairs), "verify_pairs" (segvlad_verify_pairs), "sequence_rerank" (segvlad_sequence_rerank), "db_remove" (segvlad_db_remove), "vote") is bracketed by a HIP event pair
+ *      "assign", "prep", "aggregate", "pca", "describe" (segvlad_describe as a whole: its parts overlap), "knn_level0", "knn_gemm", "knn_select", "knn_fallback", "knn_shortlist" (segvlad_search_shortlist), "knn_exclude" (the kernels segvlad_search_excluding adds to its inner search), "knn_group" (the kernels segvlad_search_grouped adds to its inner search), "knn_range" (the kernels of segvlad_range_search), "match_pairs" (segvlad_match_pairs), "verify_pairs" (segvlad_verify_pairs), "sequence_rerank" (segvlad_sequence_rerank), "incidence_rle", "rle_decode", "rle_encode" (the run-length entries), "db_remove" (segvlad_db_remove), "vote") is bracketed by a HIP event pair
  *      on the context stream.  segvlad_stage_ms returns the SUM of the elapsed times (ms) and the number
  *      of kernel launches recorded for the stage since the last segvlad_profile_reset; it returns
  *      SEGVLAD_ERR_STATE if the stage has not run.  Replaces the (discarded) time.time() pair of

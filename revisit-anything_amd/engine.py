@@ -13,7 +13,7 @@ import torch
 
 from . import _lib
 from ._lib import SegVLADDegenerateError, SegVLADError
-from .rle import RLE_CHUNK_RUNS, RleMasks  # noqa: F401  (RLE_CHUNK_RUNS: the kernels' chunk of runs, for callers and tests)
+from .rle import RLE_CHUNK_RUNS, RLE_ENCODE_ROWS, RleMasks  # noqa: F401  (the kernels' chunk of runs and rows of a unit, for callers and tests)
 
 
 def _ptr(x) -> int:
@@ -587,6 +587,50 @@ class SegVLADEngine:
         self._check(self.lib.segvlad_rle_decode(self._h, _ptr(c), _ptr(o), S, Hm, Wm, _ptr(out), _ptr(n_bad)), "rle_decode")
         self._keep = [c, o, n_bad]
         return (out, n_bad) if want_bad else out
+
+    def rle_encode(self, masks, want_area: bool = False, capacity: Optional[int] = None):
+        """segvlad_rle_encode: dense masks -> an ``RleMasks`` batch whose ``counts`` (uint32) and ``run_offsets`` (int64) are
+        device tensors, the counts of ``RleMasks.from_dense(masks)`` (mask_to_rle_pytorch); with ``want_area`` also the set
+        pixels of every mask, ``(rle, areas)`` with ``areas`` int64 [S] on the device (area_from_rle).  ``masks``: [S, Hm, Wm]
+        or one [Hm, Wm], uint8 (non-zero = set) or bool (viewed as bytes, not copied), a torch tensor on the device or the host
+        or a NumPy array; made contiguous when it is not.  The first call offers ``capacity`` slots (default
+        ``S * (2 * Wm + 2)``: a column-convex blob fits); when the runs do not fit it is repeated once with the total it
+        reported (``self.rle_encode_retried``).  Synchronises once: the total has to reach the host to size the result."""
+        if isinstance(masks, torch.Tensor):
+            m = masks.view(torch.uint8) if masks.dtype == torch.bool else masks
+            if m.dtype != torch.uint8:
+                raise TypeError(f"masks must be uint8 or bool, got {masks.dtype}")
+            m = m.contiguous()
+        else:
+            a = np.asarray(masks)
+            a = a.view(np.uint8) if a.dtype == np.bool_ else a
+            if a.dtype != np.uint8:
+                raise TypeError(f"masks must be uint8 or bool, got {a.dtype}")
+            m = np.ascontiguousarray(a)
+        if m.ndim == 2:
+            m = m[None]
+        if m.ndim != 3:
+            raise ValueError(f"masks must be [S, Hm, Wm], got {tuple(m.shape)}")
+        S, Hm, Wm = (int(v) for v in m.shape)
+        capacity = S * (2 * Wm + 2) if capacity is None else int(capacity)
+        if capacity < 0:
+            raise ValueError("capacity must be >= 0")
+        offs = self._empty((S + 1,), torch.int64)
+        areas = self._empty((S,), torch.int64) if want_area else None
+        total = C.c_int64()
+        self._stream()
+        self.rle_encode_retried = False
+        while True:
+            counts = self._empty((capacity,), torch.uint32)
+            self._check(self.lib.segvlad_rle_encode(self._h, _ptr(m) if S else None, S, Hm, Wm, _ptr(offs), _ptr(counts) if capacity else None,
+                                                    capacity, _ptr(areas) if S and want_area else None, C.byref(total)), "rle_encode")
+            if total.value <= capacity:
+                break
+            capacity = int(total.value)
+            self.rle_encode_retried = True
+        self._keep = [m]
+        rle = RleMasks(counts[:total.value], offs, Hm, Wm, validate=False)
+        return (rle, areas) if want_area else rle
 
     def adjacency(self, centroids, seg_offsets, order: int, check_empty: bool = False) -> torch.Tensor:
         """centroids [S_tot,2] fp64 -> uint8 buffer with the concatenated per-image [S_b,S_b] (A1^order > 0)

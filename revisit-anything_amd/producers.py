@@ -217,15 +217,18 @@ class SamAutoMasks:
     segmentation bool [H, W], area, bbox XYWH, predicted_iou, point_coords, stability_score, crop_box), ordered by
     decreasing predicted IoU (the order batched_nms returns).  ``output_mode="uncompressed_rle"`` puts SAM's run-length dict
     ``{"size": [H, W], "counts": [...]}`` (mask_to_rle_pytorch, utils/amg.py:107-135) under ``segmentation`` instead of the bool
-    array; ``rle.RleMasks.from_sam(records)`` takes such records to the device as they are."""
+    array; ``rle.RleMasks.from_sam(records)`` takes such records to the device as they are.  ``rle_engine`` (a SegVLADEngine, in
+    that mode): the kept masks stay on the device and ``rle_engine.rle_encode`` makes their runs and areas there -- only those are
+    read back, and the records are the ones the host path makes."""
 
     def __init__(self, model, points_per_side: int = 32, points_per_batch: int = 64, pred_iou_thresh: float = 0.88,
                  stability_score_thresh: float = 0.95, stability_score_offset: float = 1.0, box_nms_thresh: float = 0.7,
                  min_mask_region_area: int = 0, mask_threshold: float = 0.0, device: Union[str, torch.device] = "cpu",
-                 output_mode: str = "binary_mask"):
+                 output_mode: str = "binary_mask", rle_engine=None):
         if output_mode not in OUTPUT_MODES:   # (the reference's third mode, coco_rle, needs pycocotools: not offered)
             raise ValueError(f"output_mode must be one of {OUTPUT_MODES}, got {output_mode!r}")
         self.output_mode = output_mode
+        self.rle_engine = rle_engine
         self.device = torch.device(device)
         self.model = model.eval().to(self.device)
         self.img_size = int(self.model.config.vision_config.image_size)
@@ -326,13 +329,21 @@ class SamAutoMasks:
         boxes = mask_boxes(masks)
         keep = box_nms(boxes, ious, self.box_nms_thresh)                                   # _process_crop: NMS by predicted IoU
         kc = keep.cpu()
-        masks, ious, stab, pts, boxes = masks[keep].cpu().numpy(), ious[keep].cpu(), stab[keep].cpu(), pts[kc], boxes[keep].cpu()
         # output_mode (automatic_mask_generator.py:150-168): the dense mask, or mask_to_rle_pytorch's dict (utils/amg.py:107-135)
         rle_mode = getattr(self, "output_mode", "binary_mask") == "uncompressed_rle"
-        segs = RleMasks.from_dense(masks).to_sam() if rle_mode and masks.shape[0] else masks
+        engine = getattr(self, "rle_engine", None) if rle_mode else None
+        ious, stab, pts, boxes = ious[keep].cpu(), stab[keep].cpu(), pts[kc], boxes[keep].cpu()
+        if engine is not None and len(kc):
+            # the masks stay where they are: runs and areas (area_from_rle) from the device encoder, and only those come back
+            rle, areas = engine.rle_encode(masks[keep], want_area=True)
+            segs, areas = rle.to_sam(), areas.cpu().tolist()
+        else:
+            masks = masks[keep].cpu().numpy()
+            segs = RleMasks.from_dense(masks).to_sam() if rle_mode and masks.shape[0] else masks
+            areas = [int(masks[j].sum()) for j in range(masks.shape[0])]
         recs = []
-        for j in range(masks.shape[0]):
-            area = int(masks[j].sum())
+        for j in range(len(areas)):
+            area = int(areas[j])
             if area > self.min_mask_region_area:
                 x0, y0, x1, y1 = (int(v) for v in boxes[j])
                 recs.append({"segmentation": segs[j], "area": area, "bbox": [x0, y0, x1 - x0, y1 - y0],

@@ -9,8 +9,11 @@ here is the records of S masks of ONE size, concatenated:
     run_offsets  int64  [S + 1]    mask s owns counts[run_offsets[s] : run_offsets[s + 1]]
     Hm, Wm                         the masks' size
 
-Out of scope: COCO's compressed string form of the counts (``coco_rle``), and encoding dense masks that live on the device
-(``from_dense`` runs on the host)."""
+Dense masks become a batch in two places: ``RleMasks.from_dense`` on the host (NumPy; a device tensor is copied to the host
+first and the result is host arrays), and ``SegVLADEngine.rle_encode`` on the device (segvlad_rle_encode,
+csrc/rle_encode_kernels.hip: device tensors in, device tensors out, the same counts).  ``areas()`` is ``area_from_rle``.
+
+Out of scope: COCO's compressed string form of the counts (``coco_rle``)."""
 from __future__ import annotations
 
 from typing import Mapping, Optional, Sequence
@@ -19,6 +22,7 @@ import numpy as np
 import torch
 
 RLE_CHUNK_RUNS = 512   # runs per step of the kernels' run walk (csrc/rle_kernels.hip: RLE_CHUNK)
+RLE_ENCODE_ROWS = 256  # rows of one unit of the device encoder (csrc/rle_encode_kernels.hip: RLE_ENCODE_ROWS)
 
 
 def _host(x, dtype) -> np.ndarray:
@@ -181,6 +185,13 @@ class RleMasks:
         if flat.size != self.Hm * self.Wm:
             raise ValueError(f"mask {j}: the counts do not cover the mask")
         return flat.reshape(self.Wm, self.Hm).transpose()
+
+    def areas(self) -> np.ndarray:
+        """Set pixels of every mask, int64 [S] on the host: the sum of its odd-indexed runs (area_from_rle, utils/amg.py)"""
+        c, o = _host(self.counts, np.uint32), _host(self.run_offsets, np.int64)
+        odd = ((np.arange(len(c), dtype=np.int64) - np.repeat(o[:-1], np.diff(o))) & 1).astype(bool)
+        cs = np.concatenate([[0], np.cumsum(np.where(odd, c, 0), dtype=np.int64)])
+        return (cs[o[1:]] - cs[o[:-1]]).astype(np.int64)
 
     def to_sam(self) -> list:
         """One ``{"size": [Hm, Wm], "counts": [...]}`` per mask"""

@@ -2,7 +2,7 @@
  * segvlad.h -- C-ABI of the MI355X-native SegVLAD hot path (libsegvlad_hip.so, gfx950).
  *
  * The reference (AnyLoc/Revisit-Anything, all Python) exposes no FFI; the boundary it offers is
- * the function surface of func_vpr.py / place_rec_main.py.  Each of the 57 entry points below replaces the
+ * the function surface of func_vpr.py / place_rec_main.py.  Each of the 58 entry points below replaces the
  * cited reference function(s); the Python module revisit_anything_amd.func_vpr maps the reference's
  * names/arguments onto these calls (INTEGRATION.md shows the ctypes stub a maintainer would add).
  *
@@ -127,6 +127,40 @@ int segvlad_rle_decode(segvlad_ctx* ctx, const uint32_t* counts, const int64_t* 
  *      to the one before it (csrc/rle_encode_kernels.hip).                                                                     */
 int segvlad_rle_encode(segvlad_ctx* ctx, const uint8_t* masks, int S, int Hm, int Wm, int64_t* run_offsets_out, uint32_t* counts_out,
                        int64_t capacity, int64_t* area_out, int64_t* n_runs_out);
+
+/*      remove_small_regions for the batch, mode "holes" and then mode "islands" (amg.py:267-291): the cleaning step of
+ *      SamAutomaticMaskGenerator.postprocess_small_regions (automatic_mask_generator.py:325-376; its scoring and second box NMS stay
+ *      with the caller).  The reference labels every mask twice with OpenCV on the host; this labels the whole batch on the device.
+ *      masks, masks_out [S][Hm][Wm] uint8, row-major, device or host, any alignment; a NON-ZERO byte is a set pixel and the bytes
+ *      written are 0 / 1.  For every mask, in this order:
+ *        1. holes: the 8-connected components of the COMPLEMENT are labelled; every component with fewer than min_area pixels
+ *           becomes set -- the outer background too when it is that small (the reference does not treat it specially).  The pass
+ *           CHANGED the mask iff such a component exists.
+ *        2. islands, on the result of 1: the 8-connected components of the mask are labelled; if none has fewer than min_area
+ *           pixels the mask is unchanged; otherwise exactly the components with area >= min_area are kept, or, when there are
+ *           none of those, the single largest one -- and the pass CHANGED the mask in either case: a mask whose only island is
+ *           small comes back identical and flagged changed, as from the reference, whose caller turns the flag into the NMS score.
+ *      The comparison is strictly <.  A complement without pixels (1.) and a mask without pixels (2.) have no components and are
+ *      unchanged.  Tie for "largest": the reference takes argmax over OpenCV's label order; here the tie goes to THE COMPONENT WHOSE
+ *      FIRST PIXEL IN ROW-MAJOR ORDER COMES FIRST, which is scipy.ndimage.label's numbering.  OpenCV's numbering under such a tie
+ *      has not been checked (a known possible divergence).
+ *      changed_out [S] int32: bit 0 = the holes pass changed the mask, bit 1 = the islands pass did.  boxes_out [S][4] int32: the
+ *      tight XYXY box of the result in inclusive pixel coordinates, [0, 0, 0, 0] for an empty result (batched_mask_to_box).
+ *      area_out [S] int64: the set pixels of the result.  Each device or host; each may be NULL.
+ *      masks_out == masks is allowed (in place); any other overlap of the two is SEGVLAD_ERR_ARG.
+ *      S == 0: OK, nothing is written.  min_area <= 1 changes nothing: the masks are copied (as 0 / 1), boxes and areas are
+ *      computed, the flags are 0.  SEGVLAD_ERR_ARG: S < 0, Hm <= 0, Wm <= 0, min_area < 0, a NULL masks or masks_out with S > 0.
+ *      SEGVLAD_ERR_LIMIT: Hm * Wm > 2^31 - 1 (a label is a 32-bit pixel index), decided before any pointer is looked at.
+ *      SEGVLAD_ERR_STATE while a segvlad_describe_begin is open.  No mask is held whole in LDS: no other size bound.  Scratch: 8
+ *      bytes per pixel of the batch (callers with many masks call in pieces; SegVLADEngine.mask_regions does).
+ *      Synchronisation: none when every pointer is device memory; otherwise once.  Deterministic: all sums are integers and all
+ *      roots are minima, two calls write the same bytes.  Stage timer "mask_regions".
+ *      How: per pass a label plane int32 [S][Hm * Wm] (a pixel index inside the mask; union-find, the root is the component's
+ *      first pixel): a union-find per 32 x 32 tile in LDS, the tile edges (both diagonals at every corner) united with agent-scope
+ *      atomicMin, labels flattened and sizes summed with one atomic per (tile, tile-local component), one packed 64-bit maximum of
+ *      (area, ~root) per mask, one rewrite of the pixels (csrc/regions_kernels.hip).                                            */
+int segvlad_mask_regions(segvlad_ctx* ctx, const uint8_t* masks, int S, int Hm, int Wm, int min_area, uint8_t* masks_out,
+                         int32_t* changed_out, int32_t* boxes_out, int64_t* area_out);
 
 /* ---- neighbourhood adjacency for a batch: getNbrsDelaunay + nbrMasksAGGFastSingle
  *      func_vpr.py:1241-1245, 1315-1345.  centroids [S_tot][2] fp64 (x, y) from segvlad_mask_centroids,
@@ -557,7 +591,7 @@ int segvlad_vote(segvlad_ctx* ctx, const int64_t* idx, const float* sims, const 
                  int32_t* pred_out, double* score_out);
 
 /* ---- instrumentation: with profiling on, every kernel group of a stage ("incidence", "adjacency",
- *      "assign", "prep", "aggregate", "pca", "describe" (segvlad_describe as a whole: its parts overlap), "knn_level0", "knn_gemm", "knn_select", "knn_fallback", "knn_shortlist" (segvlad_search_shortlist), "knn_exclude" (the kernels segvlad_search_excluding adds to its inner search), "knn_group" (the kernels segvlad_search_grouped adds to its inner search), "knn_range" (the kernels of segvlad_range_search), "match_pairs" (segvlad_match_pairs), "verify_pairs" (segvlad_verify_pairs), "sequence_rerank" (segvlad_sequence_rerank), "incidence_rle", "rle_decode", "rle_encode" (the run-length entries), "db_remove" (segvlad_db_remove), "vote") is bracketed by a HIP event pair
+ *      "assign", "prep", "aggregate", "pca", "describe" (segvlad_describe as a whole: its parts overlap), "knn_level0", "knn_gemm", "knn_select", "knn_fallback", "knn_shortlist" (segvlad_search_shortlist), "knn_exclude" (the kernels segvlad_search_excluding adds to its inner search), "knn_group" (the kernels segvlad_search_grouped adds to its inner search), "knn_range" (the kernels of segvlad_range_search), "match_pairs" (segvlad_match_pairs), "verify_pairs" (segvlad_verify_pairs), "sequence_rerank" (segvlad_sequence_rerank), "incidence_rle", "rle_decode", "rle_encode" (the run-length entries), "mask_regions" (segvlad_mask_regions), "db_remove" (segvlad_db_remove), "vote") is bracketed by a HIP event pair
  *      on the context stream.  segvlad_stage_ms returns the SUM of the elapsed times (ms) and the number
  *      of kernel launches recorded for the stage since the last segvlad_profile_reset; it returns
  *      SEGVLAD_ERR_STATE if the stage has not run.  Replaces the (discarded) time.time() pair of

@@ -362,7 +362,9 @@ struct segvlad_ctx {
   //  s_gr_*: segvlad_search_grouped (group_kernels.hip) -- the counters + row flags, and the exact tail's open
   //  rows, their dense query block, a batch's slots / word offsets, cursors, words before and after their ordering, per-image counts;
   //  s_re_*: segvlad_rle_encode (rle_encode_kernels.hip) -- the units' (changes, last change, set pixels) planes, the masks' run
-  //  counts and final runs, and the device image of a host caller's counts
+  //  counts and final runs, and the device image of a host caller's counts;
+  //  s_rg_*: segvlad_mask_regions (regions_kernels.hip) -- the label plane and the size plane [S][P] of a connected-component pass
+  //  and the masks' decisions, areas and boxes
 #define SV_SCRATCH_BUFS(X)                                                                                                       \
   X(s_xt) X(s_labels) X(s_rnorm) X(s_gap) X(s_colmask) X(s_gscale) X(s_segimg) X(s_segoff) X(s_adjoff) X(s_dist) X(s_qnorm)      \
   X(s_misc) X(s_minmax) X(s_voteoff) X(s_cand_cnt) X(s_cand_d2) X(s_cand_id) X(s_thr_d2) X(s_thr_idx) X(s_flag) X(s_qh) X(s_ql)  \
@@ -377,7 +379,8 @@ struct segvlad_ctx {
   X(s_rs_tmp) X(s_rs_rows) X(s_rs_q) X(s_rs_misc)                                                                                 \
   X(s_mp_min) X(s_vp_best) X(s_sq_id) X(s_sq_sc)                                                                                   \
   X(s_gr_flag) X(s_gr_rows) X(s_gr_q) X(s_gr_plan) X(s_gr_cur) X(s_gr_words) X(s_gr_sorted) X(s_gr_tab)                           \
-  X(s_re_unit) X(s_re_mask) X(s_re_counts)
+  X(s_re_unit) X(s_re_mask) X(s_re_counts)                                                                                        \
+  X(s_rg_label) X(s_rg_size) X(s_rg_state)
 #define SV_DECL_BUF(n) DevBuf n;
   SV_PERSISTENT_BUFS(SV_DECL_BUF)
   SV_SCRATCH_BUFS(SV_DECL_BUF)
@@ -440,7 +443,7 @@ void sv_begin(segvlad_ctx* ctx);
 // Between segvlad_describe_begin and segvlad_describe_end the context's per-batch scratch (segment / adjacency offsets, the
 // token-major copy, the labels) belongs to THAT batch, and the mask branch is in flight on the side stream: every other entry
 // point that would write them refuses instead of describing a different batch with the open one's offsets.
-// (describe.hip's mask entries, rle_kernels.hip's and rle_encode_kernels.hip's)
+// (describe.hip's mask entries, rle_kernels.hip's, rle_encode_kernels.hip's and regions_kernels.hip's)
 #define CHECK_NO_OPEN_DESCRIBE(what)                                                                                        \
   if (ctx->desc.open)                                                                                                       \
   return ctx->fail(SEGVLAD_ERR_STATE, what ": a segvlad_describe_begin is open on this context (call segvlad_describe_end first)")

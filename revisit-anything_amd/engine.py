@@ -632,6 +632,58 @@ class SegVLADEngine:
         rle = RleMasks(counts[:total.value], offs, Hm, Wm, validate=False)
         return (rle, areas) if want_area else rle
 
+    MASK_REGIONS_SCRATCH_BYTES = 1 << 30   # mask_regions: the label and size planes of one call, 8 bytes per pixel, stay below this
+
+    def mask_regions(self, masks, min_area: int, want_boxes: bool = True, want_area: bool = True, chunk: Optional[int] = None) -> dict:
+        """segvlad_mask_regions: small holes filled and small islands removed from every mask (remove_small_regions, mode
+        "holes" then mode "islands", utils/amg.py:267-291; 8-connected, strictly ``< min_area``, keep-largest with the tie to
+        the component whose first pixel comes first).  ``masks``: [S, Hm, Wm] or one [Hm, Wm], uint8 (non-zero = set) or bool,
+        a torch tensor on the device or the host or a NumPy array; made contiguous when it is not.  Returns device tensors:
+        ``masks`` uint8 [S, Hm, Wm] of 0 / 1, ``changed`` int32 [S] (bit 0: the holes pass changed the mask, bit 1: the islands
+        pass), and with ``want_boxes`` / ``want_area`` ``boxes`` int32 [S, 4] (tight XYXY, inclusive, zeros for an empty mask:
+        ``producers.mask_boxes``) and ``area`` int64 [S].  The batch is processed ``chunk`` masks per call; by default as many as
+        keep the call's scratch, 8 bytes per pixel, under ``MASK_REGIONS_SCRATCH_BYTES`` (1 GiB).  Does not synchronise when
+        ``masks`` is on the device."""
+        if isinstance(masks, torch.Tensor):
+            m = masks.view(torch.uint8) if masks.dtype == torch.bool else masks
+            if m.dtype != torch.uint8:
+                raise TypeError(f"masks must be uint8 or bool, got {masks.dtype}")
+            m = m.contiguous()
+        else:
+            a = np.asarray(masks)
+            a = a.view(np.uint8) if a.dtype == np.bool_ else a
+            if a.dtype != np.uint8:
+                raise TypeError(f"masks must be uint8 or bool, got {a.dtype}")
+            m = np.ascontiguousarray(a)
+        if m.ndim == 2:
+            m = m[None]
+        if m.ndim != 3:
+            raise ValueError(f"masks must be [S, Hm, Wm], got {tuple(m.shape)}")
+        S, Hm, Wm = (int(v) for v in m.shape)
+        min_area = int(min_area)
+        if chunk is None:
+            chunk = max(1, self.MASK_REGIONS_SCRATCH_BYTES // (8 * max(1, Hm * Wm)))
+        chunk = int(chunk)
+        if chunk < 1:
+            raise ValueError("chunk must be >= 1")
+        out = self._empty((S, Hm, Wm), torch.uint8)
+        changed = self._empty((S,), torch.int32)
+        boxes = self._empty((S, 4), torch.int32) if want_boxes else None
+        area = self._empty((S,), torch.int64) if want_area else None
+        self._stream()
+        for s0 in range(0, max(S, 1), chunk):   # (S == 0: one call, which checks the arguments and writes nothing)
+            n = min(chunk, S - s0)
+            self._check(self.lib.segvlad_mask_regions(self._h, _ptr(m[s0:s0 + n]) if n else None, n, Hm, Wm, min_area, _ptr(out[s0:s0 + n]) if n else None,
+                                                      _ptr(changed[s0:s0 + n]) if n else None, _ptr(boxes[s0:s0 + n]) if n and want_boxes else None,
+                                                      _ptr(area[s0:s0 + n]) if n and want_area else None), "mask_regions")
+        self._keep = [m]
+        res = {"masks": out, "changed": changed}
+        if want_boxes:
+            res["boxes"] = boxes
+        if want_area:
+            res["area"] = area
+        return res
+
     def adjacency(self, centroids, seg_offsets, order: int, check_empty: bool = False) -> torch.Tensor:
         """centroids [S_tot,2] fp64 -> uint8 buffer with the concatenated per-image [S_b,S_b] (A1^order > 0)
         blocks, computed on the device.  check_empty=True synchronises and raises ValueError on an empty mask

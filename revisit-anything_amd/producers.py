@@ -212,6 +212,56 @@ def box_nms(boxes: torch.Tensor, scores: torch.Tensor, iou_threshold: float) -> 
     return order[torch.from_numpy(np.nonzero(keep)[0]).to(order.device)]
 
 
+def _ndimage():
+    try:
+        from scipy import ndimage
+    except ImportError as e:   # (scipy is a host dependency already: Qhull)
+        raise ImportError("remove_small_regions labels connected components with scipy.ndimage.label: scipy is not installed "
+                          "(or give SamAutoMasks a regions_engine to clean the masks on the device)") from e
+    return ndimage
+
+
+def remove_small_regions(mask: np.ndarray, area_thresh: float, mode: str):
+    """utils/amg.py:267-291 on the host, with ``scipy.ndimage.label`` (3 x 3 structure: 8-connected) where the reference calls
+    ``cv2.connectedComponentsWithStats(working_mask, 8)``: ``(mask, changed)``.  mode "holes": every component of the
+    complement with fewer than ``area_thresh`` pixels is filled (the outer background too, when it is that small); mode
+    "islands": when some component is that small, exactly those with ``area >= area_thresh`` are kept, or the largest one when
+    there is none -- and the mask counts as changed in either case.  A tie for the largest goes to the component whose first
+    pixel in row-major order comes first: ``ndimage.label``'s numbering under ``argmax`` (OpenCV's numbering under a tie has not
+    been checked).  An unchanged mask is returned as it came, as by the reference."""
+    if mode not in ("holes", "islands"):
+        raise ValueError(f"mode must be 'holes' or 'islands', got {mode!r}")
+    correct_holes = mode == "holes"
+    working = np.asarray(mask).astype(bool) ^ correct_holes
+    regions, n = _ndimage().label(working, structure=np.ones((3, 3), dtype=np.uint8))
+    sizes = np.bincount(regions.ravel(), minlength=n + 1)[1:]
+    small = np.nonzero(sizes < area_thresh)[0] + 1
+    if len(small) == 0:
+        return mask, False
+    if correct_holes:
+        fill = np.concatenate([[0], small])
+    else:
+        fill = np.nonzero(sizes >= area_thresh)[0] + 1
+        if len(fill) == 0:   # every region is below the threshold: keep the largest
+            fill = np.array([int(np.argmax(sizes)) + 1])
+    return np.isin(regions, fill), True
+
+
+def clean_small_regions(masks: np.ndarray, min_area: int):
+    """The host twin of ``SegVLADEngine.mask_regions``: ``remove_small_regions`` in mode "holes" and then in mode "islands" on
+    every mask of [S, H, W] (non-zero = set): ``(cleaned bool [S, H, W], changed int32 [S])`` with bit 0 = the holes pass
+    changed the mask and bit 1 = the islands pass did (automatic_mask_generator.py:343-349)."""
+    m = np.asarray(masks) != 0
+    out = np.empty(m.shape, dtype=bool)
+    changed = np.zeros(m.shape[0], dtype=np.int32)
+    for j in range(m.shape[0]):
+        a, c0 = remove_small_regions(m[j], min_area, "holes")
+        a, c1 = remove_small_regions(a, min_area, "islands")
+        out[j] = a
+        changed[j] = int(c0) | (int(c1) << 1)
+    return out, changed
+
+
 class SamAutoMasks:
     """``generate(img_rgb uint8 [H, W, 3]) -> list of SAM records`` (keys as automatic_mask_generator.py:150-168:
     segmentation bool [H, W], area, bbox XYWH, predicted_iou, point_coords, stability_score, crop_box), ordered by
@@ -219,16 +269,24 @@ class SamAutoMasks:
     ``{"size": [H, W], "counts": [...]}`` (mask_to_rle_pytorch, utils/amg.py:107-135) under ``segmentation`` instead of the bool
     array; ``rle.RleMasks.from_sam(records)`` takes such records to the device as they are.  ``rle_engine`` (a SegVLADEngine, in
     that mode): the kept masks stay on the device and ``rle_engine.rle_encode`` makes their runs and areas there -- only those are
-    read back, and the records are the ones the host path makes."""
+    read back, and the records are the ones the host path makes.
+
+    ``min_mask_region_area > 0`` runs postprocess_small_regions (automatic_mask_generator.py:165-171, 325-376) on the masks the
+    NMS kept: holes and islands smaller than it are removed, changed masks score 0 and unchanged ones 1, and box NMS runs again
+    at ``max(box_nms_thresh, crop_nms_thresh)`` on the boxes of the cleaned masks, so a repaired mask yields to an untouched
+    duplicate and unchanged masks come first.  ``regions_engine`` (a SegVLADEngine; ``rle_engine`` when only that is given)
+    cleans the masks on the device (``mask_regions``); without one the host path does (``clean_small_regions``, on scipy)."""
 
     def __init__(self, model, points_per_side: int = 32, points_per_batch: int = 64, pred_iou_thresh: float = 0.88,
                  stability_score_thresh: float = 0.95, stability_score_offset: float = 1.0, box_nms_thresh: float = 0.7,
                  min_mask_region_area: int = 0, mask_threshold: float = 0.0, device: Union[str, torch.device] = "cpu",
-                 output_mode: str = "binary_mask", rle_engine=None):
+                 output_mode: str = "binary_mask", rle_engine=None, crop_nms_thresh: float = 0.7, regions_engine=None):
         if output_mode not in OUTPUT_MODES:   # (the reference's third mode, coco_rle, needs pycocotools: not offered)
             raise ValueError(f"output_mode must be one of {OUTPUT_MODES}, got {output_mode!r}")
         self.output_mode = output_mode
         self.rle_engine = rle_engine
+        self.regions_engine = regions_engine
+        self.crop_nms_thresh = float(crop_nms_thresh)   # (crop layers stay at 0: only the second NMS's threshold reads it)
         self.device = torch.device(device)
         self.model = model.eval().to(self.device)
         self.img_size = int(self.model.config.vision_config.image_size)
@@ -333,12 +391,16 @@ class SamAutoMasks:
         rle_mode = getattr(self, "output_mode", "binary_mask") == "uncompressed_rle"
         engine = getattr(self, "rle_engine", None) if rle_mode else None
         ious, stab, pts, boxes = ious[keep].cpu(), stab[keep].cpu(), pts[kc], boxes[keep].cpu()
+        masks = masks[keep]
+        if self.min_mask_region_area > 0 and len(kc):
+            masks, boxes, k2 = self._postprocess_small_regions(masks)
+            ious, stab, pts = ious[k2], stab[k2], pts[k2]
         if engine is not None and len(kc):
             # the masks stay where they are: runs and areas (area_from_rle) from the device encoder, and only those come back
-            rle, areas = engine.rle_encode(masks[keep], want_area=True)
+            rle, areas = engine.rle_encode(masks, want_area=True)
             segs, areas = rle.to_sam(), areas.cpu().tolist()
         else:
-            masks = masks[keep].cpu().numpy()
+            masks = masks.cpu().numpy()
             segs = RleMasks.from_dense(masks).to_sam() if rle_mode and masks.shape[0] else masks
             areas = [int(masks[j].sum()) for j in range(masks.shape[0])]
         recs = []
@@ -350,6 +412,28 @@ class SamAutoMasks:
                              "predicted_iou": float(ious[j]), "point_coords": [[float(pts[j, 0]), float(pts[j, 1])]],
                              "stability_score": float(stab[j]), "crop_box": [0, 0, W, H]})
         return recs
+
+    def _postprocess_small_regions(self, masks: torch.Tensor):
+        """postprocess_small_regions (automatic_mask_generator.py:325-376) on the bool masks [S, H, W] the first NMS kept:
+        ``(cleaned masks[k2] (bool, where the masks were), their boxes (int64, host), k2 (int64, host))`` with k2 the indices
+        the second NMS keeps, in its order -- unchanged masks (score 1) before changed ones (score 0), input order inside each
+        (``box_nms`` sorts stably; torchvision leaves the order of ties open, tools/make_golden.py::torchvision_nms pins this one).
+        The reference refreshes runs and boxes of the changed survivors only; an unchanged mask's are what they were."""
+        min_area = self.min_mask_region_area
+        engine = getattr(self, "regions_engine", None)
+        if engine is None:
+            engine = getattr(self, "rle_engine", None)
+        if engine is not None:
+            out = engine.mask_regions(masks, min_area, want_boxes=True, want_area=False)
+            cleaned, changed, boxes = out["masks"].view(torch.bool), out["changed"].cpu(), out["boxes"].cpu().to(torch.int64)
+        else:
+            c, ch = clean_small_regions(masks.cpu().numpy(), min_area)
+            cleaned, changed = torch.from_numpy(c).to(masks.device), torch.from_numpy(ch)
+            boxes = mask_boxes(cleaned).cpu()
+        scores = (changed == 0).to(torch.float32)
+        thresh = max(self.box_nms_thresh, getattr(self, "crop_nms_thresh", 0.7))
+        k2 = box_nms(boxes, scores, thresh)
+        return cleaned[k2.to(cleaned.device)], boxes[k2], k2
 
 
 def resize_like_cv2(img: np.ndarray, width: int, height: int) -> np.ndarray:

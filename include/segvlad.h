@@ -50,7 +50,13 @@ int segvlad_create(segvlad_ctx** out, int device_id);
 int segvlad_destroy(segvlad_ctx* ctx);
 const char* segvlad_last_error(const segvlad_ctx* ctx);
 /* hip_stream: a hipStream_t (e.g. torch.cuda.current_stream().cuda_stream); NULL = default stream.  The context's scratch and
- * barrier words assume its work is stream-ordered: synchronise the old stream before switching to another one. */
+ * barrier words assume its work is stream-ordered: before switching to another stream, order the old stream's work before the
+ * new stream's -- synchronise the old stream, or make the new one wait on an event recorded on the old one behind the context's
+ * last call (hipStreamWaitEvent; torch's wait_stream).  Inputs follow the same order: a call reads its device inputs in the
+ * order of the context's stream (work the library runs on streams of its own is joined to it by events), and has taken what it
+ * needs of its HOST inputs when it returns -- the caller may overwrite a device input behind the call on that stream, and a host
+ * input at once (segvlad_describe_begin .. _end keep some buffers longer: see there).  tests/test_gpu_async_order.py holds every
+ * entry to this. */
 int segvlad_set_stream(segvlad_ctx* ctx, void* hip_stream);
 int segvlad_synchronize(segvlad_ctx* ctx);
 
@@ -233,7 +239,11 @@ int segvlad_describe(segvlad_ctx* ctx, const uint8_t* masks, int Hm, int Wm, int
  *      segvlad_describe_end     n_patch adjacency blocks recomputed by the caller (patch_images [n_patch] HOST, ascending image
  *                               indices; patch_blocks HOST: their [S_b][S_b] byte matrices, concatenated) are written over the
  *                               device's, then prep -> aggregation (-> projection) run: the result is that of segvlad_images[_pca]
- *                               with the patched adjacency.  Same tokens / inc_bits / seg_offsets / adj buffers as in begin.
+ *                               with the patched adjacency.  Same tokens / inc_bits / seg_offsets / adj buffers as in begin:
+ *                               from begin to end they (and the other outputs of begin) are the library's, unchanged.  The masks
+ *                               are read by the mask branch only, on the context's second stream: the caller may overwrite them
+ *                               once segvlad_describe_flags has returned (it waits for that branch), without it once
+ *                               segvlad_describe_end has.  patch_images / patch_blocks may be overwritten when end returns.
  *      A begin must be followed by an end (flags is optional) before any other describe / incidence / adjacency / images /
  *      cluster_aggregate call on the context: those return SEGVLAD_ERR_STATE while a begin is open (round 6; the rule used to
  *      be documented only).  segvlad_describe_begin and segvlad_describe return SEGVLAD_ERR_LIMIT -- "this entry point cannot,

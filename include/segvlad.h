@@ -405,6 +405,8 @@ int segvlad_exclude_stats(segvlad_ctx* ctx, int64_t* stats_out, int n);
  *      Deterministic: two calls return the same bits.  Synchronises once (the number of rows the collapse left open has to
  *      reach the host; the exact pass synchronises again).  Stage timer "knn_group": the kernels this call adds to the inner
  *      search's own stages.  One index, one context: the row-sharded and query-sharded classes have no counterpart yet.
+ *      Where only the vote's weight of one image per segment matters, SEGVLAD_VOTE_PER_IMAGE (segvlad_vote) caps the hits in
+ *      the vote instead: it costs no second search and does not back-fill the lists.
  *      segvlad_group_stats: HOST array, up to 3 values, of the last segvlad_search_grouped -- [0] the depth the inner search
  *      ran at (k_fetch), [1] query rows finished by the exact pass, [2] the largest number of list entries any row read
  *      before the collapse declared it complete (rows the exact pass finished do not count).                              */
@@ -595,7 +597,24 @@ int segvlad_minmax(segvlad_ctx* ctx, const float* sims, int64_t count, float* mi
  *      the extrema of the kept entries (pipeline.py does).  A weight below 0 or above 1 (explicit
  *      extrema inside the data's range) is added like any other.  A query image's row of pred_out /
  *      score_out depends on that image's entries and the extrema alone, bit for bit: not on the other
- *      images of the call, whose sizes only choose the kernel's code path.                           */
+ *      images of the call, whose sizes only choose the kernel's code path.
+ *      Per-image cap: at most m hits per reference image from each query segment.
+ *        #define SEGVLAD_VOTE_PER_IMAGE(m) ((m) << 8)      1 <= m <= 255; 0 = no cap
+ *      mode = base | SEGVLAD_VOTE_PER_IMAGE(m): base = mode & 0xff is SEGVLAD_VOTE_WT_BORDA_IM or SEGVLAD_VOTE_COUNT,
+ *      m = (mode >> 8) & 0xff; any bit above bit 15, or an unknown base, returns SEGVLAD_ERR_ARG.  m == 0 is the call without
+ *      a cap, launch for launch.  For m >= 1 take row q of idx and rank r: the entry is VALID when 0 <= idx[q][r] < n_ref_seg
+ *      (the rule above), its image is g = img_of_seg[idx[q][r]] (images compare as 32-bit values, negative ones included), and
+ *      it VOTES when it is valid and fewer than m valid entries at ranks r' < r of the same row carry the same g.  The call
+ *      returns, bit for bit in pred_out and score_out, what the same call with mode = base returns on the same arguments with
+ *      every non-voting entry's id replaced by -1.  Hence: the sums run in visiting order over the voting entries; ties go
+ *      by the first appearance, which always votes; a COUNT score is the sum over the segments of min(m, hits) -- at m = 1 the
+ *      number of query segments that see the image; with NaN smin / smax the extrema are still taken over ALL sims of the
+ *      call (a caller that wants others passes them); m >= k blanks nothing; sims may be NULL in COUNT; and a query image's
+ *      row still depends on that image's entries and the extrema alone.  How: one more launch in front of the vote (one wave
+ *      per row marks the voting entries into a blanked copy of idx; stage "vote"), no further synchronisation.  The cap
+ *      works behind every search variant and on lists a caller already holds; it does not back-fill a list with the entries
+ *      behind the blanked ones (segvlad_search_grouped does).                                                              */
+#define SEGVLAD_VOTE_PER_IMAGE(m) ((m) << 8)
 int segvlad_vote(segvlad_ctx* ctx, const int64_t* idx, const float* sims, const int32_t* img_of_seg,
                  int64_t n_ref_seg, const int32_t* qseg_offsets, int n_img, int k, float smin, float smax, int n_top, int mode,
                  int32_t* pred_out, double* score_out);
@@ -726,7 +745,8 @@ int segvlad_search_sharded(segvlad_ctx* ctx, const float* Q, int nq, int k, int6
  *                               rank whose local step fails (arguments included) still joins with its status in its
  *                               record, then every rank returns an error (the failing rank its own, the others
  *                               SEGVLAD_ERR_COMM naming it) and the communicator stays usable; a rank that cannot join
- *                               aborts the communicator.  Mode COUNT needs no extrema but stays collective.  No
+ *                               aborts the communicator.  Mode COUNT needs no extrema but stays collective; mode takes
+ *                               segvlad_vote's SEGVLAD_VOTE_PER_IMAGE bits (each rank caps its own rows).  No
  *                               communicator bound: exactly segvlad_vote with NaN extrema.  Synchronises the stream.
  *      Gathering the predictions in image order: segvlad_allgather_rows, a byte-exact copy.  Each rank packs its images
  *      as rows of 3 * n_top 32-bit words {pred int32 [n_top], score fp64 bits [n_top]} viewed as fp32, padded to the

@@ -16,6 +16,21 @@ SEGVLAD_ERR_ARG, SEGVLAD_ERR_HIP, SEGVLAD_ERR_STATE, SEGVLAD_ERR_LIMIT, SEGVLAD_
 COMM_ID_BYTES = 128
 VOTE_WT_BORDA_IM = 0
 VOTE_COUNT = 1
+VOTE_PER_IMAGE_SHIFT = 8   # SEGVLAD_VOTE_PER_IMAGE(m) = m << 8
+
+
+def vote_mode(base: int, per_image=None) -> int:
+    """segvlad_vote's ``mode`` word: ``base`` (VOTE_WT_BORDA_IM / VOTE_COUNT; cap bits it already carries are kept) with
+    SEGVLAD_VOTE_PER_IMAGE(per_image) folded in -- at most ``per_image`` (1 .. 255) hits per reference image from each query
+    segment.  ``per_image=None``: ``base`` as it is."""
+    base = int(base)
+    if per_image is None:
+        return base
+    if isinstance(per_image, bool) or int(per_image) != per_image or not 1 <= int(per_image) <= 255:
+        raise ValueError(f"per_image must be an integer in 1 .. 255, got {per_image!r}")
+    if base >> VOTE_PER_IMAGE_SHIFT and base >> VOTE_PER_IMAGE_SHIFT != int(per_image):
+        raise ValueError(f"mode {base:#x} already carries a per-image cap other than {int(per_image)}")
+    return (base & 0xFF) | (int(per_image) << VOTE_PER_IMAGE_SHIFT)
 
 # name -> (restype, argtypes); kept in one table so tests can check the exported symbols against the header
 SIGNATURES = {

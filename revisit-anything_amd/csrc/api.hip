@@ -597,16 +597,20 @@ int segvlad_minmax(segvlad_ctx* ctx, const float* sims, int64_t count, float* mi
 
 // The argument checks and the staging of segvlad_vote, shared with segvlad_vote_global (comm.hip): on return the operands
 // are on the device and the query-image offsets are on their way to ctx->s_voteoff; v->mm is the two-float extrema slot
-// behind them.  n_img == 0 returns SEGVLAD_OK with nothing staged.
+// behind them.  n_img == 0 returns SEGVLAD_OK with nothing staged.  mode is decoded here (v->base); with a per-image cap in its
+// bits 8..15 the blanked copy of idx is made behind the staging, in ctx->s_vote_cap, and v->di names the copy.
 int sv_vote_prepare(segvlad_ctx* ctx, const int64_t* idx, const float* sims, const int32_t* img_of_seg, int64_t n_ref_seg,
                     const int32_t* qseg_offsets, int n_img, int k, int n_top, int mode, int32_t* pred_out, double* score_out,
                     SvVote* v) {
   *v = SvVote{};
   if (n_img < 0 || k < 1 || n_top < 1) return ctx->fail(SEGVLAD_ERR_ARG, "vote: bad shape");
-  if (mode != SEGVLAD_VOTE_WT_BORDA_IM && mode != SEGVLAD_VOTE_COUNT) return ctx->fail(SEGVLAD_ERR_ARG, "vote: unknown mode %d", mode);
+  const int base = mode & 0xff, cap = (mode >> 8) & 0xff;
+  if ((mode >> 16) != 0 || (base != SEGVLAD_VOTE_WT_BORDA_IM && base != SEGVLAD_VOTE_COUNT))
+    return ctx->fail(SEGVLAD_ERR_ARG, "vote: unknown mode %d", mode);
+  v->base = base;
   if (n_img == 0) return SEGVLAD_OK;
   if (!idx || !qseg_offsets || !pred_out) return ctx->fail(SEGVLAD_ERR_ARG, "vote: null pointer");
-  if (mode == SEGVLAD_VOTE_WT_BORDA_IM && !sims) return ctx->fail(SEGVLAD_ERR_ARG, "vote: weighted mode needs sims");
+  if (base == SEGVLAD_VOTE_WT_BORDA_IM && !sims) return ctx->fail(SEGVLAD_ERR_ARG, "vote: weighted mode needs sims");
   if (sv_is_device_ptr(qseg_offsets)) return ctx->fail(SEGVLAD_ERR_ARG, "vote: qseg_offsets must be host memory");
   const int nq = qseg_offsets[n_img];
   int64_t n_ref = ctx->db_n;
@@ -627,6 +631,13 @@ int sv_vote_prepare(segvlad_ctx* ctx, const int64_t* idx, const float* sims, con
   if (score_out) SV_TRY(sv_out(ctx, score_out, (size_t)n_img * n_top * 8, &os));
   SV_HIP(ctx->s_voteoff.reserve((size_t)(n_img + 1) * 4 + 32));
   SV_HIP(hipMemcpyAsync(ctx->s_voteoff.p, qseg_offsets, (size_t)(n_img + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
+  if (cap > 0 && nq > 0) {
+    SV_HIP(ctx->s_vote_cap.reserve((size_t)nq * k * 8));
+    StageScope sc(ctx, "vote");
+    SV_TRY(sv_launch_vote_cap(ctx, (const int64_t*)di, (const int32_t*)dimg, n_ref, nq, k, cap, ctx->s_vote_cap.as<int64_t>()));
+    sc.count();
+    di = ctx->s_vote_cap.p;
+  }
   v->di = di;
   v->ds = ds;
   v->dimg = dimg;
@@ -648,7 +659,7 @@ int segvlad_vote(segvlad_ctx* ctx, const int64_t* idx, const float* sims, const 
   SV_TRY(sv_vote_prepare(ctx, idx, sims, img_of_seg, n_ref_seg, qseg_offsets, n_img, k, n_top, mode, pred_out, score_out, &v));
   if (n_img == 0) return SEGVLAD_OK;
   StageScope sc(ctx, "vote");
-  if (mode == SEGVLAD_VOTE_WT_BORDA_IM) {
+  if (v.base == SEGVLAD_VOTE_WT_BORDA_IM) {
     if (std::isnan(smin) || std::isnan(smax)) {
       SV_TRY(sv_launch_minmax(ctx, (const float*)v.ds, (int64_t)v.nq * k, v.mm));
       sc.count(3);
@@ -659,7 +670,7 @@ int segvlad_vote(segvlad_ctx* ctx, const int64_t* idx, const float* sims, const 
     }
   }
   SV_TRY(sv_launch_vote(ctx, (const int64_t*)v.di, (const float*)v.ds, (const int32_t*)v.dimg, v.n_ref, ctx->s_voteoff.as<int32_t>(),
-                        qseg_offsets, n_img, k, v.mm, n_top, mode, (int32_t*)v.op, (double*)v.os));
+                        qseg_offsets, n_img, k, v.mm, n_top, v.base, (int32_t*)v.op, (double*)v.os));
   sc.count();
   return sv_finish(ctx);
 }

@@ -394,7 +394,7 @@ int segvlad_vote_global(segvlad_ctx* ctx, const int64_t* idx, const float* sims,
   SvVote v;
   int local_rc = sv_vote_prepare(ctx, idx, sims, img_of_seg, n_ref_seg, qseg_offsets, n_img, k, n_top, mode, pred_out, score_out, &v);
   int have_mm = 0;
-  if (local_rc == SEGVLAD_OK && n_img > 0 && mode == SEGVLAD_VOTE_WT_BORDA_IM && v.nq > 0) {
+  if (local_rc == SEGVLAD_OK && n_img > 0 && v.base == SEGVLAD_VOTE_WT_BORDA_IM && v.nq > 0) {
     StageScope sc(ctx, "vote");
     local_rc = sv_launch_minmax(ctx, (const float*)v.ds, (int64_t)v.nq * k, v.mm);
     have_mm = local_rc == SEGVLAD_OK;
@@ -437,7 +437,7 @@ int segvlad_vote_global(segvlad_ctx* ctx, const int64_t* idx, const float* sims,
   if (post_rc == SEGVLAD_OK && local_rc == SEGVLAD_OK && n_img > 0) {
     StageScope sc(ctx, "vote");
     post_rc = sv_launch_vote(ctx, (const int64_t*)v.di, (const float*)v.ds, (const int32_t*)v.dimg, v.n_ref, ctx->s_voteoff.as<int32_t>(),
-                             qseg_offsets, n_img, k, gmm, n_top, mode, (int32_t*)v.op, (double*)v.os);
+                             qseg_offsets, n_img, k, gmm, n_top, v.base, (int32_t*)v.op, (double*)v.os);
     sc.count();
   }
   {

@@ -206,6 +206,74 @@ __global__ __launch_bounds__(VOTE_THREADS) void vote_kernel(const int64_t* __res
   }
 }
 
+// ---- per-image cap (SEGVLAD_VOTE_PER_IMAGE(m) in segvlad_vote's mode) -------------------------------------------------------
+// An entry of row q votes when it is valid (0 <= id < n_ref_seg) and fewer than m valid entries at earlier ranks of the row carry
+// its image id.  This pass writes a copy of idx with every other valid entry set to -1; the vote kernels then run on the copy
+// unchanged, so a capped vote IS the plain vote over the blanked lists.
+//
+// One wave per query row, 64 ranks at a time.  Every lane holds the image id of its rank and counts the earlier valid entries
+// that carry it: the earlier chunks first (their ids come back from LDS, one per lane, and are compared lane by lane through
+// v_readlane -- only the valid lanes are visited), then the lower lanes of its own chunk.  The walk over the earlier chunks ends
+// as soon as no lane of the wave can still vote.  LDS keeps the first CAP_LDS_RANKS ids of a row; a deeper row gathers the
+// ids behind them again (k > 1024 is beyond every search of the library: correct, not fast).
+constexpr int CAP_WAVES = 4;
+constexpr int CAP_LDS_RANKS = 1024;
+
+__global__ __launch_bounds__(CAP_WAVES * 64) void vote_cap_kernel(const int64_t* __restrict__ idx, const int32_t* __restrict__ img_of_seg,
+                                                                  int64_t n_ref_seg, int nq, int k, int m, int64_t* __restrict__ out) {
+  __shared__ int32_t s_img[CAP_WAVES][CAP_LDS_RANKS];
+  __shared__ uint8_t s_ok[CAP_WAVES][CAP_LDS_RANKS];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int64_t q = (int64_t)blockIdx.x * CAP_WAVES + w;
+  const bool live = q < nq;   // (a wave without a row keeps the block's barriers company)
+  const int64_t* row = idx + q * k;
+  for (int c0 = 0; c0 < k; c0 += 64) {
+    const int r = c0 + lane;
+    int64_t id = -1;
+    int32_t g = 0;
+    bool ok = false;
+    if (live && r < k) {
+      id = row[r];
+      ok = id >= 0 && id < n_ref_seg;
+      if (ok) g = img_of_seg[id];
+    }
+    if (c0 < CAP_LDS_RANKS) {
+      s_img[w][r] = g;
+      s_ok[w][r] = ok ? 1 : 0;
+    }
+    __syncthreads();
+    int cnt = 0;
+    for (int p0 = 0; p0 < c0; p0 += 64) {
+      if (!__any(ok && cnt < m)) break;   // wave-uniform: nobody here can still vote
+      int32_t gp = 0;
+      bool pok;
+      if (p0 < CAP_LDS_RANKS) {
+        gp = s_img[w][p0 + lane];
+        pok = s_ok[w][p0 + lane] != 0;
+      } else {   // (some lane is valid, so the wave has a row; p0 + lane < c0 <= k)
+        const int64_t pid = row[p0 + lane];
+        pok = pid >= 0 && pid < n_ref_seg;
+        if (pok) gp = img_of_seg[pid];
+      }
+      for (uint64_t pm = __ballot(pok); pm; pm &= pm - 1) cnt += __builtin_amdgcn_readlane(gp, __ffsll((unsigned long long)pm) - 1) == g;
+    }
+    for (uint64_t om = __ballot(ok); om; om &= om - 1) {
+      const int j = __ffsll((unsigned long long)om) - 1;
+      cnt += (j < lane) & (__builtin_amdgcn_readlane(g, j) == g);
+    }
+    if (live && r < k) out[q * k + r] = (ok && cnt >= m) ? -1 : id;
+  }
+}
+
+int sv_launch_vote_cap(segvlad_ctx* ctx, const int64_t* idx, const int32_t* img_of_seg, int64_t n_ref_seg, int nq, int k, int m,
+                       int64_t* out) {
+  if (nq <= 0) return SEGVLAD_OK;
+  hipLaunchKernelGGL(vote_cap_kernel, dim3((unsigned)(((int64_t)nq + CAP_WAVES - 1) / CAP_WAVES)), dim3(CAP_WAVES * 64), 0, ctx->stream, idx,
+                     img_of_seg, n_ref_seg, nq, k, m, out);
+  SV_HIP(hipGetLastError());
+  return SEGVLAD_OK;
+}
+
 int sv_launch_vote(segvlad_ctx* ctx, const int64_t* idx, const float* sims, const int32_t* img_of_seg,
                    int64_t n_ref_seg, const int32_t* qoff_dev, const int32_t* qoff_host, int n_img, int k,
                    const float* minmax_dev, int n_top, int mode, int32_t* pred, double* score) {

@@ -335,6 +335,38 @@ def collapse_lists(d2, idx, img_of_seg, k: int, per_image: int = 1):
     return out_d, out_i
 
 
+def blank_capped(idx, img_of_seg, per_image: int) -> np.ndarray:
+    """The rule of segvlad_vote's per-image cap (SEGVLAD_VOTE_PER_IMAGE), stated on the host for callers that already hold
+    lists: ``idx [nq][k]`` int64, ``img_of_seg [n_ref_seg]``.  An entry is valid when ``0 <= idx < n_ref_seg``; it votes when
+    fewer than ``per_image`` valid entries at EARLIER ranks of its row carry its image id (ids compare as 32-bit values,
+    negative ones included).  Returns a copy of ``idx`` with every valid entry that does not vote set to -1: the plain vote over
+    it is the capped vote over ``idx``.  Unlike collapse_lists() nothing moves up into the blanked slots."""
+    idx = np.asarray(idx.detach().cpu().numpy() if isinstance(idx, torch.Tensor) else idx, dtype=np.int64)
+    img = np.asarray(img_of_seg.detach().cpu().numpy() if isinstance(img_of_seg, torch.Tensor) else img_of_seg).reshape(-1)
+    if idx.ndim != 2:
+        raise ValueError(f"idx must be [nq][k], got {idx.shape}")
+    if isinstance(per_image, bool) or int(per_image) != per_image or not 1 <= int(per_image) <= 255:
+        raise ValueError(f"per_image must be an integer in 1 .. 255, got {per_image!r}")
+    out = idx.copy()
+    if idx.size == 0:
+        return out
+    nq, k = idx.shape
+    valid = (idx >= 0) & (idx < img.size)
+    g = img.astype(np.int64)[np.where(valid, idx, 0)]
+    # one stable sort of every row by (invalid last, image id): an entry's position inside its image's run is the number of
+    # earlier valid entries of the row that carry the image
+    order = np.lexsort((g, ~valid), axis=1)
+    gs = np.take_along_axis(g, order, 1)
+    pos = np.broadcast_to(np.arange(k), (nq, k))
+    first = np.ones((nq, k), bool)
+    first[:, 1:] = gs[:, 1:] != gs[:, :-1]
+    earlier_sorted = pos - np.maximum.accumulate(np.where(first, pos, 0), axis=1)
+    earlier = np.empty((nq, k), np.int64)
+    np.put_along_axis(earlier, order, earlier_sorted, 1)
+    out[valid & (earlier >= int(per_image))] = -1
+    return out
+
+
 def expand_radius2(radius2, nq: int, qseg_offsets=None) -> np.ndarray:
     """``radius2`` of range_search as one fp32 value per query row: a scalar, ``[nq]``, or -- with ``qseg_offsets`` --
     ``[n_img]`` (repeated over each image's rows).  Raises ValueError on any other shape."""
@@ -489,10 +521,12 @@ class SegVLADEngine:
         self._keep = [q]
         return d2, idx
 
-    def vote_global(self, idx, sims, qseg_offsets, n_top=5, mode=_lib.VOTE_WT_BORDA_IM, img_of_seg=None, want_scores=True):
+    def vote_global(self, idx, sims, qseg_offsets, n_top=5, mode=_lib.VOTE_WT_BORDA_IM, img_of_seg=None, want_scores=True,
+                    per_image=None):
         """Collective (query-sharded retrieval): vote() over this rank's query images with the min / max of the similarities of
         ALL ranks of the context's communicator (func_vpr.py:211-214).  Every rank calls it, a rank without images included
-        (idx / sims [0, k])."""
+        (idx / sims [0, k]).  ``per_image``: vote()'s cap."""
+        mode = _lib.vote_mode(mode, per_image)
         i = _as(idx, np.int64, torch.int64)
         s = None if sims is None else _as(sims, np.float32, torch.float32)
         qo = np.ascontiguousarray(qseg_offsets, dtype=np.int32)
@@ -1304,7 +1338,11 @@ class SegVLADEngine:
         return out
 
     def vote(self, idx, sims, qseg_offsets, n_top=5, mode=_lib.VOTE_WT_BORDA_IM, img_of_seg=None, smin=float("nan"),
-             smax=float("nan"), want_scores=True):
+             smax=float("nan"), want_scores=True, per_image=None):
+        """segvlad_vote.  ``per_image`` (1 .. 255): every query segment gives a reference image at most that many hits -- the
+        vote over blank_capped(idx, img_of_seg, per_image), bit for bit (SEGVLAD_VOTE_PER_IMAGE; an int ``mode`` that already
+        carries the bits is accepted as it is)."""
+        mode = _lib.vote_mode(mode, per_image)
         i = _as(idx, np.int64, torch.int64)
         s = None if sims is None else _as(sims, np.float32, torch.float32)
         qo = np.ascontiguousarray(qseg_offsets, dtype=np.int32)

@@ -22,6 +22,8 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
+from ._lib import vote_mode
+
 
 def shard_bounds(n_rows: int, world: int) -> np.ndarray:
     """Contiguous, balanced row blocks: row_start[r] = floor(r * n / world)."""
@@ -266,11 +268,15 @@ class ShardedSegmentIndex:
         return d2c, idc
 
     def retrieve(self, Q, qseg_offsets: Sequence[int], k_search: int = 200, k_vote: int = 50, n_top: int = 5, mode: int = 0,
-                 want_scores: bool = False, vote_depth_only: bool = False):
+                 want_scores: bool = False, vote_depth_only: bool = False, votes_per_image=None):
         """search -> keep k_vote, 2-d^2 -> vote with the global segment->image map.  The global min/max of the
         vote (func_vpr.py:212-213) is taken over the merged (global) similarities, so it needs no extra collective.
         vote_depth_only: a caller that does not keep the k_search-wide lists (place_rec_main.py:61-75 pickles them only under
-        save_results) may have a single index search k_vote deep as well -- same first k_vote columns, same votes."""
+        save_results) may have a single index search k_vote deep as well -- same first k_vote columns, same votes.
+        votes_per_image (1 .. 255): at most that many hits per reference image from each query segment, capped in the vote
+        (the backend's vote takes it in ``mode``, _lib.vote_mode): the lists are the merged global ones, so the result is the
+        single index's."""
+        mode = vote_mode(mode, votes_per_image)
         if hasattr(self.be, "hint_query_groups"):   # an image's rows as one group of the exact refinement (same results)
             self.be.hint_query_groups(qseg_offsets)
         if self.world > 1 or vote_depth_only:
@@ -370,11 +376,15 @@ class QueryShardedRetrieval:
 
     # ---- query --------------------------------------------------------------------------------------
     def retrieve(self, Q_local, qseg_offsets_local: Sequence[int], k_search: int = 200, k_vote: int = 50, n_top: int = 5,
-                 mode: int = 0, want_scores: bool = False, vote_depth_only: bool = False, n_query_images: Optional[int] = None) -> dict:
+                 mode: int = 0, want_scores: bool = False, vote_depth_only: bool = False, n_query_images: Optional[int] = None,
+                 votes_per_image=None) -> dict:
         """This rank's images: Q_local [nq_local, d] (their segment rows), qseg_offsets_local [n_img_local + 1] (from 0).
         Collective: every rank calls it, with the split of split(n_query_images) (or n_query_images given here).
         Returns {"pred", "score"}: the GATHERED [n_query_images, n_top] predictions / fp64 scores in global image order,
-        identical on every rank (score None unless want_scores), and {"pred_local", "score_local", "m", "sims"}: this rank's."""
+        identical on every rank (score None unless want_scores), and {"pred_local", "score_local", "m", "sims"}: this rank's.
+        votes_per_image (1 .. 255): at most that many hits per reference image from each query segment, capped in the vote
+        (in ``mode``, _lib.vote_mode); the global extrema stay those of all kept similarities."""
+        mode = vote_mode(mode, votes_per_image)
         if n_query_images is not None:
             self.split(n_query_images)
         if self.img_bounds is None:
@@ -419,7 +429,7 @@ class QueryShardedRetrieval:
     def _global_extrema(self, sims, nq: int, local_err, mode: int):
         """torch.distributed transport: this rank's record -> all_gather -> the exact global (min, max) on the host."""
         rec = torch.tensor([0x7F800000, -0x00800000, 1 if local_err is not None else 0, 0], dtype=torch.int32, device=self.device)
-        if local_err is None and nq and mode == 0:
+        if local_err is None and nq and (mode & 0xFF) == 0:
             mm = torch.as_tensor(self.be.minmax(sims)).to(self.device).to(torch.float32).contiguous()
             rec = torch.cat([mm.view(torch.int32), torch.tensor([0, nq], dtype=torch.int32, device=self.device)])
         if self.world > 1:

@@ -600,7 +600,7 @@ int segvlad_minmax(segvlad_ctx* ctx, const float* sims, int64_t count, float* mi
  *      images of the call, whose sizes only choose the kernel's code path.
  *      Per-image cap: at most m hits per reference image from each query segment.
  *        #define SEGVLAD_VOTE_PER_IMAGE(m) ((m) << 8)      1 <= m <= 255; 0 = no cap
- *      mode = base | SEGVLAD_VOTE_PER_IMAGE(m): base = mode & 0xff is SEGVLAD_VOTE_WT_BORDA_IM or SEGVLAD_VOTE_COUNT,
+ *      mode = base | SEGVLAD_VOTE_PER_IMAGE(m): base = mode & 0x7f is SEGVLAD_VOTE_WT_BORDA_IM or SEGVLAD_VOTE_COUNT,
  *      m = (mode >> 8) & 0xff; any bit above bit 15, or an unknown base, returns SEGVLAD_ERR_ARG.  m == 0 is the call without
  *      a cap, launch for launch.  For m >= 1 take row q of idx and rank r: the entry is VALID when 0 <= idx[q][r] < n_ref_seg
  *      (the rule above), its image is g = img_of_seg[idx[q][r]] (images compare as 32-bit values, negative ones included), and
@@ -613,8 +613,30 @@ int segvlad_minmax(segvlad_ctx* ctx, const float* sims, int64_t count, float* mi
  *      row still depends on that image's entries and the extrema alone.  How: one more launch in front of the vote (one wave
  *      per row marks the voting entries into a blanked copy of idx; stage "vote"), no further synchronisation.  The cap
  *      works behind every search variant and on lists a caller already holds; it does not back-fill a list with the entries
- *      behind the blanked ones (segvlad_search_grouped does).                                                              */
+ *      behind the blanked ones (segvlad_search_grouped does).
+ *      One-to-one vote: a reference segment votes once per query image.
+ *        #define SEGVLAD_VOTE_UNIQUE_REF 0x80
+ *      mode = base | SEGVLAD_VOTE_UNIQUE_REF | SEGVLAD_VOTE_PER_IMAGE(m), base = mode & 0x7f; the refusals above stand (0x82 has
+ *      an unknown base).  Take query image b with S_b rows off[b] .. off[b+1]-1: entry (q, r) is VALID as above and its visiting
+ *      position is p = r * S_b + (q - off[b]) (rank-major, then segment: the vote's order).  Among the valid entries of image b
+ *      that carry the same id exactly one WINS: the one with the largest sims value, where a NaN loses to every number and
+ *      +0.0 == -0.0; on a tie (equal values, or all NaN) the smallest p wins; with sims == NULL (COUNT only) the smallest p wins.
+ *      Whenever sims is non-NULL it decides, in both bases.  Ids compare on all 64 bits; entries of different query images never
+ *      interact.  The call returns, bit for bit in pred_out and score_out, what the same call without the flag returns on the
+ *      same arguments with every non-winning valid entry's id replaced by -1; invalid entries stay as they are, and with NaN
+ *      smin / smax the extrema are still taken over ALL sims of the call.  Together with a cap the one-to-one blanking comes
+ *      first and the cap's rule is applied to the blanked lists, where a blanked entry is invalid: it neither counts nor votes.
+ *      With the flag clear the call issues the launches of before, in their order.  How: every entry gets the 64-bit key
+ *      {sims mapped to an order-preserving uint32, ~p} and a hash table per query image ({id, best key} slots, two slots per
+ *      entry, id claimed by compare-and-swap, key raised by a 64-bit max) selects each id's largest key; an entry keeps its id
+ *      when its key is its slot's.  Launches added in front of the cap and the vote (stage "vote"): 1 when some query image has
+ *      at most 4096 entries (S_b * k; one workgroup per image, the table in LDS), and 3 more -- a table fill, insert, resolve --
+ *      when some image has more (the table in global scratch, agent-scope atomics; no grid barrier).  Scratch: the blanked copy,
+ *      nq * k * 8 bytes, and for the larger images 32 bytes per entry of the rows from the first to the last of them.  Limit:
+ *      the vote's, 2^24 entries per query image.  No synchronisation is added; idx and sims are read in the order of the
+ *      context's stream; deterministic: two calls return the same bytes.                                                  */
 #define SEGVLAD_VOTE_PER_IMAGE(m) ((m) << 8)
+#define SEGVLAD_VOTE_UNIQUE_REF 0x80
 int segvlad_vote(segvlad_ctx* ctx, const int64_t* idx, const float* sims, const int32_t* img_of_seg,
                  int64_t n_ref_seg, const int32_t* qseg_offsets, int n_img, int k, float smin, float smax, int n_top, int mode,
                  int32_t* pred_out, double* score_out);
@@ -746,8 +768,9 @@ int segvlad_search_sharded(segvlad_ctx* ctx, const float* Q, int nq, int k, int6
  *                               record, then every rank returns an error (the failing rank its own, the others
  *                               SEGVLAD_ERR_COMM naming it) and the communicator stays usable; a rank that cannot join
  *                               aborts the communicator.  Mode COUNT needs no extrema but stays collective; mode takes
- *                               segvlad_vote's SEGVLAD_VOTE_PER_IMAGE bits (each rank caps its own rows).  No
- *                               communicator bound: exactly segvlad_vote with NaN extrema.  Synchronises the stream.
+ *                               segvlad_vote's SEGVLAD_VOTE_PER_IMAGE and SEGVLAD_VOTE_UNIQUE_REF bits (each rank blanks
+ *                               its own rows).  No communicator bound: exactly segvlad_vote with NaN extrema.  Synchronises
+ *                               the stream.
  *      Gathering the predictions in image order: segvlad_allgather_rows, a byte-exact copy.  Each rank packs its images
  *      as rows of 3 * n_top 32-bit words {pred int32 [n_top], score fp64 bits [n_top]} viewed as fp32, padded to the
  *      largest rank's image count (n_local must be equal on every rank); fp64 scores arrive bit for bit.           */

@@ -17,13 +17,17 @@ COMM_ID_BYTES = 128
 VOTE_WT_BORDA_IM = 0
 VOTE_COUNT = 1
 VOTE_PER_IMAGE_SHIFT = 8   # SEGVLAD_VOTE_PER_IMAGE(m) = m << 8
+VOTE_UNIQUE_REF = 0x80      # SEGVLAD_VOTE_UNIQUE_REF; the base is mode & 0x7F
 
 
-def vote_mode(base: int, per_image=None) -> int:
-    """segvlad_vote's ``mode`` word: ``base`` (VOTE_WT_BORDA_IM / VOTE_COUNT; cap bits it already carries are kept) with
-    SEGVLAD_VOTE_PER_IMAGE(per_image) folded in -- at most ``per_image`` (1 .. 255) hits per reference image from each query
-    segment.  ``per_image=None``: ``base`` as it is."""
+def vote_mode(base: int, per_image=None, unique_ref=False) -> int:
+    """segvlad_vote's ``mode`` word: ``base`` (VOTE_WT_BORDA_IM / VOTE_COUNT; cap bits and the one-to-one flag it already carries
+    are kept) with SEGVLAD_VOTE_PER_IMAGE(per_image) folded in -- at most ``per_image`` (1 .. 255) hits per reference image from
+    each query segment -- and, with ``unique_ref``, SEGVLAD_VOTE_UNIQUE_REF: a reference segment votes once per query image.
+    ``per_image=None`` and ``unique_ref=False``: ``base`` as it is."""
     base = int(base)
+    if unique_ref:
+        base |= VOTE_UNIQUE_REF
     if per_image is None:
         return base
     if isinstance(per_image, bool) or int(per_image) != per_image or not 1 <= int(per_image) <= 255:

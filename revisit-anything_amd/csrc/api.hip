@@ -597,14 +597,16 @@ int segvlad_minmax(segvlad_ctx* ctx, const float* sims, int64_t count, float* mi
 
 // The argument checks and the staging of segvlad_vote, shared with segvlad_vote_global (comm.hip): on return the operands
 // are on the device and the query-image offsets are on their way to ctx->s_voteoff; v->mm is the two-float extrema slot
-// behind them.  n_img == 0 returns SEGVLAD_OK with nothing staged.  mode is decoded here (v->base); with a per-image cap in its
-// bits 8..15 the blanked copy of idx is made behind the staging, in ctx->s_vote_cap, and v->di names the copy.
+// behind them.  n_img == 0 returns SEGVLAD_OK with nothing staged.  mode is decoded here (v->base); with SEGVLAD_VOTE_UNIQUE_REF
+// and / or a per-image cap in its bits 8..15 the blanked copy of idx is made behind the staging -- the one-to-one pass first, into
+// ctx->s_vote_uniq, then the cap over that copy into ctx->s_vote_cap -- and v->di names the last copy.
 int sv_vote_prepare(segvlad_ctx* ctx, const int64_t* idx, const float* sims, const int32_t* img_of_seg, int64_t n_ref_seg,
                     const int32_t* qseg_offsets, int n_img, int k, int n_top, int mode, int32_t* pred_out, double* score_out,
                     SvVote* v) {
   *v = SvVote{};
   if (n_img < 0 || k < 1 || n_top < 1) return ctx->fail(SEGVLAD_ERR_ARG, "vote: bad shape");
-  const int base = mode & 0xff, cap = (mode >> 8) & 0xff;
+  const int base = mode & 0x7f, cap = (mode >> 8) & 0xff;
+  const bool unique = (mode & SEGVLAD_VOTE_UNIQUE_REF) != 0;
   if ((mode >> 16) != 0 || (base != SEGVLAD_VOTE_WT_BORDA_IM && base != SEGVLAD_VOTE_COUNT))
     return ctx->fail(SEGVLAD_ERR_ARG, "vote: unknown mode %d", mode);
   v->base = base;
@@ -631,6 +633,15 @@ int sv_vote_prepare(segvlad_ctx* ctx, const int64_t* idx, const float* sims, con
   if (score_out) SV_TRY(sv_out(ctx, score_out, (size_t)n_img * n_top * 8, &os));
   SV_HIP(ctx->s_voteoff.reserve((size_t)(n_img + 1) * 4 + 32));
   SV_HIP(hipMemcpyAsync(ctx->s_voteoff.p, qseg_offsets, (size_t)(n_img + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
+  if (unique && nq > 0) {
+    SV_HIP(ctx->s_vote_uniq.reserve((size_t)nq * k * 8));
+    StageScope sc(ctx, "vote");
+    int launches = 0;
+    SV_TRY(sv_launch_vote_unique(ctx, (const int64_t*)di, (const float*)ds, n_ref, ctx->s_voteoff.as<int32_t>(), qseg_offsets, n_img, k,
+                                 ctx->s_vote_uniq.as<int64_t>(), &launches));
+    sc.count(launches);
+    di = ctx->s_vote_uniq.p;
+  }
   if (cap > 0 && nq > 0) {
     SV_HIP(ctx->s_vote_cap.reserve((size_t)nq * k * 8));
     StageScope sc(ctx, "vote");

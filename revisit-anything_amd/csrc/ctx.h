@@ -365,13 +365,16 @@ struct segvlad_ctx {
   //  counts and final runs, and the device image of a host caller's counts;
   //  s_rg_*: segvlad_mask_regions (regions_kernels.hip) -- the label plane and the size plane [S][P] of a connected-component pass
   //  and the masks' decisions, areas and boxes;
-  //  s_vote_cap: segvlad_vote with a per-image cap (vote_kernels.hip) -- the blanked copy of idx [nq][k] that the vote then reads
+  //  s_vote_cap: segvlad_vote with a per-image cap (vote_kernels.hip) -- the blanked copy of idx [nq][k] that the vote then reads;
+  //  s_vote_uniq, s_vote_tab: segvlad_vote with SEGVLAD_VOTE_UNIQUE_REF -- the copy of idx [nq][k] with the non-winning claims on a
+  //  reference segment blanked (the cap and the vote read it), and the {id, best key} hash tables of the query images that the
+  //  LDS table does not hold (2 slots of 16 B per entry, zeroed per call)
 #define SV_SCRATCH_BUFS(X)                                                                                                      \
   X(s_xt) X(s_labels) X(s_rnorm) X(s_gap) X(s_colmask) X(s_gscale) X(s_segimg) X(s_segoff) X(s_adjoff) X(s_dist) X(s_qnorm)      \
   X(s_misc) X(s_minmax) X(s_voteoff) X(s_cand_cnt) X(s_cand_d2) X(s_cand_id) X(s_thr_d2) X(s_thr_idx) X(s_flag) X(s_qh) X(s_ql)  \
   X(s_ref_cnt) X(s_ref_id) X(s_qscale) X(s_qf16) X(s_xh1) X(s_xh2) X(s_desc) X(s_tokorder) X(s_laboff) X(s_rnsorted) X(s_ovf)     \
   X(s_fb_q) X(s_fb_d2) X(s_fb_idx) X(s_fb_rows) X(s_rd_rows) X(s_rd_q) X(s_rd_d2) X(s_rd_idx) X(s_rd_flags) X(s_rd_p1) X(s_rd_p2)  \
-  X(s_sel_todo) X(s_vote_keys) X(s_vote_cap) X(s_pz) X(s_rowbase) X(s_tilegrp) X(s_phys) X(s_covcnt) X(s_bn) X(s_l0part) X(s_ref_lim) X(s_sh_d2) X(s_sh_idx)          \
+  X(s_sel_todo) X(s_vote_keys) X(s_vote_cap) X(s_vote_uniq) X(s_vote_tab) X(s_pz) X(s_rowbase) X(s_tilegrp) X(s_phys) X(s_covcnt) X(s_bn) X(s_l0part) X(s_ref_lim) X(s_sh_d2) X(s_sh_idx)          \
   X(s_sh_rec) X(s_sh_all) X(s_sh_d2c) X(s_sh_idc) X(s_grp_cnt) X(s_grp_ids) X(s_grp_rows) X(s_grp_keys) X(s_grp_work) X(s_grp_pos) X(s_tnk_redo) X(s_tail_part) X(s_km_part) X(s_km_cnt) X(s_kflush) \
   X(s_sl_misc) X(s_sl_q) X(s_sl_cur) X(s_sl_uids) X(s_sl_uoff) X(s_sl_unum) X(s_sl_cand) X(s_sl_lens)                            \
   X(s_deep_d2) X(s_deep_idx) X(s_deep_qn) X(s_ex_flag) X(s_ex_td2) X(s_ex_tidx)                                                        \
@@ -719,10 +722,14 @@ int sv_launch_vote(segvlad_ctx* ctx, const int64_t* idx, const float* sims, cons
 // entries of its row on the same image (one launch)
 int sv_launch_vote_cap(segvlad_ctx* ctx, const int64_t* idx, const int32_t* img_of_seg, int64_t n_ref_seg, int nq, int k, int m,
                        int64_t* out);
+// SEGVLAD_VOTE_UNIQUE_REF: out [nq][k] = idx with every valid entry blanked (-1) that is not the winner (largest sim, then first in
+// visiting order) among its query image's entries on the same reference segment; sims may be null.  *launches: what was enqueued
+int sv_launch_vote_unique(segvlad_ctx* ctx, const int64_t* idx, const float* sims, int64_t n_ref_seg, const int32_t* qoff_dev,
+                          const int32_t* qoff_host, int n_img, int k, int64_t* out, int* launches);
 
 // api.hip: the checks and staging of segvlad_vote, shared with segvlad_vote_global (comm.hip)
 struct SvVote {
-  const void* di = nullptr;    // idx on the device (with a per-image cap: its blanked copy in ctx->s_vote_cap)
+  const void* di = nullptr;    // idx on the device (with UNIQUE_REF / a per-image cap: its blanked copy in ctx->s_vote_uniq / s_vote_cap)
   const void* ds = nullptr;    // sims on the device (null in COUNT mode without sims)
   const void* dimg = nullptr;  // segment -> image map on the device
   int64_t n_ref = 0;
@@ -730,7 +737,7 @@ struct SvVote {
   void* os = nullptr;
   float* mm = nullptr;         // the two-float extrema slot the vote kernel reads
   int nq = 0;                  // query segments (qseg_offsets[n_img])
-  int base = 0;                // mode & 0xff: SEGVLAD_VOTE_WT_BORDA_IM or SEGVLAD_VOTE_COUNT
+  int base = 0;                // mode & 0x7f: SEGVLAD_VOTE_WT_BORDA_IM or SEGVLAD_VOTE_COUNT
 };
 int sv_vote_prepare(segvlad_ctx* ctx, const int64_t* idx, const float* sims, const int32_t* img_of_seg, int64_t n_ref_seg,
                     const int32_t* qseg_offsets, int n_img, int k, int n_top, int mode, int32_t* pred_out, double* score_out,

@@ -274,6 +274,165 @@ int sv_launch_vote_cap(segvlad_ctx* ctx, const int64_t* idx, const int32_t* img_
   return SEGVLAD_OK;
 }
 
+// ---- one-to-one vote (SEGVLAD_VOTE_UNIQUE_REF in segvlad_vote's mode) -------------------------------------------------------
+// Among the valid entries of one query image that carry the same reference segment id, one wins: the largest sim (a NaN below
+// every number, -0 == +0), then the smallest visiting position p = rank * S + segment.  This pass writes a copy of idx with every
+// other valid entry set to -1; the cap and the vote kernels then run on the copy unchanged.
+//
+// Every entry gets one 64-bit key, {sim mapped to an order-preserving uint32, ~p}, so that the 64-bit maximum over the keys of an
+// id IS the winner, ties resolved.  A hash table per query image, open addressing with linear probing over T = 2 * entries slots
+// (never more than half full, so a probe always ends), holds {id + 1, best key} per slot: the id is claimed with a 64-bit
+// compare-and-swap (0 = free), the key raised with a 64-bit max (0 = none: ~p is never 0).  Both commute, so the table's keys do
+// not depend on the order of arrival; an entry then keeps its id exactly when its key is its slot's key.  A hot id puts hundreds
+// of entries on one slot: contention on one LDS address, not an error.
+//
+// Images of <= UNIQ_LDS_ENTRIES entries: one workgroup each, the table in LDS (ds_cmpst_rtn_b64 / ds_max_u64), one launch.
+// Larger ones: the same scheme on a zeroed global table with agent-scope atomics, insert and resolve as two launches (the kernel
+// boundary is the barrier); image b's table starts at slot 2 * (qoff[b] - qoff[first large image]) * k, so no per-image list
+// travels to the device and nothing waits for the host.
+constexpr int UNIQ_LDS_ENTRIES = 4096;   // 8192 slots x 16 B = 128 KiB of the 160
+constexpr int UNIQ_THREADS = 1024;
+constexpr int UNIQ_G_THREADS = 256;
+constexpr int UNIQ_G_PER_BLOCK = 2048;   // entries a workgroup of the global kernels walks
+
+__device__ __forceinline__ uint32_t uniq_slot(int64_t id, uint32_t T) {
+  const uint32_t h = (uint32_t)(((uint64_t)id * 0x9E3779B97F4A7C15ull) >> 32);
+  return (uint32_t)(((uint64_t)h * T) >> 32);
+}
+
+// sims == nullptr: every entry the same constant, the smallest p wins
+__device__ __forceinline__ uint64_t uniq_key(const float* __restrict__ sims, int64_t at, uint32_t p) {
+  uint32_t hi = 1u;
+  if (sims) {
+    const float s = sims[at];
+    uint32_t u = __float_as_uint(s);
+    if (s == 0.f) u = 0u;                                  // -0 -> +0
+    hi = (s != s) ? 0u : ((u & 0x80000000u) ? ~u : (u | 0x80000000u));
+  }
+  return ((uint64_t)hi << 32) | (uint32_t)~p;
+}
+
+template <int SCOPE>
+__device__ __forceinline__ void uniq_insert(unsigned long long* tid_, unsigned long long* tkey, uint32_t T, int64_t id, uint64_t key) {
+  const unsigned long long want = (unsigned long long)id + 1ull;
+  uint32_t h = uniq_slot(id, T);
+  for (;;) {
+    unsigned long long seen = 0ull;
+    if (__hip_atomic_compare_exchange_strong(&tid_[h], &seen, want, __ATOMIC_RELAXED, __ATOMIC_RELAXED, SCOPE) || seen == want) break;
+    h = h + 1u == T ? 0u : h + 1u;
+  }
+  __hip_atomic_fetch_max(&tkey[h], (unsigned long long)key, __ATOMIC_RELAXED, SCOPE);
+}
+
+// the best key of id (the table holds it: every valid entry was inserted)
+__device__ __forceinline__ uint64_t uniq_best(const unsigned long long* tid_, const unsigned long long* tkey, uint32_t T, int64_t id) {
+  const unsigned long long want = (unsigned long long)id + 1ull;
+  uint32_t h = uniq_slot(id, T);
+  while (tid_[h] != want) h = h + 1u == T ? 0u : h + 1u;
+  return tkey[h];
+}
+
+__global__ __launch_bounds__(UNIQ_THREADS) void vote_unique_lds_kernel(const int64_t* __restrict__ idx, const float* __restrict__ sims,
+                                                                       int64_t n_ref_seg, const int32_t* __restrict__ qoff, int k,
+                                                                       int64_t* __restrict__ out) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int tid = threadIdx.x;
+  const int q0 = qoff[blockIdx.x], Sq = qoff[blockIdx.x + 1] - q0;
+  const int64_t E64 = (int64_t)Sq * k;
+  if (E64 <= 0 || E64 > UNIQ_LDS_ENTRIES) return;   // oversized image: the global launches handle it
+  const int E = (int)E64;
+  const uint32_t T = 2u * (uint32_t)E;
+  unsigned long long* t_id = reinterpret_cast<unsigned long long*>(smem);   // [T]
+  unsigned long long* t_key = t_id + T;                                      // [T]
+  for (uint32_t j = tid; j < 2u * T; j += UNIQ_THREADS) t_id[j] = 0ull;
+  __syncthreads();
+  for (int o = tid; o < E; o += UNIQ_THREADS) {
+    const int rank = o / Sq, seg = o - rank * Sq;
+    const int64_t at = (int64_t)(q0 + seg) * k + rank;
+    const int64_t id = idx[at];
+    if (id >= 0 && id < n_ref_seg) uniq_insert<__HIP_MEMORY_SCOPE_WORKGROUP>(t_id, t_key, T, id, uniq_key(sims, at, (uint32_t)o));
+  }
+  __syncthreads();
+  for (int o = tid; o < E; o += UNIQ_THREADS) {
+    const int rank = o / Sq, seg = o - rank * Sq;
+    const int64_t at = (int64_t)(q0 + seg) * k + rank;
+    const int64_t id = idx[at];
+    const bool ok = id >= 0 && id < n_ref_seg;
+    out[at] = (ok && uniq_best(t_id, t_key, T, id) != uniq_key(sims, at, (uint32_t)o)) ? -1 : id;
+  }
+}
+
+// RESOLVE = false: insert.  RESOLVE = true: write the copy.  Grid (images b0 .. b0 + gridDim.x - 1, chunks); an image of that
+// range that fits the LDS kernel is skipped.
+template <bool RESOLVE>
+__global__ __launch_bounds__(UNIQ_G_THREADS) void vote_unique_global_kernel(const int64_t* __restrict__ idx, const float* __restrict__ sims,
+                                                                            int64_t n_ref_seg, const int32_t* __restrict__ qoff, int k,
+                                                                            int b0, unsigned long long* __restrict__ table,
+                                                                            int64_t* __restrict__ out) {
+  const int b = b0 + (int)blockIdx.x;
+  const int q0 = qoff[b], Sq = qoff[b + 1] - q0;
+  const int64_t E = (int64_t)Sq * k;
+  if (E <= UNIQ_LDS_ENTRIES) return;
+  const uint32_t T = (uint32_t)(2 * E);
+  unsigned long long* t_id = table + 4 * (int64_t)(q0 - qoff[b0]) * k;   // 2 slots per entry, 2 words per slot
+  unsigned long long* t_key = t_id + T;
+  const int64_t o_end = min(E, ((int64_t)blockIdx.y + 1) * UNIQ_G_PER_BLOCK);
+  for (int64_t o = (int64_t)blockIdx.y * UNIQ_G_PER_BLOCK + threadIdx.x; o < o_end; o += UNIQ_G_THREADS) {
+    const int rank = (int)(o / Sq), seg = (int)(o - (int64_t)rank * Sq);
+    const int64_t at = (int64_t)(q0 + seg) * k + rank;
+    const int64_t id = idx[at];
+    const bool ok = id >= 0 && id < n_ref_seg;
+    if (!RESOLVE) {
+      if (ok) uniq_insert<__HIP_MEMORY_SCOPE_AGENT>(t_id, t_key, T, id, uniq_key(sims, at, (uint32_t)o));
+    } else {
+      out[at] = (ok && uniq_best(t_id, t_key, T, id) != uniq_key(sims, at, (uint32_t)o)) ? -1 : id;
+    }
+  }
+}
+
+// out [nq][k] = idx with every valid entry that is not its id's winner within its query image set to -1.  *launches: what was
+// enqueued (1 for the images the LDS table holds, 3 -- table fill, insert, resolve -- for the larger ones).
+int sv_launch_vote_unique(segvlad_ctx* ctx, const int64_t* idx, const float* sims, int64_t n_ref_seg, const int32_t* qoff_dev,
+                          const int32_t* qoff_host, int n_img, int k, int64_t* out, int* launches) {
+  *launches = 0;
+  int64_t e_small = 0, e_big = 0;
+  int b_first = -1, b_last = -1;
+  for (int i = 0; i < n_img; ++i) {
+    const int s = qoff_host[i + 1] - qoff_host[i];
+    if (s < 0) return ctx->fail(SEGVLAD_ERR_ARG, "vote: qseg_offsets must be non-decreasing");
+    const int64_t e = (int64_t)s * k;
+    if (e > UNIQ_LDS_ENTRIES) {
+      if (b_first < 0) b_first = i;
+      b_last = i;
+      if (e > e_big) e_big = e;
+    } else if (e > e_small) {
+      e_small = e;
+    }
+  }
+  if (e_big > (1ll << 24)) return ctx->fail(SEGVLAD_ERR_LIMIT, "vote: %lld entries per query image", (long long)e_big);
+  if (e_small > 0) {
+    const size_t lds = (size_t)e_small * 32;   // 2 slots per entry, 16 B per slot
+    if (lds > 64 * 1024) SV_HIP(sv_max_dyn_lds(reinterpret_cast<const void*>(vote_unique_lds_kernel), lds));
+    hipLaunchKernelGGL(vote_unique_lds_kernel, dim3(n_img), dim3(UNIQ_THREADS), lds, ctx->stream, idx, sims, n_ref_seg, qoff_dev, k, out);
+    SV_HIP(hipGetLastError());
+    *launches += 1;
+  }
+  if (b_first >= 0) {
+    const size_t bytes = (size_t)(qoff_host[b_last + 1] - qoff_host[b_first]) * k * 32;
+    SV_HIP(ctx->s_vote_tab.reserve(bytes));
+    SV_HIP(hipMemsetAsync(ctx->s_vote_tab.p, 0, bytes, ctx->stream));
+    const dim3 grid((unsigned)(b_last - b_first + 1), (unsigned)((e_big + UNIQ_G_PER_BLOCK - 1) / UNIQ_G_PER_BLOCK));
+    hipLaunchKernelGGL(vote_unique_global_kernel<false>, grid, dim3(UNIQ_G_THREADS), 0, ctx->stream, idx, sims, n_ref_seg, qoff_dev, k,
+                       b_first, ctx->s_vote_tab.as<unsigned long long>(), out);
+    SV_HIP(hipGetLastError());
+    hipLaunchKernelGGL(vote_unique_global_kernel<true>, grid, dim3(UNIQ_G_THREADS), 0, ctx->stream, idx, sims, n_ref_seg, qoff_dev, k,
+                       b_first, ctx->s_vote_tab.as<unsigned long long>(), out);
+    SV_HIP(hipGetLastError());
+    *launches += 3;
+  }
+  return SEGVLAD_OK;
+}
+
 int sv_launch_vote(segvlad_ctx* ctx, const int64_t* idx, const float* sims, const int32_t* img_of_seg,
                    int64_t n_ref_seg, const int32_t* qoff_dev, const int32_t* qoff_host, int n_img, int k,
                    const float* minmax_dev, int n_top, int mode, int32_t* pred, double* score) {

@@ -367,6 +367,43 @@ def blank_capped(idx, img_of_seg, per_image: int) -> np.ndarray:
     return out
 
 
+def blank_unique(idx, sims, qseg_offsets, n_ref_seg: int) -> np.ndarray:
+    """The rule of segvlad_vote's one-to-one flag (SEGVLAD_VOTE_UNIQUE_REF), stated on the host: ``idx [nq][k]`` int64, ``sims
+    [nq][k]`` float32 or None, ``qseg_offsets [n_img + 1]``.  An entry is valid when ``0 <= idx < n_ref_seg``.  Among the valid
+    entries of one query image that carry the same id one wins: the largest sim (a NaN loses to every number, -0.0 == +0.0),
+    then -- on a tie, or without ``sims`` -- the first in the vote's visiting order (rank-major, then segment).  Returns a copy of
+    ``idx`` with every other valid entry set to -1: the plain vote over it is the flagged vote over ``idx``.  A per-image cap in
+    the same mode word is applied behind it: blank_capped(blank_unique(...), img_of_seg, m)."""
+    idx = np.asarray(idx.detach().cpu().numpy() if isinstance(idx, torch.Tensor) else idx, dtype=np.int64)
+    if idx.ndim != 2:
+        raise ValueError(f"idx must be [nq][k], got {idx.shape}")
+    if sims is not None:
+        sims = np.asarray(sims.detach().cpu().numpy() if isinstance(sims, torch.Tensor) else sims, dtype=np.float32)
+        if sims.shape != idx.shape:
+            raise ValueError(f"sims must have idx's shape {idx.shape}, got {sims.shape}")
+    off = np.asarray(qseg_offsets, dtype=np.int64).reshape(-1)
+    out = idx.copy()
+    for b in range(len(off) - 1):
+        rows = slice(off[b], off[b + 1])
+        ids = idx[rows].T.reshape(-1)                        # visiting order: position p
+        pos = np.nonzero((ids >= 0) & (ids < n_ref_seg))[0]
+        if len(pos) == 0:
+            continue
+        if sims is None:
+            order = np.lexsort((pos, ids[pos]))
+        else:
+            s = sims[rows].T.reshape(-1)[pos]
+            nan = np.isnan(s)
+            order = np.lexsort((pos, -np.where(nan, np.float32(0), s), nan, ids[pos]))   # by id; numbers first, descending; then p
+        sorted_ids = ids[pos][order]
+        lose = np.ones(len(pos), bool)
+        lose[order[np.concatenate([[True], sorted_ids[1:] != sorted_ids[:-1]])]] = False
+        view = out[rows].T.reshape(-1)                       # (a copy: the transpose of a slice is not contiguous)
+        view[pos[lose]] = -1
+        out[rows] = view.reshape(idx.shape[1], -1).T
+    return out
+
+
 def expand_radius2(radius2, nq: int, qseg_offsets=None) -> np.ndarray:
     """``radius2`` of range_search as one fp32 value per query row: a scalar, ``[nq]``, or -- with ``qseg_offsets`` --
     ``[n_img]`` (repeated over each image's rows).  Raises ValueError on any other shape."""
@@ -522,11 +559,11 @@ class SegVLADEngine:
         return d2, idx
 
     def vote_global(self, idx, sims, qseg_offsets, n_top=5, mode=_lib.VOTE_WT_BORDA_IM, img_of_seg=None, want_scores=True,
-                    per_image=None):
+                    per_image=None, unique_ref=False):
         """Collective (query-sharded retrieval): vote() over this rank's query images with the min / max of the similarities of
         ALL ranks of the context's communicator (func_vpr.py:211-214).  Every rank calls it, a rank without images included
-        (idx / sims [0, k]).  ``per_image``: vote()'s cap."""
-        mode = _lib.vote_mode(mode, per_image)
+        (idx / sims [0, k]).  ``per_image``, ``unique_ref``: vote()'s."""
+        mode = _lib.vote_mode(mode, per_image, unique_ref)
         i = _as(idx, np.int64, torch.int64)
         s = None if sims is None else _as(sims, np.float32, torch.float32)
         qo = np.ascontiguousarray(qseg_offsets, dtype=np.int32)
@@ -1338,11 +1375,14 @@ class SegVLADEngine:
         return out
 
     def vote(self, idx, sims, qseg_offsets, n_top=5, mode=_lib.VOTE_WT_BORDA_IM, img_of_seg=None, smin=float("nan"),
-             smax=float("nan"), want_scores=True, per_image=None):
+             smax=float("nan"), want_scores=True, per_image=None, unique_ref=False):
         """segvlad_vote.  ``per_image`` (1 .. 255): every query segment gives a reference image at most that many hits -- the
         vote over blank_capped(idx, img_of_seg, per_image), bit for bit (SEGVLAD_VOTE_PER_IMAGE; an int ``mode`` that already
-        carries the bits is accepted as it is)."""
-        mode = _lib.vote_mode(mode, per_image)
+        carries the bits is accepted as it is).  ``unique_ref``: a reference segment votes once per query image -- the vote over
+        blank_unique(idx, sims, qseg_offsets, n_ref_seg), bit for bit (SEGVLAD_VOTE_UNIQUE_REF); the most similar of an image's
+        claims on a segment wins wherever ``sims`` is given, COUNT included, the first visited without.  With both, the cap is
+        applied to the one-to-one lists."""
+        mode = _lib.vote_mode(mode, per_image, unique_ref)
         i = _as(idx, np.int64, torch.int64)
         s = None if sims is None else _as(sims, np.float32, torch.float32)
         qo = np.ascontiguousarray(qseg_offsets, dtype=np.int32)

@@ -230,7 +230,7 @@ class SegVLADPipeline:
     # ---- a10..a12: descriptors -> ranked reference images ----------------------------------------------
     def retrieve(self, qdesc: torch.Tensor, qseg_offsets: np.ndarray, k_search: int = 200, k_vote: int = 50, n_top: int = 5,
                  mode: int = _lib.VOTE_WT_BORDA_IM, want_scores: bool = False, vote_depth_only: bool = False, shortlist=None,
-                 exclude=None, per_image=None, votes_per_image=None):
+                 exclude=None, per_image=None, votes_per_image=None, vote_unique_ref=False):
         """search k_search (place_rec_main.py:56) -> keep k_vote and 2-d^2 (:78-81) -> vote (:84).  vote_depth_only: search
         only as deep as the vote reads (the 200-wide lists are only pickled under save_results, :61-75): the same k_vote columns
         -- an exact search's first columns do not depend on its depth -- for a quarter of the refinement.
@@ -248,8 +248,11 @@ class SegVLADPipeline:
         votes_per_image (1 .. 255): the cap is applied in the VOTE instead (engine.vote's ``per_image``): of every query
         segment's k_vote entries at most that many count for one reference image, the others are skipped and nothing moves up
         behind them.  No second search, and it combines with ``shortlist``, ``exclude`` and ``per_image``; the extrema passed
-        for the derived searches stay those of the filled slots."""
-        mode = _lib.vote_mode(mode, votes_per_image)
+        for the derived searches stay those of the filled slots.
+        vote_unique_ref: a reference segment votes once per query image (engine.vote's ``unique_ref``): of the entries of one
+        query image that name the same index row only the most similar one counts.  In front of ``votes_per_image``; combines
+        with everything above."""
+        mode = _lib.vote_mode(mode, votes_per_image, vote_unique_ref)
         if shortlist is not None and exclude is not None:
             raise ValueError("retrieve: give shortlist or exclude, not both")
         if per_image is not None and (shortlist is not None or exclude is not None):
@@ -269,7 +272,7 @@ class SegVLADPipeline:
         self.last_search = (d2, idx)   # the full-depth lists: what `save_results` pickles (place_rec_main.py:61-75)
         sims, m = self.eng.sims_from_d2(d2, idx, k_vote)
         smin = smax = float("nan")
-        if (shortlist is not None or exclude is not None or per_image is not None) and (mode & 0xFF) == _lib.VOTE_WT_BORDA_IM:
+        if (shortlist is not None or exclude is not None or per_image is not None) and (mode & 0x7F) == _lib.VOTE_WT_BORDA_IM:
             kept = sims[m >= 0]
             if kept.numel():
                 smin, smax = float(kept.min()), float(kept.max())

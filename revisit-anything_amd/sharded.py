@@ -268,15 +268,16 @@ class ShardedSegmentIndex:
         return d2c, idc
 
     def retrieve(self, Q, qseg_offsets: Sequence[int], k_search: int = 200, k_vote: int = 50, n_top: int = 5, mode: int = 0,
-                 want_scores: bool = False, vote_depth_only: bool = False, votes_per_image=None):
+                 want_scores: bool = False, vote_depth_only: bool = False, votes_per_image=None, vote_unique_ref=False):
         """search -> keep k_vote, 2-d^2 -> vote with the global segment->image map.  The global min/max of the
         vote (func_vpr.py:212-213) is taken over the merged (global) similarities, so it needs no extra collective.
         vote_depth_only: a caller that does not keep the k_search-wide lists (place_rec_main.py:61-75 pickles them only under
         save_results) may have a single index search k_vote deep as well -- same first k_vote columns, same votes.
         votes_per_image (1 .. 255): at most that many hits per reference image from each query segment, capped in the vote
         (the backend's vote takes it in ``mode``, _lib.vote_mode): the lists are the merged global ones, so the result is the
-        single index's."""
-        mode = vote_mode(mode, votes_per_image)
+        single index's.  vote_unique_ref: a reference segment votes once per query image (SEGVLAD_VOTE_UNIQUE_REF, in ``mode``
+        as well); the ids of the merged lists are global rows, so the result is again the single index's."""
+        mode = vote_mode(mode, votes_per_image, vote_unique_ref)
         if hasattr(self.be, "hint_query_groups"):   # an image's rows as one group of the exact refinement (same results)
             self.be.hint_query_groups(qseg_offsets)
         if self.world > 1 or vote_depth_only:
@@ -377,14 +378,15 @@ class QueryShardedRetrieval:
     # ---- query --------------------------------------------------------------------------------------
     def retrieve(self, Q_local, qseg_offsets_local: Sequence[int], k_search: int = 200, k_vote: int = 50, n_top: int = 5,
                  mode: int = 0, want_scores: bool = False, vote_depth_only: bool = False, n_query_images: Optional[int] = None,
-                 votes_per_image=None) -> dict:
+                 votes_per_image=None, vote_unique_ref=False) -> dict:
         """This rank's images: Q_local [nq_local, d] (their segment rows), qseg_offsets_local [n_img_local + 1] (from 0).
         Collective: every rank calls it, with the split of split(n_query_images) (or n_query_images given here).
         Returns {"pred", "score"}: the GATHERED [n_query_images, n_top] predictions / fp64 scores in global image order,
         identical on every rank (score None unless want_scores), and {"pred_local", "score_local", "m", "sims"}: this rank's.
         votes_per_image (1 .. 255): at most that many hits per reference image from each query segment, capped in the vote
-        (in ``mode``, _lib.vote_mode); the global extrema stay those of all kept similarities."""
-        mode = vote_mode(mode, votes_per_image)
+        (in ``mode``, _lib.vote_mode); the global extrema stay those of all kept similarities.  vote_unique_ref: a reference
+        segment votes once per query image (SEGVLAD_VOTE_UNIQUE_REF, in ``mode`` as well); an image's rows live on one rank."""
+        mode = vote_mode(mode, votes_per_image, vote_unique_ref)
         if n_query_images is not None:
             self.split(n_query_images)
         if self.img_bounds is None:
@@ -429,7 +431,7 @@ class QueryShardedRetrieval:
     def _global_extrema(self, sims, nq: int, local_err, mode: int):
         """torch.distributed transport: this rank's record -> all_gather -> the exact global (min, max) on the host."""
         rec = torch.tensor([0x7F800000, -0x00800000, 1 if local_err is not None else 0, 0], dtype=torch.int32, device=self.device)
-        if local_err is None and nq and (mode & 0xFF) == 0:
+        if local_err is None and nq and (mode & 0x7F) == 0:
             mm = torch.as_tensor(self.be.minmax(sims)).to(self.device).to(torch.float32).contiguous()
             rec = torch.cat([mm.view(torch.int32), torch.tensor([0, nq], dtype=torch.int32, device=self.device)])
         if self.world > 1:

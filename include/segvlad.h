@@ -687,6 +687,40 @@ int segvlad_stage_ms(segvlad_ctx* ctx, const char* stage, float* ms_out, int* la
  *                                                      group), row by row otherwise
  *        "refine_group"  1 | 0 | 2                     that grouped refinement | every row on its own (rounds 1-4) | every group
  *                                                      whose union fits, whatever the cost model says (tests); same bits
+ *        "vlad_assign"   hard | soft:<T> | soft_pooled:<T>
+ *                                                      how a token is assigned to the centres (utilities.py:862-887, VLAD.generate's
+ *                                                      vlad_mode / soft_temp).  hard (the default): every token goes to its
+ *                                                      nearest centre; every call issues the launches and returns the bytes it
+ *                                                      does without the option.  soft:<T>, T a decimal fp32 temperature, finite
+ *                                                      and > 0: every token goes to EVERY centre.  With x^_n the L2-normalised
+ *                                                      token n of the image, c_k the raw centre, c^_k its normalised copy and
+ *                                                      U(s) the token set of segment s after the neighbour union (adj; identity
+ *                                                      for order 0):
+ *                                                        w[n][k] = softmax over the K real centres of T * <x^_n, c^_k>
+ *                                                                  (max-subtracted; padded centres take no part)
+ *                                                        V[s][k] = sum_{n in U(s)} w[n][k] x^_n - (sum_{n in U(s)} w[n][k]) c_k
+ *                                                        out[s]  = L2( concat_k intra_norm(V[s][k]) )
+ *                                                      intra_norm and L2 divide by max(norm, 1e-12) like the hard path, so a
+ *                                                      segment that covers no token is a row of zeros and an all-zero block
+ *                                                      stays zero.  soft_pooled:<T> has the same weights, normalisations and
+ *                                                      outputs, and takes every block against ALL centres,
+ *                                                        V[s][k] = sum_{n in U(s)} w[n][k] sum_c (x^_n - c_c)
+ *                                                                = K sum_n w[n][k] x^_n - (sum_n w[n][k]) sum_c c_c
+ *                                                      which is what VLAD.generate computes (utilities.py:883-884 sums the
+ *                                                      weighted residuals over tokens and centres): with one all-token segment
+ *                                                      per image and order 0 it is that function on normalised tokens, as aggFt
+ *                                                      calls it.  soft:<T> tends to the hard descriptor as T grows, soft_pooled
+ *                                                      does not.  Both cover segvlad_images, segvlad_images_pca, segvlad_describe
+ *                                                      and segvlad_describe_begin / _end; labels_out and gap_out stay the hard
+ *                                                      arg-max and the top-1 / top-2 gap, block_norms_out is ||V[s][k]|| of the
+ *                                                      soft blocks.  Sums run in a fixed order without float atomics: two calls
+ *                                                      return the same bytes and an image's rows do not depend on the rest of
+ *                                                      the batch.  The "project" form of pca_path presupposes one cluster per
+ *                                                      token: under soft, auto takes "planes" and an explicit project is
+ *                                                      SEGVLAD_ERR_LIMIT.  segvlad_kmeans_step and segvlad_cluster_aggregate
+ *                                                      ignore the option (hard by definition).  A missing, empty, non-positive,
+ *                                                      non-finite or junk-trailed T and any other spelling are SEGVLAD_ERR_ARG
+ *                                                      and leave the option as it was
  *      Every other key is a DEVELOPMENT switch (kernel tuning, A/B variants, debugging, the tests' own hooks), documented in
  *      revisit-anything_amd/csrc/segvlad_dev.h and NOT part of this ABI: none changes a result, the shipped library holds
  *      only the kernels they default to and rejects the values that select another (SEGVLAD_ERR_ARG).

@@ -269,6 +269,26 @@ int segvlad_set_option(segvlad_ctx* ctx, const char* key, const char* value) {
     else return ctx->fail(SEGVLAD_ERR_ARG, "set_option(pca_path): want auto|planes|project, got '%s'", value);
     return SEGVLAD_OK;
   }
+  if (!strcmp(key, "vlad_assign")) {   // hard | soft:<T> | soft_pooled:<T>, T a decimal fp32, finite, > 0 (include/segvlad.h); a refusal
+                                       // changes nothing
+    if (!strcmp(value, "hard")) {
+      o.vlad_soft_temp = 0.f, o.vlad_soft_pooled = 0;
+      return SEGVLAD_OK;
+    }
+    const int pooled = !strncmp(value, "soft_pooled:", 12);
+    if (pooled || !strncmp(value, "soft:", 5)) {
+      const char* t = value + (pooled ? 12 : 5);
+      bool decimal = *t != 0 && (*t == '.' || (*t >= '0' && *t <= '9'));
+      for (const char* c = t; *c && decimal; ++c) decimal = strchr("0123456789.eE+-", *c) != nullptr;
+      char* end = nullptr;
+      const float temp = decimal ? strtof(t, &end) : 0.f;
+      if (decimal && end != t && *end == 0 && std::isfinite(temp) && temp > 0.f) {
+        o.vlad_soft_temp = temp, o.vlad_soft_pooled = pooled;
+        return SEGVLAD_OK;
+      }
+    }
+    return ctx->fail(SEGVLAD_ERR_ARG, "set_option(vlad_assign): want hard|soft:<T>|soft_pooled:<T> with a finite decimal T > 0, got '%s'", value);
+  }
   // Switches that select one of the fp16 filter's kernels (csrc/segvlad_dev.h): only the values that name a kernel the library
   // holds are accepted -- the measured-and-not-kept variants are gone from the tree (DESIGN.md 4 / 7 keep their numbers); the
   // development build (-DSEGVLAD_ABLATIONS: lib/libsegvlad_hip_abl.so) adds the probes of the batch kernel.

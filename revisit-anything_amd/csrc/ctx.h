@@ -196,6 +196,8 @@ struct SvOptions {
   int pca_path = 0;       // fused images_pca: 0 auto, 1 "planes" (descriptor planes x W), 2 "project" (project tokens, then aggregate)
   int cover_rows = 1;     // project form: only the tokens some segment covers get a row of the grouped planes and of Z (prep_kernel's
                           // `phys` map; same bits: every kernel keeps its logical positions); 0 = every token gets a row
+  float vlad_soft_temp = 0.f;   // "vlad_assign": 0 = hard; > 0 = soft assignment at this temperature (soft_vlad_kernels.hip)
+  int vlad_soft_pooled = 0;     // "vlad_assign" = soft_pooled:<T>: every block's residuals are taken against ALL centres (the reference's sum)
   int group_fetch = 0;    // segvlad_search_grouped: depth of the inner search, clamped to k .. 1024 (0 = min(1024, 4 k)); never changes a
                           // result, only which rows the exact tail finishes (tests reach the tail on a small index with it)
 };
@@ -368,13 +370,15 @@ struct segvlad_ctx {
   //  s_vote_cap: segvlad_vote with a per-image cap (vote_kernels.hip) -- the blanked copy of idx [nq][k] that the vote then reads;
   //  s_vote_uniq, s_vote_tab: segvlad_vote with SEGVLAD_VOTE_UNIQUE_REF -- the copy of idx [nq][k] with the non-winning claims on a
   //  reference segment blanked (the cap and the vote read it), and the {id, best key} hash tables of the query images that the
-  //  LDS table does not hold (2 slots of 16 B per entry, zeroed per call)
+  //  LDS table does not hold (2 slots of 16 B per entry, zeroed per call);
+  //  s_softw: the describe stage under vlad_assign=soft (soft_vlad_kernels.hip) -- the assignment weights w [B][N][K] of the batch;
+  //  s_softc: under vlad_assign=soft_pooled -- the mean centre [D]
 #define SV_SCRATCH_BUFS(X)                                                                                                      \
   X(s_xt) X(s_labels) X(s_rnorm) X(s_gap) X(s_colmask) X(s_gscale) X(s_segimg) X(s_segoff) X(s_adjoff) X(s_dist) X(s_qnorm)      \
   X(s_misc) X(s_minmax) X(s_voteoff) X(s_cand_cnt) X(s_cand_d2) X(s_cand_id) X(s_thr_d2) X(s_thr_idx) X(s_flag) X(s_qh) X(s_ql)  \
   X(s_ref_cnt) X(s_ref_id) X(s_qscale) X(s_qf16) X(s_xh1) X(s_xh2) X(s_desc) X(s_tokorder) X(s_laboff) X(s_rnsorted) X(s_ovf)     \
   X(s_fb_q) X(s_fb_d2) X(s_fb_idx) X(s_fb_rows) X(s_rd_rows) X(s_rd_q) X(s_rd_d2) X(s_rd_idx) X(s_rd_flags) X(s_rd_p1) X(s_rd_p2)  \
-  X(s_sel_todo) X(s_vote_keys) X(s_vote_cap) X(s_vote_uniq) X(s_vote_tab) X(s_pz) X(s_rowbase) X(s_tilegrp) X(s_phys) X(s_covcnt) X(s_bn) X(s_l0part) X(s_ref_lim) X(s_sh_d2) X(s_sh_idx)          \
+  X(s_sel_todo) X(s_vote_keys) X(s_vote_cap) X(s_vote_uniq) X(s_vote_tab) X(s_softw) X(s_softc) X(s_pz) X(s_rowbase) X(s_tilegrp) X(s_phys) X(s_covcnt) X(s_bn) X(s_l0part) X(s_ref_lim) X(s_sh_d2) X(s_sh_idx)          \
   X(s_sh_rec) X(s_sh_all) X(s_sh_d2c) X(s_sh_idc) X(s_grp_cnt) X(s_grp_ids) X(s_grp_rows) X(s_grp_keys) X(s_grp_work) X(s_grp_pos) X(s_tnk_redo) X(s_tail_part) X(s_km_part) X(s_km_cnt) X(s_kflush) \
   X(s_sl_misc) X(s_sl_q) X(s_sl_cur) X(s_sl_uids) X(s_sl_uoff) X(s_sl_unum) X(s_sl_cand) X(s_sl_lens)                            \
   X(s_deep_d2) X(s_deep_idx) X(s_deep_qn) X(s_ex_flag) X(s_ex_td2) X(s_ex_tidx)                                                        \
@@ -483,6 +487,18 @@ int sv_launch_aggregate(segvlad_ctx* ctx, const float* xt, const float* rnorm, c
                         const uint64_t* colmask, const float* centres, int K, int D, const int32_t* seg_off_dev,
                         const float* gscale, int B, int N, int SC, float* out, float* block_norms,
                         const float* mean = nullptr, float xscale = 0.f, uint16_t* h1 = nullptr, uint16_t* h2 = nullptr);
+
+// soft_vlad_kernels.hip (option vlad_assign=soft:<T>; after sv_launch_prep, whose label-grouped token order, 1/||x|| and column masks
+// they read).  weights: w[b][n][0..K) = softmax_k(temp * <x^_n, c^_k>) from the channel-major tokens.  aggregate: the intra-normalised
+// blocks V[s][k] / max(||V[s][k]||, 1e-12) into out [S][K*D] and ||V[s][k]|| into block_norms [S][K] (never null); with mean_centre
+// (soft_pooled: [D] from sv_launch_soft_centre_mean) every block is K sum w (x^ - mean centre), the residuals against all K centres.
+// finalize: every row of out scaled to unit length from its block norms.
+int sv_launch_soft_weights(segvlad_ctx* ctx, const float* tokens, int B, int N, float temp, float* w);
+int sv_launch_soft_centre_mean(segvlad_ctx* ctx, const float* centres, int K, int D, float* mean_centre);
+int sv_launch_soft_aggregate(segvlad_ctx* ctx, const float* xt, const float* w, const uint64_t* colmask, const float* centres, int K, int D,
+                             const int32_t* seg_off_dev, int B, int N, int SC, float* out, float* block_norms,
+                             const float* mean_centre = nullptr);
+int sv_launch_soft_finalize(segvlad_ctx* ctx, const float* block_norms, int S_tot, int K, int D, float* out);
 
 // block norms + the fp16 planes of the token residuals x^ - C_k, grouped by cluster (rowbase from sv_launch_group_plan); after sv_launch_prep
 int sv_launch_token_norms(segvlad_ctx* ctx, const float* xt, const uint64_t* colmask, const float* centres, int K, int D,

@@ -100,6 +100,8 @@ struct DescribePlan {
   std::vector<int64_t> adj_off;   // [B + 1]: where image b's S_b x S_b adjacency block starts
   float xscale = 1.f;      // power-of-two scale of the fp16 planes (Planes: descriptor - mean; Project: token residuals)
   float zscale = 0.f;      // Project: scale of the projected residuals on the 16-bit pipe (0: fp32 MFMA)
+  float soft_temp = 0.f;   // option vlad_assign: 0 = hard; > 0 = soft assignment at this temperature (soft_vlad_kernels.hip)
+  bool soft_pooled = false;   // ... soft_pooled:<T>: residuals against all centres
   int64_t rows_pad = 0;    // Project: grouped token rows, every cluster's rows padded to whole 256-row GEMM tiles
   bool want_desc = false, want_y = false, want_labels = false, want_gap = false, want_block_norms = false;   // the optional outputs
   bool upload_offsets = false;   // this call puts the segment / adjacency offsets on the device (else: the mask branch of its begin did)
@@ -119,9 +121,16 @@ static DescribePlan plan_describe(const segvlad_ctx* ctx, const DescribeIO& io, 
     if (B > 0 && io.seg_offsets && !sv_is_device_ptr(io.seg_offsets) && io.seg_offsets[B] > 0 && !io.y)
       return PLAN_REFUSE(SEGVLAD_ERR_ARG, "images_pca: null y");
     if (!x3 && passes != Passes::All) return PLAN_REFUSE(SEGVLAD_ERR_STATE, "describe: the split call needs the fp16x3 projection (pca_arith)");
+    // the project form gives every token the slice of ONE cluster: auto takes the planes form under soft, an explicit choice is refused
+    if (ctx->opt.vlad_soft_temp > 0.f && ctx->opt.pca_path == 2)
+      return PLAN_REFUSE(SEGVLAD_ERR_LIMIT, "images_pca: pca_path=project presupposes one cluster per token, vlad_assign=%s:%g has none "
+                                            "(set pca_path to auto or planes, or vlad_assign to hard)",
+                         ctx->opt.vlad_soft_pooled ? "soft_pooled" : "soft", (double)ctx->opt.vlad_soft_temp);
   }
   if (K == 0) return PLAN_REFUSE(SEGVLAD_ERR_STATE, "images: call segvlad_set_vocab first");
   p.passes = passes, p.B = B, p.N = N, p.K = K, p.D = D, p.P = ctx->P, p.nw = (N + 63) / 64, p.l2norm = io.l2norm;
+  p.soft_pooled = ctx->opt.vlad_soft_pooled != 0;
+  p.soft_temp = ctx->opt.vlad_soft_temp;   // (read by the passes behind prep alone: an assign-only plan is the hard assignment)
   if (passes == Passes::AssignOnly)   // tokens -> token-major copy, norms, labels in the context's scratch; no segments yet
     return (B <= 0 || N <= 0 || !io.tokens) ? PLAN_REFUSE(SEGVLAD_ERR_ARG, "images: B=%d N=%d", B, N) : p;
   if (B < 0 || N <= 0) return PLAN_REFUSE(SEGVLAD_ERR_ARG, "images: B=%d N=%d", B, N);
@@ -147,7 +156,7 @@ static DescribePlan plan_describe(const segvlad_ctx* ctx, const DescribeIO& io, 
   // "project then aggregate" (project_kernels.hip) when the descriptor itself is not asked for.  auto: when it is the smaller product
   // (N D P per image against S K D P) and the batch holds >= 128 tokens per cluster on average -- every cluster's rows are padded to
   // whole 256-row GEMM tiles, below that the split-K descriptor GEMM is quicker ("The fused VLAD -> PCA call", has the numbers)
-  const bool project = io.out == nullptr && D % 32 == 0 && ctx->P % 4 == 0 && ctx->opt.pca_path != 1 &&
+  const bool project = p.soft_temp == 0.f && io.out == nullptr && D % 32 == 0 && ctx->P % 4 == 0 && ctx->opt.pca_path != 1 &&
                        (ctx->opt.pca_path == 2 || ((double)p.S_tot * K >= 1.25 * (double)B * N && (double)B * N >= 128.0 * K));
   p.form = project ? DescribeForm::Project : DescribeForm::Planes;
   p.xscale = sv_fp16_scale(1.f + ctx->pca_mean_maxabs);
@@ -194,6 +203,12 @@ static int reserve_scratch(segvlad_ctx* ctx, const DescribePlan& p, DescribeIO& 
   SV_HIP(ctx->s_rnorm.reserve(B * N * sizeof(float)));
   if (!p.want_labels) SV_HIP(ctx->s_labels.reserve(B * N));
   if (p.passes == Passes::AssignOnly) return SEGVLAD_OK;
+  if (p.soft_temp > 0.f && S > 0) {   // the weights, the block norms the row scale is made of, the descriptor the planes are split from
+    SV_HIP(ctx->s_softw.reserve(B * N * K * sizeof(float)));
+    if (p.soft_pooled) SV_HIP(ctx->s_softc.reserve(D * sizeof(float)));
+    if (!p.want_block_norms) SV_HIP(ctx->s_bn.reserve(S * K * sizeof(float)));
+    if (p.form == DescribeForm::Planes && !p.want_desc) SV_HIP(ctx->s_desc.reserve(S * K * D * sizeof(float)));
+  }
   SV_HIP(ctx->s_colmask.reserve(B * N * p.SC * 8));
   SV_HIP(ctx->s_gscale.reserve((S + 1) * sizeof(float)));
   SV_HIP(ctx->s_segoff.reserve((B + 1) * sizeof(int32_t)));
@@ -246,11 +261,41 @@ static int pass_normalize(segvlad_ctx* ctx, const DescribePlan& p, const Describ
   return SEGVLAD_OK;
 }
 
+// Soft assignment: the weights ("assign"), then intra-normalised blocks + block norms, the rows' scale, and for the planes form the
+// split of the finished fp32 descriptor that segvlad_pca_apply uses, at the scale known in advance ("aggregate")
+static int pass_soft_descriptor(segvlad_ctx* ctx, const DescribePlan& p, const DescribeIO& io, uint16_t* h1, uint16_t* h2) {
+  float* desc = io.d_out ? (float*)io.d_out : ctx->s_desc.as<float>();
+  float* bn = io.d_bn ? (float*)io.d_bn : ctx->s_bn.as<float>();
+  {
+    StageScope sc(ctx, "assign");
+    SV_TRY(sv_launch_soft_weights(ctx, (const float*)io.d_tok, p.B, p.N, p.soft_temp, ctx->s_softw.as<float>()));
+    sc.count();
+  }
+  StageScope sc(ctx, "aggregate");
+  const float* cmean = nullptr;
+  if (p.soft_pooled) {
+    SV_TRY(sv_launch_soft_centre_mean(ctx, ctx->vocab.as<float>(), p.K, p.D, ctx->s_softc.as<float>()));
+    sc.count();
+    cmean = ctx->s_softc.as<float>();
+  }
+  SV_TRY(sv_launch_soft_aggregate(ctx, ctx->s_xt.as<float>(), ctx->s_softw.as<float>(), ctx->s_colmask.as<uint64_t>(), ctx->vocab.as<float>(),
+                                  p.K, p.D, ctx->s_segoff.as<int32_t>(), p.B, p.N, p.SC, desc, bn, cmean));
+  SV_TRY(sv_launch_soft_finalize(ctx, bn, p.S_tot, p.K, p.D, desc));
+  sc.count(2);
+  if (h1) {
+    SV_TRY(sv_launch_split_f16x2(ctx, desc, p.S_tot, ctx->KD, ctx->pca_mean.as<float>(), p.xscale, h1, h2));
+    sc.count();
+  }
+  return SEGVLAD_OK;
+}
+
 // aggregate (Planes: the descriptor's fp16 planes beside or instead of the descriptor), then planes x W
 static int pass_descriptor(segvlad_ctx* ctx, const DescribePlan& p, const DescribeIO& io) {
   const bool fused = p.form == DescribeForm::Planes;
   uint16_t *h1 = fused ? ctx->s_xh1.as<uint16_t>() : nullptr, *h2 = fused ? ctx->s_xh2.as<uint16_t>() : nullptr;
-  {
+  if (p.soft_temp > 0.f) {
+    SV_TRY(pass_soft_descriptor(ctx, p, io, h1, h2));
+  } else {
     StageScope sc(ctx, "aggregate");
     SV_TRY(sv_launch_aggregate(ctx, ctx->s_xt.as<float>(), ctx->s_rnorm.as<float>(), (const uint8_t*)io.d_lab, ctx->s_colmask.as<uint64_t>(),
                                ctx->vocab.as<float>(), p.K, p.D, ctx->s_segoff.as<int32_t>(), ctx->s_gscale.as<float>(), p.B, p.N, p.SC,
@@ -377,6 +422,10 @@ static int describe_begin(segvlad_ctx* ctx, const MaskBranch& m, const float* to
   // Configurations the split call does not take are reported as SEGVLAD_ERR_LIMIT -- the code of "this entry point cannot, the separate
   // ones (incidence_centroids -> adjacency -> images[_pca]) can", which a caller can tell from misuse: an empty batch, and a
   // PCA model without the fp16x3 form (option pca_arith=fp32, or K*D not a multiple of 32: images_pca takes its PlainProjection form)
+  if (pca && ctx->opt.vlad_soft_temp > 0.f && ctx->opt.pca_path == 2)   // (plan_describe's refusal, before the mask branch is forked)
+    return ctx->fail(SEGVLAD_ERR_LIMIT, "describe: pca_path=project presupposes one cluster per token, vlad_assign=%s:%g has none "
+                                        "(set pca_path to auto or planes, or vlad_assign to hard)",
+                     ctx->opt.vlad_soft_pooled ? "soft_pooled" : "soft", (double)ctx->opt.vlad_soft_temp);
   if (B == 0 || S_tot <= 0) return ctx->fail(SEGVLAD_ERR_LIMIT, "describe: no images / no segments (use the separate entry points)");
   // ... and an image that sv_launch_adjacency would refuse: the same bound, asked before the mask branch is forked
   const SegWalk w = walk_seg_offsets(m.seg_offsets, B);

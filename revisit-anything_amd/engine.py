@@ -404,6 +404,68 @@ def blank_unique(idx, sims, qseg_offsets, n_ref_seg: int) -> np.ndarray:
     return out
 
 
+def vlad_assign_value(mode: str = "hard", temp=None) -> str:
+    """The value of the option ``vlad_assign`` for ``mode`` in {'hard', 'soft', 'soft_pooled'}: 'hard', or 'soft:<T>' /
+    'soft_pooled:<T>' with T printed so that it reads back as the same fp32.  Refuses what segvlad_set_option refuses: another mode, a temperature with 'hard', and a soft
+    temperature that is missing, not a number, not finite as fp32, or <= 0."""
+    if mode == "hard":
+        if temp is not None:
+            raise ValueError("vlad_assign: hard assignment takes no temperature")
+        return "hard"
+    if not isinstance(mode, str) or mode not in ("soft", "soft_pooled"):
+        raise ValueError(f"vlad_assign: mode must be 'hard', 'soft' or 'soft_pooled', got {mode!r}")
+    if temp is None or isinstance(temp, (bool, str, bytes)):
+        raise ValueError(f"vlad_assign: soft assignment needs a temperature, got {temp!r}")
+    try:
+        with np.errstate(over="ignore"):
+            t = np.float32(temp)
+    except (TypeError, ValueError):
+        raise ValueError(f"vlad_assign: the temperature must be a number, got {temp!r}") from None
+    if not np.isfinite(t) or not t > 0:
+        raise ValueError(f"vlad_assign: the temperature must be a finite fp32 > 0, got {temp!r}")
+    return mode + ":" + np.format_float_scientific(t, unique=True, trim="0")
+
+
+def soft_vlad_reference(tokens, centres, inc, adj=None, temp: float = 1.0, parts: bool = False, pooled: bool = False):
+    """The definition of ``vlad_assign=soft:<T>`` (include/segvlad.h; utilities.py:862-887) for ONE image, in NumPy fp64:
+    ``tokens [D][N]`` as the engine takes them, ``centres [K][D]`` raw, ``inc [S][N]`` bool incidence, ``adj [S][S]`` or None
+    (order 0), ``temp`` = T.
+
+        w[n][k] = softmax_k(T <x^_n, c^_k>)                          max-subtracted, over the K centres
+        V[s][k] = sum_{n in U(s)} w[n][k] x^_n - (sum_{n in U(s)} w[n][k]) c_k       U(s) = tokens of (adj . inc)[s] > 0
+        out[s]  = L2(concat_k intra_norm(V[s][k]))                   both divide by max(norm, 1e-12)
+
+    ``pooled``: the definition of ``vlad_assign=soft_pooled:<T>``, what the reference's ``VLAD.generate`` computes -- block k holds
+    the residuals against ALL centres, ``V[s][k] = K sum_n w[n][k] x^_n - (sum_n w[n][k]) sum_c c_c`` (utilities.py:883-884).
+
+    Returns ``out [S][K*D]``; with ``parts`` a dict that also holds ``w [N][K]`` and ``block_norms [S][K]``."""
+    def host(x):
+        return np.asarray(x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else x)
+
+    X = host(tokens).astype(np.float64).T                       # [N][D]
+    Cm = host(centres).astype(np.float64)                       # [K][D]
+    inc = host(inc).astype(bool)
+    if X.ndim != 2 or Cm.ndim != 2 or X.shape[1] != Cm.shape[1] or inc.ndim != 2 or inc.shape[1] != X.shape[0]:
+        raise ValueError(f"soft_vlad_reference: tokens [D][N], centres [K][D], inc [S][N]; got {X.T.shape}, {Cm.shape}, {inc.shape}")
+    if not (np.isfinite(temp) and temp > 0):
+        raise ValueError(f"soft_vlad_reference: temp must be finite and > 0, got {temp!r}")
+    S, (K, D) = inc.shape[0], Cm.shape
+    xh = X / np.maximum(np.linalg.norm(X, axis=1, keepdims=True), 1e-12)
+    ch = Cm / np.maximum(np.linalg.norm(Cm, axis=1, keepdims=True), 1e-12)
+    z = float(temp) * (xh @ ch.T)
+    e = np.exp(z - z.max(axis=1, keepdims=True))
+    w = e / e.sum(axis=1, keepdims=True)                        # [N][K]
+    U = inc if adj is None else (host(adj).astype(np.float64).reshape(S, S) @ inc.astype(np.float64)) > 0
+    Uf = U.astype(np.float64)
+    V = np.einsum("sn,nk,nd->skd", Uf, w, xh, optimize=True)
+    V = K * V - (Uf @ w)[:, :, None] * Cm.sum(0)[None, None] if pooled else V - (Uf @ w)[:, :, None] * Cm[None]
+    bn = np.linalg.norm(V, axis=2)                              # [S][K]
+    V = V / np.maximum(bn, 1e-12)[:, :, None]
+    out = V.reshape(S, K * D)
+    out = out / np.maximum(np.linalg.norm(out, axis=1, keepdims=True), 1e-12)
+    return {"out": out, "w": w, "block_norms": bn} if parts else out
+
+
 def expand_radius2(radius2, nq: int, qseg_offsets=None) -> np.ndarray:
     """``radius2`` of range_search as one fp32 value per query row: a scalar, ``[nq]``, or -- with ``qseg_offsets`` --
     ``[n_img]`` (repeated over each image's rows).  Raises ValueError on any other shape."""
@@ -444,6 +506,7 @@ class SegVLADEngine:
         self.pca_generation = 0
         self._keep = []  # tensors that must outlive async kernels of the last call
         self.n_img_ref = 0   # 1 + the largest img_of_seg id given to db_add since the last db_reset
+        self.vlad_assign = "hard"   # the value of the option vlad_assign as last set through set_vlad_assign / set_option
 
     # ---- plumbing ---------------------------------------------------------------------------------
     def close(self):
@@ -482,6 +545,23 @@ class SegVLADEngine:
     def set_option(self, key: str, value):
         """segvlad_set_option: arithmetic / tuning switches of this context (see include/segvlad.h)."""
         self._check(self.lib.segvlad_set_option(self._h, str(key).encode(), str(value).encode()), f"set_option({key})")
+        if key == "vlad_assign":
+            self.vlad_assign = str(value)
+
+    def set_vlad_assign(self, mode: str = "hard", temp=None) -> str:
+        """Option ``vlad_assign`` (include/segvlad.h): ``'hard'``, or ``'soft'`` / ``'soft_pooled'`` with the temperature of
+        ``softmax_k(temp * cos(x_n, c_k))``.  ``'soft'`` takes block k's residuals against c_k; ``'soft_pooled'`` against all
+        centres, which is what the reference's ``VLAD(vlad_mode='soft', soft_temp=...)`` computes.  Holds for every later
+        seg_vlad / seg_vlad_pca / describe* of this context; kmeans_step and cluster_aggregate ignore it.  Returns the value that
+        was in force before, in the form set_option takes (for callers that restore it).
+
+        That value is this object's own record (``self.vlad_assign``: 'hard' at creation, updated by its ``set_option``); the C
+        interface has no getter for options.  An option given to the context behind this object's back -- another wrapper on the
+        same handle -- is not seen, and a restore then puts back what THIS object last set."""
+        value = vlad_assign_value(mode, temp)
+        before = self.vlad_assign
+        self.set_option("vlad_assign", value)
+        return before
 
     def hint_query_groups(self, qseg_offsets) -> int:
         """Tell the search how the query rows of the coming batches are grouped (option ``query_group``): when every query

@@ -139,8 +139,31 @@ def _pack_incidence_bool(masks_bool: torch.Tensor) -> torch.Tensor:
     return (pad.view(S, nw, 64) << sh).sum(-1)  # bit 63 wraps into the sign bit, which is what we want
 
 
+class _vlad_assign:
+    """The engine's option vlad_assign set for a block and put back to what it was (None: left alone)."""
+
+    def __init__(self, eng, mode, temp=None):
+        self.eng, self.mode, self.temp, self.before = eng, mode, temp, None
+
+    def __enter__(self):
+        if self.mode is not None:
+            self.before = self.eng.set_vlad_assign(self.mode, self.temp if self.mode != "hard" else None)
+        return self
+
+    def __exit__(self, *exc):
+        if self.before is not None:
+            self.eng.set_option("vlad_assign", self.before)
+        return False
+
+
 def _seg_vlad_common(dino_desc, segMask, c_centers, cfg, desc_dim, adj_mat):
+    """``cfg['vlad_mode']`` ('hard' | 'soft' | 'soft_pooled') and ``cfg['soft_temp']``, when present, choose the assignment for this call."""
     eng = engine()
+    with _vlad_assign(eng, cfg.get("vlad_mode"), cfg.get("soft_temp")):
+        return _seg_vlad_assigned(eng, dino_desc, segMask, c_centers, cfg, desc_dim, adj_mat)
+
+
+def _seg_vlad_assigned(eng, dino_desc, segMask, c_centers, cfg, desc_dim, adj_mat):
     H, W = cfg["desired_height"], cfg["desired_width"]
     d = dino_desc if isinstance(dino_desc, torch.Tensor) else torch.from_numpy(np.asarray(dino_desc))
     total = d.shape[2] * d.shape[3]
@@ -402,13 +425,32 @@ def _centres_of(vlad):
     return c if isinstance(c, torch.Tensor) else torch.as_tensor(np.asarray(c))
 
 
+def _assignment_of(vlad):
+    """(mode, temp) of a VLAD-like object (utilities.py:640-670); bare centres mean hard.  Its vlad_mode='soft' is the option's
+    soft_pooled: VLAD.generate sums block k's residuals against all centres (utilities.py:883-884).  The fields the device path cannot
+    honour raise instead of being ignored (the reference keeps its ``dist_mode`` argument in the attribute ``mode``)."""
+    if not hasattr(vlad, "c_centers"):
+        return "hard", None
+    for field, want in (("intra_norm", True), ("norm_descs", True), ("dist_mode", "cosine"), ("mode", "cosine")):
+        have = getattr(vlad, field, want)
+        if have != want:
+            raise NotImplementedError(f"aggFt: VLAD.{field}={have!r} is not on the device path (only {want!r})")
+    mode = getattr(vlad, "vlad_mode", "hard")
+    if mode not in ("hard", "soft"):
+        raise NotImplementedError(f"aggFt: VLAD.vlad_mode={mode!r} is not on the device path ('hard' or 'soft')")
+    return ("soft_pooled", getattr(vlad, "soft_temp", 1.0)) if mode == "soft" else ("hard", None)
+
+
 def aggFt(desc_path, masks, segRange, cfg, aggType, vlad=None, upsample=False, segment_global=False, segment=False):
     """func_vpr.py:886-946, the branch the AnyLoc baseline runs (``aggType='vlad'``, ``segment=False``,
     place_rec_main.py:383-384): one global VLAD per image over ALL patch tokens -- L2-normalised tokens, hard cosine
     assignment, residuals against the raw centres, intra-normalisation, L2 (``VLAD.generate``, utilities.py:819-890).
     ``upsample`` is accepted and ignored exactly as in that branch (its interpolation is commented out, :936-937).
     ``desc_path``: an open h5py-like mapping ``{key: {'ift_dino': [1, D, h, w]}}``, a store directory, or an .h5 path.
-    ``vlad``: the reference's VLAD object (its ``c_centers`` are used) or the centres themselves.
+    ``vlad``: the reference's VLAD object -- its ``c_centers``, ``vlad_mode`` ('hard' | 'soft') and ``soft_temp`` are honoured (soft: the option's
+    soft_pooled, which reproduces ``VLAD.generate``),
+    ``intra_norm=False``, ``norm_descs=False`` and a ``dist_mode`` other than 'cosine' raise NotImplementedError -- or the
+    centres themselves (hard).  The engine's option vlad_assign is put back to what it was before the call returns.
     Returns a list of float32 ``[K*D]`` arrays in natural key order.  On the device this is the segment-VLAD kernel with
     one all-token segment per image (a whole batch of images per call)."""
     if aggType != "vlad" or segment or segment_global:
@@ -425,9 +467,15 @@ def aggFt(desc_path, masks, segRange, cfg, aggType, vlad=None, upsample=False, s
             import h5py  # noqa: F401  (only where the reference's own files are used)
 
             f = h5py.File(desc_path, "r")
+    mode, temp = _assignment_of(vlad)
     keys = sorted(f.keys(), key=_natural_key)
     eng = engine()
     _set_vocab(_centres_of(vlad))
+    with _vlad_assign(eng, mode, temp):
+        return _agg_global_vlad(eng, f, keys)
+
+
+def _agg_global_vlad(eng, f, keys):
     out: List[np.ndarray] = []
     batch = 64
     for b0 in range(0, len(keys), batch):

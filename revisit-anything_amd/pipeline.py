@@ -44,8 +44,15 @@ def adjacency_batch(centroids: np.ndarray, seg_offsets: Sequence[int], order: in
 
 class SegVLADPipeline:
     def __init__(self, engine: SegVLADEngine, H: int, W: int, patch: int = 14, order: int = 3, use_pca: bool = True,
-                 adj_workers: int = 8, host_adjacency: bool = False, fuse_pca: bool = True, check_empty: bool = True):
+                 adj_workers: int = 8, host_adjacency: bool = False, fuse_pca: bool = True, check_empty: bool = True,
+                 vlad_mode: str = None, soft_temp: float = None):
         self.eng = engine
+        # vlad_mode 'hard' | 'soft' | 'soft_pooled' (+ soft_temp): the engine's option vlad_assign, set here for every describe of
+        # this context (soft_pooled is the reference's VLAD(vlad_mode='soft', soft_temp=...)); None leaves the engine as it is
+        if vlad_mode is not None:
+            engine.set_vlad_assign(vlad_mode, soft_temp if vlad_mode != "hard" else None)
+        elif soft_temp is not None:
+            raise ValueError("SegVLADPipeline: soft_temp needs vlad_mode='soft'")
         self.H, self.W, self.patch = H, W, patch
         self.order = order
         self.use_pca = use_pca

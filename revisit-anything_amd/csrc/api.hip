@@ -324,6 +324,7 @@ int segvlad_set_option(segvlad_ctx* ctx, const char* key, const char* value) {
   if (!strcmp(key, "pj_nw")) return as_int(&o.pj_nw);
   if (!strcmp(key, "pj_f16")) return as_int(&o.pj_f16);
   if (!strcmp(key, "cover_rows")) return as_int(&o.cover_rows);
+  if (!strcmp(key, "pj_planes")) return as_int(&o.pj_planes);
   if (!strcmp(key, "small_plan")) return as_int(&o.small_plan);
   if (!strcmp(key, "small_tail")) return as_int(&o.small_tail);
   if (!strcmp(key, "small_head")) return as_int(&o.small_head);

@@ -196,6 +196,9 @@ struct SvOptions {
   int pca_path = 0;       // fused images_pca: 0 auto, 1 "planes" (descriptor planes x W), 2 "project" (project tokens, then aggregate)
   int cover_rows = 1;     // project form: only the tokens some segment covers get a row of the grouped planes and of Z (prep_kernel's
                           // `phys` map; same bits: every kernel keeps its logical positions); 0 = every token gets a row
+  int pj_planes = 1;      // project form, 16-bit tile sums: the grouped GEMM's epilogue stores z * zscale as its fp16 pair (h | l << 16) in
+                          // place of the fp32 z and the aggregation consumes the pairs from registers (same bits:
+                          // tests/test_gpu_pj_planes.py); 0 = fp32 Z, split again in every tile
   float vlad_soft_temp = 0.f;   // "vlad_assign": 0 = hard; > 0 = soft assignment at this temperature (soft_vlad_kernels.hip)
   int vlad_soft_pooled = 0;     // "vlad_assign" = soft_pooled:<T>: every block's residuals are taken against ALL centres (the reference's sum)
   int group_fetch = 0;    // segvlad_search_grouped: depth of the inner search, clamped to k .. 1024 (0 = min(1024, 4 k)); never changes a
@@ -642,14 +645,16 @@ int sv_launch_split_f16x2(segvlad_ctx* ctx, const float* X, int64_t n_rows, int 
 int sv_launch_gemm_f16x3(segvlad_ctx* ctx, const uint16_t* A1, const uint16_t* A2, const uint16_t* B1, const uint16_t* B2, int M,
                          int N, int Kd, float out_scale, const float* col_scale, float* C);
 int sv_launch_gemm_f16x3_grouped(segvlad_ctx* ctx, const uint16_t* A1, const uint16_t* A2, const uint16_t* B1, const uint16_t* B2,
-                                 int M_pad, int N, int Kd, int n_groups, const int32_t* tile_group, float out_scale, float* C);
+                                 int M_pad, int N, int Kd, int n_groups, const int32_t* tile_group, float out_scale, float* C,
+                                 float pair_scale);
 // project_kernels.hip ("project then aggregate" form of segvlad_images_pca)
 int sv_launch_group_plan(segvlad_ctx* ctx, const int32_t* cov_cnt, int B, int K, int32_t* rowbase, int32_t* tile_group, int max_tiles);
 int sv_launch_project_consts(segvlad_ctx* ctx, const float* comps, const float* mean, int P, int64_t KD, float* wmu /*[P] = W mean*/);
+bool sv_project_z_pairs(const segvlad_ctx* ctx, float zscale, int64_t rows, int P);
 int sv_launch_project_aggregate(segvlad_ctx* ctx, const float* Z, const float* wmu, const float* block_norms, const float* gscale,
                                 const uint64_t* colmask, const int32_t* lab_off, const int32_t* rowbase, const int32_t* phys,
                                 const int32_t* seg_off_dev, int B, int N, int K, int P, int SC, int S_max, const float* col_scale,
-                                float* Y, float zscale);
+                                float* Y, float zscale, int z_pairs, int64_t zero_row);
 int sv_launch_to_f16(segvlad_ctx* ctx, const float* X, int64_t n_elems, float scale, uint16_t* out);
 // single-image searches: the query plane and its scales without a host round trip (scales_dev[0] = query scale,
 // [1] = 1 / (query scale x db_scale)); ctx->f16_scale_dev != null makes the filter kernel read [1] instead of its argument

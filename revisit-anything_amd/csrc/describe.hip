@@ -186,7 +186,7 @@ static int reserve_scratch(segvlad_ctx* ctx, const DescribePlan& p, DescribeIO& 
   if (p.form == DescribeForm::Project) {
     SV_HIP(ctx->s_xh1.reserve((size_t)(p.rows_pad + 256) * D * 2));   // + one tile: the dummy row of sv_launch_token_norms
     SV_HIP(ctx->s_xh2.reserve((size_t)(p.rows_pad + 256) * D * 2));
-    SV_HIP(ctx->s_pz.reserve((size_t)p.rows_pad * P * sizeof(float)));
+    SV_HIP(ctx->s_pz.reserve((size_t)(p.rows_pad + 1) * P * sizeof(float)));   // + the zero row of the pj_planes aggregation
     SV_HIP(ctx->s_rowbase.reserve(B * K * sizeof(int32_t)));
     SV_HIP(ctx->s_tilegrp.reserve((size_t)(p.rows_pad >> 8) * sizeof(int32_t)));
     SV_HIP(ctx->s_phys.reserve(B * N * sizeof(int32_t)));
@@ -324,12 +324,17 @@ static int pass_project(segvlad_ctx* ctx, const DescribePlan& p, const DescribeI
     sc.count(2);
   }
   StageScope sc(ctx, "pca");
+  // pj_planes: Z leaves the GEMM as the fp16 pairs of z * zscale, the aggregation's MFMA operands (same bytes, same bits of y)
+  const bool z_pairs = sv_project_z_pairs(ctx, p.zscale, p.rows_pad + 1, p.P);
+  if (z_pairs)   // the row behind the GEMM's last: what the aggregation reads for a position without a row (its loads are unconditional)
+    SV_HIP(hipMemsetAsync(ctx->s_pz.as<float>() + (size_t)p.rows_pad * p.P, 0, (size_t)p.P * sizeof(float), ctx->stream));
   SV_TRY(sv_launch_gemm_f16x3_grouped(ctx, h1, h2, ctx->pca_w1.as<uint16_t>(), ctx->pca_w2.as<uint16_t>(), (int)p.rows_pad, p.P, p.D, p.K,
-                                      ctx->s_tilegrp.as<int32_t>(), 1.f / (p.xscale * ctx->pca_w_scale), ctx->s_pz.as<float>()));
+                                      ctx->s_tilegrp.as<int32_t>(), 1.f / (p.xscale * ctx->pca_w_scale), ctx->s_pz.as<float>(),
+                                      z_pairs ? p.zscale : 0.f));
   SV_TRY(sv_launch_project_aggregate(ctx, ctx->s_pz.as<float>(), ctx->pca_cproj.as<float>(), bn, ctx->s_gscale.as<float>(),
                                      ctx->s_colmask.as<uint64_t>(), ctx->s_laboff.as<int32_t>(), ctx->s_rowbase.as<int32_t>(),
                                      ctx->s_phys.as<int32_t>(), ctx->s_segoff.as<int32_t>(), p.B, p.N, p.K, p.P, p.SC, p.S_max,
-                                     ctx->pca_scale.as<float>(), (float*)io.d_y, p.zscale));
+                                     ctx->pca_scale.as<float>(), (float*)io.d_y, p.zscale, z_pairs ? 1 : 0, p.rows_pad));
   sc.count(2);
   return pass_normalize(ctx, p, io, sc);
 }

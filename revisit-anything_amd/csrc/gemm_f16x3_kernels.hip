@@ -88,7 +88,8 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_f16x3_kernel(const uint16_t
                                                                   int tiles_m, int gm, int n_splits, int k_per_split, float out_scale,
                                                                   const float* __restrict__ col_scale,
                                                                   float* __restrict__ C, int64_t ldc,
-                                                                  const int32_t* __restrict__ tile_group, int nkb_b) {
+                                                                  const int32_t* __restrict__ tile_group, int nkb_b,
+                                                                  float pair_scale) {
   constexpr int NW = WM * WN;
   constexpr int TM = BM / (16 * WM), TN = BN / (16 * WN);   // 16 x 16 MFMA tiles per wave (4 x 8 for the 64 x 128 wave tile)
   static_assert(TM == 4 && (TN == 8 || TN == 4), "wave tiles of 64 rows, 128 or 64 columns");
@@ -237,12 +238,31 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_f16x3_kernel(const uint16_t
     if (col >= N) continue;
     const float cs = (n_splits > 1) ? 1.f : out_scale * (col_scale ? col_scale[col] : 1.f);
 #pragma unroll
-    for (int mt = 0; mt < TM; ++mt)
+    for (int mt = 0; mt < TM; ++mt) {
+      const int64_t row0 = m0 + wm * (16 * TM) + mt * 16 + 4 * kq;
+      if (pair_scale > 0.f) {
+        // the P-space aggregation's operand (project_aggregate_kernel, ZP): z * pair_scale = h + l as two fp16, h in the low half of
+        // the element's 32 bits -- the split that kernel would otherwise repeat on every element of every tile.  Two rows at a time:
+        // the conversions and the subtraction have packed forms
+        typedef float f32x2 __attribute__((ext_vector_type(2)));
+        typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 #pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int64_t row = m0 + wm * (16 * TM) + mt * 16 + 4 * kq + r;
-        if (row < M) C[row * ldc + col] = acc[mt][nt][r] * cs;
+        for (int r = 0; r < 4; r += 2) {
+          const f32x2 z = {acc[mt][nt][r] * cs, acc[mt][nt][r + 1] * cs};
+          const f32x2 v = z * pair_scale;
+          const f16x2 h = __builtin_convertvector(v, f16x2);
+          const f16x2 lo = __builtin_convertvector(v - __builtin_convertvector(h, f32x2), f16x2);
+          const uint32_t hu = __builtin_bit_cast(uint32_t, h), lu = __builtin_bit_cast(uint32_t, lo);
+          uint32_t* dst = reinterpret_cast<uint32_t*>(C) + (row0 + r) * ldc + col;
+          if (row0 + r < M) dst[0] = (hu & 0xffffu) | (lu << 16);
+          if (row0 + r + 1 < M) dst[ldc] = (hu >> 16) | (lu & 0xffff0000u);
+        }
+      } else {
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          if (row0 + r < M) C[(row0 + r) * ldc + col] = acc[mt][nt][r] * cs;
       }
+    }
   }
 }
 
@@ -304,7 +324,7 @@ static int launch_x3(segvlad_ctx* ctx, const uint16_t* A1, const uint16_t* A2, c
     grid = dim3((unsigned)((units + 7) / 8 * 8 * 32), 1);
   }
   hipLaunchKernelGGL(kern, grid, dim3(64 * WM * WN), lds, ctx->stream, A1, A2, B1, B2, M, N, Kd, tiles_m, gm, splits, k_per_split,
-                     out_scale, col_scale, dst, (int64_t)N, (const int32_t*)nullptr, 0);
+                     out_scale, col_scale, dst, (int64_t)N, (const int32_t*)nullptr, 0, 0.f);
   SV_HIP(hipGetLastError());
   if (splits > 1) {
     const int64_t mn = (int64_t)M * N;
@@ -328,7 +348,8 @@ int sv_launch_gemm_f16x3(segvlad_ctx* ctx, const uint16_t* A1, const uint16_t* A
 // every group g, in ONE launch.  A planes: [M_pad][Kd] blocked, rows grouped, every 256-row tile inside one group
 // (tile_group[tile], -1 = unused); B planes: [N][groups * Kd] blocked (the PCA components: group g = cluster g's columns).
 int sv_launch_gemm_f16x3_grouped(segvlad_ctx* ctx, const uint16_t* A1, const uint16_t* A2, const uint16_t* B1, const uint16_t* B2,
-                                 int M_pad, int N, int Kd, int n_groups, const int32_t* tile_group, float out_scale, float* C) {
+                                 int M_pad, int N, int Kd, int n_groups, const int32_t* tile_group, float out_scale, float* C,
+                                 float pair_scale) {
   if (M_pad <= 0 || N <= 0) return SEGVLAD_OK;
   constexpr int BM = 256, BN = 256;
   const int tiles_m = M_pad / BM, tiles_n = (N + BN - 1) / BN;
@@ -340,7 +361,7 @@ int sv_launch_gemm_f16x3_grouped(segvlad_ctx* ctx, const uint16_t* A1, const uin
   const int chunks = (tiles_m + rows_per_chunk - 1) / rows_per_chunk;
   const int64_t grid = (int64_t)((chunks + 7) / 8) * 8 * rows_per_chunk * tiles_n;
   hipLaunchKernelGGL(kern, dim3((unsigned)grid, 1), dim3(512), lds, ctx->stream, A1, A2, B1, B2, M_pad, N, Kd, tiles_m, 0,
-                     1, Kd, out_scale, (const float*)nullptr, C, (int64_t)N, tile_group, n_groups * (Kd >> 5));
+                     1, Kd, out_scale, (const float*)nullptr, C, (int64_t)N, tile_group, n_groups * (Kd >> 5), pair_scale);
   SV_HIP(hipGetLastError());
   return SEGVLAD_OK;
 }

@@ -123,7 +123,17 @@ constexpr int PJ_T = 32;   // rows per tile (an image has at most K + N / 32 til
 // is applied to the tile's 32 x 32 sums (one fma per accumulator element, the 16 weights of a lane's rows as four 16-byte reads
 // of a [cluster][segment] table).  The mask fragments are the same for the workgroup's eight waves: 256 threads build them once
 // per tile (from the tokens' mask words, while the tile is fetched) and every wave reads its 16 bytes per (k-step, half).
-template <int NW, bool F16 = false>   // waves per workgroup = 32-column slices: 8 (256 columns, 82 KiB of LDS: one workgroup per CU; default) or
+//
+// ZP (option pj_planes): the grouped GEMM's epilogue has already split z * zscale into its fp16 pair, one 32-bit word (h | l << 16) where
+// the fp32 z stood, so the words of a tile are what the MFMAs consume and nothing is converted here.  An element of Z is read by exactly
+// one lane of one wave (lane (i, kk) of wave w: column 32 w + i, rows 8 kk .. 8 kk + 7 of each 16-row k-step), so that lane loads its
+// 16 words itself -- two rows of 128 contiguous bytes per wave and load -- and the Z tile never passes through LDS: three register sets
+// keep tiles t+1 and t+2 in flight under the MFMAs of tile t.  The byte offsets of a tile's 32 rows come from a table built once per
+// workgroup (one add per load in the loop); a position without a row points at a zero row behind Z, so no load of the loop is
+// conditional and the compiler's waits are counted.  What is left in LDS per tile is the mask-fragment image (three slots, built by all
+// 512 threads), and the barrier per tile orders that alone.  Same operands in the same order: the bits of the fp32-Z form.
+// 200 images x 50 segments, K = 64, P = 1024: 0.58 -> 0.36 ms, the GEMM's epilogue + 0.03 ms.
+template <int NW, bool F16 = false, bool ZP = false>   // waves per workgroup = 32-column slices: 8 (256 columns, 82 KiB of LDS: one workgroup per CU; default) or
                     // 4 (128 columns, 49 KiB: three per CU; option pj_nw = 4 -- measured slower: every workgroup repeats the
                     // per-tile mask loads, barriers and the weight table)
 __global__ __launch_bounds__(64 * NW) void project_aggregate_kernel(const float* __restrict__ Z, const float* __restrict__ wmu,
@@ -134,22 +144,27 @@ __global__ __launch_bounds__(64 * NW) void project_aggregate_kernel(const float*
                                                                 const int32_t* __restrict__ phys,
                                                                 const int32_t* __restrict__ seg_off, int N, int K, int P, int SC,
                                                                 int maxt, const float* __restrict__ col_scale,
-                                                                float* __restrict__ Y, float zscale) {
+                                                                float* __restrict__ Y, float zscale, int64_t zrow) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
   static_assert(!F16 || NW == 8, "16-bit tile sums: the 8-wave workgroup");
+  static_assert(!ZP || F16, "fp16 pairs of Z: the 16-bit tile sums");
   const int KS = K + 1 + (K & 1);                                  // row stride of ag, always odd: conflict-free column reads
   float* ag = reinterpret_cast<float*>(smem);                      // [64][KS]  a_sk = g_s / ||V_sk||   (0 for empty blocks); F16: [K][64]
   constexpr int NC = 32 * NW, NT_ = 64 * NW, C4W = NC / 4;         // columns, threads, float4 per staged row
-  float* zt = ag + 64 * KS;                                        // [2][PJ_T][NC] staged rows
-  uint64_t* mk = reinterpret_cast<uint64_t*>(zt + 2 * PJ_T * NC);  // [2][PJ_T] column masks of the staged tokens
+  float* zt = ag + 64 * KS;                                        // [2][PJ_T][NC] staged rows (ZP: none)
+  uint64_t* mk = reinterpret_cast<uint64_t*>(zt + (ZP ? 0 : 2 * PJ_T * NC));  // [2][PJ_T] column masks of the staged tokens
   int32_t* tl_k = reinterpret_cast<int32_t*>(mk + 2 * PJ_T);       // [maxt] cluster of tile t
   int32_t* tl_j = tl_k + maxt;                                     // [maxt] first token (label-grouped order) of tile t
   int32_t* tl_z = tl_j + maxt;                                     // [maxt] row of Z of the cluster's first covered token
   int32_t* tl_n = tl_z + maxt;                                     // [maxt] rows in tile t
   int32_t* phl = tl_n + maxt + K + 1;                              // [N] the image's phys, behind the lists (+ K + 1 tile offsets)
-  // F16: [2 buffers][k-step][segment half][64 lanes] 16-byte mask fragments, behind them
-  uint4* af = reinterpret_cast<uint4*>((reinterpret_cast<uintptr_t>(phl + N) + 15) & ~(uintptr_t)15);
+  // F16: [2 buffers (ZP: 3 slots)][k-step][segment half][64 lanes] 16-byte mask fragments, behind them
+  // (an OFFSET rounded up, not the pointer's integer value: a pointer that has been through an integer is no LDS pointer to the compiler
+  // any more, the fragment reads become flat_load, and in front of every flat load all outstanding global loads are waited for)
+  uint4* af = reinterpret_cast<uint4*>(smem + ((size_t)(reinterpret_cast<unsigned char*>(phl + N) - smem + 15) & ~(size_t)15));
+  // ZP: [maxt + 1][PJ_T] byte offset in Z of the row behind position r of tile t, behind the three fragment slots
+  uint32_t* tro = reinterpret_cast<uint32_t*>(af + 3 * 256);
   __shared__ int s_tiles;
   const int b = blockIdx.y, p0 = blockIdx.x * NC;
   const int tid = threadIdx.x, w = tid >> 6, l = tid & 63, i = l & 31, kk = l >> 5;
@@ -191,6 +206,18 @@ __global__ __launch_bounds__(64 * NW) void project_aggregate_kernel(const float*
   }
   __syncthreads();
   const int tiles = s_tiles;
+  if constexpr (ZP) {   // (the whole of Z, zero row included, lies inside 4 GiB: sv_project_z_pairs)
+    const uint32_t zoff = (uint32_t)zrow * (uint32_t)P * 4u;
+    for (int idx = tid; idx < (tiles + 1) * PJ_T; idx += NT_) {
+      const int t = idx / PJ_T, r = idx % PJ_T;
+      uint32_t o = zoff;
+      if (t < tiles && r < tl_n[t]) {
+        const int pr = phl[tl_j[t] + r];
+        if (pr >= 0) o = (uint32_t)(tl_z[t] + pr) * (uint32_t)P * 4u;
+      }
+      tro[idx] = o;
+    }
+  }
 
   for (int sc = 0; sc < SCb; ++sc) {
     const int Sc = min(64, S - 64 * sc);
@@ -278,20 +305,36 @@ __global__ __launch_bounds__(64 * NW) void project_aggregate_kernel(const float*
         }                                                                                                       \
       }                                                                                                         \
     } while (0)
-#define SV_PJ_MUL16(t_)                                                                                         \
+    // the fp16 pair of this lane's 8 rows of k-step ks: split here from the staged fp32 tile | taken from the words V_ (ZP)
+#define SV_PJ_HL_SPLIT(cur_, V_, ks, hh, ll)                                                                    \
     do {                                                                                                        \
-      const int cur_ = (t_) & 1, k_ = tl_k[t_], nt_ = tl_n[t_];                                                 \
-      const float* ztc = zt + (size_t)cur_ * PJ_T * NC + 32 * w + i + (size_t)(8 * kk) * NC;                    \
-      const uint4* afc = af + cur_ * 256 + l;                                                                   \
+      const float* ztc = zt + (size_t)(cur_) * PJ_T * NC + 32 * w + i + (size_t)(8 * kk) * NC;                  \
+      _Pragma("unroll") for (int e = 0; e < 8; ++e) {                                                           \
+        const float v = ztc[(size_t)(16 * (ks) + e) * NC] * zscale;                                             \
+        hh[e] = (_Float16)v;                                                                                    \
+        ll[e] = (_Float16)(v - (float)hh[e]);                                                                   \
+      }                                                                                                         \
+    } while (0)
+#define SV_PJ_HL_PAIRS(cur_, V_, ks, hh, ll)                                                                    \
+    do {                                                                                                        \
+      uint32_t hd_[4], ld_[4];                                                                                  \
+      _Pragma("unroll") for (int m = 0; m < 4; ++m) {                                                           \
+        const uint32_t e0_ = V_[8 * (ks) + 2 * m], e1_ = V_[8 * (ks) + 2 * m + 1];                              \
+        hd_[m] = (e0_ & 0xffffu) | (e1_ << 16);                                                                 \
+        ld_[m] = (e0_ >> 16) | (e1_ & 0xffff0000u);                                                             \
+      }                                                                                                         \
+      hh = __builtin_bit_cast(f16x8, make_uint4(hd_[0], hd_[1], hd_[2], hd_[3]));                               \
+      ll = __builtin_bit_cast(f16x8, make_uint4(ld_[0], ld_[1], ld_[2], ld_[3]));                               \
+    } while (0)
+#define SV_PJ_MUL16(t_, cur_, HL_, V_)                                                                          \
+    do {                                                                                                        \
+      const int k_ = tl_k[t_], nt_ = tl_n[t_];                                                                  \
+      const uint4* afc = af + (cur_) * 256 + l;                                                                 \
       f32x16 ta0, ta1;                                                                                          \
       _Pragma("unroll") for (int ks = 0; ks < 2; ++ks) {                                                        \
         if (ks == 1 && nt_ <= 16) break;                                                                        \
         f16x8 hh, ll;                                                                                           \
-        _Pragma("unroll") for (int e = 0; e < 8; ++e) {                                                         \
-          const float v = ztc[(size_t)(16 * ks + e) * NC] * zscale;                                             \
-          hh[e] = (_Float16)v;                                                                                  \
-          ll[e] = (_Float16)(v - (float)hh[e]);                                                                 \
-        }                                                                                                       \
+        HL_(cur_, V_, ks, hh, ll);                                                                              \
         const uint4 a0u = afc[(2 * ks) * 64];                                                                   \
         const f16x8 a0 = __builtin_bit_cast(f16x8, a0u);                                                        \
         if (ks == 0) {                                                                                          \
@@ -334,9 +377,76 @@ __global__ __launch_bounds__(64 * NW) void project_aggregate_kernel(const float*
     } while (0)
 #define SV_PJ_MULX(t_)                                                                                          \
     do {                                                                                                        \
-      if constexpr (F16) SV_PJ_MUL16(t_);                                                                       \
+      if constexpr (F16) SV_PJ_MUL16(t_, (t_) & 1, SV_PJ_HL_SPLIT, va);                                         \
       else SV_PJ_MUL(t_);                                                                                       \
     } while (0)
+    // ZP.  Every load of the tile loop is UNCONDITIONAL: a position without a row, a row behind the tile's end and a
+    // tile behind the last one read the zero row behind Z (row `zrow`, written by nothing but the launcher's memset) -- the pad rows of Z
+    // hold any bit pattern and are never read.  With no branch around a load the compiler counts its waits (vmcnt(N), the later tiles
+    // stay in flight); one conditional load in the loop and every wait in front of an MFMA is vmcnt(0), a full round trip per tile.
+    // This lane's 16 words of a tile: q = 8 ks + e <-> row 16 ks + 8 kk + e, column pcol (a lane behind P reads column P - 1 and
+    // stores nothing: a column of the MFMA's B operand reaches that column of the result alone).  Their byte offsets in Z come
+    // from the row table `tro`, built once per workgroup; entry `tiles` of the table is the tile behind the last one.
+#define SV_PZ_FETCH(V, t_)                                                                                      \
+    do {                                                                                                        \
+      const uint4* tr_ = reinterpret_cast<const uint4*>(tro + ((t_) < tiles ? (t_) : tiles) * PJ_T + 8 * kk);   \
+      const uint4 o0_ = tr_[0], o1_ = tr_[1], o2_ = tr_[4], o3_ = tr_[5];                                       \
+      const uint32_t o_[16] = {o0_.x, o0_.y, o0_.z, o0_.w, o1_.x, o1_.y, o1_.z, o1_.w,                          \
+                               o2_.x, o2_.y, o2_.z, o2_.w, o3_.x, o3_.y, o3_.z, o3_.w};                         \
+      _Pragma("unroll") for (int q = 0; q < 16; ++q)                                                            \
+        V[q] = *reinterpret_cast<const uint32_t*>(reinterpret_cast<const unsigned char*>(Z) + (o_[q] + col4));  \
+    } while (0)
+    // The mask words of tile t_, all 512 threads: thread (k-step, half, row quad, lane) = (tid >> 8, (tid >> 7) & 1, (tid >> 6) & 1,
+    // tid & 63) loads the 32-bit half that holds segment 32 half + (lane & 31) of its lane's rows 16 ks + 8 (lane >> 5) + 4 quad + q
+#define SV_PZ_FETCH_M(Mv, t_)                                                                                   \
+    do {                                                                                                        \
+      const int tt_ = (t_) < tiles ? (t_) : tiles - 1;                                                          \
+      const int j0_ = 16 * (tid >> 8) + 8 * ((tid >> 5) & 1) + 4 * ((tid >> 6) & 1);                            \
+      const int nt_ = ((t_) < tiles ? tl_n[tt_] : 0) - j0_;                                                     \
+      const uint32_t* zero_ = reinterpret_cast<const uint32_t*>(Z) + (size_t)zrow * P;                          \
+      const uint32_t* mrow_ = reinterpret_cast<const uint32_t*>(colmask + ((size_t)b * N + tl_j[tt_] + j0_) * SC + sc) + ((tid >> 7) & 1); \
+      _Pragma("unroll") for (int q = 0; q < 4; ++q) Mv[q] = *(q < nt_ ? mrow_ + (size_t)q * SC * 2 : zero_); \
+    } while (0)
+    // ... and their 8 bytes of the fragment image ([slot][k-step][half][lane] 16-byte fragments of 8 rows as fp16 1.0 / 0.0)
+#define SV_PZ_STASH_M(Mv, slot_)                                                                                \
+    do {                                                                                                        \
+      const int sh_ = tid & 31;                                                                                 \
+      uint2 d_;                                                                                                 \
+      d_.x = (((Mv[0] >> sh_) & 1u) ? 0x3C00u : 0u) | (((Mv[1] >> sh_) & 1u) ? 0x3C000000u : 0u);               \
+      d_.y = (((Mv[2] >> sh_) & 1u) ? 0x3C00u : 0u) | (((Mv[3] >> sh_) & 1u) ? 0x3C000000u : 0u);               \
+      reinterpret_cast<uint2*>(af + (slot_) * 256 + (tid >> 7) * 64 + (tid & 63))[(tid >> 6) & 1] = d_;         \
+    } while (0)
+    // Tile t_ in set Vc / fragment slot sc_: request tile t_ + 2 into the set that tile t_ - 1 left, multiply, turn tile t_ + 1's mask
+    // words (Mn, requested a step ago) into slot sn_, whose readers -- tile t_ - 2 -- passed the previous barrier
+#define SV_PZ_STEP(Vc, sc_, Mn, sn_, V2, M2, t_)                                                                \
+    do {                                                                                                        \
+      SV_PZ_FETCH_M(M2, (t_) + 2);                                                                              \
+      SV_PZ_FETCH(V2, (t_) + 2);                                                                                \
+      SV_PJ_MUL16(t_, sc_, SV_PJ_HL_PAIRS, Vc);                                                                 \
+      SV_PZ_STASH_M(Mn, sn_);                                                                                   \
+      __syncthreads();                                                                                          \
+    } while (0)
+    if constexpr (ZP) {
+      if (tiles > 0) {
+        const uint32_t col4 = 4u * (uint32_t)(pcol < P ? pcol : P - 1);   // this lane's column, in bytes
+        uint32_t za[16], zb[16], zc[16], ma_[4], mb_[4], mc_[4];
+        SV_PZ_FETCH_M(ma_, 0);
+        SV_PZ_FETCH(za, 0);
+        SV_PZ_FETCH_M(mb_, 1);
+        SV_PZ_FETCH(zb, 1);
+        SV_PZ_STASH_M(ma_, 0);
+        __syncthreads();   // ag and tile 0's mask fragments visible
+        for (int t = 0; t < tiles; t += 3) {
+          SV_PZ_STEP(za, 0, mb_, 1, zc, mc_, t);
+          if (t + 1 >= tiles) break;
+          SV_PZ_STEP(zb, 1, mc_, 2, za, ma_, t + 1);
+          if (t + 2 >= tiles) break;
+          SV_PZ_STEP(zc, 2, ma_, 0, zb, mb_, t + 2);
+        }
+      } else {
+        __syncthreads();   // (ag: nothing reads it)
+      }
+    } else {
     // set A carries the odd tiles' predecessors: tile 0 -> LDS directly, then A = tile 1, B = tile 2, A = tile 3, ...
     if (tiles > 0) {
       SV_PJ_FETCH(va, ma, 0);
@@ -374,8 +484,15 @@ __global__ __launch_bounds__(64 * NW) void project_aggregate_kernel(const float*
       }
       __syncthreads();
     }
+    }
+#undef SV_PZ_STEP
+#undef SV_PZ_STASH_M
+#undef SV_PZ_FETCH_M
+#undef SV_PZ_FETCH
 #undef SV_PJ_MULX
 #undef SV_PJ_MUL16
+#undef SV_PJ_HL_PAIRS
+#undef SV_PJ_HL_SPLIT
 #undef SV_PJ_STASH_F
 #undef SV_PJ_FETCH_F
 #undef SV_PJ_MUL
@@ -396,10 +513,17 @@ __global__ __launch_bounds__(64 * NW) void project_aggregate_kernel(const float*
   }
 }
 
+// Whether the grouped GEMM stores, and the aggregation reads, the fp16 pairs of z * zscale in place of the fp32 z: exactly where the
+// aggregation takes its 16-bit form, under option pj_planes
+// (and where Z with its zero row -- `rows` rows -- lies inside 4 GiB, which that kernel's 32-bit row offsets presume)
+bool sv_project_z_pairs(const segvlad_ctx* ctx, float zscale, int64_t rows, int P) {
+  return zscale > 0.f && ctx->opt.pj_nw != 4 && ctx->opt.pj_f16 != 0 && ctx->opt.pj_planes != 0 && rows * P * 4 < (1ll << 32);
+}
+
 int sv_launch_project_aggregate(segvlad_ctx* ctx, const float* Z, const float* wmu, const float* block_norms, const float* gscale,
                                 const uint64_t* colmask, const int32_t* lab_off, const int32_t* rowbase, const int32_t* phys,
                                 const int32_t* seg_off_dev, int B, int N, int K, int P, int SC, int S_max, const float* col_scale,
-                                float* Y, float zscale) {
+                                float* Y, float zscale, int z_pairs, int64_t zero_row) {
   if (B <= 0 || S_max <= 0) return SEGVLAD_OK;
   if (P % 4) return ctx->fail(SEGVLAD_ERR_ARG, "project_aggregate: P=%d must be a multiple of 4", P);
   const int maxt = K + (N + PJ_T - 1) / PJ_T;   // every cluster may end in a partial tile
@@ -407,23 +531,30 @@ int sv_launch_project_aggregate(segvlad_ctx* ctx, const float* Z, const float* w
   if (K > 64 * nw) return ctx->fail(SEGVLAD_ERR_LIMIT, "project_aggregate: K=%d clusters need %d threads", K, K);
   // zscale > 0: the tile sums on the 16-bit pipe (8-wave workgroups; + the mask-fragment image: 2 x 4 KiB, 16-byte aligned)
   const bool f16 = zscale > 0.f && nw == 8 && ctx->opt.pj_f16 != 0;
-  const size_t lds = (size_t)64 * (K + 1 + (K & 1)) * 4 + (size_t)2 * PJ_T * 32 * nw * 4 + (size_t)2 * PJ_T * 8 + (size_t)4 * maxt * 4 +
-                     (size_t)(K + 1) * 4 + (size_t)N * 4 + (f16 ? 16 + 2 * 256 * 16 : 0);
+  // z_pairs: Z holds the fp16 pairs of z * zscale (sv_project_z_pairs; the caller asked the GEMM for them): no staged tile, three mask slots
+  if (z_pairs && !sv_project_z_pairs(ctx, zscale, zero_row + 1, P)) return ctx->fail(SEGVLAD_ERR_STATE, "project_aggregate: fp16 pairs of Z without the 16-bit tile sums");
+  const size_t lds = (size_t)64 * (K + 1 + (K & 1)) * 4 + (z_pairs ? 0 : (size_t)2 * PJ_T * 32 * nw * 4) + (size_t)2 * PJ_T * 8 +
+                     (size_t)4 * maxt * 4 + (size_t)(K + 1) * 4 + (size_t)N * 4 + (f16 ? 16 + (z_pairs ? 3 : 2) * 256 * 16 : 0) +
+                     (z_pairs ? (size_t)(maxt + 1) * PJ_T * 4 : 0);
   if (lds > 160 * 1024)
     return ctx->fail(SEGVLAD_ERR_LIMIT, "project_aggregate: K=%d, N=%d need %zu B of LDS", K, N, lds);
-  const void* fn = f16 ? reinterpret_cast<const void*>(project_aggregate_kernel<8, true>)
+  const void* fn = z_pairs ? reinterpret_cast<const void*>(project_aggregate_kernel<8, true, true>)
+                   : f16 ? reinterpret_cast<const void*>(project_aggregate_kernel<8, true>)
                        : nw == 8 ? reinterpret_cast<const void*>(project_aggregate_kernel<8>) : reinterpret_cast<const void*>(project_aggregate_kernel<4>);
   if (lds > 64 * 1024) SV_HIP(sv_max_dyn_lds(fn, (size_t)lds));
   const dim3 grid((P + 32 * nw - 1) / (32 * nw), B), block(64 * nw);
-  if (f16)
+  if (z_pairs)
+    hipLaunchKernelGGL((project_aggregate_kernel<8, true, true>), grid, block, lds, ctx->stream, Z, wmu, block_norms, gscale, colmask, lab_off,
+                       rowbase, phys, seg_off_dev, N, K, P, SC, maxt, col_scale, Y, zscale, zero_row);
+  else if (f16)
     hipLaunchKernelGGL((project_aggregate_kernel<8, true>), grid, block, lds, ctx->stream, Z, wmu, block_norms, gscale, colmask, lab_off,
-                       rowbase, phys, seg_off_dev, N, K, P, SC, maxt, col_scale, Y, zscale);
+                       rowbase, phys, seg_off_dev, N, K, P, SC, maxt, col_scale, Y, zscale, (int64_t)0);
   else if (nw == 8)
     hipLaunchKernelGGL(project_aggregate_kernel<8>, grid, block, lds, ctx->stream, Z, wmu, block_norms, gscale, colmask, lab_off, rowbase,
-                       phys, seg_off_dev, N, K, P, SC, maxt, col_scale, Y, 0.f);
+                       phys, seg_off_dev, N, K, P, SC, maxt, col_scale, Y, 0.f, (int64_t)0);
   else
     hipLaunchKernelGGL(project_aggregate_kernel<4>, grid, block, lds, ctx->stream, Z, wmu, block_norms, gscale, colmask, lab_off, rowbase,
-                       phys, seg_off_dev, N, K, P, SC, maxt, col_scale, Y, 0.f);
+                       phys, seg_off_dev, N, K, P, SC, maxt, col_scale, Y, 0.f, (int64_t)0);
   SV_HIP(hipGetLastError());
   return SEGVLAD_OK;
 }

@@ -29,6 +29,9 @@
  *     "tnk_fork"      1 | 0   the two-tile Gram launch on the context's side stream | in line
  *     "pj_f16"        1 | 0   P-space tile sums on the 16-bit matrix pipe | fp32 MFMA
  *     "pj_nw"         8 | 4   waves per workgroup of the P-space aggregation
+ *     "pj_planes"     1 | 0   project form, 16-bit tile sums: the grouped GEMM stores z * zscale as its fp16 pair (h | l << 16) where the
+ *                             fp32 z stood, the aggregation takes the pairs from registers, three tiles in flight (same bits:
+ *                             tests/test_gpu_pj_planes.py) | fp32 Z staged in LDS and split in every tile
  *     "cover_rows"    1 | 0   project form: only the tokens that some segment covers get a row of the grouped planes and of Z
  *                             (same bits: tests/test_gpu_cover_rows.py) | every token gets a row
  *     "x3_tile", "x3_gm", "agg_kpb", "assign_narrow"   tile / order / geometry of the projection GEMM, the descriptor

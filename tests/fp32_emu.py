@@ -6,8 +6,13 @@ What the device computes for a (query q, database row r) pair on EVERY exact pat
 refine_exact_*, refine_group_gemm_kernel, small_tail_kernel):
 
     dot   = the sequential chain  acc = fmaf(q[j], r[j], acc),  j = 0 .. d-1,  acc = 0                 (one rounding per step)
+            (gemm_nt_kernel's guarded loop pads a partial k-tile, and rows beyond the operand, with zeros: fmaf(0, 0, acc) = acc,
+            so the chain is the same for every d, every tile position and every nq, whichever of the two main loops runs)
     ||x||^2 = row_sumsq (csrc/gemm_kernels.hip): lane L of a 64-lane wave sums the float4s L, L + 64, ... of the row with fmaf
-              (x, y, z, w in turn), then the xor butterfly v += shfl_xor(v, o), o = 32, 16, 8, 4, 2, 1   (d % 4 == 0)
+              (x, y, z, w in turn), then the xor butterfly v += shfl_xor(v, o), o = 32, 16, 8, 4, 2, 1 -- when d % 4 == 0 AND
+              the row starts on a 16-byte boundary; otherwise lane L sums the single elements L, L + 64, ... with fmaf, then
+              the same butterfly.  Index rows are the library's own copy (16-byte aligned base): their form follows from d
+              alone; a query view keeps its caller's alignment.
     d2    = fmaf(-2, dot, ||q||^2 + ||r||^2), negative values set to zero                                (csrc/ctx.h: sv_d2)
 
 fp32 fma is emulated exactly in float64: the product of two fp32 numbers is exact in float64 (48 significant bits), the sum with
@@ -40,11 +45,20 @@ def fma32(a, b, c):
     return r.astype(np.float32)
 
 
-def row_sumsq(X):
-    """||row||^2 of every row of X [n, d] fp32 (d % 4 == 0) as csrc/gemm_kernels.hip: row_sumsq computes it."""
+def row_sumsq(X, aligned=True):
+    """||row||^2 of every row of X [n, d] fp32 as csrc/gemm_kernels.hip: row_sumsq computes it.  aligned: the rows start on
+    16-byte boundaries (then d % 4 == 0 takes the float4 form); False, or d % 4 != 0: the single-element form."""
     X = np.ascontiguousarray(X, np.float32)
     n, d = X.shape
-    assert d % 4 == 0
+    if d % 4 != 0 or not aligned:
+        s = np.zeros((n, 64), np.float32)
+        for j0 in range(0, d, 64):                   # lane L takes element j0 + L
+            w = min(64, d - j0)
+            v = X[:, j0:j0 + w]
+            s[:, :w] = fma32(v, v, s[:, :w])
+        for o in (32, 16, 8, 4, 2, 1):
+            s = (s + s[:, np.arange(64) ^ o]).astype(np.float32)
+        return s[:, 0].copy()
     d4 = d // 4
     X4 = X.reshape(n, d4, 4)
     s = np.zeros((n, 64), np.float32)
@@ -75,17 +89,20 @@ def d2(q2, r2, dot):
     return np.where(v < 0, np.float32(0), v).astype(np.float32)
 
 
-def check_contested(Q, R, d2_dev, idx_dev, k, queries=None, margin=1e-3, tol64=4e-6):
+def check_contested(Q, R, d2_dev, idx_dev, k, queries=None, margin=1e-3, tol64=4e-6, q_aligned=True):
     """The device's top-k lists of query rows `queries` (default: all) against the emulated fp32 reference, bit for bit and ties
     included, and the fp64 oracle beside it.  Q [nq, d], R [n, d]: fp32 torch tensors on the device; d2_dev [nq, k], idx_dev [nq, k]:
     the device's result.  The emulation runs on the CONTESTED rows only: per query every row whose distance by a plain fp32 GEMM
     (a tool of the test, not the product) lies within `margin` x max(1, k-th smallest) of the k-th smallest -- 100 x the worst fp32
     deviation at that magnitude, so no row outside the set can be in anybody's top k.  Every emulated distance of the result lies
     within tol64 x max(1, (||q||^2 + max ||r||^2) / 2) of the fp64 distance (tol64 itself for unit rows).
+    q_aligned: the query view the device was handed starts on a 16-byte boundary (row_sumsq's form for the query norms).
+    k > n: the first n slots are compared, every slot behind them must hold (+inf, -1).
     Returns (contested pairs, exact-tie neighbours among the results, worst |fp32 - fp64| relative to that scale)."""
     import torch
 
-    nq = Q.shape[0]
+    nq, n = Q.shape[0], R.shape[0]
+    k_all, k = k, min(k, n)
     queries = range(nq) if queries is None else [int(q) for q in queries]
     qsel = torch.as_tensor(list(queries), dtype=torch.int64, device=Q.device)
     Qs = Q[qsel]
@@ -93,7 +110,7 @@ def check_contested(Q, R, d2_dev, idx_dev, k, queries=None, margin=1e-3, tol64=4
     kth = torch.kthvalue(approx, k, dim=1).values
     lim = kth + margin * torch.clamp(kth, min=1.0)
     Qn = Q.cpu().numpy()
-    q2 = row_sumsq(Qn)
+    q2 = row_sumsq(Qn, aligned=q_aligned)
     dd, ii = d2_dev.cpu().numpy(), idx_dev.cpu().numpy()
     # every query's contested rows in ONE emulated chain (row-wise query operand)
     sel = [torch.nonzero(approx[j] <= lim[j]).flatten() for j in range(len(qsel))]
@@ -112,8 +129,9 @@ def check_contested(Q, R, d2_dev, idx_dev, k, queries=None, margin=1e-3, tol64=4
         ids, dist, rr = ids_all[off:off + cnt], dist_all[off:off + cnt], rr_all[off:off + cnt]
         off += cnt
         order = np.lexsort((ids, dist))[:k]                         # (distance, id): IndexFlatL2's order, ties to the lower id
-        assert np.array_equal(ids[order], ii[q]), (q, np.nonzero(ids[order] != ii[q])[0][:5])
-        assert np.array_equal(dist[order].view(np.uint32), dd[q].view(np.uint32)), q
+        assert np.array_equal(ids[order], ii[q, :k]), (q, np.nonzero(ids[order] != ii[q, :k])[0][:5])
+        assert np.array_equal(dist[order].view(np.uint32), dd[q, :k].view(np.uint32)), q
+        assert (ii[q, k:] == -1).all() and np.isposinf(dd[q, k:]).all(), (q, k, k_all)
         n_contested += cnt
         n_tie_pairs += int((np.diff(dist[order]) == 0).sum())
         d64 = ((Qn[q].astype(np.float64)[None, :] - rr[order].astype(np.float64)) ** 2).sum(1)

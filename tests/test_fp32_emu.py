@@ -66,3 +66,66 @@ def test_row_sumsq_and_chain_follow_the_documented_order():
             acc = _round32(Fraction(float(q[j])) * Fraction(float(R[i, j])) + Fraction(float(acc)))
         assert E.dot_chain(q, R)[i].view(np.uint32) == acc.view(np.uint32)
     assert E.d2(np.float32(1), np.float32(1), np.float32(1.0000001))[()] == 0.0      # the clamp
+
+
+def _scalar_lanes(x):
+    """row_sumsq's single-element form, lane by lane in exact arithmetic rounded once per operation: lane L sums x[L], x[L + 64], ..."""
+    lanes = [np.float32(0)] * 64
+    for L in range(64):
+        for j in range(L, len(x), 64):
+            lanes[L] = _round32(Fraction(float(x[j])) * Fraction(float(x[j])) + Fraction(float(lanes[L])))
+    for o in (32, 16, 8, 4, 2, 1):
+        lanes = [np.float32(lanes[i] + lanes[i ^ o]) for i in range(64)]
+    return lanes[0]
+
+
+def test_row_sumsq_scalar_form_lane_by_lane():
+    """d % 4 != 0, or a row off its 16-byte boundary: one element per lane and step.  Against the explicit per-lane loop bit for
+    bit, against float64 at 1e-6 relative -- and it is NOT the float4 form's value at a width both forms exist for."""
+    rng = np.random.Generator(np.random.PCG64(3))
+    differs = 0
+    for d in (1, 3, 5, 30, 33, 50, 63, 65, 100, 130, 36, 64, 256):
+        X = (rng.standard_normal((4, d)) * rng.uniform(0.1, 10.0, (4, 1))).astype(np.float32)
+        got = E.row_sumsq(X, aligned=False)
+        if d % 4 != 0:
+            assert np.array_equal(got.view(np.uint32), E.row_sumsq(X).view(np.uint32))       # the width alone decides
+        else:
+            differs += int((got.view(np.uint32) != E.row_sumsq(X, aligned=True).view(np.uint32)).sum())
+        ref64 = (X.astype(np.float64) ** 2).sum(1)
+        assert (np.abs(got - ref64) <= 1e-6 * ref64).all(), d
+        for row in range(4):
+            assert got[row].view(np.uint32) == _scalar_lanes(X[row]).view(np.uint32), (d, row)
+    assert differs > 0
+
+
+def test_check_contested_alignment_and_padding():
+    """check_contested's two new arguments on a result made by the emulation itself: a query view off its boundary is accepted under
+    q_aligned=False only (where the two norms differ), and k > n compares n slots and wants (+inf, -1) behind them."""
+    import pytest
+    import torch
+
+    rng = np.random.Generator(np.random.PCG64(4))
+    n, d, nq, k = 37, 64, 5, 40
+    R = rng.standard_normal((n, d)).astype(np.float32)
+    Q = rng.standard_normal((nq, d)).astype(np.float32)
+    r2 = E.row_sumsq(R)
+    results = {}
+    for aligned in (True, False):
+        q2 = E.row_sumsq(Q, aligned=aligned)
+        dist = np.stack([E.d2(q2[j], r2, E.dot_chain(Q[j], R)) for j in range(nq)])
+        order = np.stack([np.lexsort((np.arange(n), dist[j])) for j in range(nq)])
+        d2 = np.full((nq, k), np.inf, np.float32)
+        idx = np.full((nq, k), -1, np.int64)
+        d2[:, :n], idx[:, :n] = np.take_along_axis(dist, order, 1), order
+        results[aligned] = (torch.from_numpy(d2), torch.from_numpy(idx))
+    Qt, Rt = torch.from_numpy(Q), torch.from_numpy(R)
+    for aligned in (True, False):
+        E.check_contested(Qt, Rt, *results[aligned], k, q_aligned=aligned)
+    assert not torch.equal(results[True][0], results[False][0])
+    with pytest.raises(AssertionError):
+        E.check_contested(Qt, Rt, *results[False], k, q_aligned=True)
+    bad = results[True][1].clone()
+    bad[2, n] = 0                                        # a slot beyond the index that names a row
+    with pytest.raises(AssertionError):
+        E.check_contested(Qt, Rt, results[True][0], bad, k)
+    E.check_contested(Qt, Rt, results[True][0][:, :n].contiguous(), results[True][1][:, :n].contiguous(), n)      # k == n: as before

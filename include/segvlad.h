@@ -642,7 +642,7 @@ int segvlad_vote(segvlad_ctx* ctx, const int64_t* idx, const float* sims, const 
                  int32_t* pred_out, double* score_out);
 
 /* ---- instrumentation: with profiling on, every kernel group of a stage ("incidence", "adjacency",
- *      "assign", "prep", "aggregate", "pca", "describe" (segvlad_describe as a whole: its parts overlap), "knn_level0", "knn_gemm", "knn_select", "knn_fallback", "knn_shortlist" (segvlad_search_shortlist), "knn_exclude" (the kernels segvlad_search_excluding adds to its inner search), "knn_group" (the kernels segvlad_search_grouped adds to its inner search), "knn_range" (the kernels of segvlad_range_search), "match_pairs" (segvlad_match_pairs), "verify_pairs" (segvlad_verify_pairs), "sequence_rerank" (segvlad_sequence_rerank), "incidence_rle", "rle_decode", "rle_encode" (the run-length entries), "mask_regions" (segvlad_mask_regions), "db_remove" (segvlad_db_remove), "vote") is bracketed by a HIP event pair
+ *      "assign", "prep", "burst" (the two kernels of the option vlad_burst), "aggregate", "pca", "describe" (segvlad_describe as a whole: its parts overlap), "knn_level0", "knn_gemm", "knn_select", "knn_fallback", "knn_shortlist" (segvlad_search_shortlist), "knn_exclude" (the kernels segvlad_search_excluding adds to its inner search), "knn_group" (the kernels segvlad_search_grouped adds to its inner search), "knn_range" (the kernels of segvlad_range_search), "match_pairs" (segvlad_match_pairs), "verify_pairs" (segvlad_verify_pairs), "sequence_rerank" (segvlad_sequence_rerank), "incidence_rle", "rle_decode", "rle_encode" (the run-length entries), "mask_regions" (segvlad_mask_regions), "db_remove" (segvlad_db_remove), "vote") is bracketed by a HIP event pair
  *      on the context stream.  segvlad_stage_ms returns the SUM of the elapsed times (ms) and the number
  *      of kernel launches recorded for the stage since the last segvlad_profile_reset; it returns
  *      SEGVLAD_ERR_STATE if the stage has not run.  Replaces the (discarded) time.time() pair of
@@ -721,6 +721,37 @@ int segvlad_stage_ms(segvlad_ctx* ctx, const char* stage, float* ms_out, int* la
  *                                                      ignore the option (hard by definition).  A missing, empty, non-positive,
  *                                                      non-finite or junk-trailed T and any other spelling are SEGVLAD_ERR_ARG
  *                                                      and leave the option as it was
+ *        "vlad_burst"    off | <a>:<b>:<p>             burst discount: every token's assignment weight is divided by a soft
+ *                                                      count of the tokens of ITS image that look like it (the aggregation of
+ *                                                      VLAD-BuFF at its fixed test-time parameters, 8:7:1, with no training).
+ *                                                      off (the default): every call issues the launches and returns the bytes
+ *                                                      it does without the option.  a, b, p are decimal fp32 with
+ *                                                      0 <= a <= 64, -8 <= b <= 16, 0 <= p <= 2.  For one image with tokens
+ *                                                      x_0 .. x_{N-1} -- ALL N of them, whether a segment covers them or not --
+ *                                                      and x^_n = x_n / max(||x_n||, 1e-12):
+ *                                                        g[n] = sum_{m=0}^{N-1} sigmoid(a (2 <x^_n, x^_m> - 2) + b)    (m = n included)
+ *                                                        u[n] = g[n]^-p
+ *                                                      and every assignment weight is multiplied by u[n]: under vlad_assign=hard
+ *                                                      w[n][k] = u[n] for k = label(n) and 0 otherwise, under soft:<T> and
+ *                                                      soft_pooled:<T> w[n][k] = softmax_k(...) u[n]; V[s][k], intra_norm and the
+ *                                                      row L2 are vlad_assign's formulas above with these weights.  g depends on
+ *                                                      the image alone -- not on the segments, the adjacency or the rest of the
+ *                                                      batch; an all-zero token has x^ = 0 and takes part with cosine 0.  Inside
+ *                                                      the ranges g >= sigmoid(-8) and u <= 9e6, so no norm overflows fp32; with
+ *                                                      p = 0, u is exactly 1.  labels_out and gap_out stay the hard arg-max and
+ *                                                      gap, block_norms_out is ||V[s][k]|| with the discounted weights.  The
+ *                                                      N x N similarities are fp32 (fp32 MFMA), exist one tile at a time in
+ *                                                      registers, and are summed in a fixed order without float atomics: two
+ *                                                      calls return the same bytes.  Covers segvlad_images, segvlad_images_pca,
+ *                                                      segvlad_describe and segvlad_describe_begin / _end;
+ *                                                      segvlad_kmeans_step and segvlad_cluster_aggregate ignore it.  Like soft
+ *                                                      assignment it has no "project" form of pca_path (that form presupposes
+ *                                                      unweighted one-cluster tokens): auto takes "planes", an explicit project
+ *                                                      is SEGVLAD_ERR_LIMIT.  COST: hard assignment with the discount aggregates
+ *                                                      from a one-hot weight buffer on the soft path's kernel, K times the hard
+ *                                                      aggregation's matrix work (a label-grouped weighted aggregation is later
+ *                                                      work).  A missing, non-finite, out-of-range or junk-trailed field and any
+ *                                                      other spelling are SEGVLAD_ERR_ARG and leave the option as it was
  *      Every other key is a DEVELOPMENT switch (kernel tuning, A/B variants, debugging, the tests' own hooks), documented in
  *      revisit-anything_amd/csrc/segvlad_dev.h and NOT part of this ABI: none changes a result, the shipped library holds
  *      only the kernels they default to and rejects the values that select another (SEGVLAD_ERR_ARG).

@@ -289,6 +289,33 @@ int segvlad_set_option(segvlad_ctx* ctx, const char* key, const char* value) {
     }
     return ctx->fail(SEGVLAD_ERR_ARG, "set_option(vlad_assign): want hard|soft:<T>|soft_pooled:<T> with a finite decimal T > 0, got '%s'", value);
   }
+  if (!strcmp(key, "vlad_burst")) {   // off | <a>:<b>:<p>, three decimal fp32 with 0 <= a <= 64, -8 <= b <= 16, 0 <= p <= 2
+                                      // (include/segvlad.h); vlad_assign's strictness, a refusal changes nothing
+    if (!strcmp(value, "off")) {
+      o.vlad_burst = 0, o.burst_a = o.burst_b = o.burst_p = 0.f;
+      return SEGVLAD_OK;
+    }
+    static const float lo[3] = {0.f, -8.f, 0.f}, hi[3] = {64.f, 16.f, 2.f};
+    float v[3] = {0.f, 0.f, 0.f};
+    const char* t = value;
+    bool ok = true;
+    for (int f = 0; f < 3 && ok; ++f) {
+      const char* stop = f < 2 ? strchr(t, ':') : t + strlen(t);   // (a fourth field leaves a ':' inside the third: not a decimal)
+      ok = stop != nullptr && stop != t && (*t == '.' || *t == '-' || (*t >= '0' && *t <= '9'));
+      for (const char* c = t; ok && c < stop; ++c) ok = strchr("0123456789.eE+-", *c) != nullptr;
+      if (!ok) break;
+      char* end = nullptr;
+      v[f] = strtof(t, &end);
+      ok = end == stop && std::isfinite(v[f]) && v[f] >= lo[f] && v[f] <= hi[f];
+      t = stop + 1;
+    }
+    if (ok) {
+      o.vlad_burst = 1, o.burst_a = v[0], o.burst_b = v[1], o.burst_p = v[2];
+      return SEGVLAD_OK;
+    }
+    return ctx->fail(SEGVLAD_ERR_ARG, "set_option(vlad_burst): want off|<a>:<b>:<p>, finite decimals with 0 <= a <= 64, -8 <= b <= 16, "
+                                      "0 <= p <= 2, got '%s'", value);
+  }
   // Switches that select one of the fp16 filter's kernels (csrc/segvlad_dev.h): only the values that name a kernel the library
   // holds are accepted -- the measured-and-not-kept variants are gone from the tree (DESIGN.md 4 / 7 keep their numbers); the
   // development build (-DSEGVLAD_ABLATIONS: lib/libsegvlad_hip_abl.so) adds the probes of the batch kernel.

@@ -201,6 +201,8 @@ struct SvOptions {
                           // tests/test_gpu_pj_planes.py); 0 = fp32 Z, split again in every tile
   float vlad_soft_temp = 0.f;   // "vlad_assign": 0 = hard; > 0 = soft assignment at this temperature (soft_vlad_kernels.hip)
   int vlad_soft_pooled = 0;     // "vlad_assign" = soft_pooled:<T>: every block's residuals are taken against ALL centres (the reference's sum)
+  int vlad_burst = 0;           // "vlad_burst": 0 = off; 1 = every assignment weight times u[n] = g[n]^-p (burst_kernels.hip)
+  float burst_a = 0.f, burst_b = 0.f, burst_p = 0.f;   // ... g[n] = sum_m sigmoid(a (2 cos(x_n, x_m) - 2) + b) over the image's tokens
   int group_fetch = 0;    // segvlad_search_grouped: depth of the inner search, clamped to k .. 1024 (0 = min(1024, 4 k)); never changes a
                           // result, only which rows the exact tail finishes (tests reach the tail on a small index with it)
 };
@@ -375,13 +377,15 @@ struct segvlad_ctx {
   //  reference segment blanked (the cap and the vote read it), and the {id, best key} hash tables of the query images that the
   //  LDS table does not hold (2 slots of 16 B per entry, zeroed per call);
   //  s_softw: the describe stage under vlad_assign=soft (soft_vlad_kernels.hip) -- the assignment weights w [B][N][K] of the batch;
-  //  s_softc: under vlad_assign=soft_pooled -- the mean centre [D]
+  //  s_softc: under vlad_assign=soft_pooled -- the mean centre [D];
+  //  s_burst: under vlad_burst (burst_kernels.hip) -- the tile sums [B][ceil(N / 128)][N] that add up to g; the discounted weights
+  //  go to s_softw (under hard assignment: the one-hot of the labels times u)
 #define SV_SCRATCH_BUFS(X)                                                                                                      \
   X(s_xt) X(s_labels) X(s_rnorm) X(s_gap) X(s_colmask) X(s_gscale) X(s_segimg) X(s_segoff) X(s_adjoff) X(s_dist) X(s_qnorm)      \
   X(s_misc) X(s_minmax) X(s_voteoff) X(s_cand_cnt) X(s_cand_d2) X(s_cand_id) X(s_thr_d2) X(s_thr_idx) X(s_flag) X(s_qh) X(s_ql)  \
   X(s_ref_cnt) X(s_ref_id) X(s_qscale) X(s_qf16) X(s_xh1) X(s_xh2) X(s_desc) X(s_tokorder) X(s_laboff) X(s_rnsorted) X(s_ovf)     \
   X(s_fb_q) X(s_fb_d2) X(s_fb_idx) X(s_fb_rows) X(s_rd_rows) X(s_rd_q) X(s_rd_d2) X(s_rd_idx) X(s_rd_flags) X(s_rd_p1) X(s_rd_p2)  \
-  X(s_sel_todo) X(s_vote_keys) X(s_vote_cap) X(s_vote_uniq) X(s_vote_tab) X(s_softw) X(s_softc) X(s_pz) X(s_rowbase) X(s_tilegrp) X(s_phys) X(s_covcnt) X(s_bn) X(s_l0part) X(s_ref_lim) X(s_sh_d2) X(s_sh_idx)          \
+  X(s_sel_todo) X(s_vote_keys) X(s_vote_cap) X(s_vote_uniq) X(s_vote_tab) X(s_softw) X(s_softc) X(s_burst) X(s_pz) X(s_rowbase) X(s_tilegrp) X(s_phys) X(s_covcnt) X(s_bn) X(s_l0part) X(s_ref_lim) X(s_sh_d2) X(s_sh_idx)          \
   X(s_sh_rec) X(s_sh_all) X(s_sh_d2c) X(s_sh_idc) X(s_grp_cnt) X(s_grp_ids) X(s_grp_rows) X(s_grp_keys) X(s_grp_work) X(s_grp_pos) X(s_tnk_redo) X(s_tail_part) X(s_km_part) X(s_km_cnt) X(s_kflush) \
   X(s_sl_misc) X(s_sl_q) X(s_sl_cur) X(s_sl_uids) X(s_sl_uoff) X(s_sl_unum) X(s_sl_cand) X(s_sl_lens)                            \
   X(s_deep_d2) X(s_deep_idx) X(s_deep_qn) X(s_ex_flag) X(s_ex_td2) X(s_ex_tidx)                                                        \
@@ -502,6 +506,14 @@ int sv_launch_soft_aggregate(segvlad_ctx* ctx, const float* xt, const float* w, 
                              const int32_t* seg_off_dev, int B, int N, int SC, float* out, float* block_norms,
                              const float* mean_centre = nullptr);
 int sv_launch_soft_finalize(segvlad_ctx* ctx, const float* block_norms, int S_tot, int K, int D, float* out);
+
+// burst_kernels.hip (option vlad_burst=<a>:<b>:<p>; after sv_launch_assign, whose token-major copy and 1 / ||x|| they read).
+// gram: part [B][sv_burst_tiles(N)][N], the sums of sigmoid(a (2 cos(x_n, x_m) - 2) + b) over the m of one 128-token tile, every slot
+// written once.  finish: g[n] = the tile sums in tile order, u = g^-p (exactly 1 for p = 0), and w [B][N][K]: one_hot -- u[n] at
+// k = labels[n], 0 elsewhere; otherwise the rows of w (sv_launch_soft_weights) scaled by u[n].
+int sv_burst_tiles(int N);
+int sv_launch_burst_gram(segvlad_ctx* ctx, const float* xt, const float* rnorm, int B, int N, int D, float a, float b, float* part);
+int sv_launch_burst_finish(segvlad_ctx* ctx, const float* part, const uint8_t* labels, int B, int N, int K, float p, bool one_hot, float* w);
 
 // block norms + the fp16 planes of the token residuals x^ - C_k, grouped by cluster (rowbase from sv_launch_group_plan); after sv_launch_prep
 int sv_launch_token_norms(segvlad_ctx* ctx, const float* xt, const uint64_t* colmask, const float* centres, int K, int D,

@@ -102,6 +102,9 @@ struct DescribePlan {
   float zscale = 0.f;      // Project: scale of the projected residuals on the 16-bit pipe (0: fp32 MFMA)
   float soft_temp = 0.f;   // option vlad_assign: 0 = hard; > 0 = soft assignment at this temperature (soft_vlad_kernels.hip)
   bool soft_pooled = false;   // ... soft_pooled:<T>: residuals against all centres
+  bool burst = false;         // option vlad_burst: every assignment weight times u[n] = g[n]^-p (burst_kernels.hip) ...
+  float burst_a = 0.f, burst_b = 0.f, burst_p = 0.f;   // ... g[n] = sum_m sigmoid(a (2 cos(x_n, x_m) - 2) + b)
+  bool weighted() const { return soft_temp > 0.f || burst; }   // the descriptor is the weight buffer's aggregation (soft_aggregate_kernel)
   int64_t rows_pad = 0;    // Project: grouped token rows, every cluster's rows padded to whole 256-row GEMM tiles
   bool want_desc = false, want_y = false, want_labels = false, want_gap = false, want_block_norms = false;   // the optional outputs
   bool upload_offsets = false;   // this call puts the segment / adjacency offsets on the device (else: the mask branch of its begin did)
@@ -126,11 +129,16 @@ static DescribePlan plan_describe(const segvlad_ctx* ctx, const DescribeIO& io, 
       return PLAN_REFUSE(SEGVLAD_ERR_LIMIT, "images_pca: pca_path=project presupposes one cluster per token, vlad_assign=%s:%g has none "
                                             "(set pca_path to auto or planes, or vlad_assign to hard)",
                          ctx->opt.vlad_soft_pooled ? "soft_pooled" : "soft", (double)ctx->opt.vlad_soft_temp);
+    if (ctx->opt.vlad_burst && ctx->opt.pca_path == 2)   // ... and unweighted tokens
+      return PLAN_REFUSE(SEGVLAD_ERR_LIMIT, "images_pca: pca_path=project presupposes unweighted tokens, vlad_burst=%g:%g:%g weights them "
+                                            "(set pca_path to auto or planes, or vlad_burst to off)",
+                         (double)ctx->opt.burst_a, (double)ctx->opt.burst_b, (double)ctx->opt.burst_p);
   }
   if (K == 0) return PLAN_REFUSE(SEGVLAD_ERR_STATE, "images: call segvlad_set_vocab first");
   p.passes = passes, p.B = B, p.N = N, p.K = K, p.D = D, p.P = ctx->P, p.nw = (N + 63) / 64, p.l2norm = io.l2norm;
   p.soft_pooled = ctx->opt.vlad_soft_pooled != 0;
   p.soft_temp = ctx->opt.vlad_soft_temp;   // (read by the passes behind prep alone: an assign-only plan is the hard assignment)
+  p.burst = ctx->opt.vlad_burst != 0, p.burst_a = ctx->opt.burst_a, p.burst_b = ctx->opt.burst_b, p.burst_p = ctx->opt.burst_p;
   if (passes == Passes::AssignOnly)   // tokens -> token-major copy, norms, labels in the context's scratch; no segments yet
     return (B <= 0 || N <= 0 || !io.tokens) ? PLAN_REFUSE(SEGVLAD_ERR_ARG, "images: B=%d N=%d", B, N) : p;
   if (B < 0 || N <= 0) return PLAN_REFUSE(SEGVLAD_ERR_ARG, "images: B=%d N=%d", B, N);
@@ -156,7 +164,7 @@ static DescribePlan plan_describe(const segvlad_ctx* ctx, const DescribeIO& io, 
   // "project then aggregate" (project_kernels.hip) when the descriptor itself is not asked for.  auto: when it is the smaller product
   // (N D P per image against S K D P) and the batch holds >= 128 tokens per cluster on average -- every cluster's rows are padded to
   // whole 256-row GEMM tiles, below that the split-K descriptor GEMM is quicker ("The fused VLAD -> PCA call", has the numbers)
-  const bool project = p.soft_temp == 0.f && io.out == nullptr && D % 32 == 0 && ctx->P % 4 == 0 && ctx->opt.pca_path != 1 &&
+  const bool project = !p.weighted() && io.out == nullptr && D % 32 == 0 && ctx->P % 4 == 0 && ctx->opt.pca_path != 1 &&
                        (ctx->opt.pca_path == 2 || ((double)p.S_tot * K >= 1.25 * (double)B * N && (double)B * N >= 128.0 * K));
   p.form = project ? DescribeForm::Project : DescribeForm::Planes;
   p.xscale = sv_fp16_scale(1.f + ctx->pca_mean_maxabs);
@@ -203,11 +211,12 @@ static int reserve_scratch(segvlad_ctx* ctx, const DescribePlan& p, DescribeIO& 
   SV_HIP(ctx->s_rnorm.reserve(B * N * sizeof(float)));
   if (!p.want_labels) SV_HIP(ctx->s_labels.reserve(B * N));
   if (p.passes == Passes::AssignOnly) return SEGVLAD_OK;
-  if (p.soft_temp > 0.f && S > 0) {   // the weights, the block norms the row scale is made of, the descriptor the planes are split from
+  if (p.weighted() && S > 0) {   // the weights, the block norms the row scale is made of, the descriptor the planes are split from
     SV_HIP(ctx->s_softw.reserve(B * N * K * sizeof(float)));
     if (p.soft_pooled) SV_HIP(ctx->s_softc.reserve(D * sizeof(float)));
     if (!p.want_block_norms) SV_HIP(ctx->s_bn.reserve(S * K * sizeof(float)));
     if (p.form == DescribeForm::Planes && !p.want_desc) SV_HIP(ctx->s_desc.reserve(S * K * D * sizeof(float)));
+    if (p.burst) SV_HIP(ctx->s_burst.reserve(B * (size_t)sv_burst_tiles(p.N) * N * sizeof(float)));
   }
   SV_HIP(ctx->s_colmask.reserve(B * N * p.SC * 8));
   SV_HIP(ctx->s_gscale.reserve((S + 1) * sizeof(float)));
@@ -261,15 +270,25 @@ static int pass_normalize(segvlad_ctx* ctx, const DescribePlan& p, const Describ
   return SEGVLAD_OK;
 }
 
-// Soft assignment: the weights ("assign"), then intra-normalised blocks + block norms, the rows' scale, and for the planes form the
+// Soft assignment and / or burst discount: the weights ("assign"; "burst": g from the self-similarity tiles, then the weights times
+// g^-p -- under hard assignment the one-hot of the labels times g^-p, so that path too aggregates from the weight buffer, at K times
+// the hard aggregation's MFMA work), then intra-normalised blocks + block norms, the rows' scale, and for the planes form the
 // split of the finished fp32 descriptor that segvlad_pca_apply uses, at the scale known in advance ("aggregate")
 static int pass_soft_descriptor(segvlad_ctx* ctx, const DescribePlan& p, const DescribeIO& io, uint16_t* h1, uint16_t* h2) {
   float* desc = io.d_out ? (float*)io.d_out : ctx->s_desc.as<float>();
   float* bn = io.d_bn ? (float*)io.d_bn : ctx->s_bn.as<float>();
-  {
+  if (p.soft_temp > 0.f) {
     StageScope sc(ctx, "assign");
     SV_TRY(sv_launch_soft_weights(ctx, (const float*)io.d_tok, p.B, p.N, p.soft_temp, ctx->s_softw.as<float>()));
     sc.count();
+  }
+  if (p.burst) {
+    StageScope sc(ctx, "burst");
+    SV_TRY(sv_launch_burst_gram(ctx, ctx->s_xt.as<float>(), ctx->s_rnorm.as<float>(), p.B, p.N, p.D, p.burst_a, p.burst_b,
+                                ctx->s_burst.as<float>()));
+    SV_TRY(sv_launch_burst_finish(ctx, ctx->s_burst.as<float>(), (const uint8_t*)io.d_lab, p.B, p.N, p.K, p.burst_p, p.soft_temp == 0.f,
+                                  ctx->s_softw.as<float>()));
+    sc.count(2);
   }
   StageScope sc(ctx, "aggregate");
   const float* cmean = nullptr;
@@ -293,7 +312,7 @@ static int pass_soft_descriptor(segvlad_ctx* ctx, const DescribePlan& p, const D
 static int pass_descriptor(segvlad_ctx* ctx, const DescribePlan& p, const DescribeIO& io) {
   const bool fused = p.form == DescribeForm::Planes;
   uint16_t *h1 = fused ? ctx->s_xh1.as<uint16_t>() : nullptr, *h2 = fused ? ctx->s_xh2.as<uint16_t>() : nullptr;
-  if (p.soft_temp > 0.f) {
+  if (p.weighted()) {
     SV_TRY(pass_soft_descriptor(ctx, p, io, h1, h2));
   } else {
     StageScope sc(ctx, "aggregate");
@@ -431,6 +450,10 @@ static int describe_begin(segvlad_ctx* ctx, const MaskBranch& m, const float* to
     return ctx->fail(SEGVLAD_ERR_LIMIT, "describe: pca_path=project presupposes one cluster per token, vlad_assign=%s:%g has none "
                                         "(set pca_path to auto or planes, or vlad_assign to hard)",
                      ctx->opt.vlad_soft_pooled ? "soft_pooled" : "soft", (double)ctx->opt.vlad_soft_temp);
+  if (pca && ctx->opt.vlad_burst && ctx->opt.pca_path == 2)
+    return ctx->fail(SEGVLAD_ERR_LIMIT, "describe: pca_path=project presupposes unweighted tokens, vlad_burst=%g:%g:%g weights them "
+                                        "(set pca_path to auto or planes, or vlad_burst to off)",
+                     (double)ctx->opt.burst_a, (double)ctx->opt.burst_b, (double)ctx->opt.burst_p);
   if (B == 0 || S_tot <= 0) return ctx->fail(SEGVLAD_ERR_LIMIT, "describe: no images / no segments (use the separate entry points)");
   // ... and an image that sv_launch_adjacency would refuse: the same bound, asked before the mask branch is forked
   const SegWalk w = walk_seg_offsets(m.seg_offsets, B);

@@ -426,7 +426,46 @@ def vlad_assign_value(mode: str = "hard", temp=None) -> str:
     return mode + ":" + np.format_float_scientific(t, unique=True, trim="0")
 
 
-def soft_vlad_reference(tokens, centres, inc, adj=None, temp: float = 1.0, parts: bool = False, pooled: bool = False):
+BURST_RANGES = ((0.0, 64.0), (-8.0, 16.0), (0.0, 2.0))   # of a, b, p of the option vlad_burst (include/segvlad.h)
+
+
+def vlad_burst_value(a, b, p) -> str:
+    """The value ``<a>:<b>:<p>`` of the option ``vlad_burst``, every field printed so that it reads back as the same fp32.  Refuses
+    what segvlad_set_option refuses: a field that is missing, not a number, not finite as fp32, or outside 0 <= a <= 64,
+    -8 <= b <= 16, 0 <= p <= 2."""
+    fields = []
+    for name, x, (lo, hi) in zip("abp", (a, b, p), BURST_RANGES):
+        if x is None or isinstance(x, (bool, str, bytes)) or np.ndim(x) != 0:
+            raise ValueError(f"vlad_burst: {name} must be a number, got {x!r}")
+        try:
+            with np.errstate(over="ignore"):
+                v = np.float32(x)
+        except (TypeError, ValueError):
+            raise ValueError(f"vlad_burst: {name} must be a number, got {x!r}") from None
+        if not np.isfinite(v) or not lo <= v <= hi:
+            raise ValueError(f"vlad_burst: {name} must be a finite fp32 in [{lo:g}, {hi:g}], got {x!r}")
+        fields.append(np.format_float_scientific(v, unique=True, trim="0"))
+    return ":".join(fields)
+
+
+def burst_reference(tokens, a, b, p):
+    """The definition of ``vlad_burst=<a>:<b>:<p>`` (include/segvlad.h) for ONE image, in NumPy fp64: ``tokens [D][N]`` as the engine
+    takes them, ALL of them, covered by a segment or not.
+
+        g[n] = sum_{m < N} sigmoid(a (2 <x^_n, x^_m> - 2) + b)        (m = n included; an all-zero token has x^ = 0: cosine 0)
+        u[n] = g[n]^-p
+
+    Returns ``(g [N], u [N])``."""
+    X = np.asarray(tokens.detach().cpu().numpy() if isinstance(tokens, torch.Tensor) else tokens).astype(np.float64).T
+    if X.ndim != 2:
+        raise ValueError(f"burst_reference: tokens [D][N], got {X.T.shape}")
+    xh = X / np.maximum(np.linalg.norm(X, axis=1, keepdims=True), 1e-12)
+    z = float(a) * (2.0 * (xh @ xh.T) - 2.0) + float(b)
+    g = (1.0 / (1.0 + np.exp(-z))).sum(axis=1)
+    return g, g ** (-float(p))
+
+
+def soft_vlad_reference(tokens, centres, inc, adj=None, temp: float = 1.0, parts: bool = False, pooled: bool = False, burst=None):
     """The definition of ``vlad_assign=soft:<T>`` (include/segvlad.h; utilities.py:862-887) for ONE image, in NumPy fp64:
     ``tokens [D][N]`` as the engine takes them, ``centres [K][D]`` raw, ``inc [S][N]`` bool incidence, ``adj [S][S]`` or None
     (order 0), ``temp`` = T.
@@ -437,6 +476,9 @@ def soft_vlad_reference(tokens, centres, inc, adj=None, temp: float = 1.0, parts
 
     ``pooled``: the definition of ``vlad_assign=soft_pooled:<T>``, what the reference's ``VLAD.generate`` computes -- block k holds
     the residuals against ALL centres, ``V[s][k] = K sum_n w[n][k] x^_n - (sum_n w[n][k]) sum_c c_c`` (utilities.py:883-884).
+
+    ``burst``: None, or ``(a, b, p)`` of the option ``vlad_burst`` -- every row of w is multiplied by ``u[n]`` of ``burst_reference``
+    (the returned ``w`` holds the discounted weights).
 
     Returns ``out [S][K*D]``; with ``parts`` a dict that also holds ``w [N][K]`` and ``block_norms [S][K]``."""
     def host(x):
@@ -455,6 +497,8 @@ def soft_vlad_reference(tokens, centres, inc, adj=None, temp: float = 1.0, parts
     z = float(temp) * (xh @ ch.T)
     e = np.exp(z - z.max(axis=1, keepdims=True))
     w = e / e.sum(axis=1, keepdims=True)                        # [N][K]
+    if burst is not None:
+        w = w * burst_reference(X.T, *burst)[1][:, None]
     U = inc if adj is None else (host(adj).astype(np.float64).reshape(S, S) @ inc.astype(np.float64)) > 0
     Uf = U.astype(np.float64)
     V = np.einsum("sn,nk,nd->skd", Uf, w, xh, optimize=True)
@@ -507,6 +551,7 @@ class SegVLADEngine:
         self._keep = []  # tensors that must outlive async kernels of the last call
         self.n_img_ref = 0   # 1 + the largest img_of_seg id given to db_add since the last db_reset
         self.vlad_assign = "hard"   # the value of the option vlad_assign as last set through set_vlad_assign / set_option
+        self.vlad_burst = "off"     # ... of the option vlad_burst (set_vlad_burst / set_option)
 
     # ---- plumbing ---------------------------------------------------------------------------------
     def close(self):
@@ -547,6 +592,8 @@ class SegVLADEngine:
         self._check(self.lib.segvlad_set_option(self._h, str(key).encode(), str(value).encode()), f"set_option({key})")
         if key == "vlad_assign":
             self.vlad_assign = str(value)
+        if key == "vlad_burst":
+            self.vlad_burst = str(value)
 
     def set_vlad_assign(self, mode: str = "hard", temp=None) -> str:
         """Option ``vlad_assign`` (include/segvlad.h): ``'hard'``, or ``'soft'`` / ``'soft_pooled'`` with the temperature of
@@ -561,6 +608,18 @@ class SegVLADEngine:
         value = vlad_assign_value(mode, temp)
         before = self.vlad_assign
         self.set_option("vlad_assign", value)
+        return before
+
+    def set_vlad_burst(self, params=None) -> str:
+        """Option ``vlad_burst`` (include/segvlad.h): None switches it off, ``(a, b, p)`` multiplies every token's assignment weight
+        by ``g[n]^-p``, ``g[n] = sum_m sigmoid(a (2 cos(x_n, x_m) - 2) + b)`` over ALL tokens of the token's image (the fixed
+        test-time setting of the burst-aware aggregator is ``(8, 7, 1)``).  Holds for every later seg_vlad / seg_vlad_pca / describe* of
+        this context under hard and soft assignment alike; kmeans_step and cluster_aggregate ignore it.  Hard assignment with the
+        discount aggregates from a one-hot weight buffer on the soft path's kernel: K times the hard aggregation's matrix work.
+        Returns the value that was in force before, in the form set_option takes (this object's own record, like set_vlad_assign's)."""
+        value = "off" if params is None else vlad_burst_value(*params)
+        before = self.vlad_burst
+        self.set_option("vlad_burst", value)
         return before
 
     def hint_query_groups(self, qseg_offsets) -> int:

@@ -642,7 +642,7 @@ int segvlad_vote(segvlad_ctx* ctx, const int64_t* idx, const float* sims, const 
                  int32_t* pred_out, double* score_out);
 
 /* ---- instrumentation: with profiling on, every kernel group of a stage ("incidence", "adjacency",
- *      "assign", "prep", "burst" (the two kernels of the option vlad_burst), "aggregate", "pca", "describe" (segvlad_describe as a whole: its parts overlap), "knn_level0", "knn_gemm", "knn_select", "knn_fallback", "knn_shortlist" (segvlad_search_shortlist), "knn_exclude" (the kernels segvlad_search_excluding adds to its inner search), "knn_group" (the kernels segvlad_search_grouped adds to its inner search), "knn_range" (the kernels of segvlad_range_search), "match_pairs" (segvlad_match_pairs), "verify_pairs" (segvlad_verify_pairs), "sequence_rerank" (segvlad_sequence_rerank), "incidence_rle", "rle_decode", "rle_encode" (the run-length entries), "mask_regions" (segvlad_mask_regions), "db_remove" (segvlad_db_remove), "vote") is bracketed by a HIP event pair
+ *      "assign", "prep", "burst" (the kernels of the option vlad_burst: two under image scope, one under vlad_burst_scope=segment), "aggregate", "pca", "describe" (segvlad_describe as a whole: its parts overlap), "knn_level0", "knn_gemm", "knn_select", "knn_fallback", "knn_shortlist" (segvlad_search_shortlist), "knn_exclude" (the kernels segvlad_search_excluding adds to its inner search), "knn_group" (the kernels segvlad_search_grouped adds to its inner search), "knn_range" (the kernels of segvlad_range_search), "match_pairs" (segvlad_match_pairs), "verify_pairs" (segvlad_verify_pairs), "sequence_rerank" (segvlad_sequence_rerank), "incidence_rle", "rle_decode", "rle_encode" (the run-length entries), "mask_regions" (segvlad_mask_regions), "db_remove" (segvlad_db_remove), "vote") is bracketed by a HIP event pair
  *      on the context stream.  segvlad_stage_ms returns the SUM of the elapsed times (ms) and the number
  *      of kernel launches recorded for the stage since the last segvlad_profile_reset; it returns
  *      SEGVLAD_ERR_STATE if the stage has not run.  Replaces the (discarded) time.time() pair of
@@ -752,6 +752,37 @@ int segvlad_stage_ms(segvlad_ctx* ctx, const char* stage, float* ms_out, int* la
  *                                                      aggregation's matrix work (a label-grouped weighted aggregation is later
  *                                                      work).  A missing, non-finite, out-of-range or junk-trailed field and any
  *                                                      other spelling are SEGVLAD_ERR_ARG and leave the option as it was
+ *        "vlad_burst_scope"  image | segment           over which tokens vlad_burst counts.  Read only while vlad_burst is on: with
+ *                                                      vlad_burst=off the value is stored and changes neither bytes nor launches.
+ *                                                      image (the default): the text above, all N tokens of the image, one weight
+ *                                                      per token.  segment: the tokens that are aggregated with the token -- U(s),
+ *                                                      the token set of segment s after the neighbour union -- so the discount is
+ *                                                      a weight per (segment, token).  With x^_n the normalised token, c_k the raw
+ *                                                      centre and w[n][k] vlad_assign's weight (the one-hot of the label, or the
+ *                                                      softmax):
+ *                                                        g[s][n] = sum_{m in U(s)} sigmoid(a (2 <x^_n, x^_m> - 2) + b)    n in U(s), m = n included
+ *                                                        u[s][n] = g[s][n]^-p
+ *                                                        V[s][k] = sum_{n in U(s)} u[s][n] w[n][k] (x^_n - c_k)
+ *                                                        out[s]  = L2(concat_k intra_norm(V[s][k]))      both divide by max(norm, 1e-12)
+ *                                                      (soft_pooled:<T>: K sum u w x^ - (sum u w) sum_c c_c, the formula above).
+ *                                                      g depends on the image's tokens and on U(s) alone -- not on the other
+ *                                                      segments, not on the rest of the batch.  With one all-token segment per
+ *                                                      image and order 0 it is vlad_burst under image scope (NetVLAD.forward's
+ *                                                      w_burst).  With p = 0, u is exactly 1.  A token with non-zero x^ has
+ *                                                      g >= sigmoid(b) (its own term); an all-zero token takes part with cosine 0,
+ *                                                      as under image scope.  labels_out and gap_out stay the hard arg-max and
+ *                                                      gap, block_norms_out is ||V[s][k]||.  The similarities are fp32 (fp32 MFMA),
+ *                                                      exist one tile at a time in registers, and every sum runs in a fixed order
+ *                                                      (the image's tokens grouped by label) without float atomics: two calls
+ *                                                      return the same bytes.  Covers segvlad_images, segvlad_images_pca,
+ *                                                      segvlad_describe and segvlad_describe_begin / _end; segvlad_kmeans_step and
+ *                                                      segvlad_cluster_aggregate ignore it.  pca_path: auto takes "planes", an
+ *                                                      explicit project is SEGVLAD_ERR_LIMIT (naming vlad_burst), as under image
+ *                                                      scope.  COST: the self-similarity runs as the full square, twice the image
+ *                                                      scope's flops, once per 64 segments of the image; hard assignment
+ *                                                      aggregates over label k's tokens for cluster k, the hard
+ *                                                      aggregation's matrix work, with no weight buffer.  Any other spelling is
+ *                                                      SEGVLAD_ERR_ARG and leaves the option as it was
  *      Every other key is a DEVELOPMENT switch (kernel tuning, A/B variants, debugging, the tests' own hooks), documented in
  *      revisit-anything_amd/csrc/segvlad_dev.h and NOT part of this ABI: none changes a result, the shipped library holds
  *      only the kernels they default to and rejects the values that select another (SEGVLAD_ERR_ARG).

@@ -316,6 +316,11 @@ int segvlad_set_option(segvlad_ctx* ctx, const char* key, const char* value) {
     return ctx->fail(SEGVLAD_ERR_ARG, "set_option(vlad_burst): want off|<a>:<b>:<p>, finite decimals with 0 <= a <= 64, -8 <= b <= 16, "
                                       "0 <= p <= 2, got '%s'", value);
   }
+  if (!strcmp(key, "vlad_burst_scope")) {   // image | segment (include/segvlad.h); stored whatever vlad_burst holds, read only while it is on
+    if (!strcmp(value, "image")) return o.burst_segment = 0, SEGVLAD_OK;
+    if (!strcmp(value, "segment")) return o.burst_segment = 1, SEGVLAD_OK;
+    return ctx->fail(SEGVLAD_ERR_ARG, "set_option(vlad_burst_scope): want image|segment, got '%s'", value);
+  }
   // Switches that select one of the fp16 filter's kernels (csrc/segvlad_dev.h): only the values that name a kernel the library
   // holds are accepted -- the measured-and-not-kept variants are gone from the tree (DESIGN.md 4 / 7 keep their numbers); the
   // development build (-DSEGVLAD_ABLATIONS: lib/libsegvlad_hip_abl.so) adds the probes of the batch kernel.

@@ -203,6 +203,8 @@ struct SvOptions {
   int vlad_soft_pooled = 0;     // "vlad_assign" = soft_pooled:<T>: every block's residuals are taken against ALL centres (the reference's sum)
   int vlad_burst = 0;           // "vlad_burst": 0 = off; 1 = every assignment weight times u[n] = g[n]^-p (burst_kernels.hip)
   float burst_a = 0.f, burst_b = 0.f, burst_p = 0.f;   // ... g[n] = sum_m sigmoid(a (2 cos(x_n, x_m) - 2) + b) over the image's tokens
+  int burst_segment = 0;        // "vlad_burst_scope": 0 = image (the sum runs over the image's N tokens); 1 = segment (over the tokens of
+                                // U(s): a weight per (segment, token), burst_seg_kernels.hip).  Read only while vlad_burst is on
   int group_fetch = 0;    // segvlad_search_grouped: depth of the inner search, clamped to k .. 1024 (0 = min(1024, 4 k)); never changes a
                           // result, only which rows the exact tail finishes (tests reach the tail on a small index with it)
 };
@@ -379,13 +381,15 @@ struct segvlad_ctx {
   //  s_softw: the describe stage under vlad_assign=soft (soft_vlad_kernels.hip) -- the assignment weights w [B][N][K] of the batch;
   //  s_softc: under vlad_assign=soft_pooled -- the mean centre [D];
   //  s_burst: under vlad_burst (burst_kernels.hip) -- the tile sums [B][ceil(N / 128)][N] that add up to g; the discounted weights
-  //  go to s_softw (under hard assignment: the one-hot of the labels times u)
+  //  go to s_softw (under hard assignment: the one-hot of the labels times u);
+  //  s_bseg: under vlad_burst with vlad_burst_scope=segment (burst_seg_kernels.hip) -- the weights u [B][N][64 SC], token rows in
+  //  prep_kernel's label-grouped order, column s of a row the weight of that token in segment s (0 outside U(s))
 #define SV_SCRATCH_BUFS(X)                                                                                                      \
   X(s_xt) X(s_labels) X(s_rnorm) X(s_gap) X(s_colmask) X(s_gscale) X(s_segimg) X(s_segoff) X(s_adjoff) X(s_dist) X(s_qnorm)      \
   X(s_misc) X(s_minmax) X(s_voteoff) X(s_cand_cnt) X(s_cand_d2) X(s_cand_id) X(s_thr_d2) X(s_thr_idx) X(s_flag) X(s_qh) X(s_ql)  \
   X(s_ref_cnt) X(s_ref_id) X(s_qscale) X(s_qf16) X(s_xh1) X(s_xh2) X(s_desc) X(s_tokorder) X(s_laboff) X(s_rnsorted) X(s_ovf)     \
   X(s_fb_q) X(s_fb_d2) X(s_fb_idx) X(s_fb_rows) X(s_rd_rows) X(s_rd_q) X(s_rd_d2) X(s_rd_idx) X(s_rd_flags) X(s_rd_p1) X(s_rd_p2)  \
-  X(s_sel_todo) X(s_vote_keys) X(s_vote_cap) X(s_vote_uniq) X(s_vote_tab) X(s_softw) X(s_softc) X(s_burst) X(s_pz) X(s_rowbase) X(s_tilegrp) X(s_phys) X(s_covcnt) X(s_bn) X(s_l0part) X(s_ref_lim) X(s_sh_d2) X(s_sh_idx)          \
+  X(s_sel_todo) X(s_vote_keys) X(s_vote_cap) X(s_vote_uniq) X(s_vote_tab) X(s_softw) X(s_softc) X(s_burst) X(s_bseg) X(s_pz) X(s_rowbase) X(s_tilegrp) X(s_phys) X(s_covcnt) X(s_bn) X(s_l0part) X(s_ref_lim) X(s_sh_d2) X(s_sh_idx)          \
   X(s_sh_rec) X(s_sh_all) X(s_sh_d2c) X(s_sh_idc) X(s_grp_cnt) X(s_grp_ids) X(s_grp_rows) X(s_grp_keys) X(s_grp_work) X(s_grp_pos) X(s_tnk_redo) X(s_tail_part) X(s_km_part) X(s_km_cnt) X(s_kflush) \
   X(s_sl_misc) X(s_sl_q) X(s_sl_cur) X(s_sl_uids) X(s_sl_uoff) X(s_sl_unum) X(s_sl_cand) X(s_sl_lens)                            \
   X(s_deep_d2) X(s_deep_idx) X(s_deep_qn) X(s_ex_flag) X(s_ex_td2) X(s_ex_tidx)                                                        \
@@ -514,6 +518,18 @@ int sv_launch_soft_finalize(segvlad_ctx* ctx, const float* block_norms, int S_to
 int sv_burst_tiles(int N);
 int sv_launch_burst_gram(segvlad_ctx* ctx, const float* xt, const float* rnorm, int B, int N, int D, float a, float b, float* part);
 int sv_launch_burst_finish(segvlad_ctx* ctx, const float* part, const uint8_t* labels, int B, int N, int K, float p, bool one_hot, float* w);
+
+// burst_seg_kernels.hip (vlad_burst with vlad_burst_scope=segment; after sv_launch_prep, whose label-grouped order, sorted 1 / ||x|| and
+// column masks they read).  gram: u [B][N][64 SC], row = POSITION in the label-grouped order, column s = g[s][n]^-p where bit s of the
+// position's column mask is set and 0 elsewhere, g[s][n] = sum_{m in U(s)} sigmoid(a (2 cos(x_n, x_m) - 2) + b); the chunks of 64
+// columns beyond an image's segments are left unwritten.  aggregate: sv_launch_soft_aggregate's outputs with the A operand
+// bit ? u : 0; w == nullptr is hard assignment (cluster k walks label k's positions with weight 1), else w [B][N][K] of
+// sv_launch_soft_weights over every covered position.  sv_launch_soft_finalize follows as behind the soft aggregation.
+int sv_launch_burst_seg_gram(segvlad_ctx* ctx, const float* xt, const uint64_t* colmask, const int32_t* seg_off_dev, int B, int N, int D,
+                             int SC, float a, float b, float p, float* u);
+int sv_launch_burst_seg_aggregate(segvlad_ctx* ctx, const float* xt, const float* w, const float* u, const uint64_t* colmask,
+                                  const float* centres, int K, int D, const int32_t* seg_off_dev, int B, int N, int SC, float* out,
+                                  float* block_norms, const float* mean_centre = nullptr);
 
 // block norms + the fp16 planes of the token residuals x^ - C_k, grouped by cluster (rowbase from sv_launch_group_plan); after sv_launch_prep
 int sv_launch_token_norms(segvlad_ctx* ctx, const float* xt, const uint64_t* colmask, const float* centres, int K, int D,

@@ -104,6 +104,8 @@ struct DescribePlan {
   bool soft_pooled = false;   // ... soft_pooled:<T>: residuals against all centres
   bool burst = false;         // option vlad_burst: every assignment weight times u[n] = g[n]^-p (burst_kernels.hip) ...
   float burst_a = 0.f, burst_b = 0.f, burst_p = 0.f;   // ... g[n] = sum_m sigmoid(a (2 cos(x_n, x_m) - 2) + b)
+  bool burst_segment = false;   // ... option vlad_burst_scope=segment (set only with burst): the sum runs over U(s), a weight per
+                                // (segment, token) in s_bseg (burst_seg_kernels.hip)
   bool weighted() const { return soft_temp > 0.f || burst; }   // the descriptor is the weight buffer's aggregation (soft_aggregate_kernel)
   int64_t rows_pad = 0;    // Project: grouped token rows, every cluster's rows padded to whole 256-row GEMM tiles
   bool want_desc = false, want_y = false, want_labels = false, want_gap = false, want_block_norms = false;   // the optional outputs
@@ -139,6 +141,7 @@ static DescribePlan plan_describe(const segvlad_ctx* ctx, const DescribeIO& io, 
   p.soft_pooled = ctx->opt.vlad_soft_pooled != 0;
   p.soft_temp = ctx->opt.vlad_soft_temp;   // (read by the passes behind prep alone: an assign-only plan is the hard assignment)
   p.burst = ctx->opt.vlad_burst != 0, p.burst_a = ctx->opt.burst_a, p.burst_b = ctx->opt.burst_b, p.burst_p = ctx->opt.burst_p;
+  p.burst_segment = p.burst && ctx->opt.burst_segment != 0;
   if (passes == Passes::AssignOnly)   // tokens -> token-major copy, norms, labels in the context's scratch; no segments yet
     return (B <= 0 || N <= 0 || !io.tokens) ? PLAN_REFUSE(SEGVLAD_ERR_ARG, "images: B=%d N=%d", B, N) : p;
   if (B < 0 || N <= 0) return PLAN_REFUSE(SEGVLAD_ERR_ARG, "images: B=%d N=%d", B, N);
@@ -212,11 +215,13 @@ static int reserve_scratch(segvlad_ctx* ctx, const DescribePlan& p, DescribeIO& 
   if (!p.want_labels) SV_HIP(ctx->s_labels.reserve(B * N));
   if (p.passes == Passes::AssignOnly) return SEGVLAD_OK;
   if (p.weighted() && S > 0) {   // the weights, the block norms the row scale is made of, the descriptor the planes are split from
-    SV_HIP(ctx->s_softw.reserve(B * N * K * sizeof(float)));
+    // (segment scope under hard assignment has no weight buffer: label k's positions carry weight 1)
+    if (!(p.burst_segment && p.soft_temp == 0.f)) SV_HIP(ctx->s_softw.reserve(B * N * K * sizeof(float)));
     if (p.soft_pooled) SV_HIP(ctx->s_softc.reserve(D * sizeof(float)));
     if (!p.want_block_norms) SV_HIP(ctx->s_bn.reserve(S * K * sizeof(float)));
     if (p.form == DescribeForm::Planes && !p.want_desc) SV_HIP(ctx->s_desc.reserve(S * K * D * sizeof(float)));
-    if (p.burst) SV_HIP(ctx->s_burst.reserve(B * (size_t)sv_burst_tiles(p.N) * N * sizeof(float)));
+    if (p.burst_segment) SV_HIP(ctx->s_bseg.reserve(B * N * 64 * (size_t)p.SC * sizeof(float)));
+    else if (p.burst) SV_HIP(ctx->s_burst.reserve(B * (size_t)sv_burst_tiles(p.N) * N * sizeof(float)));
   }
   SV_HIP(ctx->s_colmask.reserve(B * N * p.SC * 8));
   SV_HIP(ctx->s_gscale.reserve((S + 1) * sizeof(float)));
@@ -273,7 +278,10 @@ static int pass_normalize(segvlad_ctx* ctx, const DescribePlan& p, const Describ
 // Soft assignment and / or burst discount: the weights ("assign"; "burst": g from the self-similarity tiles, then the weights times
 // g^-p -- under hard assignment the one-hot of the labels times g^-p, so that path too aggregates from the weight buffer, at K times
 // the hard aggregation's MFMA work), then intra-normalised blocks + block norms, the rows' scale, and for the planes form the
-// split of the finished fp32 descriptor that segvlad_pca_apply uses, at the scale known in advance ("aggregate")
+// split of the finished fp32 descriptor that segvlad_pca_apply uses, at the scale known in advance ("aggregate").
+// vlad_burst_scope=segment: "burst" is one kernel, the weights u[s][n] of every (segment, covered token) from the tiles of the
+// self-similarity times the column masks; the aggregation takes them as its A operand and, under hard assignment, walks label k's
+// positions for cluster k -- the hard aggregation's matrix work, no weight buffer
 static int pass_soft_descriptor(segvlad_ctx* ctx, const DescribePlan& p, const DescribeIO& io, uint16_t* h1, uint16_t* h2) {
   float* desc = io.d_out ? (float*)io.d_out : ctx->s_desc.as<float>();
   float* bn = io.d_bn ? (float*)io.d_bn : ctx->s_bn.as<float>();
@@ -282,7 +290,12 @@ static int pass_soft_descriptor(segvlad_ctx* ctx, const DescribePlan& p, const D
     SV_TRY(sv_launch_soft_weights(ctx, (const float*)io.d_tok, p.B, p.N, p.soft_temp, ctx->s_softw.as<float>()));
     sc.count();
   }
-  if (p.burst) {
+  if (p.burst_segment) {
+    StageScope sc(ctx, "burst");
+    SV_TRY(sv_launch_burst_seg_gram(ctx, ctx->s_xt.as<float>(), ctx->s_colmask.as<uint64_t>(), ctx->s_segoff.as<int32_t>(), p.B, p.N, p.D,
+                                    p.SC, p.burst_a, p.burst_b, p.burst_p, ctx->s_bseg.as<float>()));
+    sc.count();
+  } else if (p.burst) {
     StageScope sc(ctx, "burst");
     SV_TRY(sv_launch_burst_gram(ctx, ctx->s_xt.as<float>(), ctx->s_rnorm.as<float>(), p.B, p.N, p.D, p.burst_a, p.burst_b,
                                 ctx->s_burst.as<float>()));
@@ -297,8 +310,13 @@ static int pass_soft_descriptor(segvlad_ctx* ctx, const DescribePlan& p, const D
     sc.count();
     cmean = ctx->s_softc.as<float>();
   }
-  SV_TRY(sv_launch_soft_aggregate(ctx, ctx->s_xt.as<float>(), ctx->s_softw.as<float>(), ctx->s_colmask.as<uint64_t>(), ctx->vocab.as<float>(),
-                                  p.K, p.D, ctx->s_segoff.as<int32_t>(), p.B, p.N, p.SC, desc, bn, cmean));
+  if (p.burst_segment)
+    SV_TRY(sv_launch_burst_seg_aggregate(ctx, ctx->s_xt.as<float>(), p.soft_temp > 0.f ? ctx->s_softw.as<float>() : nullptr,
+                                         ctx->s_bseg.as<float>(), ctx->s_colmask.as<uint64_t>(), ctx->vocab.as<float>(), p.K, p.D,
+                                         ctx->s_segoff.as<int32_t>(), p.B, p.N, p.SC, desc, bn, cmean));
+  else
+    SV_TRY(sv_launch_soft_aggregate(ctx, ctx->s_xt.as<float>(), ctx->s_softw.as<float>(), ctx->s_colmask.as<uint64_t>(), ctx->vocab.as<float>(),
+                                    p.K, p.D, ctx->s_segoff.as<int32_t>(), p.B, p.N, p.SC, desc, bn, cmean));
   SV_TRY(sv_launch_soft_finalize(ctx, bn, p.S_tot, p.K, p.D, desc));
   sc.count(2);
   if (h1) {

@@ -465,7 +465,36 @@ def burst_reference(tokens, a, b, p):
     return g, g ** (-float(p))
 
 
-def soft_vlad_reference(tokens, centres, inc, adj=None, temp: float = 1.0, parts: bool = False, pooled: bool = False, burst=None):
+BURST_SCOPES = ("image", "segment")   # of the option vlad_burst_scope (include/segvlad.h)
+
+
+def burst_segment_reference(tokens, inc, adj, a, b, p):
+    """The definition of ``vlad_burst=<a>:<b>:<p>`` under ``vlad_burst_scope=segment`` (include/segvlad.h) for ONE image, in NumPy
+    fp64: ``tokens [D][N]`` as the engine takes them, ``inc [S][N]`` bool incidence, ``adj [S][S]`` or None (order 0).
+
+        U(s)    = the tokens of segment s after the neighbour union, (adj . inc) > 0
+        g[s][n] = sum_{m in U(s)} sigmoid(a (2 <x^_n, x^_m> - 2) + b)      n in U(s), m = n included (an all-zero token: cosine 0)
+        u[s][n] = g[s][n]^-p                                               0 outside U(s)
+
+    Returns ``(g [S][N], u [S][N])``, both 0 outside U(s)."""
+    X = np.asarray(tokens.detach().cpu().numpy() if isinstance(tokens, torch.Tensor) else tokens).astype(np.float64).T
+    inc = np.asarray(inc.detach().cpu().numpy() if isinstance(inc, torch.Tensor) else inc).astype(bool)
+    if X.ndim != 2 or inc.ndim != 2 or inc.shape[1] != X.shape[0]:
+        raise ValueError(f"burst_segment_reference: tokens [D][N] and inc [S][N], got {X.T.shape} and {inc.shape}")
+    S = inc.shape[0]
+    if adj is not None:
+        adj = np.asarray(adj.detach().cpu().numpy() if isinstance(adj, torch.Tensor) else adj).astype(np.float64).reshape(S, S)
+    U = inc if adj is None else (adj @ inc.astype(np.float64)) > 0
+    xh = X / np.maximum(np.linalg.norm(X, axis=1, keepdims=True), 1e-12)
+    z = float(a) * (2.0 * (xh @ xh.T) - 2.0) + float(b)
+    g = (U.astype(np.float64) @ (1.0 / (1.0 + np.exp(-z)))) * U          # [S][N]: row s sums the columns m in U(s)
+    u = np.zeros_like(g)
+    u[U] = g[U] ** (-float(p))
+    return g, u
+
+
+def soft_vlad_reference(tokens, centres, inc, adj=None, temp: float = 1.0, parts: bool = False, pooled: bool = False, burst=None,
+                        burst_scope: str = "image"):
     """The definition of ``vlad_assign=soft:<T>`` (include/segvlad.h; utilities.py:862-887) for ONE image, in NumPy fp64:
     ``tokens [D][N]`` as the engine takes them, ``centres [K][D]`` raw, ``inc [S][N]`` bool incidence, ``adj [S][S]`` or None
     (order 0), ``temp`` = T.
@@ -478,7 +507,8 @@ def soft_vlad_reference(tokens, centres, inc, adj=None, temp: float = 1.0, parts
     the residuals against ALL centres, ``V[s][k] = K sum_n w[n][k] x^_n - (sum_n w[n][k]) sum_c c_c`` (utilities.py:883-884).
 
     ``burst``: None, or ``(a, b, p)`` of the option ``vlad_burst`` -- every row of w is multiplied by ``u[n]`` of ``burst_reference``
-    (the returned ``w`` holds the discounted weights).
+    (the returned ``w`` holds the discounted weights).  ``burst_scope='segment'``: the option ``vlad_burst_scope`` -- the incidence
+    of (segment, token) is multiplied by ``u[s][n]`` of ``burst_segment_reference`` instead, and ``w`` stays the softmax.
 
     Returns ``out [S][K*D]``; with ``parts`` a dict that also holds ``w [N][K]`` and ``block_norms [S][K]``."""
     def host(x):
@@ -497,10 +527,14 @@ def soft_vlad_reference(tokens, centres, inc, adj=None, temp: float = 1.0, parts
     z = float(temp) * (xh @ ch.T)
     e = np.exp(z - z.max(axis=1, keepdims=True))
     w = e / e.sum(axis=1, keepdims=True)                        # [N][K]
-    if burst is not None:
+    if burst_scope not in BURST_SCOPES:
+        raise ValueError(f"soft_vlad_reference: burst_scope must be one of {BURST_SCOPES}, got {burst_scope!r}")
+    if burst is not None and burst_scope == "image":
         w = w * burst_reference(X.T, *burst)[1][:, None]
     U = inc if adj is None else (host(adj).astype(np.float64).reshape(S, S) @ inc.astype(np.float64)) > 0
     Uf = U.astype(np.float64)
+    if burst is not None and burst_scope == "segment":
+        Uf = burst_segment_reference(X.T, inc, None if adj is None else host(adj), *burst)[1]
     V = np.einsum("sn,nk,nd->skd", Uf, w, xh, optimize=True)
     V = K * V - (Uf @ w)[:, :, None] * Cm.sum(0)[None, None] if pooled else V - (Uf @ w)[:, :, None] * Cm[None]
     bn = np.linalg.norm(V, axis=2)                              # [S][K]
@@ -552,6 +586,7 @@ class SegVLADEngine:
         self.n_img_ref = 0   # 1 + the largest img_of_seg id given to db_add since the last db_reset
         self.vlad_assign = "hard"   # the value of the option vlad_assign as last set through set_vlad_assign / set_option
         self.vlad_burst = "off"     # ... of the option vlad_burst (set_vlad_burst / set_option)
+        self.vlad_burst_scope = "image"   # ... of the option vlad_burst_scope (set_vlad_burst_scope / set_option)
 
     # ---- plumbing ---------------------------------------------------------------------------------
     def close(self):
@@ -594,6 +629,8 @@ class SegVLADEngine:
             self.vlad_assign = str(value)
         if key == "vlad_burst":
             self.vlad_burst = str(value)
+        if key == "vlad_burst_scope":
+            self.vlad_burst_scope = str(value)
 
     def set_vlad_assign(self, mode: str = "hard", temp=None) -> str:
         """Option ``vlad_assign`` (include/segvlad.h): ``'hard'``, or ``'soft'`` / ``'soft_pooled'`` with the temperature of
@@ -620,6 +657,19 @@ class SegVLADEngine:
         value = "off" if params is None else vlad_burst_value(*params)
         before = self.vlad_burst
         self.set_option("vlad_burst", value)
+        return before
+
+    def set_vlad_burst_scope(self, scope: str = "image") -> str:
+        """Option ``vlad_burst_scope`` (include/segvlad.h): over which tokens the burst discount counts.  ``'image'`` (the default):
+        all N tokens of the token's image, one weight per token.  ``'segment'``: the tokens of U(s), the segment's own after the
+        neighbour union -- one weight per (segment, token), ``g[s][n] = sum_{m in U(s)} sigmoid(a (2 cos(x_n, x_m) - 2) + b)``;
+        hard assignment then aggregates at the hard path's matrix work.  Read only while ``vlad_burst`` is on; with it off the value
+        is stored and changes nothing.  Anything else is a ValueError and leaves the option as it was.  Returns the value that was
+        in force before (this object's own record, like set_vlad_burst's)."""
+        if not isinstance(scope, str) or scope not in BURST_SCOPES:
+            raise ValueError(f"vlad_burst_scope: want one of {BURST_SCOPES}, got {scope!r}")
+        before = self.vlad_burst_scope
+        self.set_option("vlad_burst_scope", scope)
         return before
 
     def hint_query_groups(self, qseg_offsets) -> int:

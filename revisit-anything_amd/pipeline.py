@@ -45,8 +45,11 @@ def adjacency_batch(centroids: np.ndarray, seg_offsets: Sequence[int], order: in
 class SegVLADPipeline:
     def __init__(self, engine: SegVLADEngine, H: int, W: int, patch: int = 14, order: int = 3, use_pca: bool = True,
                  adj_workers: int = 8, host_adjacency: bool = False, fuse_pca: bool = True, check_empty: bool = True,
-                 vlad_mode: str = None, soft_temp: float = None, vlad_burst=None):
+                 vlad_mode: str = None, soft_temp: float = None, vlad_burst=None, vlad_burst_scope: str = None):
         self.eng = engine
+        # vlad_burst_scope 'image' | 'segment': the engine's option vlad_burst_scope; None leaves the engine as it is
+        if vlad_burst_scope is not None:
+            engine.set_vlad_burst_scope(vlad_burst_scope)
         # vlad_burst (a, b, p): the engine's option vlad_burst, set here like vlad_mode; None leaves the engine as it is
         if vlad_burst is not None:
             engine.set_vlad_burst(tuple(vlad_burst))

@@ -59,8 +59,9 @@ def batch(dev, B):
     return C, x, m, (np.arange(B + 1) * S).astype(np.int32)
 
 
-def one_run(mode, B, warmup, steps):
-    """This process: one library (SEGVLAD_LIB_PATH or the tree's), one mode, one batch size."""
+def one_run(mode, B, warmup, steps, scope=None):
+    """This process: one library (SEGVLAD_LIB_PATH or the tree's), one mode, one batch size; scope: the option vlad_burst_scope
+    (tools/measure_burst_scope.py), None leaves the default."""
     import torch
 
     os.environ["SEGVLAD_GUARD"] = "0"
@@ -82,6 +83,8 @@ def one_run(mode, B, warmup, steps):
         eng.set_option("vlad_assign", assign)
     if burst:
         eng.set_option("vlad_burst", BURST)
+    if scope:
+        eng.set_option("vlad_burst_scope", scope)
 
     def call():
         return eng.describe(m, x, offs, H, W, 14, ORDER, pca=True, l2norm=True)

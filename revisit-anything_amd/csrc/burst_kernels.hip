@@ -2,7 +2,8 @@
 // of the tokens of ITS image that look like it,
 //   g[n] = sum_{m < N} sigmoid(a (2 <x^_n, x^_m> - 2) + b),      u[n] = g[n]^-p,      w[n][k] <- w[n][k] u[n].
 //
-//   burst_gram_kernel    one 128 x 128 tile of an image's N x N self-similarity on the fp32 MFMA; the sigmoid and the row (and, off the
+//   burst_gram_kernel    one 128 x 128 tile of an image's N x N self-similarity on the fp32 MFMA (sv_gram_tile, gram_tile_dev.h, which
+//                        the segment scope of burst_seg_kernels.hip runs too); the sigmoid and the row (and, off the
 //                        diagonal, column) sums in the epilogue; the matrix itself never exists outside the accumulators
 //   burst_finish_kernel  g = the tile sums added in tile order, u = g^-p, and the weights the soft aggregation reads: the one-hot of the
 //                        labels times u (hard assignment), or the rows of soft_weights_kernel's w scaled by u
@@ -12,90 +13,36 @@
 // when t >= R and by tile (t, R)'s column sums when t < R: every slot exactly once, no atomics, and burst_finish_kernel's sum over
 // t = 0 .. T-1 has one fixed order whatever the batch holds.
 #include "ctx.h"
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-#define MFMA32(a, b, c) __builtin_amdgcn_mfma_f32_32x32x2f32((a), (b), (c), 0, 0, 0)
-
-constexpr int BG_TILE = 128;   // tokens per tile side: 4 waves, each a 64 x 64 quadrant (2 x 2 MFMA tiles)
-constexpr int BG_KC = 32;      // d per LDS chunk
-constexpr int BG_LD = 36;      // LDS row stride in floats: lane i's 16 bytes start at bank 36 i mod 64 = 4 (9 i mod 16), and each of the
-                               // four 16-lane groups of a ds_read_b128 holds every i mod 16 once: no bank conflict
-
-// row of D-fragment register r for lane half kk (v_mfma_f32_32x32x2_f32 C/D layout); the column is the lane's i
-__device__ __forceinline__ int bg_frag_row(int r, int kk) { return (r & 3) + 8 * (r >> 2) + 4 * kk; }
+#include "gram_tile_dev.h"
 
 // Operands: both from the token-major copy Xt [B][N][D] (raw tokens; the cosine is the dot product times the two 1 / ||x|| in the
-// epilogue).  Lane (i, kk) of a wave reads 4 consecutive d of token i per ds_read_b128 -- d = 8 q + 4 kk + c feeds MFMA step (q, c) on
-// both sides, so the contraction runs over every d once in one fixed order.  Rows beyond N and columns of d beyond D are zero in LDS;
-// rows / columns beyond N are masked out of the sums (a padded column is not zero: it would add sigmoid(b - 2 a)).
+// epilogue), multiplied by sv_gram_tile (gram_tile_dev.h) with the positions themselves as rows.  Rows / columns beyond N are masked
+// out of the sums (a padded column is not zero: it would add sigmoid(b - 2 a)).
 __global__ __launch_bounds__(256) void burst_gram_kernel(const float* __restrict__ Xt, const float* __restrict__ rnorm, int B, int N, int D,
                                                          int T, int by_xcd, float a, float bb, float* __restrict__ part) {
-  __shared__ __attribute__((aligned(16))) float sA[BG_TILE * BG_LD];
-  __shared__ __attribute__((aligned(16))) float sB[BG_TILE * BG_LD];
-  __shared__ float rowp[2][BG_TILE], colp[2][BG_TILE];
+  __shared__ __attribute__((aligned(16))) float sA[SV_GRAM_TILE * SV_GRAM_LD];
+  __shared__ __attribute__((aligned(16))) float sB[SV_GRAM_TILE * SV_GRAM_LD];
+  __shared__ float rowp[2][SV_GRAM_TILE], colp[2][SV_GRAM_TILE];
   const int TP = T * (T + 1) / 2;
   int img, t;
-  if (by_xcd) {   // workgroups are dealt to the 8 XCDs by their linear id: the TP tiles of one image share an XCD's L2
-    const int slot = (int)blockIdx.x >> 3;
-    img = (slot / TP) * 8 + ((int)blockIdx.x & 7), t = slot % TP;
-  } else {
-    img = (int)blockIdx.x / TP, t = (int)blockIdx.x % TP;
-  }
+  sv_gram_deal(by_xcd, TP, img, t);
   if (img >= B) return;
   int I = 0;
   while (t >= T - I) t -= T - I, ++I;
   const int J = I + t;
-  const int n0 = I * BG_TILE, m0 = J * BG_TILE;
+  const int n0 = I * SV_GRAM_TILE, m0 = J * SV_GRAM_TILE;
 
   const int tid = threadIdx.x, w = tid >> 6, l = tid & 63, i = l & 31, kk = l >> 5;
   const int wr = w >> 1, wc = w & 1;
-  const float* Xb = Xt + (size_t)img * N * D;
-  const int lc = 4 * (tid & 7), lr = tid >> 3;   // this thread's float4 column of a chunk and its first row (then + 32, 64, 96)
-
-  float4 pa[4], pb[4];
-  auto fetch = [&](int d0) {
-    const bool dok = d0 + lc < D;   // (D % 4 == 0: a float4 is inside or outside as a whole)
+  int ra[4], rb[4];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int ra = n0 + lr + 32 * j, rb = m0 + lr + 32 * j;
-      pa[j] = (dok && ra < N) ? *reinterpret_cast<const float4*>(Xb + (size_t)ra * D + d0 + lc) : make_float4(0.f, 0.f, 0.f, 0.f);
-      pb[j] = (dok && rb < N) ? *reinterpret_cast<const float4*>(Xb + (size_t)rb * D + d0 + lc) : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-  };
-  f32x16 acc[2][2];
-#pragma unroll
-  for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-    for (int tj = 0; tj < 2; ++tj)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[ti][tj][r] = 0.f;
-
-  fetch(0);
-  for (int d0 = 0; d0 < D; d0 += BG_KC) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      *reinterpret_cast<float4*>(sA + (lr + 32 * j) * BG_LD + lc) = pa[j];
-      *reinterpret_cast<float4*>(sB + (lr + 32 * j) * BG_LD + lc) = pb[j];
-    }
-    __syncthreads();
-    if (d0 + BG_KC < D) fetch(d0 + BG_KC);   // the next chunk's loads are in flight under this chunk's MFMAs
-#pragma unroll
-    for (int q = 0; q < BG_KC / 8; ++q) {
-      const int dc = 8 * q + 4 * kk;
-      const float4 a0 = *reinterpret_cast<const float4*>(sA + (64 * wr + i) * BG_LD + dc);
-      const float4 a1 = *reinterpret_cast<const float4*>(sA + (64 * wr + 32 + i) * BG_LD + dc);
-      const float4 b0 = *reinterpret_cast<const float4*>(sB + (64 * wc + i) * BG_LD + dc);
-      const float4 b1 = *reinterpret_cast<const float4*>(sB + (64 * wc + 32 + i) * BG_LD + dc);
-#define BG_STEP(c)                                  \
-  acc[0][0] = MFMA32(a0.c, b0.c, acc[0][0]);        \
-  acc[0][1] = MFMA32(a0.c, b1.c, acc[0][1]);        \
-  acc[1][0] = MFMA32(a1.c, b0.c, acc[1][0]);        \
-  acc[1][1] = MFMA32(a1.c, b1.c, acc[1][1]);
-      BG_STEP(x) BG_STEP(y) BG_STEP(z) BG_STEP(w)
-#undef BG_STEP
-    }
-    __syncthreads();
+  for (int j = 0; j < 4; ++j) {
+    const int r = (tid >> 3) + 32 * j;
+    ra[j] = n0 + r < N ? n0 + r : -1;
+    rb[j] = m0 + r < N ? m0 + r : -1;
   }
+  f32x16 acc[2][2];
+  sv_gram_tile(Xt + (size_t)img * N * D, ra, rb, D, sA, sB, acc);
 
   // ---- epilogue: sigmoid(a (2 cos - 2) + b), masked; row sums over the wave's 64 columns, column sums over its 64 rows ----
   float rn_col[2];
@@ -111,7 +58,7 @@ __global__ __launch_bounds__(256) void burst_gram_kernel(const float* __restrict
   for (int ti = 0; ti < 2; ++ti) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int row = 64 * wr + 32 * ti + bg_frag_row(r, kk);
+      const int row = 64 * wr + 32 * ti + sv_frag_row(r, kk);
       const int n = n0 + row;
       const bool ok_row = n < N;
       const float rn_row = ok_row ? rnorm[(size_t)img * N + n] : 0.f;
@@ -139,23 +86,21 @@ __global__ __launch_bounds__(256) void burst_gram_kernel(const float* __restrict
     if (kk == 0) colp[wr][64 * wc + 32 * tj + i] = c;
   }
   __syncthreads();
-  if (tid < BG_TILE) {
+  if (tid < SV_GRAM_TILE) {
     if (n0 + tid < N) part[((size_t)img * T + J) * N + n0 + tid] = rowp[0][tid] + rowp[1][tid];
   } else if (I != J) {
-    const int c = tid - BG_TILE;
+    const int c = tid - SV_GRAM_TILE;
     if (m0 + c < N) part[((size_t)img * T + I) * N + m0 + c] = colp[0][c] + colp[1][c];
   }
 }
 
-int sv_burst_tiles(int N) { return (N + BG_TILE - 1) / BG_TILE; }
+int sv_burst_tiles(int N) { return (N + SV_GRAM_TILE - 1) / SV_GRAM_TILE; }
 
 int sv_launch_burst_gram(segvlad_ctx* ctx, const float* xt, const float* rnorm, int B, int N, int D, float a, float b, float* part) {
   const int T = sv_burst_tiles(N), TP = T * (T + 1) / 2;
-  // a batch of >= 8 images: image b on XCD b % 8; fewer: the tiles spread over every XCD
-  const int by_xcd = B >= 8 ? 1 : 0;
-  const long long nwg = by_xcd ? 8ll * ((B + 7) / 8) * TP : (long long)B * TP;
+  const long long nwg = sv_gram_grid(B, TP);
   if (nwg > 0x7fffffffll) return ctx->fail(SEGVLAD_ERR_LIMIT, "burst: B=%d N=%d give %lld tiles", B, N, nwg);
-  hipLaunchKernelGGL(burst_gram_kernel, dim3((unsigned)nwg), dim3(256), 0, ctx->stream, xt, rnorm, B, N, D, T, by_xcd, a, b, part);
+  hipLaunchKernelGGL(burst_gram_kernel, dim3((unsigned)nwg), dim3(256), 0, ctx->stream, xt, rnorm, B, N, D, T, sv_gram_by_xcd(B), a, b, part);
   SV_HIP(hipGetLastError());
   return SEGVLAD_OK;
 }
@@ -171,7 +116,7 @@ __global__ __launch_bounds__(256) void burst_finish_kernel(const float* __restri
     const int n = t0 + tid;
     float g = 0.f;
     for (int t = 0; t < T; ++t) g += part[((size_t)b * T + t) * N + n];   // t = 0 .. T-1: fixed order
-    su[tid] = p == 0.f ? 1.0f : p == 1.f ? 1.0f / g : powf(g, -p);
+    su[tid] = sv_burst_discount(g, p);
     slab[tid] = one_hot ? (int)labels[(size_t)b * N + n] : 0;
   }
   __syncthreads();

@@ -3,39 +3,28 @@
 // that look like it,
 //   g[s][n] = sum_{m in U(s)} sigmoid(a (2 <x^_n, x^_m> - 2) + b),      u[s][n] = g[s][n]^-p,      V[s][k] = sum_{n in U(s)} u[s][n] w[n][k] (x^_n - c_k).
 //
-//   burst_seg_gram_kernel        per (image, 128 tokens n, 64 segments): walks the 128 x 128 tiles of the self-similarity down the
-//                                image's tokens m on the fp32 MFMA, turns every tile into its sigmoid in the accumulators and feeds
+//   burst_seg_gram_kernel        per (image, 128 tokens n, 64 segments): walks the 128 x 128 tiles of the self-similarity (sv_gram_tile,
+//                                gram_tile_dev.h) down the image's tokens m on the fp32 MFMA, turns every tile into its sigmoid in the accumulators and feeds
 //                                them, as they lie, to a second MFMA product with the 0/1 tile of the column masks; u = g^-p on the
 //                                bits of U(s), 0 elsewhere, written once
-//   burst_seg_aggregate_kernel   soft_aggregate_kernel's geometry with the A operand bit ? u[s][t] : 0; under hard assignment cluster k
-//                                walks label k's positions only, with weight 1
+//   burst_seg_aggregate_kernel   the aggregation frame of weighted_agg_dev.h with the A operand bit ? u[s][t] : 0 and a plain-load loop;
+//                                under hard assignment cluster k walks label k's positions only, with weight 1
 //
 // Tokens are addressed by their POSITION in prep_kernel's label-grouped order throughout (the column masks, the sorted 1 / ||x|| and the
 // rows of u are indexed by it): every sum runs in that order of ONE image, fixed, whatever the batch or the other segments hold.  An MFMA
 // step is a k-ordered fmaf chain, a term with a zero mask bit adds an exact 0: g[s][n] is the chain over the tokens of U(s) alone.
 #include "ctx.h"
+#include "gram_tile_dev.h"
+#include "weighted_agg_dev.h"
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-#define MFMA32(a, b, c) __builtin_amdgcn_mfma_f32_32x32x2f32((a), (b), (c), 0, 0, 0)
-
-template <int CTRL>
-__device__ __forceinline__ float bs_dpp_f32(float x) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), CTRL, 0xf, 0xf, true));
-}
-// row of D-fragment register r for lane half kk (v_mfma_f32_32x32x2_f32 C/D layout); the column is the lane's i
-__device__ __forceinline__ int bs_frag_row(int r, int kk) { return (r & 3) + 8 * (r >> 2) + 4 * kk; }
-
-constexpr int BS_TILE = 128;   // tokens per tile side: 4 waves, each a 64 x 64 quadrant (2 x 2 MFMA tiles) -- burst_gram_kernel's tile
-constexpr int BS_KC = 32;      // d per LDS chunk
-constexpr int BS_LD = 36;      // LDS row stride in floats (burst_gram_kernel: no bank conflict on its ds_read_b128)
 constexpr int BS_GLD = 65;     // row stride of the [128 tokens][64 segments] image of g in LDS
 
 // ------------------------------------------------------------------------------------------------
 // gram: workgroup = (image, column tile J, chunk of 64 segments).  It owns the 128 tokens n of tile J and walks the row tiles
-// I = 0 .. T-1 (tokens m).  Tile (I, J) is burst_gram_kernel's product: rows m from sA, columns n from sB, the cosine = the raw dot
-// product times the two 1 / ||x||.  In the C/D layout lane (i, kk) holds column i and the 16 rows bs_frag_row(r, kk); the matrix being
-// symmetric that is the A operand of the product whose output rows are the tile's columns and whose contraction runs over its rows:
+// I = 0 .. T-1 (tokens m).  Tile (I, J) is sv_gram_tile's product (gram_tile_dev.h) with the tok_order entries of the positions as
+// rows: rows m on the A side, columns n on the B side, the cosine = the raw dot product times the two 1 / ||x||.  In the C/D layout
+// lane (i, kk) holds column i and the 16 rows sv_frag_row(r, kk); the matrix being symmetric that is the A operand of the product whose
+// output rows are the tile's columns and whose contraction runs over its rows:
 //   A[i][kk] = sigmoid tile[row(r, kk)][column i] = acc[r],      B[kk][j] = bit j of the column mask of the token in row(r, kk)
 // so the accumulators feed the second product with no trip through LDS, and neither the Gram matrix nor its sigmoid reaches memory.
 // A wave contracts over its own 64 rows of every tile; the two waves of a column half add their sums at the end, wr = 0 first: one
@@ -46,23 +35,17 @@ __global__ __launch_bounds__(256, 2) void burst_seg_gram_kernel(const float* __r
                                                              const int32_t* __restrict__ tok_order, const uint64_t* __restrict__ colmask,
                                                              const int32_t* __restrict__ seg_off, int B, int N, int D, int T, int SC,
                                                              int by_xcd, float a, float bb, float p, float* __restrict__ U) {
-  __shared__ __attribute__((aligned(16))) float sAB[2 * BS_TILE * BS_LD];   // the two operand chunks; at the end the image of g
-  __shared__ uint64_t smask[BS_TILE];
-  __shared__ float srn[BS_TILE];
+  __shared__ __attribute__((aligned(16))) float sAB[2 * SV_GRAM_TILE * SV_GRAM_LD];   // the two operand chunks; at the end the image of g
+  __shared__ uint64_t smask[SV_GRAM_TILE];
+  __shared__ float srn[SV_GRAM_TILE];
   float* sA = sAB;
-  float* sB = sAB + BS_TILE * BS_LD;
-  const int per = T * SC;
+  float* sB = sAB + SV_GRAM_TILE * SV_GRAM_LD;
   int img, t;
-  if (by_xcd) {   // workgroups are dealt to the 8 XCDs by their linear id: the tiles of one image share an XCD's L2
-    const int slot = (int)blockIdx.x >> 3;
-    img = (slot / per) * 8 + ((int)blockIdx.x & 7), t = slot % per;
-  } else {
-    img = (int)blockIdx.x / per, t = (int)blockIdx.x % per;
-  }
+  sv_gram_deal(by_xcd, T * SC, img, t);
   if (img >= B) return;
   const int chunk = t / T, J = t % T;
   if (64 * chunk >= seg_off[img + 1] - seg_off[img]) return;   // no segment of the image in this chunk: nothing reads its columns
-  const int n0 = J * BS_TILE;
+  const int n0 = J * SV_GRAM_TILE;
 
   const int tid = threadIdx.x, w = tid >> 6, l = tid & 63, i = l & 31, kk = l >> 5;
   const int wr = w >> 1, wc = w & 1;
@@ -70,7 +53,7 @@ __global__ __launch_bounds__(256, 2) void burst_seg_gram_kernel(const float* __r
   const int32_t* ord = tok_order + (size_t)img * N;
   const float* rns = rn_sorted + (size_t)img * N;
   const uint64_t* cm = colmask + (size_t)img * N * SC + chunk;
-  const int lc = 4 * (tid & 7), lr = tid >> 3;   // this thread's float4 column of a chunk and its first row (then + 32, 64, 96)
+  const int lr = tid >> 3;   // this thread's first row of a tile's operand chunk (then + 32, 64, 96)
 
   int tb[4];   // the token rows of Xt behind this thread's four columns n (-1: beyond N)
 #pragma unroll
@@ -90,8 +73,8 @@ __global__ __launch_bounds__(256, 2) void burst_seg_gram_kernel(const float* __r
       for (int r = 0; r < 16; ++r) gacc[tj][sj][r] = 0.f;
 
   for (int I = 0; I < T; ++I) {
-    const int m0 = I * BS_TILE;
-    if (tid < BS_TILE) {
+    const int m0 = I * SV_GRAM_TILE;
+    if (tid < SV_GRAM_TILE) {
       const bool ok = m0 + tid < N;
       smask[tid] = ok ? cm[(size_t)(m0 + tid) * SC] : 0ull;
       srn[tid] = ok ? rns[m0 + tid] : 0.f;
@@ -99,56 +82,15 @@ __global__ __launch_bounds__(256, 2) void burst_seg_gram_kernel(const float* __r
     int ta[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) ta[j] = m0 + lr + 32 * j < N ? ord[m0 + lr + 32 * j] : -1;
-    float4 pa[4], pb[4];
-    auto fetch = [&](int d0) {
-      const bool dok = d0 + lc < D;   // (D % 4 == 0: a float4 is inside or outside as a whole)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        pa[j] = (dok && ta[j] >= 0) ? *reinterpret_cast<const float4*>(Xb + (size_t)ta[j] * D + d0 + lc) : make_float4(0.f, 0.f, 0.f, 0.f);
-        pb[j] = (dok && tb[j] >= 0) ? *reinterpret_cast<const float4*>(Xb + (size_t)tb[j] * D + d0 + lc) : make_float4(0.f, 0.f, 0.f, 0.f);
-      }
-    };
     f32x16 acc[2][2];
-#pragma unroll
-    for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-      for (int tj = 0; tj < 2; ++tj)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[ti][tj][r] = 0.f;
-
-    fetch(0);
-    for (int d0 = 0; d0 < D; d0 += BS_KC) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        *reinterpret_cast<float4*>(sA + (lr + 32 * j) * BS_LD + lc) = pa[j];
-        *reinterpret_cast<float4*>(sB + (lr + 32 * j) * BS_LD + lc) = pb[j];
-      }
-      __syncthreads();
-      if (d0 + BS_KC < D) fetch(d0 + BS_KC);   // the next chunk's loads are in flight under this chunk's MFMAs
-#pragma unroll
-      for (int q = 0; q < BS_KC / 8; ++q) {
-        const int dc = 8 * q + 4 * kk;
-        const float4 a0 = *reinterpret_cast<const float4*>(sA + (64 * wr + i) * BS_LD + dc);
-        const float4 a1 = *reinterpret_cast<const float4*>(sA + (64 * wr + 32 + i) * BS_LD + dc);
-        const float4 b0 = *reinterpret_cast<const float4*>(sB + (64 * wc + i) * BS_LD + dc);
-        const float4 b1 = *reinterpret_cast<const float4*>(sB + (64 * wc + 32 + i) * BS_LD + dc);
-#define BS_STEP(c)                                  \
-  acc[0][0] = MFMA32(a0.c, b0.c, acc[0][0]);        \
-  acc[0][1] = MFMA32(a0.c, b1.c, acc[0][1]);        \
-  acc[1][0] = MFMA32(a1.c, b0.c, acc[1][0]);        \
-  acc[1][1] = MFMA32(a1.c, b1.c, acc[1][1]);
-        BS_STEP(x) BS_STEP(y) BS_STEP(z) BS_STEP(w)
-#undef BS_STEP
-      }
-      __syncthreads();
-    }
+    sv_gram_tile(Xb, ta, tb, D, sA, sB, acc);
 
     // ---- the tile's sigmoid, register by register, straight into the mask product: rows (m) are the contraction ----
 #pragma unroll
     for (int ti = 0; ti < 2; ++ti) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int row = 64 * wr + 32 * ti + bs_frag_row(r, kk);
+        const int row = 64 * wr + 32 * ti + sv_frag_row(r, kk);
         const float rn_row = srn[row];
         const uint64_t mk = smask[row];   // 0 beyond N: such a row adds an exact 0 (its sigmoid is finite)
         const float m_lo = ((mk >> i) & 1ull) ? 1.f : 0.f, m_hi = ((mk >> (32 + i)) & 1ull) ? 1.f : 0.f;
@@ -176,42 +118,40 @@ __global__ __launch_bounds__(256, 2) void burst_seg_gram_kernel(const float* __r
         for (int sj = 0; sj < 2; ++sj)
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
-            float* dst = sg + (64 * wc + 32 * tj + bs_frag_row(r, kk)) * BS_GLD + 32 * sj + i;
+            float* dst = sg + (64 * wc + 32 * tj + sv_frag_row(r, kk)) * BS_GLD + 32 * sj + i;
             *dst = pass ? gacc[tj][sj][r] : gacc[tj][sj][r] + *dst;
           }
     }
     __syncthreads();
   }
   const int ldu = 64 * SC;
-  for (int idx = tid; idx < BS_TILE * 64; idx += 256) {
+  for (int idx = tid; idx < SV_GRAM_TILE * 64; idx += 256) {
     const int c = idx >> 6, s = idx & 63, n = n0 + c;
     if (n >= N) break;   // (c grows with idx)
     const float g = sg[c * BS_GLD + s];
     const bool bit = (cm[(size_t)n * SC] >> s) & 1ull;
-    U[((size_t)img * N + n) * ldu + 64 * chunk + s] = !bit ? 0.f : p == 0.f ? 1.0f : p == 1.f ? 1.0f / g : powf(g, -p);
+    U[((size_t)img * N + n) * ldu + 64 * chunk + s] = bit ? sv_burst_discount(g, p) : 0.f;
   }
 }
 
 int sv_launch_burst_seg_gram(segvlad_ctx* ctx, const float* xt, const uint64_t* colmask, const int32_t* seg_off_dev, int B, int N, int D,
                              int SC, float a, float b, float p, float* u) {
-  const int T = (N + BS_TILE - 1) / BS_TILE;
-  // a batch of >= 8 images: image b on XCD b % 8; fewer: the tiles spread over every XCD (sv_launch_burst_gram's dealing)
-  const int by_xcd = B >= 8 ? 1 : 0;
-  const long long per = (long long)T * SC, nwg = by_xcd ? 8ll * ((B + 7) / 8) * per : (long long)B * per;
+  const int T = sv_burst_tiles(N);
+  const long long nwg = sv_gram_grid(B, (long long)T * SC);
   if (nwg > 0x7fffffffll) return ctx->fail(SEGVLAD_ERR_LIMIT, "burst (segment scope): B=%d N=%d SC=%d give %lld workgroups", B, N, SC, nwg);
   hipLaunchKernelGGL(burst_seg_gram_kernel, dim3((unsigned)nwg), dim3(256), 0, ctx->stream, xt, ctx->s_rnsorted.as<float>(),
-                     ctx->s_tokorder.as<int32_t>(), colmask, seg_off_dev, B, N, D, T, SC, by_xcd, a, b, p, u);
+                     ctx->s_tokorder.as<int32_t>(), colmask, seg_off_dev, B, N, D, T, SC, sv_gram_by_xcd(B), a, b, p, u);
   SV_HIP(hipGetLastError());
   return SEGVLAD_OK;
 }
 
 // ------------------------------------------------------------------------------------------------
-// aggregate: workgroup = (kpb consecutive clusters, image b, 32 segments of it); wave w owns d in [128 w, 128 w + 128) --
-// soft_aggregate_kernel's geometry, outputs and norm reduction.  Per cluster k the MFMA product
+// aggregate: the frame of weighted_agg_dev.h (workgroup = (kpb consecutive clusters, image b, 32 segments of it); wave w owns d in
+// [128 w, 128 w + 128)).  Per cluster k the MFMA product
 //   (32 segments x 2 tokens) . (2 tokens x 32 d):  A[i][kk] = bit i of the position's half column mask ? u[position][segment i] : 0
 //                                                  B[kk][j] = w[t_kk][k] * fma(Xt[t_kk][d], 1/||x||, -C[k][d])
 // HARD: the list is every position of the image and cluster k walks [lab_off[k], lab_off[k + 1]) with w = 1 -- the hard aggregation's
-// walk, so its matrix work.  Otherwise the list is the positions one of the 32 segments covers (ordered compaction of the column masks)
+// walk, so its matrix work.  Otherwise the list is the positions one of the 32 segments covers (sv_agg_covered_list)
 // and every cluster walks all of it with W's column k.  The token rows and the rows of u are plain loads, one group of BS_G token pairs
 // ahead of the MFMAs that use them.
 // ------------------------------------------------------------------------------------------------
@@ -228,16 +168,12 @@ __global__ __launch_bounds__(768) void burst_seg_aggregate_kernel(const float* _
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int b = blockIdx.y;
   const int tid = threadIdx.x, w = tid >> 6, l = tid & 63, i = l & 31, kk = l >> 5;
-  const int nwaves = blockDim.x >> 6;
-  const int PW = nwaves * 2 + 1;
-  uint32_t* mskl = reinterpret_cast<uint32_t*>(smem);         // [Ncap]   (Ncap % 4 == 0, > N)
-  int* tokl = reinterpret_cast<int*>(mskl + Ncap);            // [Ncap]
-  float* rnl = reinterpret_cast<float*>(tokl + Ncap);         // [Ncap]
-  float* wl = rnl + Ncap;                                     // [Ncap]   (!HARD)
-  int* posl = reinterpret_cast<int*>(wl + Ncap);              // [Ncap]   (!HARD: the position behind a list entry)
-  float* part = reinterpret_cast<float*>(posl + Ncap);        // [32][PW]
-  float* alpha = part + 32 * PW;                              // [32]
-  int* wcount = reinterpret_cast<int*>(alpha + 32);           // [16]
+  const SvAggLds<unsigned char*> L(smem, Ncap, blockDim.x >> 6, true, 0);
+  uint32_t* mskl = reinterpret_cast<uint32_t*>(L.mskl);
+  int* tokl = reinterpret_cast<int*>(L.tokl);
+  float* rnl = reinterpret_cast<float*>(L.rnl);
+  float* wl = reinterpret_cast<float*>(L.wl);       // (!HARD)
+  int* posl = reinterpret_cast<int*>(L.posl);       // (!HARD: the position behind a list entry)
 
   const int s0 = seg_off[b], S = seg_off[b + 1] - s0;
   const int r0 = 32 * (int)blockIdx.z;   // first segment of this workgroup inside the image
@@ -249,7 +185,6 @@ __global__ __launch_bounds__(768) void burst_seg_aggregate_kernel(const float* _
   const float* Xb = Xt + (size_t)b * N * D + dcol;
   const int ldu = 64 * SC;
   const float* Ub = U + (size_t)b * N * ldu + r0 + i;   // this lane's segment column of u
-  const size_t KD = (size_t)K * D;
   const int k_begin = (int)blockIdx.x * kpb, k_end = min(K, k_begin + kpb);
 
   // ---- the list: entry n is the zero entry every out-of-range step reads ----
@@ -262,36 +197,11 @@ __global__ __launch_bounds__(768) void burst_seg_aggregate_kernel(const float* _
     }
     n = N;
   } else {
-    for (int base = 0; base < N; base += (int)blockDim.x) {
-      const int j = base + tid;
-      uint32_t m = 0;
-      if (j < N) m = (uint32_t)(colmask[((size_t)b * N + j) * SC + sc] >> (32 * half));
-      const uint64_t bal = __builtin_amdgcn_ballot_w64(m != 0);
-      if (l == 0) wcount[w] = __popcll(bal);
-      __syncthreads();
-      int off = n, tot = 0;
-      for (int ww = 0; ww < nwaves; ++ww) {
-        const int c = wcount[ww];
-        if (ww < w) off += c;
-        tot += c;
-      }
-      if (m != 0) {
-        const int pos = off + __popcll(bal & ((1ull << l) - 1ull));
-        mskl[pos] = m;
-        tokl[pos] = tok_order[(size_t)b * N + j];
-        rnl[pos] = rn_sorted[(size_t)b * N + j];
-        posl[pos] = j;
-      }
-      n += tot;
-      __syncthreads();
-    }
+    n = sv_agg_covered_list<true>(colmask, tok_order, rn_sorted, b, N, SC, sc, half, mskl, tokl, rnl, posl, reinterpret_cast<int*>(L.wcount));
   }
   if (tid == 0) {
-    mskl[n] = 0;
-    tokl[n] = 0;
-    rnl[n] = 0.f;
+    sv_agg_zero_entry<true>(n, mskl, tokl, rnl, posl);
     wl[n] = 0.f;
-    posl[n] = 0;
   }
   __syncthreads();
 
@@ -345,69 +255,26 @@ __global__ __launch_bounds__(768) void burst_seg_aggregate_kernel(const float* _
 #pragma unroll
       for (int g = 0; g < BS_G; ++g) x[g] = xn[g], rn[g] = rnn[g], wt[g] = wtn[g], av[g] = avn[g];
     }
-    // ---- block norms: quad reduce in registers, then across lanes / waves through LDS (soft_aggregate_kernel's order) ----
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      float q = acc[0][r] * acc[0][r];
-      q = fmaf(acc[1][r], acc[1][r], q);
-      q = fmaf(acc[2][r], acc[2][r], q);
-      q = fmaf(acc[3][r], acc[3][r], q);
-      q += bs_dpp_f32<0xB1>(q);    // quad_perm [1,0,3,2]
-      q += bs_dpp_f32<0x4E>(q);    // quad_perm [2,3,0,1]
-      q += bs_dpp_f32<0x141>(q);   // row_half_mirror
-      q += bs_dpp_f32<0x140>(q);   // row_mirror
-      if ((l & 15) == 0) part[bs_frag_row(r, kk) * PW + w * 2 + ((l >> 4) & 1)] = q;
-    }
-    __syncthreads();
-    if (tid < Sc) {
-      float sum = 0.f;
-      const int cnt = nwaves * 2;
-      for (int c = 0; c < cnt; ++c) sum += part[tid * PW + c];
-      const float nrm = nscale * sqrtf(sum);   // nscale: 1, or K where the accumulators hold V / K (soft_pooled)
-      alpha[tid] = nscale / fmaxf(nrm, 1e-12f);   // intra-normalisation; the row's own scale follows in soft_finalize_kernel
-      block_norms[(size_t)(s0 + r0 + tid) * K + k] = nrm;
-    }
-    __syncthreads();
-    if (dvalid) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int row = bs_frag_row(r, kk);
-        if (row < Sc) {
-          const float al = alpha[row];
-          const float4 v = make_float4(acc[0][r] * al, acc[1][r] * al, acc[2][r] * al, acc[3][r] * al);
-          *reinterpret_cast<float4*>(out + (size_t)(s0 + r0 + row) * KD + (size_t)k * D + dcol) = v;
-        }
-      }
-    }
-    __syncthreads();
+    sv_agg_block_epilogue(acc, reinterpret_cast<float*>(L.part), reinterpret_cast<float*>(L.alpha), Sc, nscale, s0 + r0, k, K, D, dcol, dvalid, out,
+                          block_norms);
   }
 }
 
 int sv_launch_burst_seg_aggregate(segvlad_ctx* ctx, const float* xt, const float* w, const float* u, const uint64_t* colmask,
                                   const float* centres, int K, int D, const int32_t* seg_off_dev, int B, int N, int SC, float* out,
                                   float* block_norms, const float* mean_centre) {
-  const int nwaves = (D + 127) / 128;
-  if (nwaves > 12) return ctx->fail(SEGVLAD_ERR_LIMIT, "burst aggregate: D=%d exceeds the 1536-wide workgroup of this build", D);
-  const int Ncap = (N + 4) & ~3;
-  const int PW = nwaves * 2 + 1;
-  const size_t lds = (size_t)Ncap * 20 + (size_t)(32 * PW + 32) * sizeof(float) + 16 * sizeof(int);
-  if (lds > 160 * 1024) return ctx->fail(SEGVLAD_ERR_LIMIT, "burst aggregate: N=%d tokens need %zu B of LDS (limit 160 KiB)", N, lds);
   const void* fn = w ? reinterpret_cast<const void*>(burst_seg_aggregate_kernel<false>) : reinterpret_cast<const void*>(burst_seg_aggregate_kernel<true>);
-  if (lds > 64 * 1024) SV_HIP(sv_max_dyn_lds(fn, lds));
-  int kpb = ctx->opt.agg_kpb;   // clusters per workgroup
-  if (kpb < 1) kpb = 1;
-  const dim3 grid((K + kpb - 1) / kpb, B, 2 * SC), block(nwaves * 64);
-  const float* cen = mean_centre ? mean_centre : centres;
-  const int cstride = mean_centre ? 0 : D;
-  const float nscale = mean_centre ? (float)K : 1.0f;
+  SvAggLaunch g;
+  const int rc = sv_agg_launch_geometry(ctx, "burst aggregate", fn, true, 0, K, D, B, N, SC, centres, mean_centre, &g);
+  if (rc != SEGVLAD_OK) return rc;
   if (w)
-    hipLaunchKernelGGL(burst_seg_aggregate_kernel<false>, grid, block, lds, ctx->stream, xt, w, u, ctx->s_rnsorted.as<float>(),
-                       ctx->s_tokorder.as<int32_t>(), ctx->s_laboff.as<int32_t>(), colmask, cen, seg_off_dev, N, D, K, SC, Ncap, out,
-                       block_norms, kpb, cstride, nscale);
+    hipLaunchKernelGGL(burst_seg_aggregate_kernel<false>, g.grid, g.block, g.lds, ctx->stream, xt, w, u, ctx->s_rnsorted.as<float>(),
+                       ctx->s_tokorder.as<int32_t>(), ctx->s_laboff.as<int32_t>(), colmask, g.centres, seg_off_dev, N, D, K, SC, g.Ncap, out,
+                       block_norms, g.kpb, g.cstride, g.nscale);
   else
-    hipLaunchKernelGGL(burst_seg_aggregate_kernel<true>, grid, block, lds, ctx->stream, xt, w, u, ctx->s_rnsorted.as<float>(),
-                       ctx->s_tokorder.as<int32_t>(), ctx->s_laboff.as<int32_t>(), colmask, cen, seg_off_dev, N, D, K, SC, Ncap, out,
-                       block_norms, kpb, cstride, nscale);
+    hipLaunchKernelGGL(burst_seg_aggregate_kernel<true>, g.grid, g.block, g.lds, ctx->stream, xt, w, u, ctx->s_rnsorted.as<float>(),
+                       ctx->s_tokorder.as<int32_t>(), ctx->s_laboff.as<int32_t>(), colmask, g.centres, seg_off_dev, N, D, K, SC, g.Ncap, out,
+                       block_norms, g.kpb, g.cstride, g.nscale);
   SV_HIP(hipGetLastError());
   return SEGVLAD_OK;
 }

@@ -500,8 +500,9 @@ int sv_launch_aggregate(segvlad_ctx* ctx, const float* xt, const float* rnorm, c
                         const float* mean = nullptr, float xscale = 0.f, uint16_t* h1 = nullptr, uint16_t* h2 = nullptr);
 
 // soft_vlad_kernels.hip (option vlad_assign=soft:<T>; after sv_launch_prep, whose label-grouped token order, 1/||x|| and column masks
-// they read).  weights: w[b][n][0..K) = softmax_k(temp * <x^_n, c^_k>) from the channel-major tokens.  aggregate: the intra-normalised
-// blocks V[s][k] / max(||V[s][k]||, 1e-12) into out [S][K*D] and ||V[s][k]|| into block_norms [S][K] (never null); with mean_centre
+// they read).  weights: w[b][n][0..K) = softmax_k(temp * <x^_n, c^_k>) from the channel-major tokens.  aggregate (the frame of
+// weighted_agg_dev.h, which sv_launch_burst_seg_aggregate shares: LDS layout, covered-position list, epilogue, launch geometry): the
+// intra-normalised blocks V[s][k] / max(||V[s][k]||, 1e-12) into out [S][K*D] and ||V[s][k]|| into block_norms [S][K] (never null); with mean_centre
 // (soft_pooled: [D] from sv_launch_soft_centre_mean) every block is K sum w (x^ - mean centre), the residuals against all K centres.
 // finalize: every row of out scaled to unit length from its block norms.
 int sv_launch_soft_weights(segvlad_ctx* ctx, const float* tokens, int B, int N, float temp, float* w);
@@ -511,7 +512,8 @@ int sv_launch_soft_aggregate(segvlad_ctx* ctx, const float* xt, const float* w, 
                              const float* mean_centre = nullptr);
 int sv_launch_soft_finalize(segvlad_ctx* ctx, const float* block_norms, int S_tot, int K, int D, float* out);
 
-// burst_kernels.hip (option vlad_burst=<a>:<b>:<p>; after sv_launch_assign, whose token-major copy and 1 / ||x|| they read).
+// burst_kernels.hip (option vlad_burst=<a>:<b>:<p>; after sv_launch_assign, whose token-major copy and 1 / ||x|| they read).  The
+// 128 x 128 self-similarity tile, the dealing of workgroups to images and u = g^-p are gram_tile_dev.h's, one definition for both scopes.
 // gram: part [B][sv_burst_tiles(N)][N], the sums of sigmoid(a (2 cos(x_n, x_m) - 2) + b) over the m of one 128-token tile, every slot
 // written once.  finish: g[n] = the tile sums in tile order, u = g^-p (exactly 1 for p = 0), and w [B][N][K]: one_hot -- u[n] at
 // k = labels[n], 0 elsewhere; otherwise the rows of w (sv_launch_soft_weights) scaled by u[n].
@@ -522,8 +524,8 @@ int sv_launch_burst_finish(segvlad_ctx* ctx, const float* part, const uint8_t* l
 // burst_seg_kernels.hip (vlad_burst with vlad_burst_scope=segment; after sv_launch_prep, whose label-grouped order, sorted 1 / ||x|| and
 // column masks they read).  gram: u [B][N][64 SC], row = POSITION in the label-grouped order, column s = g[s][n]^-p where bit s of the
 // position's column mask is set and 0 elsewhere, g[s][n] = sum_{m in U(s)} sigmoid(a (2 cos(x_n, x_m) - 2) + b); the chunks of 64
-// columns beyond an image's segments are left unwritten.  aggregate: sv_launch_soft_aggregate's outputs with the A operand
-// bit ? u : 0; w == nullptr is hard assignment (cluster k walks label k's positions with weight 1), else w [B][N][K] of
+// columns beyond an image's segments are left unwritten.  aggregate: the frame of weighted_agg_dev.h -- the intra-normalised blocks
+// into out [S][K*D], ||V[s][k]|| into block_norms [S][K], mean_centre as above -- with the A operand bit ? u : 0; w == nullptr is hard assignment (cluster k walks label k's positions with weight 1), else w [B][N][K] of
 // sv_launch_soft_weights over every covered position.  sv_launch_soft_finalize follows as behind the soft aggregation.
 int sv_launch_burst_seg_gram(segvlad_ctx* ctx, const float* xt, const uint64_t* colmask, const int32_t* seg_off_dev, int B, int N, int D,
                              int SC, float a, float b, float p, float* u);

@@ -112,6 +112,24 @@ struct DescribePlan {
   bool upload_offsets = false;   // this call puts the segment / adjacency offsets on the device (else: the mask branch of its begin did)
 };
 
+// The project form gives every token the slice of ONE cluster, unweighted: auto takes the planes form under soft assignment or the burst
+// discount, an explicit pca_path=project is refused (SEGVLAD_ERR_LIMIT).  True, with the message under the caller's name in `why`, when
+// the options ask for that.
+static bool refuses_project(const segvlad_ctx* ctx, const char* who, char* why, size_t n) {
+  if (ctx->opt.pca_path != 2) return false;
+  if (ctx->opt.vlad_soft_temp > 0.f)
+    snprintf(why, n, "%s: pca_path=project presupposes one cluster per token, vlad_assign=%s:%g has none "
+                     "(set pca_path to auto or planes, or vlad_assign to hard)",
+             who, ctx->opt.vlad_soft_pooled ? "soft_pooled" : "soft", (double)ctx->opt.vlad_soft_temp);
+  else if (ctx->opt.vlad_burst)
+    snprintf(why, n, "%s: pca_path=project presupposes unweighted tokens, vlad_burst=%g:%g:%g weights them "
+                     "(set pca_path to auto or planes, or vlad_burst to off)",
+             who, (double)ctx->opt.burst_a, (double)ctx->opt.burst_b, (double)ctx->opt.burst_p);
+  else
+    return false;
+  return true;
+}
+
 // Every check and every decision of a call, before anything is enqueued: arithmetic on the arguments, the options and the context's scalars.
 static DescribePlan plan_describe(const segvlad_ctx* ctx, const DescribeIO& io, bool pca, Passes passes) {
   DescribePlan p;
@@ -126,15 +144,7 @@ static DescribePlan plan_describe(const segvlad_ctx* ctx, const DescribeIO& io, 
     if (B > 0 && io.seg_offsets && !sv_is_device_ptr(io.seg_offsets) && io.seg_offsets[B] > 0 && !io.y)
       return PLAN_REFUSE(SEGVLAD_ERR_ARG, "images_pca: null y");
     if (!x3 && passes != Passes::All) return PLAN_REFUSE(SEGVLAD_ERR_STATE, "describe: the split call needs the fp16x3 projection (pca_arith)");
-    // the project form gives every token the slice of ONE cluster: auto takes the planes form under soft, an explicit choice is refused
-    if (ctx->opt.vlad_soft_temp > 0.f && ctx->opt.pca_path == 2)
-      return PLAN_REFUSE(SEGVLAD_ERR_LIMIT, "images_pca: pca_path=project presupposes one cluster per token, vlad_assign=%s:%g has none "
-                                            "(set pca_path to auto or planes, or vlad_assign to hard)",
-                         ctx->opt.vlad_soft_pooled ? "soft_pooled" : "soft", (double)ctx->opt.vlad_soft_temp);
-    if (ctx->opt.vlad_burst && ctx->opt.pca_path == 2)   // ... and unweighted tokens
-      return PLAN_REFUSE(SEGVLAD_ERR_LIMIT, "images_pca: pca_path=project presupposes unweighted tokens, vlad_burst=%g:%g:%g weights them "
-                                            "(set pca_path to auto or planes, or vlad_burst to off)",
-                         (double)ctx->opt.burst_a, (double)ctx->opt.burst_b, (double)ctx->opt.burst_p);
+    if (refuses_project(ctx, "images_pca", p.why, sizeof(p.why))) return (p.code = SEGVLAD_ERR_LIMIT, p);
   }
   if (K == 0) return PLAN_REFUSE(SEGVLAD_ERR_STATE, "images: call segvlad_set_vocab first");
   p.passes = passes, p.B = B, p.N = N, p.K = K, p.D = D, p.P = ctx->P, p.nw = (N + 63) / 64, p.l2norm = io.l2norm;
@@ -464,14 +474,9 @@ static int describe_begin(segvlad_ctx* ctx, const MaskBranch& m, const float* to
   // Configurations the split call does not take are reported as SEGVLAD_ERR_LIMIT -- the code of "this entry point cannot, the separate
   // ones (incidence_centroids -> adjacency -> images[_pca]) can", which a caller can tell from misuse: an empty batch, and a
   // PCA model without the fp16x3 form (option pca_arith=fp32, or K*D not a multiple of 32: images_pca takes its PlainProjection form)
-  if (pca && ctx->opt.vlad_soft_temp > 0.f && ctx->opt.pca_path == 2)   // (plan_describe's refusal, before the mask branch is forked)
-    return ctx->fail(SEGVLAD_ERR_LIMIT, "describe: pca_path=project presupposes one cluster per token, vlad_assign=%s:%g has none "
-                                        "(set pca_path to auto or planes, or vlad_assign to hard)",
-                     ctx->opt.vlad_soft_pooled ? "soft_pooled" : "soft", (double)ctx->opt.vlad_soft_temp);
-  if (pca && ctx->opt.vlad_burst && ctx->opt.pca_path == 2)
-    return ctx->fail(SEGVLAD_ERR_LIMIT, "describe: pca_path=project presupposes unweighted tokens, vlad_burst=%g:%g:%g weights them "
-                                        "(set pca_path to auto or planes, or vlad_burst to off)",
-                     (double)ctx->opt.burst_a, (double)ctx->opt.burst_b, (double)ctx->opt.burst_p);
+  char why[256];
+  if (pca && refuses_project(ctx, "describe", why, sizeof(why)))   // (plan_describe's refusal, before the mask branch is forked)
+    return ctx->fail(SEGVLAD_ERR_LIMIT, "%s", why);
   if (B == 0 || S_tot <= 0) return ctx->fail(SEGVLAD_ERR_LIMIT, "describe: no images / no segments (use the separate entry points)");
   // ... and an image that sv_launch_adjacency would refuse: the same bound, asked before the mask branch is forked
   const SegWalk w = walk_seg_offsets(m.seg_offsets, B);

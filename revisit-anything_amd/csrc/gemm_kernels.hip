@@ -14,9 +14,7 @@
 #include <algorithm>
 
 #include "ctx.h"
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-#define MFMA32(a, b, c) __builtin_amdgcn_mfma_f32_32x32x2f32((a), (b), (c), 0, 0, 0)
+#include "mfma_f32_dev.h"
 
 constexpr int BM = 128, BN = 128, BK = 32, LDT = 129;  // LDT = 1 (mod 32): conflict-free k-major stores
 

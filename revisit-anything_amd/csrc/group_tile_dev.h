@@ -27,12 +27,7 @@
 
 #include <hip/hip_runtime.h>
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
-// row of accumulator register r of a 32 x 32 MFMA tile, in the lane half kk (the column is the lane & 31)
-__device__ __forceinline__ int sv_frag_row(int r, int kk) { return (r & 3) + 8 * (r >> 2) + 4 * kk; }
+#include "mfma_f32_dev.h"   // f32x16, f32x4, f32x2, sv_frag_row
 
 constexpr int SV_GT_KS = 32;   // floats of a row piece = k of a super-tile
 

@@ -19,9 +19,7 @@
 //   project_consts_kernel      W mu ([P])                                         (once per PCA model)
 //   project_aggregate_kernel   the weighted sums above on fp32 MFMA (exact fp32 chains), mean term and whitening scale fused
 #include "ctx.h"
-#include "group_tile_dev.h"   // f32x16, sv_frag_row
-
-#define MFMA32(a, b, c) __builtin_amdgcn_mfma_f32_32x32x2f32((a), (b), (c), 0, 0, 0)
+#include "mfma_f32_dev.h"
 
 // ---- grouping plan ---------------------------------------------------------------------------------------------------
 // One workgroup.  Cluster k's tokens of all images occupy rows [base_k, base_k + M_k) of the grouped planes, base_k a

@@ -3,7 +3,7 @@
 //   soft_centre_mean_kernel soft_pooled alone: the mean centre that stands in for every c_k below
 //   soft_weights_kernel     tokens [D][N] -> w[n][0..K) = softmax_k(T <x^_n, c^_k>), max-subtracted, over the K real centres
 //   soft_aggregate_kernel   per (image, cluster): V[s][k] = sum_{n in U(s)} w[n][k] (x^_n - c_k) on the fp32 MFMA, ||V[s][k]||,
-//                           the intra-normalised block stored packed
+//                           the intra-normalised block stored packed: the frame of weighted_agg_dev.h around a DMA-queue loop
 //   soft_finalize_kernel    per segment: the row scaled to unit length from its K block norms
 //
 // V is accumulated as sum w (x^ - c), which is sum w x^ - (sum w) c of segvlad.h term for term regrouped: the token's residual is
@@ -11,17 +11,7 @@
 // weighted residuals exists one (token pair, cluster, 128-column slice) at a time in the B operand's registers, never in memory.
 // Every sum runs in the order of prep_kernel's label-grouped token positions of ONE image: fixed, and independent of the batch.
 #include "ctx.h"
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-#define MFMA32(a, b, c) __builtin_amdgcn_mfma_f32_32x32x2f32((a), (b), (c), 0, 0, 0)
-
-template <int CTRL>
-__device__ __forceinline__ float dpp_f32(float x) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), CTRL, 0xf, 0xf, true));
-}
-// row of D-fragment register r for lane half kk (v_mfma_f32_32x32x2_f32 C/D layout)
-__device__ __forceinline__ int frag_row(int r, int kk) { return (r & 3) + 8 * (r >> 2) + 4 * kk; }
+#include "weighted_agg_dev.h"
 
 // ------------------------------------------------------------------------------------------------
 // weights: workgroup = (image, 64-token tile), wave w owns tokens 32 w .. 32 w + 31 for ALL d: one sequential fp32 chain per score,
@@ -61,7 +51,7 @@ __global__ __launch_bounds__(128) void soft_weights_kernel(const float* __restri
 #pragma unroll
   for (int n = 0; n < NT; ++n)
 #pragma unroll
-    for (int r = 0; r < 16; ++r) sc[(32 * w + frag_row(r, kk)) * (KP + 1) + n * 32 + i] = acc[n][r];
+    for (int r = 0; r < 16; ++r) sc[(32 * w + sv_frag_row(r, kk)) * (KP + 1) + n * 32 + i] = acc[n][r];
   __syncthreads();
   if (tid < 64) {
     const float rn = 1.0f / fmaxf(sqrtf(ssum[tid]), 1e-12f);
@@ -118,30 +108,21 @@ int sv_launch_soft_centre_mean(segvlad_ctx* ctx, const float* centres, int K, in
 }
 
 // ------------------------------------------------------------------------------------------------
-// aggregate: workgroup = (kpb consecutive clusters, image b, 32 segments of it); wave w owns d in [128 w, 128 w + 128) --
-// aggregate_kernel's geometry with one M-tile (16 accumulator quads less: no spill inside the counted-wait loop).
-// The workgroup first lists the positions some segment of its 32 covers (ordered compaction of the column masks: a token none of
-// them covers is never read), then per cluster k runs the MFMA product
+// aggregate: the frame of weighted_agg_dev.h (workgroup = (kpb consecutive clusters, image b, 32 segments of it); one M-tile, 16
+// accumulator quads less than aggregate_kernel: no spill inside the counted-wait loop).  The workgroup first lists the positions some
+// segment of its 32 covers (a token none of them covers is never read), then per cluster k runs the MFMA product
 //   (32 segments x 2 tokens) . (2 tokens x 32 d):  A[i][kk] = bit i of the token's half column mask (0/1 exact),
 //                                                  B[kk][j] = w[t_kk][k] * fma(Xt[t_kk][d], 1/||x||, -C[k][d])
 // with the token rows streaming through a wave-private queue of global->LDS DMAs.
 // ------------------------------------------------------------------------------------------------
-typedef const __attribute__((address_space(1))) void* soft_gptr_t;
-typedef __attribute__((address_space(3))) void* soft_lptr_t;
-__device__ __forceinline__ unsigned soft_lds_addr(const void* p) { return (unsigned)(size_t)(soft_lptr_t)p; }
-// Raw LDS reads: before an LDS load the compiler emits itself it waits for every outstanding DMA; these are invisible to that pass,
-// the counted s_waitcnt in the loop is the only wait (see aggregate_kernel).
+// one step's operands, a raw LDS read (mfma_f32_dev.h: the counted s_waitcnt in the loop is the only wait): the queue slot (16 B),
+// 1 / ||x||, the weight and the half column mask of the lane's token
 __device__ __forceinline__ void soft_step_read(unsigned a_slot, unsigned a_rn, unsigned a_w, unsigned a_m, f32x4& x, float& rn, float& wt,
                                                uint32_t& m) {
   asm volatile("ds_read_b128 %0, %4\n\tds_read_b32 %1, %5\n\tds_read_b32 %2, %6\n\tds_read_b32 %3, %7\n\ts_waitcnt lgkmcnt(0)"
                : "=&v"(x), "=&v"(rn), "=&v"(wt), "=&v"(m)
                : "v"(a_slot), "v"(a_rn), "v"(a_w), "v"(a_m)
                : "memory");
-}
-__device__ __forceinline__ int soft_lds_read_i32(unsigned a) {
-  int v;
-  asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=&v"(v) : "v"(a) : "memory");
-  return v;
 }
 
 constexpr int SOFT_QD = 6;   // token-pair rows in flight per wave
@@ -155,16 +136,12 @@ __global__ __launch_bounds__(768) void soft_aggregate_kernel(const float* __rest
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int b = blockIdx.y;
   const int tid = threadIdx.x, w = tid >> 6, l = tid & 63, i = l & 31, kk = l >> 5;
-  const int nwaves = blockDim.x >> 6;
-  const int PW = nwaves * 2 + 1;
-  uint32_t* mskl = reinterpret_cast<uint32_t*>(smem);         // [Ncap]   (Ncap % 4 == 0, > N)
-  int* tokl = reinterpret_cast<int*>(mskl + Ncap);            // [Ncap]
-  float* rnl = reinterpret_cast<float*>(tokl + Ncap);         // [Ncap]
-  float* wl = rnl + Ncap;                                     // [Ncap]
-  float* part = wl + Ncap;                                    // [32][PW]
-  float* alpha = part + 32 * PW;                              // [32]
-  int* wcount = reinterpret_cast<int*>(alpha + 32);           // [16]
-  unsigned char* xq = reinterpret_cast<unsigned char*>(wcount + 16);  // [nwaves][SOFT_QD][1 KiB] DMA queue (16-B aligned)
+  const SvAggLds<unsigned char*> L(smem, Ncap, blockDim.x >> 6, false, SOFT_QD * 1024);
+  uint32_t* mskl = reinterpret_cast<uint32_t*>(L.mskl);
+  int* tokl = reinterpret_cast<int*>(L.tokl);
+  float* rnl = reinterpret_cast<float*>(L.rnl);
+  float* wl = reinterpret_cast<float*>(L.wl);
+  unsigned char* xq = L.queue;   // [nwaves][SOFT_QD][1 KiB] DMA queue
 
   const int s0 = seg_off[b], S = seg_off[b + 1] - s0;
   const int r0 = 32 * (int)blockIdx.z;   // first segment of this workgroup inside the image
@@ -174,38 +151,10 @@ __global__ __launch_bounds__(768) void soft_aggregate_kernel(const float* __rest
   const int dcol = w * 128 + 4 * i;
   const bool dvalid = dcol < D;
   const float* Xb = Xt + (size_t)b * N * D + dcol;
-  const size_t KD = (size_t)K * D;
   const int k_begin = (int)blockIdx.x * kpb, k_end = min(K, k_begin + kpb);
 
-  // ---- the positions (label-grouped order of prep_kernel) that one of the 32 segments covers, ascending ----
-  int n = 0;
-  for (int base = 0; base < N; base += (int)blockDim.x) {
-    const int j = base + tid;
-    uint32_t m = 0;
-    if (j < N) m = (uint32_t)(colmask[((size_t)b * N + j) * SC + sc] >> (32 * half));
-    const uint64_t bal = __builtin_amdgcn_ballot_w64(m != 0);
-    if (l == 0) wcount[w] = __popcll(bal);
-    __syncthreads();
-    int off = n, tot = 0;
-    for (int ww = 0; ww < nwaves; ++ww) {
-      const int c = wcount[ww];
-      if (ww < w) off += c;
-      tot += c;
-    }
-    if (m != 0) {
-      const int pos = off + __popcll(bal & ((1ull << l) - 1ull));
-      mskl[pos] = m;
-      tokl[pos] = tok_order[(size_t)b * N + j];
-      rnl[pos] = rn_sorted[(size_t)b * N + j];
-    }
-    n += tot;
-    __syncthreads();
-  }
-  if (tid == 0 && (n & 1)) {  // pad to an even count with a zero-weight entry
-    mskl[n] = 0;
-    tokl[n] = 0;
-    rnl[n] = 0.f;
-  }
+  const int n = sv_agg_covered_list<false>(colmask, tok_order, rn_sorted, b, N, SC, sc, half, mskl, tokl, rnl, nullptr, reinterpret_cast<int*>(L.wcount));
+  if (tid == 0 && (n & 1)) sv_agg_zero_entry<false>(n, mskl, tokl, rnl, nullptr);   // pad to an even count with a zero-weight entry
   __syncthreads();
   const int npairs = (n + 1) >> 1;
   unsigned char* qbase = xq + (size_t)__builtin_amdgcn_readfirstlane(w) * (SOFT_QD * 1024);   // wave-uniform: lives in M0
@@ -223,10 +172,10 @@ __global__ __launch_bounds__(768) void soft_aggregate_kernel(const float* __rest
       for (int r = 0; r < 16; ++r) acc[q][r] = 0.f;
     {
       auto issue = [&](int p) {
-        const int t = soft_lds_read_i32(soft_lds_addr(tokl + 2 * p + kk));
+        const int t = sv_lds_read_i32(sv_lds_addr(tokl + 2 * p + kk));
         // lanes beyond D (a partial last wave) fetch a valid dummy address: their 16 B are never used
         const float* src = dvalid ? Xb + (size_t)t * D : Xt;
-        __builtin_amdgcn_global_load_lds((soft_gptr_t)src, (soft_lptr_t)(qbase + (p % SOFT_QD) * 1024), 16, 0, 0);
+        __builtin_amdgcn_global_load_lds((sv_gptr_t)src, (sv_lptr_t)(qbase + (p % SOFT_QD) * 1024), 16, 0, 0);
       };
       for (int q = 0; q < SOFT_QD && q < npairs; ++q) issue(q);
       for (int p = 0; p < npairs; ++p) {
@@ -241,8 +190,8 @@ __global__ __launch_bounds__(768) void soft_aggregate_kernel(const float* __rest
         f32x4 x;
         float rn, wt;
         uint32_t m;
-        soft_step_read(soft_lds_addr(qbase + (p % SOFT_QD) * 1024 + l * 16), soft_lds_addr(rnl + j), soft_lds_addr(wl + j),
-                       soft_lds_addr(mskl + j), x, rn, wt, m);
+        soft_step_read(sv_lds_addr(qbase + (p % SOFT_QD) * 1024 + l * 16), sv_lds_addr(rnl + j), sv_lds_addr(wl + j),
+                       sv_lds_addr(mskl + j), x, rn, wt, m);
         // (the slot has been read -- lgkmcnt(0) inside -- before it is refilled)
         if (p + SOFT_QD < npairs) issue(p + SOFT_QD);
         if (!dvalid) x = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -255,59 +204,20 @@ __global__ __launch_bounds__(768) void soft_aggregate_kernel(const float* __rest
         acc[3] = MFMA32(a0, b3, acc[3]);
       }
     }
-    // ---- block norms: quad reduce in registers, then across lanes / waves through LDS (aggregate_kernel's order) ----
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      float p = acc[0][r] * acc[0][r];
-      p = fmaf(acc[1][r], acc[1][r], p);
-      p = fmaf(acc[2][r], acc[2][r], p);
-      p = fmaf(acc[3][r], acc[3][r], p);
-      p += dpp_f32<0xB1>(p);    // quad_perm [1,0,3,2]
-      p += dpp_f32<0x4E>(p);    // quad_perm [2,3,0,1]
-      p += dpp_f32<0x141>(p);   // row_half_mirror
-      p += dpp_f32<0x140>(p);   // row_mirror
-      if ((l & 15) == 0) part[frag_row(r, kk) * PW + w * 2 + ((l >> 4) & 1)] = p;
-    }
-    __syncthreads();
-    if (tid < Sc) {
-      float sum = 0.f;
-      const int cnt = nwaves * 2;
-      for (int c = 0; c < cnt; ++c) sum += part[tid * PW + c];
-      const float nrm = nscale * sqrtf(sum);   // nscale: 1, or K where the accumulators hold V / K (soft_pooled)
-      alpha[tid] = nscale / fmaxf(nrm, 1e-12f);   // intra-normalisation; the row's own scale follows in soft_finalize_kernel
-      block_norms[(size_t)(s0 + r0 + tid) * K + k] = nrm;
-    }
-    __syncthreads();
-    if (dvalid) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int row = frag_row(r, kk);
-        if (row < Sc) {
-          const float a = alpha[row];
-          const float4 v = make_float4(acc[0][r] * a, acc[1][r] * a, acc[2][r] * a, acc[3][r] * a);
-          *reinterpret_cast<float4*>(out + (size_t)(s0 + r0 + row) * KD + (size_t)k * D + dcol) = v;
-        }
-      }
-    }
-    __syncthreads();
+    sv_agg_block_epilogue(acc, reinterpret_cast<float*>(L.part), reinterpret_cast<float*>(L.alpha), Sc, nscale, s0 + r0, k, K, D, dcol, dvalid, out,
+                          block_norms);
   }
 }
 
 int sv_launch_soft_aggregate(segvlad_ctx* ctx, const float* xt, const float* w, const uint64_t* colmask, const float* centres, int K, int D,
                              const int32_t* seg_off_dev, int B, int N, int SC, float* out, float* block_norms, const float* mean_centre) {
-  const int nwaves = (D + 127) / 128;
-  if (nwaves > 12) return ctx->fail(SEGVLAD_ERR_LIMIT, "soft aggregate: D=%d exceeds the 1536-wide workgroup of this build", D);
-  const int Ncap = (N + 4) & ~3;
-  const int PW = nwaves * 2 + 1;
-  size_t lds = (size_t)Ncap * 16 + (size_t)(32 * PW + 32) * sizeof(float) + 16 * sizeof(int);   // a multiple of 16
-  lds += (size_t)nwaves * SOFT_QD * 1024;   // DMA queue
-  if (lds > 160 * 1024) return ctx->fail(SEGVLAD_ERR_LIMIT, "soft aggregate: N=%d tokens need %zu B of LDS (limit 160 KiB)", N, lds);
-  if (lds > 64 * 1024) SV_HIP(sv_max_dyn_lds(reinterpret_cast<const void*>(soft_aggregate_kernel), lds));
-  int kpb = ctx->opt.agg_kpb;   // clusters per workgroup
-  if (kpb < 1) kpb = 1;
-  hipLaunchKernelGGL(soft_aggregate_kernel, dim3((K + kpb - 1) / kpb, B, 2 * SC), dim3(nwaves * 64), lds, ctx->stream, xt, w,
-                     ctx->s_rnsorted.as<float>(), ctx->s_tokorder.as<int32_t>(), colmask, mean_centre ? mean_centre : centres, seg_off_dev, N,
-                     D, K, SC, Ncap, out, block_norms, kpb, mean_centre ? 0 : D, mean_centre ? (float)K : 1.0f);
+  SvAggLaunch g;
+  const int rc = sv_agg_launch_geometry(ctx, "soft aggregate", reinterpret_cast<const void*>(soft_aggregate_kernel), false, SOFT_QD * 1024,
+                                        K, D, B, N, SC, centres, mean_centre, &g);
+  if (rc != SEGVLAD_OK) return rc;
+  hipLaunchKernelGGL(soft_aggregate_kernel, g.grid, g.block, g.lds, ctx->stream, xt, w, ctx->s_rnsorted.as<float>(),
+                     ctx->s_tokorder.as<int32_t>(), colmask, g.centres, seg_off_dev, N, D, K, SC, g.Ncap, out, block_norms, g.kpb, g.cstride,
+                     g.nscale);
   SV_HIP(hipGetLastError());
   return SEGVLAD_OK;
 }

@@ -15,19 +15,7 @@
 
 #include "ctx.h"
 #include "incidence_dev.h"
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-#define MFMA32(a, b, c) __builtin_amdgcn_mfma_f32_32x32x2f32((a), (b), (c), 0, 0, 0)
-
-// cross-lane move inside a 16-lane DPP row (quad_perm / row mirrors): plain VALU, no LDS crossbar
-template <int CTRL>
-__device__ __forceinline__ float dpp_f32(float x) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), CTRL, 0xf, 0xf, true));
-}
-
-// row of D-fragment register r for lane half kk (v_mfma_f32_32x32x2_f32 C/D layout)
-__device__ __forceinline__ int frag_row(int r, int kk) { return (r & 3) + 8 * (r >> 2) + 4 * kk; }
+#include "mfma_f32_dev.h"
 
 // ------------------------------------------------------------------------------------------------
 // vocabulary: c^ = C / max(||C||, 1e-12), stored in MFMA B-operand order
@@ -540,7 +528,7 @@ __global__ __launch_bounds__(256) void assign_kernel(const float* __restrict__ T
         for (int n = 0; n < NT; ++n)
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
-            const int tok = 2 * frag_row(r, kk) + mt;
+            const int tok = 2 * sv_frag_row(r, kk) + mt;
             float* p = &sc[tok * (KP + 1) + n * 32 + i];
             *p = (rnd == 0) ? acc[mt][n][r] : (*p + acc[mt][n][r]);
           }
@@ -693,7 +681,7 @@ __global__ __launch_bounds__(256) void assign_wide_kernel(const float* __restric
 #pragma unroll
   for (int n = 0; n < NT; ++n)
 #pragma unroll
-    for (int r = 0; r < 16; ++r) sc[(32 * w + frag_row(r, kk)) * (KP + 1) + n * 32 + i] = acc[n][r];
+    for (int r = 0; r < 16; ++r) sc[(32 * w + sv_frag_row(r, kk)) * (KP + 1) + n * 32 + i] = acc[n][r];
   __syncthreads();
   if (tid < 128 && t0 + tid < N) {
     const float rn = 1.0f / fmaxf(sqrtf(ssum[tid]), 1e-12f);
@@ -975,30 +963,13 @@ int sv_launch_prep(segvlad_ctx* ctx, const uint8_t* labels, const uint64_t* inc_
 //   (v - mean) * xscale = h1 + h2 (two fp16 terms, see gemm_f16x3_kernels.hip), so that the projection GEMM reads the
 //   descriptor without a separate max-abs + split pass and the fp32 descriptor need not reach HBM at all
 //   (|v| <= 1 by construction, which is what makes the scale known in advance).
-typedef const __attribute__((address_space(1))) void* agg_gptr_t;
-typedef __attribute__((address_space(3))) void* agg_lptr_t;
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-// Raw LDS reads for the loops that keep global->LDS DMAs in flight.  The compiler cannot tell the DMA'd queue slots from
-// any other LDS address, so before every LDS load IT emits it waits for all outstanding DMAs (s_waitcnt vmcnt(0)) -- which
-// turns a queue of QD loads in flight into one round trip per step.  Reads issued from inline asm are invisible to that
-// pass; the counted s_waitcnt in the loop is then the only wait.
-__device__ __forceinline__ unsigned lds_addr(const void* p) { return (unsigned)(size_t)(agg_lptr_t)p; }
-// one step's operands: the queue slot (16 B), 1/||x|| and the column mask of the lane's token
+// one step's operands, a raw LDS read (mfma_f32_dev.h: invisible to the compiler's wait insertion, the loop's counted s_waitcnt is
+// the only wait): the queue slot (16 B), 1/||x|| and the column mask of the lane's token
 __device__ __forceinline__ void lds_step_read(unsigned a_slot, unsigned a_rn, unsigned a_m, f32x4& x, float& rn, uint64_t& m) {
   asm volatile("ds_read_b128 %0, %3\n\tds_read_b32 %1, %4\n\tds_read_b64 %2, %5\n\ts_waitcnt lgkmcnt(0)"
                : "=&v"(x), "=&v"(rn), "=&v"(m)
                : "v"(a_slot), "v"(a_rn), "v"(a_m)
                : "memory");
-}
-__device__ __forceinline__ int lds_read_i32(unsigned a) {
-  int v;
-  asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=&v"(v) : "v"(a) : "memory");
-  return v;
-}
-__device__ __forceinline__ f32x4 lds_read_f32x4(unsigned a) {
-  f32x4 v;
-  asm volatile("ds_read_b128 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=&v"(v) : "v"(a) : "memory");
-  return v;
 }
 __device__ unsigned long long sv_agg_phase_cycles[8];   // ABL == 9: s_memtime phase sums of wave 0 (SEGVLAD_AGG_ABL=9 prints)
 #define SV_APHASE(k)                                                              \
@@ -1086,10 +1057,10 @@ __global__ __launch_bounds__(768) void aggregate_kernel(const float* __restrict_
     {
       unsigned char* qbase = xq + (size_t)__builtin_amdgcn_readfirstlane(w) * (QD * 1024);   // wave-uniform: lives in M0
       auto issue = [&](int p) {
-        const int t = lds_read_i32(lds_addr(tokl + 2 * p + kk));
+        const int t = sv_lds_read_i32(sv_lds_addr(tokl + 2 * p + kk));
         // lanes beyond D (a partial last wave) fetch a valid dummy address: their 16 B are never used
         const float* src = dvalid ? Xb + (size_t)t * D : Xt;
-        __builtin_amdgcn_global_load_lds((agg_gptr_t)src, (agg_lptr_t)(qbase + (p % QD) * 1024), 16, 0, 0);
+        __builtin_amdgcn_global_load_lds((sv_gptr_t)src, (sv_lptr_t)(qbase + (p % QD) * 1024), 16, 0, 0);
       };
       if (ABL != 1)
         for (int q = 0; q < QD && q < npairs; ++q) issue(q);
@@ -1105,7 +1076,7 @@ __global__ __launch_bounds__(768) void aggregate_kernel(const float* __restrict_
         f32x4 x;
         float rn;
         uint64_t m;
-        lds_step_read(lds_addr(qbase + (p % QD) * 1024 + l * 16), lds_addr(rnl + j), lds_addr(mskl + j), x, rn, m);
+        lds_step_read(sv_lds_addr(qbase + (p % QD) * 1024 + l * 16), sv_lds_addr(rnl + j), sv_lds_addr(mskl + j), x, rn, m);
         // (the slot has been read -- lgkmcnt(0) inside -- before it is refilled)
         if (ABL != 1 && p + QD < npairs) issue(p + QD);
         if (!dvalid || ABL == 1) x = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -1138,11 +1109,11 @@ __global__ __launch_bounds__(768) void aggregate_kernel(const float* __restrict_
         p = fmaf(acc[mt][3][r], acc[mt][3][r], p);
         // sum over the 16 lanes of a DPP row (quad swaps, then the two mirrors): VALU only -- ds_bpermute shuffles and
         // 96 partials per row made this phase 40 % of the kernel
-        p += dpp_f32<0xB1>(p);    // quad_perm [1,0,3,2]
-        p += dpp_f32<0x4E>(p);    // quad_perm [2,3,0,1]
-        p += dpp_f32<0x141>(p);   // row_half_mirror
-        p += dpp_f32<0x140>(p);   // row_mirror
-        if ((l & 15) == 0) part[(32 * mt + frag_row(r, kk)) * PW + w * 2 + ((l >> 4) & 1)] = p;
+        p += sv_dpp_f32<0xB1>(p);    // quad_perm [1,0,3,2]
+        p += sv_dpp_f32<0x4E>(p);    // quad_perm [2,3,0,1]
+        p += sv_dpp_f32<0x141>(p);   // row_half_mirror
+        p += sv_dpp_f32<0x140>(p);   // row_mirror
+        if ((l & 15) == 0) part[(32 * mt + sv_frag_row(r, kk)) * PW + w * 2 + ((l >> 4) & 1)] = p;
       }
     }
     SV_APHASE(5)  // partial norms computed
@@ -1166,7 +1137,7 @@ __global__ __launch_bounds__(768) void aggregate_kernel(const float* __restrict_
         if (mt == 1 && !two) break;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int row = 32 * mt + frag_row(r, kk);
+          const int row = 32 * mt + sv_frag_row(r, kk);
           if (row < Sc) {
             const float a = alpha[row];
             float4 v = make_float4(acc[mt][0][r] * a, acc[mt][1][r] * a, acc[mt][2][r] * a, acc[mt][3][r] * a);
@@ -1300,10 +1271,10 @@ __global__ __launch_bounds__(64 * TNK_WAVES, 2) void token_norms_kernel(const fl
     int idc = 0, ip = 0, fi = 0;   // issue cursor
     auto issue = [&]() {
       const int j = 2 * ip + kk;
-      const int t = single ? lds_read_i32(lds_addr(tokl + j)) : (j < n ? tok_order[tb + j] : 0);
+      const int t = single ? sv_lds_read_i32(sv_lds_addr(tokl + j)) : (j < n ? tok_order[tb + j] : 0);
       const int dcol = idc * 128 + 4 * i;
       const float* src = dcol < D ? Xb + (size_t)t * D + dcol : Xt;   // lanes beyond D fetch a valid dummy address
-      __builtin_amdgcn_global_load_lds((agg_gptr_t)src, (agg_lptr_t)(qbase + (fi % TNK_QD) * 1024), 16, 0, 0);
+      __builtin_amdgcn_global_load_lds((sv_gptr_t)src, (sv_lptr_t)(qbase + (fi % TNK_QD) * 1024), 16, 0, 0);
       ++fi;
       if (++ip == npairs) {
         ip = 0;
@@ -1315,7 +1286,7 @@ __global__ __launch_bounds__(64 * TNK_WAVES, 2) void token_norms_kernel(const fl
     for (int dc = 0; dc < nd; ++dc) {
       const int dcol = dc * 128 + 4 * i;
       const bool dvalid = dcol < D;
-      const f32x4 c4 = lds_read_f32x4(lds_addr(cl + dcol));
+      const f32x4 c4 = sv_lds_read_f32x4(sv_lds_addr(cl + dcol));
       const size_t kb_dc = (size_t)(dcol >> 5);                       // k-block of this lane's four columns
       const unsigned lane_c = (unsigned)((dcol & 31) >> 3), lane_o = (unsigned)(dcol & 7);
       for (int p = 0; p < npairs; ++p, ++f) {
@@ -1345,9 +1316,9 @@ __global__ __launch_bounds__(64 * TNK_WAVES, 2) void token_norms_kernel(const fl
           asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // list entries come from global memory on this path
         }
         if (single)
-          lds_step_read(lds_addr(qbase + (f % TNK_QD) * 1024 + l * 16), lds_addr(rnl + j), lds_addr(mskl + j), x, rn, m);
+          lds_step_read(sv_lds_addr(qbase + (f % TNK_QD) * 1024 + l * 16), sv_lds_addr(rnl + j), sv_lds_addr(mskl + j), x, rn, m);
         else
-          x = lds_read_f32x4(lds_addr(qbase + (f % TNK_QD) * 1024 + l * 16));
+          x = sv_lds_read_f32x4(sv_lds_addr(qbase + (f % TNK_QD) * 1024 + l * 16));
         // (the slot has been read -- lgkmcnt(0) inside -- before it is refilled)
         if (fi < total) issue();
         if (!dvalid) x = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -1363,7 +1334,7 @@ __global__ __launch_bounds__(64 * TNK_WAVES, 2) void token_norms_kernel(const fl
             p2[e] = (_Float16)(fv[e] - (float)p1[e]);
           }
           // (the row list is read on the first chunk only; these stores are never predicated away: the counted waits count them)
-          if (single) prw = lds_read_i32(lds_addr(rowl + j));
+          if (single) prw = sv_lds_read_i32(sv_lds_addr(rowl + j));
           const bool real = dvalid && prw >= 0;
           // sv_x3_off(row, dcol, D) with the lane / chunk constants of this 128-column chunk taken out of the loop
           const unsigned rr = (unsigned)prw;
@@ -1408,12 +1379,12 @@ __global__ __launch_bounds__(64 * TNK_WAVES, 2) void token_norms_kernel(const fl
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         float p = nsq[mt][r];
-        p += dpp_f32<0xB1>(p);
-        p += dpp_f32<0x4E>(p);
-        p += dpp_f32<0x141>(p);
-        p += dpp_f32<0x140>(p);
+        p += sv_dpp_f32<0xB1>(p);
+        p += sv_dpp_f32<0x4E>(p);
+        p += sv_dpp_f32<0x141>(p);
+        p += sv_dpp_f32<0x140>(p);
         p += __shfl_xor(p, 16);
-        const int row = 32 * mt + frag_row(r, kk);
+        const int row = 32 * mt + sv_frag_row(r, kk);
         if (i == 0 && row < Sc) block_norms[(size_t)(s0 + 64 * sc + row) * K + k] = sqrtf(p);
       }
     }
@@ -1493,7 +1464,7 @@ __global__ __launch_bounds__(T == 1 ? 256 : 128, 2) void gram_norms_kernel(const
     for (int pz = 0; pz < 4 * T; ++pz)
       if (pz < NP) {   // (wave-uniform: the instruction is issued, and counted, exactly NP times per step)
         if (8 * pz + (l >> 3) < n)
-          __builtin_amdgcn_global_load_lds((agg_gptr_t)(src[pz] + 32 * f), (agg_lptr_t)(qbase + (f % QS) * (T * GNK_SLOT) + pz * 1024), 16, 0, 0);
+          __builtin_amdgcn_global_load_lds((sv_gptr_t)(src[pz] + 32 * f), (sv_lptr_t)(qbase + (f % QS) * (T * GNK_SLOT) + pz * 1024), 16, 0, 0);
       }
   };
 #pragma unroll
@@ -1517,7 +1488,7 @@ __global__ __launch_bounds__(T == 1 ? 256 : 128, 2) void gram_norms_kernel(const
     pswz[tt] = (unsigned)sv_x3_swz(rr);
   }
   const unsigned fsw = (unsigned)((i >> 1) & 7);
-  const unsigned a_tok = lds_addr(qbase) + (unsigned)i * 128u;
+  const unsigned a_tok = sv_lds_addr(qbase) + (unsigned)i * 128u;
   for (int f = 0; f < steps; ++f) {
     // the DMAs of step f have landed: behind them were issued, for each of the QS - 1 steps in between, 4 T plane stores and NP
     // DMAs, and the 4 T stores of step f - 1 (loads and stores retire in issue order)
@@ -1526,7 +1497,7 @@ __global__ __launch_bounds__(T == 1 ? 256 : 128, 2) void gram_norms_kernel(const
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     f32x4 x[T][4], c[4];
     {
-      const unsigned ac = lds_addr(cl) + (unsigned)(32 * f + 8 * kk) * 4u;
+      const unsigned ac = sv_lds_addr(cl) + (unsigned)(32 * f + 8 * kk) * 4u;
       // chunks 2 kk, 2 kk + 1 (k-step 0) and 4 + 2 kk, 5 + 2 kk (k-step 1) of token i, at their swizzled positions
       const unsigned p0 = ((unsigned)(2 * kk) ^ fsw) << 4, p1 = ((unsigned)(2 * kk + 1) ^ fsw) << 4;
       const unsigned p2 = ((unsigned)(4 + 2 * kk) ^ fsw) << 4, p3 = ((unsigned)(5 + 2 * kk) ^ fsw) << 4;
@@ -1579,7 +1550,7 @@ __global__ __launch_bounds__(T == 1 ? 256 : 128, 2) void gram_norms_kernel(const
         }
     }
   }
-  // ---- per segment: m^T G m over this lane's 16 entries G(a, b)[frag_row(r, kk)][i] of every tile, then across the wave ------
+  // ---- per segment: m^T G m over this lane's 16 entries G(a, b)[sv_frag_row(r, kk)][i] of every tile, then across the wave ------
   // CANCELLATION: the quadratic form carries ~n 2^-22 of the COVERED DIAGONAL sum_t m_t G_tt, not of its own value;
   // when a segment's residuals nearly cancel (m^T G m << the diagonal sum) that is no longer small against the norm it divides
   // by.  Such a task is flagged (redo_task) and token_norms_kernel recomputes it with the fp32 block sums, which have no such
@@ -1591,7 +1562,7 @@ __global__ __launch_bounds__(T == 1 ? 256 : 128, 2) void gram_norms_kernel(const
     const int gd = tt == 0 ? 0 : NG - 1;   // tiles (0,0) and (T-1,T-1)
 #pragma unroll
     for (int r = 0; r < 16; ++r)
-      if (frag_row(r, kk) == i) dgl[tt] = acc[gd][r];
+      if (sv_frag_row(r, kk) == i) dgl[tt] = acc[gd][r];
   }
   bool cancels = false;
   const float inv_x2 = 1.f / (xscale * xscale);
@@ -1617,23 +1588,23 @@ __global__ __launch_bounds__(T == 1 ? 256 : 128, 2) void gram_norms_kernel(const
           for (int tb2 = ta; tb2 < T; ++tb2, ++g) {
             float q = 0.f;
 #pragma unroll
-            for (int r = 0; r < 16; ++r) q += ((W[ta] >> frag_row(r, kk)) & 1u) ? acc[g][r] : 0.f;
+            for (int r = 0; r < 16; ++r) q += ((W[ta] >> sv_frag_row(r, kk)) & 1u) ? acc[g][r] : 0.f;
             q = ((W[tb2] >> i) & 1u) ? q : 0.f;
             p += (ta == tb2) ? q : 2.f * q;   // the off-diagonal tile stands for its transpose as well
           }
-        p += dpp_f32<0xB1>(p);
-        p += dpp_f32<0x4E>(p);
-        p += dpp_f32<0x141>(p);
-        p += dpp_f32<0x140>(p);
+        p += sv_dpp_f32<0xB1>(p);
+        p += sv_dpp_f32<0x4E>(p);
+        p += sv_dpp_f32<0x141>(p);
+        p += sv_dpp_f32<0x140>(p);
         p += __shfl_xor(p, 16);
         p += __shfl_xor(p, 32);
         float dg = 0.f;   // the covered diagonal
 #pragma unroll
         for (int tt = 0; tt < T; ++tt) dg += ((W[tt] >> i) & 1u) ? dgl[tt] : 0.f;
-        dg += dpp_f32<0xB1>(dg);
-        dg += dpp_f32<0x4E>(dg);
-        dg += dpp_f32<0x141>(dg);
-        dg += dpp_f32<0x140>(dg);
+        dg += sv_dpp_f32<0xB1>(dg);
+        dg += sv_dpp_f32<0x4E>(dg);
+        dg += sv_dpp_f32<0x141>(dg);
+        dg += sv_dpp_f32<0x140>(dg);
         dg += __shfl_xor(dg, 16);
         dg += __shfl_xor(dg, 32);
         cancels = cancels || (p < 0.0625f * dg);

@@ -479,24 +479,26 @@ struct StageScope {
 };
 
 // ---- kernel launchers (defined in the *_kernels.hip units) ---------------------------------------
-// vlad_kernels.hip
-int sv_launch_vocab_prepare(segvlad_ctx* ctx);
+// mask_kernels.hip
 int sv_launch_incidence(segvlad_ctx* ctx, const uint8_t* masks, int S, int Hm, int Wm, int H, int W, int patch,
                         uint64_t* inc_bits, double* centroids /* may be null */);
 int sv_launch_centroids(segvlad_ctx* ctx, const uint8_t* masks, int S, int Hm, int Wm, double* out);
 bool sv_adjacency_fits(int S_max);   // an image of S_max segments fits the in-LDS Delaunay (else: SEGVLAD_ERR_LIMIT)
 int sv_launch_adjacency(segvlad_ctx* ctx, const double* cent, const int32_t* seg_off_dev, const int64_t* adj_off_dev,
                         int B, int S_max, int order, uint8_t* adj, uint32_t* n_bad, uint8_t* img_flags = nullptr);
+// assign_kernels.hip
+int sv_launch_vocab_prepare(segvlad_ctx* ctx);
 int sv_launch_assign(segvlad_ctx* ctx, const float* tokens, int B, int N, float* xt, uint8_t* labels, float* rnorm,
                      float* gap);
+// vlad_kernels.hip
 int sv_launch_prep(segvlad_ctx* ctx, const uint8_t* labels, const uint64_t* inc_bits, const int32_t* seg_off_dev,
                    const int64_t* adj_off_dev, const uint8_t* adj, int B, int N, int K, int S_max, int SC,
                    uint64_t* colmask, float* gscale, int32_t* phys /* [B][N], or null */, int32_t* cov_cnt /* [B][K] */,
                    int cover /* 0: every token counts as covered */);
-// centres == nullptr: the inputs are residuals already (x * rnorm - 0)
-int sv_launch_aggregate(segvlad_ctx* ctx, const float* xt, const float* rnorm, const uint8_t* labels,
-                        const uint64_t* colmask, const float* centres, int K, int D, const int32_t* seg_off_dev,
-                        const float* gscale, int B, int N, int SC, float* out, float* block_norms,
+// after sv_launch_prep, whose label-grouped token order and 1/||x|| it reads.  centres == nullptr: the inputs are residuals already
+// (x * rnorm - 0)
+int sv_launch_aggregate(segvlad_ctx* ctx, const float* xt, const uint64_t* colmask, const float* centres, int K, int D,
+                        const int32_t* seg_off_dev, const float* gscale, int B, int N, int SC, float* out, float* block_norms,
                         const float* mean = nullptr, float xscale = 0.f, uint16_t* h1 = nullptr, uint16_t* h2 = nullptr);
 
 // soft_vlad_kernels.hip (option vlad_assign=soft:<T>; after sv_launch_prep, whose label-grouped token order, 1/||x|| and column masks
@@ -533,6 +535,7 @@ int sv_launch_burst_seg_aggregate(segvlad_ctx* ctx, const float* xt, const float
                                   const float* centres, int K, int D, const int32_t* seg_off_dev, int B, int N, int SC, float* out,
                                   float* block_norms, const float* mean_centre = nullptr);
 
+// block_norm_kernels.hip
 // block norms + the fp16 planes of the token residuals x^ - C_k, grouped by cluster (rowbase from sv_launch_group_plan); after sv_launch_prep
 int sv_launch_token_norms(segvlad_ctx* ctx, const float* xt, const uint64_t* colmask, const float* centres, int K, int D,
                           const int32_t* seg_off_dev, int B, int N, int SC, float* block_norms, float xscale, uint16_t* h1,

@@ -344,9 +344,9 @@ static int pass_descriptor(segvlad_ctx* ctx, const DescribePlan& p, const Descri
     SV_TRY(pass_soft_descriptor(ctx, p, io, h1, h2));
   } else {
     StageScope sc(ctx, "aggregate");
-    SV_TRY(sv_launch_aggregate(ctx, ctx->s_xt.as<float>(), ctx->s_rnorm.as<float>(), (const uint8_t*)io.d_lab, ctx->s_colmask.as<uint64_t>(),
-                               ctx->vocab.as<float>(), p.K, p.D, ctx->s_segoff.as<int32_t>(), ctx->s_gscale.as<float>(), p.B, p.N, p.SC,
-                               (float*)io.d_out, (float*)io.d_bn, fused ? ctx->pca_mean.as<float>() : nullptr, p.xscale, h1, h2));
+    SV_TRY(sv_launch_aggregate(ctx, ctx->s_xt.as<float>(), ctx->s_colmask.as<uint64_t>(), ctx->vocab.as<float>(), p.K, p.D,
+                               ctx->s_segoff.as<int32_t>(), ctx->s_gscale.as<float>(), p.B, p.N, p.SC, (float*)io.d_out,
+                               (float*)io.d_bn, fused ? ctx->pca_mean.as<float>() : nullptr, p.xscale, h1, h2));
     sc.count();
   }
   if (!fused) return SEGVLAD_OK;
@@ -696,8 +696,8 @@ extern "C" int segvlad_cluster_aggregate(segvlad_ctx* ctx, int num_c, const floa
   hipLaunchKernelGGL(fill_ones_kernel, dim3((N + 255) / 256), dim3(256), 0, ctx->stream, ctx->s_rnorm.as<float>(), N);
   SV_TRY(sv_launch_prep(ctx, (const uint8_t*)d_lab, (const uint64_t*)d_inc, ctx->s_segoff.as<int32_t>(), ctx->s_adjoff.as<int64_t>(),
                         (const uint8_t*)d_adj, 1, N, num_c, S, SC, ctx->s_colmask.as<uint64_t>(), ctx->s_gscale.as<float>(), nullptr, nullptr, 0));
-  SV_TRY(sv_launch_aggregate(ctx, (const float*)d_res, ctx->s_rnorm.as<float>(), (const uint8_t*)d_lab, ctx->s_colmask.as<uint64_t>(), nullptr,
-                             num_c, D, ctx->s_segoff.as<int32_t>(), ctx->s_gscale.as<float>(), 1, N, SC, (float*)d_out, nullptr));
+  SV_TRY(sv_launch_aggregate(ctx, (const float*)d_res, ctx->s_colmask.as<uint64_t>(), nullptr, num_c, D, ctx->s_segoff.as<int32_t>(),
+                             ctx->s_gscale.as<float>(), 1, N, SC, (float*)d_out, nullptr));
   SV_HIP(hipStreamSynchronize(ctx->stream));  // so[] / ao[] live on this frame
   return sv_finish(ctx);
 }

@@ -25,6 +25,7 @@
 #include <stdlib.h>
 
 #include "ctx.h"
+#include "waitcnt_dev.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
@@ -69,14 +70,6 @@ int sv_launch_split_f16x2(segvlad_ctx* ctx, const float* X, int64_t n_rows, int 
                      reinterpret_cast<_Float16*>(h1), reinterpret_cast<_Float16*>(h2));
   SV_HIP(hipGetLastError());
   return SEGVLAD_OK;
-}
-
-template <int N_>
-__device__ __forceinline__ void wait_vm_lgkm0_() {
-  if (N_ == 0) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-  else if (N_ == 2) asm volatile("s_waitcnt vmcnt(2) lgkmcnt(0)" ::: "memory");
-  else if (N_ == 4) asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory");
-  else asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)" ::: "memory");
 }
 
 // C[M][N] (+ split-K partials) = sum_k (A1+A2)[m][k] (B1+B2)[n][k], k in this block's slice.
@@ -188,7 +181,7 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_f16x3_kernel(const uint16_t
     }
   };
   dma_tile(0, 0);
-  wait_vm_lgkm0_<0>();
+  sv_wait_vm_lgkm0<0>();
   __builtin_amdgcn_s_barrier();
   int cur = 0;
   const int fa0 = wm * (16 * TM) + i, fb0 = wn * (16 * TN) + i;
@@ -226,7 +219,7 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_f16x3_kernel(const uint16_t
 #pragma unroll
         for (int nt = 0; nt < 4; ++nt) acc[mt][4 * h + nt] = MFMA_F16(a1[mt], b1[nt], acc[mt][4 * h + nt]);
     }
-    wait_vm_lgkm0_<0>();
+    sv_wait_vm_lgkm0<0>();
     __builtin_amdgcn_s_barrier();
     cur ^= 1;
   }

@@ -1,5 +1,5 @@
 // Token cells and nearest-neighbour source indices of the incidence kernels: ONE definition for the kernels that read dense
-// mask bytes (vlad_kernels.hip) and the one that reads run-length masks (rle_kernels.hip), so that every path samples the
+// mask bytes (mask_kernels.hip) and the one that reads run-length masks (rle_kernels.hip), so that every path samples the
 // same source pixels (func_vpr.py:1088-1092: F.interpolate(mode="nearest") to H x W, then the patch x patch cells).
 #pragma once
 #include <hip/hip_runtime.h>

@@ -1,9 +1,12 @@
 // Device helpers shared by the search's translation units: the order-preserving float <-> key map (its only definition), the
-// workgroup bitonic sort of keys or (key << 32 | id) words, DPP wave reductions, the flagging of a row.
+// workgroup bitonic sort of keys or (key << 32 | id) words, DPP wave reductions, the flagging of a row; the counted waits of the
+// filter's DMA loops come with it (waitcnt_dev.h).
 #pragma once
 #include <stdint.h>
 
 #include <hip/hip_runtime.h>
+
+#include "waitcnt_dev.h"
 
 __device__ __forceinline__ uint32_t f2key_(float f) {
   const uint32_t u = __float_as_uint(f);

@@ -487,17 +487,6 @@ int sv_launch_to_f16(segvlad_ctx* ctx, const float* X, int64_t n_elems, float sc
 typedef const __attribute__((address_space(1))) void* gptr_t;
 typedef __attribute__((address_space(3))) void* lptr_t;
 
-template <int N_>
-__device__ __forceinline__ void wait_vm_lgkm0() {  // s_waitcnt needs a literal count
-  static_assert(N_ == 0 || N_ == 1 || N_ == 2 || N_ == 3 || N_ == 4 || N_ == 8, "add the literal");
-  if constexpr (N_ == 0) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-  else if constexpr (N_ == 1) asm volatile("s_waitcnt vmcnt(1) lgkmcnt(0)" ::: "memory");
-  else if constexpr (N_ == 2) asm volatile("s_waitcnt vmcnt(2) lgkmcnt(0)" ::: "memory");
-  else if constexpr (N_ == 3) asm volatile("s_waitcnt vmcnt(3) lgkmcnt(0)" ::: "memory");
-  else if constexpr (N_ == 4) asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory");
-  else asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)" ::: "memory");
-}
-
 // Operand tiles go global -> LDS directly (global_load_lds_dwordx4, no VGPR staging, no ds_write): one
 // wave-instruction fills 1 KiB of the LDS image, lane l landing at base + 16 l, i.e. RP = 1024 / row_bytes rows
 // of HBK fp16.  The LDS image must be lane-linear, so the bank-conflict swizzle is applied on the SOURCE side:
@@ -836,9 +825,9 @@ __global__ __launch_bounds__(64 * C::WM * C::WN) void knn_f16_filter_kernel(
   int rev = PERSIST ? rev_of(seq) : 0;   // (only the persistent walk has steps to alternate / rotate)
   issue_head(tm, tn, rev);
   if (ntiles > 1)
-    wait_vm_lgkm0<JB>();
+    sv_wait_vm_lgkm0<JB>();
   else
-    wait_vm_lgkm0<0>();
+    sv_wait_vm_lgkm0<0>();
   // (the barrier that publishes the head to the other waves is the one at the top of the tile loop)
 
   for (;;) {   // PERSIST: one iteration per tile; otherwise a single pass
@@ -1025,9 +1014,9 @@ __global__ __launch_bounds__(64 * C::WM * C::WN) void knn_f16_filter_kernel(
           // youngest JB DMA instructions, may still fly).  The barriers between here and the first read of tile kt+1
           // (one for the leading half, two for the lagging half) make that true for every wave's pieces.
           if (kt + 2 < ntiles)
-            wait_vm_lgkm0<JB>();
+            sv_wait_vm_lgkm0<JB>();
           else
-            wait_vm_lgkm0<0>();
+            sv_wait_vm_lgkm0<0>();
         } else {
           asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         }
@@ -1125,9 +1114,9 @@ __global__ __launch_bounds__(64 * C::WM * C::WN) void knn_f16_filter_kernel(
           for (int nt = 0; nt < TN16; ++nt) acc16[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[mt], b[nt], acc16[mt][nt], 0, 0, 0);
       }
       if (kt + 2 < ntiles)
-        wait_vm_lgkm0<JB>();
+        sv_wait_vm_lgkm0<JB>();
       else
-        wait_vm_lgkm0<0>();
+        sv_wait_vm_lgkm0<0>();
       __builtin_amdgcn_s_barrier();
       ia ^= 1;
       ib = (ib + 1 >= NB) ? 0 : ib + 1;
@@ -1175,9 +1164,9 @@ __global__ __launch_bounds__(64 * C::WM * C::WN) void knn_f16_filter_kernel(
       // instructions -- may still fly: vmcnt retires in order) and its LDS reads are done; after the barrier that
       // holds for every wave, so the stages of tile kt may be overwritten
       if (kt + 2 < ntiles)
-        wait_vm_lgkm0<JB>();
+        sv_wait_vm_lgkm0<JB>();
       else
-        wait_vm_lgkm0<0>();
+        sv_wait_vm_lgkm0<0>();
       __builtin_amdgcn_s_barrier();
       ia ^= 1;
       ib = (ib + 1 >= NB) ? 0 : ib + 1;

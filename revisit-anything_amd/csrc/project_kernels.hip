@@ -11,7 +11,7 @@
 // i.e. every TOKEN's residual is projected once with its cluster's slice of the components -- 2 N D P flops per image
 // instead of 2 S K D P for the descriptor (1530 x 1536 instead of 50 x 98 304 rows x columns: 2.1 x fewer) -- and the
 // segments are aggregated in the P-dimensional space.  Only the block norms ||V_sk|| still come from the D-space
-// (token_norms_kernel, vlad_kernels.hip, which also emits the fp16 planes of the residuals, grouped by cluster).
+// (token_norms_kernel / gram_norms_kernel, block_norm_kernels.hip, which also emit the fp16 planes of the residuals, grouped by cluster).
 // Projecting the RESIDUAL (not the token, with the centre term subtracted afterwards) keeps the sums free of cancellation:
 // the result is as accurate as projecting the finished descriptor.
 //

@@ -7,9 +7,8 @@
  * Builds.  The SHIPPED library (revisit-anything_amd/build.py; lib/libsegvlad_hip.so) and the DEVELOPMENT build
  * (`python revisit-anything_amd/build.py --ablations`, -DSEGVLAD_ABLATIONS -> lib/libsegvlad_hip_abl.so, loaded with
  * SEGVLAD_LIB_PATH) hold the same kernels; the development build adds three probes of the batch filter kernel (f16_cfg 93:
- * phase timing; 94 / 95: timing ablations with WRONG results), the timing ablations of the VLAD kernels (SEGVLAD_ASSIGN_ABL,
- * SEGVLAD_AGG_ABL, WRONG results) and their phase timers.  A value that names no kernel of the build is rejected with
- * SEGVLAD_ERR_ARG.  (The fp16 filter's measured-and-not-kept variants -- "f16_mf", "f16_epi", "f16_pp", "f16_dsplit",
+ * phase timing; 94 / 95: timing ablations with WRONG results) and nothing else.  A value that names no kernel of the build is
+ * rejected with SEGVLAD_ERR_ARG.  (The fp16 filter's measured-and-not-kept variants -- "f16_mf", "f16_epi", "f16_pp", "f16_dsplit",
  * "f16_small_mf", f16_deep_cfg 0 - 3, f16_buf 1, the other f16_cfg values -- left the tree; DESIGN.md 4 / 7 has their
  * measurements and names the commit that last held them.)
  *
@@ -24,7 +23,7 @@
  *     "f16_walk"      tile walk of the persistent kernel: bit 0 = an XCD keeps its block of query tiles, bit 1 = odd steps run
  *                     their k-tiles backwards, bit 2 = rotated k start per workgroup (-1 = 3)    any (a launch parameter)
  *     "f16_gm"        tile-block height of the XCD-aware order                                    any (a launch parameter)
- *   fused VLAD -> PCA (vlad_kernels.hip, project_kernels.hip, gemm_f16x3_kernels.hip)
+ *   fused VLAD -> PCA (assign_kernels.hip, vlad_kernels.hip, block_norm_kernels.hip, project_kernels.hip, gemm_f16x3_kernels.hip)
  *     "tnk_gram"      1 | 0   block norms from the Gram matrix of a task's residuals (16-bit matrix pipe) | fp32 block sums
  *     "tnk_fork"      1 | 0   the two-tile Gram launch on the context's side stream | in line
  *     "pj_f16"        1 | 0   P-space tile sums on the 16-bit matrix pipe | fp32 MFMA

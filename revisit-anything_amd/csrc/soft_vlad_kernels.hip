@@ -11,6 +11,7 @@
 // weighted residuals exists one (token pair, cluster, 128-column slice) at a time in the B operand's registers, never in memory.
 // Every sum runs in the order of prep_kernel's label-grouped token positions of ONE image: fixed, and independent of the batch.
 #include "ctx.h"
+#include "assign_dev.h"
 #include "weighted_agg_dev.h"
 
 // ------------------------------------------------------------------------------------------------
@@ -46,12 +47,7 @@ __global__ __launch_bounds__(128) void soft_weights_kernel(const float* __restri
 #pragma unroll
     for (int n = 0; n < NT; ++n) acc[n] = MFMA32(x, bp[n * 64], acc[n]);
   }
-  ss += __shfl_xor(ss, 32);
-  if (kk == 0) ssum[32 * w + i] = ss;
-#pragma unroll
-  for (int n = 0; n < NT; ++n)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) sc[(32 * w + sv_frag_row(r, kk)) * (KP + 1) + n * 32 + i] = acc[n][r];
+  SV_SCORE_TILE_STORE(NT, acc, ss, sc, ssum, w, i, kk);
   __syncthreads();
   if (tid < 64) {
     const float rn = 1.0f / fmaxf(sqrtf(ssum[tid]), 1e-12f);
@@ -180,13 +176,7 @@ __global__ __launch_bounds__(768) void soft_aggregate_kernel(const float* __rest
       for (int q = 0; q < SOFT_QD && q < npairs; ++q) issue(q);
       for (int p = 0; p < npairs; ++p) {
         const int j = 2 * p + kk;
-        const int rem = npairs - 1 - p;   // DMAs issued after pair p's
-        if (rem >= SOFT_QD - 1) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
-        else if (rem == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-        else if (rem == 3) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
-        else if (rem == 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-        else if (rem == 1) asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        sv_wait_queue<SOFT_QD>(npairs - 1 - p);   // (the DMAs issued after pair p's)
         f32x4 x;
         float rn, wt;
         uint32_t m;

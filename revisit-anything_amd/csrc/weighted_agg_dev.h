@@ -92,10 +92,7 @@ __device__ __forceinline__ void sv_agg_block_epilogue(const f32x16 (&acc)[4], fl
     p = fmaf(acc[1][r], acc[1][r], p);
     p = fmaf(acc[2][r], acc[2][r], p);
     p = fmaf(acc[3][r], acc[3][r], p);
-    p += sv_dpp_f32<0xB1>(p);    // quad_perm [1,0,3,2]
-    p += sv_dpp_f32<0x4E>(p);    // quad_perm [2,3,0,1]
-    p += sv_dpp_f32<0x141>(p);   // row_half_mirror
-    p += sv_dpp_f32<0x140>(p);   // row_mirror
+    p = sv_dpp_row_sum(p);
     if ((l & 15) == 0) part[sv_frag_row(r, kk) * PW + w * 2 + ((l >> 4) & 1)] = p;
   }
   __syncthreads();

@@ -1,5 +1,5 @@
 """The describe stage's shape table: hand-chosen (K, D, N, S) cases, one per branch that the launchers of
-csrc/vlad_kernels.hip, csrc/project_kernels.hip and csrc/describe.hip take from the shape alone.  A plain module (no
+csrc/assign_kernels.hip, csrc/vlad_kernels.hip, csrc/block_norm_kernels.hip, csrc/project_kernels.hip and csrc/describe.hip take from the shape alone.  A plain module (no
 fixtures): tests/test_describe_shape_cases.py checks on the CPU, with the fp64 oracle only, that every case qualifies
 (top-2 gap, block-norm floor, the branch it is named for); tests/test_gpu_describe_shapes.py runs the kernels on it.
 

@@ -1,6 +1,6 @@
 """The mask branch's shape table: which tokens belong to which segment (segvlad_incidence, segvlad_incidence_centroids,
 segvlad_mask_centroids) and which segments are pooled together (segvlad_adjacency, segvlad_adjacency_flagged) -- one case per
-branch that sv_launch_incidence and sv_launch_adjacency (csrc/vlad_kernels.hip) take from the shape alone.  A plain module (no
+branch that sv_launch_incidence and sv_launch_adjacency (csrc/mask_kernels.hip) take from the shape alone.  A plain module (no
 fixtures): tests/test_mask_branch_cases.py qualifies the table on the CPU with references only, tests/test_gpu_mask_branch.py runs
 the kernels on it.  Every comparison made with this table is exact.
 

@@ -25,6 +25,8 @@ def test_header_declares_the_expected_surface():
 def test_library_builds_loads_and_exports_every_declared_symbol():
     from revisit_anything_amd import _lib, build
 
+    csrc = os.path.join(ROOT, "revisit-anything_amd", "csrc")
+    assert sorted(build.SOURCES) == sorted(f for f in os.listdir(csrc) if f.endswith(".hip")), "build.SOURCES is not the set of csrc/*.hip"
     path = build.build()
     assert os.path.exists(path)
     lib = ctypes.CDLL(path)

@@ -14,7 +14,7 @@ The bound on sums[k][c], read off the code (u = 2^-24):
     contraction the product and the sum round once each and the first sum (onto 0) is exact.  Either way a token's term passes
     through at most (n_bk - 1) + 1 roundings, n_bk = the tokens of image b in cluster k; one more u covers the second order of
     (1 + u)^m, m <= 513 + 1 + rho (m^2 u / 2 <= 1 for m <= 5792): n_bk - 1 + 2.
-  * rnorm[t] = 1.0f / fmaxf(sqrtf(s2), 1e-12f) (assign_kernel and assign_wide_kernel, csrc/vlad_kernels.hip).  s2: every square
+  * rnorm[t] = 1.0f / fmaxf(sqrtf(s2), 1e-12f) (SV_ASSIGN_TOKEN, csrc/assign_dev.h: assign_kernel and assign_wide_kernel).  s2: every square
     enters an fmaf chain (ss = fmaf(x, x, ss): the square itself is not rounded) of at most D / 2 terms -- the half-waves kk = 0, 1
     split D, the narrow kernel's four waves split it again -- and then one add across the half-waves and, in the narrow kernel,
     three across the waves: at most D / 2 + 3 roundings of non-negative terms, relative error (D / 2 + 3) u.  The square root

@@ -1,5 +1,6 @@
 """The records of tests/golden/weighted_vlad_bytes.json: SHA-256 digests of what the weighted describe-stage kernels
-(csrc/soft_vlad_kernels.hip, csrc/burst_kernels.hip, csrc/burst_seg_kernels.hip, and csrc/vlad_kernels.hip behind hard + off) write,
+(csrc/soft_vlad_kernels.hip, csrc/burst_kernels.hip, csrc/burst_seg_kernels.hip, and csrc/assign_kernels.hip + csrc/vlad_kernels.hip
+behind hard + off) write,
 recorded once at the commit before their shared headers (csrc/mfma_f32_dev.h, csrc/gram_tile_dev.h, csrc/weighted_agg_dev.h) were
 split out.  These kernels sum in one fixed order, so a refactor of them is held to the recorded bytes, not to a tolerance.
 

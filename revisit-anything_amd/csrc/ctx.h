@@ -575,7 +575,29 @@ int sv_launch_l2_filter(segvlad_ctx* ctx, const float* Q, const float* R, int M,
                         const float* rn, int b_stride, const float* thr, int64_t thr_ld, uint32_t* cand_cnt,
                         float* cand_d2, uint32_t* cand_id, int cap);
 
-// knn_filter_kernels.hip
+// knn_filter_kernels.hip (the fp16 filter; sv_choose_f16_kernel and sv_f16_eps_kblock, declared with the options above, live there too)
+int sv_launch_f16_filter(segvlad_ctx* ctx, const uint16_t* Qh, const uint16_t* Rh, int M, int n_sample, int d, int b_stride,
+                         float inv_scale, const float* qn, const float* rn, const float* thr, int64_t thr_ld, float eps_mult,
+                         float c_eps, float rn_max, uint32_t* cand_cnt, float* cand_d2, uint32_t* cand_id, int cap, int skip = 0);
+// skip = 16: the operand rows are the database rows that are NOT multiples of 16, in order (n_sample of them; b_stride = 1)
+bool sv_f16_filter_skip_ok(const segvlad_ctx* ctx, int M, int64_t n_rows, int d);
+// knn_operand_kernels.hip (the filters' operand planes and the scalars a search reads back)
+int sv_launch_to_f16(segvlad_ctx* ctx, const float* X, int64_t n_elems, float scale, uint16_t* out);
+// single-image searches: the query plane and its scales without a host round trip (scales_dev[0] = query scale,
+// [1] = 1 / (query scale x db_scale)); ctx->f16_scale_dev != null makes the filter kernel read [1] instead of its argument
+// qn_out != null (needs d % 4 == 0, 16-byte aligned rows): also the rows' squared norms, bit for bit sv_launch_row_sumsq's
+int sv_launch_query_f16_small(segvlad_ctx* ctx, const float* X, int64_t n_elems, float db_scale, uint16_t* out, float* scales_dev,
+                              float* qn_out, int nq, int d, uint32_t* zero, int zero_words);
+int sv_launch_to_f16_devscale(segvlad_ctx* ctx, const float* X, int64_t n_elems, const float* scales_dev, uint16_t* out);
+int sv_row_norm_max(segvlad_ctx* ctx, const float* norms, int64_t n, float* out_host, bool finite_only = false);
+int sv_row_norm_min(segvlad_ctx* ctx, const float* norms, int64_t n, float* out_host);
+int sv_maxabs(segvlad_ctx* ctx, const float* x, int64_t n, float* out_host, bool finite_only = false, bool* nonfinite_host = nullptr);
+int sv_ensure_pinned_words(segvlad_ctx* ctx);
+int sv_maxabs_and_norm_min_begin(segvlad_ctx* ctx, const float* x, int64_t n, const float* norms, int64_t n_norms);
+// (the scalars over the finite values alone; *nonfinite_host: x holds a NaN or an Inf; *norm_max_host: the largest finite norm)
+int sv_maxabs_and_norm_min_end(segvlad_ctx* ctx, int64_t n, int64_t n_norms, float* maxabs_host, float* norm_min_host, bool* nonfinite_host,
+                               float* norm_max_host);
+// knn_bf16_filter_kernels.hip
 int sv_launch_split_bf16(segvlad_ctx* ctx, const float* X, int64_t n_elems, uint16_t* hi, uint16_t* lo);
 int sv_launch_bf16_filter(segvlad_ctx* ctx, const uint16_t* Qh, const uint16_t* Ql, const uint16_t* Rh, const uint16_t* Rl,
                           int M, int n_sample, int d, int b_stride, const float* qn, const float* rn, const float* thr,
@@ -646,7 +668,6 @@ int sv_refine_small_repair(segvlad_ctx* ctx);
 int sv_launch_small_tail(segvlad_ctx* ctx, const float* Q, const float* R, const float* qn, const float* rn, int64_t n, int d, int m, int k,
                          uint32_t* fail_rows, uint32_t* fail_count, uint32_t* rovf_rows, const float* ref_lim, const uint32_t* cand_cnt,
                          const float* cand_d2, const uint32_t* cand_id, int cap, float* d2_out, int64_t* idx_out, uint32_t* stats);
-int sv_ensure_pinned_words(segvlad_ctx* ctx);
 // the HEAD of such a pass in one launch: the queries' fp16 plane (scales_dev[0] = scale, [1] = 1 / (scale x db_scale)), their squared
 // norms (row_sumsq's bits), the zeroed flag block, and thr_out[q] = the rank-th smallest APPROXIMATE distance (the filter's own fp16
 // product) of query q to the n0 sample rows 0, stride, 2 stride, ... of the fp16 plane Rh; cand_cnt[q] = 0.
@@ -665,13 +686,6 @@ int sv_launch_refine_grouped(segvlad_ctx* ctx, const float* Q, const float* R, i
                              const uint32_t* ref_cnt, const uint32_t* ref_id, int rcap, int k, float* d2_out, int64_t* idx_out,
                              int* launches, const uint32_t* only_rows = nullptr, int live_groups_hint = 0);
 int sv_refine_group_stats(segvlad_ctx* ctx, int nq, int64_t* groups, int64_t* grouped, int64_t* union_sum);
-int sv_row_norm_max(segvlad_ctx* ctx, const float* norms, int64_t n, float* out_host, bool finite_only = false);
-int sv_row_norm_min(segvlad_ctx* ctx, const float* norms, int64_t n, float* out_host);
-int sv_maxabs(segvlad_ctx* ctx, const float* x, int64_t n, float* out_host, bool finite_only = false, bool* nonfinite_host = nullptr);
-int sv_maxabs_and_norm_min_begin(segvlad_ctx* ctx, const float* x, int64_t n, const float* norms, int64_t n_norms);
-// (the scalars over the finite values alone; *nonfinite_host: x holds a NaN or an Inf; *norm_max_host: the largest finite norm)
-int sv_maxabs_and_norm_min_end(segvlad_ctx* ctx, int64_t n, int64_t n_norms, float* maxabs_host, float* norm_min_host, bool* nonfinite_host,
-                               float* norm_max_host);
 // gemm_f16x3_kernels.hip
 int sv_launch_split_f16x2(segvlad_ctx* ctx, const float* X, int64_t n_rows, int d, const float* sub, float scale, uint16_t* h1,
                           uint16_t* h2);
@@ -688,18 +702,6 @@ int sv_launch_project_aggregate(segvlad_ctx* ctx, const float* Z, const float* w
                                 const uint64_t* colmask, const int32_t* lab_off, const int32_t* rowbase, const int32_t* phys,
                                 const int32_t* seg_off_dev, int B, int N, int K, int P, int SC, int S_max, const float* col_scale,
                                 float* Y, float zscale, int z_pairs, int64_t zero_row);
-int sv_launch_to_f16(segvlad_ctx* ctx, const float* X, int64_t n_elems, float scale, uint16_t* out);
-// single-image searches: the query plane and its scales without a host round trip (scales_dev[0] = query scale,
-// [1] = 1 / (query scale x db_scale)); ctx->f16_scale_dev != null makes the filter kernel read [1] instead of its argument
-// qn_out != null (needs d % 4 == 0, 16-byte aligned rows): also the rows' squared norms, bit for bit sv_launch_row_sumsq's
-int sv_launch_query_f16_small(segvlad_ctx* ctx, const float* X, int64_t n_elems, float db_scale, uint16_t* out, float* scales_dev,
-                              float* qn_out, int nq, int d, uint32_t* zero, int zero_words);
-int sv_launch_to_f16_devscale(segvlad_ctx* ctx, const float* X, int64_t n_elems, const float* scales_dev, uint16_t* out);
-int sv_launch_f16_filter(segvlad_ctx* ctx, const uint16_t* Qh, const uint16_t* Rh, int M, int n_sample, int d, int b_stride,
-                         float inv_scale, const float* qn, const float* rn, const float* thr, int64_t thr_ld, float eps_mult,
-                         float c_eps, float rn_max, uint32_t* cand_cnt, float* cand_d2, uint32_t* cand_id, int cap, int skip = 0);
-// skip = 16: the operand rows are the database rows that are NOT multiples of 16, in order (n_sample of them; b_stride = 1)
-bool sv_f16_filter_skip_ok(const segvlad_ctx* ctx, int M, int64_t n_rows, int d);
 
 // select_kernels.hip
 // top-k of per-query candidate lists (LDS sort on (distance, id)); a list longer than cap flags its query row in

@@ -1,4 +1,4 @@
-// Exact kNN, large-database path: what happens to the candidate lists the 16-bit filters (knn_filter_kernels.hip) leave behind.
+// Exact kNN, large-database path: what happens to the candidate lists the 16-bit filters (knn_filter_kernels.hip, knn_bf16_filter_kernels.hip) leave behind.
 //   select_approx_kernel     per query: sort candidates by d2~; intermediate level: A_k (k-th smallest);
 //                            last level: the refine list {d2~ <= A_k + 2 eps}
 //   refine_exact_kernel      per query: exact fp32 distances of the refine list (the SAME sequential fp32 fma chain as the

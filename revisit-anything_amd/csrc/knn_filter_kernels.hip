@@ -1,491 +1,25 @@
-// Exact kNN, large-database path: 16-bit MFMA candidate FILTERS + exact fp32 refinement (gfx950).
-// (This file was knn_bf16_kernels.hip until round 6: it started as the bf16x3 filter below; the default filter since round 2 is the
-//  single-product fp16 kernel knn_f16_filter_kernel further down, the bf16x3 form serves d % 64 != 0.)
+// Exact kNN, large-database path: the fp16 candidate FILTER, the default filter of segvlad_search (gfx950).
 //
-// fp32 MFMA runs at 1/16 of the bf16 rate on CDNA4.  Every fp32 value is split into two bf16 pieces
-// x = hi + lo + e, |e| <= 2^-16 |x|, and the filter GEMM accumulates hi.hi + hi.lo + lo.hi on
-// v_mfma_f32_32x32x16_bf16 (products of two bf16 are exact in fp32).  The result differs from the fp32
-// fma-chain value of the exact path by at most
-//        |dot~ - dot| <= (3*2^-16 + 4*d*2^-24) * ||q|| * ||r||         (dropped terms + accumulation)
-// so a candidate filter with that margin can never drop a true neighbour.  The filter's survivors
-// (about k per query after the threshold levels) are then re-evaluated with the SAME sequential fp32
-// fma chain as the matrix path (gemm_nt_kernel<1>), sorted by (distance, id) and emitted: the final
-// distances and ids are bit-identical to the all-fp32 path.
-//
-//   split_bf16_kernel        fp32 [n][d] -> hi, lo bf16 planes
-//   knn_bf16_filter_kernel   128x128x32 tiles, 4 waves x (2x2) 32x32x16 MFMA tiles x 3 products;
-//                            16-B coalesced global loads -> registers -> XOR-swizzled LDS (conflict-free
-//                            ds_read_b128 fragments), double-buffered LDS, two register stages in flight;
-//                            epilogue appends (d2~, id) with d2~ <= thr + margin to the candidate lists
-//   knn_f16_filter_kernel    the default filter: one fp16 product, one configuration type per kernel the library holds,
-//                            sv_choose_f16_kernel picks one per launch
-// (select_approx_kernel, refine_exact_kernel and the single-image forms of both: knn_candidate_kernels.hip)
-#include <stdlib.h>
-
+//   knn_f16_filter_kernel<C>  one fp16 MFMA product per fp32 fma; one configuration type C per kernel the library holds (F16BatchDefault,
+//                             F16DeepFlush, ...: 14, and three probes in the development build)
+//   launch_f16_filter<C>      its launch: the walk's geometry from f16_walk.h, the LDS bytes from F16Lds<C>, the flush scratch
+//   sv_choose_f16_kernel      which kernel a launch takes: the ONE place that knows the rule; f16_with_config maps the choice to its type
+//   sv_launch_f16_filter      the entry; sv_f16_filter_skip_ok and sv_f16_eps_kblock ask the same rule
+// (operand planes and scales: knn_operand_kernels.hip; the bf16x3 filter for d % 64 != 0: knn_bf16_filter_kernels.hip; what happens to the
+//  candidate lists: knn_candidate_kernels.hip)
 #include <stdio.h>
 
 #include "ctx.h"
+#include "f16_walk.h"
 #include "knn_dev.h"
+#include "mfma_f32_dev.h"
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
-// ---- fp32 -> (hi, lo) bf16, round-to-nearest-even ---------------------------------------------------
-__device__ __forceinline__ uint16_t bf16_rne(float x) {
-  uint32_t u = __float_as_uint(x);
-  u += 0x7fffu + ((u >> 16) & 1u);
-  return (uint16_t)(u >> 16);
-}
-__device__ __forceinline__ float bf16_to_f32(uint16_t h) { return __uint_as_float((uint32_t)h << 16); }
-
-__global__ __launch_bounds__(256) void split_bf16_kernel(const float* __restrict__ X, int64_t n4, uint16_t* __restrict__ hi,
-                                                         uint16_t* __restrict__ lo) {
-  for (int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x; j < n4; j += (int64_t)gridDim.x * 256) {
-    const float4 v = reinterpret_cast<const float4*>(X)[j];
-    const float f[4] = {v.x, v.y, v.z, v.w};
-    uint16_t h[4], l[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      h[e] = bf16_rne(f[e]);
-      l[e] = bf16_rne(f[e] - bf16_to_f32(h[e]));
-    }
-    reinterpret_cast<uint2*>(hi)[j] = make_uint2((uint32_t)h[0] | ((uint32_t)h[1] << 16), (uint32_t)h[2] | ((uint32_t)h[3] << 16));
-    reinterpret_cast<uint2*>(lo)[j] = make_uint2((uint32_t)l[0] | ((uint32_t)l[1] << 16), (uint32_t)l[2] | ((uint32_t)l[3] << 16));
-  }
-}
-
-int sv_launch_split_bf16(segvlad_ctx* ctx, const float* X, int64_t n_elems, uint16_t* hi, uint16_t* lo) {
-  if (n_elems <= 0) return SEGVLAD_OK;
-  const int64_t n4 = n_elems / 4;  // callers guarantee d % 8 == 0
-  int64_t blocks = (n4 + 255) / 256;
-  if (blocks > 8192) blocks = 8192;
-  hipLaunchKernelGGL(split_bf16_kernel, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, X, n4, hi, lo);
-  SV_HIP(hipGetLastError());
-  return SEGVLAD_OK;
-}
-
-// ---- filter GEMM ---------------------------------------------------------------------------------------
-// Tile BM x BN x 32 (32 bf16 = 64 B = 4 chunks of 16 B per row and plane); WM x WN waves, each wave TM x TN
-// MFMA tiles of 32x32.  Instantiated as 128x128 with 2x2 waves (2 workgroups per CU); a 256x256 variant
-// measured the same time (the kernel is bound by HBM latency of the streamed DB operand, not by L2->LDS
-// bandwidth), so the prefetch depth, not the tile, is the lever.
-constexpr int FBK = 32;
-
-// physical chunk of logical chunk c in row r: spreads a 16-lane ds_read_b128 group over all 16 slots
-__device__ __forceinline__ int swz(int r, int c) { return c ^ ((r >> 2) & 3); }
-
-#define MFMA_BF16(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_bf16((a), (b), (c), 0, 0, 0)
-
-// Register stages: two 16-B loads per thread and plane in both tile configurations; THREE named stage sets
-// rotate so that every k-tile's global loads are issued three k-tiles before they are written to LDS (the DB
-// operand streams from HBM with ~2 us latency while a k-tile of bf16 MFMAs lasts only ~0.4-0.7 us).
-// Named locals + macros: a struct or indexed array here is not promoted to registers by hipcc 7.2.
-#define F_DECL(X) uint4 gah0##X, gah1##X, gal0##X, gal1##X, gbh0##X, gbh1##X, gbl0##X, gbl1##X
-#define F_GLOAD(X, k0_)                                                          \
-  do {                                                                           \
-    const int64_t ko_ = (int64_t)(k0_) + 8 * (tid & 3);                          \
-    gah0##X = *reinterpret_cast<const uint4*>(Qh + qa0 * d + ko_);               \
-    gah1##X = *reinterpret_cast<const uint4*>(Qh + qa1 * d + ko_);               \
-    gal0##X = *reinterpret_cast<const uint4*>(Ql + qa0 * d + ko_);               \
-    gal1##X = *reinterpret_cast<const uint4*>(Ql + qa1 * d + ko_);               \
-    gbh0##X = *reinterpret_cast<const uint4*>(Rh + rb0 * ldb + ko_);             \
-    gbh1##X = *reinterpret_cast<const uint4*>(Rh + rb1 * ldb + ko_);             \
-    gbl0##X = *reinterpret_cast<const uint4*>(Rl + rb0 * ldb + ko_);             \
-    gbl1##X = *reinterpret_cast<const uint4*>(Rl + rb1 * ldb + ko_);             \
-  } while (0)
-
-#define F_SSTORE(X, S_)                                                          \
-  do {                                                                           \
-    unsigned char* s_ = (S_);                                                    \
-    *reinterpret_cast<uint4*>(s_ + so0) = gah0##X;                               \
-    *reinterpret_cast<uint4*>(s_ + so1) = gah1##X;                               \
-    *reinterpret_cast<uint4*>(s_ + PA + so0) = gal0##X;                          \
-    *reinterpret_cast<uint4*>(s_ + PA + so1) = gal1##X;                          \
-    *reinterpret_cast<uint4*>(s_ + 2 * PA + so0) = gbh0##X;                      \
-    *reinterpret_cast<uint4*>(s_ + 2 * PA + so1) = gbh1##X;                      \
-    *reinterpret_cast<uint4*>(s_ + 2 * PA + PB + so0) = gbl0##X;                 \
-    *reinterpret_cast<uint4*>(s_ + 2 * PA + PB + so1) = gbl1##X;                 \
-  } while (0)
-
-template <int BM, int BN, int WM, int WN, int DEPTH>
-__global__ __launch_bounds__(64 * WM * WN, 2) void knn_bf16_filter_kernel(
-    const uint16_t* __restrict__ Qh, const uint16_t* __restrict__ Ql, const uint16_t* __restrict__ Rh,
-    const uint16_t* __restrict__ Rl, int M, int N, int d, int b_stride, int tiles_m, const float* __restrict__ qn,
-    const float* __restrict__ rn, const float* __restrict__ thr, int64_t thr_ld, float eps_mult, float c_eps, float rn_max,
-    uint32_t* __restrict__ cand_cnt, float* __restrict__ cand_d2, uint32_t* __restrict__ cand_id, int cap) {
-  constexpr int T = 64 * WM * WN;
-  constexpr int TM = BM / (32 * WM), TN = BN / (32 * WN);  // MFMA tiles per wave
-  constexpr int LA = BM * 4 / T, LB = BN * 4 / T;          // 16-B loads per thread, plane and k-tile
-  constexpr int PA = BM * 64, PB = BN * 64;                // plane bytes
-  constexpr int STAGE = 2 * PA + 2 * PB;                   // Ah, Al, Bh, Bl
-  extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
-  const int tile = blockIdx.x;
-  const int tm = tile % tiles_m, tn = tile / tiles_m;
-  const int64_t m0 = (int64_t)tm * BM, n0 = (int64_t)tn * BN;
-  const int tid = threadIdx.x, w = tid >> 6, l = tid & 63, i = l & 31, kk = l >> 5;
-  const int wm = w / WN, wn = w % WN;
-  const int64_t ldb = (int64_t)d * b_stride;
-  const int ntiles = d / FBK;
-
-  f32x16 acc[TM][TN];
-#pragma unroll
-  for (int a = 0; a < TM; ++a)
-#pragma unroll
-    for (int b = 0; b < TN; ++b)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
-
-  static_assert(LA == 2 && LB == 2, "two 16-B loads per thread and plane");
-  F_DECL(A);
-  F_DECL(B);
-  F_DECL(C);
-  const int lr0 = tid >> 2, lr1 = lr0 + T / 4;
-  // clamp: rows beyond the edge are loaded from the last valid row and never emitted
-  const int64_t qa0 = (m0 + lr0 < M) ? (m0 + lr0) : (M - 1), qa1 = (m0 + lr1 < M) ? (m0 + lr1) : (M - 1);
-  const int64_t rb0 = (n0 + lr0 < N) ? (n0 + lr0) : (N - 1), rb1 = (n0 + lr1 < N) ? (n0 + lr1) : (N - 1);
-  const int so0 = lr0 * 64 + swz(lr0, tid & 3) * 16, so1 = lr1 * 64 + swz(lr1, tid & 3) * 16;
-  F_GLOAD(A, 0);
-  F_SSTORE(A, lds);
-  if (ntiles > 1) F_GLOAD(A, FBK);
-  if (DEPTH == 3) {
-    if (ntiles > 2) F_GLOAD(B, 2 * FBK);
-    if (ntiles > 3) F_GLOAD(C, 3 * FBK);
-  }
-  __syncthreads();
-  int cur = 0;
-  const int fa0 = wm * (32 * TM) + i, fb0 = wn * (32 * TN) + i;
-  // multiply k-tile `kt` out of LDS buffer `cur`
-  auto compute = [&]() {
-    const unsigned char* S = lds + cur * STAGE;
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      const int cl = 2 * ks + kk;  // logical 16-B chunk (8 consecutive k) of this lane
-      bf16x8 ah[TM], al[TM], bh[TN], bl[TN];
-#pragma unroll
-      for (int t = 0; t < TM; ++t) {
-        const int ra = fa0 + 32 * t;
-        ah[t] = *reinterpret_cast<const bf16x8*>(S + ra * 64 + swz(ra, cl) * 16);
-        al[t] = *reinterpret_cast<const bf16x8*>(S + PA + ra * 64 + swz(ra, cl) * 16);
-      }
-#pragma unroll
-      for (int t = 0; t < TN; ++t) {
-        const int rb = fb0 + 32 * t;
-        bh[t] = *reinterpret_cast<const bf16x8*>(S + 2 * PA + rb * 64 + swz(rb, cl) * 16);
-        bl[t] = *reinterpret_cast<const bf16x8*>(S + 2 * PA + PB + rb * 64 + swz(rb, cl) * 16);
-      }
-      // three products per accumulator, small terms first; the TM*TN accumulators are independent, so
-      // consecutive MFMAs never wait on each other
-#pragma unroll
-      for (int mt = 0; mt < TM; ++mt)
-#pragma unroll
-        for (int nt = 0; nt < TN; ++nt) acc[mt][nt] = MFMA_BF16(al[mt], bh[nt], acc[mt][nt]);
-#pragma unroll
-      for (int mt = 0; mt < TM; ++mt)
-#pragma unroll
-        for (int nt = 0; nt < TN; ++nt) acc[mt][nt] = MFMA_BF16(ah[mt], bl[nt], acc[mt][nt]);
-#pragma unroll
-      for (int mt = 0; mt < TM; ++mt)
-#pragma unroll
-        for (int nt = 0; nt < TN; ++nt) acc[mt][nt] = MFMA_BF16(ah[mt], bh[nt], acc[mt][nt]);
-    }
-  };
-  // iteration kt: compute tile kt; write stage X (tile kt+1, loaded three k-tiles ago) to the other buffer;
-  // barrier; refill X with tile kt+4
-#define F_STEP(X)                                                     \
-  do {                                                                \
-    compute();                                                        \
-    if (kt + 1 < ntiles) F_SSTORE(X, lds + (cur ^ 1) * STAGE);        \
-    __syncthreads();                                                  \
-    if (kt + 4 < ntiles) F_GLOAD(X, (kt + 4) * FBK);                  \
-    cur ^= 1;                                                         \
-    ++kt;                                                             \
-  } while (0)
-  int kt = 0;
-  if (DEPTH == 3) {
-    while (kt < ntiles) {
-      F_STEP(A);
-      if (kt >= ntiles) break;
-      F_STEP(B);
-      if (kt >= ntiles) break;
-      F_STEP(C);
-    }
-  } else {
-    for (; kt < ntiles; ++kt) {
-      compute();
-      if (kt + 1 < ntiles) F_SSTORE(A, lds + (cur ^ 1) * STAGE);
-      __syncthreads();
-      if (kt + 2 < ntiles) F_GLOAD(A, (kt + 2) * FBK);
-      cur ^= 1;
-    }
-  }
-#undef F_STEP
-
-  // ---- epilogue: d2~ = (||q||^2 + ||r||^2) - 2 dot~ ; keep d2~ <= thr + eps_mult * eps(q) -----------------
-#pragma unroll
-  for (int nt = 0; nt < TN; ++nt) {
-    const int64_t col = n0 + wn * (32 * TN) + nt * 32 + i;
-    if (col >= N) continue;
-    const float cn = rn[col * b_stride];
-#pragma unroll
-    for (int mt = 0; mt < TM; ++mt) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int64_t row = m0 + wm * (32 * TM) + mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * kk;
-        if (row < M) {
-          const float q2 = qn[row];
-          const float v = sv_d2_screen(q2, cn, acc[mt][nt][r]);
-          const float lim = thr[row * thr_ld] + eps_mult * c_eps * sqrtf(q2 * rn_max);
-          if (v <= lim) {
-            const uint32_t slot = atomicAdd(&cand_cnt[row], 1u);
-            if (slot < (uint32_t)cap) {
-              cand_d2[row * cap + slot] = v;
-              cand_id[row * cap + slot] = (uint32_t)(col * b_stride);
-            }
-          }
-        }
-      }
-    }
-  }
-}
-
-template <int BM, int BN, int WM, int WN, int DEPTH>
-static int launch_filter(segvlad_ctx* ctx, const uint16_t* Qh, const uint16_t* Ql, const uint16_t* Rh, const uint16_t* Rl,
-                         int M, int n_sample, int d, int b_stride, const float* qn, const float* rn, const float* thr,
-                         int64_t thr_ld, float eps_mult, float c_eps, float rn_max, uint32_t* cand_cnt, float* cand_d2,
-                         uint32_t* cand_id, int cap) {
-  const int tiles_m = (M + BM - 1) / BM, tiles_n = (n_sample + BN - 1) / BN;
-  const int64_t tiles = (int64_t)tiles_m * tiles_n;
-  if (tiles > 0x7fffffffLL) return ctx->fail(SEGVLAD_ERR_LIMIT, "bf16 filter: too many tiles");
-  const size_t lds = 2 * (size_t)(2 * BM * 64 + 2 * BN * 64);
-  auto kern = knn_bf16_filter_kernel<BM, BN, WM, WN, DEPTH>;
-  if (lds > 64 * 1024)
-    SV_HIP(sv_max_dyn_lds(reinterpret_cast<const void*>(kern), (size_t)lds));
-  hipLaunchKernelGGL(kern, dim3((unsigned)tiles), dim3(64 * WM * WN), lds, ctx->stream, Qh, Ql, Rh, Rl, M, n_sample, d, b_stride,
-                     tiles_m, qn, rn, thr, thr_ld, eps_mult, c_eps, rn_max, cand_cnt, cand_d2, cand_id, cap);
-  SV_HIP(hipGetLastError());
-  return SEGVLAD_OK;
-}
-
-int sv_launch_bf16_filter(segvlad_ctx* ctx, const uint16_t* Qh, const uint16_t* Ql, const uint16_t* Rh, const uint16_t* Rl,
-                          int M, int n_sample, int d, int b_stride, const float* qn, const float* rn, const float* thr,
-                          int64_t thr_ld, float eps_mult, float c_eps, float rn_max, uint32_t* cand_cnt, float* cand_d2,
-                          uint32_t* cand_id, int cap) {
-  if (M <= 0 || n_sample <= 0) return SEGVLAD_OK;
-  return launch_filter<128, 128, 2, 2, 1>(ctx, Qh, Ql, Rh, Rl, M, n_sample, d, b_stride, qn, rn, thr, thr_ld, eps_mult, c_eps, rn_max,
-                                          cand_cnt, cand_d2, cand_id, cap);
-}
-
-// ---- fp16 single-product filter ----------------------------------------------------------------------------
 // One fp16 MFMA product per fp32 fma: x~ = fl16(s * x) with a power-of-two scale s (exact), products of two
 // fp16 are exact in fp32, so   |dot~ - dot| <= (2^-10 + 2^-22 + 2 d 2^-24) ||q|| ||r||   against the fp32 chain.
 // The margin is ~24x wider than bf16x3's, which lets ~1.3-1.4x more candidates through (they are cheap: the
 // exact refinement only sees the ~k survivors) for one third of the MFMA work.
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4v __attribute__((ext_vector_type(4)));
 #define MFMA_F16(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_f16((a), (b), (c), 0, 0, 0)
-
-// max |x| of a block of floats.  16-byte loads where the pointer allows, ONE atomic per workgroup: the first version's 4-byte
-// loads and one atomicMax per WAVE (16 384 of them on one word for a 10 000 x 1024 query batch) took 190 us in front of every
-// batch search (round 5 kernel trace) for 41 MB -- 10 us of reading.
-// FINITE_ONLY: NaN and Inf entries do not count (their |x| bit patterns sort above every finite value's): the maximum a
-// power-of-two scale is derived from must not be taken over by one bad row (segvlad_pca_apply, the index and the queries of
-// segvlad_search).  FLAG (with FINITE_ONLY): out[2] is raised when such an entry was seen.
-template <bool FINITE_ONLY, bool FLAG = false>
-__global__ __launch_bounds__(256) void maxabs_kernel(const float* __restrict__ x, int64_t n, uint32_t* __restrict__ out) {
-  __shared__ uint32_t wmax[4];
-  uint32_t m = 0, bad = 0;
-  auto mag = [&bad](uint32_t u) -> uint32_t {
-    u &= 0x7fffffffu;
-    if (FLAG) bad |= (uint32_t)(u >= 0x7f800000u);
-    return (FINITE_ONLY && u >= 0x7f800000u) ? 0u : u;
-  };
-  const int64_t tid = (int64_t)blockIdx.x * 256 + threadIdx.x, nth = (int64_t)gridDim.x * 256;
-  int64_t head = 0;   // elements in front of the first 16-byte boundary
-  if ((reinterpret_cast<uintptr_t>(x) & 15) != 0) head = min<int64_t>(n, (int64_t)((16 - (reinterpret_cast<uintptr_t>(x) & 15)) >> 2));
-  const int64_t n4 = (n - head) >> 2;
-  const uint4* x4 = reinterpret_cast<const uint4*>(x + head);
-  for (int64_t j = tid; j < n4; j += nth) {
-    const uint4 v = x4[j];
-    m = max(max(m, mag(v.x)), max(max(mag(v.y), mag(v.z)), mag(v.w)));  // |x| bit pattern orders like the value
-  }
-  if (tid < head) m = max(m, mag(__float_as_uint(x[tid])));
-  const int64_t tail0 = head + 4 * n4;
-  if (tid < n - tail0) m = max(m, mag(__float_as_uint(x[tail0 + tid])));
-  for (int o = 32; o > 0; o >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, o));
-  if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = m;
-  __syncthreads();
-  if (threadIdx.x == 0) atomicMax(out, max(max(wmax[0], wmax[1]), max(wmax[2], wmax[3])));
-  if (FLAG && __ballot(bad != 0u) != 0ull && (threadIdx.x & 63) == 0) atomicOr(out + 2, 1u);
-}
-
-// nonfinite_host != null (finite_only): set when the block holds a NaN or an Inf
-int sv_maxabs(segvlad_ctx* ctx, const float* x, int64_t n, float* out_host, bool finite_only, bool* nonfinite_host) {
-  SV_HIP(ctx->s_minmax.reserve(32));
-  uint32_t* mm = ctx->s_minmax.as<uint32_t>() + 4;   // [4] = max |x| bits, [6] = the non-finite flag
-  SV_HIP(hipMemsetAsync(mm, 0, 12, ctx->stream));
-  int64_t blocks = (n + 1023) / 1024;
-  if (blocks > 1024) blocks = 1024;
-  if (n > 0 && finite_only && nonfinite_host)
-    hipLaunchKernelGGL((maxabs_kernel<true, true>), dim3((unsigned)blocks), dim3(256), 0, ctx->stream, x, n, mm);
-  else if (n > 0 && finite_only)
-    hipLaunchKernelGGL(maxabs_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, x, n, mm);
-  else if (n > 0)
-    hipLaunchKernelGGL(maxabs_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, x, n, mm);
-  uint32_t u[3] = {0, 0, 0};
-  SV_HIP(hipMemcpyAsync(u, mm, 12, hipMemcpyDeviceToHost, ctx->stream));
-  SV_HIP(hipStreamSynchronize(ctx->stream));
-  float f;
-  memcpy(&f, &u[0], 4);
-  *out_host = f;
-  if (nonfinite_host) *nonfinite_host = u[2] != 0u;
-  return SEGVLAD_OK;
-}
-
-__global__ __launch_bounds__(256) void to_f16_kernel(const float* __restrict__ X, int64_t n4, float scale,
-                                                     _Float16* __restrict__ out) {
-  for (int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x; j < n4; j += (int64_t)gridDim.x * 256) {
-    const float4 v = reinterpret_cast<const float4*>(X)[j];
-    typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-    h4 h;
-    h[0] = (_Float16)(v.x * scale);  // round-to-nearest-even conversion
-    h[1] = (_Float16)(v.y * scale);
-    h[2] = (_Float16)(v.z * scale);
-    h[3] = (_Float16)(v.w * scale);
-    reinterpret_cast<h4*>(out)[j] = h;
-  }
-}
-
-// A handful of query rows (<= 128 x d floats): largest magnitude, the power-of-two scale that puts it in [8192, 16384) --
-// the host's pow2_scale, bit for bit -- and the fp16 plane, in ONE workgroup and one launch; the scales stay on the device
-// (scales[0] = query scale, scales[1] = 1 / (query scale x db_scale)): no memset, no atomics, no host round trip.
-// qn_out != null: the rows' squared norms as well (one wave per row, 16 rows in flight: the arithmetic of row_sumsq_kernel,
-// gemm_kernels.hip, operation for operation -- lane j sums the squares of float4 j, j + 64, ... with fmaf, then the xor
-// butterfly -- so that the single-image pass sees the very bits the batch path computes), instead of a launch of its own in
-// front of this one.
-__global__ __launch_bounds__(1024) void query_f16_small_kernel(const float* __restrict__ X, int64_t n4, float db_scale,
-                                                               _Float16* __restrict__ out, float* __restrict__ scales,
-                                                               float* __restrict__ qn_out, int nq, int d,
-                                                               uint32_t* __restrict__ zero, int zero_words) {
-  __shared__ uint32_t wmax[16];
-  __shared__ uint32_t badrow[128];   // (nq <= 128)
-  __shared__ float s_scale;
-  const int tid = threadIdx.x;
-  // the search's flag block, zeroed here instead of by a fill launch of its own in front of the pass's dependent chain
-  for (int j = tid; j < zero_words; j += 1024) zero[j] = 0u;
-  if (qn_out) {
-    const int lane = tid & 63;
-    for (int row = tid >> 6; row < nq; row += 16) {
-      const float4* x4 = reinterpret_cast<const float4*>(X + (int64_t)row * d);
-      float s = 0.f;
-      for (int j = lane; j < (d >> 2); j += 64) {
-        const float4 v = x4[j];
-        s = fmaf(v.x, v.x, s);
-        s = fmaf(v.y, v.y, s);
-        s = fmaf(v.z, v.z, s);
-        s = fmaf(v.w, v.w, s);
-      }
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-      if (lane == 0) qn_out[row] = s;
-    }
-  }
-  uint32_t m = 0;
-  for (int64_t j = tid; j < n4; j += 1024) {
-    const float4 v = reinterpret_cast<const float4*>(X)[j];
-    m = max(m, mag4_(v));
-  }
-  for (int o = 32; o > 0; o >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, o));
-  if ((tid & 63) == 0) wmax[tid >> 6] = m;
-  __syncthreads();
-  for (int w = 0; w < 16; ++w) m = max(m, wmax[w]);
-  if (m >= SV_BIG_BITS) {   // (uniform) a NaN, an Inf or a huge value: the maximum again, over the rows with a finite norm (knn_dev.h)
-    const int d4 = d >> 2;
-    for (int row = tid >> 6; row < nq; row += 16) {
-      const bool bad = row_norm_bad_(X + (int64_t)row * d, d4, tid & 63);
-      if ((tid & 63) == 0) badrow[row] = bad ? 1u : 0u;
-    }
-    __syncthreads();
-    m = 0;
-    for (int64_t j = tid; j < n4; j += 1024)
-      if (!badrow[j / d4]) m = max(m, mag4_(reinterpret_cast<const float4*>(X)[j]));
-    for (int o = 32; o > 0; o >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, o));
-    if ((tid & 63) == 0) wmax[tid >> 6] = m;
-    __syncthreads();
-  }
-  if (tid == 0) {
-    for (int w = 1; w < 16; ++w) m = max(m, wmax[w]);
-    const float maxabs = __uint_as_float(m);
-    float scale = 1.f;
-    if (maxabs > 0.f && isfinite(maxabs)) {
-      int e;
-      frexpf(maxabs, &e);
-      scale = ldexpf(1.f, 14 - e);
-    }
-    s_scale = scale;
-    scales[0] = scale;
-    scales[1] = 1.f / (scale * db_scale);
-  }
-  __syncthreads();
-  const float scale = s_scale;
-  for (int64_t j = tid; j < n4; j += 1024) {
-    const float4 v = reinterpret_cast<const float4*>(X)[j];
-    typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-    h4 h;
-    h[0] = (_Float16)(v.x * scale);
-    h[1] = (_Float16)(v.y * scale);
-    h[2] = (_Float16)(v.z * scale);
-    h[3] = (_Float16)(v.w * scale);
-    reinterpret_cast<h4*>(out)[j] = h;
-  }
-}
-
-int sv_launch_query_f16_small(segvlad_ctx* ctx, const float* X, int64_t n_elems, float db_scale, uint16_t* out, float* scales_dev,
-                              float* qn_out, int nq, int d, uint32_t* zero, int zero_words) {
-  hipLaunchKernelGGL(query_f16_small_kernel, dim3(1), dim3(1024), 0, ctx->stream, X, n_elems / 4, db_scale,
-                     reinterpret_cast<_Float16*>(out), scales_dev, qn_out, nq, d, zero, zero_words);
-  SV_HIP(hipGetLastError());
-  return SEGVLAD_OK;
-}
-
-__global__ __launch_bounds__(256) void to_f16_devscale_kernel(const float* __restrict__ X, int64_t n4, const float* __restrict__ scales,
-                                                              _Float16* __restrict__ out) {
-  const float scale = scales[0];
-  for (int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x; j < n4; j += (int64_t)gridDim.x * 256) {
-    const float4 v = reinterpret_cast<const float4*>(X)[j];
-    typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-    h4 h;
-    h[0] = (_Float16)(v.x * scale);
-    h[1] = (_Float16)(v.y * scale);
-    h[2] = (_Float16)(v.z * scale);
-    h[3] = (_Float16)(v.w * scale);
-    reinterpret_cast<h4*>(out)[j] = h;
-  }
-}
-
-int sv_launch_to_f16_devscale(segvlad_ctx* ctx, const float* X, int64_t n_elems, const float* scales_dev, uint16_t* out) {
-  if (n_elems <= 0) return SEGVLAD_OK;
-  const int64_t n4 = n_elems / 4;
-  int64_t blocks = (n4 + 255) / 256;
-  if (blocks > 8192) blocks = 8192;
-  hipLaunchKernelGGL(to_f16_devscale_kernel, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, X, n4, scales_dev,
-                     reinterpret_cast<_Float16*>(out));
-  SV_HIP(hipGetLastError());
-  return SEGVLAD_OK;
-}
-
-int sv_launch_to_f16(segvlad_ctx* ctx, const float* X, int64_t n_elems, float scale, uint16_t* out) {
-  if (n_elems <= 0) return SEGVLAD_OK;
-  const int64_t n4 = n_elems / 4;
-  int64_t blocks = (n4 + 255) / 256;
-  if (blocks > 8192) blocks = 8192;
-  hipLaunchKernelGGL(to_f16_kernel, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, X, n4, scale,
-                     reinterpret_cast<_Float16*>(out));
-  SV_HIP(hipGetLastError());
-  return SEGVLAD_OK;
-}
-
-typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
 
 // Operand tiles go global -> LDS directly (global_load_lds_dwordx4, no VGPR staging, no ds_write): one
 // wave-instruction fills 1 KiB of the LDS image, lane l landing at base + 16 l, i.e. RP = 1024 / row_bytes rows
@@ -564,7 +98,7 @@ typedef int sv_rsrc_t;
 // (every kernel: k-tiles of SV_F16_HBK = 64, SV_F16_NB = 3 database stages, wave tiles of 64 rows.  The variants that were
 //  measured on the way and not kept -- other tile shapes, 32-deep k-tiles, a software-pipelined loop, other DMA placements --
 //  are described in DESIGN.md 4 / 7 with their numbers.)
-constexpr int SV_F16_HBK = 64, SV_F16_NB = 3;
+constexpr int SV_F16_NB = 3;   // (SV_F16_HBK: f16_walk.h)
 struct F16BatchUnbiasedSmall {   // 8 waves of 64 x 128 on a 256 x 256 tile, ping-pong loop, 32 x 32 x 16 MFMA, workgroup-level epilogue
   static constexpr int BM = 256, BN = 256, WM = 4, WN = 2;
   static constexpr bool PERSIST = false;
@@ -610,6 +144,29 @@ struct F16ProbeNoEpilogueNoDma : F16BatchDefault { static constexpr int PROBE = 
 template <class C>
 constexpr int f16_kblock_of() { return (C::KBT > C::KFL ? C::KBT : C::KFL) * SV_F16_HBK; }
 
+
+// The launch contract of knn_f16_filter_kernel<C>: the LDS bytes of a workgroup, for the kernel's layout, its static_asserts and
+// launch_f16_filter.  Stages: two A stages (PA bytes each) + SV_F16_NB B stages (PB each); PERSIST: five equal slots (see a_off / b_off).
+// Epilogue scratch, over the stages of the finished tile (PERSIST: over slots 0 and 1 only, the next tile's head lands in the others):
+//   EPI = 0   [BM] row records (16 B) + [BM] counters + [BN] column norms + [BM] screening bounds + per wave a hit list of LCAP + 1
+//             records of 8 B (a quarter of the wave's elements at most)
+//   EPI = 1   per wave WSZ bytes: 1024 of row records, bounds and counters + a hit list of LCAPE + 1 records (see the epilogue)
+template <class C>
+struct F16Lds {
+  static constexpr int NW = C::WM * C::WN, TM = C::BM / (32 * C::WM), TN = C::BN / (32 * C::WN);
+  static constexpr int PA = C::BM * SV_F16_HBK * 2, PB = C::BN * SV_F16_HBK * 2;
+  static constexpr size_t STAGES = C::PERSIST ? 5 * (size_t)PA : 2 * (size_t)PA + (size_t)SV_F16_NB * PB;
+  static constexpr int LCAP = C::PERSIST ? 896 : ((TM * TN * 256 < 2048) ? TM * TN * 256 : 2048);
+  static constexpr int LCAPE = 864;
+  static constexpr int WSZ = (1024 + (LCAPE + 1) * 8 + 15) & ~15;
+  static constexpr size_t EPILOGUE = C::EPI == 1 ? (size_t)NW * WSZ : (size_t)C::BM * 24 + (size_t)C::BN * 4 + (size_t)NW * (LCAP + 1) * 8;
+  static constexpr size_t BYTES = STAGES > EPILOGUE ? STAGES : EPILOGUE;   // the launch's dynamic LDS
+  static_assert(!C::PERSIST || (PA == PB && STAGES <= 160 * 1024), "persistent layout: five equal slots");
+  static_assert(!C::PERSIST || EPILOGUE <= 2 * (size_t)PA, "epilogue scratch");   // (not PERSIST: the scratch overlays the stages; BYTES covers both)
+};
+// KFL: fp32 words of a wave's slice of the flush scratch (kscr: [workgroup][wave][128][64 lanes], one word per accumulator and lane)
+constexpr int SV_F16_KSCR_FLOATS = 128 * 64;
+
 template <class C>
 __global__ __launch_bounds__(64 * C::WM * C::WN) void knn_f16_filter_kernel(
     const uint16_t* __restrict__ Qh, const uint16_t* __restrict__ Rh, int M, int N, int d, int b_stride, int tiles_m, int gm,
@@ -635,14 +192,13 @@ __global__ __launch_bounds__(64 * C::WM * C::WN) void knn_f16_filter_kernel(
   constexpr int CH = RB / 16;            // 16-B chunks per row (8)
   constexpr int RP = 1024 / RB;          // rows per 1-KiB DMA piece
   constexpr int KS = HBK / 16;           // MFMA k-steps per tile
-  constexpr int PA = BM * RB, PB = BN * RB;
+  using L = F16Lds<C>;                   // the LDS bytes of the launch
+  constexpr int PA = L::PA, PB = L::PB;  // stage bytes
   constexpr int JA = BM / RP / NW, JB = BN / RP / NW;  // DMA pieces per wave and operand
   static_assert(JA * RP * NW == BM && JB * RP * NW == BN && (PP > 0 || (JA + JB) % (MF ? 2 : KS) == 0), "tile/wave geometry");
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   unsigned long long phase_t0 = PROBE == 1 ? __builtin_amdgcn_s_memtime() : 0ull;
-  // XCD-aware tile order.  Workgroup ids are dealt round-robin to the 8 XCDs (each with its own 4 MiB L2); the 32
-  // workgroups an XCD runs side by side form one gm x (32/gm) block of tiles, so that they share their query and
-  // database rows in that L2 while they march over k (tm-fastest order made every XCD fetch every database row).
+  // XCD-aware tile order: f16_walk.h.
   // PERSIST: 8 x 32 workgroups stay resident and walk their XCD's sequence 32 positions at a time; the head of the next
   // tile (A(0), B(0), B(1)) is requested before the epilogue of the current one, which hides the ~2 us a fresh
   // workgroup spends waiting for its first operands (6 % of the kernel: one workgroup per CU, nothing else covers it).
@@ -652,7 +208,7 @@ __global__ __launch_bounds__(64 * C::WM * C::WN) void knn_f16_filter_kernel(
   // KFL: this wave's slice of the flush scratch, as a scalar (wave-uniform) base address -- formed where it is used (a few SALU
   // instructions every 64 k-tiles) rather than kept live through the main loop
   auto kscr_base = [&]() -> float* {
-    const unsigned long long ka = (unsigned long long)(size_t)(kscr + ((size_t)blockIdx.x * NW + (size_t)w) * (128 * 64));
+    const unsigned long long ka = (unsigned long long)(size_t)(kscr + ((size_t)blockIdx.x * NW + (size_t)w) * SV_F16_KSCR_FLOATS);
     return reinterpret_cast<float*>((size_t)(((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(ka >> 32)) << 32) |
                                              (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)ka)));
   };
@@ -668,66 +224,10 @@ __global__ __launch_bounds__(64 * C::WM * C::WN) void knn_f16_filter_kernel(
   const int ntiles = d / HBK;
   const int tiles_n = (N + BN - 1) / BN;
   auto swz = [](int r, int c) { return c ^ ((r >> 1) & 7); };
-  // walk bit 0 ("query-block-resident"): an XCD keeps ONE block of gm query tiles while it steps through its share of the
-  // database blocks (blocks xcd, xcd + 8, ... -- the direction alternates from one query block to the next), instead of
-  // meeting a different query block at every step: the gm query tiles (gm x 512 KiB of fp16 rows at d = 1024) are then
-  // re-referenced by every step.  walk bit 1 ("serpentine k"): odd steps run their k-tiles from the END of the rows to the
-  // start.  Under an LRU-like L2 a cyclic re-reference of a working set larger than the cache (4 MiB of query tiles + 2 MiB
-  // of database tiles per step against 4 MiB of L2 per XCD) never hits; reversing the direction makes the most recently
-  // used half of the resident block hit (the filter's result does not depend on the accumulation order: the margin
-  // sv_f16_c_eps bounds ANY order).
-  auto tile_of = [&](int sq, int& tm_, int& tn_) -> bool {   // sq: position in this XCD's sequence
-    const int xcd = blockIdx.x & 7, within = sq & 31;
-    const int gn = 32 / gm, sm_cnt = (tiles_m + gm - 1) / gm;
-    if (walk & 1) {
-      // sn_cnt database blocks = 8 nbf + rem: every XCD sweeps nbf of them per query block; the sm_cnt x rem left-over
-      // (query block, database block) pairs are dealt round-robin to the XCDs at the end of the sequence (all of a query
-      // block's left-overs on XCD 0 would lengthen that XCD's sequence by sm_cnt steps: +0.7 % on the bench shape)
-      const int sn_cnt = (tiles_n + gn - 1) / gn, nbf = sn_cnt >> 3, rem = sn_cnt - 8 * nbf;
-      const int s_ = sq >> 5;
-      int qb, nb;
-      if (s_ < sm_cnt * nbf) {
-        qb = s_ / nbf;
-        int j = s_ - qb * nbf;
-        if (qb & 1) j = nbf - 1 - j;
-        nb = j * 8 + xcd;
-      } else {
-        const int idx = (s_ - sm_cnt * nbf) * 8 + xcd;
-        if (rem == 0 || idx >= sm_cnt * rem) return false;
-        qb = idx / rem;
-        nb = 8 * nbf + (idx - qb * rem);
-      }
-      tm_ = qb * gm + within % gm;
-      tn_ = nb * gn + within / gm;
-    } else {
-      const int st = (sq >> 5) * 8 + xcd;
-      tm_ = (st % sm_cnt) * gm + within % gm;
-      tn_ = (st / sm_cnt) * gn + within / gm;
-    }
-    return tm_ < tiles_m && tn_ < tiles_n;
-  };
-  // serpentine k: element offset of k-tile x of a step that runs backwards (wave-uniform)
-  // walk bit 2 ("rotated k start"): workgroup (i_m, i_n) of the XCD's gm x gn block starts its k-loop at k-tile
-  // (i_m ntiles / gm + i_n) mod ntiles and wraps around.  The gm workgroups that share a database tile (and the gn that share a
-  // query tile) otherwise ask for the same k-slice at the same moment: one L2 miss, everybody waiting out its HBM latency;
-  // rotated, a slice is fetched by the first workgroup that reaches it and is an L2 HIT for the others, one to two k-tiles
-  // later.  The k-order of a step: rot, rot + 1, ... (mod ntiles), or -- serpentine, odd steps -- rot - 1, rot - 2, ...: the
-  // reversed step starts on the slice the previous one ended on.  (rev_of packs both: bit 0 = reversed, bits 1.. = rot.)
-  auto rev_of = [&](int sq) -> int {
-    int rot = 0;
-    if (walk & 4) {
-      const int within = sq & 31, im = within % gm, in_ = within / gm;
-      rot = (im * (ntiles >= gm ? ntiles / gm : 1) + in_) % ntiles;
-    }
-    return 2 * rot + (((walk & 2) && ((sq >> 5) & 1)) ? 1 : 0);
-  };
-  auto kofs = [&](int rev_, int x) -> int {
-    const int rot = rev_ >> 1;
-    int i = (rev_ & 1) ? rot - 1 - x : rot + x;
-    if (i < 0) i += ntiles;
-    if (i >= ntiles) i -= ntiles;
-    return i * HBK;
-  };
+  // the walk (f16_walk.h) bound to this launch: the tile of position sq in this XCD's sequence, and the k-order of its step
+  auto tile_of = [&](int sq, int& tm_, int& tn_) -> bool { SV_F16_WALK_TILE_OF(sq, blockIdx.x & 7, tiles_m, tiles_n, gm, walk, tm_, tn_) };
+  auto rev_of = [&](int sq) -> int { return f16_walk_rev_of(sq, gm, ntiles, walk); };
+  auto kofs = [&](int rev_, int x) -> int { return f16_walk_kofs(rev_, x, ntiles); };
   int tm, tn;
   int seq = (int)(blockIdx.x >> 3);
   // PERSIST: resident workgroups per XCD = the stride of a workgroup through its XCD's sequence (bits 8.. of `walk`; 32 = one per
@@ -745,13 +245,21 @@ __global__ __launch_bounds__(64 * C::WM * C::WN) void knn_f16_filter_kernel(
   // LDS stages.  Plain: A stages at 0, PA; B stages behind them.  PERSIST (five 32-KiB slots): the first stages of both
   // operands and B's second sit in slots 3, 4, 2 -- outside the epilogue's scratch (slots 0, 1) -- so that the next
   // tile's head can land while the epilogue runs.
-  static_assert(!PERSIST || (PA == PB && 5 * PA <= 160 * 1024), "persistent layout: five equal slots");
   auto a_off = [](int st_) { return PERSIST ? (st_ == 0 ? 3 * PA : 0) : st_ * PA; };
   auto b_off = [](int st_) { return PERSIST ? (st_ == 0 ? 4 * PA : (st_ == 1 ? 2 * PA : PA)) : 2 * PA + st_ * PB; };
   const int lrow_p = l / CH, lch = l % CH;
-  // head of a tile: A(0), B(0) and B(1), by global->LDS DMA
-  // BUF: byte offset of this lane's 16 bytes of piece j inside its tile (rows beyond the operand clamp to its last row: they
-  // are never emitted), and the tile's buffer resource
+  // Source of this lane's 16 bytes of DMA piece j of the tile at m0_ / n0_ (k-tile 0; rows beyond the operand clamp to its last row:
+  // they are never emitted; the chunk is the swizzled one, see above): as a pointer, and -- BUF -- as a byte offset inside the tile
+  auto src_a = [&](int64_t m0_, int j) -> const uint16_t* {
+    const int row = (w * JA + j) * RP + lrow_p;
+    const int64_t qa = (m0_ + row < M) ? (m0_ + row) : (int64_t)(M - 1);
+    return Qh + qa * d + 8 * swz(row, lch);
+  };
+  auto src_b = [&](int64_t n0_, int j) -> const uint16_t* {
+    const int row = (w * JB + j) * RP + lrow_p;
+    const int64_t rb = (n0_ + row < N) ? (n0_ + row) : (int64_t)(N - 1);
+    return Rh + grow(rb) * ldr + 8 * swz(row, lch);
+  };
   auto voff_a = [&](int64_t m0_, int j) -> unsigned {
     const int row = (w * JA + j) * RP + lrow_p;
     const int rr = (m0_ + row < M) ? row : (int)((int64_t)M - 1 - m0_);
@@ -763,49 +271,38 @@ __global__ __launch_bounds__(64 * C::WM * C::WN) void knn_f16_filter_kernel(
     if constexpr (SKIP > 0) return (unsigned)(grow(n0_ + rr) - grow(n0_)) * (unsigned)(d * 2) + 16u * (unsigned)swz(row, lch);
     return (unsigned)rr * (unsigned)(ldb * 2) + 16u * (unsigned)swz(row, lch);
   };
-  auto rsrc_of = [](const uint16_t* base) -> sv_rsrc_t { return SV_BUF_RSRC(base); };
+  auto rsrc_of = [](const uint16_t* base) -> sv_rsrc_t { return SV_BUF_RSRC(base); };   // BUF: the tile's buffer resource
+  // head of a tile: A(0), B(0) and B(1), by global->LDS DMA.  (The three groups stay three loops per DMA form: issued through one inner
+  // helper, the scalar head code of all 14 kernels moved and the deep-row record of the bench came out 0.6-1.0 % slower:
+  // profiles/knn_filter_split_ab.txt.)
   auto issue_head = [&](int tm_, int tn_, int rev_) {
     const int64_t m0_ = (int64_t)tm_ * BM, n0_ = (int64_t)tn_ * BN;
     const int k0_ = kofs(rev_, 0), k1_ = kofs(rev_, 1);
     if constexpr (BUF) {
       const sv_rsrc_t ra = rsrc_of(Qh + m0_ * d), rb_ = rsrc_of(Rh + grow(n0_) * ldr);
 #pragma unroll
-      for (int j = 0; j < JA; ++j)
-        SV_BUF_LOAD_LDS(ra, (lptr_t)(lds + a_off(0) + (w * JA + j) * 1024), voff_a(m0_, j), 2 * k0_, 0);
+      for (int j = 0; j < JA; ++j) SV_BUF_LOAD_LDS(ra, (sv_lptr_t)(lds + a_off(0) + (w * JA + j) * 1024), voff_a(m0_, j), 2 * k0_, 0);
 #pragma unroll
       for (int j = 0; j < JB; ++j) {
         const unsigned vo = voff_b(n0_, j);
-        SV_BUF_LOAD_LDS(rb_, (lptr_t)(lds + b_off(0) + (w * JB + j) * 1024), vo, 2 * k0_, AUXB);
+        SV_BUF_LOAD_LDS(rb_, (sv_lptr_t)(lds + b_off(0) + (w * JB + j) * 1024), vo, 2 * k0_, AUXB);
       }
       if (ntiles > 1) {
 #pragma unroll
-        for (int j = 0; j < JB; ++j)
-          SV_BUF_LOAD_LDS(rb_, (lptr_t)(lds + b_off(1) + (w * JB + j) * 1024), voff_b(n0_, j), 2 * k1_, AUXB);
+        for (int j = 0; j < JB; ++j) SV_BUF_LOAD_LDS(rb_, (sv_lptr_t)(lds + b_off(1) + (w * JB + j) * 1024), voff_b(n0_, j), 2 * k1_, AUXB);
       }
       return;
     }
 #pragma unroll
-    for (int j = 0; j < JA; ++j) {
-      const int row = (w * JA + j) * RP + lrow_p;
-      const int64_t qa = (m0_ + row < M) ? (m0_ + row) : (int64_t)(M - 1);
-      __builtin_amdgcn_global_load_lds((gptr_t)(Qh + qa * d + 8 * swz(row, lch) + k0_), (lptr_t)(lds + a_off(0) + (w * JA + j) * 1024), 16,
-                                       0, 0);
-    }
+    for (int j = 0; j < JA; ++j)
+      __builtin_amdgcn_global_load_lds((sv_gptr_t)(src_a(m0_, j) + k0_), (sv_lptr_t)(lds + a_off(0) + (w * JA + j) * 1024), 16, 0, 0);
 #pragma unroll
-    for (int j = 0; j < JB; ++j) {
-      const int row = (w * JB + j) * RP + lrow_p;
-      const int64_t rb = (n0_ + row < N) ? (n0_ + row) : (int64_t)(N - 1);
-      __builtin_amdgcn_global_load_lds((gptr_t)(Rh + grow(rb) * ldr + 8 * swz(row, lch) + k0_), (lptr_t)(lds + b_off(0) + (w * JB + j) * 1024), 16,
-                                       0, AUXB);
-    }
+    for (int j = 0; j < JB; ++j)
+      __builtin_amdgcn_global_load_lds((sv_gptr_t)(src_b(n0_, j) + k0_), (sv_lptr_t)(lds + b_off(0) + (w * JB + j) * 1024), 16, 0, AUXB);
     if (ntiles > 1) {
 #pragma unroll
-      for (int j = 0; j < JB; ++j) {
-        const int row = (w * JB + j) * RP + lrow_p;
-        const int64_t rb = (n0_ + row < N) ? (n0_ + row) : (int64_t)(N - 1);
-        __builtin_amdgcn_global_load_lds((gptr_t)(Rh + grow(rb) * ldr + 8 * swz(row, lch) + k1_),
-                                         (lptr_t)(lds + b_off(1) + (w * JB + j) * 1024), 16, 0, AUXB);
-      }
+      for (int j = 0; j < JB; ++j)
+        __builtin_amdgcn_global_load_lds((sv_gptr_t)(src_b(n0_, j) + k1_), (sv_lptr_t)(lds + b_off(1) + (w * JB + j) * 1024), 16, 0, AUXB);
     }
   };
   // BIAS: this lane's column norms of the (next) tile, requested BEFORE the tile's head so that the head's wait covers them
@@ -813,6 +310,7 @@ __global__ __launch_bounds__(64 * C::WM * C::WN) void knn_f16_filter_kernel(
   constexpr int TN16 = (BN / WN) / 16;                // MF = 1: column tiles of 16 per wave (8, or 4 with blocked accumulation)
   constexpr int CW = MF ? 16 : 32;                    // columns (and rows) per MFMA tile
   constexpr int NCN = (BN / WN) / CW;                 // column tiles per wave = column norms per lane
+  static_assert(KFL == 0 || 4 * TN16 * 4 * 64 == SV_F16_KSCR_FLOATS, "flush scratch: one word per accumulator and lane of a wave");
   float cnn[NCN];
   auto load_cn = [&](int tn_) {
 #pragma unroll
@@ -821,6 +319,15 @@ __global__ __launch_bounds__(64 * C::WM * C::WN) void knn_f16_filter_kernel(
       cnn[nt] = (colj < N) ? rn[grow(colj)] : INFINITY;  // +inf: columns beyond N never pass
     }
   };
+  // PERSIST: this workgroup's next tile behind the current one -- found (sq < seq_total), its column norms and its head requested.
+  // A statement macro: as a lambda around issue_head the five persistent kernels gain 27 to 50 instructions (profiles/knn_filter_split_ab.txt).
+#define SV_F16_NEXT_TILE(sq, tm_, tn_)                                 \
+  sq = seq + pstep;                                                    \
+  while (sq < seq_total && !tile_of(sq, tm_, tn_)) sq += pstep;        \
+  if (sq < seq_total) {                                                \
+    if (BIAS) load_cn(tn_);                                            \
+    if (PROBE != 3) issue_head(tm_, tn_, rev_of(sq));                  \
+  }
   if (BIAS) load_cn(tn);
   int rev = PERSIST ? rev_of(seq) : 0;   // (only the persistent walk has steps to alternate / rotate)
   issue_head(tm, tn, rev);
@@ -831,718 +338,700 @@ __global__ __launch_bounds__(64 * C::WM * C::WN) void knn_f16_filter_kernel(
   // (the barrier that publishes the head to the other waves is the one at the top of the tile loop)
 
   for (;;) {   // PERSIST: one iteration per tile; otherwise a single pass
-  __builtin_amdgcn_s_barrier();   // head of this tile landed for every wave; (PERSIST) every wave left the previous epilogue
-  // the lane id is re-derived from an opaque copy in every iteration: otherwise the hundreds of constant addresses of
-  // the unrolled epilogue are hoisted out of the tile loop and spill (713 VGPRs)
-  int lane_opaque = (int)threadIdx.x;
-  asm volatile("" : "+v"(lane_opaque));
-  const int tid = lane_opaque, l = tid & 63, i = l & 31, kk = l >> 5;
-  const int64_t m0 = (int64_t)tm * BM, n0 = (int64_t)tn * BN;
+    __builtin_amdgcn_s_barrier();   // head of this tile landed for every wave; (PERSIST) every wave left the previous epilogue
+    // the lane id is re-derived from an opaque copy in every iteration: otherwise the hundreds of constant addresses of
+    // the unrolled epilogue are hoisted out of the tile loop and spill (713 VGPRs)
+    int lane_opaque = (int)threadIdx.x;
+    asm volatile("" : "+v"(lane_opaque));
+    const int tid = lane_opaque, l = tid & 63, i = l & 31, kk = l >> 5;
+    const int64_t m0 = (int64_t)tm * BM, n0 = (int64_t)tn * BN;
 
-  float cn[NCN];
-  if (BIAS) {
+    float cn[NCN];
+    if (BIAS) {
 #pragma unroll
-    for (int nt = 0; nt < NCN; ++nt) cn[nt] = cnn[nt];
-  }
-  f32x16 acc[MF ? 1 : TM][MF ? 1 : TN];
-  f32x4v acc16[MF ? 4 : 1][MF ? TN16 : 1];   // MF = 1: element j of tile (mt, nt) = row mt*16 + 4*(lane>>4) + j, column nt*16 + (lane&15)
-  f32x4v accb16[(MF && KBT > 0) ? 4 : 1][(MF && KBT > 0) ? TN16 : 1];   // blocked accumulation: the sum of the finished k-blocks (+ the bias)
-  if constexpr (MF == 0) {
+      for (int nt = 0; nt < NCN; ++nt) cn[nt] = cnn[nt];
+    }
+    f32x16 acc[MF ? 1 : TM][MF ? 1 : TN];
+    f32x4 acc16[MF ? 4 : 1][MF ? TN16 : 1];   // MF = 1: element j of tile (mt, nt) = row mt*16 + 4*(lane>>4) + j, column nt*16 + (lane&15)
+    f32x4 accb16[(MF && KBT > 0) ? 4 : 1][(MF && KBT > 0) ? TN16 : 1];   // blocked accumulation: the sum of the finished k-blocks (+ the bias)
+    if constexpr (MF == 0) {
 #pragma unroll
-    for (int a = 0; a < TM; ++a)
+      for (int a = 0; a < TM; ++a)
 #pragma unroll
-      for (int b = 0; b < TN; ++b) {
-        const float a0_ = BIAS ? -(cn[b] * (0.5f / inv_scale)) : 0.f;   // (the same product the epilogue forms: cnh)
+        for (int b = 0; b < TN; ++b) {
+          const float a0_ = BIAS ? -(cn[b] * (0.5f / inv_scale)) : 0.f;   // (the same product the epilogue forms: cnh)
 #pragma unroll
-        for (int r = 0; r < 16; ++r) acc[a][b][r] = a0_;
-      }
-  } else {
-#pragma unroll
-    for (int b = 0; b < TN16; ++b) {
-      const float a0_ = -(cn[b] * (0.5f / inv_scale));
-#pragma unroll
-      for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          if constexpr (KBT > 0) {   // the bias lives in the sum of the blocks; every block starts at zero
-            accb16[a][b][r] = a0_;
-            acc16[a][b][r] = 0.f;
-          } else {
-            acc16[a][b][r] = a0_;
-          }
+          for (int r = 0; r < 16; ++r) acc[a][b][r] = a0_;
         }
+    } else {
+#pragma unroll
+      for (int b = 0; b < TN16; ++b) {
+        const float a0_ = -(cn[b] * (0.5f / inv_scale));
+#pragma unroll
+        for (int a = 0; a < 4; ++a)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            if constexpr (KBT > 0) {   // the bias lives in the sum of the blocks; every block starts at zero
+              accb16[a][b][r] = a0_;
+              acc16[a][b][r] = 0.f;
+            } else {
+              acc16[a][b][r] = a0_;
+            }
+          }
+      }
     }
-  }
-  f32x16 accb[KBT > 0 ? TM : 1][KBT > 0 ? TN : 1];   // blocked accumulation: the sum of the finished k-blocks
-  if (KBT > 0) {
+    f32x16 accb[KBT > 0 ? TM : 1][KBT > 0 ? TN : 1];   // blocked accumulation: the sum of the finished k-blocks
+    if (KBT > 0) {
 #pragma unroll
-    for (int a = 0; a < TM; ++a)
+      for (int a = 0; a < TM; ++a)
 #pragma unroll
-      for (int b = 0; b < TN; ++b)
+        for (int b = 0; b < TN; ++b)
 #pragma unroll
-        for (int r = 0; r < 16; ++r) accb[KBT > 0 ? a : 0][KBT > 0 ? b : 0][r] = 0.f;
-  }
+          for (int r = 0; r < 16; ++r) accb[KBT > 0 ? a : 0][KBT > 0 ? b : 0][r] = 0.f;
+    }
 
-  // epilogue inputs, requested now so that their latency hides under the main loop (one workgroup per CU: nothing
-  // else would cover it): row tid's ||q||^2 and threshold, this lane's column norms
-  static_assert(BM <= 64 * NW, "one thread per query row stages the epilogue's row record");
-  float pre_q2 = 0.f, pre_thr = 0.f;
-  if (EPI == 1) {   // wave-private epilogue: lane l stages row l of THIS wave's 64 query rows
-    const int64_t qrow = m0 + wm * (32 * TM) + l;
-    if (qrow < M) {
-      pre_q2 = qn[qrow];
-      pre_thr = thr[qrow * thr_ld];
+    // epilogue inputs, requested now so that their latency hides under the main loop (one workgroup per CU: nothing
+    // else would cover it): row tid's ||q||^2 and threshold, this lane's column norms
+    static_assert(BM <= 64 * NW, "one thread per query row stages the epilogue's row record");
+    float pre_q2 = 0.f, pre_thr = 0.f;
+    if (EPI == 1) {   // wave-private epilogue: lane l stages row l of THIS wave's 64 query rows
+      const int64_t qrow = m0 + wm * (32 * TM) + l;
+      if (qrow < M) {
+        pre_q2 = qn[qrow];
+        pre_thr = thr[qrow * thr_ld];
+      }
+    } else if (tid < BM && m0 + tid < M) {
+      pre_q2 = qn[m0 + tid];
+      pre_thr = thr[(m0 + tid) * thr_ld];
     }
-  } else if (tid < BM && m0 + tid < M) {
-    pre_q2 = qn[m0 + tid];
-    pre_thr = thr[(m0 + tid) * thr_ld];
-  }
-  if constexpr (!BIAS) {
+    if constexpr (!BIAS) {
 #pragma unroll
-    for (int nt = 0; nt < TN; ++nt) {
-      const int64_t colj = n0 + wn * (32 * TN) + nt * 32 + i;
-      cn[nt] = (colj < N) ? rn[grow(colj)] : INFINITY;  // +inf: columns beyond N never pass
+      for (int nt = 0; nt < TN; ++nt) {
+        const int64_t colj = n0 + wn * (32 * TN) + nt * 32 + i;
+        cn[nt] = (colj < N) ? rn[grow(colj)] : INFINITY;  // +inf: columns beyond N never pass
+      }
     }
-  }
 
-  // per-lane source rows of this wave's DMA pieces (clamped: edge rows are never emitted)
-  const uint16_t* srcA[BUF ? 1 : JA];
-  const uint16_t* srcB[BUF ? 1 : JB];
-  unsigned voA[BUF ? JA : 1], voB[BUF ? JB : 1];
-  const sv_rsrc_t rsA = rsrc_of(Qh + m0 * d), rsB = rsrc_of(Rh + grow(n0) * ldr);
-  if constexpr (BUF) {
-#pragma unroll
-    for (int j = 0; j < JA; ++j) voA[j] = voff_a(m0, j);
-#pragma unroll
-    for (int j = 0; j < JB; ++j) voB[j] = voff_b(n0, j);
-  } else {
-#pragma unroll
-    for (int j = 0; j < JA; ++j) {
-      const int row = (w * JA + j) * RP + lrow_p;
-      const int64_t qa = (m0 + row < M) ? (m0 + row) : (int64_t)(M - 1);
-      srcA[j] = Qh + qa * d + 8 * swz(row, lch);
-    }
-#pragma unroll
-    for (int j = 0; j < JB; ++j) {
-      const int row = (w * JB + j) * RP + lrow_p;
-      const int64_t rb = (n0 + row < N) ? (n0 + row) : (int64_t)(N - 1);
-      srcB[j] = Rh + grow(rb) * ldr + 8 * swz(row, lch);
-    }
-  }
-  constexpr int BAHEAD = NB - 1;  // how many k-tiles ahead the B DMA runs (A always runs one ahead)
-  // DMA piece p of iteration kt: pieces 0..JA-1 belong to A(kt+1), JA..JA+JB-1 to B(kt+BAHEAD)
-  auto dma_piece = [&](int piece, int kt, int ia_next, int ib_next) {
-    if (PROBE == 3) return;  // (development build) no DMA in the loop
+    // per-lane source rows of this wave's DMA pieces (clamped: edge rows are never emitted)
+    const uint16_t* srcA[BUF ? 1 : JA];
+    const uint16_t* srcB[BUF ? 1 : JB];
+    unsigned voA[BUF ? JA : 1], voB[BUF ? JB : 1];
+    const sv_rsrc_t rsA = rsrc_of(Qh + m0 * d), rsB = rsrc_of(Rh + grow(n0) * ldr);
     if constexpr (BUF) {
-      if (piece < JA) {
+#pragma unroll
+      for (int j = 0; j < JA; ++j) voA[j] = voff_a(m0, j);
+#pragma unroll
+      for (int j = 0; j < JB; ++j) voB[j] = voff_b(n0, j);
+    } else {
+#pragma unroll
+      for (int j = 0; j < JA; ++j) srcA[j] = src_a(m0, j);
+#pragma unroll
+      for (int j = 0; j < JB; ++j) srcB[j] = src_b(n0, j);
+    }
+    constexpr int BAHEAD = NB - 1;  // how many k-tiles ahead the B DMA runs (A always runs one ahead)
+    // DMA piece p of iteration kt: pieces 0..JA-1 belong to A(kt+1), JA..JA+JB-1 to B(kt+BAHEAD)
+    auto dma_piece = [&](int piece, int kt, int ia_next, int ib_next) {
+      if (PROBE == 3) return;  // (development build) no DMA in the loop
+      if constexpr (BUF) {
+        if (piece < JA) {
+          if (kt + 1 < ntiles)
+            SV_BUF_LOAD_LDS(rsA, (sv_lptr_t)(lds + a_off(ia_next) + (w * JA + piece) * 1024), voA[piece], 2 * kofs(rev, kt + 1), 0);
+        } else {
+          const int j = piece - JA;
+          if (kt + BAHEAD < ntiles)
+            SV_BUF_LOAD_LDS(rsB, (sv_lptr_t)(lds + b_off(ib_next) + (w * JB + j) * 1024), voB[j], 2 * kofs(rev, kt + BAHEAD), AUXB);
+        }
+      } else if (piece < JA) {
         if (kt + 1 < ntiles)
-          SV_BUF_LOAD_LDS(rsA, (lptr_t)(lds + a_off(ia_next) + (w * JA + piece) * 1024), voA[piece], 2 * kofs(rev, kt + 1), 0);
+          __builtin_amdgcn_global_load_lds((sv_gptr_t)(srcA[piece] + kofs(rev, kt + 1)),
+                                           (sv_lptr_t)(lds + a_off(ia_next) + (w * JA + piece) * 1024), 16, 0, 0);
       } else {
         const int j = piece - JA;
         if (kt + BAHEAD < ntiles)
-          SV_BUF_LOAD_LDS(rsB, (lptr_t)(lds + b_off(ib_next) + (w * JB + j) * 1024), voB[j], 2 * kofs(rev, kt + BAHEAD), AUXB);
+          __builtin_amdgcn_global_load_lds((sv_gptr_t)(srcB[j] + kofs(rev, kt + BAHEAD)),
+                                           (sv_lptr_t)(lds + b_off(ib_next) + (w * JB + j) * 1024), 16, 0, AUXB);
       }
-    } else if (piece < JA) {
-      if (kt + 1 < ntiles)
-        __builtin_amdgcn_global_load_lds((gptr_t)(srcA[piece] + kofs(rev, kt + 1)),
-                                         (lptr_t)(lds + a_off(ia_next) + (w * JA + piece) * 1024), 16, 0, 0);
-    } else {
-      const int j = piece - JA;
-      if (kt + BAHEAD < ntiles)
-        __builtin_amdgcn_global_load_lds((gptr_t)(srcB[j] + kofs(rev, kt + BAHEAD)),
-                                         (lptr_t)(lds + b_off(ib_next) + (w * JB + j) * 1024), 16, 0, AUXB);
-    }
-  };
-  SV_PHASE(0)  // prologue: first tiles landed
+    };
+    SV_PHASE(0)  // prologue: first tiles landed
 
-  int ia = 0, ib = 0;
-  const int fa0 = wm * (32 * TM) + i, fb0 = wn * (32 * TN) + i;
-  if constexpr (PP > 0) {
-    constexpr int PH = KS / 2;            // MFMA k-steps per phase
-    constexpr int DPP = (JA + JB) / 2;    // DMA pieces per phase and wave
-    static_assert(KS % 2 == 0 && (JA + JB) % 2 == 0, "phase geometry");
-    const bool lag = w >= NW / 2;           // wave-uniform (w comes from readfirstlane)
-    if (lag) __builtin_amdgcn_s_barrier(); // the second half of the waves runs one barrier (= one segment) behind
-    // (KFL: the k-tiles run in blocks of KFL; the flush sits BETWEEN two runs of the inner loop, not behind a branch inside it -- with
-    //  the branch inside, the 128 accumulators met a zeroed copy of themselves at the loop's back edge and 40 registers spilled)
-    int kt = 0;
-    for (int kstop = (KFL > 0 && KFL < ntiles) ? KFL : ntiles;;) {
-    for (; kt < kstop; ++kt) {
-      const int ibn = (ib + BAHEAD >= NB) ? ib + BAHEAD - NB : ib + BAHEAD;
-      const unsigned char* SA = lds + a_off(ia);
-      const unsigned char* SB = lds + b_off(ib);
+    int ia = 0, ib = 0;
+    const int fa0 = wm * (32 * TM) + i, fb0 = wn * (32 * TN) + i;
+    if constexpr (PP > 0) {
+      constexpr int PH = KS / 2;            // MFMA k-steps per phase
+      constexpr int DPP = (JA + JB) / 2;    // DMA pieces per phase and wave
+      static_assert(KS % 2 == 0 && (JA + JB) % 2 == 0, "phase geometry");
+      const bool lag = w >= NW / 2;           // wave-uniform (w comes from readfirstlane)
+      if (lag) __builtin_amdgcn_s_barrier(); // the second half of the waves runs one barrier (= one segment) behind
+      // (KFL: the k-tiles run in blocks of KFL; the flush sits BETWEEN two runs of the inner loop, not behind a branch inside it -- with
+      //  the branch inside, the 128 accumulators met a zeroed copy of themselves at the loop's back edge and 40 registers spilled)
+      int kt = 0;
+      for (int kstop = (KFL > 0 && KFL < ntiles) ? KFL : ntiles;;) {
+        for (; kt < kstop; ++kt) {
+          const int ibn = (ib + BAHEAD >= NB) ? ib + BAHEAD - NB : ib + BAHEAD;
+          const unsigned char* SA = lds + a_off(ia);
+          const unsigned char* SB = lds + b_off(ib);
 #pragma unroll
-      for (int ph = 0; ph < 2; ++ph) {
-        // ---- load segment: fragments of this phase's k-steps, this phase's share of the DMA pieces ----
-        f16x8 a[MF ? 1 : PH][MF ? 4 : TM], b[MF ? 1 : PH][MF ? TN16 : TN];
-        if constexpr (MF == 0) {
+          for (int ph = 0; ph < 2; ++ph) {
+            // ---- load segment: fragments of this phase's k-steps, this phase's share of the DMA pieces ----
+            f16x8 a[MF ? 1 : PH][MF ? 4 : TM], b[MF ? 1 : PH][MF ? TN16 : TN];
+            if constexpr (MF == 0) {
 #pragma unroll
-          for (int k2 = 0; k2 < PH; ++k2) {
-            const int cl = 2 * (ph * PH + k2) + kk;
+              for (int k2 = 0; k2 < PH; ++k2) {
+                const int cl = 2 * (ph * PH + k2) + kk;
 #pragma unroll
-            for (int t = 0; t < TM; ++t) {
-              const int ra = fa0 + 32 * t;
-              a[k2][t] = *reinterpret_cast<const f16x8*>(SA + ra * RB + swz(ra, cl) * 16);
+                for (int t = 0; t < TM; ++t) {
+                  const int ra = fa0 + 32 * t;
+                  a[k2][t] = *reinterpret_cast<const f16x8*>(SA + ra * RB + swz(ra, cl) * 16);
+                }
+#pragma unroll
+                for (int t = 0; t < TN; ++t) {
+                  const int rb = fb0 + 32 * t;
+                  b[k2][t] = *reinterpret_cast<const f16x8*>(SB + rb * RB + swz(rb, cl) * 16);
+                }
+              }
+            } else {
+              // one k-step of 32 per phase: lane l holds row / column (l & 15) of a 16-wide tile, k-chunk (l >> 4) of the step's four
+              // (the source-side swizzle of the 128-byte rows is conflict-free for this pattern too: a 16-lane ds_read_b128 group
+              //  covers rows {0-3, 12-15} of one chunk and rows {4-11} of the next, 16 distinct bank groups)
+              static_assert(PH == 2 && CH == 8, "a phase = 32 k of 128-byte rows");
+              const int cl = 4 * ph + (l >> 4);
+#pragma unroll
+              for (int t = 0; t < 4; ++t) {
+                const int ra = wm * 64 + 16 * t + (l & 15);
+                a[0][t] = *reinterpret_cast<const f16x8*>(SA + ra * RB + swz(ra, cl) * 16);
+              }
+#pragma unroll
+              for (int t = 0; t < TN16; ++t) {
+                const int rb = wn * (16 * TN16) + 16 * t + (l & 15);
+                b[0][t] = *reinterpret_cast<const f16x8*>(SB + rb * RB + swz(rb, cl) * 16);
+              }
             }
 #pragma unroll
-            for (int t = 0; t < TN; ++t) {
-              const int rb = fb0 + 32 * t;
-              b[k2][t] = *reinterpret_cast<const f16x8*>(SB + rb * RB + swz(rb, cl) * 16);
+            for (int pz = 0; pz < DPP; ++pz) dma_piece(ph * DPP + pz, kt, ia ^ 1, ibn);
+            if (ph == 1) {
+              // last load segment of the k-tile: this wave's pieces of A(kt+1) and B(kt+1) have landed (B(kt+2), the
+              // youngest JB DMA instructions, may still fly).  The barriers between here and the first read of tile kt+1
+              // (one for the leading half, two for the lagging half) make that true for every wave's pieces.
+              if (kt + 2 < ntiles)
+                sv_wait_vm_lgkm0<JB>();
+              else
+                sv_wait_vm_lgkm0<0>();
+            } else {
+              asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             }
+            __builtin_amdgcn_sched_barrier(0);
+            __builtin_amdgcn_s_barrier();
+            __builtin_amdgcn_sched_barrier(0);
+            // ---- MFMA segment ----
+            __builtin_amdgcn_s_setprio(1);
+            if constexpr (MF == 0) {
+#pragma unroll
+              for (int k2 = 0; k2 < PH; ++k2)
+#pragma unroll
+                for (int mt = 0; mt < TM; ++mt)
+#pragma unroll
+                  for (int nt = 0; nt < TN; ++nt) acc[mt][nt] = MFMA_F16(a[k2][mt], b[k2][nt], acc[mt][nt]);
+            } else {
+#pragma unroll
+              for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+                for (int nt = 0; nt < TN16; ++nt)
+                  acc16[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[0][mt], b[0][nt], acc16[mt][nt], 0, 0, 0);
+            }
+            __builtin_amdgcn_s_setprio(0);
+            __builtin_amdgcn_sched_barrier(0);
+            __builtin_amdgcn_s_barrier();
+            __builtin_amdgcn_sched_barrier(0);
           }
-        } else {
-          // one k-step of 32 per phase: lane l holds row / column (l & 15) of a 16-wide tile, k-chunk (l >> 4) of the step's four
-          // (the source-side swizzle of the 128-byte rows is conflict-free for this pattern too: a 16-lane ds_read_b128 group
-          //  covers rows {0-3, 12-15} of one chunk and rows {4-11} of the next, 16 distinct bank groups)
-          static_assert(PH == 2 && CH == 8, "a phase = 32 k of 128-byte rows");
-          const int cl = 4 * ph + (l >> 4);
-#pragma unroll
-          for (int t = 0; t < 4; ++t) {
-            const int ra = wm * 64 + 16 * t + (l & 15);
-            a[0][t] = *reinterpret_cast<const f16x8*>(SA + ra * RB + swz(ra, cl) * 16);
-          }
-#pragma unroll
-          for (int t = 0; t < TN16; ++t) {
-            const int rb = wn * (16 * TN16) + 16 * t + (l & 15);
-            b[0][t] = *reinterpret_cast<const f16x8*>(SB + rb * RB + swz(rb, cl) * 16);
-          }
+          ia ^= 1;
+          ib = (ib + 1 >= NB) ? 0 : ib + 1;
         }
-#pragma unroll
-        for (int pz = 0; pz < DPP; ++pz) dma_piece(ph * DPP + pz, kt, ia ^ 1, ibn);
-        if (ph == 1) {
-          // last load segment of the k-tile: this wave's pieces of A(kt+1) and B(kt+1) have landed (B(kt+2), the
-          // youngest JB DMA instructions, may still fly).  The barriers between here and the first read of tile kt+1
-          // (one for the leading half, two for the lagging half) make that true for every wave's pieces.
-          if (kt + 2 < ntiles)
-            sv_wait_vm_lgkm0<JB>();
-          else
-            sv_wait_vm_lgkm0<0>();
-        } else {
-          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_sched_barrier(0);
-        // ---- MFMA segment ----
-        __builtin_amdgcn_s_setprio(1);
-        if constexpr (MF == 0) {
-#pragma unroll
-          for (int k2 = 0; k2 < PH; ++k2)
-#pragma unroll
-            for (int mt = 0; mt < TM; ++mt)
-#pragma unroll
-              for (int nt = 0; nt < TN; ++nt) acc[mt][nt] = MFMA_F16(a[k2][mt], b[k2][nt], acc[mt][nt]);
-        } else {
-#pragma unroll
-          for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-            for (int nt = 0; nt < TN16; ++nt)
-              acc16[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[0][mt], b[0][nt], acc16[mt][nt], 0, 0, 0);
-        }
-        __builtin_amdgcn_s_setprio(0);
-        __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_sched_barrier(0);
-      }
-      ia ^= 1;
-      ib = (ib + 1 >= NB) ? 0 : ib + 1;
-    }
-    if (KFL == 0 || kt >= ntiles) break;
-    if constexpr (KFL > 0) {   // close a k-block into the wave's global scratch slice (see KFL)
-      static_assert(MF == 1 && KBT == 0 && PERSIST && TN16 == 8, "flushed blocks: the persistent 16 x 16 x 32 ping-pong kernel");
-      float* const kscr_w = kscr_base() + l;
-#pragma unroll
-      for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-        for (int nt = 0; nt < TN16; ++nt)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            sv_atomic_add_noret(kscr_w + 64 * ((mt * TN16 + nt) * 4 + r), acc16[mt][nt][r]);
-            acc16[mt][nt][r] = 0.f;
-          }
-    }
-    kstop = (kt + (KFL > 0 ? KFL : 1) < ntiles) ? kt + (KFL > 0 ? KFL : 1) : ntiles;
-    }
-    if (!lag) __builtin_amdgcn_s_barrier();  // the leading half waits for the lagging half's last MFMA segment
-    if constexpr (KFL > 0) {
-      if (ntiles > KFL) {   // the last block joins the flushed ones; totals back into the accumulators; the slice is left zero
-        float* const kscr_w = kscr_base() + l;
-#pragma unroll
-        for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-          for (int nt = 0; nt < TN16; ++nt)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) sv_atomic_add_noret(kscr_w + 64 * ((mt * TN16 + nt) * 4 + r), acc16[mt][nt][r]);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#pragma unroll
-        for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-          for (int nt = 0; nt < TN16; ++nt)
-#pragma unroll
-            for (int r = 0; r < 4; ++r)   // (agent-scope load: from L2, not from a line the previous tile left in this CU's vector cache)
-              acc16[mt][nt][r] = __hip_atomic_load(kscr_w + 64 * ((mt * TN16 + nt) * 4 + r), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#pragma unroll
-        for (int j = 0; j < 16 * TN16; ++j) __hip_atomic_store(kscr_w + 64 * j, 0.f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-    }
-  } else if constexpr (MF == 1) {
-    // the plain loop (one barrier per k-tile) on the 16 x 16 x 32 shape: two k-steps of 32 per k-tile
-    static_assert(KS == 4 && (JA + JB) % 2 == 0, "two k-steps of 32 per 64-deep k-tile");
-    for (int kt = 0; kt < ntiles; ++kt) {
-      const int ibn = (ib + BAHEAD >= NB) ? ib + BAHEAD - NB : ib + BAHEAD;
-      const unsigned char* SA = lds + a_off(ia);
-      const unsigned char* SB = lds + b_off(ib);
-#pragma unroll
-      for (int k2 = 0; k2 < 2; ++k2) {
-        const int cl = 4 * k2 + (l >> 4);
-        f16x8 a[4], b[TN16];
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-          const int ra = wm * 64 + 16 * t + (l & 15);
-          a[t] = *reinterpret_cast<const f16x8*>(SA + ra * RB + swz(ra, cl) * 16);
-        }
-#pragma unroll
-        for (int t = 0; t < TN16; ++t) {
-          const int rb = wn * (16 * TN16) + 16 * t + (l & 15);
-          b[t] = *reinterpret_cast<const f16x8*>(SB + rb * RB + swz(rb, cl) * 16);
-        }
-#pragma unroll
-        for (int pz = 0; pz < (JA + JB) / 2; ++pz) dma_piece(k2 * ((JA + JB) / 2) + pz, kt, ia ^ 1, ibn);
-#pragma unroll
-        for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-          for (int nt = 0; nt < TN16; ++nt) acc16[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[mt], b[nt], acc16[mt][nt], 0, 0, 0);
-      }
-      if (kt + 2 < ntiles)
-        sv_wait_vm_lgkm0<JB>();
-      else
-        sv_wait_vm_lgkm0<0>();
-      __builtin_amdgcn_s_barrier();
-      ia ^= 1;
-      ib = (ib + 1 >= NB) ? 0 : ib + 1;
-      if constexpr (KBT > 0) {
-        if ((kt + 1) % (KBT > 0 ? KBT : 1) == 0 || kt + 1 == ntiles) {   // close a k-block (wave-uniform)
+        if (KFL == 0 || kt >= ntiles) break;
+        if constexpr (KFL > 0) {   // close a k-block into the wave's global scratch slice (see KFL)
+          static_assert(MF == 1 && KBT == 0 && PERSIST && TN16 == 8, "flushed blocks: the persistent 16 x 16 x 32 ping-pong kernel");
+          float* const kscr_w = kscr_base() + l;
 #pragma unroll
           for (int mt = 0; mt < 4; ++mt)
 #pragma unroll
             for (int nt = 0; nt < TN16; ++nt)
 #pragma unroll
               for (int r = 0; r < 4; ++r) {
-                accb16[mt][nt][r] += acc16[mt][nt][r];
-                acc16[mt][nt][r] = (kt + 1 == ntiles) ? accb16[mt][nt][r] : 0.f;   // last block: acc = the total
+                sv_atomic_add_noret(kscr_w + 64 * ((mt * TN16 + nt) * 4 + r), acc16[mt][nt][r]);
+                acc16[mt][nt][r] = 0.f;
+              }
+        }
+        kstop = (kt + (KFL > 0 ? KFL : 1) < ntiles) ? kt + (KFL > 0 ? KFL : 1) : ntiles;
+      }
+      if (!lag) __builtin_amdgcn_s_barrier();  // the leading half waits for the lagging half's last MFMA segment
+      if constexpr (KFL > 0) {
+        if (ntiles > KFL) {   // the last block joins the flushed ones; totals back into the accumulators; the slice is left zero
+          float* const kscr_w = kscr_base() + l;
+#pragma unroll
+          for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+            for (int nt = 0; nt < TN16; ++nt)
+#pragma unroll
+              for (int r = 0; r < 4; ++r) sv_atomic_add_noret(kscr_w + 64 * ((mt * TN16 + nt) * 4 + r), acc16[mt][nt][r]);
+          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#pragma unroll
+          for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+            for (int nt = 0; nt < TN16; ++nt)
+#pragma unroll
+              for (int r = 0; r < 4; ++r)   // (agent-scope load: from L2, not from a line the previous tile left in this CU's vector cache)
+                acc16[mt][nt][r] = __hip_atomic_load(kscr_w + 64 * ((mt * TN16 + nt) * 4 + r), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#pragma unroll
+          for (int j = 0; j < 16 * TN16; ++j) __hip_atomic_store(kscr_w + 64 * j, 0.f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+      }
+    } else if constexpr (MF == 1) {
+      // the plain loop (one barrier per k-tile) on the 16 x 16 x 32 shape: two k-steps of 32 per k-tile
+      static_assert(KS == 4 && (JA + JB) % 2 == 0, "two k-steps of 32 per 64-deep k-tile");
+      for (int kt = 0; kt < ntiles; ++kt) {
+        const int ibn = (ib + BAHEAD >= NB) ? ib + BAHEAD - NB : ib + BAHEAD;
+        const unsigned char* SA = lds + a_off(ia);
+        const unsigned char* SB = lds + b_off(ib);
+#pragma unroll
+        for (int k2 = 0; k2 < 2; ++k2) {
+          const int cl = 4 * k2 + (l >> 4);
+          f16x8 a[4], b[TN16];
+#pragma unroll
+          for (int t = 0; t < 4; ++t) {
+            const int ra = wm * 64 + 16 * t + (l & 15);
+            a[t] = *reinterpret_cast<const f16x8*>(SA + ra * RB + swz(ra, cl) * 16);
+          }
+#pragma unroll
+          for (int t = 0; t < TN16; ++t) {
+            const int rb = wn * (16 * TN16) + 16 * t + (l & 15);
+            b[t] = *reinterpret_cast<const f16x8*>(SB + rb * RB + swz(rb, cl) * 16);
+          }
+#pragma unroll
+          for (int pz = 0; pz < (JA + JB) / 2; ++pz) dma_piece(k2 * ((JA + JB) / 2) + pz, kt, ia ^ 1, ibn);
+#pragma unroll
+          for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+            for (int nt = 0; nt < TN16; ++nt) acc16[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[mt], b[nt], acc16[mt][nt], 0, 0, 0);
+        }
+        if (kt + 2 < ntiles)
+          sv_wait_vm_lgkm0<JB>();
+        else
+          sv_wait_vm_lgkm0<0>();
+        __builtin_amdgcn_s_barrier();
+        ia ^= 1;
+        ib = (ib + 1 >= NB) ? 0 : ib + 1;
+        if constexpr (KBT > 0) {
+          if ((kt + 1) % (KBT > 0 ? KBT : 1) == 0 || kt + 1 == ntiles) {   // close a k-block (wave-uniform)
+#pragma unroll
+            for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+              for (int nt = 0; nt < TN16; ++nt)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                  accb16[mt][nt][r] += acc16[mt][nt][r];
+                  acc16[mt][nt][r] = (kt + 1 == ntiles) ? accb16[mt][nt][r] : 0.f;   // last block: acc = the total
+                }
+          }
+        }
+      }
+    } else {
+      for (int kt = 0; kt < ntiles; ++kt) {
+        const int ibn = (ib + BAHEAD >= NB) ? ib + BAHEAD - NB : ib + BAHEAD;
+        const unsigned char* SA = lds + a_off(ia);
+        const unsigned char* SB = lds + b_off(ib);
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) {
+          const int cl = 2 * ks + kk;  // logical 16-B chunk (8 consecutive k) of this lane
+          f16x8 a[TM], b[TN];
+#pragma unroll
+          for (int t = 0; t < TM; ++t) {
+            const int ra = fa0 + 32 * t;
+            a[t] = *reinterpret_cast<const f16x8*>(SA + ra * RB + swz(ra, cl) * 16);
+          }
+#pragma unroll
+          for (int t = 0; t < TN; ++t) {
+            const int rb = fb0 + 32 * t;
+            b[t] = *reinterpret_cast<const f16x8*>(SB + rb * RB + swz(rb, cl) * 16);
+          }
+#pragma unroll
+          for (int pz = 0; pz < (JA + JB) / KS; ++pz) dma_piece(ks * ((JA + JB) / KS) + pz, kt, ia ^ 1, ibn);
+#pragma unroll
+          for (int mt = 0; mt < TM; ++mt)
+#pragma unroll
+            for (int nt = 0; nt < TN; ++nt) acc[mt][nt] = MFMA_F16(a[mt], b[nt], acc[mt][nt]);
+        }
+        // this wave's pieces of A(kt+1) and B(kt+1) have landed (B(kt+2) -- the youngest JB DMA
+        // instructions -- may still fly: vmcnt retires in order) and its LDS reads are done; after the barrier that
+        // holds for every wave, so the stages of tile kt may be overwritten
+        if (kt + 2 < ntiles)
+          sv_wait_vm_lgkm0<JB>();
+        else
+          sv_wait_vm_lgkm0<0>();
+        __builtin_amdgcn_s_barrier();
+        ia ^= 1;
+        ib = (ib + 1 >= NB) ? 0 : ib + 1;
+        if (KBT > 0 && ((kt + 1) % (KBT > 0 ? KBT : 1) == 0 || kt + 1 == ntiles)) {   // close a k-block (wave-uniform)
+#pragma unroll
+          for (int mt = 0; mt < TM; ++mt)
+#pragma unroll
+            for (int nt = 0; nt < TN; ++nt)
+#pragma unroll
+              for (int r = 0; r < 16; ++r) {
+                accb[KBT > 0 ? mt : 0][KBT > 0 ? nt : 0][r] += acc[mt][nt][r];
+                acc[mt][nt][r] = (kt + 1 == ntiles) ? accb[KBT > 0 ? mt : 0][KBT > 0 ? nt : 0][r] : 0.f;   // last block: acc = the total
               }
         }
       }
     }
-  } else {
-  for (int kt = 0; kt < ntiles; ++kt) {
-      const int ibn = (ib + BAHEAD >= NB) ? ib + BAHEAD - NB : ib + BAHEAD;
-      const unsigned char* SA = lds + a_off(ia);
-      const unsigned char* SB = lds + b_off(ib);
-  #pragma unroll
-      for (int ks = 0; ks < KS; ++ks) {
-        const int cl = 2 * ks + kk;  // logical 16-B chunk (8 consecutive k) of this lane
-        f16x8 a[TM], b[TN];
-  #pragma unroll
-        for (int t = 0; t < TM; ++t) {
-          const int ra = fa0 + 32 * t;
-          a[t] = *reinterpret_cast<const f16x8*>(SA + ra * RB + swz(ra, cl) * 16);
-        }
-  #pragma unroll
-        for (int t = 0; t < TN; ++t) {
-          const int rb = fb0 + 32 * t;
-          b[t] = *reinterpret_cast<const f16x8*>(SB + rb * RB + swz(rb, cl) * 16);
-        }
-  #pragma unroll
-        for (int pz = 0; pz < (JA + JB) / KS; ++pz) dma_piece(ks * ((JA + JB) / KS) + pz, kt, ia ^ 1, ibn);
-  #pragma unroll
-        for (int mt = 0; mt < TM; ++mt)
-  #pragma unroll
-          for (int nt = 0; nt < TN; ++nt) acc[mt][nt] = MFMA_F16(a[mt], b[nt], acc[mt][nt]);
-      }
-      // this wave's pieces of A(kt+1) and B(kt+1) have landed (B(kt+2) -- the youngest JB DMA
-      // instructions -- may still fly: vmcnt retires in order) and its LDS reads are done; after the barrier that
-      // holds for every wave, so the stages of tile kt may be overwritten
-      if (kt + 2 < ntiles)
-        sv_wait_vm_lgkm0<JB>();
-      else
-        sv_wait_vm_lgkm0<0>();
-      __builtin_amdgcn_s_barrier();
-      ia ^= 1;
-      ib = (ib + 1 >= NB) ? 0 : ib + 1;
-      if (KBT > 0 && ((kt + 1) % (KBT > 0 ? KBT : 1) == 0 || kt + 1 == ntiles)) {   // close a k-block (wave-uniform)
-#pragma unroll
-        for (int mt = 0; mt < TM; ++mt)
-#pragma unroll
-          for (int nt = 0; nt < TN; ++nt)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-              accb[KBT > 0 ? mt : 0][KBT > 0 ? nt : 0][r] += acc[mt][nt][r];
-              acc[mt][nt][r] = (kt + 1 == ntiles) ? accb[KBT > 0 ? mt : 0][KBT > 0 ? nt : 0][r] : 0.f;   // last block: acc = the total
-            }
-      }
-    }
-  }
 
-  SV_PHASE(1)  // main loop
-  if constexpr (PROBE >= 2) {  // (development build) no epilogue: WRONG results (the accumulators stay live)
-    static_assert(PROBE < 2 || (MF == 1 && PERSIST), "the probes are forms of the default batch kernel");
-    float t = 0.f;
-#pragma unroll
-    for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-      for (int nt = 0; nt < TN16; ++nt) t += acc16[mt][nt][0] + acc16[mt][nt][3];
-    if (t == 12345.678f) cand_cnt[0] = 1;
-    // on to the workgroup's next tile (its head requested here, waited for at once)
-    int tm_n = 0, tn_n = 0, sq_n = seq + pstep;
-    while (sq_n < seq_total && !tile_of(sq_n, tm_n, tn_n)) sq_n += pstep;
-    if (sq_n >= seq_total) return;
-    if (BIAS) load_cn(tn_n);
-    if (PROBE != 3) issue_head(tm_n, tn_n, rev_of(sq_n));
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    seq = sq_n;
-    tm = tm_n;
-    tn = tn_n;
-    rev = rev_of(seq);
-    continue;
-  }
-  // The epilogue's row record {||q||^2, exact limit, screening bound} of this thread's row, in registers and BEFORE the next
-  // tile's head is requested: the compiler waits for the two global loads behind it (issued before the main loop, long
-  // since landed) with s_waitcnt vmcnt(0) at their first use -- placed behind the head's DMA instructions that wait sat out
-  // the head's whole flight (~2 us per tile, with nothing else to do: the very latency the early request is meant to hide).
-  //   v <= lim  <=>  acc - cn * half_scale >= (q2 - lim) * half_scale; the slack (relative 2^-17 of the largest possible
-  //   magnitude) makes rounding of this shortcut only ever ADD candidates
-  const float half_scale = 0.5f / inv_scale;
-  const float rmax_hs = rn_max * half_scale;
-  float st_q2 = 0.f, st_lim = -INFINITY, st_tau = INFINITY;
-  if (EPI == 1 ? (m0 + wm * (32 * TM) + l < M) : (tid < BM && m0 + tid < M)) {
-    st_q2 = pre_q2;
-    st_lim = pre_thr + eps_mult * c_eps * sqrtf(st_q2 * rn_max);
-    const float base = (st_q2 - st_lim) * half_scale;
-    st_tau = base - 7.7e-6f * (fabsf(base) + rmax_hs);
-  }
-  asm volatile("" : "+v"(st_q2), "+v"(st_lim), "+v"(st_tau));   // (keeps the computation -- and its wait -- on this side of the DMA issue)
-  // PERSIST: the next tile of this workgroup; its head is requested now and lands under the epilogue
-  int tm_next = 0, tn_next = 0, seq_next = seq_total;
-  if (PERSIST) {
-    seq_next = seq + pstep;
-    while (seq_next < seq_total && !tile_of(seq_next, tm_next, tn_next)) seq_next += pstep;
-    if (seq_next < seq_total) {
-      if (BIAS) load_cn(tn_next);
-      issue_head(tm_next, tn_next, rev_of(seq_next));
-    }
-  }
-  // ---- epilogue: keep d2~ <= thr + eps_mult * eps(q) -----------------------------------------------------------
-  // The epilogue is VALU-issue bound (s_memtime phase timing, see PROBE: every instruction of the sparse
-  // per-survivor paths is paid by the whole wave), so it is organised around instruction count and everything
-  // per-survivor happens on DENSE lanes:
-  //  * per-row quantities {||q||^2, exact limit, screening bound} and the tile's column norms are staged once per
-  //    workgroup in LDS (their global loads were issued before the main loop);
-  //  * pass 1 screens every accumulator element with one fma + compare against the row's bound; the (rare) waves
-  //    that see a hit compact the raw {accumulator, row | column} pairs by ballot/mbcnt into a wave-private LDS
-  //    list -- three instructions per element on the common path, no atomics, no exact arithmetic;
-  //  * pass 2a walks that list 64 records at a time (all lanes busy): exact d2~, exact limit test, LDS count per row;
-  //  * ONE global atomic per row and workgroup reserves a slot range in that query's candidate list;
-  //  * pass 2b walks the list again and stores the survivors at range + LDS ticket.
-  // (History: one returning global atomic per survivor parked the wave ~1.5 us each; re-walking the 128 accumulator
-  // elements under a per-lane bitmap cost 20 % of the kernel; ~100-instruction exact-test bodies per hit row 25 %.)
-  // A wave whose 64 x 128 block holds more than LCAP hits (databases are spatially coherent: the 50 segments of a
-  // query image against the rows of the same place) abandons its list and walks its accumulators directly
-  // (per-hit LDS atomics: slow, but only for the handful of dense blocks).  The list order is arbitrary: every
-  // consumer ranks or sorts it.
-  // records per wave: a quarter of its elements at most; PERSIST keeps the whole scratch inside LDS slots 0 and 1
-  constexpr int LCAP = PERSIST ? 896 : ((TM * TN * 256 < 2048) ? TM * TN * 256 : 2048);
-  static_assert(!PERSIST || (size_t)BM * 24 + (size_t)BN * 4 + (size_t)NW * (LCAP + 1) * 8 <= 2 * (size_t)PA, "epilogue scratch");
-  if constexpr (EPI == 1) {
-    // ---- wave-private epilogue (EPI = 1; persistent + biased kernels) ------------------------------------------------
-    // Nothing in it is shared between waves, so nothing in it waits for another wave: every wave stages the records of ITS
-    // 64 query rows, screens its 64 x 128 block into its own LDS list, tests the list densely and takes ONE returning global
-    // atomic per ROW WITH SURVIVORS (ranks inside a row from a wave-private LDS counter): the reservation's round trip
-    // overlaps the wait for the next tile's head, which the wave has to sit out anyway, and the stores are left in flight.
-    // A block that fills its list (spatially coherent databases: the 50 segments of a query image against the 200 rows of the
-    // same place are thousands of hits in ONE 64 x 128 block) flushes it in place and goes on screening -- still one round
-    // trip per flush.  (First version: one returning global atomic per survivor, 64 at a time -- fine at ~6 survivors per
-    // block, 150 round trips for such a block.  A re-entrant screening pass -- flush, then jump back in -- turns the pass
-    // into a loop whose invariants the compiler hoists and spills: 80 dwords.)
-    static_assert(BIAS && MF == 1, "wave-private epilogue: the biased kernels on the 16 x 16 x 32 shape");
-    constexpr int LCAPE = 864;   // records per wave list
-    constexpr int WSZ = (1024 + (LCAPE + 1) * 8 + 15) & ~15;
-    static_assert((size_t)NW * WSZ <= (PERSIST ? 2 * (size_t)PA : 2 * (size_t)PA + (size_t)NB * PB), "epilogue scratch");
-    // Every LDS access between the head's DMA instructions and the wait inside the first flush is RAW (inline asm): the
-    // compiler cannot tell DMA'd LDS bytes from any other LDS address and puts s_waitcnt vmcnt(0) in front of every LDS
-    // instruction it can see while a DMA is pending -- the wave would sit out the head's flight before its first epilogue
-    // instruction (which is what EPI = 0 does).  One wave's LDS instructions execute in order, so a write followed by a read
-    // of the same bytes needs no wait in between; reads are waited for with explicit lgkmcnt.
-    // per wave: [64] {||q||^2, exact limit} | +512: [64] screening bounds | +768: [64] survivors per row, then the row's first
-    // global slot | +1024: [LCAPE + 1] hits {accumulator bits -> d2~, row << 16 | rank in the row << 8 | column}
-    const unsigned wb_a = (unsigned)(size_t)(lptr_t)(lds + (size_t)w * WSZ);
-    {
-      const float2 qr = make_float2(st_q2, st_lim);
-      asm volatile("ds_write_b64 %0, %1\n\tds_write_b32 %2, %3 offset:512\n\tds_write_b32 %2, %4 offset:768" ::"v"(wb_a + 8u * (unsigned)l), "v"(qr),
-                   "v"(wb_a + 4u * (unsigned)l), "v"(st_tau), "v"(0u)
-                   : "memory");
-    }
-    SV_PHASE(2)
-    // this lane's screening bounds: element j of tile mt is row mt*16 + 4*(lane>>4) + j -- 4 groups of 4 consecutive rows
-    float4 tqw[4];
-    {
-      const unsigned ta = wb_a + 512u + 16u * (unsigned)(l >> 4);
-      asm volatile(
-          "ds_read_b128 %0, %4\n\tds_read_b128 %1, %4 offset:64\n\tds_read_b128 %2, %4 offset:128\n\tds_read_b128 %3, %4 offset:192\n\t"
-          "s_waitcnt lgkmcnt(0)"
-          : "=&v"(tqw[0]), "=&v"(tqw[1]), "=&v"(tqw[2]), "=&v"(tqw[3])
-          : "v"(ta)
-          : "memory");
-    }
-    uint32_t wave_cnt = 0;   // wave-uniform
-    const uint32_t colbase = (uint32_t)(wn * (32 * TN) + (l & 15)), rowsel = (uint32_t)(4 * (l >> 4));
-    const int64_t rowbase = m0 + wm * 64;
-    // dense exact test of the list, one returning global atomic per row with survivors, the stores left in flight
-    auto flush = [&]() {
-      const uint32_t n_w = wave_cnt;
-      for (uint32_t tb = 0; tb < n_w; tb += 64u) {   // exact test; a survivor draws its rank inside its row
-        const uint32_t t = tb + (uint32_t)l;
-        if (t < n_w) {
-          uint2 rec;
-          float2 rr;
-          asm volatile("ds_read_b64 %0, %1 offset:1024\n\ts_waitcnt lgkmcnt(0)" : "=v"(rec) : "v"(wb_a + 8u * t) : "memory");
-          const unsigned lrow = rec.y >> 16;
-          asm volatile("ds_read_b64 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(rr) : "v"(wb_a + 8u * lrow) : "memory");
-          const float v = __fmaf_rn(-2.f, __uint_as_float(rec.x) * inv_scale, rr.x);
-          if (v <= rr.y && v < INFINITY) {   // +inf: padding columns beyond N (admitted by the screen when thr = +inf)
-            uint32_t rank;
-            asm volatile("ds_add_rtn_u32 %0, %1, %2 offset:768\n\ts_waitcnt lgkmcnt(0)" : "=v"(rank) : "v"(wb_a + 4u * lrow), "v"(1u) : "memory");
-            rec.x = __float_as_uint(v);
-            rec.y |= rank << 8;              // (< 128 survivors per row and block; the column keeps bits 0-7)
-          } else {
-            rec.y = 0xffffffffu;             // screened in by the slack only
-          }
-          asm volatile("ds_write_b64 %0, %1 offset:1024" ::"v"(wb_a + 8u * t), "v"(rec) : "memory");
-        }
-      }
-      uint32_t c;
-      asm volatile("ds_read_b32 %0, %1 offset:768\n\ts_waitcnt lgkmcnt(0)" : "=v"(c) : "v"(wb_a + 4u * (unsigned)l) : "memory");
-      uint32_t base = 0u;
-      if (c) base = atomicAdd(&cand_cnt[rowbase + l], c);   // (rows >= M screen with +inf: no survivors)
-      // the reservations -- and, the first time round, this wave's DMA pieces of the next tile's head (requested before the
-      // screening pass; loads retire in order): the barrier at the top of the tile loop makes that true for every wave
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      asm volatile("ds_write_b32 %0, %1 offset:768" ::"v"(wb_a + 4u * (unsigned)l), "v"(base) : "memory");
-      for (uint32_t tb = 0; tb < n_w; tb += 64u) {
-        const uint32_t t = tb + (uint32_t)l;
-        if (t < n_w) {
-          uint2 rec;
-          asm volatile("ds_read_b64 %0, %1 offset:1024\n\ts_waitcnt lgkmcnt(0)" : "=v"(rec) : "v"(wb_a + 8u * t) : "memory");
-          if (rec.y != 0xffffffffu) {
-            const unsigned lrow = rec.y >> 16;
-            uint32_t b0;
-            asm volatile("ds_read_b32 %0, %1 offset:768\n\ts_waitcnt lgkmcnt(0)" : "=v"(b0) : "v"(wb_a + 4u * lrow) : "memory");
-            const uint32_t slot = b0 + ((rec.y >> 8) & 0xffu);
-            if (slot < (uint32_t)cap) {
-              const int64_t row = rowbase + (int64_t)lrow;
-              cand_d2[row * cap + slot] = __uint_as_float(rec.x);
-              cand_id[row * cap + slot] = (uint32_t)grow(n0 + (int64_t)(rec.y & 0xffu));
-            }
-          }
-        }
-      }
-      asm volatile("ds_write_b32 %0, %1 offset:768" ::"v"(wb_a + 4u * (unsigned)l), "v"(0u) : "memory");
-      wave_cnt = 0u;
-    };
-    {
-      // 16 screening steps of 8 elements (one row of the wave tile across its 8 column tiles)
+    SV_PHASE(1)  // main loop
+    if constexpr (PROBE >= 2) {  // (development build) no epilogue: WRONG results (the accumulators stay live)
+      static_assert(PROBE < 2 || (MF == 1 && PERSIST), "the probes are forms of the default batch kernel");
+      float t = 0.f;
 #pragma unroll
       for (int mt = 0; mt < 4; ++mt)
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const float4 tq4 = tqw[mt];
-          const float tau = j == 0 ? tq4.x : j == 1 ? tq4.y : j == 2 ? tq4.z : tq4.w;
-          float best;
-          asm volatile("v_max3_f32 %0, %1, %2, %3" : "=v"(best) : "v"(acc16[mt][0][j]), "v"(acc16[mt][1][j]), "v"(acc16[mt][2][j]));
-          if constexpr (TN16 == 8) {
-            asm volatile("v_max3_f32 %0, %1, %2, %3" : "=v"(best) : "v"(best), "v"(acc16[mt][3][j]), "v"(acc16[mt][TN16 == 8 ? 4 : 0][j]));
-            asm volatile("v_max3_f32 %0, %1, %2, %3" : "=v"(best) : "v"(best), "v"(acc16[mt][TN16 == 8 ? 5 : 0][j]), "v"(acc16[mt][TN16 == 8 ? 6 : 0][j]));
-            asm volatile("v_max_f32 %0, %1, %2" : "=v"(best) : "v"(best), "v"(acc16[mt][TN16 == 8 ? 7 : 0][j]));
-          } else {
-            asm volatile("v_max_f32 %0, %1, %2" : "=v"(best) : "v"(best), "v"(acc16[mt][3][j]));
+        for (int nt = 0; nt < TN16; ++nt) t += acc16[mt][nt][0] + acc16[mt][nt][3];
+      if (t == 12345.678f) cand_cnt[0] = 1;
+      // on to the workgroup's next tile (its head requested here, waited for at once)
+      int tm_n = 0, tn_n = 0, sq_n;
+      SV_F16_NEXT_TILE(sq_n, tm_n, tn_n)
+      if (sq_n >= seq_total) return;
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      seq = sq_n;
+      tm = tm_n;
+      tn = tn_n;
+      rev = rev_of(seq);
+      continue;
+    }
+    // The epilogue's row record {||q||^2, exact limit, screening bound} of this thread's row, in registers and BEFORE the next
+    // tile's head is requested: the compiler waits for the two global loads behind it (issued before the main loop, long
+    // since landed) with s_waitcnt vmcnt(0) at their first use -- placed behind the head's DMA instructions that wait sat out
+    // the head's whole flight (~2 us per tile, with nothing else to do: the very latency the early request is meant to hide).
+    //   v <= lim  <=>  acc - cn * half_scale >= (q2 - lim) * half_scale; the slack (relative 2^-17 of the largest possible
+    //   magnitude) makes rounding of this shortcut only ever ADD candidates
+    const float half_scale = 0.5f / inv_scale;
+    const float rmax_hs = rn_max * half_scale;
+    float st_q2 = 0.f, st_lim = -INFINITY, st_tau = INFINITY;
+    if (EPI == 1 ? (m0 + wm * (32 * TM) + l < M) : (tid < BM && m0 + tid < M)) {
+      st_q2 = pre_q2;
+      st_lim = pre_thr + eps_mult * c_eps * sqrtf(st_q2 * rn_max);
+      const float base = (st_q2 - st_lim) * half_scale;
+      st_tau = base - 7.7e-6f * (fabsf(base) + rmax_hs);
+    }
+    asm volatile("" : "+v"(st_q2), "+v"(st_lim), "+v"(st_tau));   // (keeps the computation -- and its wait -- on this side of the DMA issue)
+    // PERSIST: the next tile of this workgroup; its head is requested now and lands under the epilogue
+    int tm_next = 0, tn_next = 0, seq_next = seq_total;
+    if (PERSIST) {
+      SV_F16_NEXT_TILE(seq_next, tm_next, tn_next)
+    }
+    // ---- epilogue: keep d2~ <= thr + eps_mult * eps(q) -----------------------------------------------------------
+    // The epilogue is VALU-issue bound (s_memtime phase timing, see PROBE: every instruction of the sparse
+    // per-survivor paths is paid by the whole wave), so it is organised around instruction count and everything
+    // per-survivor happens on DENSE lanes:
+    //  * per-row quantities {||q||^2, exact limit, screening bound} and the tile's column norms are staged once per
+    //    workgroup in LDS (their global loads were issued before the main loop);
+    //  * pass 1 screens every accumulator element with one fma + compare against the row's bound; the (rare) waves
+    //    that see a hit compact the raw {accumulator, row | column} pairs by ballot/mbcnt into a wave-private LDS
+    //    list -- three instructions per element on the common path, no atomics, no exact arithmetic;
+    //  * pass 2a walks that list 64 records at a time (all lanes busy): exact d2~, exact limit test, LDS count per row;
+    //  * ONE global atomic per row and workgroup reserves a slot range in that query's candidate list;
+    //  * pass 2b walks the list again and stores the survivors at range + LDS ticket.
+    // (History: one returning global atomic per survivor parked the wave ~1.5 us each; re-walking the 128 accumulator
+    // elements under a per-lane bitmap cost 20 % of the kernel; ~100-instruction exact-test bodies per hit row 25 %.)
+    // A wave whose 64 x 128 block holds more than LCAP hits (databases are spatially coherent: the 50 segments of a
+    // query image against the rows of the same place) abandons its list and walks its accumulators directly
+    // (per-hit LDS atomics: slow, but only for the handful of dense blocks).  The list order is arbitrary: every
+    // consumer ranks or sorts it.
+    // records per wave: a quarter of its elements at most; PERSIST keeps the whole scratch inside LDS slots 0 and 1 (F16Lds)
+    constexpr int LCAP = L::LCAP, LCAPE = L::LCAPE, WSZ = L::WSZ;   // EPI = 0: records per wave list | EPI = 1: the same, bytes per wave
+    if constexpr (EPI == 1) {
+      // ---- wave-private epilogue (EPI = 1; persistent + biased kernels) ------------------------------------------------
+      // Nothing in it is shared between waves, so nothing in it waits for another wave: every wave stages the records of ITS
+      // 64 query rows, screens its 64 x 128 block into its own LDS list, tests the list densely and takes ONE returning global
+      // atomic per ROW WITH SURVIVORS (ranks inside a row from a wave-private LDS counter): the reservation's round trip
+      // overlaps the wait for the next tile's head, which the wave has to sit out anyway, and the stores are left in flight.
+      // A block that fills its list (spatially coherent databases: the 50 segments of a query image against the 200 rows of the
+      // same place are thousands of hits in ONE 64 x 128 block) flushes it in place and goes on screening -- still one round
+      // trip per flush.  (First version: one returning global atomic per survivor, 64 at a time -- fine at ~6 survivors per
+      // block, 150 round trips for such a block.  A re-entrant screening pass -- flush, then jump back in -- turns the pass
+      // into a loop whose invariants the compiler hoists and spills: 80 dwords.)
+      static_assert(BIAS && MF == 1, "wave-private epilogue: the biased kernels on the 16 x 16 x 32 shape");
+      // Every LDS access between the head's DMA instructions and the wait inside the first flush is RAW (inline asm): the
+      // compiler cannot tell DMA'd LDS bytes from any other LDS address and puts s_waitcnt vmcnt(0) in front of every LDS
+      // instruction it can see while a DMA is pending -- the wave would sit out the head's flight before its first epilogue
+      // instruction (which is what EPI = 0 does).  One wave's LDS instructions execute in order, so a write followed by a read
+      // of the same bytes needs no wait in between; reads are waited for with explicit lgkmcnt.
+      // per wave: [64] {||q||^2, exact limit} | +512: [64] screening bounds | +768: [64] survivors per row, then the row's first
+      // global slot | +1024: [LCAPE + 1] hits {accumulator bits -> d2~, row << 16 | rank in the row << 8 | column}
+      const unsigned wb_a = (unsigned)(size_t)(sv_lptr_t)(lds + (size_t)w * WSZ);
+      {
+        const float2 qr = make_float2(st_q2, st_lim);
+        asm volatile("ds_write_b64 %0, %1\n\tds_write_b32 %2, %3 offset:512\n\tds_write_b32 %2, %4 offset:768" ::"v"(wb_a + 8u * (unsigned)l), "v"(qr),
+                     "v"(wb_a + 4u * (unsigned)l), "v"(st_tau), "v"(0u)
+                     : "memory");
+      }
+      SV_PHASE(2)
+      // this lane's screening bounds: element j of tile mt is row mt*16 + 4*(lane>>4) + j -- 4 groups of 4 consecutive rows
+      float4 tqw[4];
+      {
+        const unsigned ta = wb_a + 512u + 16u * (unsigned)(l >> 4);
+        asm volatile(
+            "ds_read_b128 %0, %4\n\tds_read_b128 %1, %4 offset:64\n\tds_read_b128 %2, %4 offset:128\n\tds_read_b128 %3, %4 offset:192\n\t"
+            "s_waitcnt lgkmcnt(0)"
+            : "=&v"(tqw[0]), "=&v"(tqw[1]), "=&v"(tqw[2]), "=&v"(tqw[3])
+            : "v"(ta)
+            : "memory");
+      }
+      uint32_t wave_cnt = 0;   // wave-uniform
+      const uint32_t colbase = (uint32_t)(wn * (32 * TN) + (l & 15)), rowsel = (uint32_t)(4 * (l >> 4));
+      const int64_t rowbase = m0 + wm * 64;
+      // dense exact test of the list, one returning global atomic per row with survivors, the stores left in flight
+      auto flush = [&]() {
+        const uint32_t n_w = wave_cnt;
+        for (uint32_t tb = 0; tb < n_w; tb += 64u) {   // exact test; a survivor draws its rank inside its row
+          const uint32_t t = tb + (uint32_t)l;
+          if (t < n_w) {
+            uint2 rec;
+            float2 rr;
+            asm volatile("ds_read_b64 %0, %1 offset:1024\n\ts_waitcnt lgkmcnt(0)" : "=v"(rec) : "v"(wb_a + 8u * t) : "memory");
+            const unsigned lrow = rec.y >> 16;
+            asm volatile("ds_read_b64 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(rr) : "v"(wb_a + 8u * lrow) : "memory");
+            const float v = __fmaf_rn(-2.f, __uint_as_float(rec.x) * inv_scale, rr.x);
+            if (v <= rr.y && v < INFINITY) {   // +inf: padding columns beyond N (admitted by the screen when thr = +inf)
+              uint32_t rank;
+              asm volatile("ds_add_rtn_u32 %0, %1, %2 offset:768\n\ts_waitcnt lgkmcnt(0)" : "=v"(rank) : "v"(wb_a + 4u * lrow), "v"(1u) : "memory");
+              rec.x = __float_as_uint(v);
+              rec.y |= rank << 8;              // (< 128 survivors per row and block; the column keeps bits 0-7)
+            } else {
+              rec.y = 0xffffffffu;             // screened in by the slack only
+            }
+            asm volatile("ds_write_b64 %0, %1 offset:1024" ::"v"(wb_a + 8u * t), "v"(rec) : "memory");
           }
-          if (__builtin_amdgcn_ballot_w64(best >= tau) != 0ull) {
-            const uint32_t rc = (((uint32_t)(mt * 16 + j) + rowsel) << 16) | colbase;
+        }
+        uint32_t c;
+        asm volatile("ds_read_b32 %0, %1 offset:768\n\ts_waitcnt lgkmcnt(0)" : "=v"(c) : "v"(wb_a + 4u * (unsigned)l) : "memory");
+        uint32_t base = 0u;
+        if (c) base = atomicAdd(&cand_cnt[rowbase + l], c);   // (rows >= M screen with +inf: no survivors)
+        // the reservations -- and, the first time round, this wave's DMA pieces of the next tile's head (requested before the
+        // screening pass; loads retire in order): the barrier at the top of the tile loop makes that true for every wave
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        asm volatile("ds_write_b32 %0, %1 offset:768" ::"v"(wb_a + 4u * (unsigned)l), "v"(base) : "memory");
+        for (uint32_t tb = 0; tb < n_w; tb += 64u) {
+          const uint32_t t = tb + (uint32_t)l;
+          if (t < n_w) {
+            uint2 rec;
+            asm volatile("ds_read_b64 %0, %1 offset:1024\n\ts_waitcnt lgkmcnt(0)" : "=v"(rec) : "v"(wb_a + 8u * t) : "memory");
+            if (rec.y != 0xffffffffu) {
+              const unsigned lrow = rec.y >> 16;
+              uint32_t b0;
+              asm volatile("ds_read_b32 %0, %1 offset:768\n\ts_waitcnt lgkmcnt(0)" : "=v"(b0) : "v"(wb_a + 4u * lrow) : "memory");
+              const uint32_t slot = b0 + ((rec.y >> 8) & 0xffu);
+              if (slot < (uint32_t)cap) {
+                const int64_t row = rowbase + (int64_t)lrow;
+                cand_d2[row * cap + slot] = __uint_as_float(rec.x);
+                cand_id[row * cap + slot] = (uint32_t)grow(n0 + (int64_t)(rec.y & 0xffu));
+              }
+            }
+          }
+        }
+        asm volatile("ds_write_b32 %0, %1 offset:768" ::"v"(wb_a + 4u * (unsigned)l), "v"(0u) : "memory");
+        wave_cnt = 0u;
+      };
+      {
+        // 16 screening steps of 8 elements (one row of the wave tile across its 8 column tiles)
 #pragma unroll
-            for (int nt = 0; nt < TN16; ++nt) {
-              const bool hit = acc16[mt][nt][j] >= tau;
+        for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            const float4 tq4 = tqw[mt];
+            const float tau = j == 0 ? tq4.x : j == 1 ? tq4.y : j == 2 ? tq4.z : tq4.w;
+            float best;
+            asm volatile("v_max3_f32 %0, %1, %2, %3" : "=v"(best) : "v"(acc16[mt][0][j]), "v"(acc16[mt][1][j]), "v"(acc16[mt][2][j]));
+            if constexpr (TN16 == 8) {
+              asm volatile("v_max3_f32 %0, %1, %2, %3" : "=v"(best) : "v"(best), "v"(acc16[mt][3][j]), "v"(acc16[mt][TN16 == 8 ? 4 : 0][j]));
+              asm volatile("v_max3_f32 %0, %1, %2, %3" : "=v"(best) : "v"(best), "v"(acc16[mt][TN16 == 8 ? 5 : 0][j]), "v"(acc16[mt][TN16 == 8 ? 6 : 0][j]));
+              asm volatile("v_max_f32 %0, %1, %2" : "=v"(best) : "v"(best), "v"(acc16[mt][TN16 == 8 ? 7 : 0][j]));
+            } else {
+              asm volatile("v_max_f32 %0, %1, %2" : "=v"(best) : "v"(best), "v"(acc16[mt][3][j]));
+            }
+            if (__builtin_amdgcn_ballot_w64(best >= tau) != 0ull) {
+              const uint32_t rc = (((uint32_t)(mt * 16 + j) + rowsel) << 16) | colbase;
+#pragma unroll
+              for (int nt = 0; nt < TN16; ++nt) {
+                const bool hit = acc16[mt][nt][j] >= tau;
+                const uint64_t mk = __builtin_amdgcn_ballot_w64(hit);
+                if (mk != 0ull) {
+                  const uint32_t pos = wave_cnt + __builtin_amdgcn_mbcnt_hi((uint32_t)(mk >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mk, 0u));
+                  if (hit) {
+                    const uint2 rec = make_uint2(__float_as_uint(acc16[mt][nt][j]), rc + (uint32_t)(nt * 16));
+                    asm volatile("ds_write_b64 %0, %1 offset:1024" ::"v"(wb_a + 8u * pos), "v"(rec) : "memory");
+                  }
+                  wave_cnt += (uint32_t)__popcll(mk);
+                }
+              }
+              if (wave_cnt > (uint32_t)(LCAPE - 64 * TN16)) flush();   // (a step adds up to TN16 x 64 records)
+            }
+          }
+      }
+      SV_PHASE(3)
+      flush();
+      SV_PHASE(4)
+    }
+    if constexpr (EPI == 0) {
+      float4* rrec = reinterpret_cast<float4*>(lds);                         // [BM] {||q||^2, exact limit, screening bound, -}
+      uint32_t* rowcnt = reinterpret_cast<uint32_t*>(rrec + BM);             // [BM] survivors per row -> next free global slot
+      float* cnl = reinterpret_cast<float*>(rowcnt + BM);                    // [BN] column norms
+      float* taul = cnl + BN;                                                // [BM] screening bounds, contiguous (16-B reads)
+      uint2* wlist = reinterpret_cast<uint2*>(taul + BM) + (size_t)w * (LCAP + 1);  // this wave's hit list (+1 dump slot)
+      if (tid < BM) {
+        const int j = tid;
+        rrec[j] = make_float4(st_q2, st_lim, st_tau, 0.f);
+        rowcnt[j] = 0u;
+        taul[j] = st_tau;
+      }
+      float cnh[TN];
+#pragma unroll
+      for (int nt = 0; nt < TN; ++nt) {
+        cnh[nt] = BIAS ? 0.f : cn[nt] * half_scale;                  // BIAS: already inside the accumulators
+        if (!BIAS && wm == 0) cnl[wn * (32 * TN) + nt * 32 + i] = cn[nt];   // both half-waves hold the same value
+      }
+      __syncthreads();
+      uint32_t wave_cnt = 0;  // wave-uniform: only updated under wave-uniform control flow
+      // this lane's 16 * TM screening bounds, fetched up front with 16-B reads (accumulator element r of tile mt belongs to
+      // row mt*32 + 8*(r>>2) + 4*kk + (r&3): four consecutive rows per (mt, r>>2)) -- a per-iteration LDS read put ~100
+      // cycles of latency into each of the 32 screening steps (two waves per SIMD cannot hide it)
+      float4 tq[TM][4];
+#pragma unroll
+      for (int mt = 0; mt < TM; ++mt)
+#pragma unroll
+        for (int g = 0; g < 4; ++g)
+          tq[mt][g] = *reinterpret_cast<const float4*>(taul + wm * (32 * TM) + mt * 32 + 8 * g + 4 * kk);
+#pragma unroll
+      for (int mt = 0; mt < TM; ++mt) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const uint32_t lrow16 = (uint32_t)(wm * (32 * TM) + mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * kk) << 16;
+          const float4 tq4 = tq[mt][r >> 2];
+          const float tau = (r & 3) == 0 ? tq4.x : (r & 3) == 1 ? tq4.y : (r & 3) == 2 ? tq4.z : tq4.w;
+          float av[TN], dd[TN];
+#pragma unroll
+          for (int nt = 0; nt < TN; ++nt) {
+            av[nt] = acc[mt][nt][r];
+            dd[nt] = BIAS ? av[nt] : av[nt] - cnh[nt];
+          }
+          float best = dd[0];
+#pragma unroll
+          for (int nt = 1; nt < TN; ++nt) best = fmaxf(best, dd[nt]);
+          if (__builtin_amdgcn_ballot_w64(best >= tau) != 0ull) {
+#pragma unroll
+            for (int nt = 0; nt < TN; ++nt) {
+              const bool hit = dd[nt] >= tau;
               const uint64_t mk = __builtin_amdgcn_ballot_w64(hit);
               if (mk != 0ull) {
-                const uint32_t pos = wave_cnt + __builtin_amdgcn_mbcnt_hi((uint32_t)(mk >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mk, 0u));
-                if (hit) {
-                  const uint2 rec = make_uint2(__float_as_uint(acc16[mt][nt][j]), rc + (uint32_t)(nt * 16));
-                  asm volatile("ds_write_b64 %0, %1 offset:1024" ::"v"(wb_a + 8u * pos), "v"(rec) : "memory");
-                }
+                uint32_t pos = wave_cnt + __builtin_amdgcn_mbcnt_hi((uint32_t)(mk >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mk, 0u));
+                pos = pos < (uint32_t)LCAP ? pos : (uint32_t)LCAP;   // beyond the list: the dump slot (the block turns dense below)
+                if (hit)
+                  wlist[pos] = make_uint2(__float_as_uint(av[nt]), lrow16 | (uint32_t)(wn * (32 * TN) + nt * 32 + i));
                 wave_cnt += (uint32_t)__popcll(mk);
               }
             }
-            if (wave_cnt > (uint32_t)(LCAPE - 64 * TN16)) flush();   // (a step adds up to TN16 x 64 records)
-          }
-        }
-    }
-    SV_PHASE(3)
-    flush();
-    SV_PHASE(4)
-  }
-  if constexpr (EPI == 0) {
-  float4* rrec = reinterpret_cast<float4*>(lds);                         // [BM] {||q||^2, exact limit, screening bound, -}
-  uint32_t* rowcnt = reinterpret_cast<uint32_t*>(rrec + BM);             // [BM] survivors per row -> next free global slot
-  float* cnl = reinterpret_cast<float*>(rowcnt + BM);                    // [BN] column norms
-  float* taul = cnl + BN;                                                // [BM] screening bounds, contiguous (16-B reads)
-  uint2* wlist = reinterpret_cast<uint2*>(taul + BM) + (size_t)w * (LCAP + 1);  // this wave's hit list (+1 dump slot)
-  if (tid < BM) {
-    const int j = tid;
-    rrec[j] = make_float4(st_q2, st_lim, st_tau, 0.f);
-    rowcnt[j] = 0u;
-    taul[j] = st_tau;
-  }
-  float cnh[TN];
-#pragma unroll
-  for (int nt = 0; nt < TN; ++nt) {
-    cnh[nt] = BIAS ? 0.f : cn[nt] * half_scale;                  // BIAS: already inside the accumulators
-    if (!BIAS && wm == 0) cnl[wn * (32 * TN) + nt * 32 + i] = cn[nt];   // both half-waves hold the same value
-  }
-  __syncthreads();
-  uint32_t wave_cnt = 0;  // wave-uniform: only updated under wave-uniform control flow
-  // this lane's 16 * TM screening bounds, fetched up front with 16-B reads (accumulator element r of tile mt belongs to
-  // row mt*32 + 8*(r>>2) + 4*kk + (r&3): four consecutive rows per (mt, r>>2)) -- a per-iteration LDS read put ~100
-  // cycles of latency into each of the 32 screening steps (two waves per SIMD cannot hide it)
-  float4 tq[TM][4];
-#pragma unroll
-  for (int mt = 0; mt < TM; ++mt)
-#pragma unroll
-    for (int g = 0; g < 4; ++g)
-      tq[mt][g] = *reinterpret_cast<const float4*>(taul + wm * (32 * TM) + mt * 32 + 8 * g + 4 * kk);
-#pragma unroll
-  for (int mt = 0; mt < TM; ++mt) {
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const uint32_t lrow16 = (uint32_t)(wm * (32 * TM) + mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * kk) << 16;
-      const float4 tq4 = tq[mt][r >> 2];
-      const float tau = (r & 3) == 0 ? tq4.x : (r & 3) == 1 ? tq4.y : (r & 3) == 2 ? tq4.z : tq4.w;
-      float av[TN], dd[TN];
-#pragma unroll
-      for (int nt = 0; nt < TN; ++nt) {
-        av[nt] = acc[mt][nt][r];
-        dd[nt] = BIAS ? av[nt] : av[nt] - cnh[nt];
-      }
-      float best = dd[0];
-#pragma unroll
-      for (int nt = 1; nt < TN; ++nt) best = fmaxf(best, dd[nt]);
-      if (__builtin_amdgcn_ballot_w64(best >= tau) != 0ull) {
-#pragma unroll
-        for (int nt = 0; nt < TN; ++nt) {
-          const bool hit = dd[nt] >= tau;
-          const uint64_t mk = __builtin_amdgcn_ballot_w64(hit);
-          if (mk != 0ull) {
-            uint32_t pos = wave_cnt + __builtin_amdgcn_mbcnt_hi((uint32_t)(mk >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mk, 0u));
-            pos = pos < (uint32_t)LCAP ? pos : (uint32_t)LCAP;   // beyond the list: the dump slot (the block turns dense below)
-            if (hit)
-              wlist[pos] = make_uint2(__float_as_uint(av[nt]), lrow16 | (uint32_t)(wn * (32 * TN) + nt * 32 + i));
-            wave_cnt += (uint32_t)__popcll(mk);
           }
         }
       }
-    }
-  }
-  // pass 2a: exact test of this wave's hits, dense (the list is wave-private: no barrier needed before reading it)
-  const uint32_t n_w = wave_cnt <= (uint32_t)LCAP ? wave_cnt : 0u;   // a dense block abandons its (truncated) list
-  for (uint32_t t = (uint32_t)l; t < n_w; t += 64u) {
-    uint2 rec = wlist[t];
-    const int lrow = (int)(rec.y >> 16);
-    const float4 rr = rrec[lrow];
-    const float v = BIAS ? __fmaf_rn(-2.f, __uint_as_float(rec.x) * inv_scale, rr.x)
-                         : sv_d2_screen(rr.x, cnl[rec.y & 0xffffu], __uint_as_float(rec.x) * inv_scale);
-    if (v <= rr.y && v < INFINITY) {   // +inf: padding columns beyond N (admitted by the screen when thr = +inf)
-      atomicAdd(&rowcnt[lrow], 1u);
-      rec.x = __float_as_uint(v);
-    } else {
-      rec.y = 0xffffffffu;   // screened in by the slack only
-    }
-    wlist[t] = rec;
-  }
-  const bool dense = wave_cnt > (uint32_t)LCAP;   // wave-uniform
-  if (dense) {
-    // (the scale is laundered through an empty asm so that the compiler does not keep 128 values of pass 1 or of this
-    //  walk alive for the next one: that spilled the common path)
-    float isc = inv_scale;
-    asm volatile("" : "+v"(isc));
-#pragma unroll
-    for (int mt = 0; mt < TM; ++mt)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int lrow = wm * (32 * TM) + mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * kk;
-#pragma unroll
-        for (int nt = 0; nt < TN; ++nt) {
-          const float4 rr = rrec[lrow];
-          const float v = BIAS ? __fmaf_rn(-2.f, acc[mt][nt][r] * isc, rr.x)
-                               : sv_d2_screen(rr.x, cn[nt], acc[mt][nt][r] * isc);
-          if (v <= rr.y && v < INFINITY) atomicAdd(&rowcnt[lrow], 1u);
+      // pass 2a: exact test of this wave's hits, dense (the list is wave-private: no barrier needed before reading it)
+      const uint32_t n_w = wave_cnt <= (uint32_t)LCAP ? wave_cnt : 0u;   // a dense block abandons its (truncated) list
+      for (uint32_t t = (uint32_t)l; t < n_w; t += 64u) {
+        uint2 rec = wlist[t];
+        const int lrow = (int)(rec.y >> 16);
+        const float4 rr = rrec[lrow];
+        const float v = BIAS ? __fmaf_rn(-2.f, __uint_as_float(rec.x) * inv_scale, rr.x)
+                             : sv_d2_screen(rr.x, cnl[rec.y & 0xffffu], __uint_as_float(rec.x) * inv_scale);
+        if (v <= rr.y && v < INFINITY) {   // +inf: padding columns beyond N (admitted by the screen when thr = +inf)
+          atomicAdd(&rowcnt[lrow], 1u);
+          rec.x = __float_as_uint(v);
+        } else {
+          rec.y = 0xffffffffu;   // screened in by the slack only
         }
-        __builtin_amdgcn_sched_barrier(0);   // keep the 32 row-record loads from being hoisted (register pressure)
+        wlist[t] = rec;
       }
-  }
-  // PERSIST: this wave's DMA pieces of the next tile's head have landed by now (requested before pass 1; loads retire
-  // in order); the barrier below makes that true for every wave, so the next tile starts without a memory wait
-  if (PERSIST) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (tid < BM) {
-    const uint32_t c = rowcnt[tid];
-    rowcnt[tid] = (c > 0u) ? atomicAdd(&cand_cnt[m0 + tid], c) : 0u;  // rows >= M never count
-  }
-  __syncthreads();
-  for (uint32_t t = (uint32_t)l; t < n_w; t += 64u) {
-    const uint2 rec = wlist[t];
-    if (rec.y != 0xffffffffu) {
-      const int lrow = (int)(rec.y >> 16);
-      const uint32_t slot = atomicAdd(&rowcnt[lrow], 1u);
-      if (slot < (uint32_t)cap) {
-        const int64_t row = m0 + lrow;
-        cand_d2[row * cap + slot] = __uint_as_float(rec.x);
-        cand_id[row * cap + slot] = (uint32_t)grow(n0 + (int64_t)(rec.y & 0xffffu));
+      const bool dense = wave_cnt > (uint32_t)LCAP;   // wave-uniform
+      if (dense) {
+        // (the scale is laundered through an empty asm so that the compiler does not keep 128 values of pass 1 or of this
+        //  walk alive for the next one: that spilled the common path)
+        float isc = inv_scale;
+        asm volatile("" : "+v"(isc));
+#pragma unroll
+        for (int mt = 0; mt < TM; ++mt)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) {
+            const int lrow = wm * (32 * TM) + mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * kk;
+#pragma unroll
+            for (int nt = 0; nt < TN; ++nt) {
+              const float4 rr = rrec[lrow];
+              const float v = BIAS ? __fmaf_rn(-2.f, acc[mt][nt][r] * isc, rr.x)
+                                   : sv_d2_screen(rr.x, cn[nt], acc[mt][nt][r] * isc);
+              if (v <= rr.y && v < INFINITY) atomicAdd(&rowcnt[lrow], 1u);
+            }
+            __builtin_amdgcn_sched_barrier(0);   // keep the 32 row-record loads from being hoisted (register pressure)
+          }
       }
-    }
-  }
-  if (dense) {
-    float isc = inv_scale;
-    asm volatile("" : "+v"(isc));
+      // PERSIST: this wave's DMA pieces of the next tile's head have landed by now (requested before pass 1; loads retire
+      // in order); the barrier below makes that true for every wave, so the next tile starts without a memory wait
+      if (PERSIST) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __syncthreads();
+      if (tid < BM) {
+        const uint32_t c = rowcnt[tid];
+        rowcnt[tid] = (c > 0u) ? atomicAdd(&cand_cnt[m0 + tid], c) : 0u;  // rows >= M never count
+      }
+      __syncthreads();
+      for (uint32_t t = (uint32_t)l; t < n_w; t += 64u) {
+        const uint2 rec = wlist[t];
+        if (rec.y != 0xffffffffu) {
+          const int lrow = (int)(rec.y >> 16);
+          const uint32_t slot = atomicAdd(&rowcnt[lrow], 1u);
+          if (slot < (uint32_t)cap) {
+            const int64_t row = m0 + lrow;
+            cand_d2[row * cap + slot] = __uint_as_float(rec.x);
+            cand_id[row * cap + slot] = (uint32_t)grow(n0 + (int64_t)(rec.y & 0xffffu));
+          }
+        }
+      }
+      if (dense) {
+        float isc = inv_scale;
+        asm volatile("" : "+v"(isc));
 #pragma unroll
-    for (int mt = 0; mt < TM; ++mt)
+        for (int mt = 0; mt < TM; ++mt)
 #pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int lrow = wm * (32 * TM) + mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * kk;
+          for (int r = 0; r < 16; ++r) {
+            const int lrow = wm * (32 * TM) + mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * kk;
 #pragma unroll
-        for (int nt = 0; nt < TN; ++nt) {
-          const float4 rr = rrec[lrow];
-          {
-            const float v = BIAS ? __fmaf_rn(-2.f, acc[mt][nt][r] * isc, rr.x)
-                                 : sv_d2_screen(rr.x, cn[nt], acc[mt][nt][r] * isc);
-            if (v <= rr.y && v < INFINITY) {
-              const uint32_t slot = atomicAdd(&rowcnt[lrow], 1u);
-              if (slot < (uint32_t)cap) {
-                const int64_t row = m0 + lrow;
-                cand_d2[row * cap + slot] = v;
-                cand_id[row * cap + slot] = (uint32_t)grow(n0 + wn * (32 * TN) + nt * 32 + i);
+            for (int nt = 0; nt < TN; ++nt) {
+              const float4 rr = rrec[lrow];
+              {
+                const float v = BIAS ? __fmaf_rn(-2.f, acc[mt][nt][r] * isc, rr.x)
+                                     : sv_d2_screen(rr.x, cn[nt], acc[mt][nt][r] * isc);
+                if (v <= rr.y && v < INFINITY) {
+                  const uint32_t slot = atomicAdd(&rowcnt[lrow], 1u);
+                  if (slot < (uint32_t)cap) {
+                    const int64_t row = m0 + lrow;
+                    cand_d2[row * cap + slot] = v;
+                    cand_id[row * cap + slot] = (uint32_t)grow(n0 + wn * (32 * TN) + nt * 32 + i);
+                  }
+                }
               }
             }
+            __builtin_amdgcn_sched_barrier(0);
           }
-        }
-        __builtin_amdgcn_sched_barrier(0);
       }
-  }
-  }   // EPI == 0
-  SV_PHASE(5)  // reservation + pass 2b
-  if (!PERSIST || seq_next >= seq_total) break;
-  seq = seq_next;
-  tm = tm_next;
-  tn = tn_next;
-  rev = rev_of(seq);
+    }   // EPI == 0
+    SV_PHASE(5)  // reservation + pass 2b
+    if (!PERSIST || seq_next >= seq_total) break;
+    seq = seq_next;
+    tm = tm_next;
+    tn = tn_next;
+    rev = rev_of(seq);
   }   // tile loop
+#undef SV_F16_NEXT_TILE
 }
 
 template <class C>
@@ -1550,18 +1039,10 @@ static int launch_f16_filter(segvlad_ctx* ctx, const uint16_t* Qh, const uint16_
                              float inv_scale, const float* qn, const float* rn, const float* thr, int64_t thr_ld,
                              float eps_mult, float c_eps, float rn_max, uint32_t* cand_cnt, float* cand_d2, uint32_t* cand_id,
                              int cap) {
-  constexpr int BM = C::BM, BN = C::BN, WM = C::WM, WN = C::WN, HBK = SV_F16_HBK, NB = SV_F16_NB, KFL = C::KFL;
+  constexpr int BM = C::BM, BN = C::BN, WM = C::WM, WN = C::WN, KFL = C::KFL;
   constexpr bool PERSIST = C::PERSIST;
   const int tiles_m = (M + BM - 1) / BM, tiles_n = (n_sample + BN - 1) / BN;
-  int64_t tiles = (int64_t)tiles_m * tiles_n;
-  // tile-block height of the XCD-aware order (0 = plain tm-fastest order).  Every database tile is fetched once per
-  // block ROW of query tiles: with >= 16 query tiles (one pass over 10 000 queries has 40) blocks of 8 x 4 halve that
-  // re-read against 4 x 8 (10 -> 5 fetches of the fp16 plane per launch) at the same speed; 16 x 2 is 14 % slower (the 16
-  // query tiles no longer stay in the XCD's L2).
-  int gm = ctx->opt.f16_gm >= 0 ? ctx->opt.f16_gm : (tiles_m >= 16 ? 8 : 4);
-  if (PERSIST && gm <= 0) gm = 4;
-  int seq_total = 0;
-  // tile walk of the persistent kernel (see the kernel): bit 0 = query-block-resident order, bit 1 = serpentine k
+  // tile walk of the persistent kernel (f16_walk.h): bit 0 = query-block-resident order, bit 1 = serpentine k
   // default 3: measured on 10 000 x 1 M x 1024 (rocprofv3 FETCH_SIZE, calibrated; tools/pmc_walk.sh): L2 fills of the full-level
   // launch 42.7 GB (walk 0) / 45.1 GB (2: serpentine alone) / 26.3 GB (3), at the same speed (18.39 / 18.34 ms per search's filter
   // launches, interleaved A/B)
@@ -1570,34 +1051,19 @@ static int launch_f16_filter(segvlad_ctx* ctx, const uint16_t* Qh, const uint16_
   // launch either way (a query block is 8 x 50 MB there: "resident" means nothing at that depth, and the resident order makes the 32
   // workgroups of an XCD meet a NEW database block at every step)
   int walk = PERSIST ? (ctx->opt.f16_walk >= 0 ? (ctx->opt.f16_walk & 7) : (KFL > 0 ? 2 : 3)) : 0;
+  // 8 XCDs x 32 (option f16_persist_wgs) resident workgroups, each walks its XCD's sequence
   const int pwgs = (ctx->opt.f16_persist_wgs >= 1 && ctx->opt.f16_persist_wgs <= 32) ? ctx->opt.f16_persist_wgs : 32;
   if (PERSIST) walk |= pwgs << 8;
-  if (gm > 0) {
-    gm = gm >= 32 ? 32 : gm >= 16 ? 16 : gm >= 8 ? 8 : gm >= 4 ? 4 : gm >= 2 ? 2 : 1;
-    while (gm > 1 && gm / 2 >= tiles_m) gm >>= 1;
-    const int gn = 32 / gm;
-    int64_t st = (int64_t)((tiles_m + gm - 1) / gm) * ((tiles_n + gn - 1) / gn);
-    if (walk & 1) {   // per XCD: query blocks x its share of the database blocks, + its share of the left-over pairs (see the kernel)
-      const int64_t smc = (tiles_m + gm - 1) / gm, snc = (tiles_n + gn - 1) / gn, nbf = snc / 8, rem = snc - 8 * nbf;
-      st = (smc * nbf + (smc * rem + 7) / 8) * 8;
-    }
-    tiles = (st + 7) / 8 * 8 * 32;
-    if (tiles / 8 > 0x7fffffffLL) return ctx->fail(SEGVLAD_ERR_LIMIT, "f16 filter: too many tiles");
-    seq_total = (int)(tiles / 8);
-    if (PERSIST) tiles = 8 * pwgs;   // 8 XCDs x 32 (option f16_persist_wgs) resident workgroups, each walks its XCD's sequence
-  }
-  if (tiles > 0x7fffffffLL) return ctx->fail(SEGVLAD_ERR_LIMIT, "f16 filter: too many tiles");
-  size_t lds = 2 * (size_t)BM * HBK * 2 + (size_t)NB * BN * HBK * 2;  // two A stages + NB B stages
-  if (!PERSIST && C::EPI == 0) {  // epilogue: row records + per-row counters + one survivor list per wave
-    constexpr int TMl = BM / (32 * WM), TNl = BN / (32 * WN);
-    constexpr int LCAPl = (TMl * TNl * 256 < 2048) ? TMl * TNl * 256 : 2048;
-    const size_t elds = (size_t)BM * 24 + (size_t)BN * 4 + (size_t)WM * WN * (LCAPl + 1) * 8;
-    if (lds < elds) lds = elds;
-  }
+  // (option f16_gm: the walk's block height; 0 = plain tm-fastest order, which the persistent kernels do not have)
+  const F16Walk g = f16_walk_geometry(tiles_m, tiles_n, (PERSIST && ctx->opt.f16_gm == 0) ? 4 : ctx->opt.f16_gm, walk);
+  const int64_t tiles = f16_walk_grid(g, PERSIST ? pwgs : 0);
+  if (g.seq_total > 0x7fffffffLL || tiles > 0x7fffffffLL) return ctx->fail(SEGVLAD_ERR_LIMIT, "f16 filter: too many tiles");
+  const int gm = g.gm, seq_total = (int)g.seq_total;
+  const size_t lds = F16Lds<C>::BYTES;
   auto kern = knn_f16_filter_kernel<C>;
   float* kscr = nullptr;
-  if (KFL > 0) {   // one slice of 128 x 64 fp32 per resident wave, all zero between tiles (the kernel leaves it so); zeroed here as well
-    const size_t bytes = (size_t)tiles * (WM * WN) * 128 * 64 * 4;
+  if (KFL > 0) {   // one slice per resident wave, all zero between tiles (the kernel leaves it so); zeroed here as well
+    const size_t bytes = (size_t)tiles * (WM * WN) * SV_F16_KSCR_FLOATS * 4;
     SV_HIP(ctx->s_kflush.reserve(bytes));
     SV_HIP(hipMemsetAsync(ctx->s_kflush.p, 0, bytes, ctx->stream));
     kscr = ctx->s_kflush.as<float>();
@@ -1728,120 +1194,4 @@ int sv_launch_f16_filter(segvlad_ctx* ctx, const uint16_t* Qh, const uint16_t* R
   }
 #endif
   return f16_with_config(c.kernel, launch);
-}
-
-// ---- max of the database row norms (margin scale) -------------------------------------------------------------
-// Both reductions order the values by their keys, where a NaN sorts above +inf or -- sign bit set -- below 0.0.  For the search
-// (FINITE_ONLY; min_kernel always) NaN and Inf norms -- rows that are never listed -- do not count, or one such row would take the
-// margin's scale from every other row; segvlad_set_vocab keeps the plain maximum.
-__device__ __forceinline__ bool norm_counts_(float v) { return (__float_as_uint(v) & 0x7fffffffu) < 0x7f800000u; }
-template <bool FINITE_ONLY>
-__global__ __launch_bounds__(256) void max_kernel(const float* __restrict__ x, int64_t n, uint32_t* __restrict__ out) {
-  uint32_t m = 0;
-  for (int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x; j < n; j += (int64_t)gridDim.x * 256) {
-    const float v = x[j];
-    if (!FINITE_ONLY || norm_counts_(v)) m = max(m, f2key_(v));
-  }
-  for (int o = 32; o > 0; o >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, o));
-  if ((threadIdx.x & 63) == 0) atomicMax(out, m);
-}
-
-__global__ __launch_bounds__(256) void min_kernel(const float* __restrict__ x, int64_t n, uint32_t* __restrict__ out) {
-  uint32_t m = 0xffffffffu;
-  for (int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x; j < n; j += (int64_t)gridDim.x * 256) {
-    const float v = x[j];
-    if (norm_counts_(v)) m = min(m, f2key_(v));
-  }
-  for (int o = 32; o > 0; o >>= 1) m = min(m, (uint32_t)__shfl_xor((int)m, o));
-  if ((threadIdx.x & 63) == 0) atomicMin(out, m);
-}
-
-// smallest of n non-negative values (the query batch's smallest squared norm), read back to the host (synchronises)
-int sv_row_norm_min(segvlad_ctx* ctx, const float* norms, int64_t n, float* out_host) {
-  SV_HIP(ctx->s_minmax.reserve(32));
-  uint32_t* mm = ctx->s_minmax.as<uint32_t>() + 6;
-  SV_HIP(hipMemsetAsync(mm, 0xff, 4, ctx->stream));
-  int blocks = (int)((n + 255) / 256);
-  if (blocks > 1024) blocks = 1024;
-  if (n > 0) hipLaunchKernelGGL(min_kernel, dim3(blocks), dim3(256), 0, ctx->stream, norms, n, mm);
-  uint32_t key = 0;
-  SV_HIP(hipMemcpyAsync(&key, mm, 4, hipMemcpyDeviceToHost, ctx->stream));
-  SV_HIP(hipStreamSynchronize(ctx->stream));
-  const uint32_t u = (key & 0x80000000u) ? (key & 0x7fffffffu) : ~key;
-  float f;
-  memcpy(&f, &u, 4);
-  *out_host = (n > 0 && key != 0xffffffffu) ? f : 0.f;
-  return SEGVLAD_OK;
-}
-
-int sv_ensure_pinned_words(segvlad_ctx* ctx) {
-  if (!ctx->h_pin) {
-    SV_HIP(hipHostMalloc(reinterpret_cast<void**>(&ctx->h_pin), 64, hipHostMallocDefault));
-    for (int j = 0; j < 16; ++j) ctx->h_pin[j] = 0u;
-    SV_HIP(hipEventCreateWithFlags(&ctx->ev_scalars, hipEventDisableTiming));
-  }
-  return SEGVLAD_OK;
-}
-
-// max |x| of a block (finite values), the smallest and the largest finite of a list of row norms and the block's non-finite flag
-// behind ONE read-back, WITHOUT a wait in between: _begin enqueues the reductions and the copy into pinned words of the
-// context and records an event behind them; _end blocks on that event only.  What the caller enqueues between the two runs on
-// the device while the host waits.
-int sv_maxabs_and_norm_min_begin(segvlad_ctx* ctx, const float* x, int64_t n, const float* norms, int64_t n_norms) {
-  SV_HIP(ctx->s_minmax.reserve(32));
-  SV_TRY(sv_ensure_pinned_words(ctx));
-  uint32_t* mm = ctx->s_minmax.as<uint32_t>() + 4;   // [4] = finite max |x| bits (init 0), [5] = min key (init all ones), [6] = non-finite flag
-  static const uint32_t init[4] = {0u, 0xffffffffu, 0u, 0u};   // ..., [7] = max finite norm key
-  SV_HIP(hipMemcpyAsync(mm, init, 16, hipMemcpyHostToDevice, ctx->stream));
-  int64_t blocks = (n + 1023) / 1024;
-  if (blocks > 1024) blocks = 1024;
-  if (n > 0) hipLaunchKernelGGL((maxabs_kernel<true, true>), dim3((unsigned)blocks), dim3(256), 0, ctx->stream, x, n, mm);
-  int nb = (int)((n_norms + 255) / 256);
-  if (nb > 1024) nb = 1024;
-  if (n_norms > 0) hipLaunchKernelGGL(min_kernel, dim3(nb), dim3(256), 0, ctx->stream, norms, n_norms, mm + 1);
-  if (n_norms > 0) hipLaunchKernelGGL(max_kernel<true>, dim3(nb), dim3(256), 0, ctx->stream, norms, n_norms, mm + 3);
-  SV_HIP(hipGetLastError());
-  SV_HIP(hipMemcpyAsync(ctx->h_pin, mm, 16, hipMemcpyDeviceToHost, ctx->stream));
-  SV_HIP(hipEventRecord(ctx->ev_scalars, ctx->stream));
-  return SEGVLAD_OK;
-}
-
-static float key_to_float(uint32_t key) {
-  const uint32_t u = (key & 0x80000000u) ? (key & 0x7fffffffu) : ~key;
-  float f;
-  memcpy(&f, &u, 4);
-  return f;
-}
-
-int sv_maxabs_and_norm_min_end(segvlad_ctx* ctx, int64_t n, int64_t n_norms, float* maxabs_host, float* norm_min_host, bool* nonfinite_host,
-                               float* norm_max_host) {
-  SV_HIP(hipEventSynchronize(ctx->ev_scalars));
-  const uint32_t h0 = ctx->h_pin[0], h1 = ctx->h_pin[1];
-  memcpy(maxabs_host, &h0, 4);
-  if (n <= 0) *maxabs_host = 0.f;
-  *nonfinite_host = n > 0 && ctx->h_pin[2] != 0u;
-  *norm_max_host = (n_norms > 0 && ctx->h_pin[3] != 0u) ? key_to_float(ctx->h_pin[3]) : 0.f;
-  const uint32_t u = (h1 & 0x80000000u) ? (h1 & 0x7fffffffu) : ~h1;
-  float f;
-  memcpy(&f, &u, 4);
-  *norm_min_host = (n_norms > 0 && h1 != 0xffffffffu) ? f : 0.f;
-  return SEGVLAD_OK;
-}
-
-int sv_row_norm_max(segvlad_ctx* ctx, const float* norms, int64_t n, float* out_host, bool finite_only) {
-  SV_HIP(ctx->s_minmax.reserve(16));
-  uint32_t* mm = ctx->s_minmax.as<uint32_t>() + 2;
-  SV_HIP(hipMemsetAsync(mm, 0, 4, ctx->stream));
-  int blocks = (int)((n + 255) / 256);
-  if (blocks > 1024) blocks = 1024;
-  if (n > 0 && finite_only) hipLaunchKernelGGL(max_kernel<true>, dim3(blocks), dim3(256), 0, ctx->stream, norms, n, mm);
-  else if (n > 0) hipLaunchKernelGGL(max_kernel<false>, dim3(blocks), dim3(256), 0, ctx->stream, norms, n, mm);
-  uint32_t key = 0;
-  SV_HIP(hipMemcpyAsync(&key, mm, 4, hipMemcpyDeviceToHost, ctx->stream));
-  SV_HIP(hipStreamSynchronize(ctx->stream));
-  const uint32_t u = (key & 0x80000000u) ? (key & 0x7fffffffu) : ~key;
-  float f;
-  memcpy(&f, &u, 4);
-  *out_host = (n > 0 && key != 0) ? f : 0.f;
-  return SEGVLAD_OK;
 }

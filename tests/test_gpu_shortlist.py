@@ -7,7 +7,7 @@ import pytest
 import torch
 from conftest import engine_scope
 
-import fp32_emu as E
+from shortlist_cases import _brute
 
 pytestmark = pytest.mark.gpu
 
@@ -24,25 +24,6 @@ def eng():
 
 def _unit(x):
     return (x / np.linalg.norm(x, axis=1, keepdims=True)).astype(np.float32)
-
-
-def _brute(Q, R, img, qoff, shortlist, k):
-    """Host reference: per query row, the rows whose image is in its image's shortlist, emulated fp32 distances,
-    (distance, id) order, (+inf, -1) padding."""
-    qn, rn = E.row_sumsq(Q), E.row_sumsq(R)
-    nq = Q.shape[0]
-    d2 = np.full((nq, k), np.inf, np.float32)
-    ids = np.full((nq, k), -1, np.int64)
-    for b in range(len(qoff) - 1):
-        allowed = np.nonzero(np.isin(img, shortlist[b][shortlist[b] >= 0]))[0]
-        for q in range(qoff[b], qoff[b + 1]):
-            if not len(allowed):
-                continue
-            dd = E.d2(qn[q], rn[allowed], E.dot_chain(Q[q], R[allowed]))
-            o = np.lexsort((allowed, dd))[:k]
-            d2[q, :len(o)] = dd[o]
-            ids[q, :len(o)] = allowed[o]
-    return d2, ids
 
 
 def _check(got, want):

@@ -11,7 +11,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB_DIR = os.path.join(HERE, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libsegvlad_hip.so")
 SOURCES = ["api.hip", "describe.hip", "search.hip", "mask_kernels.hip", "assign_kernels.hip", "vlad_kernels.hip", "block_norm_kernels.hip", "gemm_kernels.hip", "select_kernels.hip", "vote_kernels.hip",
-           "knn_filter_kernels.hip", "knn_bf16_filter_kernels.hip", "knn_operand_kernels.hip", "knn_candidate_kernels.hip", "gemm_f16x3_kernels.hip", "project_kernels.hip", "comm.hip", "refine_group_kernels.hip", "small_pass_kernels.hip", "kmeans_kernels.hip",
+           "knn_filter_kernels.hip", "knn_bf16_filter_kernels.hip", "knn_operand_kernels.hip", "knn_select_kernels.hip", "knn_refine_kernels.hip", "gemm_f16x3_kernels.hip", "project_kernels.hip", "comm.hip", "refine_group_kernels.hip", "small_pass_kernels.hip", "kmeans_kernels.hip",
            "shortlist_kernels.hip", "remove_kernels.hip", "exclude_kernels.hip", "range_kernels.hip", "match_kernels.hip", "group_kernels.hip", "verify_kernels.hip",
            "sequence_kernels.hip", "rle_kernels.hip", "rle_encode_kernels.hip", "regions_kernels.hip", "soft_vlad_kernels.hip", "burst_kernels.hip", "burst_seg_kernels.hip"]
 

@@ -282,6 +282,7 @@ struct OpenDescribe {
   int slot = 0;
 };
 
+constexpr int SV_PIN_TOTALS = 8;   // word of segvlad_ctx::h_pin that mirrors the single-image pass's totals (layout: small_pass_dev.h)
 struct segvlad_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -289,7 +290,8 @@ struct segvlad_ctx {
   // `stream` behind an event and joined back before anything else is enqueued (sv_fork_side / sv_join_side); created on first use
   hipStream_t side = nullptr;
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-  uint32_t* h_pin = nullptr;          // 64 pinned bytes: scalars read back behind an event instead of a stream synchronisation
+  uint32_t* h_pin = nullptr;          // 64 pinned bytes: scalars read back behind an event instead of a stream synchronisation;
+                                      // words SV_PIN_TOTALS, + 1: the single-image pass's running totals (small_pass_dev.h)
   hipEvent_t ev_scalars = nullptr;
   unsigned char* h_desc = nullptr;    // pinned: the per-image flags and the centroids of a segvlad_describe_begin
   size_t h_desc_cap = 0;
@@ -322,7 +324,7 @@ struct segvlad_ctx {
   int64_t db_rn_max_rows = 0;
   bool f16_bias_ok = false;   // this search's batch filter launches may use the biased-accumulator kernel (segvlad_search)
   const float* f16_scale_dev = nullptr;   // set by segvlad_search for the duration of a single-image search (see above)
-  // small_head_kernel's grid barrier: arrivals on the device counter (s_tail_tick words 132-133) of every head launched on this
+  // small_head_kernel's grid barrier: arrivals on the device counter (s_tail_tick's last two words: small_pass_dev.h) of every head launched on this
   // context -- the next launch's target is this + its grid size (stream order: see segvlad_set_stream)
   uint64_t small_head_arrivals = 0;
   bool small_head_ran = false;   // this search's pass started with small_head_kernel (which also repairs a poisoned hand-over buffer)
@@ -345,7 +347,7 @@ struct segvlad_ctx {
   // through two pinned words that segvlad_search looks at WITHOUT synchronising -- a database on which the low-rank thresholds
   // keep failing is switched to the rigorous plan one or two calls late instead of never
   const uint32_t* tail_stats_dev = nullptr;   // [4]: rows redone by brute force, second-tier rows, hand-over failures; null = none pending
-  uint32_t tail_fail_base = 0;                // h_pin[8] when the index last changed
+  uint32_t tail_fail_base = 0;                // h_pin[SV_PIN_TOTALS] when the index last changed
   int64_t tail_rows_since = 0;                // query rows sent through device-driven passes since then
 
   // Device buffers, as X-macro lists (segvlad_create tags them, segvlad_destroy releases them, guard mode walks them).
@@ -603,7 +605,7 @@ int sv_launch_bf16_filter(segvlad_ctx* ctx, const uint16_t* Qh, const uint16_t* 
                           int M, int n_sample, int d, int b_stride, const float* qn, const float* rn, const float* thr,
                           int64_t thr_ld, float eps_mult, float c_eps, float rn_max, uint32_t* cand_cnt, float* cand_d2,
                           uint32_t* cand_id, int cap);
-// knn_candidate_kernels.hip (the filters' candidate lists: select, exact refinement; sv_launch_l0_reduce_rank above lives there too)
+// knn_select_kernels.hip (the filters' candidate lists ranked; sv_launch_l0_reduce_rank above lives there too)
 // A select ranks every row's candidate list and then decides what its order statistic A (the k-th smallest d2~) means:
 //   Threshold  thr_out[row] = A, the next level's threshold; cnt[row] is ZEROED (the next level's filter appends from zero, no
 //              memset launch between the levels).
@@ -646,6 +648,7 @@ struct SvSelectArgs {
 int sv_launch_select_approx(segvlad_ctx* ctx, int nq, const SvSelectArgs& a);
 int sv_launch_refine2_compact(segvlad_ctx* ctx, const uint32_t* rovf_rows, const float* ref_lim, uint32_t* cand_cnt,
                               const float* cand_d2, uint32_t* cand_id, int nq, int cap);
+// knn_refine_kernels.hip (the refine lists evaluated exactly)
 // only_rows != null: rows whose flag is clear are skipped (their outputs stay as they are)
 // fail_rows / fail_count / poison_dev (optional): the single-image refinement hands keys between workgroups through global
 // memory and CHECKS the hand-over (refine_exact_small_kernel): a query whose keys did not all arrive is flagged there like
@@ -658,11 +661,12 @@ int sv_launch_refine_exact(segvlad_ctx* ctx, const float* Q, const float* R, int
                            const uint32_t* ref_cnt, const uint32_t* ref_id, int rcap, int k, float* d2_out, int64_t* idx_out,
                            const uint32_t* only_rows = nullptr, uint32_t* fail_rows = nullptr, uint32_t* fail_count = nullptr,
                            const uint32_t** poison_dev = nullptr, const SvSmallFinish* fz = nullptr, bool* fused_done = nullptr);
-int sv_small_words(segvlad_ctx* ctx);   // ctx->s_tail_tick: [129] tail tickets, [2] totals, pad, the head's 64-bit arrival counter
+int sv_refine_small_repair(segvlad_ctx* ctx);
+// small_pass_kernels.hip
+int sv_small_words(segvlad_ctx* ctx);   // ctx->s_tail_tick reserved and zeroed (its words: small_pass_dev.h)
 // tests only (option debug_small_tail): force the flags of a pass that needed none
 int sv_launch_small_tail_debug(segvlad_ctx* ctx, int m, uint32_t* fail_rows, uint32_t* fail_count, uint32_t* rovf_rows, float* ref_lim);
-int sv_refine_small_repair(segvlad_ctx* ctx);
-// small_pass_kernels.hip: the device-driven tail of a single-image pass (<= 128 rows): launched behind the refinement, returns at
+// the device-driven tail of a single-image pass (<= 128 rows): launched behind the refinement, returns at
 // once when fail_count[0] == fail_count[1] == 0, else finishes the flagged rows on the device (second tier from the candidate
 // lists; exact brute force for rows flagged for a redo) -- the search needs no read-back.  stats: [4] device words of this search.
 int sv_launch_small_tail(segvlad_ctx* ctx, const float* Q, const float* R, const float* qn, const float* rn, int64_t n, int d, int m, int k,

@@ -16,7 +16,7 @@
 //                            16-B coalesced global loads -> registers -> XOR-swizzled LDS (conflict-free
 //                            ds_read_b128 fragments), double-buffered LDS, two register stages in flight;
 //                            epilogue appends (d2~, id) with d2~ <= thr + margin to the candidate lists
-// (select_approx_kernel, refine_exact_kernel and the single-image forms of both: knn_candidate_kernels.hip)
+// (select_approx_kernel, refine_exact_kernel and the single-image forms of both: knn_select_kernels.hip, knn_refine_kernels.hip)
 #include "ctx.h"
 #include "knn_dev.h"
 #include "mfma_f32_dev.h"

@@ -1,21 +1,14 @@
-// Device helpers shared by the search's translation units: the order-preserving float <-> key map (its only definition), the
-// workgroup bitonic sort of keys or (key << 32 | id) words, DPP wave reductions, the flagging of a row; the counted waits of the
-// filter's DMA loops come with it (waitcnt_dev.h).
+// Device helpers shared by the search's translation units: the (distance, id) word and its order-preserving float <-> key map
+// (key_word.h, their only definition), the workgroup bitonic sort of keys or words and the top-k write-out behind it, the exact
+// fp32 chain in its two shapes (a row in global memory, a row of an LDS tile), DPP wave reductions, the flagging of a row; the
+// counted waits of the filter's DMA loops come with it (waitcnt_dev.h).
 #pragma once
 #include <stdint.h>
 
 #include <hip/hip_runtime.h>
 
+#include "key_word.h"
 #include "waitcnt_dev.h"
-
-__device__ __forceinline__ uint32_t f2key_(float f) {
-  const uint32_t u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float key2f_(uint32_t k) {
-  const uint32_t u = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k;
-  return __uint_as_float(u);
-}
 
 // a row redone on another path: marked once in its flag word, counted once
 __device__ __forceinline__ void sv_flag_once_(uint32_t* rows, uint32_t* count, int64_t row) {
@@ -67,9 +60,30 @@ __device__ __forceinline__ void sv_bitonic(T* a, int n, int tid) {
   __syncthreads();
 }
 
-// The exact chain of every distance the search reports: the sequential fp32 fma dot product over k = 0 .. 4 n4 - 1 (what
-// refine_exact_kernel evaluates, bit for bit the fp32 distance GEMM's chain), with U 16-byte loads of the index row in flight
-// per lane (n4 % U == 0); the query row sits in LDS.
+// The write-out of every exact path: the k result slots of row `row` from the ascending words a[0 .. len) -- the entries, then
+// (+inf, -1).  UNTIL_NONE = false: the first len words are real; true: real until the first empty word.  k > len is fine in both.
+// (The row index, not the row's pointers: with d2_out + row * k formed by the caller hipcc moves the address arithmetic of the
+//  refinement kernels to the scalar unit and their instruction text changes.)
+template <bool UNTIL_NONE>
+__device__ __forceinline__ void sv_write_topk(const uint64_t* a, int len, int k, float* __restrict__ d2_out, int64_t* __restrict__ idx_out,
+                                              int64_t row, int tid) {
+  for (int j = tid; j < k; j += 256) {
+    float dd = INFINITY;
+    int64_t id = -1;
+    if (j < len && (!UNTIL_NONE || a[j] != SV_WORD_NONE)) {
+      dd = sv_word_d2(a[j]);
+      id = sv_word_id(a[j]);
+    }
+    d2_out[row * k + j] = dd;
+    idx_out[row * k + j] = id;
+  }
+}
+
+// The exact chain of every distance the search reports: the sequential fp32 fma dot product over k = 0 .. 4 n4 - 1 (bit for bit the
+// chain of v_mfma_f32_32x32x2_f32 on the matrix path), with U 16-byte loads of the index row in flight per lane (n4 % U == 0); the
+// query row sits in LDS or in global memory.  U = 32 is refine_exact_kernel's walk: 512 B of the row in flight per lane, 8 round
+// trips for a 1024-d row -- a 50-query pass has fewer waves than the chip has SIMDs, so the loop is pure load latency (an 8-deep
+// register double buffer still paid one round trip per 128 B: 78 us per pass).
 template <int U>
 __device__ __forceinline__ float sv_dot_seq_(const float4* qp, const float4* __restrict__ rp, int n4) {
   float acc = 0.f;
@@ -77,7 +91,9 @@ __device__ __forceinline__ float sv_dot_seq_(const float4* qp, const float4* __r
     float4 buf[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) buf[u] = rp[t + u];
-    __builtin_amdgcn_sched_barrier(0);   // every load is issued before the first fma (see refine_exact_kernel)
+    // all U loads are issued before the first fma (the scheduler otherwise sinks them next to their uses to save registers -- and
+    // pays the latency U times); U = 1 holds nothing back: the compiler unrolls that loop itself
+    if constexpr (U > 1) __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const float4 qv = qp[t + u];
@@ -89,6 +105,24 @@ __device__ __forceinline__ float sv_dot_seq_(const float4* qp, const float4* __r
   }
   return acc;
 }
+
+// The same chain for one lane walking ONE ROW of an LDS tile (tr_: the row, n4_ float4s) against query floats in LDS (qb_: broadcast
+// reads), UNROLL float4s per trip; acc carries the chain from step to step.  A statement macro: as a force-inlined function template
+// refine_exact_wide_kernel<128, 4> comes out with other registers and 254 -> 256 VGPRs (the named rings around it leave no slack).
+#define SV_PRAGMA_(x) _Pragma(#x)
+#define SV_LDS_ROW_WALK(tr_, qb_, n4_, UNROLL, acc)                      \
+  {                                                                      \
+    const float* tr = (tr_);                                             \
+    const float* qb = (qb_);                                             \
+    SV_PRAGMA_(unroll UNROLL) for (int s4 = 0; s4 < (n4_); ++s4) {       \
+      const float4 rv = *reinterpret_cast<const float4*>(tr + s4 * 4);   \
+      const float4 qv = *reinterpret_cast<const float4*>(qb + s4 * 4);   \
+      acc = fmaf(qv.x, rv.x, acc);                                       \
+      acc = fmaf(qv.y, rv.y, acc);                                       \
+      acc = fmaf(qv.z, rv.z, acc);                                       \
+      acc = fmaf(qv.w, rv.w, acc);                                       \
+    }                                                                    \
+  }
 
 // sum over the 64 lanes, returned wave-uniform: quad swaps, half-row and row mirrors (DPP: no LDS crossbar), then the four
 // row sums through readlane

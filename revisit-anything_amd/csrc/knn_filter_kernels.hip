@@ -6,7 +6,7 @@
 //   sv_choose_f16_kernel      which kernel a launch takes: the ONE place that knows the rule; f16_with_config maps the choice to its type
 //   sv_launch_f16_filter      the entry; sv_f16_filter_skip_ok and sv_f16_eps_kblock ask the same rule
 // (operand planes and scales: knn_operand_kernels.hip; the bf16x3 filter for d % 64 != 0: knn_bf16_filter_kernels.hip; what happens to the
-//  candidate lists: knn_candidate_kernels.hip)
+//  candidate lists: knn_select_kernels.hip, knn_refine_kernels.hip)
 #include <stdio.h>
 
 #include "ctx.h"

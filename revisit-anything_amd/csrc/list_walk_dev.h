@@ -28,9 +28,9 @@ struct SvListWords {
   int64_t n;
   __device__ __forceinline__ bool get(int64_t j, float& dd, int64_t& id) const {
     const unsigned long long wd = w[j];
-    dd = key2f_((uint32_t)(wd >> 32));
-    id = (int64_t)(uint32_t)wd;
-    return wd != ~0ull;
+    dd = sv_word_d2(wd);
+    id = sv_word_id(wd);
+    return wd != SV_WORD_NONE;
   }
 };
 

@@ -98,10 +98,9 @@ __global__ __launch_bounds__(256) void range_refine_kernel(const float* __restri
     return;
   }
   const int n = (int)cand_cnt[row];   // <= cap: a longer list flagged its row
-  int np2 = 2;
-  while (np2 < n) np2 <<= 1;
+  const int np2 = sv_np2(n);
   for (int j = tid; j < (d >> 2); j += 256) reinterpret_cast<float4*>(qs)[j] = reinterpret_cast<const float4*>(Q + row * d)[j];
-  for (int j = tid; j < np2; j += 256) a[j] = ~0ull;
+  for (int j = tid; j < np2; j += 256) a[j] = SV_WORD_NONE;
   if (tid == 0) s_hits = 0u;
   __syncthreads();
   const float q2 = qn[row], rad = eff[row];
@@ -111,7 +110,7 @@ __global__ __launch_bounds__(256) void range_refine_kernel(const float* __restri
     const float acc = sv_dot_seq_<U>(qp, reinterpret_cast<const float4*>(R + (size_t)id * d), d >> 2);
     const float v = sv_d2(q2, rn[id], acc);
     if (v < rad) {
-      a[j] = ((uint64_t)f2key_(v) << 32) | id;
+      a[j] = sv_word(v, id);
       atomicAdd(&s_hits, 1u);
     }
   }
@@ -208,7 +207,7 @@ __global__ __launch_bounds__(256) void range_block_kernel(const float* __restric
     slot0 = (uint32_t)__shfl((int)slot0, 0);
     if (hit) {
       const uint32_t pos = slot0 + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull));
-      words[base + pos] = ((unsigned long long)f2key_(v) << 32) | (unsigned long long)(uint32_t)(col0 + j);
+      words[base + pos] = sv_word_key(f2key_(v), (uint32_t)(col0 + j));
     }
   }
 }
@@ -223,8 +222,8 @@ __global__ __launch_bounds__(256) void range_unpack_kernel(const unsigned long l
   const int64_t lo = lims[q], n = lims[q + 1] - lo, so = srcoff[q];
   for (int64_t j = threadIdx.x; j < n; j += 256) {
     const unsigned long long w = src[so + j];
-    d2_out[lo + j] = key2f_((uint32_t)(w >> 32));
-    idx_out[lo + j] = (int64_t)(uint32_t)w;
+    d2_out[lo + j] = sv_word_d2(w);
+    idx_out[lo + j] = sv_word_id(w);
   }
 }
 
@@ -249,8 +248,7 @@ int sv_launch_range_refine(segvlad_ctx* ctx, const float* Q, const float* R, int
                            const uint32_t* flags, uint32_t* cnt, int64_t* soff, uint64_t* stage, uint64_t* cursor) {
   if (m <= 0) return SEGVLAD_OK;
   if (d % 64 != 0) return ctx->fail(SEGVLAD_ERR_STATE, "range refine: d=%d is not a multiple of 64", d);
-  size_t np2 = 2;
-  while (np2 < std::min<size_t>(list_max, (size_t)cap)) np2 <<= 1;
+  const size_t np2 = (size_t)sv_np2((int)std::min<size_t>(list_max, (size_t)cap));
   const size_t lds = (size_t)d * 4 + np2 * 8;
   if (lds > 160 * 1024 - 64) return ctx->fail(SEGVLAD_ERR_LIMIT, "range refine: a %zu-entry list of %d-d rows exceeds the LDS", np2, d);
   auto go = [&](auto kern) -> int {

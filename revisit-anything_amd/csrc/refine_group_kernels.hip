@@ -185,7 +185,7 @@ __global__ __launch_bounds__(256) void refine_group_gemm_kernel(const float* __r
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int q = q0 + 32 * t + sv_frag_row(r, kk);
-        if (q < q_end) keys[(size_t)q * ucap + col] = ((uint64_t)f2key_(sv_d2(qn[q], r2, acc[t][r])) << 32) | id;
+        if (q < q_end) keys[(size_t)q * ucap + col] = sv_word(sv_d2(qn[q], r2, acc[t][r]), id);
       }
   }
 }
@@ -202,20 +202,10 @@ __global__ __launch_bounds__(256) void refine_group_select_kernel(const uint32_t
   if (grp_cnt[row / G] == 0) return;   // the per-row kernels' group
   int n = (int)ref_cnt[row];
   if (n > rcap) n = 0;
-  int np2 = 2;
-  while (np2 < n) np2 <<= 1;
-  for (int j = tid; j < np2; j += 256) a[j] = j < n ? keys[(size_t)row * ucap + grp_pos[(size_t)row * rcap + j]] : ~0ull;
+  const int np2 = sv_np2(n);
+  for (int j = tid; j < np2; j += 256) a[j] = j < n ? keys[(size_t)row * ucap + grp_pos[(size_t)row * rcap + j]] : SV_WORD_NONE;
   sv_bitonic<uint64_t>(a, np2, tid);
-  for (int j = tid; j < k; j += 256) {
-    float dd = INFINITY;
-    int64_t id = -1;
-    if (j < n) {
-      dd = key2f_((uint32_t)(a[j] >> 32));
-      id = (int64_t)(uint32_t)a[j];
-    }
-    d2_out[row * k + j] = dd;
-    idx_out[row * k + j] = id;
-  }
+  sv_write_topk<false>(a, n, k, d2_out, idx_out, row, tid);
 }
 
 }   // namespace
@@ -278,8 +268,7 @@ int sv_launch_refine_grouped(segvlad_ctx* ctx, const float* Q, const float* R, i
     SV_HIP(hipGetLastError());
   }
   {
-    int rpad = 2;
-    while (rpad < rcap) rpad <<= 1;
+    const int rpad = sv_np2(rcap);
     if ((size_t)rpad * 8 + 1024 > 64 * 1024) SV_HIP(sv_max_dyn_lds(reinterpret_cast<const void*>(refine_group_select_kernel), (size_t)rpad * 8));
     hipLaunchKernelGGL(refine_group_select_kernel, dim3(nq), dim3(256), (size_t)rpad * 8, ctx->stream, gcnt, gkeys, ref_cnt,
                        ctx->s_grp_pos.as<uint16_t>(), rcap, G, ucap, k, d2_out, idx_out);

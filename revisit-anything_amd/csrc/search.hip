@@ -32,7 +32,7 @@ static void index_changed(segvlad_ctx* ctx) {
   ctx->sl_map_valid = false;
   ctx->db_heur_off = false;
   if (ctx->tail_rows_since > 0) (void)hipStreamSynchronize(ctx->stream);   // (the tail's pinned totals have landed)
-  ctx->tail_fail_base = ctx->h_pin ? reinterpret_cast<volatile uint32_t*>(ctx->h_pin)[8] : 0u;
+  ctx->tail_fail_base = ctx->h_pin ? reinterpret_cast<volatile uint32_t*>(ctx->h_pin)[SV_PIN_TOTALS] : 0u;
   ctx->tail_rows_since = 0;
 }
 
@@ -1192,7 +1192,7 @@ int sv_search_dev(segvlad_ctx* ctx, const float* q, int nq, int k, float* d2, in
   // of >= 64 rows redone since the index last changed: the sample misleads on this database, stop guessing (as redo_rows
   // decides for its own redos).
   if (ctx->h_pin && ctx->tail_rows_since >= 64) {
-    const uint32_t redone = reinterpret_cast<volatile uint32_t*>(ctx->h_pin)[8] - ctx->tail_fail_base;
+    const uint32_t redone = reinterpret_cast<volatile uint32_t*>(ctx->h_pin)[SV_PIN_TOTALS] - ctx->tail_fail_base;
     if ((int64_t)redone * 4 > ctx->tail_rows_since) ctx->db_heur_off = true;
   }
 

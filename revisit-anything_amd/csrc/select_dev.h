@@ -1,4 +1,4 @@
-// What the selects of the search share (knn_candidate_kernels.hip, select_kernels.hip):
+// What the selects of the search share (knn_select_kernels.hip, select_kernels.hip):
 //   * the row rule of the candidate-list selects (SvSelectArgs, ctx.h): entry test, flagging, band and carry limit, closing a band;
 //   * the binary MSB-first radix select over keys in registers, by a wave or by a workgroup;
 //   * the 8-bit radix select over keys in LDS or memory, with its wave-aggregated histogram.

@@ -144,17 +144,15 @@ __global__ __launch_bounds__(256) void select_cand_kernel(const uint32_t* __rest
     return;
   }
   if (ovf_rows[row]) return;   // flagged at a coarser level: its result comes from the fallback
-  int npad = 2;
-  while (npad < (int)c) npad <<= 1;
-  for (int j = tid; j < npad; j += 256)
-    a[j] = (j < (int)c) ? (((uint64_t)f2key_(cd2[row * cap + j]) << 32) | cid[row * cap + j]) : ~0ull;
+  const int npad = sv_np2((int)c);
+  for (int j = tid; j < npad; j += 256) a[j] = (j < (int)c) ? sv_word(cd2[row * cap + j], cid[row * cap + j]) : SV_WORD_NONE;
   sv_bitonic(a, npad, tid);
   for (int j = tid; j < k; j += 256) {
     float d = INFINITY;
     int64_t id = -1;
     if (j < (int)c) {
-      d = key2f_((uint32_t)(a[j] >> 32));
-      id = (int64_t)(uint32_t)a[j];
+      d = sv_word_d2(a[j]);
+      id = sv_word_id(a[j]);
     }
     d2_out[row * k + j] = d;
     if (idx_out) idx_out[row * k + j] = id;

@@ -99,8 +99,7 @@ __global__ __launch_bounds__(256) void sl_sort_kernel(const int32_t* __restrict_
   const int c = (int)(off[g + 1] - o);
   if (c <= 1) return;
   if (c <= SL_SORT_CAP) {
-    int np2 = 2;
-    while (np2 < c) np2 <<= 1;
+    const int np2 = sv_np2(c);
     for (int j = tid; j < np2; j += 256) a[j] = j < c ? rows[o + j] : 0xffffffffu;
     sv_bitonic<uint32_t>(a, np2, tid);
     for (int j = tid; j < c; j += 256) rows[o + j] = a[j];
@@ -226,7 +225,7 @@ __global__ __launch_bounds__(256) void sl_gemm_kernel(const float* __restrict__ 
   const int U = (int)uo[nu];
   const int tid = threadIdx.x, w = tid >> 6, l = tid & 63, i = l & 31, kk = l >> 5;
   if (tid < 32 * MT) {
-    s_thr[tid] = ~0ull;
+    s_thr[tid] = SV_WORD_NONE;
     s_cnt[tid] = 0u;
   }
   __syncthreads();
@@ -234,9 +233,8 @@ __global__ __launch_bounds__(256) void sl_gemm_kernel(const float* __restrict__ 
   auto compact = [&](int r, int keep) {
     uint64_t* buf = cand + ((size_t)(o0 + r) * S + s) * cap;
     const int n = (int)s_cnt[r];
-    int np2 = 2;
-    while (np2 < n) np2 <<= 1;
-    for (int j = tid; j < np2; j += 256) scratch[j] = j < n ? buf[j] : ~0ull;
+    const int np2 = sv_np2(n);
+    for (int j = tid; j < np2; j += 256) scratch[j] = j < n ? buf[j] : SV_WORD_NONE;
     sv_bitonic<uint64_t>(scratch, np2, tid);
     const int nn = min(n, keep);
     for (int j = tid; j < nn; j += 256) buf[j] = scratch[j];
@@ -287,7 +285,7 @@ __global__ __launch_bounds__(256) void sl_gemm_kernel(const float* __restrict__ 
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
         const int col = l + 64 * h;
-        const uint64_t key = ((uint64_t)dk[r * 128 + col] << 32) | ids[col];
+        const uint64_t key = sv_word_key(dk[r * 128 + col], ids[col]);
         const bool pass = c0 + col < U && key < thr;
         const uint64_t mk = __builtin_amdgcn_ballot_w64(pass);
         if (pass) buf[cnt + __builtin_amdgcn_mbcnt_hi((uint32_t)(mk >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mk, 0u))] = key;
@@ -319,14 +317,14 @@ __global__ __launch_bounds__(256) void sl_final_kernel(const uint64_t* __restric
     for (int j = tid; j < n; j += 256) a[total + j] = buf[j];
     total += n;
   }
-  for (int j = total + tid; j < np2; j += 256) a[j] = ~0ull;
+  for (int j = total + tid; j < np2; j += 256) a[j] = SV_WORD_NONE;
   if (S > 1 || total > 1) sv_bitonic<uint64_t>(a, np2, tid);
   for (int j = tid; j < k; j += 256) {
     float dd = INFINITY;
     int64_t id = -1;
     if (j < total) {
-      dd = key2f_((uint32_t)(a[j] >> 32));
-      id = (int64_t)(uint32_t)a[j];
+      dd = sv_word_d2(a[j]);
+      id = sv_word_id(a[j]);
       if (!(dd < INFINITY)) id = -1;   // (never listed: segvlad.h, "Non-finite rows"; sv_d2 has made a NaN +inf)
     }
     d2_out[q * k + j] = dd;
@@ -419,8 +417,7 @@ static int sl_launch_gemm(segvlad_ctx* ctx, bool ex, const float* Q, const float
                      ctx->db_norms.as<float>(), (const SlGroup*)dgrp, S, M, ctx->sl_img_off.as<uint32_t>(),
                      ctx->sl_img_rows.as<uint32_t>(), uids, uoff, unum, k, cap, cand, lens, flags);
   SV_HIP(hipGetLastError());
-  int np2 = 2;
-  while (np2 < S * k) np2 <<= 1;
+  const int np2 = sv_np2(S * k);
   const size_t flds = (size_t)np2 * 8;
   if (flds > 48 * 1024) SV_HIP(sv_max_dyn_lds(reinterpret_cast<const void*>(sl_final_kernel), flds));
   hipLaunchKernelGGL(sl_final_kernel, dim3((unsigned)n_lists), dim3(256), flds, ctx->stream, cand, lens, S, cap, k, np2, d2_out, idx_out);

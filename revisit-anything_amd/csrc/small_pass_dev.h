@@ -1,12 +1,22 @@
-// Device helpers of the single-image pass's exact finish (small_pass_kernels.hip: small_tail_kernel; knn_candidate_kernels.hip:
+// Device helpers of the single-image pass's exact finish (small_pass_kernels.hip: small_tail_kernel; knn_refine_kernels.hip:
 // refine_exact_small_kernel's fused finish) -- round 6.  Everything here evaluates a distance as the sequential chain
 // acc = fma(q[j], r[j], acc), j = 0 .. d-1, then sv_d2 with the same norms, and orders by (distance, id): the bits of every exact path.
+// Also the word layout of the buffers the pass keeps between launches (below), for the kernels and launchers of both files.
 #pragma once
 #include <math.h>
 #include <stdint.h>
 
 #include "ctx.h"
 #include "knn_dev.h"
+
+// ctx->s_ref_tick, the hand-over of refine_exact_small_kernel: [SV_TICK_ROWS] one ticket counter per query row, then the sticky
+// failure word.  ctx->s_tail_tick: [SV_TICK_ROWS] small_tail_kernel's ticket per query row, the ticket of its last workgroup out,
+// [2] running totals (rows redone by brute force, second-tier rows), one pad word, small_head_kernel's 64-bit arrival counter (8-byte
+// aligned).  ctx->h_pin: the totals' pinned mirror at word SV_PIN_TOTALS (ctx.h: search.hip reads it).  All of it is zero between launches, the totals and the
+// arrival counter apart.
+constexpr int SV_TICK_ROWS = 128, SV_TICK_POISON = SV_TICK_ROWS, SV_TICK_WORDS = SV_TICK_ROWS + 1;
+constexpr int SV_TAIL_LAST = SV_TICK_ROWS, SV_TAIL_TOTALS = SV_TAIL_LAST + 1, SV_TAIL_ARRIVALS = SV_TAIL_TOTALS + 2 + 1;
+constexpr int SV_TAIL_WORDS = SV_TAIL_ARRIVALS + 2;
 
 namespace {
 
@@ -50,6 +60,21 @@ __device__ __forceinline__ void chain_step(const float* __restrict__ rrow, int k
   }
 }
 
+// ONE index row (rrow: its d floats) against query row `row`, the whole chain: the query passes through qs (ST_KC floats of LDS) a
+// chunk at a time, staged by the workgroup -- all 256 threads call it together; have == false: this lane has no row and only stages.
+__device__ __forceinline__ float sp_chain_row(const float* __restrict__ Q, int d, int64_t row, const float* __restrict__ rrow, bool have,
+                                              float* qs, int tid) {
+  float acc[1] = {0.f};
+  for (int c0 = 0; c0 < d; c0 += ST_KC) {
+    const int kc = min(ST_KC, d - c0);
+    __syncthreads();
+    for (int t = tid; t < kc; t += 256) qs[t] = Q[(size_t)row * d + c0 + t];
+    __syncthreads();
+    if (have) chain_step<1>(rrow + c0, kc, qs, acc);
+  }
+  return acc[0];
+}
+
 // best[0..kp) (ascending, padded with all ones) <- the kp smallest of best U {mine of the 256 threads}; a: >= kp + 256 words of
 // scratch, sort length ns = the power of two holding kp + 256.  Skipped (workgroup-uniformly) when nobody brings a key below
 // best[k - 1].
@@ -58,8 +83,8 @@ __device__ __forceinline__ void merge_best(uint64_t* __restrict__ best, int kp, 
   const bool better = mine < best[k - 1];
   if (!__syncthreads_or(better ? 1 : 0)) return;
   for (int j = tid; j < kp; j += 256) a[j] = best[j];
-  a[kp + tid] = better ? mine : ~0ull;
-  for (int j = kp + 256 + tid; j < ns; j += 256) a[j] = ~0ull;
+  a[kp + tid] = better ? mine : SV_WORD_NONE;
+  for (int j = kp + 256 + tid; j < ns; j += 256) a[j] = SV_WORD_NONE;
   sv_bitonic(a, ns, tid);
   for (int j = tid; j < kp; j += 256) best[j] = a[j];
   __syncthreads();
@@ -95,7 +120,7 @@ __device__ __forceinline__ void sp_brute_slice(const float* __restrict__ Q, cons
                                                int tid) {
   int ns = 512;
   while (ns < kp + 256) ns <<= 1;
-  for (int j = tid; j < kp; j += 256) best[j] = ~0ull;
+  for (int j = tid; j < kp; j += 256) best[j] = SV_WORD_NONE;
   __syncthreads();
   const int64_t per = (n + P - 1) / P;
   const int64_t r_lo = (int64_t)p * per, r_hi = min(n, r_lo + per);
@@ -104,15 +129,8 @@ __device__ __forceinline__ void sp_brute_slice(const float* __restrict__ Q, cons
     const int64_t r = base + tid;
     const bool live = r < r_hi;
     const int64_t rr = live ? r : r_lo;
-    float acc[1] = {0.f};
-    for (int c0 = 0; c0 < d; c0 += ST_KC) {
-      const int kc = min(ST_KC, d - c0);
-      __syncthreads();
-      for (int t = tid; t < kc; t += 256) qs[t] = Q[(size_t)row * d + c0 + t];
-      __syncthreads();
-      chain_step<1>(R + (size_t)rr * d + c0, kc, qs, acc);
-    }
-    const uint64_t key = live ? (((uint64_t)f2key_(sv_d2(q2, rn[rr], acc[0])) << 32) | (uint32_t)r) : ~0ull;
+    const float acc = sp_chain_row(Q, d, row, R + (size_t)rr * d, live, qs, tid);
+    const uint64_t key = live ? sv_word(sv_d2(q2, rn[rr], acc), (uint32_t)r) : SV_WORD_NONE;
     merge_best(best, kp, k, key, a, ns, tid);
   }
   uint64_t* mine = slot + (size_t)p * kp;
@@ -124,12 +142,12 @@ __device__ __forceinline__ void sp_brute_merge(const uint64_t* __restrict__ slot
                                                uint64_t* best, int tid) {
   int ns = 512;
   while (ns < kp + 256) ns <<= 1;
-  for (int j = tid; j < kp; j += 256) best[j] = ~0ull;
+  for (int j = tid; j < kp; j += 256) best[j] = SV_WORD_NONE;
   __syncthreads();
   const uint64_t* all = slot;
   for (int64_t j0 = 0; j0 < (int64_t)P * kp; j0 += 256) {
     const int64_t j = j0 + tid;
-    merge_best(best, kp, k, j < (int64_t)P * kp ? __hip_atomic_load(&all[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : ~0ull, a, ns, tid);
+    merge_best(best, kp, k, j < (int64_t)P * kp ? __hip_atomic_load(&all[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : SV_WORD_NONE, a, ns, tid);
   }
 }
 
@@ -146,15 +164,8 @@ __device__ __forceinline__ void sp_tier2_slice(const float* __restrict__ Q, cons
     const int j = j0 + tid;
     const bool in = j < j_hi && (uint32_t)j < c && cand_d2[(size_t)row * cap + j] <= lim;
     const uint32_t id = in ? cand_id[(size_t)row * cap + j] : 0u;
-    float acc[1] = {0.f};
-    for (int c0 = 0; c0 < d; c0 += ST_KC) {
-      const int kc = min(ST_KC, d - c0);
-      __syncthreads();
-      for (int t = tid; t < kc; t += 256) qs[t] = Q[(size_t)row * d + c0 + t];
-      __syncthreads();
-      if (in) chain_step<1>(R + (size_t)id * d + c0, kc, qs, acc);
-    }
-    if (j < j_hi) keys_row[j] = in ? ((((uint64_t)f2key_(sv_d2(q2, rn[id], acc[0]))) << 32) | id) : ~0ull;
+    const float acc = sp_chain_row(Q, d, row, R + (size_t)id * d, in, qs, tid);
+    if (j < j_hi) keys_row[j] = in ? sv_word(sv_d2(q2, rn[id], acc), id) : SV_WORD_NONE;
   }
 }
 

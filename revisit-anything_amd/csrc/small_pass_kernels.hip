@@ -65,7 +65,7 @@ __global__ __launch_bounds__(256) void small_tail_kernel(const float* __restrict
   uint64_t* best = a + ST_CAP;                                              // [ST_QB][kp] (phase 2)   | the band's ids (phase 1)
   uint32_t* band = reinterpret_cast<uint32_t*>(best);                       // [ST_CAP]
   float* qs = reinterpret_cast<float*>(best + (size_t)ST_QB * 1024);        // [ST_QB][ST_KC]
-  __shared__ int s_list[128];
+  __shared__ int s_list[SV_TICK_ROWS];
   __shared__ int s_nlist, s_last;
   __shared__ uint32_t s_cnt;
   const int tid = threadIdx.x, G = gridDim.x;
@@ -73,7 +73,7 @@ __global__ __launch_bounds__(256) void small_tail_kernel(const float* __restrict
   // ---- phase 0: a failed hand-over of refine_exact_small_kernel (its rows are flagged: phase 2 redoes them) ---------------------
   if (tick && __hip_atomic_load(&tick[tick_poison], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) {
     for (int64_t j = (int64_t)blockIdx.x * 256 + tid; j < gkeys_words; j += (int64_t)G * 256)
-      __hip_atomic_store(&gkeys[j], ~0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_store(&gkeys[j], SV_WORD_NONE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     // (the sticky word itself is cleared by the LAST workgroup to leave the kernel -- below -- so that every workgroup sees it)
   }
 
@@ -90,29 +90,17 @@ __global__ __launch_bounds__(256) void small_tail_kernel(const float* __restrict
       __syncthreads();
       const int nb = (int)s_cnt;
       if (nb == 0) continue;   // (cannot happen for a row that outgrew the first tier; workgroup-uniform)
-      int np2 = 2;
-      while (np2 < nb) np2 <<= 1;
-      for (int j = tid; j < np2; j += 256) a[j] = ~0ull;
+      const int np2 = sv_np2(nb);
+      for (int j = tid; j < np2; j += 256) a[j] = SV_WORD_NONE;
       const float q2 = qn[row];
       for (int j0 = 0; j0 < nb; j0 += 256) {
         const int j = j0 + tid;
         const uint32_t id = j < nb ? band[j] : band[0];
-        float acc[1] = {0.f};
-        for (int c0 = 0; c0 < d; c0 += ST_KC) {
-          const int kc = min(ST_KC, d - c0);
-          __syncthreads();
-          for (int t = tid; t < kc; t += 256) qs[t] = Q[(size_t)row * d + c0 + t];
-          __syncthreads();
-          chain_step<1>(R + (size_t)id * d + c0, kc, qs, acc);
-        }
-        if (j < nb) a[j] = ((uint64_t)f2key_(sv_d2(q2, rn[id], acc[0])) << 32) | id;
+        const float acc = sp_chain_row(Q, d, row, R + (size_t)id * d, j < nb, qs, tid);
+        if (j < nb) a[j] = sv_word(sv_d2(q2, rn[id], acc), id);
       }
       sv_bitonic(a, np2, tid);
-      for (int j = tid; j < k; j += 256) {
-        const bool in = j < nb;
-        d2_out[(size_t)row * k + j] = in ? key2f_((uint32_t)(a[j] >> 32)) : INFINITY;
-        idx_out[(size_t)row * k + j] = in ? (int64_t)(uint32_t)a[j] : -1;
-      }
+      sv_write_topk<false>(a, nb, k, d2_out, idx_out, row, tid);
       __syncthreads();
     }
   }
@@ -121,7 +109,7 @@ __global__ __launch_bounds__(256) void small_tail_kernel(const float* __restrict
   if (n_fail) {
     if (tid == 0) s_nlist = 0;
     __syncthreads();
-    if (tid < m && tid < 128 && fail_rows[tid]) s_list[atomicAdd(&s_nlist, 1)] = tid;
+    if (tid < m && tid < SV_TICK_ROWS && fail_rows[tid]) s_list[atomicAdd(&s_nlist, 1)] = tid;
     __syncthreads();
     const int nl = s_nlist;
     // (the order of s_list differs between workgroups; every row is handled on its own slot, so it does not matter -- sorted
@@ -141,7 +129,7 @@ __global__ __launch_bounds__(256) void small_tail_kernel(const float* __restrict
     while (ns < kp + 256) ns <<= 1;
     for (int l0 = 0; l0 < nl; l0 += ST_QB) {
       const int nbq = min(ST_QB, nl - l0);
-      for (int j = tid; j < ST_QB * kp; j += 256) best[j] = ~0ull;
+      for (int j = tid; j < ST_QB * kp; j += 256) best[j] = SV_WORD_NONE;
       __syncthreads();
       for (int64_t base = r_lo; base < r_hi; base += 256) {
         const int64_t r = base + tid;
@@ -160,7 +148,7 @@ __global__ __launch_bounds__(256) void small_tail_kernel(const float* __restrict
         }
         const float r2 = rn[rr];
         for (int b = 0; b < nbq; ++b) {
-          const uint64_t key = live ? (((uint64_t)f2key_(sv_d2(qn[s_list[l0 + b]], r2, acc[b])) << 32) | (uint32_t)r) : ~0ull;
+          const uint64_t key = live ? sv_word(sv_d2(qn[s_list[l0 + b]], r2, acc[b]), (uint32_t)r) : SV_WORD_NONE;
           merge_best(best + (size_t)b * kp, kp, k, key, a, ns, tid);
         }
       }
@@ -176,16 +164,8 @@ __global__ __launch_bounds__(256) void small_tail_kernel(const float* __restrict
         if (!s_last) continue;
         __threadfence();
         uint64_t* bb = best + (size_t)b * kp;
-        for (int j = tid; j < kp; j += 256) bb[j] = ~0ull;
-        __syncthreads();
-        const uint64_t* all = part + (size_t)row * G * kp;
-        for (int64_t j0 = 0; j0 < (int64_t)G * kp; j0 += 256)
-          merge_best(bb, kp, k, __hip_atomic_load(&all[j0 + tid], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), a, ns, tid);
-        for (int j = tid; j < k; j += 256) {
-          const uint64_t v = bb[j];
-          d2_out[(size_t)row * k + j] = v != ~0ull ? key2f_((uint32_t)(v >> 32)) : INFINITY;
-          idx_out[(size_t)row * k + j] = v != ~0ull ? (int64_t)(uint32_t)v : -1;
-        }
+        sp_brute_merge(part + (size_t)row * G * kp, k, kp, G, a, bb, tid);
+        sv_write_topk<true>(bb, kp, k, d2_out, idx_out, row, tid);
         if (tid == 0) tickets[row] = 0u;   // all zero again for the next pass
         __syncthreads();
       }
@@ -196,8 +176,8 @@ __global__ __launch_bounds__(256) void small_tail_kernel(const float* __restrict
   __syncthreads();
   if (tid == 0) {
     __threadfence();
-    if (atomicAdd(&tickets[128], 1u) == (uint32_t)(G - 1)) {
-      tickets[128] = 0u;
+    if (atomicAdd(&tickets[SV_TAIL_LAST], 1u) == (uint32_t)(G - 1)) {
+      tickets[SV_TAIL_LAST] = 0u;
       stats[0] = n_fail;
       stats[1] = n_rovf;
       if (tick && __hip_atomic_load(&tick[tick_poison], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) {
@@ -260,7 +240,7 @@ __global__ __launch_bounds__(SH_T) void small_head_kernel(const float* __restric
   const bool repair = rtick && __hip_atomic_load(&rtick[rtick_poison], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u;
   if (repair)
     for (int64_t j = (int64_t)w * SH_T + tid; j < gkeys_words; j += (int64_t)NW * SH_T)
-      __hip_atomic_store(&gkeys[j], ~0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_store(&gkeys[j], SV_WORD_NONE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   const int mpad = (m + 15) & ~15, MT = mpad >> 4;
   const int lda = d + 8;                                   // halves per LDS row of the query operand (+16 B: the 16 rows of a fragment read hit 16 bank groups)
   _Float16* As = reinterpret_cast<_Float16*>(smem);        // [mpad][lda]
@@ -615,9 +595,9 @@ bool sv_small_head_ok(int m, int d, int n0, int rank) {
          nw <= 64 * SH_PER && nw >= 4 * rank;
 }
 
-int sv_small_words(segvlad_ctx* ctx) {   // [129] tail tickets, [2] tail totals, 1 pad, [2] the head's 64-bit arrival counter
+int sv_small_words(segvlad_ctx* ctx) {   // (the layout: small_pass_dev.h)
   const size_t tcap = ctx->s_tail_tick.cap;
-  SV_HIP(ctx->s_tail_tick.reserve((size_t)(129 + 2 + 1 + 2) * 4));
+  SV_HIP(ctx->s_tail_tick.reserve((size_t)SV_TAIL_WORDS * 4));
   if (ctx->s_tail_tick.cap != tcap) {
     SV_HIP(hipMemsetAsync(ctx->s_tail_tick.p, 0, ctx->s_tail_tick.cap, ctx->stream));
     ctx->small_head_arrivals = 0;   // (the head's barrier: the host's count of the device counter, zeroed with it)
@@ -648,13 +628,13 @@ int sv_launch_small_head(segvlad_ctx* ctx, const float* X, int m, int d, const u
   SV_HIP(sv_max_dyn_lds(reinterpret_cast<const void*>(kern), lds));
   hipLaunchKernelGGL(kern, dim3(nw), dim3(SH_T), lds, ctx->stream, X, m, d, reinterpret_cast<const _Float16*>(Rh), rn, stride, n0,
                      db_scale, rank, reinterpret_cast<_Float16*>(qplane), scales_dev, qn_out, zero, zero_words, cand_scratch,
-                     reinterpret_cast<unsigned long long*>(ctx->s_tail_tick.as<uint32_t>() + 132), target, thr_out, cand_cnt,
+                     reinterpret_cast<unsigned long long*>(ctx->s_tail_tick.as<uint32_t>() + SV_TAIL_ARRIVALS), target, thr_out, cand_cnt,
 #ifdef SV_HEAD_TIMING
                      1,
 #else
                      0,
 #endif
-                     ctx->s_ref_tick.as<uint32_t>(), 128, ctx->s_ref_keys.as<uint64_t>(), (int64_t)(ctx->s_ref_keys.cap / 8));
+                     ctx->s_ref_tick.as<uint32_t>(), SV_TICK_POISON, ctx->s_ref_keys.as<uint64_t>(), (int64_t)(ctx->s_ref_keys.cap / 8));
   ctx->small_head_ran = true;
   SV_HIP(hipGetLastError());
   ctx->small_head_arrivals = target;
@@ -743,19 +723,19 @@ __global__ void small_tail_debug_kernel(int bits, int m, uint32_t* fail_rows, ui
 int sv_launch_small_tail_debug(segvlad_ctx* ctx, int m, uint32_t* fail_rows, uint32_t* fail_count, uint32_t* rovf_rows, float* ref_lim) {
   if ((ctx->opt.debug_small_tail & 7) == 0) return SEGVLAD_OK;
   hipLaunchKernelGGL(small_tail_debug_kernel, dim3(1), dim3(128), 0, ctx->stream, ctx->opt.debug_small_tail & 7, m, fail_rows, fail_count, rovf_rows,
-                     ref_lim, ctx->s_ref_tick.as<uint32_t>(), 128);
+                     ref_lim, ctx->s_ref_tick.as<uint32_t>(), SV_TICK_POISON);
   SV_HIP(hipGetLastError());
   return SEGVLAD_OK;
 }
 
-// part: [m][G][kp] words, tickets: [129] words (all zero between launches), stats: [4] words of THIS search (zeroed by the pass's
+// part: [m][G][kp] words, tickets: ctx->s_tail_tick (small_pass_dev.h), stats: [4] words of THIS search (zeroed by the pass's
 // first kernel), totals: [2] words accumulated over the context's life, host_totals: their pinned mirror (or null)
 int sv_launch_small_tail(segvlad_ctx* ctx, const float* Q, const float* R, const float* qn, const float* rn, int64_t n, int d, int m, int k,
                          uint32_t* fail_rows, uint32_t* fail_count, uint32_t* rovf_rows, const float* ref_lim, const uint32_t* cand_cnt,
                          const float* cand_d2, const uint32_t* cand_id, int cap, float* d2_out, int64_t* idx_out, uint32_t* stats) {
   if (m <= 0) return SEGVLAD_OK;
   SV_TRY(sv_launch_small_tail_debug(ctx, m, fail_rows, fail_count, rovf_rows, const_cast<float*>(ref_lim)));
-  if (m > 128 || k > 1024 || cap > ST_CAP || (d & 3)) return ctx->fail(SEGVLAD_ERR_LIMIT, "small tail: m=%d k=%d cap=%d d=%d", m, k, cap, d);
+  if (m > SV_TICK_ROWS || k > 1024 || cap > ST_CAP || (d & 3)) return ctx->fail(SEGVLAD_ERR_LIMIT, "small tail: m=%d k=%d cap=%d d=%d", m, k, cap, d);
   const int G = (ctx->opt.debug_small_tail >> 8) > 0 ? (ctx->opt.debug_small_tail >> 8) : 64;   // (development: bits 8.. = grid size A/B)
   int kp = 256;
   while (kp < k) kp <<= 1;
@@ -768,7 +748,7 @@ int sv_launch_small_tail(segvlad_ctx* ctx, const float* Q, const float* R, const
   hipLaunchKernelGGL(small_tail_kernel, dim3(G), dim3(256), lds, ctx->stream, Q, R, qn, rn, n, d, m, k, fail_rows, fail_count, rovf_rows,
                      ref_lim, cand_cnt, cand_d2, cand_id, cap, d2_out, idx_out, ctx->s_tail_part.as<uint64_t>(), tickets, kp,
                      ctx->s_ref_keys.as<uint64_t>(), (int64_t)(ctx->s_ref_keys.cap / 8), ctx->s_ref_tick.as<uint32_t>(),
-                     ctx->s_ref_tick.p ? 129 : 0, 128, stats, tickets + 129, ctx->h_pin + 8);
+                     ctx->s_ref_tick.p ? SV_TICK_WORDS : 0, SV_TICK_POISON, stats, tickets + SV_TAIL_TOTALS, ctx->h_pin + SV_PIN_TOTALS);
   SV_HIP(hipGetLastError());
   return SEGVLAD_OK;
 }

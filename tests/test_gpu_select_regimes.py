@@ -1,4 +1,4 @@
-"""Every instantiation of the candidate-list selects at its boundary (csrc/select_dev.h, csrc/knn_candidate_kernels.hip): the wave
+"""Every instantiation of the candidate-list selects at its boundary (csrc/select_dev.h, csrc/knn_select_kernels.hip): the wave
 select's 4 / 16 / 32 / 64 keys per lane (lists of <= 256 / 1024 / 2048 / 4096 entries), the workgroup forms beyond it
 (select_approx_kernel for batches, select_wg_kernel's 16 / 32 keys per thread for a single image) and the overflow of the lists'
 capacity (8192).  One clump of near-copies of a vector, with a dozen queries next to it, sets the longest list: every case asserts
